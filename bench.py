@@ -116,6 +116,9 @@ def make_clip(B, H, W, device, rank=0):
     key = key.to(device)
     ys, xs = torch.meshgrid(torch.arange(H, device=device, dtype=torch.float32),
                             torch.arange(W, device=device, dtype=torch.float32), indexing="ij")
+    # the sensor noise has a seeded generator of its own: torch's default one can start from a different seed in every process,
+    # and the inputs must be the same from run to run
+    gn = torch.Generator(device=device).manual_seed(5678 + rank)
     frames = []
     for t in range(B):
         ph = 0.37 * (t + 1 + 64 * rank)
@@ -125,7 +128,7 @@ def make_clip(B, H, W, device, rank=0):
         gy = 2 * (ys + fy) / (H - 1) - 1
         fr = torch.nn.functional.grid_sample(key, torch.stack([gx, gy], -1)[None], mode="bilinear", padding_mode="border",
                                              align_corners=True)
-        fr = fr * 255 + 2.0 * torch.randn(fr.shape, device=device)
+        fr = fr * 255 + 2.0 * torch.randn(fr.shape, device=device, generator=gn)
         frames.append(fr.clamp(0, 255).round().to(torch.uint8)[0].permute(1, 2, 0))
     frames = torch.stack(frames).contiguous()
     key_u8 = (key[0] * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous()
@@ -273,7 +276,7 @@ def flush_c_stdio():
 def self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start N ranks ourselves (one process per GPU
     under torch.distributed.run, RCCL rendezvous on 127.0.0.1) instead of measuring one GPU under a label that says N."""
-    have = torch.cuda.device_count()
+    have = 0 if args.stub_step else torch.cuda.device_count()
     if have < args.gpus and not args.stub_step:
         print(f"bench.py: --gpus {args.gpus} asked for but only {have} HIP device(s) are visible; refusing to measure "
               f"fewer GPUs than requested", file=sys.stderr)
@@ -285,7 +288,9 @@ def self_launch(args):
     sock.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    # a child process, not os.exec*: counting the devices has started the GPU runtime in this one
+    import subprocess
+    sys.exit(subprocess.run(cmd).returncode)
 
 
 def make_step(eng, frames, key, key_ai, conf, warp_mode="bilinear", separate_warp=False):
@@ -391,6 +396,39 @@ def workspace_end_to_end(args, dist, dev, rank, world):
             shutil.rmtree(root[0], ignore_errors=True)
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(outdir, last, seed=0):
+    """What the last timed step returned -- flow f32 [B,H,W,2], warped u8 [B,H,W,3], mask u8 [B,H,W] -- as float32 .npy files in
+    `outdir`.  All B frames when they fit in DUMP_LIMIT_BYTES; otherwise a seeded choice of whole frames (`frame_index.npy`) and, for
+    every frame of the batch, the same seeded pixel positions (`*_pixels.npy`, positions in `pixel_yx.npy`)."""
+    import numpy as np
+    flow, warped, mask = last
+    B, Hh, Ww = mask.shape
+    per_frame = 4 * Hh * Ww * (flow.shape[-1] + warped.shape[-1] + 1)
+    g = torch.Generator().manual_seed(seed)
+    if B * per_frame <= DUMP_LIMIT_BYTES:
+        frames = torch.arange(B)
+        pix = None
+    else:
+        n_pix = min(Hh * Ww, 4096)
+        budget = DUMP_LIMIT_BYTES - B * n_pix * per_frame // (Hh * Ww) - 8 * (n_pix * 2 + B)
+        frames = torch.randperm(B, generator=g)[:max(1, budget // per_frame)].sort().values
+        pix = torch.randperm(Hh * Ww, generator=g)[:n_pix].sort().values
+    os.makedirs(outdir, exist_ok=True)
+    out = {"frame_index": frames.double()}
+    for name, t in (("flow", flow), ("warped", warped), ("mask", mask)):
+        out[name] = t[frames.to(t.device)].float()
+        if pix is not None:
+            out[name + "_pixels"] = t.reshape(B, Hh * Ww, *t.shape[3:])[:, pix.to(t.device)].float()
+    if pix is not None:
+        out["pixel_yx"] = torch.stack([pix // Ww, pix % Ww], -1).double()
+    for name, t in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), t.cpu().numpy())
+    return sorted(out)
+
+
 def stub_step_factory(dev):
     """CPU stand-in for the hot path (hidden --stub-step): lets the world_size-2 gloo test drive every line of the
     rank plumbing (init, key-frame broadcast, barrier, timed loop, MAX all-reduce, one JSON line) without a GPU."""
@@ -431,8 +469,12 @@ def main():
     ap.add_argument("--stub-step", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--workspace", action="store_true", help="also run the rank-parallel END-TO-END mode: every rank runs ClipPipeline.run "
                     "on its share of one shared PNG workspace (secondary keys under `workspace_ranks`; `value` is unchanged)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (flow, warped frame, mask; float32 .npy, <= 64 MB) into DIR")
     ap.add_argument("--ws-segment", type=int, default=64, help="frames per key-frame segment of the --workspace mode (one segment per rank)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(verify=args.verify_npz)))
         return
@@ -522,6 +564,9 @@ def main():
     if prof:
         layers = ops.prof_collect()
         ops.prof_enable(False)
+    dumped = None
+    if args.dump_outputs and rank == 0 and last is not None:
+        dumped = dump_outputs(args.dump_outputs, last)
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -550,6 +595,8 @@ def main():
     }
     if ws_ranks is not None:
         out["workspace_ranks"] = ws_ranks
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if args.stub_step:
         out["data"] = "stub step (rank-plumbing test, no GPU work)"
         if dist is not None:

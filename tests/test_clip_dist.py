@@ -40,7 +40,14 @@ def _free_port():
     return p
 
 
+def _cpu_rank():
+    """The ranks of these tests compute on the CPU.  `dist.barrier()` asks torch for the host's accelerator, and on a GPU host
+    that question starts the GPU runtime in every rank: eight ranks would hold the device at once.  Answer it with the CPU."""
+    torch._C._get_accelerator = lambda: torch.device("cpu")
+
+
 def _worker(rank, world, port, outdir):
+    _cpu_rank()
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -192,6 +199,7 @@ _FLAGS = [True] + [False] * 11 + [True] + [False] * 2 + [True, True] + [False] *
 
 
 def _pipeline_worker(rank, world, port, ws):
+    _cpu_rank()
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -246,6 +254,7 @@ _FLAGS8_B = _flags_of([3, 0, 2])              # 8 frames, 5 to warp on 8 ranks: 
 
 
 def _pipeline8_worker(rank, world, port, ws_a, ws_b):
+    _cpu_rank()
     import datetime
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -375,6 +384,7 @@ def test_bench_workspace_mode_two_ranks_gloo():
 
 
 def _subgroup_worker(rank, world, port, ws):
+    _cpu_rank()
     import datetime
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
