@@ -226,7 +226,14 @@ typedef struct ofx_conv_desc {
                                                     counters and must be ZERO before the first use (the kernel leaves them
                                                     zero); one scratch per stream that may run a convolution concurrently.
                                                     NULL / 0: never split. */
+    const float* wino_w;                         /* optional (3x3 layers): the same weights as ofx_wino_conv_weight makes them.
+                                                    When set, a stride-1 'same' fp32 layer with a plain epilogue over whole 8x16
+                                                    patches runs the fused Winograd F(2x2,3x3) kernel on grids that fill the chip
+                                                    (OFX_CONV_NO_WINOGRAD in the environment: never); tile = OFX_CONV_TILE_WINOGRAD
+                                                    forces it at any grid size and is rejected (OFX_EINVAL) when the layer does not
+                                                    qualify.  NULL: direct kernels only. */
 } ofx_conv_desc;
+#define OFX_CONV_TILE_WINOGRAD 1
 
 int ofx_conv2d(const ofx_conv_desc* d, void* stream);
 /* host-side helper: OIHW fp32 -> packed [Cout][Kpad] with Cin padded to cin_pad (>= Cin, %4==0).
@@ -238,6 +245,11 @@ long ofx_pack_conv_weight(const float* w_oihw, int Cout, int Cin, int KH, int KW
  * lo = bf16(x - hi), both round-to-nearest-even -- bit-identical to what the kernel's on-the-fly split makes.
  * Same size as the input; use with precision = OFX_PREC_BF16X3_W. Returns 0 or OFX_EINVAL. */
 int ofx_split_conv_weight(const float* packed, long n_floats, float* out);
+/* Host-side: OIHW fp32 3x3 weights -> the Winograd F(2x2,3x3) operand of ofx_conv_desc.wino_w: U = G g G^T per channel pair,
+ * computed in float64 and rounded once, stored [16 points][Cout rounded up to 64][Cin] in the kernel's operand order (the
+ * exact index is documented at the definition, conv_wino.hip).  Cin % 16 == 0.  Returns the float count (`out` may be NULL
+ * to query it) or OFX_EINVAL. */
+long ofx_wino_conv_weight(const float* w_oihw, int Cout, int Cin, float* out);
 /* The same for the three-piece arithmetic (OFX_PREC_BF16X6_W): `out` holds 1.5 * n_floats floats -- first the [hi x4 | mid x4] groups
  * (16 bytes per four consecutive k), then the [lo x4] groups (8 bytes per four k); hi + mid + lo = x exactly unless lo underflows.
  * The whole matrix [Cout][Kpad] must be converted in one call (the lo groups are addressed from its end): a convolution that uses it

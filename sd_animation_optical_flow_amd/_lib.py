@@ -42,6 +42,7 @@ class ConvDesc(C.Structure):
         ("padH", C.c_int), ("padW", C.c_int),
         ("act", C.c_int), ("epi", C.c_int), ("tile", C.c_int), ("precision", C.c_int),
         ("splitk_ws", C.c_void_p), ("splitk_ws_bytes", C.c_size_t),
+        ("wino_w", C.c_void_p),
     ]
 
 
@@ -74,6 +75,7 @@ SIGNATURES = {
     "ofx_warp_and_mask": (_i, [_p, _l, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _i, _p]),
     "ofx_conv2d": (_i, [C.POINTER(ConvDesc), _p]),
     "ofx_pack_conv_weight": (_l, [_p, _i, _i, _i, _i, _i, _p]),
+    "ofx_wino_conv_weight": (_l, [_p, _i, _i, _p]),
     "ofx_split_conv_weight": (_i, [_p, _l, _p]),
     "ofx_split_conv_weight3": (_i, [_p, _l, _p]),
     "ofx_gaussian_blur_u8": (_i, [_p, _p, _p, _i, _i, _i, _f, _p]),

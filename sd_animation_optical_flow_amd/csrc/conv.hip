@@ -1385,6 +1385,24 @@ extern "C" int ofx_conv2d_alpha(const ofx_conv_desc* d, float alpha, void* strea
         default: return OFX_EINVAL;
     }
 
+    // ---- fused Winograd F(2x2,3x3) (conv_wino.hip): 4 instead of 9 multiplies per output for the update block's 3x3 layers.  Only
+    // on grids of at least four workgroups per CU (two rounds at its two per CU): smaller grids, the single pair among them, keep the
+    // direct kernels and their small-grid schedules.
+    {
+        static const bool no_wino = getenv("OFX_CONV_NO_WINOGRAD") != nullptr;
+        const bool force = d->tile == OFX_CONV_TILE_WINOGRAD;
+        constexpr long kWinoMinBlocks = 1024;
+        if (force || (d->tile == 0 && !no_wino && d->wino_w)) {
+            const bool fits = nz == 1 && !tl_stats.on && !tl_pool.on && ofx_conv_wino_fits(d);
+            if (force && !fits) return OFX_EINVAL;
+            if (fits && (force || ofx_conv_wino_blocks(d) >= kWinoMinBlocks)) {
+                OfxProfScope prof("igemm_conv", (hipStream_t)stream);   // the convolution family of the per-layer profile
+                prof.flops(ofx_conv_wino_flops(d));
+                return ofx_conv_wino_launch(d, alpha, (hipStream_t)stream);
+            }
+        }
+    }
+
     // ---- tile selection
     int bm, bn;
     if (d->tile) {

@@ -36,6 +36,7 @@ struct ConvW {
     float* wsplit3 = nullptr; // ... and into (hi, mid | lo) for the bf16x6 mode (ofx_split_conv_weight3: 1.5 x the floats)
     float* scale = nullptr;   // [Cout] or null
     float* shift = nullptr;   // [Cout] or null
+    float* wino = nullptr;    // 3x3 update-block layers: the Winograd F(2x2,3x3) operand (ofx_wino_conv_weight), or null
     int cout = 0, cin = 0, cin_pad = 0, kh = 0, kw = 0;
     long kpad = 0;
     std::string name;         // layer label for the per-layer profile (ofx_prof_enable(2))
@@ -234,6 +235,20 @@ int add_conv(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const std
     return 0;
 }
 
+// the Winograd operand U = G g G^T of an already added 3x3 layer (conv.hip takes the fused Winograd kernel with it when the grid
+// fills the chip; the direct packing stays for every other launch)
+int add_wino(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const std::string& name, const std::string& store_as) {
+    const HostTensor* w = find(sd, name + ".weight");
+    ConvW& c = r->convs[store_as];
+    if (!w || w->ndim != 4 || w->shape[0] != c.cout || w->shape[1] != c.cin || c.kh != 3 || c.kw != 3 || c.cin_pad != c.cin) return OFX_EKEY;
+    const long n = ofx_wino_conv_weight(nullptr, c.cout, c.cin, nullptr);
+    if (n < 0) return (int)n;
+    std::vector<float> u((size_t)n);
+    const long st = ofx_wino_conv_weight(w->data, c.cout, c.cin, u.data());
+    if (st < 0) return (int)st;
+    return upload(r, u, &c.wino);
+}
+
 // `as`: name the packed layers are stored under.  "cnetb" = the context encoder's convolutions WITHOUT the folded running
 // statistics, plus gamma / beta of every BatchNorm: the layers of the batch-statistics mode (see ofx_raft_forward).
 int build_encoder(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const std::string& enc, bool bn,
@@ -355,6 +370,7 @@ struct Launcher {
         d.act = act; d.epi = epi;
         d.precision = wsplit3 ? OFX_PREC_BF16X6_W : wsplit ? OFX_PREC_BF16X3_W : precision;
         d.splitk_ws = sk_ws; d.splitk_ws_bytes = sk_bytes;
+        d.wino_w = row_off == 0 && rows == 0 ? c.wino : nullptr;
         if (c0 + c1 != c.cin_pad) { st = OFX_EKEY; return; }
         ofx_prof_set_tag(c.name.c_str());
         stats_rows = 0;
@@ -742,6 +758,7 @@ int ofx_raft_create(const ofx_tensor* tensors, int n, ofx_raft** out) {
     const char* ub = "update_block.";
     if (!st) st = add_conv(r, sd, std::string(ub) + "encoder.convc1", "convc1", CORR_LD, "", 1.f);   // input rows padded to 336 (zero weights)
     if (!st) st = add_conv(r, sd, std::string(ub) + "encoder.convc2", "convc2", 0, "", 1.f);
+    if (!st) st = add_wino(r, sd, std::string(ub) + "encoder.convc2", "convc2");
     std::vector<float> wf1;   // must outlive add_conv below
     if (!st) {
         // convf1 (7x7 on the 2-channel flow, update.py:93) as a 7x1 convolution over the 16-float flow rows the flow head leaves
@@ -766,10 +783,13 @@ int ofx_raft_create(const ofx_tensor* tensors, int n, ofx_raft** out) {
         }
     }
     if (!st) st = add_conv(r, sd, std::string(ub) + "encoder.convf2", "convf2", 0, "", 1.f);
+    if (!st) st = add_wino(r, sd, std::string(ub) + "encoder.convf2", "convf2");
     if (!st) st = add_conv(r, sd, std::string(ub) + "encoder.conv", "conv", 0, "", 1.f);
+    if (!st) st = add_wino(r, sd, std::string(ub) + "encoder.conv", "conv");
     if (!st) st = build_gru(r, sd, "1");
     if (!st) st = build_gru(r, sd, "2");
     if (!st) st = add_conv(r, sd, std::string(ub) + "flow_head.conv1", "fh1", 0, "", 1.f);
+    if (!st) st = add_wino(r, sd, std::string(ub) + "flow_head.conv1", "fh1");
     if (!st) st = add_conv(r, sd, std::string(ub) + "flow_head.conv2", "fh2", 0, "", 1.f);
     if (!st) st = add_conv(r, sd, std::string(ub) + "mask.0", "mask0", 0, "", 1.f);
     if (!st) st = add_conv(r, sd, std::string(ub) + "mask.2", "mask2", 0, "", 0.25f);

@@ -19,6 +19,7 @@ from ._lib import ConvDesc, check
 WARP_MODES = {"bilinear": 0, "bicubic": 1, "cv2_cubic": 2}
 ACTS = {None: 0, "none": 0, "relu": 1, "sigmoid": 2, "tanh": 3}
 EPI_PLAIN, EPI_GRU_ZR, EPI_GRU_Q, EPI_FLOW = 0, 1, 2, 3
+TILE_WINOGRAD = 1      # conv2d_nhwc(tile=): force the fused Winograd F(2x2,3x3) kernel (OFX_CONV_TILE_WINOGRAD)
 
 
 def _stream() -> C.c_void_p:
@@ -237,6 +238,24 @@ def pack_conv_weight(w_oihw: torch.Tensor, cin_pad: Optional[int] = None) -> tor
     return out
 
 
+def wino_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
+    """OIHW fp32 3x3 (CPU) -> the Winograd F(2x2,3x3) operand U = G g G^T (float64, one rounding) as a flat fp32 CPU tensor
+    in the fused kernel's order (ofx_wino_conv_weight); pass it to conv2d_nhwc(..., wino_w=)."""
+    w = w_oihw.detach().to(torch.float32).contiguous().cpu()
+    co, ci, kh, kw = w.shape
+    if (kh, kw) != (3, 3):
+        raise RuntimeError("wino_conv_weight: 3x3 weights only")
+    L = _lib.lib()
+    n = L.ofx_wino_conv_weight(None, co, ci, None)
+    if n < 0:
+        raise _lib.OfxError(int(n), "ofx_wino_conv_weight")
+    out = torch.empty((n,), dtype=torch.float32)
+    st = L.ofx_wino_conv_weight(C.c_void_p(w.data_ptr()), co, ci, C.c_void_p(out.data_ptr()))
+    if st < 0:
+        raise _lib.OfxError(int(st), "ofx_wino_conv_weight")
+    return out
+
+
 def split_conv_weight(w_packed: torch.Tensor) -> torch.Tensor:
     """Packed fp32 weights (CPU) -> the pre-split bf16x3 operand format (same shape, fp32 container); feed it to
     conv2d_nhwc(..., precision="bf16x3_w")."""
@@ -260,12 +279,15 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
                 x2: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
                 nmean: Optional[torch.Tensor] = None, nrstd: Optional[torch.Tensor] = None, tile: int = 0,
                 precision: str = "fp32", splitk_ws: Optional[torch.Tensor] = None, pad: Optional[Tuple[int, int]] = None,
-                out_hw: Optional[Tuple[int, int]] = None, addend: Optional[torch.Tensor] = None) -> torch.Tensor:
+                out_hw: Optional[Tuple[int, int]] = None, addend: Optional[torch.Tensor] = None,
+                wino_w: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_off: int = 0) -> torch.Tensor:
     """Plain-epilogue convolution: x [B,H,W,C0] (+ optional second channel segment x2 [B,H,W,C1]),
     'same' padding (k//2) unless `pad` = (top, left) is given; `out_hw` overrides the output size (taps beyond the
     input read zeros: pad (0, 0) with out_hw = (H/2, W/2) is the VAE's F.pad(x, (0,1,0,1)) + stride-2 convolution).
     `addend` [B,Hout,Wout,cout] is added before the activation (`res` adds after it and applies ReLU).
-    Returns [B,Hout,Wout,cout]."""
+    `wino_w` (wino_conv_weight, on the device) lets a qualifying 3x3 layer run the fused Winograd kernel (tile =
+    TILE_WINOGRAD forces it).  `out` [B,Hout,Wout,C >= out_off + cout]: write channels [out_off, out_off + cout) of it.
+    Returns [B,Hout,Wout,cout], or `out`."""
     x = _chk(x, "x", torch.float32)
     B, H, W, c0 = x.shape
     d = ConvDesc()
@@ -279,8 +301,14 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
     d.shift = 0 if shift is None else _chk(shift, "shift", torch.float32).data_ptr()
     ph, pw = (kh // 2, kw // 2) if pad is None else pad
     Ho, Wo = ((H + 2 * ph - kh) // stride + 1, (W + 2 * pw - kw) // stride + 1) if out_hw is None else out_hw
-    out = torch.empty((B, Ho, Wo, cout), dtype=torch.float32, device=x.device)
-    d.out, d.ldo = out.data_ptr(), cout
+    if out is None:
+        out = torch.empty((B, Ho, Wo, cout), dtype=torch.float32, device=x.device)
+    out = _chk(out, "out", torch.float32)
+    if tuple(out.shape[:3]) != (B, Ho, Wo) or out.shape[3] < out_off + cout or out_off < 0:
+        raise RuntimeError(f"out must be [{B},{Ho},{Wo},>= {out_off + cout}], got {tuple(out.shape)}")
+    d.out, d.ldo = out.data_ptr() + 4 * out_off, out.shape[3]
+    if wino_w is not None:
+        d.wino_w = _chk(wino_w, "wino_w", torch.float32).data_ptr()
     if addend is not None:
         addend = _chk(addend, "addend", torch.float32)
         if tuple(addend.shape) != (B, Ho, Wo, cout):

@@ -53,6 +53,14 @@ if os.environ.get("CONV_BENCH_C1"):      # the motion encoder's 1x1 over the cor
         ("1x1 256->576", 64, 96, 64, 256, 576, 1, 1, 1, 0),
     ]
     TILES = [0, 16128064, 32128128, 32128064]
+if os.environ.get("CONV_BENCH_WINO"):    # the fused Winograd F(2x2,3x3) kernel (tile 1) against the direct kernel on the update block's 3x3 layers
+    SHAPES = [
+        ("3x3 256->192", 64, 64, 96, 256, 192, 3, 3, 1, 0),
+        ("3x3 128->256", 64, 64, 96, 128, 256, 3, 3, 1, 0),
+        ("3x3 256->126", 64, 64, 96, 256, 126, 3, 3, 1, 0),
+        ("3x3 128->64", 64, 64, 96, 128, 64, 3, 3, 1, 0),
+    ]
+    TILES = [0, 1]
 if os.environ.get('CONV_BENCH_TILES'):
     TILES = [int(t) for t in os.environ['CONV_BENCH_TILES'].split(',')]
 if os.environ.get("CONV_BENCH_ONLY"):
@@ -78,6 +86,10 @@ def run(libpath):
             d = _lib.ConvDesc()
             d.in0, d.ld0, d.c0 = x.data_ptr(), ci, ci
             d.w = w.data_ptr(); d.out = out.data_ptr(); d.ldo = co
+            if tile == 1:   # Winograd operand of a 3x3 weight with the same random statistics
+                from sd_animation_optical_flow_amd import ops
+                u = ops.wino_conv_weight(torch.randn((co, ci, 3, 3)) * 0.02).cuda()
+                d.wino_w = u.data_ptr()
             d.B, d.Hin, d.Win, d.Hout, d.Wout, d.Cout = B, H, W, H // st, W // st, co
             d.KH, d.KW, d.stride, d.padH, d.padW = kh, kw, st, kh // 2, kw // 2
             d.act, d.epi, d.tile = 1, 0, tile
@@ -93,7 +105,7 @@ def run(libpath):
                 lib.ofx_conv2d(C.byref(d), s)
             e1.record(); torch.cuda.synchronize()
             ms = e0.elapsed_time(e1) / n
-            fl = 2.0 * B * (H // st) * (W // st) * co * K
+            fl = 2.0 * B * (H // st) * (W // st) * co * K   # direct-convolution FLOPs for every tile (Winograd: "effective" rate)
             print(f"  {name:<24} tile {tile:>9} {ms:8.3f} ms  {fl / ms / 1e9:7.1f} TFLOP/s")
 if __name__ == "__main__":
     libs = sys.argv[1:] or [_lib.LIB_PATH]
