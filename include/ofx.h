@@ -231,7 +231,12 @@ typedef struct ofx_conv_desc {
                                                     patches runs the fused Winograd F(2x2,3x3) kernel on grids that fill the chip
                                                     (OFX_CONV_NO_WINOGRAD in the environment: never); tile = OFX_CONV_TILE_WINOGRAD
                                                     forces it at any grid size and is rejected (OFX_EINVAL) when the layer does not
-                                                    qualify.  NULL: direct kernels only. */
+                                                    qualify.  NULL: direct kernels only.
+                                                    1x5 / 5x1 layers: the operand of ofx_wino15_conv_weight.  A stride-1 fp32
+                                                    layer keeping the map size (pad 0,2 / 2,0) over whole 8x16 patches, with a
+                                                    plain (ReLU / identity, optional addend) or GRU gate epilogue, runs the fused
+                                                    1D Winograd F(4,5) kernel on grids that fill the chip (OFX_CONV_NO_WINOGRAD or
+                                                    OFX_CONV_NO_WINOGRAD15: never); OFX_CONV_TILE_WINOGRAD forces it as above. */
 } ofx_conv_desc;
 #define OFX_CONV_TILE_WINOGRAD 1
 
@@ -250,6 +255,11 @@ int ofx_split_conv_weight(const float* packed, long n_floats, float* out);
  * exact index is documented at the definition, conv_wino.hip).  Cin % 16 == 0.  Returns the float count (`out` may be NULL
  * to query it) or OFX_EINVAL. */
 long ofx_wino_conv_weight(const float* w_oihw, int Cout, int Cin, float* out);
+/* Host-side: OIHW fp32 1x5 or 5x1 weights (KH, KW) -> the 1D Winograd F(4,5) operand of ofx_conv_desc.wino_w: U = G g per
+ * channel pair over the points {0, 1, -1, 2, -2, 1/2, -1/2, inf}, computed in float64 and rounded once, stored [8 points][Cout
+ * rounded up to 128][Cin] in the kernel's operand order (the exact index is documented at the definition, conv_wino15.hip).
+ * Cin % 16 == 0.  Returns the float count (`out` may be NULL to query it) or OFX_EINVAL. */
+long ofx_wino15_conv_weight(const float* w_oihw, int Cout, int Cin, int KH, int KW, float* out);
 /* The same for the three-piece arithmetic (OFX_PREC_BF16X6_W): `out` holds 1.5 * n_floats floats -- first the [hi x4 | mid x4] groups
  * (16 bytes per four consecutive k), then the [lo x4] groups (8 bytes per four k); hi + mid + lo = x exactly unless lo underflows.
  * The whole matrix [Cout][Kpad] must be converted in one call (the lo groups are addressed from its end): a convolution that uses it

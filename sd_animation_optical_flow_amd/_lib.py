@@ -76,6 +76,7 @@ SIGNATURES = {
     "ofx_conv2d": (_i, [C.POINTER(ConvDesc), _p]),
     "ofx_pack_conv_weight": (_l, [_p, _i, _i, _i, _i, _i, _p]),
     "ofx_wino_conv_weight": (_l, [_p, _i, _i, _p]),
+    "ofx_wino15_conv_weight": (_l, [_p, _i, _i, _i, _i, _p]),
     "ofx_split_conv_weight": (_i, [_p, _l, _p]),
     "ofx_split_conv_weight3": (_i, [_p, _l, _p]),
     "ofx_gaussian_blur_u8": (_i, [_p, _p, _p, _i, _i, _i, _f, _p]),

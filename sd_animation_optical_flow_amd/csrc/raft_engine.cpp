@@ -36,7 +36,8 @@ struct ConvW {
     float* wsplit3 = nullptr; // ... and into (hi, mid | lo) for the bf16x6 mode (ofx_split_conv_weight3: 1.5 x the floats)
     float* scale = nullptr;   // [Cout] or null
     float* shift = nullptr;   // [Cout] or null
-    float* wino = nullptr;    // 3x3 update-block layers: the Winograd F(2x2,3x3) operand (ofx_wino_conv_weight), or null
+    float* wino = nullptr;    // 3x3 update-block layers: the Winograd F(2x2,3x3) operand (ofx_wino_conv_weight); the GRU's
+                              // per-iteration 1x5 / 5x1 layers: the F(4,5) operand (ofx_wino15_conv_weight); or null
     int cout = 0, cin = 0, cin_pad = 0, kh = 0, kw = 0;
     long kpad = 0;
     std::string name;         // layer label for the per-layer profile (ofx_prof_enable(2))
@@ -249,6 +250,34 @@ int add_wino(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const std
     return upload(r, u, &c.wino);
 }
 
+// the 1D Winograd F(4,5) operand U = G g of an already added 1x5 / 5x1 layer made of the input channels `sel` of one or more
+// checkpoint convolutions stacked along Cout in the given order (the GRU's z | r): the same rows and channels as its direct packing
+int add_wino15(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const std::vector<std::string>& names,
+               const std::vector<int>& sel, const std::string& store_as) {
+    ConvW& c = r->convs[store_as];
+    const int ci = (int)sel.size();
+    if (c.cin != ci || c.cin_pad != ci || !((c.kh == 1 && c.kw == 5) || (c.kh == 5 && c.kw == 1))) return OFX_EKEY;
+    std::vector<float> g;   // [Cout][ci][5]
+    for (const std::string& name : names) {
+        const HostTensor* w = find(sd, name + ".weight");
+        if (!w || w->ndim != 4 || w->shape[2] != c.kh || w->shape[3] != c.kw) return OFX_EKEY;
+        const int co = (int)w->shape[0], full = (int)w->shape[1];
+        for (int o = 0; o < co; ++o)
+            for (int k = 0; k < ci; ++k) {
+                if (sel[k] < 0 || sel[k] >= full) return OFX_EKEY;
+                const float* src = w->data + ((size_t)o * full + sel[k]) * 5;
+                g.insert(g.end(), src, src + 5);
+            }
+    }
+    if ((long)g.size() != (long)c.cout * ci * 5) return OFX_EKEY;
+    const long n = ofx_wino15_conv_weight(nullptr, c.cout, ci, c.kh, c.kw, nullptr);
+    if (n < 0) return (int)n;
+    std::vector<float> u((size_t)n);
+    const long st = ofx_wino15_conv_weight(g.data(), c.cout, ci, c.kh, c.kw, u.data());
+    if (st < 0) return (int)st;
+    return upload(r, u, &c.wino);
+}
+
 // `as`: name the packed layers are stored under.  "cnetb" = the context encoder's convolutions WITHOUT the folded running
 // statistics, plus gamma / beta of every BatchNorm: the layers of the batch-statistics mode (see ofx_raft_forward).
 int build_encoder(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const std::string& enc, bool bn,
@@ -323,6 +352,11 @@ int build_gru(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const st
         r->convs["gru.zr" + tag + sfx] = c;
         st = add_conv(r, sd, "update_block.gru.convq" + tag, "gru.q" + tag + sfx, 0, "", 1.f, nullptr, nullptr, sel, bias);
         if (st) return st;
+        if (part == 0) {   // the per-iteration parts also get the 1D Winograd operand (the once-per-forward .inp parts stay direct)
+            st = add_wino15(r, sd, {"update_block.gru.convz" + tag, "update_block.gru.convr" + tag}, rec, "gru.zr" + tag);
+            if (!st) st = add_wino15(r, sd, {"update_block.gru.convq" + tag}, rec, "gru.q" + tag);
+            if (st) return st;
+        }
     }
     return 0;
 }

@@ -19,7 +19,7 @@ from ._lib import ConvDesc, check
 WARP_MODES = {"bilinear": 0, "bicubic": 1, "cv2_cubic": 2}
 ACTS = {None: 0, "none": 0, "relu": 1, "sigmoid": 2, "tanh": 3}
 EPI_PLAIN, EPI_GRU_ZR, EPI_GRU_Q, EPI_FLOW = 0, 1, 2, 3
-TILE_WINOGRAD = 1      # conv2d_nhwc(tile=): force the fused Winograd F(2x2,3x3) kernel (OFX_CONV_TILE_WINOGRAD)
+TILE_WINOGRAD = 1      # conv2d_nhwc(tile=): force the fused Winograd kernel, F(2x2,3x3) or F(4,5) (OFX_CONV_TILE_WINOGRAD)
 
 
 def _stream() -> C.c_void_p:
@@ -256,6 +256,22 @@ def wino_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def wino15_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
+    """OIHW fp32 1x5 or 5x1 (CPU) -> the 1D Winograd F(4,5) operand U = G g (float64, one rounding) as a flat fp32 CPU tensor
+    in the fused kernel's order (ofx_wino15_conv_weight); pass it to conv2d_nhwc(..., wino_w=)."""
+    w = w_oihw.detach().to(torch.float32).contiguous().cpu()
+    co, ci, kh, kw = w.shape
+    L = _lib.lib()
+    n = L.ofx_wino15_conv_weight(None, co, ci, kh, kw, None)
+    if n < 0:
+        raise _lib.OfxError(int(n), "ofx_wino15_conv_weight")
+    out = torch.empty((n,), dtype=torch.float32)
+    st = L.ofx_wino15_conv_weight(C.c_void_p(w.data_ptr()), co, ci, kh, kw, C.c_void_p(out.data_ptr()))
+    if st < 0:
+        raise _lib.OfxError(int(st), "ofx_wino15_conv_weight")
+    return out
+
+
 def split_conv_weight(w_packed: torch.Tensor) -> torch.Tensor:
     """Packed fp32 weights (CPU) -> the pre-split bf16x3 operand format (same shape, fp32 container); feed it to
     conv2d_nhwc(..., precision="bf16x3_w")."""
@@ -285,8 +301,9 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
     'same' padding (k//2) unless `pad` = (top, left) is given; `out_hw` overrides the output size (taps beyond the
     input read zeros: pad (0, 0) with out_hw = (H/2, W/2) is the VAE's F.pad(x, (0,1,0,1)) + stride-2 convolution).
     `addend` [B,Hout,Wout,cout] is added before the activation (`res` adds after it and applies ReLU).
-    `wino_w` (wino_conv_weight, on the device) lets a qualifying 3x3 layer run the fused Winograd kernel (tile =
-    TILE_WINOGRAD forces it).  `out` [B,Hout,Wout,C >= out_off + cout]: write channels [out_off, out_off + cout) of it.
+    `wino_w` (wino_conv_weight / wino15_conv_weight, on the device) lets a qualifying 3x3 / 1x5 / 5x1 layer run the fused
+    Winograd kernel (tile = TILE_WINOGRAD forces it).  `out` [B,Hout,Wout,C >= out_off + cout]: write channels
+    [out_off, out_off + cout) of it.
     Returns [B,Hout,Wout,cout], or `out`."""
     x = _chk(x, "x", torch.float32)
     B, H, W, c0 = x.shape

@@ -11,6 +11,10 @@ convolution (two input segments: rh with row stride 128, then hx[:, 128:256]; ep
     q ld136      rh with row stride 136 instead of 128             -> what the power-of-two row stride costs
     zr           as the engine launches it
     zr plain-epi plain store epilogue
+
+GRU_BENCH_WINO=1: instead, the four per-iteration layers (zr / q, 1x5 / 5x1) as the engine launches them, on the direct kernel and
+on the fused 1D Winograd F(4,5) kernel (tile 1, conv_wino15.hip); its rate is also given in executed FLOPs (2.5x fewer).
+GRU_BENCH_B=n: batch size (default 64).
 usage: python tools/gru_bench.py [libofx variant .so]"""
 import ctypes as C, os, sys
 import torch
@@ -18,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sd_animation_optical_flow_amd import _lib
 
 EPI_PLAIN, EPI_ZR, EPI_Q = 0, 1, 2
-B, h, w = 64, 96, 64
+B, h, w = int(os.environ.get("GRU_BENCH_B", "64")), 64, 96
 M = B * h * w
 
 
@@ -40,7 +44,14 @@ def run(libpath):
     wzr = torch.randn((256, Kq), device=dev) * 0.02
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
-    def desc(kh, kw, cout, epi, in0, ld0, c0, in1=None, ld1=0, c1=0, wt=None, addend=None):
+    wino = {}
+    if os.environ.get("GRU_BENCH_WINO"):   # F(4,5) operands of weights with the same statistics
+        from sd_animation_optical_flow_amd import ops
+        for co in (128, 256):
+            for kh, kw in ((1, 5), (5, 1)):
+                wino[(co, kh)] = ops.wino15_conv_weight(torch.randn((co, 256, kh, kw)) * 0.02).to(dev)
+
+    def desc(kh, kw, cout, epi, in0, ld0, c0, in1=None, ld1=0, c1=0, wt=None, addend=None, tile=0):
         d = _lib.ConvDesc()
         d.in0, d.ld0, d.c0 = in0.data_ptr(), ld0, c0
         if in1 is not None:
@@ -55,6 +66,8 @@ def run(libpath):
             d.aux_z, d.aux_rh, d.aux_h, d.ldh = z.data_ptr(), rh_out.data_ptr(), hx.data_ptr(), 384
         if addend is not None:
             d.addend, d.ldadd = addend.data_ptr(), 768
+        if tile:
+            d.tile, d.wino_w = tile, wino[(cout, kh)].data_ptr()
         return d
 
     mot = hx.data_ptr() + 128 * 4
@@ -70,7 +83,15 @@ def run(libpath):
             (f"zr {tag}", desc(kh, kw, 256, EPI_ZR, hx, 384, 256, None, 0, 0, wzr, gadd)),
             (f"zr {tag} plain-epi", desc(kh, kw, 256, EPI_PLAIN, hx, 384, 256, None, 0, 0, wzr)),
         ]
-    print("==", os.path.basename(libpath))
+    if wino:
+        cases = []
+        for kh, kw, tag in ((1, 5, "1x5"), (5, 1, "5x1")):
+            for tile, route in ((0, "direct"), (1, "wino15")):
+                cases += [
+                    (f"zr {tag} {route}", desc(kh, kw, 256, EPI_ZR, hx, 384, 256, None, 0, 0, wzr, gadd, tile)),
+                    (f"q {tag} {route}", desc(kh, kw, 128, EPI_Q, rh128, 128, 128, mot, 384, 128, wq, gadd, tile)),
+                ]
+    print("==", os.path.basename(libpath), f"B = {B}")
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for rep in range(2):
         for name, d in cases:
@@ -86,8 +107,9 @@ def run(libpath):
             torch.cuda.synchronize()
             ms = e0.elapsed_time(e1) / n
             fl = 2.0 * M * d.Cout * Kq
+            ex = f"  executed {fl / 2.5 / ms / 1e9:7.1f} TFLOP/s" if d.tile == 1 else ""
             if rep:
-                print(f"  {name:<24}{ms * 1e3:9.1f} us {fl / ms / 1e9:7.1f} TFLOP/s")
+                print(f"  {name:<24}{ms * 1e3:9.1f} us {fl / ms / 1e9:7.1f} TFLOP/s{ex}")
 
 
 if __name__ == "__main__":
