@@ -257,7 +257,7 @@ int ofx_split_conv_weight(const float* packed, long n_floats, float* out);
 long ofx_wino_conv_weight(const float* w_oihw, int Cout, int Cin, float* out);
 /* Host-side: OIHW fp32 1x5 or 5x1 weights (KH, KW) -> the 1D Winograd F(4,5) operand of ofx_conv_desc.wino_w: U = G g per
  * channel pair over the points {0, 1, -1, 2, -2, 1/2, -1/2, inf}, computed in float64 and rounded once, stored [8 points][Cout
- * rounded up to 128][Cin] in the kernel's operand order (the exact index is documented at the definition, conv_wino15.hip).
+ * rounded up to 128][Cin] in the kernel's operand order (the exact index is documented at the definition, conv_wino.hip).
  * Cin % 16 == 0.  Returns the float count (`out` may be NULL to query it) or OFX_EINVAL. */
 long ofx_wino15_conv_weight(const float* w_oihw, int Cout, int Cin, int KH, int KW, float* out);
 /* The same for the three-piece arithmetic (OFX_PREC_BF16X6_W): `out` holds 1.5 * n_floats floats -- first the [hi x4 | mid x4] groups

@@ -1385,40 +1385,20 @@ extern "C" int ofx_conv2d_alpha(const ofx_conv_desc* d, float alpha, void* strea
         default: return OFX_EINVAL;
     }
 
-    // ---- fused 1D Winograd F(4,5) (conv_wino15.hip): 2 instead of 5 multiplies per output for the SepConvGRU's 1x5 / 5x1 layers,
-    // GRU gate epilogues included.  Only on maps of at least one 8x16 patch per CU (kWino15MinPatches: from six 512x768 pairs on;
-    // in isolation the kernel already beat the direct one at four): smaller grids, the single pair and B <= 5
-    // among them, keep the direct kernels and their small-grid schedules.  Ahead of the 2D route, so that a forced 1x5 / 5x1 layer
-    // is decided here.
-    {
-        static const bool no_wino15 = getenv("OFX_CONV_NO_WINOGRAD") != nullptr || getenv("OFX_CONV_NO_WINOGRAD15") != nullptr;
-        const bool force = d->tile == OFX_CONV_TILE_WINOGRAD;
-        constexpr long kWino15MinPatches = 256;
-        const bool one_d = (d->KH == 1 && d->KW == 5) || (d->KH == 5 && d->KW == 1);
-        if ((force && one_d) || (d->tile == 0 && !no_wino15 && d->wino_w && one_d)) {
-            const bool fits = nz == 1 && !tl_stats.on && !tl_pool.on && ofx_conv_wino15_fits(d);
-            if (force && !fits) return OFX_EINVAL;
-            if (fits && (force || ofx_conv_wino15_patches(d) >= kWino15MinPatches)) {
-                OfxProfScope prof(d->epi == OFX_EPI_GRU_ZR ? "igemm_conv_gru_zr" : d->epi == OFX_EPI_GRU_Q ? "igemm_conv_gru_q" : "igemm_conv",
-                                  (hipStream_t)stream);   // the convolution families of the per-layer profile
-                prof.flops(ofx_conv_wino15_flops(d));
-                return ofx_conv_wino15_launch(d, alpha, (hipStream_t)stream);
-            }
-        }
-    }
-
-    // ---- fused Winograd F(2x2,3x3) (conv_wino.hip): 4 instead of 9 multiplies per output for the update block's 3x3 layers.  Only
-    // on grids of at least four workgroups per CU (two rounds at its two per CU): smaller grids, the single pair among them, keep the
-    // direct kernels and their small-grid schedules.
+    // ---- fused Winograd (conv_wino.hip): F(2x2,3x3) for the update block's 3x3 layers (4 instead of 9 multiplies per output) and
+    // F(4,5) for the SepConvGRU's 1x5 / 5x1 layers (2 instead of 5, GRU gate epilogues included).  Only on grids that fill the chip
+    // (ofx_conv_wino_pays): smaller grids, the single pair among them, keep the direct kernels and their small-grid schedules.
     {
         static const bool no_wino = getenv("OFX_CONV_NO_WINOGRAD") != nullptr;
+        static const bool no_wino15 = no_wino || getenv("OFX_CONV_NO_WINOGRAD15") != nullptr;
         const bool force = d->tile == OFX_CONV_TILE_WINOGRAD;
-        constexpr long kWinoMinBlocks = 1024;
-        if (force || (d->tile == 0 && !no_wino && d->wino_w)) {
+        const bool one_d = (d->KH == 1 && d->KW == 5) || (d->KH == 5 && d->KW == 1);
+        if (force || (d->tile == 0 && !(one_d ? no_wino15 : no_wino) && d->wino_w)) {
             const bool fits = nz == 1 && !tl_stats.on && !tl_pool.on && ofx_conv_wino_fits(d);
             if (force && !fits) return OFX_EINVAL;
-            if (fits && (force || ofx_conv_wino_blocks(d) >= kWinoMinBlocks)) {
-                OfxProfScope prof("igemm_conv", (hipStream_t)stream);   // the convolution family of the per-layer profile
+            if (fits && (force || ofx_conv_wino_pays(d))) {
+                OfxProfScope prof(d->epi == OFX_EPI_GRU_ZR ? "igemm_conv_gru_zr" : d->epi == OFX_EPI_GRU_Q ? "igemm_conv_gru_q" : "igemm_conv",
+                                  (hipStream_t)stream);   // the convolution families of the per-layer profile
                 prof.flops(ofx_conv_wino_flops(d));
                 return ofx_conv_wino_launch(d, alpha, (hipStream_t)stream);
             }

@@ -1,24 +1,31 @@
-// Fused Winograd F(2x2, 3x3) convolution on the fp32 matrix cores of gfx950.
+// Fused Winograd convolutions on the fp32 matrix cores of gfx950.
 //
-// For the stride-1 3x3 "same" layers of the update block (convc2, conv, flow_head.conv1, convf2 at 1/8 resolution) the direct
-// halo-patch kernel of conv.hip runs at ~0.9 of the fp32 MFMA peak, so the only way to take real time off them is to execute fewer
-// multiplies.  F(2x2, 3x3) produces a 2x2 output tile from a 4x4 input tile with 16 point-wise products per (input, output)
-// channel pair instead of 36: 4 multiplies per output pixel instead of 9.
+// For the update block's stride-1 3x3 "same" layers (convc2, conv, flow_head.conv1, convf2 at 1/8 resolution) and the SepConvGRU's
+// per-iteration 1x5 / 5x1 layers (gru.zr1 / q1, gru.zr2 / q2, 256 input channels) the direct halo-patch kernel of conv.hip runs at
+// ~0.9 of the fp32 MFMA peak, so the only way to take real time off them is to execute fewer multiplies:
 //
-//   Y = A^T [ (G g G^T) (.) (B^T d B) ] A     (Lavin & Gray, "Fast Algorithms for Convolutional Neural Networks", 2016)
+//   F(2x2, 3x3):  Y = A^T [ (G g G^T) (.) (B^T d B) ] A   2x2 outputs from a 4x4 input tile, 16 point products: 4 multiplies per
+//                                                          output instead of 9
+//   F(4, 5):      y = A^T [ (G g) (.) (B^T d) ]           4 outputs from 8 inputs, points {0, 1, -1, 2, -2, 1/2, -1/2, inf}, 8 point
+//                                                          products: 2 multiplies per output instead of 5
+//   (Lavin & Gray, "Fast Algorithms for Convolutional Neural Networks", 2016; Toom-Cook)
 //
 // Everything between the input and the output stays on chip -- the unfused form (transformed input and output through HBM) costs as
-// much traffic as it saves multiplies ("Winograd"):
-//   * a workgroup owns one 8x16-pixel output patch (32 Winograd tiles of 2x2) and 64 output channels;
-//   * per 16-channel slab the 10x18 input halo is staged in LDS once (buffer descriptors return the zero padding), every thread
-//     applies B^T d B to one (tile, channel pair) -- additions only -- and writes the 16 transformed values to LDS;
-//   * wave w owns the four points (w, 0..3) of the 4x4 transform grid: for each it runs the point-wise GEMM
-//     [32 tiles x 16 channels] x [16 channels x 64 outputs] on v_mfma_f32_32x32x2_f32 into 2 x 16 accumulators;
-//   * the pre-transformed weights U = G g G^T (host, float64, one rounding: ofx_wino_conv_weight) are stored in the MFMA's B-operand
-//     lane order, so every wave loads its own 1 KB fragments straight into registers, one slab ahead, with fully contiguous loads;
-//   * after the last slab, each wave folds its four points along the transform's column (A^T from the right), the partial rows
-//     meet in LDS, and the row fold (A^T from the left) feeds the plain epilogue: scale / shift, ReLU, strided store.
-// Executed multiplies per output: 16 / 4 = 4 per (cin, cout) against 9 for the direct kernel.
+// much traffic as it saves multiplies ("Winograd").  Both kernels share one scaffold:
+//   * a workgroup owns one 8x16-pixel output patch -- 32 tiles of 2x2, 1x4 (1x5 layers, along W) or 4x1 (5x1 layers, along H) --
+//     and 64 (2D) or 128 (1D) output channels;
+//   * per 16-channel slab the input halo is staged in LDS once (buffer descriptors return the zero padding), every thread applies
+//     the input transform to one (tile, channel pair) -- additions and constant scalings -- and writes the transformed values to LDS;
+//   * per transform point the GEMM [32 tiles x 16 channels] x [16 channels x 32 outputs] runs on v_mfma_f32_32x32x2_f32.  2D: wave w
+//     owns the four points (w, 0..3) of the 4x4 grid and 64 outputs; 1D: wave w owns all 8 points and 32 outputs;
+//   * the pre-transformed weights U (host, float64, one rounding: ofx_wino_conv_weight / ofx_wino15_conv_weight) are stored in the
+//     MFMA's B-operand lane order, so every wave loads its own 1 KB fragments straight into registers, one slab ahead, with fully
+//     contiguous loads (64 registers in both kernels);
+//   * output side, 2D: each wave folds its four points along the transform's column (A^T from the right), the partial rows meet in
+//     LDS, and the row fold (A^T from the left) feeds the plain epilogue (scale / shift, ReLU, strided store).  1D: a lane holds the
+//     8 point values of each of its (tile, channel) elements, so A^T runs in registers and the epilogue starts straight from them:
+//     plain (with addend) or the two GRU gate epilogues with the semantics of igemm_kernel (conv.hip): z = sigmoid -> aux_z,
+//     r * h -> aux_rh; h = (1 - z) h + z tanh(.) in place.
 #include "ofx_internal.h"
 
 #include <cmath>
@@ -28,50 +35,50 @@
 namespace {
 
 constexpr int kWBK = 16;                    // channels per slab
-constexpr int kHaloW = 18, kHaloH = 10;     // input halo of an 8x16 output patch
-constexpr int kHaloPix = kHaloW * kHaloH;   // 180
-constexpr int kHaloItems = kHaloPix * (kWBK / 4);   // float4 pieces per slab: 720
-constexpr int kHaloSlots = (kHaloItems + 255) / 256;   // per thread: 3
-// halo pixel stride 24 floats: the transform's float2 reads (four tiles two pixels apart per half-wave) land in disjoint banks
-constexpr int kLDH = 24;
 // transformed tile row stride 20 floats: conflict-free ds_read_b128 A fragments (as the direct kernel's LDK)
 constexpr int kLDV = kWBK + 4;
-constexpr int kLDX = 32;                    // output exchange: [wave][column fold][tile][32 channels]
-constexpr int kHaloF = kHaloPix * kLDH;     // 4320 floats
-constexpr int kVF = 16 * 32 * kLDV;         // 10240 floats
-constexpr int kXF = 4 * 2 * 32 * kLDX;      // 8192 floats (reuses the halo / V space after the last slab)
-constexpr int kSmemF = kHaloF + kVF;        // 58 240 bytes: two workgroups per CU
-static_assert(kXF <= kSmemF, "exchange must fit");
 constexpr int kOOB = 0x7FFFFFF0;
+
+// Input halo of an 8x16 output patch: W x H pixels from (y0 + Y0, x0 + X0), staged at a pixel stride of LDH floats.  The strides
+// put a half-wave's transform reads in disjoint banks: 3x3, 10 x 18 at 24 (float2 reads of four tiles two pixels apart); 1x5, 8 x 20
+// at 20 (four tiles 4 pixels apart, 16 floats each); 5x1, 12 x 16 at 16 (four tiles 1 pixel apart).
+template <int W_, int H_, int LDH, int Y0, int X0> struct Halo {
+    static constexpr int W = W_, H = H_, ldh = LDH, y_org = Y0, x_org = X0;
+    static constexpr int pix = W * H;                       // 180 / 160 / 192
+    static constexpr int items = pix * (kWBK / 4);          // float4 pieces per slab: 720 / 640 / 768
+    static constexpr int slots = (items + 255) / 256;       // per thread: 3
+    static constexpr int floats = pix * ldh;                // 4320 / 3200 / 3072
+};
+using Halo3x3 = Halo<18, 10, 24, -1, -1>;
+template <bool VERT> using Halo15 = Halo<VERT ? 16 : 20, VERT ? 12 : 8, VERT ? 16 : 20, VERT ? -2 : 0, VERT ? 0 : -2>;
 
 struct WinoK {
     const float* in0;
     const float* in1;
-    const float* u;          // ofx_wino_conv_weight layout
+    const float* u;          // ofx_wino_conv_weight / ofx_wino15_conv_weight layout
     const float* scale;
     const float* shift;
+    const float* addend;     // 1D kernel only, as the GRU pointers below
     float* out;
-    int ld0, c0, ld1, cin, ldo;
+    float* aux_z;
+    float* aux_rh;
+    float* aux_h;
+    int ld0, c0, ld1, cin, ldo, ldadd, ldh;
     int H, W, Cout, act;
-    int nblk;                // 64-channel output blocks
+    int nblk;                // output blocks of 64 (2D) or 128 (1D) channels
     int nb32;                // 32-channel blocks of u
     int tpr, tpi, mtiles;    // patches per image row / per image, patches in all
     int bytes0, bytes1, bytesu;
     float alpha;
 };
 
-__device__ __forceinline__ float2 f2sub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 f2add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+// Output block nb of image pb's patch at (y0, x0)
+struct Patch {
+    int nb, pb, y0, x0;
+};
 
-__global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    __shared__ __attribute__((aligned(16))) float smem[kSmemF];
-    float* const Hs = smem;
-    float* const Vs = smem + kHaloF;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the weight offsets below stay scalar too
-
-    // the XCD remap of conv.hip: the output blocks of one patch run back to back on one XCD (shared halo in its L2)
+// the XCD remap of conv.hip: the output blocks of one patch run back to back on one XCD (shared halo in its L2)
+__device__ __forceinline__ Patch wino_patch(const WinoK& p) {
     const int nblk = p.mtiles * p.nblk;
     const int bid = blockIdx.x;
     const int q8 = nblk >> 3, r8 = nblk & 7;
@@ -81,25 +88,38 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
     const int pb = mt / p.tpi;
     const int trem = mt - pb * p.tpi;
     const int py = trem / p.tpr;
-    const int y0 = py * 8, x0 = (trem - py * p.tpr) * 16;
+    return {nb, pb, py * 8, (trem - py * p.tpr) * 16};
+}
 
-    // ---- halo staging: item i = (pixel i / 4, float4 slot i % 4) of the slab, pixels row-major over the 10 x 18 halo
+// The slab pipeline of both kernels.  ALG is the algorithm's policy: its halo geometry ALG::HALO; the wave's share of the products,
+// P transform points from ALG::pt0(wave) on and NT 32-channel blocks of u from ALG::blk0(nb, wave) on; and its input transform,
+// built from (Hs, Vs, tid, wave), whose call transforms the calling thread's (tile, channel pair) from the halo in Hs into Vs
+// ([point][tile][channel] at row stride kLDV).  The wave's point-wise products accumulate into acc.
+template <class ALG>
+__device__ __forceinline__ void wino_slabs(const WinoK& p, const Patch& pt, float* Hs, float* Vs, int tid, int wave,
+                                           f32x16 (&acc)[ALG::P][ALG::NT]) {
+    typedef int v4i __attribute__((ext_vector_type(4)));
+    using HALO = typename ALG::HALO;
+    constexpr int P = ALG::P, NT = ALG::NT;
+    const int lane = tid & 63;
+
+    // ---- halo staging: item i = (pixel i / 4, float4 slot i % 4) of the slab, pixels row-major over the halo
     const float* in1s = p.in1 ? p.in1 : p.in0;
     const int bytes1s = p.in1 ? p.bytes1 : p.bytes0;
-    int hpix[kHaloSlots];
+    int hpix[HALO::slots];
     unsigned hok = 0;
 #pragma unroll
-    for (int k = 0; k < kHaloSlots; ++k) {
+    for (int k = 0; k < HALO::slots; ++k) {
         const int i = tid + 256 * k;
         const int pix = i >> 2;
-        const int hy = pix / kHaloW, hx = pix - hy * kHaloW;
-        const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-        const bool ok = i < kHaloItems && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
-        hpix[k] = ok ? (pb * p.H + gy) * p.W + gx : 0;
+        const int hy = pix / HALO::W, hx = pix - hy * HALO::W;
+        const int gy = pt.y0 + HALO::y_org + hy, gx = pt.x0 + HALO::x_org + hx;
+        const bool ok = i < HALO::items && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
+        hpix[k] = ok ? (pt.pb * p.H + gy) * p.W + gx : 0;
         hok |= (ok ? 1u : 0u) << k;
     }
     const int hq = (tid & 3) * 16;   // byte offset of this thread's float4 slot (256 % 4 == 0: the same for every k)
-    float4 pa[kHaloSlots];
+    float4 pa[HALO::slots];
     auto a_issue = [&](int cb) __attribute__((always_inline)) {
         const int c = cb * kWBK;
         const bool s0 = c < p.c0;    // wave-uniform
@@ -107,92 +127,67 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
         const int so = (s0 ? c : c - p.c0) * 4;
         const int ldb = (s0 ? p.ld0 : p.ld1) * 4;
 #pragma unroll
-        for (int k = 0; k < kHaloSlots; ++k) {
+        for (int k = 0; k < HALO::slots; ++k) {
             const int vo = ((hok >> k) & 1u) ? hpix[k] * ldb + hq : kOOB;
             v4i t = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, 0);
             pa[k] = *reinterpret_cast<float4*>(&t);
         }
     };
 
-    // ---- weights: wave w, point (w, q), 32-channel block 2 nb + nt, 8-channel chunk 2 cb + ks -> one contiguous 1 KB fragment
+    // ---- weights: point pt0 + q, 32-channel block blk0 + nt, 8-channel chunk 2 cb + ks -> one contiguous 1 KB fragment
     const __amdgpu_buffer_rsrc_t rsu = __builtin_amdgcn_make_buffer_rsrc((void*)p.u, (short)0, p.bytesu, 0x00020000);
     const int c8n = p.cin >> 3;
     const int wlane = lane * 16;
-    float4 wr[4][2][2];
+    const int pt0 = ALG::pt0(wave), blk0 = ALG::blk0(pt.nb, wave);
+    float4 wr[P][NT][2];
     auto w_issue = [&](int q, int cb) __attribute__((always_inline)) {
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
+        for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const int so = (((wave * 4 + q) * p.nb32 + 2 * nb + nt) * c8n + 2 * cb + ks) * 1024;   // scalar
+                const int so = (((pt0 + q) * p.nb32 + blk0 + nt) * c8n + 2 * cb + ks) * 1024;   // scalar
                 v4i t = __builtin_amdgcn_raw_buffer_load_b128(rsu, wlane, so, 0);
                 wr[q][nt][ks] = *reinterpret_cast<float4*>(&t);
             }
     };
 
-    f32x16 acc[4][2];
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
+    for (int q = 0; q < P; ++q)
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
+        for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[q][nt][e] = 0.f;
 
-    // input transform: thread = (tile row = wave, tile column tx, channel pair cp)
-    const int ttx = lane >> 3, tcp = lane & 7;
-    const int ttile = wave * 8 + ttx;
-    const float* const tsrc = Hs + (2 * wave * kHaloW + 2 * ttx) * kLDH + 2 * tcp;
-    float* const tdst = Vs + ttile * kLDV + 2 * tcp;
+    const ALG xf(Hs, Vs, tid, wave);
     // A fragment: tile = lane & 31, channels 8 ks + 4 (lane >> 5) + 0..3 (the k order the weights are stored in)
-    const float* const afrag = Vs + (wave * 4 * 32 + (lane & 31)) * kLDV + 4 * (lane >> 5);
+    const float* const afrag = Vs + (pt0 * 32 + (lane & 31)) * kLDV + 4 * (lane >> 5);
 
     const int CB = p.cin / kWBK;
     a_issue(0);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) w_issue(q, 0);
+    for (int q = 0; q < P; ++q) w_issue(q, 0);
     for (int cb = 0; cb < CB; ++cb) {
         const int nx = cb + 1 < CB ? cb + 1 : cb;   // the last slab re-issues itself: no branch, loads stay in bounds
 #pragma unroll
-        for (int k = 0; k < kHaloSlots; ++k) {
+        for (int k = 0; k < HALO::slots; ++k) {
             const int i = tid + 256 * k;
-            if (kHaloSlots * 256 > kHaloItems && k == kHaloSlots - 1 && i >= kHaloItems) break;
-            *reinterpret_cast<float4*>(&Hs[(i >> 2) * kLDH + (i & 3) * 4]) = pa[k];
+            if (HALO::slots * 256 > HALO::items && k == HALO::slots - 1 && i >= HALO::items) break;
+            *reinterpret_cast<float4*>(&Hs[(i >> 2) * HALO::ldh + (i & 3) * 4]) = pa[k];
         }
         __syncthreads();
-        {
-            float2 d[4][4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) d[r][c] = *reinterpret_cast<const float2*>(tsrc + (r * kHaloW + c) * kLDH);
-            float2 t[4][4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {           // B^T d
-                t[0][c] = f2sub(d[0][c], d[2][c]);
-                t[1][c] = f2add(d[1][c], d[2][c]);
-                t[2][c] = f2sub(d[2][c], d[1][c]);
-                t[3][c] = f2sub(d[1][c], d[3][c]);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {           // (B^T d) B
-                float2 v[4];
-                v[0] = f2sub(t[i][0], t[i][2]);
-                v[1] = f2add(t[i][1], t[i][2]);
-                v[2] = f2sub(t[i][2], t[i][1]);
-                v[3] = f2sub(t[i][1], t[i][3]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) *reinterpret_cast<float2*>(tdst + (i * 4 + j) * 32 * kLDV) = v[j];
-            }
-        }
+        xf();
         __syncthreads();
         a_issue(nx);   // the next slab's halo lands during this slab's products (issued here, not live across the transform)
+        // ... and is issued ahead of them: left free, the scheduler sinks these loads below most of the MFMAs, and the next slab's
+        // LDS store then waits for them (profiles/r09_wino_shared_ab.txt)
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < P; ++q) {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 const float4 a = *reinterpret_cast<const float4*>(afrag + q * 32 * kLDV + 8 * ks);
 #pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
+                for (int nt = 0; nt < NT; ++nt) {
                     const float4 b = wr[q][nt][ks];
                     acc[q][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[q][nt], 0, 0, 0);
                     acc[q][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[q][nt], 0, 0, 0);
@@ -203,6 +198,115 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
             w_issue(q, nx);   // this point's fragments for the next slab: the rest of the slab hides the load
         }
     }
+}
+
+__device__ __forceinline__ float2 f2(float a, float b) { return make_float2(a, b); }
+__device__ __forceinline__ float2 operator+(float2 a, float2 b) { return f2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 operator-(float2 a, float2 b) { return f2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ float2 operator*(float s, float2 a) { return f2(s * a.x, s * a.y); }
+
+// F(2x2, 3x3): wave w = the four points (w, 0..3) of the 4x4 grid x both 32-channel halves of the workgroup's 64 outputs.  Input
+// transform B^T d B of one (tile, channel pair): 4x4 float2 window of the halo at src -> the 16 points at dst; thread = (tile row =
+// wave, tile column tx, channel pair cp).
+struct Wino3x3 {
+    using HALO = Halo3x3;
+    static constexpr int P = 4, NT = 2;
+    __device__ static int pt0(int wave) { return 4 * wave; }
+    __device__ static int blk0(int nb, int) { return 2 * nb; }
+    const float* src;
+    float* dst;
+    __device__ __forceinline__ Wino3x3(const float* Hs, float* Vs, int tid, int wave) {
+        const int ttx = (tid & 63) >> 3, tcp = tid & 7;
+        src = Hs + (2 * wave * HALO::W + 2 * ttx) * HALO::ldh + 2 * tcp;
+        dst = Vs + (wave * 8 + ttx) * kLDV + 2 * tcp;
+    }
+    __device__ __forceinline__ void operator()() const {
+        float2 d[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) d[r][c] = *reinterpret_cast<const float2*>(src + (r * HALO::W + c) * HALO::ldh);
+        float2 t[4][4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {           // B^T d
+            t[0][c] = d[0][c] - d[2][c];
+            t[1][c] = d[1][c] + d[2][c];
+            t[2][c] = d[2][c] - d[1][c];
+            t[3][c] = d[1][c] - d[3][c];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {           // (B^T d) B
+            float2 v[4];
+            v[0] = t[i][0] - t[i][2];
+            v[1] = t[i][1] + t[i][2];
+            v[2] = t[i][2] - t[i][1];
+            v[3] = t[i][1] - t[i][3];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) *reinterpret_cast<float2*>(dst + (i * 4 + j) * 32 * kLDV) = v[j];
+        }
+    }
+};
+
+// F(4, 5): wave w = all 8 points x the w-th 32 of the workgroup's 128 outputs.  Input transform B^T d of one (tile, channel pair):
+// 8 float2 taps at src -> the 8 points at dst; thread = (tile tid / 8, channel pair tid % 8).  VERT = false (1x5): tile t = (row
+// t / 4, column group t % 4) reads halo pixels row * 20 + 4 (t % 4) + 0..7.  VERT = true (5x1): tile t = (row group t / 16, column
+// t % 16) reads pixels (4 (t / 16) + 0..7) * 16 + t % 16.
+template <bool VERT> struct Wino15 {
+    using HALO = Halo15<VERT>;
+    static constexpr int P = 8, NT = 1;
+    __device__ static int pt0(int) { return 0; }
+    __device__ static int blk0(int nb, int wave) { return 4 * nb + wave; }
+    static constexpr int tap = (VERT ? HALO::W : 1) * HALO::ldh;   // floats between taps
+    const float* src;
+    float* dst;
+    __device__ static int base(int t) { return VERT ? (4 * (t >> 4)) * HALO::W + (t & 15) : (t >> 2) * HALO::W + 4 * (t & 3); }
+    // output pixel (dy, dx) in the patch of tile t, output i of the tile
+    __device__ static int oy(int t, int i) { return VERT ? 4 * (t >> 4) + i : t >> 2; }
+    __device__ static int ox(int t, int i) { return VERT ? (t & 15) : 4 * (t & 3) + i; }
+    __device__ __forceinline__ Wino15(const float* Hs, float* Vs, int tid, int) {
+        const int ttile = tid >> 3, tcp = tid & 7;
+        src = Hs + base(ttile) * HALO::ldh + 2 * tcp;
+        dst = Vs + ttile * kLDV + 2 * tcp;
+    }
+    __device__ __forceinline__ void operator()() const {
+        float2 d[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d[j] = *reinterpret_cast<const float2*>(src + j * tap);
+        // B^T d (rows 0 and 7 with the 21/4 pair, rows 1..6 as even / odd halves)
+        float2 v[8];
+        v[0] = (d[0] - d[6]) + 5.25f * (d[4] - d[2]);
+        v[7] = (d[7] - d[1]) + 5.25f * (d[3] - d[5]);
+        float2 te = (d[2] + d[6]) - 4.25f * d[4], to = (d[1] + d[5]) - 4.25f * d[3];
+        v[1] = te + to;
+        v[2] = te - to;
+        te = (0.25f * d[2] + d[6]) - 1.25f * d[4];
+        to = (0.5f * d[1] - 2.5f * d[3]) + 2.0f * d[5];
+        v[3] = te + to;
+        v[4] = te - to;
+        te = (4.0f * d[2] + d[6]) - 5.0f * d[4];
+        to = (2.0f * d[1] - 2.5f * d[3]) + 0.5f * d[5];
+        v[5] = te + to;
+        v[6] = te - to;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) *reinterpret_cast<float2*>(dst + j * 32 * kLDV) = v[j];
+    }
+};
+
+// ---- F(2x2, 3x3): 64 output channels per workgroup, wave w = points (w, 0..3) x both 32-channel halves
+constexpr int kLDX = 32;                                    // output exchange: [wave][column fold][tile][32 channels]
+constexpr int kVF2 = 16 * 32 * kLDV;                        // 10240 floats
+constexpr int kSmem2 = Halo3x3::floats + kVF2;              // 58 240 bytes: two workgroups per CU
+static_assert(4 * 2 * 32 * kLDX <= kSmem2, "exchange must fit");   // reuses the halo / V space after the last slab
+
+__global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
+    __shared__ __attribute__((aligned(16))) float smem[kSmem2];
+    float* const Hs = smem;
+    float* const Vs = smem + Halo3x3::floats;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the weight offsets stay scalar too
+    const Patch pt = wino_patch(p);
+    f32x16 acc[4][2];
+    wino_slabs<Wino3x3>(p, pt, Hs, Vs, tid, wave, acc);
 
     // ---- output transform and plain epilogue, one 32-channel half at a time through LDS
     const float act_lo = p.act == OFX_ACT_RELU ? 0.0f : -3.402823466e38f;
@@ -220,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
             X[((wave * 2 + 1) * 32 + tile) * kLDX + (lane & 31)] = m1 - m2 - m3;
         }
         __syncthreads();
-        const int oc = nb * 64 + nt * 32 + on;
+        const int oc = pt.nb * 64 + nt * 32 + on;
         if (oc < p.Cout) {
             const float sc = (p.scale ? p.scale[oc] : 1.0f) * p.alpha;
             const float sh = p.shift ? p.shift[oc] : 0.0f;
@@ -237,7 +341,7 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
                         const float y = a == 0 ? x[0][j] + x[1][j] + x[2][j] : x[1][j] - x[2][j] - x[3][j];
-                        const long pix = ((long)pb * p.H + y0 + 2 * ty + a) * p.W + x0 + 2 * otx + j;
+                        const long pix = ((long)pt.pb * p.H + pt.y0 + 2 * ty + a) * p.W + pt.x0 + 2 * otx + j;
                         p.out[pix * p.ldo + oc] = fmaxf(y * sc + sh, act_lo);
                     }
             }
@@ -245,75 +349,215 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
     }
 }
 
+// ---- F(4, 5): 128 output channels per workgroup, wave w = all 8 points x 32 channels
+template <bool VERT, int EPI>
+__global__ __launch_bounds__(256, 2) void wino15_conv_kernel(const WinoK p) {
+    using T = Wino15<VERT>;
+    using HALO = typename T::HALO;
+    __shared__ __attribute__((aligned(16))) float smem[HALO::floats + 8 * 32 * kLDV];   // halo + [point][tile][channel]: ~33 KB
+    float* const Hs = smem;
+    float* const Vs = smem + HALO::floats;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the weight offsets stay scalar too
+    const Patch pt = wino_patch(p);
+    f32x16 acc[8][1];
+    wino_slabs<T>(p, pt, Hs, Vs, tid, wave, acc);
+
+    // ---- output transform in registers, then the epilogue.  Element e of the C layout: tile (e & 3) + 8 (e >> 2) + 4 (lane >> 5),
+    // output channel lane & 31 of the wave's 32.
+    const int n = pt.nb * 128 + wave * 32 + (lane & 31);
+    if (n >= p.Cout) return;   // no barrier follows
+    const float sc = (p.scale ? p.scale[n] : 1.0f) * p.alpha;
+    const float sh = p.shift ? p.shift[n] : 0.0f;
+    const float act_lo = p.act == OFX_ACT_RELU ? 0.0f : -3.402823466e38f;
+    const int hd = p.Cout >> 1;
+    const bool r_half = EPI == OFX_EPI_GRU_ZR && pt.nb * 128 >= hd;   // block-uniform (fits: hd % 128 == 0)
+    // Four elements (16 outputs) per batch: every global read of the batch is issued before its arithmetic and stores (h is read
+    // and written in place; interleaved, each read would wait behind the previous store).
+#pragma unroll
+    for (int eb = 0; eb < 16; eb += 4) {
+        long pix[4][4];
+        float y[4][4], ad[4][4], x1[4][4], x2[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int e = eb + u;
+            const int tile = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) pix[u][i] = ((long)pt.pb * p.H + pt.y0 + T::oy(tile, i)) * p.W + pt.x0 + T::ox(tile, i);
+            const float m0 = acc[0][0][e], m1 = acc[1][0][e], m2 = acc[2][0][e], m3 = acc[3][0][e];
+            const float m4 = acc[4][0][e], m5 = acc[5][0][e], m6 = acc[6][0][e], m7 = acc[7][0][e];
+            const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4, s56 = m5 + m6, d56 = m5 - m6;
+            y[u][0] = m0 + s12 + s34 + s56;                          // A^T
+            y[u][1] = d12 + 2.0f * d34 + 0.5f * d56;
+            y[u][2] = s12 + 4.0f * s34 + 0.25f * s56;
+            y[u][3] = d12 + 8.0f * d34 + 0.125f * d56 + m7;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                ad[u][i] = p.addend ? p.addend[pix[u][i] * p.ldadd + n] : 0.0f;
+                x1[u][i] = EPI == OFX_EPI_GRU_ZR ? (r_half ? p.aux_h[pix[u][i] * p.ldh + n - hd] : 1.0f)
+                           : EPI == OFX_EPI_GRU_Q ? p.aux_z[pix[u][i] * p.Cout + n] : 0.0f;
+                x2[u][i] = EPI == OFX_EPI_GRU_Q ? p.aux_h[pix[u][i] * p.ldh + n] : 0.0f;
+            }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float v = y[u][i] * sc + sh + ad[u][i];
+                if (EPI == OFX_EPI_PLAIN) {
+                    p.out[pix[u][i] * p.ldo + n] = fmaxf(v, act_lo);
+                } else if (EPI == OFX_EPI_GRU_ZR) {
+                    const float g = ofx_sigmoid(v) * x1[u][i];            // z, or r * h
+                    if (r_half) p.aux_rh[pix[u][i] * hd + n - hd] = g;
+                    else p.aux_z[pix[u][i] * hd + n] = g;
+                } else {
+                    p.aux_h[pix[u][i] * p.ldh + n] = (1.0f - x1[u][i]) * x2[u][i] + x1[u][i] * ofx_tanh(v);
+                }
+            }
+    }
+}
+
+template <bool VERT>
+int launch15(const WinoK& k, int epi, dim3 grid, dim3 block, hipStream_t s) {
+    switch (epi) {
+        case OFX_EPI_PLAIN: OFX_LAUNCH((wino15_conv_kernel<VERT, OFX_EPI_PLAIN>), grid, block, s, k); break;
+        case OFX_EPI_GRU_ZR: OFX_LAUNCH((wino15_conv_kernel<VERT, OFX_EPI_GRU_ZR>), grid, block, s, k); break;
+        case OFX_EPI_GRU_Q: OFX_LAUNCH((wino15_conv_kernel<VERT, OFX_EPI_GRU_Q>), grid, block, s, k); break;
+        default: return OFX_EINVAL;
+    }
+    return ofx_launch_status();
+}
+
+bool is_3x3(const ofx_conv_desc* d) { return d->KH == 3 && d->KW == 3; }
+bool is_1d(int KH, int KW) { return (KH == 1 && KW == 5) || (KH == 5 && KW == 1); }
+int wino_points(const ofx_conv_desc* d) { return is_3x3(d) ? 16 : 8; }
+int wino_cblk(const ofx_conv_desc* d) { return is_3x3(d) ? 64 : 128; }   // output channels per workgroup
+
 }  // namespace
 
-// Shape test for the fused kernel: fp32, one problem, 3x3 stride 1 'same', a map of whole 8x16 patches, 16-channel slabs that never
-// straddle the two input segments, the plain epilogue without fused norm, residual or addend, ReLU or identity.
+// Shape test: fp32, one problem, stride 1, 3x3 (pad 1, 1), 1x5 (pad 0, 2) or 5x1 (pad 2, 0) keeping the map size, a map of whole
+// 8x16 patches, 16-channel slabs that never straddle the two input segments, no fused norm or residual.  Epilogues: 3x3, plain
+// without addend; 1x5 / 5x1, plain (optional addend) or a GRU gate epilogue whose z | r split falls on a 128-channel block boundary.
+// Plain: ReLU or identity.
 bool ofx_conv_wino_fits(const ofx_conv_desc* d) {
     const int cin = d->c0 + d->c1;
-    return d->precision == OFX_PREC_FP32 && (d->nz <= 1) && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->padH == 1 &&
-           d->padW == 1 && d->Hout == d->Hin && d->Wout == d->Win && d->Hin % 8 == 0 && d->Win % 16 == 0 && cin % kWBK == 0 &&
-           d->c0 % kWBK == 0 && d->epi == OFX_EPI_PLAIN && !d->nmean && !d->res && !d->addend && d->out != nullptr &&
-           d->ldo >= d->Cout && (d->act == OFX_ACT_NONE || d->act == OFX_ACT_RELU) && d->wino_w != nullptr && ofx_aligned16(d->wino_w);
+    const bool plain = d->epi == OFX_EPI_PLAIN && d->out != nullptr && d->ldo >= d->Cout && (d->act == OFX_ACT_NONE || d->act == OFX_ACT_RELU);
+    bool shape_epi = false;
+    if (is_3x3(d)) {
+        shape_epi = d->padH == 1 && d->padW == 1 && plain && !d->addend;
+    } else if (is_1d(d->KH, d->KW)) {
+        shape_epi = d->padH == d->KH / 2 && d->padW == d->KW / 2 &&
+                    (plain || (d->epi == OFX_EPI_GRU_ZR && (d->Cout / 2) % 128 == 0) || d->epi == OFX_EPI_GRU_Q);
+    }
+    return shape_epi && d->precision == OFX_PREC_FP32 && (d->nz <= 1) && d->stride == 1 && d->Hout == d->Hin && d->Wout == d->Win &&
+           d->Hin % 8 == 0 && d->Win % 16 == 0 && cin % kWBK == 0 && d->c0 % kWBK == 0 && !d->nmean && !d->res &&
+           d->wino_w != nullptr && ofx_aligned16(d->wino_w);
 }
 
-long ofx_conv_wino_blocks(const ofx_conv_desc* d) {
-    return (long)d->B * (d->Hin / 8) * (d->Win / 16) * ((d->Cout + 63) / 64);
+// Whether the grid fills the chip enough for the fused kernel to beat the direct kernels and their small-grid schedules: 3x3, at
+// least four workgroups per CU (two rounds at its two per CU); 1x5 / 5x1, at least one 8x16 patch per CU (from six 512x768 pairs on;
+// in isolation the kernel already beat the direct one at four).
+bool ofx_conv_wino_pays(const ofx_conv_desc* d) {
+    const long patches = (long)d->B * (d->Hin / 8) * (d->Win / 16);
+    return is_3x3(d) ? patches * ((d->Cout + 63) / 64) >= 1024 : patches >= 256;
 }
 
-// Multiplies the fused kernel executes for `d` (x 2 FLOPs): 16 point products per 2x2 tile, input channel and output channel
+// Multiplies the fused kernel executes for `d` (x 2 FLOPs): 16 (3x3) or 8 (1D) point products per 4-output tile, input channel and
+// output channel
 double ofx_conv_wino_flops(const ofx_conv_desc* d) {
-    return 2.0 * 16.0 * ((double)d->B * d->Hout * d->Wout / 4.0) * (double)(d->c0 + d->c1) * d->Cout;
+    return 2.0 * wino_points(d) * ((double)d->B * d->Hout * d->Wout / 4.0) * (double)(d->c0 + d->c1) * d->Cout;
 }
 
 // The caller has validated the descriptor (ofx_conv2d_alpha) and ofx_conv_wino_fits(d).
 int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, hipStream_t s) {
     WinoK k;
-    k.in0 = d->in0; k.in1 = d->in1; k.u = d->wino_w; k.scale = d->scale; k.shift = d->shift; k.out = d->out;
-    k.ld0 = d->ld0; k.c0 = d->c0; k.ld1 = d->ld1; k.cin = d->c0 + d->c1; k.ldo = d->ldo;
+    k.in0 = d->in0; k.in1 = d->in1; k.u = d->wino_w; k.scale = d->scale; k.shift = d->shift; k.addend = d->addend; k.out = d->out;
+    k.aux_z = d->aux_z; k.aux_rh = d->aux_rh; k.aux_h = d->aux_h;
+    k.ld0 = d->ld0; k.c0 = d->c0; k.ld1 = d->ld1; k.cin = d->c0 + d->c1; k.ldo = d->ldo; k.ldadd = d->ldadd; k.ldh = d->ldh;
     k.H = d->Hin; k.W = d->Win; k.Cout = d->Cout; k.act = d->act;
-    k.nblk = (d->Cout + 63) / 64;
-    k.nb32 = 2 * k.nblk;
+    const int cblk = wino_cblk(d);
+    k.nblk = (d->Cout + cblk - 1) / cblk;
+    k.nb32 = cblk / 32 * k.nblk;
     k.tpr = d->Win / 16;
     k.tpi = (d->Hin / 8) * k.tpr;
     const long mtiles = (long)d->B * k.tpi;
     const long npix = (long)d->B * d->Hin * d->Win;
     const long ext0 = ((npix - 1) * d->ld0 + d->c0) * 4, ext1 = d->in1 ? ((npix - 1) * d->ld1 + d->c1) * 4 : 0;
-    const long extu = 16L * k.nb32 * 32 * k.cin * 4;
+    const long extu = (long)wino_points(d) * k.nb32 * 32 * k.cin * 4;
     OFX_REQUIRE(ext0 < (1L << 31) - 64 && ext1 < (1L << 31) - 64 && extu < (1L << 31) - 64, OFX_EINVAL);
-    OFX_REQUIRE(mtiles * k.nblk < (1L << 31) && npix * d->ldo < (1L << 31), OFX_EINVAL);
+    OFX_REQUIRE(mtiles * k.nblk < (1L << 31) && (!is_3x3(d) || npix * d->ldo < (1L << 31)), OFX_EINVAL);
     k.mtiles = (int)mtiles;
     k.bytes0 = (int)ext0; k.bytes1 = (int)ext1; k.bytesu = (int)extu;
     k.alpha = alpha;
-    dim3 grid((unsigned)(k.mtiles * k.nblk), 1, 1), block(256, 1, 1);
-    OFX_LAUNCH(wino_conv_kernel, grid, block, s, k);
-    return ofx_launch_status();
+    const dim3 grid((unsigned)(k.mtiles * k.nblk), 1, 1), block(256, 1, 1);
+    if (is_3x3(d)) {
+        OFX_LAUNCH(wino_conv_kernel, grid, block, s, k);
+        return ofx_launch_status();
+    }
+    return d->KH == 5 ? launch15<true>(k, d->epi, grid, block, s) : launch15<false>(k, d->epi, grid, block, s);
 }
 
-// Host: OIHW 3x3 weights -> U = G g G^T per (output, input) channel pair in float64, rounded once to fp32, in the fused kernel's
-// operand order: [16 points][Cout rounded up to 64, as 32-channel blocks][Cin / 8][2][32][4], i.e. point (i, j) = 4 i + j, output
-// channel o = 32 nb + n, input channel c = 8 c8 + 4 h + e at float ((((4 i + j) * NB + nb) * Cin / 8 + c8) * 2 + h) * 128 + 4 n + e.
-// Padded output channels are zero.  Returns the float count (out may be NULL to query it) or OFX_EINVAL.
-extern "C" long ofx_wino_conv_weight(const float* w, int Cout, int Cin, float* out) {
+namespace {
+
+// Host: U = T g per (output, input) channel pair of OIHW weights w (`taps` contiguous floats per pair) in float64 (`xf` writes the
+// `points` values), rounded once to fp32, in the fused kernel's operand order: [points][Cout rounded up to `cblk`, as 32-channel
+// blocks][Cin / 8][2][32][4], i.e. point q, output channel o = 32 nb + n, input channel c = 8 c8 + 4 h + e at float
+// (((q * NB + nb) * Cin / 8 + c8) * 2 + h) * 128 + 4 n + e.  Padded output channels are zero.  Returns the float count (out may be
+// NULL to query it) or OFX_EINVAL.
+template <class XF>
+long wino_weight(const float* w, int Cout, int Cin, int taps, int points, int cblk, float* out, XF xf) {
     OFX_REQUIRE(Cout > 0 && Cin > 0 && Cin % kWBK == 0, OFX_EINVAL);
-    const int nb32 = 2 * ((Cout + 63) / 64);
-    const long n = 16L * nb32 * 32 * Cin;
+    const int nb32 = cblk / 32 * ((Cout + cblk - 1) / cblk);
+    const long n = (long)points * nb32 * 32 * Cin;
     if (!out) return n;
     OFX_REQUIRE(w != nullptr, OFX_EINVAL);
     std::memset(out, 0, (size_t)n * sizeof(float));
-    static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    double u[16];
     for (int o = 0; o < Cout; ++o)
         for (int c = 0; c < Cin; ++c) {
-            const float* g = w + ((size_t)o * Cin + c) * 9;
-            double gg[4][3];   // G g
-            for (int i = 0; i < 4; ++i)
-                for (int x = 0; x < 3; ++x) gg[i][x] = G[i][0] * g[x] + G[i][1] * g[3 + x] + G[i][2] * g[6 + x];
-            for (int i = 0; i < 4; ++i)
-                for (int j = 0; j < 4; ++j) {
-                    const double u = gg[i][0] * G[j][0] + gg[i][1] * G[j][1] + gg[i][2] * G[j][2];
-                    const long at = ((((long)(4 * i + j) * nb32 + o / 32) * (Cin / 8) + c / 8) * 2 + (c % 8) / 4) * 128 + 4 * (o % 32) + c % 4;
-                    out[at] = (float)u;
-                }
+            xf(w + ((size_t)o * Cin + c) * taps, u);
+            for (int q = 0; q < points; ++q) {
+                const long at = ((((long)q * nb32 + o / 32) * (Cin / 8) + c / 8) * 2 + (c % 8) / 4) * 128 + 4 * (o % 32) + c % 4;
+                out[at] = (float)u[q];
+            }
         }
     return n;
+}
+
+}  // namespace
+
+// 3x3: U = G g G^T, point (i, j) = 4 i + j; Cout rounded up to 64.
+extern "C" long ofx_wino_conv_weight(const float* w, int Cout, int Cin, float* out) {
+    return wino_weight(w, Cout, Cin, 9, 16, 64, out, [](const float* g, double* u) {
+        static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+        double gg[4][3];   // G g
+        for (int i = 0; i < 4; ++i)
+            for (int x = 0; x < 3; ++x) gg[i][x] = G[i][0] * g[x] + G[i][1] * g[3 + x] + G[i][2] * g[6 + x];
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) u[4 * i + j] = gg[i][0] * G[j][0] + gg[i][1] * G[j][1] + gg[i][2] * G[j][2];
+    });
+}
+
+// 1x5 or 5x1 (the 5 taps are contiguous in either orientation): U = G g; Cout rounded up to 128.  G rows: the points 0, 1, -1, 2,
+// -2, 1/2, -1/2 scaled by 1 / prod_{k != j} (a_j - a_k) (row 0 sign-flipped, with B^T's), and inf.
+extern "C" long ofx_wino15_conv_weight(const float* w, int Cout, int Cin, int KH, int KW, float* out) {
+    OFX_REQUIRE(is_1d(KH, KW), OFX_EINVAL);
+    return wino_weight(w, Cout, Cin, 5, 8, 128, out, [](const float* g, double* u) {
+        static const double G[8][5] = {
+            {1, 0, 0, 0, 0},
+            {-2.0 / 9, -2.0 / 9, -2.0 / 9, -2.0 / 9, -2.0 / 9},
+            {-2.0 / 9, 2.0 / 9, -2.0 / 9, 2.0 / 9, -2.0 / 9},
+            {1.0 / 90, 1.0 / 45, 2.0 / 45, 4.0 / 45, 8.0 / 45},
+            {1.0 / 90, -1.0 / 45, 2.0 / 45, -4.0 / 45, 8.0 / 45},
+            {32.0 / 45, 16.0 / 45, 8.0 / 45, 4.0 / 45, 2.0 / 45},
+            {32.0 / 45, -16.0 / 45, 8.0 / 45, -4.0 / 45, 2.0 / 45},
+            {0, 0, 0, 0, 1},
+        };
+        for (int q = 0; q < 8; ++q) {
+            u[q] = 0.0;
+            for (int t = 0; t < 5; ++t) u[q] += G[q][t] * (double)g[t];
+        }
+    });
 }

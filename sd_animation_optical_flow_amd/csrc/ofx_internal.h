@@ -58,17 +58,12 @@ static inline int ofx_launch_status() {
 
 // conv.hip: ofx_conv2d with an extra scalar multiplier on the accumulator (out = act(acc*alpha*scale + shift))
 extern "C" int ofx_conv2d_alpha(const ofx_conv_desc* d, float alpha, void* stream);
-// conv_wino.hip: the fused Winograd F(2x2,3x3) path of ofx_conv2d (shape test, grid size, executed FLOPs, launch)
+// conv_wino.hip: the fused Winograd paths of ofx_conv2d, F(2x2,3x3) for 3x3 and F(4,5) for 1x5 / 5x1 layers, picked from KH / KW
+// (shape test, whether the grid is large enough to take it, executed FLOPs, launch)
 bool ofx_conv_wino_fits(const ofx_conv_desc* d);
-long ofx_conv_wino_blocks(const ofx_conv_desc* d);
+bool ofx_conv_wino_pays(const ofx_conv_desc* d);
 double ofx_conv_wino_flops(const ofx_conv_desc* d);
 int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, hipStream_t s);
-// conv_wino15.hip: the fused 1D Winograd F(4,5) path of ofx_conv2d for 1x5 / 5x1 layers (shape test, 8x16 patches of the map,
-// executed FLOPs, launch)
-bool ofx_conv_wino15_fits(const ofx_conv_desc* d);
-long ofx_conv_wino15_patches(const ofx_conv_desc* d);
-double ofx_conv_wino15_flops(const ofx_conv_desc* d);
-int ofx_conv_wino15_launch(const ofx_conv_desc* d, float alpha, hipStream_t s);
 // conv.hip: the blocked correlation volume GEMM that also writes pyramid level 1 from its accumulators
 int ofx_conv2d_volpool(const ofx_conv_desc* d, float alpha, float* pool_out, long pool_zs, int wb0, int wb1, int slice1, void* stream);
 

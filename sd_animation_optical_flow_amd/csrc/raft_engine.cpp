@@ -236,44 +236,38 @@ int add_conv(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const std
     return 0;
 }
 
-// the Winograd operand U = G g G^T of an already added 3x3 layer (conv.hip takes the fused Winograd kernel with it when the grid
-// fills the chip; the direct packing stays for every other launch)
-int add_wino(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const std::string& name, const std::string& store_as) {
-    const HostTensor* w = find(sd, name + ".weight");
+// the Winograd operand of an already added 3x3 (F(2x2,3x3), U = G g G^T) or 1x5 / 5x1 (F(4,5), U = G g) layer, made of the input
+// channels `sel` (empty: all) of one or more checkpoint convolutions stacked along Cout in the given order (the GRU's z | r): the
+// same rows and channels as its direct packing.  conv.hip takes the fused Winograd kernel with it when the grid fills the chip; the
+// direct packing stays for every other launch.
+int add_wino(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const std::vector<std::string>& names, const std::vector<int>& sel,
+             const std::string& store_as) {
     ConvW& c = r->convs[store_as];
-    if (!w || w->ndim != 4 || w->shape[0] != c.cout || w->shape[1] != c.cin || c.kh != 3 || c.kw != 3 || c.cin_pad != c.cin) return OFX_EKEY;
-    const long n = ofx_wino_conv_weight(nullptr, c.cout, c.cin, nullptr);
-    if (n < 0) return (int)n;
-    std::vector<float> u((size_t)n);
-    const long st = ofx_wino_conv_weight(w->data, c.cout, c.cin, u.data());
-    if (st < 0) return (int)st;
-    return upload(r, u, &c.wino);
-}
-
-// the 1D Winograd F(4,5) operand U = G g of an already added 1x5 / 5x1 layer made of the input channels `sel` of one or more
-// checkpoint convolutions stacked along Cout in the given order (the GRU's z | r): the same rows and channels as its direct packing
-int add_wino15(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const std::vector<std::string>& names,
-               const std::vector<int>& sel, const std::string& store_as) {
-    ConvW& c = r->convs[store_as];
-    const int ci = (int)sel.size();
-    if (c.cin != ci || c.cin_pad != ci || !((c.kh == 1 && c.kw == 5) || (c.kh == 5 && c.kw == 1))) return OFX_EKEY;
-    std::vector<float> g;   // [Cout][ci][5]
+    const int ci = c.cin, taps = c.kh * c.kw;
+    const bool k3x3 = c.kh == 3 && c.kw == 3, k1d = (c.kh == 1 && c.kw == 5) || (c.kh == 5 && c.kw == 1);
+    if ((!k3x3 && !k1d) || c.cin_pad != ci || (!sel.empty() && (int)sel.size() != ci)) return OFX_EKEY;
+    std::vector<float> g;   // [Cout][ci][taps]
     for (const std::string& name : names) {
         const HostTensor* w = find(sd, name + ".weight");
         if (!w || w->ndim != 4 || w->shape[2] != c.kh || w->shape[3] != c.kw) return OFX_EKEY;
         const int co = (int)w->shape[0], full = (int)w->shape[1];
+        if (sel.empty() && full != ci) return OFX_EKEY;
         for (int o = 0; o < co; ++o)
             for (int k = 0; k < ci; ++k) {
-                if (sel[k] < 0 || sel[k] >= full) return OFX_EKEY;
-                const float* src = w->data + ((size_t)o * full + sel[k]) * 5;
-                g.insert(g.end(), src, src + 5);
+                const int ch = sel.empty() ? k : sel[k];
+                if (ch < 0 || ch >= full) return OFX_EKEY;
+                const float* src = w->data + ((size_t)o * full + ch) * taps;
+                g.insert(g.end(), src, src + taps);
             }
     }
-    if ((long)g.size() != (long)c.cout * ci * 5) return OFX_EKEY;
-    const long n = ofx_wino15_conv_weight(nullptr, c.cout, ci, c.kh, c.kw, nullptr);
+    if ((long)g.size() != (long)c.cout * ci * taps) return OFX_EKEY;
+    auto xf = [&](const float* w, float* out) {
+        return k3x3 ? ofx_wino_conv_weight(w, c.cout, ci, out) : ofx_wino15_conv_weight(w, c.cout, ci, c.kh, c.kw, out);
+    };
+    const long n = xf(nullptr, nullptr);
     if (n < 0) return (int)n;
     std::vector<float> u((size_t)n);
-    const long st = ofx_wino15_conv_weight(g.data(), c.cout, ci, c.kh, c.kw, u.data());
+    const long st = xf(g.data(), u.data());
     if (st < 0) return (int)st;
     return upload(r, u, &c.wino);
 }
@@ -353,8 +347,8 @@ int build_gru(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const st
         st = add_conv(r, sd, "update_block.gru.convq" + tag, "gru.q" + tag + sfx, 0, "", 1.f, nullptr, nullptr, sel, bias);
         if (st) return st;
         if (part == 0) {   // the per-iteration parts also get the 1D Winograd operand (the once-per-forward .inp parts stay direct)
-            st = add_wino15(r, sd, {"update_block.gru.convz" + tag, "update_block.gru.convr" + tag}, rec, "gru.zr" + tag);
-            if (!st) st = add_wino15(r, sd, {"update_block.gru.convq" + tag}, rec, "gru.q" + tag);
+            st = add_wino(r, sd, {"update_block.gru.convz" + tag, "update_block.gru.convr" + tag}, rec, "gru.zr" + tag);
+            if (!st) st = add_wino(r, sd, {"update_block.gru.convq" + tag}, rec, "gru.q" + tag);
             if (st) return st;
         }
     }
@@ -792,7 +786,7 @@ int ofx_raft_create(const ofx_tensor* tensors, int n, ofx_raft** out) {
     const char* ub = "update_block.";
     if (!st) st = add_conv(r, sd, std::string(ub) + "encoder.convc1", "convc1", CORR_LD, "", 1.f);   // input rows padded to 336 (zero weights)
     if (!st) st = add_conv(r, sd, std::string(ub) + "encoder.convc2", "convc2", 0, "", 1.f);
-    if (!st) st = add_wino(r, sd, std::string(ub) + "encoder.convc2", "convc2");
+    if (!st) st = add_wino(r, sd, {std::string(ub) + "encoder.convc2"}, {}, "convc2");
     std::vector<float> wf1;   // must outlive add_conv below
     if (!st) {
         // convf1 (7x7 on the 2-channel flow, update.py:93) as a 7x1 convolution over the 16-float flow rows the flow head leaves
@@ -817,13 +811,13 @@ int ofx_raft_create(const ofx_tensor* tensors, int n, ofx_raft** out) {
         }
     }
     if (!st) st = add_conv(r, sd, std::string(ub) + "encoder.convf2", "convf2", 0, "", 1.f);
-    if (!st) st = add_wino(r, sd, std::string(ub) + "encoder.convf2", "convf2");
+    if (!st) st = add_wino(r, sd, {std::string(ub) + "encoder.convf2"}, {}, "convf2");
     if (!st) st = add_conv(r, sd, std::string(ub) + "encoder.conv", "conv", 0, "", 1.f);
-    if (!st) st = add_wino(r, sd, std::string(ub) + "encoder.conv", "conv");
+    if (!st) st = add_wino(r, sd, {std::string(ub) + "encoder.conv"}, {}, "conv");
     if (!st) st = build_gru(r, sd, "1");
     if (!st) st = build_gru(r, sd, "2");
     if (!st) st = add_conv(r, sd, std::string(ub) + "flow_head.conv1", "fh1", 0, "", 1.f);
-    if (!st) st = add_wino(r, sd, std::string(ub) + "flow_head.conv1", "fh1");
+    if (!st) st = add_wino(r, sd, {std::string(ub) + "flow_head.conv1"}, {}, "fh1");
     if (!st) st = add_conv(r, sd, std::string(ub) + "flow_head.conv2", "fh2", 0, "", 1.f);
     if (!st) st = add_conv(r, sd, std::string(ub) + "mask.0", "mask0", 0, "", 1.f);
     if (!st) st = add_conv(r, sd, std::string(ub) + "mask.2", "mask2", 0, "", 0.25f);

@@ -238,6 +238,19 @@ def pack_conv_weight(w_oihw: torch.Tensor, cin_pad: Optional[int] = None) -> tor
     return out
 
 
+def _wino_weight(fn: str, w: torch.Tensor, *shape) -> torch.Tensor:
+    """The Winograd operand of `w` (fp32 OIHW, CPU) from the C entry point `fn`(w, *shape, out) as a flat fp32 CPU tensor."""
+    f = getattr(_lib.lib(), fn)
+    n = f(None, *shape, None)
+    if n < 0:
+        raise _lib.OfxError(int(n), fn)
+    out = torch.empty((n,), dtype=torch.float32)
+    st = f(C.c_void_p(w.data_ptr()), *shape, C.c_void_p(out.data_ptr()))
+    if st < 0:
+        raise _lib.OfxError(int(st), fn)
+    return out
+
+
 def wino_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
     """OIHW fp32 3x3 (CPU) -> the Winograd F(2x2,3x3) operand U = G g G^T (float64, one rounding) as a flat fp32 CPU tensor
     in the fused kernel's order (ofx_wino_conv_weight); pass it to conv2d_nhwc(..., wino_w=)."""
@@ -245,15 +258,7 @@ def wino_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
     co, ci, kh, kw = w.shape
     if (kh, kw) != (3, 3):
         raise RuntimeError("wino_conv_weight: 3x3 weights only")
-    L = _lib.lib()
-    n = L.ofx_wino_conv_weight(None, co, ci, None)
-    if n < 0:
-        raise _lib.OfxError(int(n), "ofx_wino_conv_weight")
-    out = torch.empty((n,), dtype=torch.float32)
-    st = L.ofx_wino_conv_weight(C.c_void_p(w.data_ptr()), co, ci, C.c_void_p(out.data_ptr()))
-    if st < 0:
-        raise _lib.OfxError(int(st), "ofx_wino_conv_weight")
-    return out
+    return _wino_weight("ofx_wino_conv_weight", w, co, ci)
 
 
 def wino15_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
@@ -261,15 +266,7 @@ def wino15_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
     in the fused kernel's order (ofx_wino15_conv_weight); pass it to conv2d_nhwc(..., wino_w=)."""
     w = w_oihw.detach().to(torch.float32).contiguous().cpu()
     co, ci, kh, kw = w.shape
-    L = _lib.lib()
-    n = L.ofx_wino15_conv_weight(None, co, ci, kh, kw, None)
-    if n < 0:
-        raise _lib.OfxError(int(n), "ofx_wino15_conv_weight")
-    out = torch.empty((n,), dtype=torch.float32)
-    st = L.ofx_wino15_conv_weight(C.c_void_p(w.data_ptr()), co, ci, kh, kw, C.c_void_p(out.data_ptr()))
-    if st < 0:
-        raise _lib.OfxError(int(st), "ofx_wino15_conv_weight")
-    return out
+    return _wino_weight("ofx_wino15_conv_weight", w, co, ci, kh, kw)
 
 
 def split_conv_weight(w_packed: torch.Tensor) -> torch.Tensor:

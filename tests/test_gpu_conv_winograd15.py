@@ -1,4 +1,4 @@
-"""The fused 1D Winograd F(4,5) convolution (conv_wino15.hip) of the SepConvGRU's 1x5 and 5x1 layers.
+"""The fused 1D Winograd F(4,5) convolution (conv_wino.hip) of the SepConvGRU's 1x5 and 5x1 layers.
 
 GPU tests are marked -m gpu; the host weight transform is checked without a GPU.
 """

@@ -13,7 +13,7 @@ convolution (two input segments: rh with row stride 128, then hx[:, 128:256]; ep
     zr plain-epi plain store epilogue
 
 GRU_BENCH_WINO=1: instead, the four per-iteration layers (zr / q, 1x5 / 5x1) as the engine launches them, on the direct kernel and
-on the fused 1D Winograd F(4,5) kernel (tile 1, conv_wino15.hip); its rate is also given in executed FLOPs (2.5x fewer).
+on the fused 1D Winograd F(4,5) kernel (tile 1, conv_wino.hip); its rate is also given in executed FLOPs (2.5x fewer).
 GRU_BENCH_B=n: batch size (default 64).
 usage: python tools/gru_bench.py [libofx variant .so]"""
 import ctypes as C, os, sys
