@@ -203,7 +203,7 @@ int ofx_abs_diff_sum_u8(const uint8_t* a, long a_bstride, const uint8_t* b, long
 typedef struct ofx_conv_desc {
     /* input: NHWC fp32, up to two channel segments (torch.cat along C without materialising) */
     const float* in0; int ld0; int c0;
-    const float* in1; int ld1; int c1;          /* in1 may be NULL (c1 = 0) */
+    const float* in1; int ld1; int c1;          /* in1 may be NULL (c1 = 0); with in1, c0 and c1 multiples of 32 (else OFX_EALIGN) */
     /* weights packed [Cout][Kpad], k = (ky*KW + kx)*(c0+c1) + c, Kpad = K rounded up to 32 */
     const float* w;
     const float* scale;                          /* [Cout] or NULL (=1) */

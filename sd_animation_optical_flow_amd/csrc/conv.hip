@@ -1362,7 +1362,9 @@ extern "C" int ofx_conv2d_alpha(const ofx_conv_desc* d, float alpha, void* strea
     const long extw = (long)d->Cout * k.Kpad * 4;
     OFX_REQUIRE(ext0 < (1L << 31) - 64 && ext1 < (1L << 31) - 64 && extw < (1L << 31) - 64, OFX_EINVAL);
     OFX_REQUIRE(k.Kpad < 65536, OFX_EINVAL);                       // umulhi division is exact in this range
-    if (d->in1) OFX_REQUIRE(d->c0 % kKAlign == 0, OFX_EALIGN);           // a K chunk never straddles the two segments
+    // a K chunk never straddles the two segments: not at c0 inside a tap, nor at the wrap from one tap's last channels (in1) to the
+    // next tap's first (in0) -- the general schedule picks one segment per chunk (issue: readfirstlane), so c1 must be whole chunks too
+    if (d->in1) OFX_REQUIRE(d->c0 % kKAlign == 0 && d->c1 % kKAlign == 0, OFX_EALIGN);
     k.bytes0 = (int)ext0; k.bytes1 = (int)ext1; k.bytesw = (int)extw;
     k.pool_out = tl_pool.on ? tl_pool.out : nullptr; k.pool_zs = tl_pool.zs; k.pool_wb0 = tl_pool.wb0; k.pool_wb1 = tl_pool.wb1;
     k.pool_slice1 = tl_pool.slice1;
