@@ -331,6 +331,19 @@ int ofx_upsample_flow(const float* coords1, const float* mask, float* flow_up, i
  * Bit-identical to ofx_upsample_flow followed by ofx_warp_u8(OFX_WARP_BILINEAR) with frame_batch_stride = 0. */
 int ofx_upsample_flow_warp(const float* coords1, const float* mask, float* flow_up, const uint8_t* frame,
                            uint8_t* warped, int B, int h, int w, float sign, void* stream);
+/* The flow head's second convolution (update.py:6-14, 3x3, 256 -> 2) fused with coords1 += delta (raft.py:131), as the RAFT
+ * executor runs it.  x [B*h*w][ldx] NHWC fp32, the first 256 channels read (ldx >= 256, ldx % 4 == 0, 16-byte aligned);
+ * w [2][kpad] as ofx_pack_conv_weight packs the OIHW [2][256][3][3] weight (kpad >= 2304, kpad % 4 == 0, 16-byte aligned);
+ * bias [2]; coords1 [B*h*w][2] (8-byte aligned).  Per pixel m = (b*h + y)*w + x, channel o in {0, 1}:
+ *   coords1[m*2 + o] += conv + bias            (delta first, then the add: one rounding at the coordinate's magnitude)
+ *   hx_flow[m*ldh + o] = coords1[m*2 + o] - (o == 0 ? x : y)          (ldh >= 2)
+ *   frows[m*16 + 2*s + o] = the hx_flow value of pixel x + s - 3 of the same row, for slot s = 0..6, written only where that
+ *                           pixel is inside the image (convf1's 7-wide row of flows)
+ * Nothing else is written: slots of neighbours outside the image, floats 14 and 15 of every row and the other channels of an hx
+ * row keep what they held.  B*h*w*ldx*4 < 2^31 (32-bit byte offsets).  OFX_EINVAL for a null pointer, a non-positive size or a
+ * short ldx / kpad / ldh, OFX_EALIGN for the alignments above. */
+int ofx_flow_head(const float* x, int ldx, const float* w, int kpad, const float* bias, float* coords1, float* hx_flow,
+                  int ldh, float* frows, int B, int h, int w_, void* stream);
 
 /* ---------------------------------------------------------------- RAFT engine */
 typedef struct ofx_tensor {            /* one entry of a checkpoint state_dict (host memory, fp32) */

@@ -102,6 +102,7 @@ SIGNATURES = {
     "ofx_avgpool2_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "ofx_upsample_flow": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "ofx_upsample_flow_warp": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _p]),
+    "ofx_flow_head": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _p]),
     "ofx_raft_create": (_i, [C.POINTER(Tensor), _i, C.POINTER(_p)]),
     "ofx_raft_destroy": (_i, [_p]),
     "ofx_raft_workspace_bytes": (_z, [_p, _i, _i, _i]),

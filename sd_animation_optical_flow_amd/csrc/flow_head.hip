@@ -182,3 +182,14 @@ int ofx_flow_head_launch(const float* x, int ldx, const float* w, int Kpad, cons
     OFX_LAUNCH(flow_head_kernel, dim3(blocks), dim3(256), s, a);
     return ofx_launch_status();
 }
+
+// Checked entry point of include/ofx.h: the launcher above trusts the RAFT executor's layout; callers of the C ABI get every
+// assumption of the kernel checked -- the 16-byte lane loads of x and w, the float2 view of coords1, the 32-bit byte offsets into x.
+extern "C" int ofx_flow_head(const float* x, int ldx, const float* w, int kpad, const float* bias, float* coords1, float* hx_flow,
+                             int ldh, float* frows, int B, int h, int w_, void* stream) {
+    OFX_REQUIRE(x && w && bias && coords1 && hx_flow && frows && B > 0 && h > 0 && w_ > 0, OFX_EINVAL);
+    OFX_REQUIRE(ldx >= 256 && kpad >= 9 * 256 && ldh >= 2, OFX_EINVAL);
+    OFX_REQUIRE(ldx % 4 == 0 && kpad % 4 == 0 && ofx_aligned16(x) && ofx_aligned16(w) && (((uintptr_t)coords1) & 7u) == 0, OFX_EALIGN);
+    OFX_REQUIRE((long)B * h * w_ * ldx * 4 < (1L << 31) - 64, OFX_EINVAL);
+    return ofx_flow_head_launch(x, ldx, w, kpad, bias, coords1, hx_flow, ldh, frows, B, h, w_, (hipStream_t)stream);
+}

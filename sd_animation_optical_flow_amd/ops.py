@@ -345,6 +345,28 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
     return out
 
 
+def flow_head(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, coords1: torch.Tensor, hx: torch.Tensor,
+              frows: torch.Tensor, flow_off: int = 0) -> None:
+    """The flow head's 3x3 256 -> 2 convolution fused with coords1 += delta (`ofx_flow_head`, update.py:6-14 + raft.py:131).
+    x f32 [B,h,w,ldx] (the first 256 channels are read); w_packed [2, kpad] = pack_conv_weight of the OIHW [2,256,3,3] weight, on
+    the device; bias [2].  Written in place: coords1 f32 [B,h,w,2]; channels flow_off, flow_off + 1 of hx f32 [B,h,w,ldh] get
+    coords1 - grid; frows f32 [B,h,w,16] gets, in slot s = 0..6 of a pixel's row, the flow of the pixel s - 3 columns away where
+    that pixel is inside the image (nothing else of hx or frows is touched)."""
+    x = _chk(x, "x", torch.float32)
+    wp = _chk(w_packed, "w_packed", torch.float32)
+    b = _chk(bias, "bias", torch.float32)
+    c = _chk(coords1, "coords1", torch.float32)
+    hx = _chk(hx, "hx", torch.float32)
+    fr = _chk(frows, "frows", torch.float32)
+    B, h, w, ldx = x.shape
+    if (tuple(c.shape) != (B, h, w, 2) or tuple(hx.shape[:3]) != (B, h, w) or tuple(fr.shape) != (B, h, w, 16)
+            or wp.dim() != 2 or wp.shape[0] != 2 or b.numel() != 2 or not 0 <= flow_off <= hx.shape[3] - 2):
+        raise RuntimeError("shapes: x [B,h,w,ldx], w_packed [2,kpad], bias [2], coords1 [B,h,w,2], hx [B,h,w,ldh] with "
+                           "flow_off + 2 <= ldh, frows [B,h,w,16]")
+    check(_lib.lib().ofx_flow_head(_ptr(x), ldx, _ptr(wp), wp.shape[1], _ptr(b), _ptr(c), C.c_void_p(hx.data_ptr() + 4 * flow_off),
+                                   hx.shape[3], _ptr(fr), B, h, w, _stream()), "ofx_flow_head")
+
+
 def conv2d_desc(d: ConvDesc) -> None:
     check(_lib.lib().ofx_conv2d(C.byref(d), _stream()), "ofx_conv2d")
 

@@ -78,6 +78,32 @@ def test_stage_parity_one_iteration(engine, raft_sd):
     assert not corr[:, 324:].any()
 
 
+@pytest.mark.parametrize("H, W, B", [(128, 160, 2), (512, 768, 8)])
+def test_stage_parity_two_iterations(engine, raft_sd, H, W, B):
+    """The second iteration is the first to read what the flow head leaves behind: convf1's 16-float flow rows (frows) and the flow
+    slot of hx.  The flow after iteration 2, from the engine's coords1, elementwise and on the border ring of the 1/8 map on its own
+    (where a wrong or missing frows slot would sit).  B = 8 at 512x768: the flow head's four-wave launch (1536 strips) and the
+    Winograd routes of the update block.  Measured on MI355X: 3.8e-6 (ring 1.9e-6) at 2 x 128x160, 1.5e-5 (ring 7.6e-6) at
+    8 x 512x768, against the 2e-4 bar of the one-iteration test."""
+    key, frames = _frames(5, B, H, W)
+    img2 = key[None].repeat(B, 1, 1, 1)
+    tr = {"keep_iters": (2,)}
+    _oracle_flow(raft_sd, frames, img2, 2, trace=tr)
+    engine.forward(frames.cuda(), img2.cuda(), iters=2)
+    h, w = H // 8, W // 8
+    ref = tr["flow_low_at"][2].permute(0, 2, 3, 1)
+    grid = RO.coords_grid(B, h, w).permute(0, 2, 3, 1)
+    flow = engine.buffer("coords1").cpu().reshape(B, h, w, 2) - grid
+    hx = engine.buffer("hx").cpu().reshape(B, h, w, 384)
+    assert torch.equal(hx[..., 254:256], flow)                           # the flow slot is coords1 - grid, bit for bit
+    err = (flow - ref).abs()
+    ring = torch.zeros((h, w), dtype=torch.bool)
+    ring[0], ring[-1], ring[:, 0], ring[:, -1] = True, True, True, True
+    worst, worst_ring = err.max().item(), err[:, ring].max().item()
+    print(f"two iterations {B}x{H}x{W}: max |flow - oracle| {worst:.3g}, border ring {worst_ring:.3g}")
+    assert worst < 2e-4 and worst_ring < 2e-4, (worst, worst_ring)
+
+
 @pytest.mark.parametrize("H,W,B", [(128, 160, 3), (200, 136, 1)])
 def test_full_flow_epe_small(engine, raft_sd, H, W, B):
     key, frames = _frames(2, B, H, W)
