@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: frame-pairs/sec for flow + warp + mask at 512x768 on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic input per GPU: B frames
 (default 64 = BASELINE.json configs[2]/[3], "64-frame 512x768 clip ... HBM-resident cost volumes")
@@ -15,14 +15,19 @@ Prints ONE JSON line (rank 0) with the driver's contract fields plus
   "roofline":     the dominant kernel family (fp32-MFMA implicit-GEMM convolutions) measured live
                   with HIP events on the launch stream inside the timed region,
   "kernels":      the same measurement for the HBM-bound kernels (correlation volume, lookup,
-                  upsample, warp, mask) against the 8 TB/s HBM peak,
+                  upsample, warp, mask) against the 8 TB/s HBM peak.
+A plain run stops there: set-up, warm-up, the timed steps, --dump-outputs and the line.  --full adds every
+measurement beyond the headline, each after the timed region (the --no-* switches leave single ones out):
+  "verified":     three pairs of the last timed step against the CPU oracle in fp32 and float64,
   "cpu_baseline": the CPU oracle (a port; the reference's Python cannot travel to the GPU box) timed
                   on the host cores on a bounded sample of the same workload,
   "single_pair":  BASELINE.json configs[1] (one 512x768 pair) latency/throughput,
   "batch_sweep":  the batches in between (1, 4, 16, 64 frames per call),
   "workspace_pipeline": the path end to end over a PNG workspace (`pipeline.ClipPipeline.run`: decode -> H2D -> flow both ways ->
                   warp + mask -> SD-inpaint inputs -> render -> D2H -> encode) against the same calls on resident frames, with the
-                  host CPU-seconds per frame and the one-batch-per-rank share of BASELINE configs[3]; never `value`.
+                  host CPU-seconds per frame and the one-batch-per-rank share of BASELINE configs[3]; never `value`,
+  "raft2_as_written", "sd_handoff_1024", "kernels.corr_volume_gemm_split", "fast_mode", "split3_mode": the
+                  other configurations and precisions, on the same clip.
 """
 from __future__ import annotations
 
@@ -472,9 +477,15 @@ def main():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write what the last timed step computed (flow, warped frame, mask; float32 .npy, <= 64 MB) into DIR")
     ap.add_argument("--ws-segment", type=int, default=64, help="frames per key-frame segment of the --workspace mode (one segment per rank)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every secondary measurement: oracle check, CPU "
+                    "baseline, single pair, batch sweep, hand-off, other precisions, workspace pipeline (the --no-* switches apply here)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run measures the headline alone: every block after the timed region is --full's
+        args.no_verify = args.no_cpu_baseline = args.no_single = args.no_sweep = True
+        args.no_handoff = args.no_fast = args.no_volsplit = args.no_pipeline = True
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(verify=args.verify_npz)))
         return
