@@ -331,6 +331,16 @@ int ofx_upsample_flow(const float* coords1, const float* mask, float* flow_up, i
  * Bit-identical to ofx_upsample_flow followed by ofx_warp_u8(OFX_WARP_BILINEAR) with frame_batch_stride = 0. */
 int ofx_upsample_flow_warp(const float* coords1, const float* mask, float* flow_up, const uint8_t* frame,
                            uint8_t* warped, int B, int h, int w, float sign, void* stream);
+/* upflow8 of the small network (RAFT/core/utils/utils.py:80-82, raft.py:134-135): flow = coords1 - coords0 on the coarse grid,
+ * bilinear upsampled with align_corners=True to [8h, 8w] and multiplied by 8 (8 * F.interpolate(flow, (8h, 8w), 'bilinear',
+ * align_corners=True)).  coords1 [B*h*w][2] (8-byte aligned) -> flow_up f32[B, 8h, 8w, 2] (16-byte aligned); any h, w >= 1. */
+int ofx_upflow8(const float* coords1, float* flow_up, int B, int h, int w, void* stream);
+/* ofx_upflow8 + the bilinear backward warp of one shared frame u8 [8h][8w][3] in ONE kernel (the counterpart of
+ * ofx_upsample_flow_warp for the small network): warped u8 [B][8h][8w][3]; flow_up f32 [B][8h][8w][2] or NULL (not written).
+ * sign = +1 (pdcnet_of.py:34-42) or -1 (ofgen_keyframe_inpaint.py:92-98).
+ * Bit-identical to ofx_upflow8 followed by ofx_warp_u8(OFX_WARP_BILINEAR) with frame_batch_stride = 0. */
+int ofx_upflow8_warp(const float* coords1, float* flow_up, const uint8_t* frame, uint8_t* warped, int B, int h, int w,
+                     float sign, void* stream);
 /* The flow head's second convolution (update.py:6-14, 3x3, 256 -> 2) fused with coords1 += delta (raft.py:131), as the RAFT
  * executor runs it.  x [B*h*w][ldx] NHWC fp32, the first 256 channels read (ldx >= 256, ldx % 4 == 0, 16-byte aligned);
  * w [2][kpad] as ofx_pack_conv_weight packs the OIHW [2][256][3][3] weight (kpad >= 2304, kpad % 4 == 0, 16-byte aligned);
@@ -408,8 +418,18 @@ int ofx_raft_forward_pairs_warp(ofx_raft* r, const uint8_t* images, int n_images
                                 const int* idx2, int B, int H, int W, int iters, int flags, float* flow_up,
                                 float* flow_low, const uint8_t* warp_frame, float warp_sign, int n_warp,
                                 uint8_t* warped, void* workspace, size_t workspace_bytes, void* stream);
+/* Which network the checkpoint given to ofx_raft_create holds: 0 = basic (raft-things.pth: BasicEncoder, SepConvGRU, convex
+ * upsample), 1 = small (raft-small.pth: SmallEncoder, radius-3 lookup, ConvGRU, upflow8; RAFT/core/raft.py:29-33, :48-51).
+ * ofx_raft_create picks it from the key set (update_block.gru.convz + fnet.layer1.0.conv3 = small); a dict with keys of both or a
+ * partial one is OFX_EKEY.  The small network takes every entry point and flag above except the split-bf16 modes (OFX_RAFT_BF16X3,
+ * _BF16X6, _VOL_BF16X3, _VOL_BF16X6: OFX_EINVAL) -- it runs in exact fp32 only; OFX_RAFT_BN_BATCH has no meaning for it (no
+ * BatchNorm) and is ignored; its launches always stay on the caller's stream (OFX_RAFT_SERIAL implied).  Its widest convolution
+ * operand is the 256-float GRU row, so one call takes up to (2^31 - 4096) / ((H/8)*(W/8)*1024) pairs. */
+int ofx_raft_variant(const ofx_raft* r);
 /* debug / stage-parity access to the buffers of the last forward: returns a device pointer and
- * element count for a named intermediate ("fmap1","fmap2","hx","corr","pyr0".."pyr3","mask",...) */
+ * element count for a named intermediate ("fmap1","fmap2","hx","corr","pyr0".."pyr3","mask",...).  The small network's
+ * (ofx_raft_forward / _warp only): "fmap1", "fmap2" ([n][h*w][128]), "hx" (rows of 256: net 0..95, inp 96..159, motion 160..239,
+ * flow 240..241, zeros), "corr" (rows of 224: the 196 lookup features of the last iteration, then zeros), "coords1", "pyr0".."pyr3". */
 int ofx_raft_buffer(const ofx_raft* r, const char* name, void** ptr, size_t* nfloats);
 
 #ifdef __cplusplus

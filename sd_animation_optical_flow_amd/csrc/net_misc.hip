@@ -211,6 +211,12 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
     if (o.valid) ofx_upsample_store(o, flow_up, h, w);
 }
 
+// ---- upflow8 of the small network (the per-thread arithmetic lives in upsample_inl.h, shared with the upflow8 + warp kernel)
+__global__ __launch_bounds__(256) void upflow8_kernel(const float* __restrict__ coords1, float* __restrict__ flow_up, int B, int h, int w) {
+    const OfxUp8Group o = ofx_upflow8_group(coords1, B, h, w, (long)blockIdx.x * 256 + threadIdx.x);
+    if (o.valid) ofx_upflow8_store(o, flow_up, h, w);
+}
+
 // coords1 = pixel grid, frows (the flow rows convf1 reads, flow_head.hip) = 0, hx[:, flow_off:flow_off+2] = 0   (RAFT.initialize_flow, raft.py:63-70)
 __global__ __launch_bounds__(256) void init_state_kernel(float* __restrict__ coords1, float* __restrict__ frows,
                                                          float* __restrict__ hx, int ldh, int flow_off, int h, int w, long M) {
@@ -349,6 +355,17 @@ int ofx_upsample_flow(const float* coords1, const float* mask, float* flow_up, i
     OfxProfScope prof("upsample_flow", s);
     const long groups = (M / w) * ((w + 3) / 4);   // 4 coarse pixels per wavefront, 4 wavefronts per workgroup
     hipLaunchKernelGGL(upsample_kernel, dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, s, coords1, mask, flow_up, h, w, M);
+    return ofx_launch_status();
+}
+
+int ofx_upflow8(const float* coords1, float* flow_up, int B, int h, int w, void* stream) {
+    OFX_REQUIRE(coords1 && flow_up && B > 0 && h > 0 && w > 0, OFX_EINVAL);
+    OFX_REQUIRE((((uintptr_t)coords1) & 7u) == 0 && ofx_aligned16(flow_up), OFX_EALIGN);
+    const long groups = (long)B * h * 8 * (2 * w);   // 4 fine pixels per thread
+    OFX_REQUIRE((groups + 255) / 256 < (1L << 31), OFX_EINVAL);
+    hipStream_t s = (hipStream_t)stream;
+    OfxProfScope prof("upflow8", s);
+    hipLaunchKernelGGL(upflow8_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, coords1, flow_up, B, h, w);
     return ofx_launch_status();
 }
 

@@ -110,6 +110,7 @@ struct Carver {
 }  // namespace
 
 struct ofx_raft {
+    int variant = 0;   // 0 = basic (raft-things.pth), 1 = small (raft-small.pth): picked from the checkpoint's key set
     std::map<std::string, ConvW> convs;
     // gamma / beta of the context encoder's BatchNorm layers for the batch-statistics mode (OFX_RAFT_BN_BATCH), by norm name
     std::map<std::string, std::pair<float*, float*>> affine;
@@ -762,6 +763,17 @@ static int raft_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* 
                              float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign, uint8_t* warped, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+// the small network (raft.py:29-33, :48-51): its own builder, workspace and schedule, further down
+static int small_detect(const std::map<std::string, HostTensor>& sd);
+static int small_build(ofx_raft* r, const std::map<std::string, HostTensor>& sd);
+static size_t small_workspace_bytes(int B, int H, int W, int n_images);
+static int small_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* image2, int B, int H, int W, int iters, int flags,
+                              float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign, uint8_t* warped, void* workspace,
+                              size_t workspace_bytes, void* stream);
+static int small_forward_pairs_impl(ofx_raft* r, const uint8_t* images, int n_images, const int* idx1, const int* idx2, int B, int H, int W,
+                                    int iters, int flags, float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign,
+                                    int n_warp, uint8_t* warped, void* workspace, size_t workspace_bytes, void* stream);
+
 extern "C" {
 
 int ofx_raft_create(const ofx_tensor* tensors, int n, ofx_raft** out) {
@@ -779,7 +791,19 @@ int ofx_raft_create(const ofx_tensor* tensors, int n, ofx_raft** out) {
         for (int j = 0; j < 4; ++j) t.shape[j] = j < t.ndim ? tensors[i].shape[j] : 1;
         sd[k] = t;
     }
+    const int variant = small_detect(sd);
+    if (variant < 0) return variant;
     ofx_raft* r = new ofx_raft();
+    r->variant = variant;
+    if (variant == 1) {
+        int st = small_build(r, sd);
+        if (st) {
+            ofx_raft_destroy(r);
+            return st;
+        }
+        *out = r;
+        return 0;
+    }
     int st = build_encoder(r, sd, "fnet", false);
     if (!st) st = build_encoder(r, sd, "cnet", true);
     if (!st) st = build_encoder(r, sd, "cnet", true, "cnetb");
@@ -847,8 +871,8 @@ int ofx_raft_destroy(ofx_raft* r) {
 }
 
 size_t ofx_raft_workspace_bytes(const ofx_raft* r, int B, int H, int W) {
-    (void)r;
     if (B <= 0 || H <= 0 || W <= 0 || (H % 8) || (W % 8)) return 0;
+    if (r && r->variant == 1) return small_workspace_bytes(B, H, W, 0);
     // the volume layout is the larger of the two correlation modes
     size_t a = carve(nullptr, 0, B, H, W, 0).bytes;
     size_t b = carve(nullptr, 0, B, H, W, OFX_RAFT_ALT_CORR).bytes;
@@ -875,6 +899,9 @@ int ofx_raft_forward_warp(ofx_raft* r, const uint8_t* image1, const uint8_t* ima
 static int raft_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* image2, int B, int H, int W, int iters, int flags,
                              float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign, uint8_t* warped, void* workspace,
                              size_t workspace_bytes, void* stream) {
+    if (r && r->variant == 1)
+        return small_forward_impl(r, image1, image2, B, H, W, iters, flags, flow_up, flow_low, warp_frame, warp_sign, warped, workspace,
+                                  workspace_bytes, stream);
     OFX_REQUIRE(r && image1 && image2 && (flow_up || warped) && workspace, OFX_EINVAL);
     OFX_REQUIRE(B > 0 && H >= 64 && W >= 64 && (H % 8) == 0 && (W % 8) == 0 && iters >= 1, OFX_EINVAL);
     OFX_REQUIRE((((uintptr_t)workspace) & 255u) == 0, OFX_EALIGN);
@@ -1013,8 +1040,8 @@ static int raft_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* 
 extern "C" {
 
 size_t ofx_raft_workspace_bytes_pairs(const ofx_raft* r, int n_images, int B, int H, int W) {
-    (void)r;
     if (n_images <= 0 || B <= 0 || H <= 0 || W <= 0 || (H % 8) || (W % 8)) return 0;
+    if (r && r->variant == 1) return small_workspace_bytes(B, H, W, n_images);
     return carve(nullptr, 0, B, H, W, 0, n_images).bytes;
 }
 
@@ -1029,6 +1056,9 @@ int ofx_raft_forward_pairs_warp(ofx_raft* r, const uint8_t* images, int n_images
                                 int W, int iters, int flags, float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign,
                                 int n_warp, uint8_t* warped, void* workspace, size_t workspace_bytes, void* stream) {
     OFX_REQUIRE(r && images && idx1 && idx2 && flow_up && workspace, OFX_EINVAL);
+    if (r->variant == 1)
+        return small_forward_pairs_impl(r, images, n_images, idx1, idx2, B, H, W, iters, flags, flow_up, flow_low, warp_frame, warp_sign, n_warp,
+                                        warped, workspace, workspace_bytes, stream);
     if (warped || warp_frame || n_warp) {
         OFX_REQUIRE(warp_frame && warped && n_warp > 0 && n_warp <= B && (warp_sign == 1.0f || warp_sign == -1.0f), OFX_EINVAL);
         OFX_REQUIRE(ofx_upsample_warp_ok(n_warp, H, W) && (((uintptr_t)warped) & 3u) == 0, OFX_EINVAL);
@@ -1120,6 +1150,11 @@ int ofx_raft_forward_pairs_warp(ofx_raft* r, const uint8_t* images, int n_images
     return 0;
 }
 
+int ofx_raft_variant(const ofx_raft* r) {
+    OFX_REQUIRE(r, OFX_EINVAL);
+    return r->variant;
+}
+
 int ofx_raft_buffer(const ofx_raft* r, const char* name, void** ptr, size_t* nfloats) {
     OFX_REQUIRE(r && name && ptr && nfloats, OFX_EINVAL);
     auto it = r->bufs.find(name);
@@ -1130,3 +1165,409 @@ int ofx_raft_buffer(const ofx_raft* r, const char* name, void** ptr, size_t* nfl
 }
 
 }  // extern "C"
+
+// ============================================================================================
+// The small network (raft-small.pth; RAFT/core/raft.py:29-33, :48-51): SmallEncoder feature / context networks
+// (extractor.py:195-267, bottleneck blocks :60-116), radius-3 lookup, SmallUpdateBlock (update.py:62-77, :99-112: a 3x3 ConvGRU,
+// no mask head) and upflow8 (utils/utils.py:80-82) in place of the convex upsample.  Everything runs on the general kernels the
+// basic network's schedule also uses (ofx_conv2d, ofx_inorm_*, the blocked volume + pool, ofx_corr_lookup's generic kernel,
+// ofx_local_corr) plus ofx_upflow8 / its warp form; every launch stays on the caller's stream (no side streams, no stop events).
+//
+//   encoders   preprocess -> 7x7/s2 conv (3 -> 32) -> 3 stages x 2 bottleneck blocks (32, 64, 96) -> 1x1 conv
+//              fnet: InstanceNorm2d without affine -- statistics pass + normalise/ReLU pass after each raw convolution;
+//              cnet: no norm at all -- ReLU and the residual add live in the convolution epilogues
+//   volume     D = 128 (scaled by 1 / sqrt(128)); the same batched GEMM + pooling kernels as the basic network
+//   iteration  lookup (4 x 49) -> convc1 -> convf1 -> convf2 -> conv -> zr -> q -> flow head (EPI_FLOW: coords1 += delta)
+//   tail       upflow8 (optionally with the warp of one shared frame) of the last iteration only
+namespace {
+
+constexpr int S_HD = 96, S_CD = 64, S_FD = 128, S_RADIUS = 3;
+constexpr int S_CORR_CH = LEVELS * (2 * S_RADIUS + 1) * (2 * S_RADIUS + 1);   // 196
+// convc1's operand row: 196 correlation features + 28 zeros (Kpad of a 1x1 conv over 196 channels is 224 anyway).  The generic
+// lookup writes only the features: the zeros are set once per forward (a NaN left in them times a zero weight would be NaN).
+constexpr int S_CORR_LD = 224;
+// hx row = [h(96) | inp(64) | motion(80) flow(2) | 14 zeros] = 256: the ConvGRU's cat([h, x]) (update.py:20-21) with
+// x = cat([inp, motion features]) (update.py:109); the zeros make x a whole number of 32-channel K chunks for the q convolution's
+// second segment (cat([r*h, x]), update.py:26).  The zeros are set once per forward.
+constexpr int S_HX_LD = 256, S_INP_OFF = S_HD, S_MOT_OFF = S_HD + S_CD, S_FLOW_OFF = S_MOT_OFF + 80;
+constexpr int S_X_CH = S_HX_LD - S_HD;   // 160
+
+struct SmallWs {
+    float *x0, *X, *Y, *T1, *T2, *T3, *Dn, *N1, *N2;   // encoder activations of one chunk
+    float* stats;      // 8 x [chunk][128]: mean / rstd of up to four norms
+    float* scratch;    // f64 partial sums of ofx_inorm_stats
+    float *fmap1, *fmap2, *f2l[LEVELS], *fmap2b, *ctx;
+    float* pyr[LEVELS];
+    float *hx, *coords1, *flow4, *corr, *corflo, *f1, *z, *rh, *fh;
+    void* warp_pad;
+    int nch;
+    size_t bytes;
+};
+
+SmallWs small_carve(void* base, size_t cap, int B, int H, int W, int flags, int n_images) {
+    SmallWs w{};
+    Carver c(base, cap);
+    const int h = H / 8, wd = W / 8;
+    const long N = (long)h * wd, M = (long)B * N;
+    const int most = n_images > 0 ? n_images : std::max(B, 1);
+    w.nch = std::min(enc_chunk(H, W), most);
+    const size_t act = (size_t)w.nch * (H / 2) * (W / 2) * 32;   // the widest activation: 32 channels at half resolution
+    w.x0 = c.take((size_t)w.nch * H * W * 4);
+    float** bufs[8] = {&w.X, &w.Y, &w.T1, &w.T2, &w.T3, &w.Dn, &w.N1, &w.N2};
+    for (float** b : bufs) *b = c.take(act);
+    w.stats = c.take((size_t)8 * w.nch * 128);
+    w.scratch = c.take((size_t)std::max(w.nch * 64, std::min(w.nch, 7) * 256) * 128 * 2 * 2);   // doubles (ofx.h: ofx_inorm_stats)
+    long n1 = (flags & OFX_RAFT_SHARED_IMG1) ? 1 : B, n2 = (flags & OFX_RAFT_SHARED_IMG2) ? 1 : B;
+    if (n_images > 0) {
+        n1 = n_images;
+        n2 = 0;
+        w.ctx = c.take((size_t)n_images * N * S_HX_LD);
+    }
+    w.fmap1 = c.take((size_t)n1 * N * S_FD);
+    w.fmap2 = n2 ? c.take((size_t)n2 * N * S_FD) : w.fmap1;
+    if (flags & OFX_RAFT_ALT_CORR) {
+        w.f2l[0] = w.fmap2;
+        for (int l = 1; l < LEVELS; ++l) w.f2l[l] = c.take((size_t)n2 * (h >> l) * (wd >> l) * S_FD);
+    } else {
+        w.fmap2b = c.take((size_t)(n_images > 0 ? n_images : n2) * ofx_corr_slice_floats_l(h, wd) * S_FD);
+        for (int l = 0; l < LEVELS; ++l) w.pyr[l] = c.take((size_t)M * ofx_corr_slice_floats_l(h >> l, wd >> l));
+    }
+    w.hx = c.take((size_t)M * S_HX_LD);
+    w.coords1 = c.take((size_t)M * 2);
+    w.flow4 = c.take((size_t)M * FROW);   // [M][4] flow operand of convf1 (EPI_FLOW); 16 floats a pixel: ofx_init_state zeroes that many
+    w.corr = c.take((size_t)M * S_CORR_LD);
+    w.corflo = c.take((size_t)M * 128);
+    w.f1 = c.take((size_t)M * 64);
+    w.z = c.take((size_t)M * S_HD);
+    w.rh = c.take((size_t)M * S_HD);
+    w.fh = c.take((size_t)M * 128);
+    w.warp_pad = c.take(ofx_warp_pad_bytes(H, W) / sizeof(float) + 4);
+    w.bytes = c.off;
+    return w;
+}
+
+// one SmallEncoder over n images (u8 [n][H][W][3]); out [n*h*w][out_ld].  instance: fnet ('instance', no affine), else cnet ('none');
+// tanh_rows > 0 (cnet): out rows [0, tanh_rows) = tanh, the rest = relu (raft.py:111-114)
+int small_encoder(ofx_raft* r, const char* enc, bool instance, const uint8_t* imgs, int n, int H, int W, int bgr, const SmallWs& ws, float* out,
+                  int out_ld, int tanh_rows, hipStream_t s) {
+    Launcher L{s};
+    auto C = [&](const std::string& k) -> const ConvW& { return r->convs[std::string(enc) + "." + k]; };
+    const int SC = ws.nch * 128;
+    float* mean[4] = {ws.stats, ws.stats + 2 * SC, ws.stats + 4 * SC, ws.stats + 6 * SC};
+    float* rstd[4] = {ws.stats + SC, ws.stats + 3 * SC, ws.stats + 5 * SC, ws.stats + 7 * SC};
+    auto stats = [&](const float* x, long HW, int ch, int k) {
+        if (!L.st) L.st = ofx_inorm_stats(x, ch, mean[k], rstd[k], ws.scratch, n, HW, ch, 1e-5f, s);
+    };
+    auto norm_relu = [&](const float* x, long HW, int ch, int k, float* o) {   // o = relu(inorm(x))
+        if (!L.st) L.st = ofx_inorm_apply(x, mean[k], rstd[k], nullptr, nullptr, nullptr, o, n, HW, ch, 1, s);
+    };
+    int st = ofx_preprocess_u8(imgs, ws.x0, (long)n * H * W, bgr, s);
+    if (st) return st;
+    float* X = ws.X;
+    float* Y = ws.Y;
+    int hin = H / 2, win = W / 2, cin = 32;
+    if (instance) {
+        L.conv(C("conv1"), ws.x0, 4, 4, nullptr, 0, 0, ws.T3, 32, n, H, W, 2, OFX_ACT_NONE);
+        stats(ws.T3, (long)hin * win, 32, 0);
+        norm_relu(ws.T3, (long)hin * win, 32, 0, X);
+    } else {
+        L.conv(C("conv1"), ws.x0, 4, 4, nullptr, 0, 0, X, 32, n, H, W, 2, OFX_ACT_RELU);
+    }
+    const int dims[3] = {32, 64, 96};
+    for (int li = 1; li <= 3; ++li) {
+        const int dim = dims[li - 1], mid = dim / 4;
+        for (int bi = 0; bi < 2; ++bi) {
+            const int stride = (li > 1 && bi == 0) ? 2 : 1;
+            const int ho = (hin - 1) / stride + 1, wo = (win - 1) / stride + 1;   // 3x3 pad 1 and 1x1 pad 0: the same output size
+            const long HWo = (long)ho * wo;
+            const std::string p = "layer" + std::to_string(li) + "." + std::to_string(bi);
+            if (instance) {
+                L.conv(C(p + ".conv1"), X, cin, cin, nullptr, 0, 0, ws.T1, mid, n, hin, win, 1, OFX_ACT_NONE);
+                stats(ws.T1, (long)hin * win, mid, 0);
+                norm_relu(ws.T1, (long)hin * win, mid, 0, ws.N1);
+                L.conv(C(p + ".conv2"), ws.N1, mid, mid, nullptr, 0, 0, ws.T2, mid, n, hin, win, stride, OFX_ACT_NONE);
+                stats(ws.T2, HWo, mid, 1);
+                norm_relu(ws.T2, HWo, mid, 1, ws.N2);
+                L.conv(C(p + ".conv3"), ws.N2, mid, mid, nullptr, 0, 0, ws.T3, dim, n, ho, wo, 1, OFX_ACT_NONE);
+                stats(ws.T3, HWo, dim, 2);
+                if (stride == 2) {   // relu(norm4(down(x)) + relu(norm3(conv3)))
+                    L.conv(C(p + ".down"), X, cin, cin, nullptr, 0, 0, ws.Dn, dim, n, hin, win, 2, OFX_ACT_NONE);
+                    stats(ws.Dn, HWo, dim, 3);
+                    if (!L.st) L.st = ofx_inorm_apply(ws.T3, mean[2], rstd[2], ws.Dn, mean[3], rstd[3], Y, n, HWo, dim, 1, s);
+                } else {             // relu(x + relu(norm3(conv3)))
+                    if (!L.st) L.st = ofx_inorm_apply(ws.T3, mean[2], rstd[2], X, nullptr, nullptr, Y, n, HWo, dim, 1, s);
+                }
+            } else {
+                L.conv(C(p + ".conv1"), X, cin, cin, nullptr, 0, 0, ws.T1, mid, n, hin, win, 1, OFX_ACT_RELU);
+                L.conv(C(p + ".conv2"), ws.T1, mid, mid, nullptr, 0, 0, ws.T2, mid, n, hin, win, stride, OFX_ACT_RELU);
+                const float* res = X;
+                if (stride == 2) {
+                    L.conv(C(p + ".down"), X, cin, cin, nullptr, 0, 0, ws.Dn, dim, n, hin, win, 2, OFX_ACT_NONE);
+                    res = ws.Dn;
+                }
+                // relu(x' + relu(conv3)): the residual merge of EPI_PLAIN
+                L.conv(C(p + ".conv3"), ws.T2, mid, mid, nullptr, 0, 0, Y, dim, n, ho, wo, 1, OFX_ACT_RELU, OFX_EPI_PLAIN, res, dim);
+            }
+            std::swap(X, Y);
+            hin = ho; win = wo; cin = dim;
+        }
+    }
+    const ConvW& c2 = C("conv2");
+    if (tanh_rows <= 0) {
+        L.conv(c2, X, 96, 96, nullptr, 0, 0, out, out_ld, n, hin, win, 1, OFX_ACT_NONE);
+    } else {
+        L.conv(c2, X, 96, 96, nullptr, 0, 0, out, out_ld, n, hin, win, 1, OFX_ACT_TANH, OFX_EPI_PLAIN, nullptr, 0, nullptr, nullptr, nullptr,
+               nullptr, nullptr, 0, nullptr, nullptr, 0, tanh_rows);
+        L.conv(c2, X, 96, 96, nullptr, 0, 0, out + tanh_rows, out_ld, n, hin, win, 1, OFX_ACT_RELU, OFX_EPI_PLAIN, nullptr, 0, nullptr, nullptr,
+               nullptr, nullptr, nullptr, 0, nullptr, nullptr, tanh_rows, c2.cout - tanh_rows);
+    }
+    return L.st;
+}
+
+// level 0 (and level 1 from the accumulators where the shape allows) of the volume of nz pairs: f1 rows [N][128] at a_zs floats per
+// pair, f2 in blocked row order [Nb][128] at w_zs per pair (zero strides broadcast a shared feature map); *fused tells the pooling
+// launch whether level 1 is already there
+int small_volume(const float* f1, long a_zs, const float* f2b, long w_zs, float* l0, float* l1, int nz, int h, int w, bool* fused,
+                 hipStream_t s) {
+    const long N = (long)h * w, Nb = ofx_corr_slice_floats_l(h, w), slice1 = ofx_corr_slice_floats_l(h >> 1, w >> 1);
+    ofx_conv_desc d{};
+    d.in0 = f1; d.ld0 = S_FD; d.c0 = S_FD;
+    d.w = f2b;
+    d.out = l0; d.ldo = (int)Nb;
+    d.nz = nz; d.a_zs = a_zs; d.w_zs = w_zs; d.o_zs = N * Nb;
+    d.B = 1; d.Hin = h; d.Win = w; d.Hout = h; d.Wout = w; d.Cout = (int)Nb;
+    d.KH = 1; d.KW = 1; d.stride = 1;
+    d.act = OFX_ACT_NONE; d.epi = OFX_EPI_PLAIN;
+    *fused = ofx_corr_volpool_ok(h, w) && Nb % 128 == 0 && N * slice1 * 4 < (1L << 31) - 64;
+    const float alpha = 1.0f / std::sqrt((float)S_FD);
+    if (*fused) return ofx_conv2d_volpool(&d, alpha, l1, N * slice1, (w + 7) >> 3, ((w >> 1) + 7) >> 3, (int)slice1, s);
+    return ofx_conv2d_alpha(&d, alpha, s);
+}
+
+// state init, `iters` refinement iterations of SmallUpdateBlock, upflow8 (with the warp of one shared frame for the first n_warp pairs)
+int small_recurrence(ofx_raft* r, const SmallWs& ws, int B, int h, int w, int iters, bool alt, float* flow_up, float* flow_low, uint8_t* warped,
+                     float warp_sign, int n_warp, hipStream_t s) {
+    const long N = (long)h * w, M = (long)B * N;
+    int st = ofx_init_state(ws.coords1, ws.flow4, ws.hx, S_HX_LD, S_FLOW_OFF, B, h, w, s);
+    if (st) return st;
+    OFX_HIP_CHECK(hipMemsetAsync(ws.corr, 0, (size_t)M * S_CORR_LD * sizeof(float), s));   // the 28 pad columns of every row
+    Launcher L{s};
+    auto C = [&](const char* k) -> const ConvW& { return r->convs[k]; };
+    const float* pyr_c[LEVELS] = {ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3]};
+    const int rd2 = (2 * S_RADIUS + 1) * (2 * S_RADIUS + 1);
+    for (int it = 0; it < iters && !L.st; ++it) {
+        if (!alt) {
+            L.st = ofx_corr_lookup(pyr_c, ws.coords1, ws.corr, S_CORR_LD, B, h, w, LEVELS, S_RADIUS, s);
+        } else {
+            for (int l = 0; l < LEVELS && !L.st; ++l)
+                L.st = ofx_local_corr_launch(ws.fmap1, ws.f2l[l], ws.coords1, ws.corr + (long)l * rd2, N * S_CORR_LD, 0, 1, S_CORR_LD, B, h, w,
+                                             h >> l, w >> l, S_FD, 1, S_RADIUS, 1.0f / std::sqrt((float)S_FD), 1.0f / (float)(1 << l), s);
+        }
+        // SmallMotionEncoder (update.py:70-77): cor_flo = [relu(convc1(corr)) (96) | relu(convf2(relu(convf1(flow)))) (32)]
+        L.conv(C("convc1"), ws.corr, S_CORR_LD, S_CORR_LD, nullptr, 0, 0, ws.corflo, 128, B, h, w, 1, OFX_ACT_RELU);
+        L.conv(C("convf1"), ws.flow4, 4, 4, nullptr, 0, 0, ws.f1, 64, B, h, w, 1, OFX_ACT_RELU);
+        L.conv(C("convf2"), ws.f1, 64, 64, nullptr, 0, 0, ws.corflo + 96, 128, B, h, w, 1, OFX_ACT_RELU);
+        L.conv(C("conv"), ws.corflo, 128, 128, nullptr, 0, 0, ws.hx + S_MOT_OFF, S_HX_LD, B, h, w, 1, OFX_ACT_RELU);
+        // ConvGRU (update.py:16-31): z | r in one convolution over cat([h, x]), q over cat([r*h, x]), h updated in place
+        L.conv(C("gru.zr"), ws.hx, S_HX_LD, S_HX_LD, nullptr, 0, 0, nullptr, 0, B, h, w, 1, OFX_ACT_NONE, OFX_EPI_GRU_ZR, nullptr, 0, nullptr,
+               nullptr, ws.z, ws.rh, ws.hx, S_HX_LD);
+        L.conv(C("gru.q"), ws.rh, S_HD, S_HD, ws.hx + S_INP_OFF, S_HX_LD, S_X_CH, nullptr, 0, B, h, w, 1, OFX_ACT_NONE, OFX_EPI_GRU_Q, nullptr,
+               0, nullptr, nullptr, ws.z, nullptr, ws.hx, S_HX_LD);
+        // FlowHead(96, 128) (update.py:6-14); coords1 += delta in the second convolution's epilogue (one rounding: delta, then the add),
+        // which also leaves the new flow in hx's flow slot and in convf1's operand
+        L.conv(C("fh1"), ws.hx, S_HX_LD, S_HD, nullptr, 0, 0, ws.fh, 128, B, h, w, 1, OFX_ACT_RELU);
+        L.conv(C("fh2"), ws.fh, 128, 128, nullptr, 0, 0, nullptr, 0, B, h, w, 1, OFX_ACT_NONE, OFX_EPI_FLOW, nullptr, 0, nullptr, nullptr,
+               nullptr, nullptr, ws.hx + S_FLOW_OFF, S_HX_LD, ws.coords1, ws.flow4);
+    }
+    if (L.st) return L.st;
+    // upflow8 of the last iteration only (raft.py:134-135; test_mode returns the last prediction)
+    const int nw = warped ? (n_warp < 0 ? B : std::min(n_warp, B)) : 0;
+    if (nw > 0) st = ofx_upflow8_warp_launch(ws.coords1, flow_up, ws.warp_pad, warped, nw, h, w, warp_sign, s);
+    if (!st && nw < B) {
+        if (!flow_up) return OFX_EINVAL;
+        st = ofx_upflow8(ws.coords1 + (long)nw * N * 2, flow_up + (long)nw * N * 128, B - nw, h, w, s);
+    }
+    if (st) return st;
+    if (flow_low) return ofx_coords_to_flow(ws.coords1, flow_low, B, h, w, s);
+    return 0;
+}
+
+// the split-bf16 modes have no small-network form: its convolutions and its D = 128 volume run in exact fp32 only
+constexpr int S_UNSUPPORTED = OFX_RAFT_BF16X3 | OFX_RAFT_BF16X6 | OFX_RAFT_VOL_BF16X3 | OFX_RAFT_VOL_BF16X6;
+
+void small_register(ofx_raft* r, const SmallWs& ws, long n1, long n2, long M, int h, int w, bool alt) {
+    r->bufs.clear();
+    const long N = (long)h * w;
+    auto reg = [&](const char* k, float* p, size_t nf) { r->bufs[k] = std::make_pair((void*)p, nf); };
+    reg("fmap1", ws.fmap1, (size_t)n1 * N * S_FD);
+    reg("fmap2", ws.fmap2, (size_t)n2 * N * S_FD);
+    reg("hx", ws.hx, (size_t)M * S_HX_LD);            // rows of 256: h (96) | inp (64) | motion (80) | flow (2) | zeros
+    reg("coords1", ws.coords1, (size_t)M * 2);
+    reg("corr", ws.corr, (size_t)M * S_CORR_LD);      // rows of 224: 196 features + 28 zeros
+    if (!alt)
+        for (int l = 0; l < LEVELS; ++l) {
+            char nm[8];
+            snprintf(nm, sizeof nm, "pyr%d", l);
+            reg(nm, ws.pyr[l], (size_t)M * ofx_corr_slice_floats_l(h >> l, w >> l));
+        }
+}
+
+}  // namespace
+
+// 0 = basic, 1 = small, OFX_EKEY = neither, or keys of both
+static int small_detect(const std::map<std::string, HostTensor>& sd) {
+    auto has = [&](const char* k) { return sd.count(k) > 0; };
+    const bool small = has("update_block.gru.convz.weight") && has("fnet.layer1.0.conv3.weight");
+    const bool basic_marks = has("update_block.gru.convz1.weight") || has("update_block.mask.0.weight") ||
+                             has("update_block.encoder.convc2.weight") || has("cnet.norm1.weight");
+    const bool small_marks = has("update_block.gru.convz.weight") || has("fnet.layer1.0.conv3.weight") || has("cnet.layer1.0.conv3.weight");
+    if (small && !basic_marks) return 1;
+    if (small_marks) return OFX_EKEY;
+    return 0;
+}
+
+static int small_build(ofx_raft* r, const std::map<std::string, HostTensor>& sd) {
+    for (const char* enc : {"fnet", "cnet"}) {
+        const std::string e = enc;
+        int st = add_conv(r, sd, e + ".conv1", e + ".conv1", 4, "", 1.f);
+        if (st) return st;
+        for (int li = 1; li <= 3; ++li)
+            for (int bi = 0; bi < 2; ++bi) {
+                const std::string p = e + ".layer" + std::to_string(li) + "." + std::to_string(bi);
+                for (const char* cv : {".conv1", ".conv2", ".conv3"}) {
+                    st = add_conv(r, sd, p + cv, p + cv, 0, "", 1.f);
+                    if (st) return st;
+                }
+                if (li > 1 && bi == 0) {
+                    st = add_conv(r, sd, p + ".downsample.0", p + ".down", 0, "", 1.f);
+                    if (st) return st;
+                }
+            }
+        st = add_conv(r, sd, e + ".conv2", e + ".conv2", 0, "", 1.f);
+        if (st) return st;
+    }
+    const ConvW& fo = r->convs["fnet.conv2"];
+    const ConvW& co = r->convs["cnet.conv2"];
+    if (fo.cout != S_FD || fo.cin != 96 || co.cout != S_HD + S_CD || co.cin != 96) return OFX_EKEY;
+    const std::string ub = "update_block.";
+    int st = add_conv(r, sd, ub + "encoder.convc1", "convc1", S_CORR_LD, "", 1.f);
+    if (!st && (r->convs["convc1"].cin != S_CORR_CH || r->convs["convc1"].cout != 96)) st = OFX_EKEY;
+    if (!st) st = add_conv(r, sd, ub + "encoder.convf1", "convf1", 4, "", 1.f);   // 7x7 over the [M][4] flow operand (channels 2, 3 zero)
+    if (!st) st = add_conv(r, sd, ub + "encoder.convf2", "convf2", 0, "", 1.f);
+    if (!st) st = add_conv(r, sd, ub + "encoder.conv", "conv", 0, "", 1.f);
+    if (!st && (r->convs["conv"].cout != 80 || r->convs["convf2"].cout != 32)) st = OFX_EKEY;
+    if (!st) {   // z and r share their input: one convolution with Cout = 192 ([convz ; convr] rows), input rows padded 242 -> 256
+        std::vector<float> wzr, shzr;
+        st = add_conv(r, sd, ub + "gru.convz", "gru.z", S_HX_LD, "", 1.f, &wzr, &shzr);
+        if (!st) st = add_conv(r, sd, ub + "gru.convr", "gru.r", S_HX_LD, "", 1.f, &wzr, &shzr);
+        if (!st) {
+            ConvW c = r->convs["gru.z"];
+            if (c.cout != S_HD || c.cin != S_HX_LD - 14 || c.kh != 3 || c.kw != 3) return OFX_EKEY;
+            c.cout *= 2;
+            st = upload_weight(r, wzr, &c);
+            if (!st) st = upload(r, shzr, &c.shift);
+            c.name = "gru.zr";
+            r->convs["gru.zr"] = c;
+        }
+    }
+    if (!st) st = add_conv(r, sd, ub + "gru.convq", "gru.q", S_HX_LD, "", 1.f);
+    if (!st) st = add_conv(r, sd, ub + "flow_head.conv1", "fh1", 0, "", 1.f);
+    if (!st) st = add_conv(r, sd, ub + "flow_head.conv2", "fh2", 0, "", 1.f);
+    if (!st && (r->convs["fh1"].cin != S_HD || r->convs["fh2"].cout != 2)) st = OFX_EKEY;
+    return st;
+}
+
+static size_t small_workspace_bytes(int B, int H, int W, int n_images) {
+    if (n_images > 0) return small_carve(nullptr, 0, B, H, W, 0, n_images).bytes;
+    const size_t a = small_carve(nullptr, 0, B, H, W, 0, 0).bytes, b = small_carve(nullptr, 0, B, H, W, OFX_RAFT_ALT_CORR, 0).bytes;
+    return a > b ? a : b;
+}
+
+static int small_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* image2, int B, int H, int W, int iters, int flags,
+                              float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign, uint8_t* warped, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    OFX_REQUIRE(r && image1 && image2 && (flow_up || warped) && workspace, OFX_EINVAL);
+    OFX_REQUIRE(B > 0 && H >= 64 && W >= 64 && (H % 8) == 0 && (W % 8) == 0 && iters >= 1, OFX_EINVAL);
+    OFX_REQUIRE(!(flags & S_UNSUPPORTED), OFX_EINVAL);
+    OFX_REQUIRE((((uintptr_t)workspace) & 255u) == 0, OFX_EALIGN);
+    const bool sh1 = flags & OFX_RAFT_SHARED_IMG1, sh2 = flags & OFX_RAFT_SHARED_IMG2, alt = flags & OFX_RAFT_ALT_CORR;
+    OFX_REQUIRE(!(alt && (sh1 || sh2)), OFX_EINVAL);   // alt-corr path: per-pair feature maps only (as for the basic network)
+    SmallWs ws = small_carve(workspace, workspace_bytes, B, H, W, flags, 0);
+    OFX_REQUIRE(ws.bytes <= workspace_bytes, OFX_ENOMEM);
+    hipStream_t s = (hipStream_t)stream;
+    const int h = H / 8, w = W / 8, bgr = (flags & OFX_RAFT_BGR) ? 1 : 0;
+    const long N = (long)h * w, M = (long)B * N, img_bytes = (long)H * W * 3;
+    const int n1 = sh1 ? 1 : B, n2 = sh2 ? 1 : B;
+    int st = 0;
+    OFX_HIP_CHECK(hipMemsetAsync(ws.hx, 0, (size_t)M * S_HX_LD * sizeof(float), s));   // the 14 pad columns of every row
+    for (int i0 = 0; i0 < n1 && !st; i0 += ws.nch)
+        st = small_encoder(r, "fnet", true, image1 + i0 * img_bytes, std::min(ws.nch, n1 - i0), H, W, bgr, ws, ws.fmap1 + (long)i0 * N * S_FD, S_FD,
+                           0, s);
+    for (int i0 = 0; i0 < n2 && !st; i0 += ws.nch)
+        st = small_encoder(r, "fnet", true, image2 + i0 * img_bytes, std::min(ws.nch, n2 - i0), H, W, bgr, ws, ws.fmap2 + (long)i0 * N * S_FD, S_FD,
+                           0, s);
+    // context network on image1 -> hx[:, 0:96] = tanh (net), hx[:, 96:160] = relu (inp)
+    for (int i0 = 0; i0 < n1 && !st; i0 += ws.nch)
+        st = small_encoder(r, "cnet", false, image1 + i0 * img_bytes, std::min(ws.nch, n1 - i0), H, W, bgr, ws, ws.hx + (long)i0 * N * S_HX_LD,
+                           S_HX_LD, S_HD, s);
+    for (int k = 1; k < B && !st && sh1; ++k)   // one shared image1: replicate its context rows
+        OFX_HIP_CHECK(hipMemcpyAsync(ws.hx + (long)k * N * S_HX_LD, ws.hx, (size_t)N * S_HX_LD * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (st) return st;
+    if (!alt) {
+        bool fused = false;
+        const long Nb = ofx_corr_slice_floats_l(h, w);
+        st = ofx_corr_block_rows(ws.fmap2, ws.fmap2b, n2, h, w, S_FD, s);
+        if (!st) st = small_volume(ws.fmap1, sh1 ? 0 : N * S_FD, ws.fmap2b, sh2 ? 0 : Nb * S_FD, ws.pyr[0], ws.pyr[1], B, h, w, &fused, s);
+        if (!st) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused);
+    } else {
+        for (int l = 1; l < LEVELS && !st; ++l) st = ofx_avgpool2_nhwc(ws.f2l[l - 1], ws.f2l[l], n2, h >> (l - 1), w >> (l - 1), S_FD, s);
+    }
+    if (!st && warped) st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
+    if (!st) st = small_recurrence(r, ws, B, h, w, iters, alt, flow_up, flow_low, warped, warp_sign, -1, s);
+    if (st) return st;
+    small_register(r, ws, n1, n2, M, h, w, alt);
+    return 0;
+}
+
+static int small_forward_pairs_impl(ofx_raft* r, const uint8_t* images, int n_images, const int* idx1, const int* idx2, int B, int H, int W,
+                                    int iters, int flags, float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign,
+                                    int n_warp, uint8_t* warped, void* workspace, size_t workspace_bytes, void* stream) {
+    if (warped || warp_frame || n_warp) {
+        OFX_REQUIRE(warp_frame && warped && n_warp > 0 && n_warp <= B && (warp_sign == 1.0f || warp_sign == -1.0f), OFX_EINVAL);
+        OFX_REQUIRE(ofx_upsample_warp_ok(n_warp, H, W) && (((uintptr_t)warped) & 3u) == 0, OFX_EINVAL);
+    }
+    OFX_REQUIRE(n_images > 0 && B > 0 && H >= 64 && W >= 64 && (H % 8) == 0 && (W % 8) == 0 && iters >= 1, OFX_EINVAL);
+    OFX_REQUIRE(!(flags & (OFX_RAFT_ALT_CORR | OFX_RAFT_SHARED_IMG1 | OFX_RAFT_SHARED_IMG2 | S_UNSUPPORTED)), OFX_EINVAL);
+    OFX_REQUIRE((((uintptr_t)workspace) & 255u) == 0, OFX_EALIGN);
+    for (int b = 0; b < B; ++b)
+        OFX_REQUIRE(idx1[b] >= 0 && idx1[b] < n_images && idx2[b] >= 0 && idx2[b] < n_images, OFX_EINVAL);
+    SmallWs ws = small_carve(workspace, workspace_bytes, B, H, W, 0, n_images);
+    OFX_REQUIRE(ws.bytes <= workspace_bytes, OFX_ENOMEM);
+    hipStream_t s = (hipStream_t)stream;
+    const int h = H / 8, w = W / 8, bgr = (flags & OFX_RAFT_BGR) ? 1 : 0;
+    const long N = (long)h * w, img_bytes = (long)H * W * 3;
+    int st = 0;
+    // every image is encoded once (feature + context network), however many pairs it takes part in; its context rows are laid out as
+    // the hx rows they are copied into (pad columns zero)
+    OFX_HIP_CHECK(hipMemsetAsync(ws.ctx, 0, (size_t)n_images * N * S_HX_LD * sizeof(float), s));
+    for (int i0 = 0; i0 < n_images && !st; i0 += ws.nch) {
+        const int n = std::min(ws.nch, n_images - i0);
+        st = small_encoder(r, "fnet", true, images + i0 * img_bytes, n, H, W, bgr, ws, ws.fmap1 + (long)i0 * N * S_FD, S_FD, 0, s);
+        if (!st) st = small_encoder(r, "cnet", false, images + i0 * img_bytes, n, H, W, bgr, ws, ws.ctx + (long)i0 * N * S_HX_LD, S_HX_LD, S_HD, s);
+    }
+    for (int b = 0; b < B && !st; ++b)
+        OFX_HIP_CHECK(hipMemcpyAsync(ws.hx + (long)b * N * S_HX_LD, ws.ctx + (long)idx1[b] * N * S_HX_LD, (size_t)N * S_HX_LD * sizeof(float),
+                                     hipMemcpyDeviceToDevice, s));
+    const long Nb = ofx_corr_slice_floats_l(h, w), slice1 = ofx_corr_slice_floats_l(h >> 1, w >> 1);
+    if (!st) st = ofx_corr_block_rows(ws.fmap1, ws.fmap2b, n_images, h, w, S_FD, s);   // every image can be an image2
+    bool fused = false;
+    for (int b = 0; b < B && !st; ++b)   // one correlation GEMM per pair, straight from the shared feature maps
+        st = small_volume(ws.fmap1 + (long)idx1[b] * N * S_FD, 0, ws.fmap2b + (long)idx2[b] * Nb * S_FD, 0, ws.pyr[0] + (long)b * N * Nb,
+                          ws.pyr[1] + (long)b * N * slice1, 1, h, w, &fused, s);
+    if (!st) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused);
+    if (!st && warped) st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
+    if (!st) st = small_recurrence(r, ws, B, h, w, iters, false, flow_up, flow_low, warped, warp_sign, n_warp, s);
+    if (st) return st;
+    r->bufs.clear();
+    return 0;
+}

@@ -87,3 +87,64 @@ __device__ __forceinline__ void ofx_upsample_store(const OfxUpLane& o, float* __
     d[0] = make_float4(o.ax.x, o.ay.x, o.ax.y, o.ay.y);
     d[1] = make_float4(o.ax.z, o.ay.z, o.ax.w, o.ay.w);
 }
+
+// Bilinear 8x upsample of the flow with align_corners = True, times 8 (upflow8, RAFT/core/utils/utils.py:80-82: the small
+// network's upsample, raft.py:134-135) for ONE thread: four consecutive fine pixels (X .. X+3, X % 4 == 0) of fine row Y of image b,
+// returned as (fx0, fy0, fx1, fy1) | (fx2, fy2, fx3, fy3) -- the layout of flow_up and of the warp's flow operand.  Shared by the
+// plain kernel (net_misc.hip) and the upsample + warp kernel (warp_fast.hip) so that both produce the same bits.
+// Source position as F.interpolate computes it: src = dst * (in - 1) / (out - 1) with the scale rounded to fp32 first, i0 = floor,
+// i1 = min(i0 + 1, in - 1), lambda = src - i0; value = (1 - ly) * ((1 - lx) v00 + lx v01) + ly * ((1 - lx) v10 + lx v11).
+struct OfxUp8Group {
+    bool valid;
+    long b;
+    int Y, X;
+    float4 fa, fb;
+};
+
+__device__ __forceinline__ float2 ofx_up8_flow_at(const float* __restrict__ coords1, long base, int w, int yy, int xx) {
+    const float2 c = reinterpret_cast<const float2*>(coords1)[base + (long)yy * w + xx];
+    return make_float2(c.x - (float)xx, c.y - (float)yy);   // coords1 - coords0
+}
+
+__device__ __forceinline__ OfxUp8Group ofx_upflow8_group(const float* __restrict__ coords1, int B, int h, int w, long g) {
+    OfxUp8Group o;
+    const int W4 = 2 * w;                                          // groups of 4 fine pixels per fine row (8w / 4)
+    const long rows = (long)B * h * 8;
+    o.valid = g < rows * W4;
+    if (!o.valid) return o;
+    const long row = g / W4;                                       // b * 8h + Y
+    o.X = (int)(g - row * W4) * 4;
+    o.Y = (int)(row % (8 * h));
+    o.b = row / (8 * h);
+    const float sy = h > 1 ? (float)(h - 1) / (float)(8 * h - 1) : 0.f;
+    const float sx = w > 1 ? (float)(w - 1) / (float)(8 * w - 1) : 0.f;
+    const float ry = __fmul_rn(sy, (float)o.Y);
+    const int y0 = (int)ry;
+    const int y1 = y0 + (y0 < h - 1 ? 1 : 0);
+    const float ly = ry - (float)y0, gy = 1.f - ly;
+    const long base = o.b * h * w;
+    float fx[4], fy[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float rx = __fmul_rn(sx, (float)(o.X + k));
+        const int x0 = (int)rx;
+        const int x1 = x0 + (x0 < w - 1 ? 1 : 0);
+        const float lx = rx - (float)x0, gx = 1.f - lx;
+        const float2 v00 = ofx_up8_flow_at(coords1, base, w, y0, x0), v01 = ofx_up8_flow_at(coords1, base, w, y0, x1);
+        const float2 v10 = ofx_up8_flow_at(coords1, base, w, y1, x0), v11 = ofx_up8_flow_at(coords1, base, w, y1, x1);
+        // every rounding spelled out (no contraction left to the compiler): the two kernels that inline this must agree bit for bit
+        const float tx = __builtin_fmaf(lx, v01.x, __fmul_rn(gx, v00.x)), bx = __builtin_fmaf(lx, v11.x, __fmul_rn(gx, v10.x));
+        const float ty = __builtin_fmaf(lx, v01.y, __fmul_rn(gx, v00.y)), by = __builtin_fmaf(lx, v11.y, __fmul_rn(gx, v10.y));
+        fx[k] = __fmul_rn(8.0f, __builtin_fmaf(ly, bx, __fmul_rn(gy, tx)));
+        fy[k] = __fmul_rn(8.0f, __builtin_fmaf(ly, by, __fmul_rn(gy, ty)));
+    }
+    o.fa = make_float4(fx[0], fy[0], fx[1], fy[1]);
+    o.fb = make_float4(fx[2], fy[2], fx[3], fy[3]);
+    return o;
+}
+
+__device__ __forceinline__ void ofx_upflow8_store(const OfxUp8Group& o, float* __restrict__ flow_up, int h, int w) {
+    float4* d = reinterpret_cast<float4*>(flow_up + 2 * ((o.b * h * 8 + o.Y) * (long)(8 * w) + o.X));
+    d[0] = o.fa;
+    d[1] = o.fb;
+}

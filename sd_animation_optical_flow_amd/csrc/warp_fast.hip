@@ -138,6 +138,16 @@ __global__ __launch_bounds__(256) void upsample_warp_kernel(const float* __restr
     warp_group(a, row, X, Y, make_float4(o.ax.x, o.ay.x, o.ax.y, o.ay.y), make_float4(o.ax.z, o.ay.z, o.ax.w, o.ay.w));
 }
 
+// ---- upflow8 (the small network's bilinear upsample) + warp in one pass: the same arrangement as above, for four fine pixels of one
+// fine row per thread; the same arithmetic as upflow8_kernel (net_misc.hip) followed by warp_bilinear_shared_kernel.
+__global__ __launch_bounds__(256) void upflow8_warp_kernel(const float* __restrict__ coords1, float* __restrict__ flow_up, const FastArgs a,
+                                                           int B, int h, int w) {
+    const OfxUp8Group o = ofx_upflow8_group(coords1, B, h, w, (long)blockIdx.x * 256 + threadIdx.x);
+    if (!o.valid) return;
+    if (flow_up) ofx_upflow8_store(o, flow_up, h, w);
+    warp_group(a, (unsigned)(o.b * a.H + o.Y), o.X, o.Y, o.fa, o.fb);
+}
+
 }  // namespace
 
 // zero-bordered RGBX copy of a key frame for the bilinear warp: `pad` holds (H + 4) * (W + 4) uint32
@@ -173,7 +183,40 @@ int ofx_upsample_warp_launch(const float* coords1, const float* mask, float* flo
     return ofx_launch_status();
 }
 
+// coords1 [B*h*w][2] -> warped u8 [B, 8h, 8w, 3] (and flow_up f32 [B, 8h, 8w, 2] unless NULL) through upflow8; `pad` from ofx_warp_pad_launch
+int ofx_upflow8_warp_launch(const float* coords1, float* flow_up, const void* pad, uint8_t* warped, int B, int h, int w, float sign, hipStream_t s) {
+    const int H = h * 8, W = w * 8;
+    OFX_REQUIRE(coords1 && pad && warped && ofx_upsample_warp_ok(B, H, W), OFX_EINVAL);
+    OFX_REQUIRE((((uintptr_t)coords1) & 7u) == 0 && (!flow_up || ofx_aligned16(flow_up)) && (((uintptr_t)warped) & 3u) == 0, OFX_EALIGN);
+    const long groups = (long)B * H * (W / 4);
+    OFX_REQUIRE((groups + 255) / 256 < (1L << 31), OFX_EINVAL);
+    const int Wp = W + 2 * kPad;
+    FastArgs a;
+    a.pad = (const uint32_t*)pad + (size_t)kPad * Wp + kPad;
+    a.flow = nullptr; a.out = warped;
+    a.H = H; a.W = W; a.Wp = Wp;
+    a.sign = sign;
+    OfxProfScope prof("upflow8_warp", s);
+    hipLaunchKernelGGL(upflow8_warp_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, coords1, flow_up, a, B, h, w);
+    return ofx_launch_status();
+}
+
 extern "C" {
+
+// upflow8 (RAFT/core/utils/utils.py:80-82, the small network's upsample) + the bilinear backward warp of ONE shared uint8 RGB frame in one
+// kernel: coords1 [B*h*w][2]; frame u8 [8h][8w][3]; warped u8 [B][8h][8w][3]; flow_up f32 [B][8h][8w][2] or NULL (not written).
+// Bit-identical to ofx_upflow8 followed by ofx_warp_u8(bilinear) with frame_bstride = 0.
+int ofx_upflow8_warp(const float* coords1, float* flow_up, const uint8_t* frame, uint8_t* warped, int B, int h, int w, float sign, void* stream) {
+    OFX_REQUIRE(coords1 && frame && warped && B > 0 && h > 0 && w > 0, OFX_EINVAL);
+    OFX_REQUIRE(ofx_upsample_warp_ok(B, h * 8, w * 8), OFX_EINVAL);
+    hipStream_t s = (hipStream_t)stream;
+    void* pad = nullptr;
+    OFX_HIP_CHECK(hipMallocAsync(&pad, ofx_warp_pad_bytes(h * 8, w * 8), s));
+    int st = ofx_warp_pad_launch(frame, pad, h * 8, w * 8, s);
+    if (!st) st = ofx_upflow8_warp_launch(coords1, flow_up, pad, warped, B, h, w, sign, s);
+    const hipError_t e = hipFreeAsync(pad, s);
+    return st ? st : (int)e;
+}
 
 // RAFT.upsample_flow (raft.py:72-83) + the bilinear backward warp of ONE shared uint8 RGB frame (pdcnet_of.py:34-42 in its bilinear
 // mode; sign = +1: out(y,x) = frame(y + fy, x + fx), -1: the RAFT-side convention of ofgen_keyframe_inpaint.py:92-98) in one kernel.

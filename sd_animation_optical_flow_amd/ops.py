@@ -462,6 +462,31 @@ def upsample_flow_warp(coords1: torch.Tensor, mask: torch.Tensor, frame: torch.T
     return flow, warped
 
 
+def upflow8(coords1: torch.Tensor) -> torch.Tensor:
+    """The small network's upsample (upflow8, RAFT/core/utils/utils.py:80-82): coords1 f32 [B,h,w,2] -> flow_up f32 [B,8h,8w,2] =
+    8 * F.interpolate(coords1 - coords0, (8h, 8w), mode='bilinear', align_corners=True), channels-last."""
+    c = _chk(coords1, "coords1", torch.float32)
+    B, h, w, _ = c.shape
+    out = torch.empty((B, 8 * h, 8 * w, 2), dtype=torch.float32, device=c.device)
+    check(_lib.lib().ofx_upflow8(_ptr(c), _ptr(out), B, h, w, _stream()), "ofx_upflow8")
+    return out
+
+
+def upflow8_warp(coords1: torch.Tensor, frame: torch.Tensor, sign: float = 1.0, want_flow: bool = True):
+    """upflow8 + the bilinear backward warp of one shared uint8 frame [8h,8w,3] in ONE kernel.
+    coords1 f32 [B,h,w,2] -> (flow_up f32 [B,8h,8w,2] or None, warped u8 [B,8h,8w,3])."""
+    c = _chk(coords1, "coords1", torch.float32)
+    fr = _chk(frame, "frame", torch.uint8)
+    B, h, w, _ = c.shape
+    if tuple(fr.shape) != (8 * h, 8 * w, 3):
+        raise RuntimeError("shapes: coords1 [B,h,w,2], frame [8h,8w,3]")
+    flow = torch.empty((B, 8 * h, 8 * w, 2), dtype=torch.float32, device=c.device) if want_flow else None
+    warped = torch.empty((B, 8 * h, 8 * w, 3), dtype=torch.uint8, device=c.device)
+    check(_lib.lib().ofx_upflow8_warp(_ptr(c), _ptr(flow) if want_flow else C.c_void_p(0), _ptr(fr), _ptr(warped), B, h, w, float(sign),
+                                      _stream()), "ofx_upflow8_warp")
+    return flow, warped
+
+
 def corr_lookup(pyr: Sequence[torch.Tensor], coords: torch.Tensor, B: int, h: int, w: int, radius: int = 4) -> torch.Tensor:
     """coords f32 [B,h,w,2] (x,y) -> [B,h,w,L*(2r+1)^2] (channels-last version of CorrBlock.__call__)."""
     c = _chk(coords, "coords", torch.float32)

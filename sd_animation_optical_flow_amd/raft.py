@@ -1,7 +1,8 @@
 """Python handle of the native RAFT engine (csrc/raft_engine.cpp).
 
 `RaftEngine(state_dict)` packs and uploads the weights once (state_dict keys are the reference
-checkpoint's, `raft-things.pth` loads unchanged -- `module.` prefixes are accepted);
+checkpoint's, `raft-things.pth` and `raft-small.pth` load unchanged -- `module.` prefixes are accepted; the key set
+selects the network, `.variant`);
 `forward(image1, image2)` runs `RAFT.forward(iters=20, test_mode=True)` (RAFT/core/raft.py:86-144)
 for a batch of uint8 frame pairs resident on the GPU and returns flow f32[B,H,W,2] on the GPU.
 """
@@ -15,12 +16,15 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check
+from .weights import raft_variant
 
 FLAG_BGR, FLAG_SHARED_IMG2, FLAG_SHARED_IMG1, FLAG_ALT_CORR, FLAG_BF16X3, FLAG_SERIAL, FLAG_BF16X6, FLAG_BN_BATCH, FLAG_SEPARATE_STATS = 1, 2, 4, 8, 16, 32, 64, 128, 256
 CNET_NORMS = {"eval": 0, "batch": FLAG_BN_BATCH}
 PRECISIONS = {"fp32": 0, "bf16x3": FLAG_BF16X3, "bf16x6": FLAG_BF16X6}
 FLAG_VOL_BF16X3, FLAG_VOL_BF16X6 = 512, 1024
 VOLUME_PRECISIONS = {None: 0, "fp32": 0, "bf16x3": FLAG_VOL_BF16X3, "bf16x6": FLAG_VOL_BF16X6}
+# floats of the widest row a convolution of one executor call addresses, per network (see pairs_per_call)
+ROW_FLOATS = {"basic": 768, "small": 256}
 
 
 class RaftEngine:
@@ -41,7 +45,17 @@ class RaftEngine:
         products, fp32 accumulate: fp32-level accuracy on the bf16 matrix cores).
         volume_precision: None / 'fp32' (default), 'bf16x3' or 'bf16x6' -- the arithmetic of the all-pairs correlation volume ALONE
         (RAFT/core/corr.py:52-60), every convolution stays exact fp32: the GEMM runs on the bf16 matrix cores from operands pre-split
-        into bf16 planes (csrc/corr_split.hip; needs H % 64 == 0 and W % 128 == 0, other shapes silently take the fp32 GEMM)."""
+        into bf16 planes (csrc/corr_split.hip; needs H % 64 == 0 and W % 128 == 0, other shapes silently take the fp32 GEMM).
+
+        THE SMALL NETWORK (`raft-small.pth`, RAFT/core/raft.py:29-33): a state_dict with its key set builds it (`.variant == 'small'`;
+        `weights.raft_variant` decides, the C side checks again).  It has no BatchNorm, so `cnet_norm` is ignored for it; it runs in
+        exact fp32 only -- precision / volume_precision other than 'fp32' raise ValueError -- and every launch stays on the current
+        stream (`serial` is implied)."""
+        self.variant = raft_variant(state_dict)
+        if self.variant == "small" and precision != "fp32":
+            raise ValueError("the small RAFT network runs in exact fp32 only (precision='fp32')")
+        if self.variant == "small" and volume_precision not in (None, "fp32"):
+            raise ValueError("the small RAFT network's correlation volume (D = 128) runs in exact fp32 only (volume_precision=None / 'fp32')")
         if volume_precision not in VOLUME_PRECISIONS:
             raise ValueError("volume_precision must be None, 'fp32', 'bf16x3' or 'bf16x6'")
         self.volume_precision = volume_precision
@@ -77,6 +91,8 @@ class RaftEngine:
         with torch.cuda.device(self.device):
             check(L.ofx_raft_create(arr, n, C.byref(h)), "ofx_raft_create")
         self._h = h
+        assert L.ofx_raft_variant(h) == (1 if self.variant == "small" else 0)
+        self._row_floats = ROW_FLOATS[self.variant]
         self._ws: Optional[torch.Tensor] = None
         self._ws_key: Optional[Tuple[int, int, int]] = None
         self.ws_budget_bytes: Optional[int] = None     # see pairs_that_fit
@@ -128,7 +144,8 @@ class RaftEngine:
         """`max_pairs` further bounded by the device memory that is free right now, for the indexed-pairs calls (`forward_pairs`:
         every pair may bring two images of its own -- the bound assumes so): what `pdcnet_of` slices its batches by."""
         L = _lib.lib()
-        B = self.max_pairs(H, W) if limit is None else max(1, min(int(limit), self.max_pairs(H, W)))
+        cap = self.pairs_per_call(H, W)
+        B = cap if limit is None else max(1, min(int(limit), cap))
         Hp, Wp = (H + 7) // 8 * 8, (W + 7) // 8 * 8
         need = lambda b: L.ofx_raft_workspace_bytes_pairs(self._h, 2 * b, b, Hp, Wp)
         budget = self.ws_budget_bytes
@@ -155,6 +172,13 @@ class RaftEngine:
         32-bit byte offsets (buffer descriptors), so the widest array (the 768-float row of the hoisted GRU context
         term) must stay below 2 GiB.  Larger batches are processed in slices (pairs are independent)."""
         return max(1, ((1 << 31) - 4096) // (((H + 7) // 8) * ((W + 7) // 8) * 768 * 4))
+
+    def pairs_per_call(self, H: int, W: int) -> int:
+        """`max_pairs` for this engine's network: the basic network's is `max_pairs` itself; the small network's widest
+        convolution operand is its 256-float GRU row (ROW_FLOATS), three times as many pairs."""
+        if self.variant == "basic":
+            return self.max_pairs(H, W)
+        return max(1, ((1 << 31) - 4096) // (((H + 7) // 8) * ((W + 7) // 8) * self._row_floats * 4))
 
     @staticmethod
     def pad_to_8(img: torch.Tensor) -> torch.Tensor:
@@ -217,7 +241,7 @@ class RaftEngine:
             warp_frame = warp_frame.contiguous()
         elif not want_flow:
             raise ValueError("want_flow=False only makes sense together with warp_frame")
-        max_pairs = self.max_pairs(H, W)
+        max_pairs = self.pairs_per_call(H, W)
         if B > 1:
             max_pairs = min(max_pairs, self.pairs_that_fit(min(B, max_pairs), H, W))
         if B > max_pairs:
