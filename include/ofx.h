@@ -355,6 +355,16 @@ int ofx_upflow8_warp(const float* coords1, float* flow_up, const uint8_t* frame,
 int ofx_flow_head(const float* x, int ldx, const float* w, int kpad, const float* bias, float* coords1, float* hx_flow,
                   int ldh, float* frows, int B, int h, int w_, void* stream);
 
+/* forward_interpolate of RAFT/core/utils/utils.py:26-53 (the warm start of a video chain, OFX_RAFT_FLOW_INIT): flow f32[B,h,w,2] ->
+ * out f32[B,h,w,2] (the flow_low layout; fields independent; out must not be flow).  Every pixel (x0, y0) is a source at
+ * (x1, y1) = (x0 + dx, y0 + dy) in float64, valid iff 0 < x1 < w and 0 < y1 < h (strict); every output pixel takes the (dx, dy) of
+ * the valid source nearest to its integer position by the float64 squared distance (x1-x0)^2 + (y1-y0)^2 (no FMA) -- scipy's
+ * griddata(method='nearest').  Ties: the lowest source index (y0 * w + x0).  A field without a valid source gives NaN everywhere.
+ * Exact whatever the field; cost grows with the distance to the nearest source (large holes approach O(h*w) per pixel).
+ * scratch: ofx_forward_interpolate_scratch_bytes(B, h, w) bytes, 4-byte aligned (0 = unsupported size: h*w >= 2^30). */
+size_t ofx_forward_interpolate_scratch_bytes(int B, int h, int w);
+int ofx_forward_interpolate(const float* flow, float* out, void* scratch, size_t scratch_bytes, int B, int h, int w, void* stream);
+
 /* ---------------------------------------------------------------- RAFT engine */
 typedef struct ofx_tensor {            /* one entry of a checkpoint state_dict (host memory, fp32) */
     const char* name;                  /* reference key, e.g. "fnet.layer1.0.conv1.weight"        */
@@ -386,6 +396,12 @@ size_t ofx_raft_workspace_bytes(const ofx_raft* r, int B, int H, int W);
 #define OFX_RAFT_VOL_BF16X6 1024  /* the same with three planes per operand (fp32-level accuracy) */
 #define OFX_RAFT_SERIAL       32  /* keep every launch on the caller's stream (default: small batches run their
                                      independent chains on internal side streams, joined before returning) */
+#define OFX_RAFT_FLOW_INIT  2048  /* warm start (RAFT.forward(flow_init=...), raft.py:118-119): flow_low is in/out and must be non-NULL
+                                     (else OFX_EINVAL) and 8-byte aligned.  It is read at the start of the call as the initial flow
+                                     f32[B,H/8,W/8,2], one field per pair in pair order (the padded 1/8 grid), and overwritten with the
+                                     final low-resolution flow.  coords1 = coords0 + init (one fp32 rounding); the first iteration sees
+                                     the flow (coords0 + init) - coords0.  Every entry point and both networks; without the flag nothing
+                                     changes.  ofx_forward_interpolate makes the init of the next pair of a video from this one's. */
 
 /* RAFT.forward(test_mode=True): image1/image2 u8 [B,H,W,3] on device -> flow_up f32[B,H,W,2]
  * (flow on image1's grid pointing into image2) and, if non-NULL, flow_low f32[B,H/8,W/8,2].

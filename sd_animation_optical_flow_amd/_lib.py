@@ -105,6 +105,8 @@ SIGNATURES = {
     "ofx_upflow8": (_i, [_p, _p, _i, _i, _i, _p]),
     "ofx_upflow8_warp": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p]),
     "ofx_flow_head": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _p]),
+    "ofx_forward_interpolate_scratch_bytes": (_z, [_i, _i, _i]),
+    "ofx_forward_interpolate": (_i, [_p, _p, _p, _z, _i, _i, _i, _p]),
     "ofx_raft_create": (_i, [C.POINTER(Tensor), _i, C.POINTER(_p)]),
     "ofx_raft_destroy": (_i, [_p]),
     "ofx_raft_workspace_bytes": (_z, [_p, _i, _i, _i]),

@@ -231,6 +231,51 @@ __global__ __launch_bounds__(256) void init_state_kernel(float* __restrict__ coo
     }
 }
 
+// The warm-started form of init_state_kernel (RAFT.forward(flow_init=...), raft.py:118-119): coords1 = coords0 + flow_init, one fp32
+// rounding, and the flow the first iteration sees is (coords0 + flow_init) - coords0, rounded again (raft.py:127) -- not flow_init
+// itself.  That flow goes wherever the iteration-end writers put it: the hx flow slot, and convf1's operand -- either the 16-float
+// rows of the basic network (flow_head.hip: slot s of pixel x holds the flow of pixel x + s - 3, zero outside the image; each thread
+// builds its own row, recomputing the neighbours' flows) or the [M][4] rows of the small network's EPI_FLOW epilogue (conv.hip;
+// the rest of the 16 floats a pixel that ofx_init_state zeroes stays zero).  init: f32 [M][2], the layout of flow_low.
+__device__ __forceinline__ float2 ofx_warm_flow(const float* __restrict__ init, long m, int x, int y, float2* c) {
+    const float2 f = reinterpret_cast<const float2*>(init)[m];
+    const float cx = (float)x + f.x, cy = (float)y + f.y;
+    if (c) *c = make_float2(cx, cy);
+    return make_float2(cx - (float)x, cy - (float)y);
+}
+
+__global__ __launch_bounds__(256) void init_state_warm_kernel(float* __restrict__ coords1, float* __restrict__ frows,
+                                                              float* __restrict__ hx, int ldh, int flow_off, int rows4,
+                                                              const float* __restrict__ init, int h, int w, long M) {
+    for (long m = (long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long)gridDim.x * blockDim.x) {
+        const int rem = (int)(m % ((long)h * w));
+        const int y = rem / w, x = rem - y * w;
+        float2 c;
+        const float2 fl = ofx_warm_flow(init, m, x, y, &c);
+        reinterpret_cast<float2*>(coords1)[m] = c;
+        hx[m * ldh + flow_off] = fl.x;
+        hx[m * ldh + flow_off + 1] = fl.y;
+        float4* fr = reinterpret_cast<float4*>(frows);
+        if (rows4) {
+            fr[m] = make_float4(fl.x, fl.y, 0.f, 0.f);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) fr[M + m * 3 + q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            float v[16];
+#pragma unroll
+            for (int s = 0; s < 7; ++s) {
+                const int xs = x + s - 3;
+                const float2 f = (unsigned)xs < (unsigned)w ? ofx_warm_flow(init, m + s - 3, xs, y, nullptr) : make_float2(0.f, 0.f);
+                v[2 * s] = f.x;
+                v[2 * s + 1] = f.y;
+            }
+            v[14] = v[15] = 0.f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) fr[m * 4 + q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void coords_to_flow_kernel(const float* __restrict__ coords1, float* __restrict__ flow,
                                                              int h, int w, long M) {
     for (long m = (long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long)gridDim.x * blockDim.x) {
@@ -271,6 +316,15 @@ int ofx_ctx_gather(const float* ctx, const int* idx_dev, float* hx, int ldh, int
     OfxProfScope prof("ctx_gather", s);
     hipLaunchKernelGGL(ctx_gather_kernel, dim3((unsigned)std::min<long>((total4 + 255) / 256, 8192)), dim3(256), 0, s, ctx, idx_dev,
                        hx, ldh, off2, half, N, total4);
+    return ofx_launch_status();
+}
+
+int ofx_init_state_warm(float* coords1, float* frows, float* hx, int ldh, int flow_off, bool rows4, const float* init, int B, int h,
+                        int w, hipStream_t s) {
+    const long M = (long)B * h * w;
+    OfxProfScope prof("init_state_warm", s);
+    hipLaunchKernelGGL(init_state_warm_kernel, dim3((unsigned)std::min<long>((M + 255) / 256, 8192)), dim3(256), 0, s, coords1,
+                       frows, hx, ldh, flow_off, rows4 ? 1 : 0, init, h, w, M);
     return ofx_launch_status();
 }
 

@@ -120,6 +120,10 @@ int ofx_upsample_warp_launch(const float* coords1, const float* mask, float* flo
 // warp_fast.hip: upflow8 (the small network's upsample) + bilinear warp of one shared key frame in one pass
 int ofx_upflow8_warp_launch(const float* coords1, float* flow_up, const void* pad, uint8_t* warped, int B, int h, int w, float sign, hipStream_t s);
 int ofx_init_state(float* coords1, float* frows, float* hx, int ldh, int flow_off, int B, int h, int w, hipStream_t s);
+// ofx_init_state from an initial flow init f32 [B*h*w][2] (OFX_RAFT_FLOW_INIT): rows4 = the small network's [M][4] flow operand,
+// else the basic network's 16-float convf1 rows
+int ofx_init_state_warm(float* coords1, float* frows, float* hx, int ldh, int flow_off, bool rows4, const float* init, int B, int h,
+                        int w, hipStream_t s);
 int ofx_coords_to_flow(const float* coords1, float* flow, int B, int h, int w, hipStream_t s);
 int ofx_flow_head_launch(const float* x, int ldx, const float* w, int Kpad, const float* bias, float* coords1, float* hx_flow,
                          int ldh, float* frows, int B, int h, int w_, hipStream_t s);

@@ -645,13 +645,15 @@ static RaftWs carve(void* base, size_t cap, int B, int H, int W, int flags, int 
 
 // everything after the feature / context encoders and the correlation volume: state init, the loop-invariant
 // GRU terms, `iters` refinement iterations, mask head, convex upsample
+// warm: flow_low holds the initial flow (OFX_RAFT_FLOW_INIT); it is read here and overwritten with the final flow at the end
 static int run_recurrence(ofx_raft* r, const RaftWs& ws, int B, int h, int w, int iters, bool alt, bool shared,
-                          float* flow_up, float* flow_low, hipStream_t s, int precision, bool overlap,
+                          float* flow_up, float* flow_low, hipStream_t s, int precision, bool overlap, bool warm,
                           uint8_t* warped = nullptr, float warp_sign = 1.0f, int n_warp = -1) {
     const long N = (long)h * w;
     const bool sh1 = shared, sh2 = shared;
     int st = 0;
-    st = ofx_init_state(ws.coords1, ws.frows, ws.hx, HX_LD, FLOW_OFF, B, h, w, s);
+    st = warm ? ofx_init_state_warm(ws.coords1, ws.frows, ws.hx, HX_LD, FLOW_OFF, false, flow_low, B, h, w, s)
+              : ofx_init_state(ws.coords1, ws.frows, ws.hx, HX_LD, FLOW_OFF, B, h, w, s);
     if (st) return st;
     {   // loop-invariant GRU terms: conv(W[:, inp], inp) + bias for z|r and q of both passes
         Launcher G{s};
@@ -899,6 +901,8 @@ int ofx_raft_forward_warp(ofx_raft* r, const uint8_t* image1, const uint8_t* ima
 static int raft_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* image2, int B, int H, int W, int iters, int flags,
                              float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign, uint8_t* warped, void* workspace,
                              size_t workspace_bytes, void* stream) {
+    OFX_REQUIRE(!(flags & OFX_RAFT_FLOW_INIT) || flow_low, OFX_EINVAL);   // flow_low carries the initial flow in
+    if (flags & OFX_RAFT_FLOW_INIT) OFX_REQUIRE((((uintptr_t)flow_low) & 7u) == 0, OFX_EALIGN);
     if (r && r->variant == 1)
         return small_forward_impl(r, image1, image2, B, H, W, iters, flags, flow_up, flow_low, warp_frame, warp_sign, warped, workspace,
                                   workspace_bytes, stream);
@@ -1016,8 +1020,8 @@ static int raft_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* 
         st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
         if (st) return st;
     }
-    st = run_recurrence(r, ws, B, h, w, iters, alt, sh1 || sh2, flow_up, flow_low, s, prec, overlap, warped,
-                        warp_sign);
+    st = run_recurrence(r, ws, B, h, w, iters, alt, sh1 || sh2, flow_up, flow_low, s, prec, overlap, flags & OFX_RAFT_FLOW_INIT,
+                        warped, warp_sign);
     if (st) return st;
 
     r->bufs.clear();
@@ -1056,6 +1060,8 @@ int ofx_raft_forward_pairs_warp(ofx_raft* r, const uint8_t* images, int n_images
                                 int W, int iters, int flags, float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign,
                                 int n_warp, uint8_t* warped, void* workspace, size_t workspace_bytes, void* stream) {
     OFX_REQUIRE(r && images && idx1 && idx2 && flow_up && workspace, OFX_EINVAL);
+    OFX_REQUIRE(!(flags & OFX_RAFT_FLOW_INIT) || flow_low, OFX_EINVAL);
+    if (flags & OFX_RAFT_FLOW_INIT) OFX_REQUIRE((((uintptr_t)flow_low) & 7u) == 0, OFX_EALIGN);
     if (r->variant == 1)
         return small_forward_pairs_impl(r, images, n_images, idx1, idx2, B, H, W, iters, flags, flow_up, flow_low, warp_frame, warp_sign, n_warp,
                                         warped, workspace, workspace_bytes, stream);
@@ -1143,7 +1149,7 @@ int ofx_raft_forward_pairs_warp(ofx_raft* r, const uint8_t* images, int n_images
         st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
         if (st) return st;
     }
-    st = run_recurrence(r, ws, B, h, w, iters, false, false, flow_up, flow_low, s, prec, overlap, warped, warp_sign,
+    st = run_recurrence(r, ws, B, h, w, iters, false, false, flow_up, flow_low, s, prec, overlap, flags & OFX_RAFT_FLOW_INIT, warped, warp_sign,
                         n_warp);
     if (st) return st;
     r->bufs.clear();
@@ -1345,10 +1351,12 @@ int small_volume(const float* f1, long a_zs, const float* f2b, long w_zs, float*
 }
 
 // state init, `iters` refinement iterations of SmallUpdateBlock, upflow8 (with the warp of one shared frame for the first n_warp pairs)
-int small_recurrence(ofx_raft* r, const SmallWs& ws, int B, int h, int w, int iters, bool alt, float* flow_up, float* flow_low, uint8_t* warped,
-                     float warp_sign, int n_warp, hipStream_t s) {
+// (warm: flow_low holds the initial flow, OFX_RAFT_FLOW_INIT)
+int small_recurrence(ofx_raft* r, const SmallWs& ws, int B, int h, int w, int iters, bool alt, float* flow_up, float* flow_low, bool warm,
+                     uint8_t* warped, float warp_sign, int n_warp, hipStream_t s) {
     const long N = (long)h * w, M = (long)B * N;
-    int st = ofx_init_state(ws.coords1, ws.flow4, ws.hx, S_HX_LD, S_FLOW_OFF, B, h, w, s);
+    int st = warm ? ofx_init_state_warm(ws.coords1, ws.flow4, ws.hx, S_HX_LD, S_FLOW_OFF, true, flow_low, B, h, w, s)
+                  : ofx_init_state(ws.coords1, ws.flow4, ws.hx, S_HX_LD, S_FLOW_OFF, B, h, w, s);
     if (st) return st;
     OFX_HIP_CHECK(hipMemsetAsync(ws.corr, 0, (size_t)M * S_CORR_LD * sizeof(float), s));   // the 28 pad columns of every row
     Launcher L{s};
@@ -1523,7 +1531,7 @@ static int small_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t*
         for (int l = 1; l < LEVELS && !st; ++l) st = ofx_avgpool2_nhwc(ws.f2l[l - 1], ws.f2l[l], n2, h >> (l - 1), w >> (l - 1), S_FD, s);
     }
     if (!st && warped) st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
-    if (!st) st = small_recurrence(r, ws, B, h, w, iters, alt, flow_up, flow_low, warped, warp_sign, -1, s);
+    if (!st) st = small_recurrence(r, ws, B, h, w, iters, alt, flow_up, flow_low, flags & OFX_RAFT_FLOW_INIT, warped, warp_sign, -1, s);
     if (st) return st;
     small_register(r, ws, n1, n2, M, h, w, alt);
     return 0;
@@ -1566,7 +1574,7 @@ static int small_forward_pairs_impl(ofx_raft* r, const uint8_t* images, int n_im
                           ws.pyr[1] + (long)b * N * slice1, 1, h, w, &fused, s);
     if (!st) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused);
     if (!st && warped) st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
-    if (!st) st = small_recurrence(r, ws, B, h, w, iters, false, flow_up, flow_low, warped, warp_sign, n_warp, s);
+    if (!st) st = small_recurrence(r, ws, B, h, w, iters, false, flow_up, flow_low, flags & OFX_RAFT_FLOW_INIT, warped, warp_sign, n_warp, s);
     if (st) return st;
     r->bufs.clear();
     return 0;

@@ -4,6 +4,7 @@ Same names, argument meaning and mutation behaviour as the reference functions t
 (file:line in the reference repo):
 
     RAFT_2().calc(img1_bgr, img2_bgr) -> flow        ofgen_keyframe_inpaint.py:47-71 ; ofgen.py:55-79
+    forward_interpolate(flow)                        RAFT/core/utils/utils.py:26-53 (+ RAFT_2(warm_start=True))
     warp_frame(frame, flow)          (RAFT convention) ofgen_keyframe_inpaint.py:92-98
     warp_frame_latent(latent, flow)                  ofgen_keyframe_inpaint.py:100-111
     of_calc(frame1, frame2, algo)                    ofgen_keyframe_inpaint.py:113-133 ; ofgen.py:45-49 (bare-flow algo -> (flow, v))
@@ -56,11 +57,21 @@ class RAFT_2:
     tests/golden/raft_ref_trainbn_128x160.npz (the reference module left in train mode) -- DESIGN.md section 2."""
 
     def __init__(self, model="../RAFT/models/raft-things.pth", device="cuda", iters: int = 20, alternate_corr: bool = False,
-                 cnet_norm: str = "batch"):
+                 cnet_norm: str = "batch", warm_start: bool = False):
+        """warm_start=True (extension: RAFT's warm start for video, RAFT.forward(flow_init=...) with utils.forward_interpolate): every
+        `calc` after the first starts its refinement from `forward_interpolate` of the previous call's 1/8-resolution flow -- what
+        makes the reference's consecutive-frame chain `of_calc(last_frame, frame)` warm.  A call starts cold when the padded frame
+        size changed or the carried field is not finite; `reset()` drops the state.  Default: every call cold, as the reference."""
         self.device = torch.device(device)
         self.iters = iters
         self.alternate_corr = alternate_corr
+        self.warm_start = warm_start
         self.model = RaftEngine(load_checkpoint(model), self.device, cnet_norm=cnet_norm)
+        self._low: Optional[torch.Tensor] = None      # the previous call's flow_low [1,h,w,2] (warm_start)
+
+    def reset(self) -> None:
+        """Forget the previous flow: the next `calc` starts cold."""
+        self._low = None
 
     @torch.no_grad()
     def calc(self, img1: np.ndarray, img2: np.ndarray) -> np.ndarray:
@@ -68,8 +79,27 @@ class RAFT_2:
         not un-pad, :70)."""
         a = _dev(img1, self.device)[None]
         b = _dev(img2, self.device)[None]
-        flo = self.model.forward(a, b, iters=self.iters, bgr=True, alternate_corr=self.alternate_corr)
+        if not self.warm_start:
+            flo = self.model.forward(a, b, iters=self.iters, bgr=True, alternate_corr=self.alternate_corr)
+            return flo[0].cpu().numpy()
+        grid = ((a.shape[1] + 7) // 8, (a.shape[2] + 7) // 8)       # the padded 1/8 grid (RaftEngine.pad_to_8)
+        init = None
+        if self._low is not None and tuple(self._low.shape[1:3]) == grid:
+            init = ops.forward_interpolate(self._low)
+            if not bool(torch.isfinite(init).all()):
+                init = None
+        flo, self._low = self.model.forward(a, b, iters=self.iters, bgr=True, alternate_corr=self.alternate_corr, want_low=True,
+                                            flow_init=init)
         return flo[0].cpu().numpy()
+
+
+def forward_interpolate(flow) -> torch.Tensor:
+    """RAFT/core/utils/utils.py:26-53 (the reference's signature and result): flow [2,h,w] (any device; float32 values) -> CPU float
+    tensor [2,h,w].  Computed on the device (`ops.forward_interpolate`, exact to scipy's float64 nearest search; ties go to the
+    lowest source index, a field without a valid source gives NaN)."""
+    t = torch.as_tensor(flow).detach().to(device="cuda", dtype=torch.float32)
+    out = ops.forward_interpolate(t.permute(1, 2, 0).contiguous())
+    return out.permute(2, 0, 1).contiguous().cpu()
 
 
 def create_of_algo(ckpt="../DenseMatching/pre_trained_models/PDCNet_plus_m.pth.tar"):

@@ -367,6 +367,28 @@ def flow_head(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, coord
                                    hx.shape[3], _ptr(fr), B, h, w, _stream()), "ofx_flow_head")
 
 
+def forward_interpolate(flow: torch.Tensor) -> torch.Tensor:
+    """forward_interpolate of RAFT/core/utils/utils.py:26-53 on the device (`ofx_forward_interpolate`): the warm start of a video
+    chain.  flow f32 [B,h,w,2] or [h,w,2] (the engine's flow_low layout) -> the same shape: every output pixel takes the flow of the
+    valid source (x0 + dx, y0 + dy; 0 < x1 < w, 0 < y1 < h) nearest to it in float64, ties to the lowest source index; a field
+    without a valid source gives NaN.  Fields are independent; runs on the current stream."""
+    fl = _chk(flow, "flow", torch.float32)
+    one = fl.dim() == 3
+    if one:
+        fl = fl[None]
+    if fl.dim() != 4 or fl.shape[3] != 2 or fl.numel() == 0:
+        raise RuntimeError("flow must be f32 [B,h,w,2] or [h,w,2]")
+    B, h, w, _ = fl.shape
+    L = _lib.lib()
+    need = L.ofx_forward_interpolate_scratch_bytes(B, h, w)
+    if need == 0:
+        raise RuntimeError(f"unsupported size B={B} h={h} w={w}")
+    scratch = torch.empty((need,), dtype=torch.uint8, device=fl.device)
+    out = torch.empty_like(fl)
+    check(L.ofx_forward_interpolate(_ptr(fl), _ptr(out), _ptr(scratch), need, B, h, w, _stream()), "ofx_forward_interpolate")
+    return out[0] if one else out
+
+
 def conv2d_desc(d: ConvDesc) -> None:
     check(_lib.lib().ofx_conv2d(C.byref(d), _stream()), "ofx_conv2d")
 

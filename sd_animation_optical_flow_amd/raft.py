@@ -22,6 +22,7 @@ FLAG_BGR, FLAG_SHARED_IMG2, FLAG_SHARED_IMG1, FLAG_ALT_CORR, FLAG_BF16X3, FLAG_S
 CNET_NORMS = {"eval": 0, "batch": FLAG_BN_BATCH}
 PRECISIONS = {"fp32": 0, "bf16x3": FLAG_BF16X3, "bf16x6": FLAG_BF16X6}
 FLAG_VOL_BF16X3, FLAG_VOL_BF16X6 = 512, 1024
+FLAG_FLOW_INIT = 2048
 VOLUME_PRECISIONS = {None: 0, "fp32": 0, "bf16x3": FLAG_VOL_BF16X3, "bf16x6": FLAG_VOL_BF16X6}
 # floats of the widest row a convolution of one executor call addresses, per network (see pairs_per_call)
 ROW_FLOATS = {"basic": 768, "small": 256}
@@ -197,7 +198,7 @@ class RaftEngine:
     def forward(self, image1: torch.Tensor, image2: torch.Tensor, iters: int = 20, bgr: bool = False,
                 alternate_corr: bool = False, want_low: bool = False, serial: bool = False, separate_stats: bool = False,
                 warp_frame: Optional[torch.Tensor] = None, warp_sign: float = 1.0,
-                want_flow: bool = True):
+                want_flow: bool = True, flow_init: Optional[torch.Tensor] = None):
         """image1: uint8 [B,H,W,3] or [H,W,3] (shared by the batch); image2 likewise.  Flow is defined
         on image1's grid and points into image2.  Returns flow_up f32[B,H,W,2] (and flow_low).
         serial=True keeps every launch on the current stream (small batches otherwise overlap their
@@ -207,7 +208,10 @@ class RaftEngine:
         final flow is produced INSIDE the convex upsample (`ofx_raft_forward_warp`; warp_sign +1 = pdcnet_of.warp_frame's convention,
         -1 = ofgen.warp_frame's) and returned after the flow: (flow_up[, flow_low], warped u8 [B,H,W,3]) -- bit-identical to
         `ops.warp(warp_frame, flow_up, mode="bilinear")`.  want_flow=False skips writing the full-resolution flow (None is returned in
-        its place)."""
+        its place).
+        flow_init: warm start (RAFT.forward(flow_init=...), raft.py:118-119): CUDA f32 [B,Hp/8,Wp/8,2] on the padded 1/8 grid (Hp, Wp =
+        the size after pad_to_8), [Hp/8,Wp/8,2] when B == 1 -- the refinement starts at coords0 + flow_init instead of zero flow
+        (OFX_RAFT_FLOW_INIT).  Typically `ops.forward_interpolate` of the previous pair's flow_low.  Not modified."""
         for nm, t in (("image1", image1), ("image2", image2)):
             if not t.is_cuda:
                 raise RuntimeError(f"{nm} must be a CUDA tensor")
@@ -241,6 +245,8 @@ class RaftEngine:
             warp_frame = warp_frame.contiguous()
         elif not want_flow:
             raise ValueError("want_flow=False only makes sense together with warp_frame")
+        if flow_init is not None:
+            flow_init = self._check_init(flow_init, B, H, W)
         max_pairs = self.pairs_per_call(H, W)
         if B > 1:
             max_pairs = min(max_pairs, self.pairs_that_fit(min(B, max_pairs), H, W))
@@ -250,16 +256,21 @@ class RaftEngine:
                 a = image1 if sh1 else image1[b0:b0 + max_pairs]
                 c = image2 if sh2 else image2[b0:b0 + max_pairs]
                 r = self.forward(a, c, iters=iters, bgr=bgr, alternate_corr=alternate_corr, want_low=want_low, serial=serial, separate_stats=separate_stats,
-                                 warp_frame=warp_frame, warp_sign=warp_sign, want_flow=want_flow)
+                                 warp_frame=warp_frame, warp_sign=warp_sign, want_flow=want_flow,
+                                 flow_init=None if flow_init is None else flow_init[b0:b0 + max_pairs])
                 outs.append(r if isinstance(r, tuple) else (r,))
             cat = tuple(None if parts[0] is None else torch.cat(parts) for parts in zip(*outs))
             return cat if len(cat) > 1 else cat[0]
         ws = self._workspace(B, H, W)
         flow_up = torch.empty((B, H, W, 2), dtype=torch.float32, device=self.device) if want_flow else None
-        flow_low = torch.empty((B, H // 8, W // 8, 2), dtype=torch.float32, device=self.device) if want_low else None
+        if flow_init is not None:       # flow_low is in/out: the initial flow in, the final one out
+            flow_low = flow_init.clone(memory_format=torch.contiguous_format)
+            flags |= FLAG_FLOW_INIT
+        else:
+            flow_low = torch.empty((B, H // 8, W // 8, 2), dtype=torch.float32, device=self.device) if want_low else None
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         fu = C.c_void_p(flow_up.data_ptr() if want_flow else 0)
-        fl = C.c_void_p(flow_low.data_ptr() if want_low else 0)
+        fl = C.c_void_p(flow_low.data_ptr() if flow_low is not None else 0)
         if warp_frame is None:
             check(_lib.lib().ofx_raft_forward(self._h, C.c_void_p(i1.data_ptr()), C.c_void_p(i2.data_ptr()), B, H, W, int(iters),
                                               flags, fu, fl, C.c_void_p(ws.data_ptr()), ws.numel(), stream), "ofx_raft_forward")
@@ -272,13 +283,15 @@ class RaftEngine:
 
     @torch.no_grad()
     def forward_pairs(self, images: torch.Tensor, idx1, idx2, iters: int = 20, bgr: bool = False,
-                      warp_frame: Optional[torch.Tensor] = None, warp_sign: float = 1.0, n_warp: int = 0):
+                      warp_frame: Optional[torch.Tensor] = None, warp_sign: float = 1.0, n_warp: int = 0,
+                      flow_init: Optional[torch.Tensor] = None):
         """images: uint8 [n,H,W,3] on the device (H, W multiples of 8); pair b = (idx1[b], idx2[b]):
         flow b lives on image idx1[b] and points into image idx2[b].  Every image is encoded once however
         many pairs use it (KeyframeConv's N x N sweep).  Returns f32 [B,H,W,2] on the device.
         warp_frame (uint8 [H,W,3], one frame shared by the batch) + n_warp: the first n_warp pairs also get the bilinear
         backward warp of warp_frame along their final flow, produced inside the convex upsample
-        (`ofx_raft_forward_pairs_warp`); returns (flow, warped u8 [n_warp,H,W,3])."""
+        (`ofx_raft_forward_pairs_warp`); returns (flow, warped u8 [n_warp,H,W,3]).
+        flow_init: warm start, CUDA f32 [B,H/8,W/8,2], one initial flow per pair in pair order (see `forward`)."""
         if not images.is_cuda or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
             raise RuntimeError("images must be a CUDA uint8 tensor [n,H,W,3]")
         imgs = images.contiguous()
@@ -290,6 +303,9 @@ class RaftEngine:
             raise RuntimeError("idx1 / idx2 must be non-empty and of equal length")
         a1 = (C.c_int * B)(*[int(i) for i in idx1])
         a2 = (C.c_int * B)(*[int(i) for i in idx2])
+        flow_low = None
+        if flow_init is not None:
+            flow_low = self._check_init(flow_init, B, H, W).clone(memory_format=torch.contiguous_format)
         L = _lib.lib()
         need = L.ofx_raft_workspace_bytes_pairs(self._h, n, B, H, W)
         if need == 0:
@@ -300,9 +316,12 @@ class RaftEngine:
         flow_up = torch.empty((B, H, W, 2), dtype=torch.float32, device=self.device)
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         flags = (FLAG_BGR if bgr else 0) | PRECISIONS[self.precision] | CNET_NORMS[self.cnet_norm] | VOLUME_PRECISIONS[self.volume_precision]
+        if flow_low is not None:
+            flags |= FLAG_FLOW_INIT
+        fl = C.c_void_p(flow_low.data_ptr() if flow_low is not None else 0)
         if warp_frame is None:
             check(L.ofx_raft_forward_pairs(self._h, C.c_void_p(imgs.data_ptr()), n, a1, a2, B, H, W, int(iters), flags,
-                                           C.c_void_p(flow_up.data_ptr()), None,
+                                           C.c_void_p(flow_up.data_ptr()), fl,
                                            C.c_void_p(self._ws.data_ptr()), self._ws.numel(), stream), "ofx_raft_forward_pairs")
             return flow_up
         if not warp_frame.is_cuda or warp_frame.dtype != torch.uint8 or tuple(warp_frame.shape) != (H, W, 3):
@@ -315,10 +334,20 @@ class RaftEngine:
         wf = warp_frame.contiguous()
         warped = torch.empty((n_warp, H, W, 3), dtype=torch.uint8, device=self.device)
         check(L.ofx_raft_forward_pairs_warp(self._h, C.c_void_p(imgs.data_ptr()), n, a1, a2, B, H, W, int(iters), flags,
-                                            C.c_void_p(flow_up.data_ptr()), None, C.c_void_p(wf.data_ptr()), float(warp_sign), n_warp,
+                                            C.c_void_p(flow_up.data_ptr()), fl, C.c_void_p(wf.data_ptr()), float(warp_sign), n_warp,
                                             C.c_void_p(warped.data_ptr()), C.c_void_p(self._ws.data_ptr()), self._ws.numel(), stream),
               "ofx_raft_forward_pairs_warp")
         return flow_up, warped
+
+    def _check_init(self, flow_init, B: int, H: int, W: int) -> torch.Tensor:
+        """flow_init as the engine takes it: CUDA f32 [B,H/8,W/8,2] ([H/8,W/8,2] accepted when B == 1), else RuntimeError."""
+        if not torch.is_tensor(flow_init) or not flow_init.is_cuda or flow_init.dtype != torch.float32:
+            raise RuntimeError("flow_init must be a CUDA float32 tensor")
+        want = (B, H // 8, W // 8, 2)
+        t = flow_init[None] if B == 1 and tuple(flow_init.shape) == want[1:] else flow_init
+        if tuple(t.shape) != want:
+            raise RuntimeError(f"flow_init must be [{B},{H // 8},{W // 8},2] (the padded 1/8 grid), got {tuple(flow_init.shape)}")
+        return t
 
     def buffer(self, name: str) -> torch.Tensor:
         """Copy of a named intermediate of the last forward (flat f32) -- for stage-level parity tests."""
