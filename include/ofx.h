@@ -227,9 +227,16 @@ typedef struct ofx_conv_desc {
                                                     zero); one scratch per stream that may run a convolution concurrently.
                                                     NULL / 0: never split. */
     const float* wino_w;                         /* optional (3x3 layers): the same weights as ofx_wino_conv_weight makes them.
-                                                    When set, a stride-1 'same' fp32 layer with a plain epilogue over whole 8x16
-                                                    patches runs the fused Winograd F(2x2,3x3) kernel on grids that fill the chip
-                                                    (OFX_CONV_NO_WINOGRAD in the environment: never); tile = OFX_CONV_TILE_WINOGRAD
+                                                    When set, a layer runs the fused Winograd F(2x2,3x3) kernel on grids that
+                                                    fill the chip if all of these hold:
+                                                    - fp32, stride 1, 'same' padding, a map of whole 8x16 patches;
+                                                    - plain epilogue, ReLU or identity, no addend;
+                                                    - `res` (residual merge) is allowed;
+                                                    - a fused norm (`nmean` / `nrstd`) is allowed over a single input segment;
+                                                    - under ofx_conv2d_stats, only identity outputs without `res` qualify, and
+                                                      the partials come one row per 8x16 patch.
+                                                    Otherwise, or with OFX_CONV_NO_WINOGRAD in the
+                                                    environment, the direct kernels run.  tile = OFX_CONV_TILE_WINOGRAD
                                                     forces it at any grid size and is rejected (OFX_EINVAL) when the layer does not
                                                     qualify.  NULL: direct kernels only.
                                                     1x5 / 5x1 layers: the operand of ofx_wino15_conv_weight.  A stride-1 fp32
@@ -271,6 +278,14 @@ int ofx_split_conv_weight3(const float* packed, long n_floats, float* out);
  * scratch: max(B*64, min(B,7)*256) * C * 2 doubles (f64 partial sums per image slice), 8-byte aligned. */
 int ofx_inorm_stats(const float* x, int ld, float* mean, float* rstd, float* scratch,
                     int B, long HW, int C, float eps, void* stream);
+/* ofx_conv2d that also leaves per-channel (sum, sum of squares) partials of the outputs it writes in `part`, as
+ * [B][*rows_per_image][Cout][2] floats, when the launch can produce them: fp32, plain epilogue, identity activation, no `res`, and
+ * at most part_floats floats.  *rows_per_image = 0: not produced (use ofx_inorm_stats).  Both the direct and the fused Winograd
+ * kernels write them, in a fixed order (repeats are bit-identical). */
+int ofx_conv2d_stats(const ofx_conv_desc* d, float* part, size_t part_floats, int* rows_per_image, void* stream);
+/* mean and 1/sqrt(var+eps) (biased var) per (b,c) [B][C] from ofx_conv2d_stats' partials of HW pixels per image (the `rows` rows
+ * of an image added in a fixed order) */
+int ofx_inorm_finalize(const float* part, float* mean, float* rstd, int B, int rows, long HW, int C, float eps, void* stream);
 /* out = relu?( (x-mean)*rstd ) ; with res: out = relu( r + relu((x-mean)*rstd) ) where
  * r = res (res_mean==NULL) or (res-res_mean)*res_rstd -- or relu of that when bit 1 of `relu` is set (relu = 3: the residual is
  * itself the raw output of a normalised + ReLU layer, RAFT/core/extractor.py:160-165 feeding :44-56).  C % 4 == 0 and C <= 1024 (a thread keeps one channel quad:

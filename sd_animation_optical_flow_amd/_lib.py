@@ -86,6 +86,8 @@ SIGNATURES = {
     "ofx_detect_edges": (_i, [_p, _p, _p, _z, _i, _i, _i, _i, _p]),
     "ofx_abs_diff_sum_u8": (_i, [_p, _l, _p, _l, _p, _i, _l, _p]),
     "ofx_inorm_stats": (_i, [_p, _i, _p, _p, _p, _i, _l, _i, _f, _p]),
+    "ofx_conv2d_stats": (_i, [C.POINTER(ConvDesc), _p, _z, _p, _p]),
+    "ofx_inorm_finalize": (_i, [_p, _p, _p, _i, _i, _l, _i, _f, _p]),
     "ofx_inorm_apply": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p]),
     "ofx_preprocess_u8": (_i, [_p, _p, _l, _i, _p]),
     "ofx_groupnorm_scratch_bytes": (C.c_size_t, [_i, _i]),

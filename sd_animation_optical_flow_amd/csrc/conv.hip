@@ -1387,22 +1387,27 @@ extern "C" int ofx_conv2d_alpha(const ofx_conv_desc* d, float alpha, void* strea
         default: return OFX_EINVAL;
     }
 
-    // ---- fused Winograd (conv_wino.hip): F(2x2,3x3) for the update block's 3x3 layers (4 instead of 9 multiplies per output) and
-    // F(4,5) for the SepConvGRU's 1x5 / 5x1 layers (2 instead of 5, GRU gate epilogues included).  Only on grids that fill the chip
-    // (ofx_conv_wino_pays): smaller grids, the single pair among them, keep the direct kernels and their small-grid schedules.
+    // ---- fused Winograd (conv_wino.hip): F(2x2,3x3) for the update block's and the encoders' stride-1 3x3 layers (4 instead of 9
+    // multiplies per output; residual merge, fused instance norm and epilogue statistics included) and F(4,5) for the SepConvGRU's
+    // 1x5 / 5x1 layers (2 instead of 5, GRU gate epilogues included).  Only on grids that fill the chip (ofx_conv_wino_pays):
+    // smaller grids, the single pair among them, keep the direct kernels and their small-grid schedules.
     {
         static const bool no_wino = getenv("OFX_CONV_NO_WINOGRAD") != nullptr;
         static const bool no_wino15 = no_wino || getenv("OFX_CONV_NO_WINOGRAD15") != nullptr;
         const bool force = d->tile == OFX_CONV_TILE_WINOGRAD;
         const bool one_d = (d->KH == 1 && d->KW == 5) || (d->KH == 5 && d->KW == 1);
         if (force || (d->tile == 0 && !(one_d ? no_wino15 : no_wino) && d->wino_w)) {
-            const bool fits = nz == 1 && !tl_stats.on && !tl_pool.on && ofx_conv_wino_fits(d);
+            // asked for statistics: only where the fused kernel leaves them (one row per 8x16 patch), in the caller's room
+            const int srows = tl_stats.on ? ofx_conv_wino_stats_rows(d) : 0;
+            const bool stats_ok = !tl_stats.on || (srows > 0 && (size_t)d->B * srows * d->Cout * 2 <= tl_stats.cap_floats);
+            const bool fits = nz == 1 && stats_ok && !tl_pool.on && ofx_conv_wino_fits(d);
             if (force && !fits) return OFX_EINVAL;
             if (fits && (force || ofx_conv_wino_pays(d))) {
                 OfxProfScope prof(d->epi == OFX_EPI_GRU_ZR ? "igemm_conv_gru_zr" : d->epi == OFX_EPI_GRU_Q ? "igemm_conv_gru_q" : "igemm_conv",
                                   (hipStream_t)stream);   // the convolution families of the per-layer profile
                 prof.flops(ofx_conv_wino_flops(d));
-                return ofx_conv_wino_launch(d, alpha, (hipStream_t)stream);
+                if (tl_stats.on) tl_stats.rows_per_image = srows;
+                return ofx_conv_wino_launch(d, alpha, tl_stats.on ? tl_stats.part : nullptr, (hipStream_t)stream);
             }
         }
     }

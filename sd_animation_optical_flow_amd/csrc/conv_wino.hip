@@ -1,6 +1,7 @@
 // Fused Winograd convolutions on the fp32 matrix cores of gfx950.
 //
-// For the update block's stride-1 3x3 "same" layers (convc2, conv, flow_head.conv1, convf2 at 1/8 resolution) and the SepConvGRU's
+// For the stride-1 3x3 "same" layers (the update block's convc2, conv, flow_head.conv1, convf2 and mask.0 at 1/8 resolution; the
+// encoders' residual stages at 1/2 - 1/8, with their fused instance norm, residual merge and epilogue statistics) and the SepConvGRU's
 // per-iteration 1x5 / 5x1 layers (gru.zr1 / q1, gru.zr2 / q2, 256 input channels) the direct halo-patch kernel of conv.hip runs at
 // ~0.9 of the fp32 MFMA peak, so the only way to take real time off them is to execute fewer multiplies:
 //
@@ -59,11 +60,15 @@ struct WinoK {
     const float* scale;
     const float* shift;
     const float* addend;     // 1D kernel only, as the GRU pointers below
+    const float* res;        // 3x3 kernel only: residual merge relu(y + res)
+    const float* nmean;      // 3x3 kernel only: relu((x - mean) * rstd) on the operand, [B][c0]
+    const float* nrstd;
+    float* stats;            // 3x3 kernel only: per-patch (sum, sum of squares) of every output channel, [B][tpi][Cout][2]
     float* out;
     float* aux_z;
     float* aux_rh;
     float* aux_h;
-    int ld0, c0, ld1, cin, ldo, ldadd, ldh;
+    int ld0, c0, ld1, cin, ldo, ldadd, ldh, ldres;
     int H, W, Cout, act;
     int nblk;                // output blocks of 64 (2D) or 128 (1D) channels
     int nb32;                // 32-channel blocks of u
@@ -94,8 +99,9 @@ __device__ __forceinline__ Patch wino_patch(const WinoK& p) {
 // The slab pipeline of both kernels.  ALG is the algorithm's policy: its halo geometry ALG::HALO; the wave's share of the products,
 // P transform points from ALG::pt0(wave) on and NT 32-channel blocks of u from ALG::blk0(nb, wave) on; and its input transform,
 // built from (Hs, Vs, tid, wave), whose call transforms the calling thread's (tile, channel pair) from the halo in Hs into Vs
-// ([point][tile][channel] at row stride kLDV).  The wave's point-wise products accumulate into acc.
-template <class ALG>
+// ([point][tile][channel] at row stride kLDV).  The wave's point-wise products accumulate into acc.  NORM: the operand is
+// relu((x - mean) * rstd) of image pt.pb (single segment), applied as the halo is staged; the zero padding stays zero.
+template <class ALG, bool NORM = false>
 __device__ __forceinline__ void wino_slabs(const WinoK& p, const Patch& pt, float* Hs, float* Vs, int tid, int wave,
                                            f32x16 (&acc)[ALG::P][ALG::NT]) {
     typedef int v4i __attribute__((ext_vector_type(4)));
@@ -120,6 +126,7 @@ __device__ __forceinline__ void wino_slabs(const WinoK& p, const Patch& pt, floa
     }
     const int hq = (tid & 3) * 16;   // byte offset of this thread's float4 slot (256 % 4 == 0: the same for every k)
     float4 pa[HALO::slots];
+    float4 pmu, prs;                 // NORM: mean / rstd of this thread's four channels of the slab in flight
     auto a_issue = [&](int cb) __attribute__((always_inline)) {
         const int c = cb * kWBK;
         const bool s0 = c < p.c0;    // wave-uniform
@@ -131,6 +138,11 @@ __device__ __forceinline__ void wino_slabs(const WinoK& p, const Patch& pt, floa
             const int vo = ((hok >> k) & 1u) ? hpix[k] * ldb + hq : kOOB;
             v4i t = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, 0);
             pa[k] = *reinterpret_cast<float4*>(&t);
+        }
+        if constexpr (NORM) {
+            const long at = (long)pt.pb * p.c0 + c + (tid & 3) * 4;
+            pmu = *reinterpret_cast<const float4*>(p.nmean + at);
+            prs = *reinterpret_cast<const float4*>(p.nrstd + at);
         }
     };
 
@@ -172,7 +184,15 @@ __device__ __forceinline__ void wino_slabs(const WinoK& p, const Patch& pt, floa
         for (int k = 0; k < HALO::slots; ++k) {
             const int i = tid + 256 * k;
             if (HALO::slots * 256 > HALO::items && k == HALO::slots - 1 && i >= HALO::items) break;
-            *reinterpret_cast<float4*>(&Hs[(i >> 2) * HALO::ldh + (i & 3) * 4]) = pa[k];
+            float4 v = pa[k];
+            if constexpr (NORM) {   // as the direct kernel's a_commit (conv.hip): padding is applied to the normalised map
+                v.x = fmaxf((v.x - pmu.x) * prs.x, 0.f);
+                v.y = fmaxf((v.y - pmu.y) * prs.y, 0.f);
+                v.z = fmaxf((v.z - pmu.z) * prs.z, 0.f);
+                v.w = fmaxf((v.w - pmu.w) * prs.w, 0.f);
+                if (!((hok >> k) & 1u)) v = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            *reinterpret_cast<float4*>(&Hs[(i >> 2) * HALO::ldh + (i & 3) * 4]) = v;
         }
         __syncthreads();
         xf();
@@ -296,8 +316,13 @@ template <bool VERT> struct Wino15 {
 constexpr int kLDX = 32;                                    // output exchange: [wave][column fold][tile][32 channels]
 constexpr int kVF2 = 16 * 32 * kLDV;                        // 10240 floats
 constexpr int kSmem2 = Halo3x3::floats + kVF2;              // 58 240 bytes: two workgroups per CU
-static_assert(4 * 2 * 32 * kLDX <= kSmem2, "exchange must fit");   // reuses the halo / V space after the last slab
+constexpr int kXF = 4 * 2 * 32 * kLDX;                      // 8192 floats
+static_assert(kXF + 2 * 4 * 32 * 2 <= kSmem2, "exchange and statistics must fit");   // reuse the halo / V space after the last slab
 
+// NORM: relu(norm(.)) on the operand (wino_slabs).  RES: the residual merge relu(y + res) after the activation, as the direct
+// kernel's plain epilogue.  STATS: per (patch, output channel) sum and sum of squares of the stored values, [B][tpi][Cout][2] for
+// ofx_inorm_finalize_part, in a fixed order.  <false, false, false> is the update block's kernel.
+template <bool NORM, bool RES, bool STATS>
 __global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
     __shared__ __attribute__((aligned(16))) float smem[kSmem2];
     float* const Hs = smem;
@@ -306,11 +331,12 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the weight offsets stay scalar too
     const Patch pt = wino_patch(p);
     f32x16 acc[4][2];
-    wino_slabs<Wino3x3>(p, pt, Hs, Vs, tid, wave, acc);
+    wino_slabs<Wino3x3, NORM>(p, pt, Hs, Vs, tid, wave, acc);
 
     // ---- output transform and plain epilogue, one 32-channel half at a time through LDS
     const float act_lo = p.act == OFX_ACT_RELU ? 0.0f : -3.402823466e38f;
     float* const X = smem;
+    float* const Sx = smem + kXF;   // STATS: [32-channel half][wave][channel][sum, sum of squares]
     const int on = tid & 31, otx = tid >> 5;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
@@ -325,9 +351,10 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
         }
         __syncthreads();
         const int oc = pt.nb * 64 + nt * 32 + on;
-        if (oc < p.Cout) {
+        if (oc < p.Cout) {   // (the same for lanes l and l ^ 32: the statistics' shuffle below stays within active lanes)
             const float sc = (p.scale ? p.scale[oc] : 1.0f) * p.alpha;
             const float sh = p.shift ? p.shift[oc] : 0.0f;
+            float st_s = 0.0f, st_q = 0.0f;
 #pragma unroll
             for (int ty = 0; ty < 4; ++ty) {
                 const int tile = ty * 8 + otx;
@@ -336,17 +363,69 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
                 for (int w = 0; w < 4; ++w)
 #pragma unroll
                     for (int j = 0; j < 2; ++j) x[w][j] = X[((w * 2 + j) * 32 + tile) * kLDX + on];
+                float r[2][2];
+                if constexpr (RES) {
+#pragma unroll
+                    for (int a = 0; a < 2; ++a)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            r[a][j] = p.res[(((long)pt.pb * p.H + pt.y0 + 2 * ty + a) * p.W + pt.x0 + 2 * otx + j) * p.ldres + oc];
+                }
 #pragma unroll
                 for (int a = 0; a < 2; ++a)
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
                         const float y = a == 0 ? x[0][j] + x[1][j] + x[2][j] : x[1][j] - x[2][j] - x[3][j];
                         const long pix = ((long)pt.pb * p.H + pt.y0 + 2 * ty + a) * p.W + pt.x0 + 2 * otx + j;
-                        p.out[pix * p.ldo + oc] = fmaxf(y * sc + sh, act_lo);
+                        float v = fmaxf(y * sc + sh, act_lo);
+                        if constexpr (RES) v = fmaxf(v + r[a][j], 0.0f);
+                        p.out[pix * p.ldo + oc] = v;
+                        if constexpr (STATS) {
+                            st_s += v;
+                            st_q = fmaf(v, v, st_q);
+                        }
                     }
+            }
+            if constexpr (STATS) {   // the lane halves hold the patch's other tile column of the same channel
+                st_s += __shfl_xor(st_s, 32, 64);
+                st_q += __shfl_xor(st_q, 32, 64);
+                if (lane < 32) {
+                    Sx[((nt * 4 + wave) * 32 + on) * 2 + 0] = st_s;
+                    Sx[((nt * 4 + wave) * 32 + on) * 2 + 1] = st_q;
+                }
             }
         }
     }
+    if constexpr (STATS) {   // the four waves' partials of each channel, added in wave order
+        __syncthreads();
+        const int nt = tid >> 5;
+        const int oc = pt.nb * 64 + nt * 32 + on;
+        if (tid < 64 && oc < p.Cout) {
+            float s = 0.0f, q = 0.0f;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                s += Sx[((nt * 4 + w) * 32 + on) * 2 + 0];
+                q += Sx[((nt * 4 + w) * 32 + on) * 2 + 1];
+            }
+            const long row = (long)pt.pb * p.tpi + (pt.y0 >> 3) * p.tpr + (pt.x0 >> 4);
+            p.stats[(row * p.Cout + oc) * 2 + 0] = s;
+            p.stats[(row * p.Cout + oc) * 2 + 1] = q;
+        }
+    }
+}
+
+int launch3x3(const WinoK& k, dim3 grid, dim3 block, hipStream_t s) {
+    const int v = (k.nmean ? 4 : 0) | (k.res ? 2 : 0) | (k.stats ? 1 : 0);
+    switch (v) {
+        case 0: OFX_LAUNCH((wino_conv_kernel<false, false, false>), grid, block, s, k); break;
+        case 1: OFX_LAUNCH((wino_conv_kernel<false, false, true>), grid, block, s, k); break;
+        case 2: OFX_LAUNCH((wino_conv_kernel<false, true, false>), grid, block, s, k); break;
+        case 4: OFX_LAUNCH((wino_conv_kernel<true, false, false>), grid, block, s, k); break;
+        case 5: OFX_LAUNCH((wino_conv_kernel<true, false, true>), grid, block, s, k); break;
+        case 6: OFX_LAUNCH((wino_conv_kernel<true, true, false>), grid, block, s, k); break;
+        default: return OFX_EINVAL;   // statistics are of raw outputs: never with a residual merge
+    }
+    return ofx_launch_status();
 }
 
 // ---- F(4, 5): 128 output channels per workgroup, wave w = all 8 points x 32 channels
@@ -438,22 +517,30 @@ int wino_cblk(const ofx_conv_desc* d) { return is_3x3(d) ? 64 : 128; }   // outp
 }  // namespace
 
 // Shape test: fp32, one problem, stride 1, 3x3 (pad 1, 1), 1x5 (pad 0, 2) or 5x1 (pad 2, 0) keeping the map size, a map of whole
-// 8x16 patches, 16-channel slabs that never straddle the two input segments, no fused norm or residual.  Epilogues: 3x3, plain
-// without addend; 1x5 / 5x1, plain (optional addend) or a GRU gate epilogue whose z | r split falls on a 128-channel block boundary.
-// Plain: ReLU or identity.
+// 8x16 patches, 16-channel slabs that never straddle the two input segments.  Epilogues: 3x3, plain without addend, optionally
+// with the residual merge relu(y + res) and / or relu(norm(.)) fused into the operand (single segment: the encoders' layers);
+// 1x5 / 5x1, no fused norm or residual, plain (optional addend) or a GRU gate epilogue whose z | r split falls on a 128-channel
+// block boundary.  Plain: ReLU or identity.
 bool ofx_conv_wino_fits(const ofx_conv_desc* d) {
     const int cin = d->c0 + d->c1;
     const bool plain = d->epi == OFX_EPI_PLAIN && d->out != nullptr && d->ldo >= d->Cout && (d->act == OFX_ACT_NONE || d->act == OFX_ACT_RELU);
     bool shape_epi = false;
     if (is_3x3(d)) {
-        shape_epi = d->padH == 1 && d->padW == 1 && plain && !d->addend;
+        shape_epi = d->padH == 1 && d->padW == 1 && plain && !d->addend && (!d->res || d->ldres >= d->Cout) &&
+                    (!d->nmean || (d->nrstd && !d->in1 && ofx_aligned16(d->nmean) && ofx_aligned16(d->nrstd)));
     } else if (is_1d(d->KH, d->KW)) {
-        shape_epi = d->padH == d->KH / 2 && d->padW == d->KW / 2 &&
+        shape_epi = d->padH == d->KH / 2 && d->padW == d->KW / 2 && !d->nmean && !d->res &&
                     (plain || (d->epi == OFX_EPI_GRU_ZR && (d->Cout / 2) % 128 == 0) || d->epi == OFX_EPI_GRU_Q);
     }
     return shape_epi && d->precision == OFX_PREC_FP32 && (d->nz <= 1) && d->stride == 1 && d->Hout == d->Hin && d->Wout == d->Win &&
-           d->Hin % 8 == 0 && d->Win % 16 == 0 && cin % kWBK == 0 && d->c0 % kWBK == 0 && !d->nmean && !d->res &&
+           d->Hin % 8 == 0 && d->Win % 16 == 0 && cin % kWBK == 0 && d->c0 % kWBK == 0 &&
            d->wino_w != nullptr && ofx_aligned16(d->wino_w);
+}
+
+// Rows per image of the instance-norm partial sums the fused kernel leaves for a fitting `d` (one per 8x16 patch), or 0 when it
+// cannot produce them: 3x3 raw outputs only (identity, no residual), as the direct kernel's epilogue statistics.
+int ofx_conv_wino_stats_rows(const ofx_conv_desc* d) {
+    return is_3x3(d) && d->act == OFX_ACT_NONE && !d->res ? (d->Hin / 8) * (d->Win / 16) : 0;
 }
 
 // Whether the grid fills the chip enough for the fused kernel to beat the direct kernels and their small-grid schedules: 3x3, at
@@ -470,12 +557,16 @@ double ofx_conv_wino_flops(const ofx_conv_desc* d) {
     return 2.0 * wino_points(d) * ((double)d->B * d->Hout * d->Wout / 4.0) * (double)(d->c0 + d->c1) * d->Cout;
 }
 
-// The caller has validated the descriptor (ofx_conv2d_alpha) and ofx_conv_wino_fits(d).
-int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, hipStream_t s) {
+// The caller has validated the descriptor (ofx_conv2d_alpha) and ofx_conv_wino_fits(d).  stats: null, or room for the partial
+// sums of ofx_conv_wino_stats_rows(d) > 0 rows per image (the caller has checked the size).
+int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, float* stats, hipStream_t s) {
+    OFX_REQUIRE(!stats || ofx_conv_wino_stats_rows(d) > 0, OFX_EINVAL);
     WinoK k;
     k.in0 = d->in0; k.in1 = d->in1; k.u = d->wino_w; k.scale = d->scale; k.shift = d->shift; k.addend = d->addend; k.out = d->out;
+    k.res = d->res; k.nmean = d->nmean; k.nrstd = d->nrstd; k.stats = stats;
     k.aux_z = d->aux_z; k.aux_rh = d->aux_rh; k.aux_h = d->aux_h;
     k.ld0 = d->ld0; k.c0 = d->c0; k.ld1 = d->ld1; k.cin = d->c0 + d->c1; k.ldo = d->ldo; k.ldadd = d->ldadd; k.ldh = d->ldh;
+    k.ldres = d->ldres;
     k.H = d->Hin; k.W = d->Win; k.Cout = d->Cout; k.act = d->act;
     const int cblk = wino_cblk(d);
     k.nblk = (d->Cout + cblk - 1) / cblk;
@@ -492,10 +583,7 @@ int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, hipStream_t s) {
     k.bytes0 = (int)ext0; k.bytes1 = (int)ext1; k.bytesu = (int)extu;
     k.alpha = alpha;
     const dim3 grid((unsigned)(k.mtiles * k.nblk), 1, 1), block(256, 1, 1);
-    if (is_3x3(d)) {
-        OFX_LAUNCH(wino_conv_kernel, grid, block, s, k);
-        return ofx_launch_status();
-    }
+    if (is_3x3(d)) return launch3x3(k, grid, block, s);
     return d->KH == 5 ? launch15<true>(k, d->epi, grid, block, s) : launch15<false>(k, d->epi, grid, block, s);
 }
 

@@ -433,3 +433,7 @@ int ofx_inorm_finalize_part(const float* part, float* mean, float* rstd, int B, 
     return ofx_launch_status();
 }
 
+extern "C" int ofx_inorm_finalize(const float* part, float* mean, float* rstd, int B, int rows, long HW, int C, float eps, void* stream) {
+    return ofx_inorm_finalize_part(part, mean, rstd, B, rows, HW, C, eps, (hipStream_t)stream);
+}
+

@@ -59,17 +59,16 @@ static inline int ofx_launch_status() {
 // conv.hip: ofx_conv2d with an extra scalar multiplier on the accumulator (out = act(acc*alpha*scale + shift))
 extern "C" int ofx_conv2d_alpha(const ofx_conv_desc* d, float alpha, void* stream);
 // conv_wino.hip: the fused Winograd paths of ofx_conv2d, F(2x2,3x3) for 3x3 and F(4,5) for 1x5 / 5x1 layers, picked from KH / KW
-// (shape test, whether the grid is large enough to take it, executed FLOPs, launch)
+// (shape test, whether the grid is large enough to take it, rows per image of its epilogue statistics, executed FLOPs, launch)
 bool ofx_conv_wino_fits(const ofx_conv_desc* d);
 bool ofx_conv_wino_pays(const ofx_conv_desc* d);
+int ofx_conv_wino_stats_rows(const ofx_conv_desc* d);
 double ofx_conv_wino_flops(const ofx_conv_desc* d);
-int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, hipStream_t s);
+int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, float* stats, hipStream_t s);
 // conv.hip: the blocked correlation volume GEMM that also writes pyramid level 1 from its accumulators
 int ofx_conv2d_volpool(const ofx_conv_desc* d, float alpha, float* pool_out, long pool_zs, int wb0, int wb1, int slice1, void* stream);
 
-// conv.hip / net_misc.hip: instance-norm statistics out of the convolution epilogue (rows_per_image = 0: not produced, use
-// ofx_inorm_stats) and their per-image reduction
-int ofx_conv2d_stats(const ofx_conv_desc* d, float* part, size_t part_floats, int* rows_per_image, void* stream);
+// net_misc.hip: the per-image reduction of ofx_conv2d_stats' partials (ofx.h, ofx_inorm_finalize) with an optional
 // gamma / beta (both or neither): an affine folded into the (mean, rstd) pair, (x - mean') * rstd' = (x - mu) * rs * gamma + beta
 int ofx_inorm_finalize_part(const float* part, float* mean, float* rstd, int B, int rows, long HW, int C, float eps, hipStream_t s,
                             const float* gamma = nullptr, const float* beta = nullptr);

@@ -36,7 +36,8 @@ struct ConvW {
     float* wsplit3 = nullptr; // ... and into (hi, mid | lo) for the bf16x6 mode (ofx_split_conv_weight3: 1.5 x the floats)
     float* scale = nullptr;   // [Cout] or null
     float* shift = nullptr;   // [Cout] or null
-    float* wino = nullptr;    // 3x3 update-block layers: the Winograd F(2x2,3x3) operand (ofx_wino_conv_weight); the GRU's
+    float* wino = nullptr;    // stride-1 3x3 layers (update block, mask.0, the encoders' residual stages): the Winograd F(2x2,3x3)
+                              // operand (ofx_wino_conv_weight); the GRU's
                               // per-iteration 1x5 / 5x1 layers: the F(4,5) operand (ofx_wino15_conv_weight); or null
     int cout = 0, cin = 0, cin_pad = 0, kh = 0, kw = 0;
     long kpad = 0;
@@ -306,6 +307,15 @@ int build_encoder(ofx_raft* r, const std::map<std::string, HostTensor>& sd, cons
             st = add_conv(r, sd, p + ".conv2", pa + ".conv2", 0, B(pb + ".norm2"), 1.f);
             if (!st) st = A(pb + ".norm2");
             if (st) return st;
+            // the stride-1 3x3 layers also get the Winograd F(2x2,3x3) operand: every conv2, and conv1 but for the first block of
+            // a strided stage (conv.hip takes the fused kernel when the grid fills the chip).  OFX_CONV_NO_WINOGRAD_ENC, read once per
+            // process at the first engine build: never here
+            static const bool no_wino_enc = getenv("OFX_CONV_NO_WINOGRAD_ENC") != nullptr;
+            if (!no_wino_enc) {
+                if (li == 1 || bi == 1) st = add_wino(r, sd, {p + ".conv1"}, {}, pa + ".conv1");
+                if (!st) st = add_wino(r, sd, {p + ".conv2"}, {}, pa + ".conv2");
+                if (st) return st;
+            }
             if (li > 1 && bi == 0) {
                 st = add_conv(r, sd, p + ".downsample.0", pa + ".down", 0, B(pb + ".norm3"), 1.f);
                 if (!st) st = A(pb + ".norm3");
@@ -846,6 +856,7 @@ int ofx_raft_create(const ofx_tensor* tensors, int n, ofx_raft** out) {
     if (!st) st = add_wino(r, sd, {std::string(ub) + "flow_head.conv1"}, {}, "fh1");
     if (!st) st = add_conv(r, sd, std::string(ub) + "flow_head.conv2", "fh2", 0, "", 1.f);
     if (!st) st = add_conv(r, sd, std::string(ub) + "mask.0", "mask0", 0, "", 1.f);
+    if (!st) st = add_wino(r, sd, {std::string(ub) + "mask.0"}, {}, "mask0");
     if (!st) st = add_conv(r, sd, std::string(ub) + "mask.2", "mask2", 0, "", 0.25f);
     for (int i = 0; i < 2 && !st; ++i) {
         if (hipStreamCreateWithFlags(&r->aux[i], hipStreamNonBlocking) != hipSuccess) st = OFX_ENODEV;

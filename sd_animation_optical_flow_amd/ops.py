@@ -293,15 +293,17 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
                 nmean: Optional[torch.Tensor] = None, nrstd: Optional[torch.Tensor] = None, tile: int = 0,
                 precision: str = "fp32", splitk_ws: Optional[torch.Tensor] = None, pad: Optional[Tuple[int, int]] = None,
                 out_hw: Optional[Tuple[int, int]] = None, addend: Optional[torch.Tensor] = None,
-                wino_w: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_off: int = 0) -> torch.Tensor:
+                wino_w: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_off: int = 0,
+                stats_part: Optional[torch.Tensor] = None):
     """Plain-epilogue convolution: x [B,H,W,C0] (+ optional second channel segment x2 [B,H,W,C1]),
     'same' padding (k//2) unless `pad` = (top, left) is given; `out_hw` overrides the output size (taps beyond the
     input read zeros: pad (0, 0) with out_hw = (H/2, W/2) is the VAE's F.pad(x, (0,1,0,1)) + stride-2 convolution).
     `addend` [B,Hout,Wout,cout] is added before the activation (`res` adds after it and applies ReLU).
     `wino_w` (wino_conv_weight / wino15_conv_weight, on the device) lets a qualifying 3x3 / 1x5 / 5x1 layer run the fused
     Winograd kernel (tile = TILE_WINOGRAD forces it).  `out` [B,Hout,Wout,C >= out_off + cout]: write channels
-    [out_off, out_off + cout) of it.
-    Returns [B,Hout,Wout,cout], or `out`."""
+    [out_off, out_off + cout) of it.  `stats_part` (f32 on the device): run ofx_conv2d_stats, which leaves the per-channel
+    (sum, sum of squares) partials of the outputs there when the launch can produce them ([B][rows][cout][2]; see inorm_finalize).
+    Returns [B,Hout,Wout,cout], or `out`; with `stats_part`, (that, rows per image), rows = 0 when none were produced."""
     x = _chk(x, "x", torch.float32)
     B, H, W, c0 = x.shape
     d = ConvDesc()
@@ -341,8 +343,24 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
     if splitk_ws is not None:       # uint8 scratch whose first 64 KiB are zero (see ofx_conv_desc.splitk_ws): allows split-K
         ws = _chk(splitk_ws, "splitk_ws", torch.uint8)
         d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), ws.numel()
+    if stats_part is not None:
+        part = _chk(stats_part, "stats_part", torch.float32)
+        rows = C.c_int(0)
+        check(_lib.lib().ofx_conv2d_stats(C.byref(d), C.c_void_p(part.data_ptr()), part.numel(), C.byref(rows), _stream()),
+              "ofx_conv2d_stats")
+        return out, rows.value
     check(_lib.lib().ofx_conv2d(C.byref(d), _stream()), "ofx_conv2d")
     return out
+
+
+def inorm_finalize(part: torch.Tensor, B: int, rows: int, HW: int, C_: int, eps: float = 1e-5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """mean and 1/sqrt(var + eps) [B, C_] from the partials conv2d_nhwc(..., stats_part=part) left (rows per image, HW pixels per
+    image), reduced in a fixed order (ofx_inorm_finalize)."""
+    part = _chk(part, "part", torch.float32)
+    mean = torch.empty((B, C_), dtype=torch.float32, device=part.device)
+    rstd = torch.empty_like(mean)
+    check(_lib.lib().ofx_inorm_finalize(_ptr(part), _ptr(mean), _ptr(rstd), B, rows, HW, C_, float(eps), _stream()), "ofx_inorm_finalize")
+    return mean, rstd
 
 
 def flow_head(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, coords1: torch.Tensor, hx: torch.Tensor,

@@ -61,6 +61,13 @@ if os.environ.get("CONV_BENCH_WINO"):    # the fused Winograd F(2x2,3x3) kernel 
         ("3x3 128->64", 64, 64, 96, 128, 64, 3, 3, 1, 0),
     ]
     TILES = [0, 1]
+if os.environ.get("CONV_BENCH_WINO_ENC"):   # ... and on the encoders' stride-1 3x3 layers (65 images) with the epilogues they run, and mask.0
+    # 11th field, the epilogue: relu (cnet conv1, mask.0), res (cnet conv2: relu, then relu(y + res)), stats (fnet conv1: identity with
+    # the instance-norm partial sums, ofx_conv2d_stats), norm+stats (fnet conv2: relu(norm(x)) on the operand, partial sums)
+    SHAPES = [(f"enc 3x3 {c}->{c} @1/{s} {e}", 65, H, W, c, c, 3, 3, 1, 0, e)
+              for c, s, H, W in ((64, 2, 384, 256), (96, 4, 192, 128), (128, 8, 96, 64)) for e in ("relu", "res", "stats", "norm+stats")]
+    SHAPES.append(("mask.0 3x3 128->256", 64, 64, 96, 128, 256, 3, 3, 1, 0))
+    TILES = [0, 1]
 if os.environ.get('CONV_BENCH_TILES'):
     TILES = [int(t) for t in os.environ['CONV_BENCH_TILES'].split(',')]
 if os.environ.get("CONV_BENCH_ONLY"):
@@ -71,8 +78,11 @@ def run(libpath):
     lib = C.CDLL(libpath)
     lib.ofx_conv2d.restype = C.c_int
     lib.ofx_conv2d.argtypes = [C.POINTER(_lib.ConvDesc), C.c_void_p]
+    lib.ofx_conv2d_stats.restype = C.c_int
+    lib.ofx_conv2d_stats.argtypes = [C.POINTER(_lib.ConvDesc), C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.c_void_p]
     print("==", os.path.basename(libpath))
-    for name, B, H, W, ci, co, kh, kw, st, _ in SHAPES:
+    for name, B, H, W, ci, co, kh, kw, st, _, *epi in SHAPES:
+      epi = epi[0] if epi else "relu"
       for tile in TILES:
             x = torch.randn((B, H, W, ci), device="cuda")
             if os.environ.get("CONV_BENCH_ZERO"):       # power probe: same instruction stream on all-zero operands
@@ -92,21 +102,35 @@ def run(libpath):
                 d.wino_w = u.data_ptr()
             d.B, d.Hin, d.Win, d.Hout, d.Wout, d.Cout = B, H, W, H // st, W // st, co
             d.KH, d.KW, d.stride, d.padH, d.padW = kh, kw, st, kh // 2, kw // 2
-            d.act, d.epi, d.tile = 1, 0, tile
+            d.act, d.epi, d.tile = (0 if "stats" in epi else 1), 0, tile
+            keep = []   # buffers the descriptor points at
+            if epi == "res":
+                r = torch.randn_like(out)
+                keep.append(r)
+                d.res, d.ldres = r.data_ptr(), co
+            if "norm" in epi:
+                m, rs = torch.zeros((B, ci), device="cuda"), torch.ones((B, ci), device="cuda")
+                keep += [m, rs]
+                d.nmean, d.nrstd = m.data_ptr(), rs.data_ptr()
+            part = torch.empty((B * H * W * co // 16 + 4096,), device="cuda") if "stats" in epi else None   # room for the direct kernels' rows too
+            rows = C.c_int(0)
             d.precision = int(os.environ.get('CONV_BENCH_PREC', '0'))
             s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            call = (lambda: lib.ofx_conv2d_stats(C.byref(d), part.data_ptr(), part.numel(), C.byref(rows), s)) if part is not None \
+                else (lambda: lib.ofx_conv2d(C.byref(d), s))
             for _ in range(3):
-                assert lib.ofx_conv2d(C.byref(d), s) == 0
+                assert call() == 0
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             n = int(os.environ.get('CONV_BENCH_REPS', '10'))
             e0.record()
             for _ in range(n):
-                lib.ofx_conv2d(C.byref(d), s)
+                call()
             e1.record(); torch.cuda.synchronize()
             ms = e0.elapsed_time(e1) / n
             fl = 2.0 * B * (H // st) * (W // st) * co * K   # direct-convolution FLOPs for every tile (Winograd: "effective" rate)
-            print(f"  {name:<24} tile {tile:>9} {ms:8.3f} ms  {fl / ms / 1e9:7.1f} TFLOP/s")
+            extra = f"  stats rows {rows.value}" if part is not None else ""
+            print(f"  {name:<24} tile {tile:>9} {ms:8.3f} ms  {fl / ms / 1e9:7.1f} TFLOP/s{extra}")
 if __name__ == "__main__":
     libs = sys.argv[1:] or [_lib.LIB_PATH]
     for l in libs:
