@@ -274,14 +274,18 @@ long ofx_wino15_conv_weight(const float* w_oihw, int Cout, int Cin, int KH, int 
  * ofx_conv2d returns OFX_EINVAL for nz > 1, and for a precision outside OFX_PREC_FP32 .. OFX_PREC_BF16X6_W). */
 int ofx_split_conv_weight3(const float* packed, long n_floats, float* out);
 
-/* instance norm statistics over HW per (b,c): mean and 1/sqrt(var+eps) (biased var), NHWC input; C <= 256.
+/* instance norm statistics over HW per (b,c): mean and 1/sqrt(var+eps) (biased var), NHWC input with rows of ld >= C floats
+ * (ld > C: the statistics of a channel slice).  C % 4 == 0, C <= 256, ld % 4 == 0 and x 16-byte aligned: OFX_EALIGN otherwise.
  * scratch: max(B*64, min(B,7)*256) * C * 2 doubles (f64 partial sums per image slice), 8-byte aligned. */
 int ofx_inorm_stats(const float* x, int ld, float* mean, float* rstd, float* scratch,
                     int B, long HW, int C, float eps, void* stream);
 /* ofx_conv2d that also leaves per-channel (sum, sum of squares) partials of the outputs it writes in `part`, as
- * [B][*rows_per_image][Cout][2] floats, when the launch can produce them: fp32, plain epilogue, identity activation, no `res`, and
- * at most part_floats floats.  *rows_per_image = 0: not produced (use ofx_inorm_stats).  Both the direct and the fused Winograd
- * kernels write them, in a fixed order (repeats are bit-identical). */
+ * [B][*rows_per_image][Cout][2] floats, when the launch can produce them: plain epilogue, identity activation, no `res`, tiles
+ * that stay inside one image, and at most part_floats floats.  Every precision of the direct kernels produces them (the sums are
+ * fp32 sums of the stored fp32 outputs whatever the arithmetic of the products; the split-bf16 modes map the tile onto 128x128,
+ * 128x64 or 64x64 first, so their row count can differ from the fp32 launch of the same layer).  *rows_per_image = 0: not
+ * produced (use ofx_inorm_stats).  Both the direct and the fused Winograd kernels write them, in a fixed order (repeats are
+ * bit-identical). */
 int ofx_conv2d_stats(const ofx_conv_desc* d, float* part, size_t part_floats, int* rows_per_image, void* stream);
 /* mean and 1/sqrt(var+eps) (biased var) per (b,c) [B][C] from ofx_conv2d_stats' partials of HW pixels per image (the `rows` rows
  * of an image added in a fixed order) */

@@ -411,23 +411,31 @@ def conv2d_desc(d: ConvDesc) -> None:
     check(_lib.lib().ofx_conv2d(C.byref(d), _stream()), "ofx_conv2d")
 
 
-def inorm_stats(x: torch.Tensor, eps: float = 1e-5) -> Tuple[torch.Tensor, torch.Tensor]:
+def inorm_stats(x: torch.Tensor, eps: float = 1e-5, c_off: int = 0, c: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """mean and 1/sqrt(var + eps) [B, c] of x [B,H,W,ld] per image and channel (`ofx_inorm_stats`); `c_off` / `c` select the channel
+    slice [c_off, c_off + c) of the rows (c_off % 4 == 0; default: all ld channels)."""
     x = _chk(x, "x", torch.float32)
-    B, H, W, Cn = x.shape
+    B, H, W, ld = x.shape
+    Cn = ld - c_off if c is None else c
+    if c_off < 0 or Cn <= 0 or c_off + Cn > ld:
+        raise RuntimeError(f"channel slice [{c_off}, {c_off + Cn}) outside the {ld} channels of x")
     mean = torch.empty((B, Cn), dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
     scratch = torch.empty((max(B * 64, min(B, 7) * 256) * Cn * 2,), dtype=torch.float64, device=x.device)
-    check(_lib.lib().ofx_inorm_stats(_ptr(x), Cn, _ptr(mean), _ptr(rstd), _ptr(scratch), B, H * W, Cn, float(eps), _stream()),
-          "ofx_inorm_stats")
+    check(_lib.lib().ofx_inorm_stats(C.c_void_p(x.data_ptr() + 4 * c_off), ld, _ptr(mean), _ptr(rstd), _ptr(scratch), B, H * W, Cn,
+                                     float(eps), _stream()), "ofx_inorm_stats")
     return mean, rstd
 
 
 def inorm_apply(x, mean, rstd, res=None, res_mean=None, res_rstd=None, relu=True) -> torch.Tensor:
+    """`ofx_inorm_apply`.  relu: True / False (ReLU or not; a residual merge always applies it), or the integer mode of the C entry
+    point -- bit 0 the ReLU, bit 1 (relu = 3) a ReLU on the normalised residual as well."""
     x = _chk(x, "x", torch.float32)
     B, H, W, Cn = x.shape
     out = torch.empty_like(x)
+    mode = (1 if relu else 0) if isinstance(relu, bool) else int(relu)
     check(_lib.lib().ofx_inorm_apply(_ptr(x), _ptr(mean), _ptr(rstd), _ptr(res), _ptr(res_mean), _ptr(res_rstd), _ptr(out),
-                                     B, H * W, Cn, 1 if relu else 0, _stream()), "ofx_inorm_apply")
+                                     B, H * W, Cn, mode, _stream()), "ofx_inorm_apply")
     return out
 
 
