@@ -15,13 +15,16 @@
 // much traffic as it saves multiplies ("Winograd").  Both kernels share one scaffold:
 //   * a workgroup owns one 8x16-pixel output patch -- 32 tiles of 2x2, 1x4 (1x5 layers, along W) or 4x1 (5x1 layers, along H) --
 //     and 64 (2D) or 128 (1D) output channels;
-//   * per 16-channel slab the input halo is staged in LDS once (buffer descriptors return the zero padding), every thread applies
-//     the input transform to one (tile, channel pair) -- additions and constant scalings -- and writes the transformed values to LDS;
+//   * per 16-channel slab the input halo is staged in LDS once (buffer descriptors return the zero padding);
 //   * per transform point the GEMM [32 tiles x 16 channels] x [16 channels x 32 outputs] runs on v_mfma_f32_32x32x2_f32.  2D: wave w
 //     owns the four points (w, 0..3) of the 4x4 grid and 64 outputs; 1D: wave w owns all 8 points and 32 outputs;
+//   * input transform -- additions and constant scalings.  1D: every thread transforms one (tile, channel pair) and writes the
+//     transformed values to LDS, where the waves read their A fragments (each wave needs all 8 points).  2D: a wave's row of the
+//     point grid needs two rows of the tile's window only, so each lane forms its own A operands in registers straight from the
+//     halo (wino3x3_slabs): no transformed tile in LDS, the halo double-buffered instead, one barrier per slab;
 //   * the pre-transformed weights U (host, float64, one rounding: ofx_wino_conv_weight / ofx_wino15_conv_weight) are stored in the
-//     MFMA's B-operand lane order, so every wave loads its own 1 KB fragments straight into registers, one slab ahead, with fully
-//     contiguous loads (64 registers in both kernels);
+//     MFMA's B-operand lane order, so every wave loads its own 1 KB fragments straight into registers with fully contiguous loads,
+//     one slab ahead (1D, 64 registers) or one 8-channel step ahead (2D, 32 registers);
 //   * output side, 2D: each wave folds its four points along the transform's column (A^T from the right), the partial rows meet in
 //     LDS, and the row fold (A^T from the left) feeds the plain epilogue (scale / shift, ReLU, strided store).  1D: a lane holds the
 //     8 point values of each of its (tile, channel) elements, so A^T runs in registers and the epilogue starts straight from them:
@@ -40,18 +43,30 @@ constexpr int kWBK = 16;                    // channels per slab
 constexpr int kLDV = kWBK + 4;
 constexpr int kOOB = 0x7FFFFFF0;
 
-// Input halo of an 8x16 output patch: W x H pixels from (y0 + Y0, x0 + X0), staged at a pixel stride of LDH floats.  The strides
-// put a half-wave's transform reads in disjoint banks: 3x3, 10 x 18 at 24 (float2 reads of four tiles two pixels apart); 1x5, 8 x 20
-// at 20 (four tiles 4 pixels apart, 16 floats each); 5x1, 12 x 16 at 16 (four tiles 1 pixel apart).
-template <int W_, int H_, int LDH, int Y0, int X0> struct Halo {
-    static constexpr int W = W_, H = H_, ldh = LDH, y_org = Y0, x_org = X0;
+// Input halo of an 8x16 output patch: W x H pixels from (y0 + Y0, x0 + X0); pixel `pix` (row-major) is staged at float at(pix).
+template <int W_, int H_, int Y0, int X0> struct HaloGeom {
+    static constexpr int W = W_, H = H_, y_org = Y0, x_org = X0;
     static constexpr int pix = W * H;                       // 180 / 160 / 192
     static constexpr int items = pix * (kWBK / 4);          // float4 pieces per slab: 720 / 640 / 768
     static constexpr int slots = (items + 255) / 256;       // per thread: 3
-    static constexpr int floats = pix * ldh;                // 4320 / 3200 / 3072
 };
-using Halo3x3 = Halo<18, 10, 24, -1, -1>;
-template <bool VERT> using Halo15 = Halo<VERT ? 16 : 20, VERT ? 12 : 8, VERT ? 16 : 20, VERT ? -2 : 0, VERT ? 0 : -2>;
+// F(4, 5): a pixel stride that puts a half-wave's transform reads in disjoint banks: 1x5, 8 x 20 at 20 (four tiles 4 pixels apart,
+// 16 floats each); 5x1, 12 x 16 at 16 (four tiles 1 pixel apart).
+template <bool VERT> struct Halo15 : HaloGeom<VERT ? 16 : 20, VERT ? 12 : 8, VERT ? -2 : 0, VERT ? 0 : -2> {
+    static constexpr int ldh = VERT ? 16 : 20;
+    static constexpr int floats = Halo15::pix * ldh;        // 3200 / 3072
+    __device__ static int at(int pix) { return pix * ldh; }
+};
+// F(2x2, 3x3), 10 x 18: the pixels (x, x + 1), x even, are 32 contiguous floats, pairs 36 floats apart, rows 336.  Both accesses
+// of the slab loop are then free of bank conflicts (tools/lds_bank_model.py, profiles/r13_lds_bank_model.txt): the staging
+// ds_write_b128 (groups of 8 lanes = one pixel pair = 32 banks) and the operand ds_read_b128 (groups of 16 lanes = four runs of four
+// tiles, two pixels apart along a row, from all four tile rows: 16 float4 in 16 different bank quads).
+struct Halo3x3 : HaloGeom<18, 10, -1, -1> {
+    static constexpr int lpair = 36, lrow = 336;
+    static constexpr int floats = H * lrow;                 // 3360
+    __device__ static int at(int y, int x) { return y * lrow + (x >> 1) * lpair + (x & 1) * 16; }
+    __device__ static int at(int pix) { return at(pix / W, pix % W); }
+};
 
 struct WinoK {
     const float* in0;
@@ -96,15 +111,114 @@ __device__ __forceinline__ Patch wino_patch(const WinoK& p) {
     return {nb, pb, py * 8, (trem - py * p.tpr) * 16};
 }
 
-// The slab pipeline of both kernels.  ALG is the algorithm's policy: its halo geometry ALG::HALO; the wave's share of the products,
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+// Halo staging: item i = tid + 256 k = (pixel i / 4, float4 slot i % 4) of a slab, pixels row-major over the halo.
+// issue(cb) starts the loads of slab cb into registers (buffer descriptors return the zero padding), store(Hs) puts them into the
+// halo buffer at Hs.  NORM: the operand is relu((x - mean) * rstd) of image pt.pb (single segment), applied as the halo is stored;
+// the zero padding stays zero.
+template <class HALO, bool NORM> struct HaloStage {
+    const WinoK& p;
+    const int pb, tid;
+    const float* in1s;
+    int bytes1s;
+    int hpix[HALO::slots];
+    unsigned hok = 0;
+    int hq;                          // byte offset of this thread's float4 slot (256 % 4 == 0: the same for every k)
+    float4 pa[HALO::slots];
+    float4 pmu, prs;                 // NORM: mean / rstd of this thread's four channels of the slab in flight
+
+    __device__ __forceinline__ HaloStage(const WinoK& p_, const Patch& pt, int tid_) : p(p_), pb(pt.pb), tid(tid_) {
+        in1s = p.in1 ? p.in1 : p.in0;
+        bytes1s = p.in1 ? p.bytes1 : p.bytes0;
+#pragma unroll
+        for (int k = 0; k < HALO::slots; ++k) {
+            const int i = tid + 256 * k;
+            const int pix = i >> 2;
+            const int hy = pix / HALO::W, hx = pix - hy * HALO::W;
+            const int gy = pt.y0 + HALO::y_org + hy, gx = pt.x0 + HALO::x_org + hx;
+            const bool ok = i < HALO::items && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
+            hpix[k] = ok ? (pt.pb * p.H + gy) * p.W + gx : 0;
+            hok |= (ok ? 1u : 0u) << k;
+        }
+        hq = (tid & 3) * 16;
+    }
+    __device__ __forceinline__ void issue(int cb) {
+        const int c = cb * kWBK;
+        const bool s0 = c < p.c0;    // wave-uniform
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(s0 ? p.in0 : in1s), (short)0, s0 ? p.bytes0 : bytes1s, 0x00020000);
+        const int so = (s0 ? c : c - p.c0) * 4;
+        const int ldb = (s0 ? p.ld0 : p.ld1) * 4;
+#pragma unroll
+        for (int k = 0; k < HALO::slots; ++k) {
+            const int vo = ((hok >> k) & 1u) ? hpix[k] * ldb + hq : kOOB;
+            v4i t = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, 0);
+            pa[k] = *reinterpret_cast<float4*>(&t);
+        }
+        if constexpr (NORM) {
+            const long at = (long)pb * p.c0 + c + (tid & 3) * 4;
+            pmu = *reinterpret_cast<const float4*>(p.nmean + at);
+            prs = *reinterpret_cast<const float4*>(p.nrstd + at);
+        }
+    }
+    __device__ __forceinline__ void store(float* Hs) const {
+#pragma unroll
+        for (int k = 0; k < HALO::slots; ++k) {
+            const int i = tid + 256 * k;
+            if (HALO::slots * 256 > HALO::items && k == HALO::slots - 1 && i >= HALO::items) break;
+            float4 v = pa[k];
+            if constexpr (NORM) {   // as the direct kernel's a_commit (conv.hip): padding is applied to the normalised map
+                v.x = fmaxf((v.x - pmu.x) * prs.x, 0.f);
+                v.y = fmaxf((v.y - pmu.y) * prs.y, 0.f);
+                v.z = fmaxf((v.z - pmu.z) * prs.z, 0.f);
+                v.w = fmaxf((v.w - pmu.w) * prs.w, 0.f);
+                if (!((hok >> k) & 1u)) v = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            *reinterpret_cast<float4*>(&Hs[HALO::at(i >> 2) + (i & 3) * 4]) = v;
+        }
+    }
+};
+
+// The pre-transformed weights: point pt, 32-channel block blk, 8-channel chunk c8 -> one contiguous 1 KB fragment, 16 bytes per lane
+struct WinoU {
+    const __amdgpu_buffer_rsrc_t rs;
+    const int nb32, c8n, wlane;
+    __device__ __forceinline__ WinoU(const WinoK& p, int lane)
+        : rs(__builtin_amdgcn_make_buffer_rsrc((void*)p.u, (short)0, p.bytesu, 0x00020000)), nb32(p.nb32), c8n(p.cin >> 3), wlane(lane * 16) {}
+    __device__ __forceinline__ float4 load(int pt, int blk, int c8) const {
+        const int so = ((pt * nb32 + blk) * c8n + c8) * 1024;   // scalar
+        v4i t = __builtin_amdgcn_raw_buffer_load_b128(rs, wlane, so, 0);
+        return *reinterpret_cast<float4*>(&t);
+    }
+};
+
+template <int P, int NT> __device__ __forceinline__ void wino_zero(f32x16 (&acc)[P][NT]) {
+#pragma unroll
+    for (int q = 0; q < P; ++q)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[q][nt][e] = 0.f;
+}
+
+// One 8-channel step of a point's product: A = a (tile lane & 31, channels 4 (lane >> 5) + 0..3 of the step), B = b
+__device__ __forceinline__ void wino_mfma4(f32x16& acc, const float4& a, const float4& b) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+}
+
+// The staged slab pipeline (F(4, 5)).  ALG is the algorithm's policy: its halo geometry ALG::HALO; the wave's share of the products,
 // P transform points from ALG::pt0(wave) on and NT 32-channel blocks of u from ALG::blk0(nb, wave) on; and its input transform,
 // built from (Hs, Vs, tid, wave), whose call transforms the calling thread's (tile, channel pair) from the halo in Hs into Vs
-// ([point][tile][channel] at row stride kLDV).  The wave's point-wise products accumulate into acc.  NORM: the operand is
-// relu((x - mean) * rstd) of image pt.pb (single segment), applied as the halo is staged; the zero padding stays zero.
-template <class ALG, bool NORM = false>
-__device__ __forceinline__ void wino_slabs(const WinoK& p, const Patch& pt, float* Hs, float* Vs, int tid, int wave,
+// ([point][tile][channel] at row stride kLDV).  The wave's point-wise products accumulate into acc, weights one slab ahead in
+// registers.  It shares the halo geometry, the patch remap and the operand order with wino3x3_slabs but spells its staging and
+// weight loads out: routed through HaloStage / WinoU the compiler schedules the 5x1 kernels 1.5-4 % slower
+// (profiles/r13_wino_rows_kernel_stats.txt), and this text compiles to the instructions the GRU layers were measured with.
+template <class ALG>
+__device__ __forceinline__ void wino_slabs_staged(const WinoK& p, const Patch& pt, float* Hs, float* Vs, int tid, int wave,
                                            f32x16 (&acc)[ALG::P][ALG::NT]) {
-    typedef int v4i __attribute__((ext_vector_type(4)));
     using HALO = typename ALG::HALO;
     constexpr int P = ALG::P, NT = ALG::NT;
     const int lane = tid & 63;
@@ -126,7 +240,6 @@ __device__ __forceinline__ void wino_slabs(const WinoK& p, const Patch& pt, floa
     }
     const int hq = (tid & 3) * 16;   // byte offset of this thread's float4 slot (256 % 4 == 0: the same for every k)
     float4 pa[HALO::slots];
-    float4 pmu, prs;                 // NORM: mean / rstd of this thread's four channels of the slab in flight
     auto a_issue = [&](int cb) __attribute__((always_inline)) {
         const int c = cb * kWBK;
         const bool s0 = c < p.c0;    // wave-uniform
@@ -138,11 +251,6 @@ __device__ __forceinline__ void wino_slabs(const WinoK& p, const Patch& pt, floa
             const int vo = ((hok >> k) & 1u) ? hpix[k] * ldb + hq : kOOB;
             v4i t = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, 0);
             pa[k] = *reinterpret_cast<float4*>(&t);
-        }
-        if constexpr (NORM) {
-            const long at = (long)pt.pb * p.c0 + c + (tid & 3) * 4;
-            pmu = *reinterpret_cast<const float4*>(p.nmean + at);
-            prs = *reinterpret_cast<const float4*>(p.nrstd + at);
         }
     };
 
@@ -185,14 +293,7 @@ __device__ __forceinline__ void wino_slabs(const WinoK& p, const Patch& pt, floa
             const int i = tid + 256 * k;
             if (HALO::slots * 256 > HALO::items && k == HALO::slots - 1 && i >= HALO::items) break;
             float4 v = pa[k];
-            if constexpr (NORM) {   // as the direct kernel's a_commit (conv.hip): padding is applied to the normalised map
-                v.x = fmaxf((v.x - pmu.x) * prs.x, 0.f);
-                v.y = fmaxf((v.y - pmu.y) * prs.y, 0.f);
-                v.z = fmaxf((v.z - pmu.z) * prs.z, 0.f);
-                v.w = fmaxf((v.w - pmu.w) * prs.w, 0.f);
-                if (!((hok >> k) & 1u)) v = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            *reinterpret_cast<float4*>(&Hs[(i >> 2) * HALO::ldh + (i & 3) * 4]) = v;
+            *reinterpret_cast<float4*>(&Hs[HALO::at(i >> 2) + (i & 3) * 4]) = v;
         }
         __syncthreads();
         xf();
@@ -220,52 +321,75 @@ __device__ __forceinline__ void wino_slabs(const WinoK& p, const Patch& pt, floa
     }
 }
 
+__device__ __forceinline__ float4 operator+(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ __forceinline__ float4 operator-(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
+
+// The slab pipeline of F(2x2, 3x3): the MFMAs' A operands come straight from the halo.  Wave i owns row i of the 4x4 point grid,
+// and row i of B^T d needs two rows of the tile's 4x4 window only: d0 - d2, d1 + d2, d2 - d1, d1 - d3.  Per 8-channel step a lane
+// (tile lane & 31, channels 4 (lane >> 5) + 0..3, as the weights' k order requires) reads those two rows over the window's four
+// columns, forms the row sum and from it the row's four points t0 - t2, t1 + t2, t2 - t1, t1 - t3 -- over the four waves the same
+// additions, in the same order, as a transform of whole tiles would make, none of them twice.  No transformed tile in LDS; the
+// halo is double-buffered instead (slab cb + 1 is stored while slab cb is multiplied), so a slab has one barrier.  The weights
+// run one 8-channel step ahead in registers.  NORM: as HaloStage.
+template <bool NORM>
+__device__ __forceinline__ void wino3x3_slabs(const WinoK& p, const Patch& pt, float* Hs, int tid, int wave, f32x16 (&acc)[4][2]) {
+    using HALO = Halo3x3;
+    const int lane = tid & 63;
+    HaloStage<HALO, NORM> hs(p, pt, tid);
+    const WinoU u(p, lane);
+    const int pt0 = 4 * wave, blk0 = 2 * pt.nb;
+    float4 wr[4][2];
+    wino_zero(acc);
+
+    // rows ra, rb of the window and the sign of the second: t = d[ra] + sg * d[rb] (an fma by +-1 rounds as the sum itself)
+    const int ra = wave == 0 ? 0 : wave == 2 ? 2 : 1, rb = wave == 2 ? 1 : wave == 3 ? 3 : 2;
+    const float sg = wave == 1 ? 1.0f : -1.0f;
+    const int tile = lane & 31;
+    const int at0 = HALO::at(2 * (tile >> 3), 2 * (tile & 7)) + 4 * (lane >> 5);
+    const int at_a = at0 + ra * HALO::lrow, at_b = at0 + rb * HALO::lrow;
+
+    const int CB = p.cin / kWBK;
+    hs.issue(0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) wr[q][nt] = u.load(pt0 + q, blk0 + nt, 0);
+    hs.store(Hs);
+    hs.issue(CB > 1 ? 1 : 0);
+    for (int cb = 0; cb < CB; ++cb) {
+        const float* const H = Hs + (cb & 1) * HALO::floats;
+        __syncthreads();   // slab cb is in H, and every wave has left the other buffer
+        hs.store(Hs + (~cb & 1) * HALO::floats);
+        // the last slabs re-issue the last one (and store it where nothing reads it): no branch, loads stay in bounds
+        hs.issue(cb + 2 < CB ? cb + 2 : CB - 1);
+        __builtin_amdgcn_sched_barrier(0);   // the loads go ahead of the products, as in wino_slabs_staged
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            float4 t[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float4 a = *reinterpret_cast<const float4*>(H + at_a + HALO::at(0, c) + 8 * ks);
+                const float4 b = *reinterpret_cast<const float4*>(H + at_b + HALO::at(0, c) + 8 * ks);
+                t[c] = make_float4(__builtin_fmaf(sg, b.x, a.x), __builtin_fmaf(sg, b.y, a.y), __builtin_fmaf(sg, b.z, a.z),
+                                   __builtin_fmaf(sg, b.w, a.w));
+            }
+            const float4 v[4] = {t[0] - t[2], t[1] + t[2], t[2] - t[1], t[1] - t[3]};
+            const int c8 = 2 * cb + ks + 1 < 2 * CB ? 2 * cb + ks + 1 : 2 * cb + ks;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) {
+                    wino_mfma4(acc[q][nt], v[q], wr[q][nt]);
+                    wr[q][nt] = u.load(pt0 + q, blk0 + nt, c8);   // the next step's fragment: three quarters of a step hide the load
+                }
+        }
+    }
+}
+
 __device__ __forceinline__ float2 f2(float a, float b) { return make_float2(a, b); }
 __device__ __forceinline__ float2 operator+(float2 a, float2 b) { return f2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 operator-(float2 a, float2 b) { return f2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ float2 operator*(float s, float2 a) { return f2(s * a.x, s * a.y); }
-
-// F(2x2, 3x3): wave w = the four points (w, 0..3) of the 4x4 grid x both 32-channel halves of the workgroup's 64 outputs.  Input
-// transform B^T d B of one (tile, channel pair): 4x4 float2 window of the halo at src -> the 16 points at dst; thread = (tile row =
-// wave, tile column tx, channel pair cp).
-struct Wino3x3 {
-    using HALO = Halo3x3;
-    static constexpr int P = 4, NT = 2;
-    __device__ static int pt0(int wave) { return 4 * wave; }
-    __device__ static int blk0(int nb, int) { return 2 * nb; }
-    const float* src;
-    float* dst;
-    __device__ __forceinline__ Wino3x3(const float* Hs, float* Vs, int tid, int wave) {
-        const int ttx = (tid & 63) >> 3, tcp = tid & 7;
-        src = Hs + (2 * wave * HALO::W + 2 * ttx) * HALO::ldh + 2 * tcp;
-        dst = Vs + (wave * 8 + ttx) * kLDV + 2 * tcp;
-    }
-    __device__ __forceinline__ void operator()() const {
-        float2 d[4][4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) d[r][c] = *reinterpret_cast<const float2*>(src + (r * HALO::W + c) * HALO::ldh);
-        float2 t[4][4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {           // B^T d
-            t[0][c] = d[0][c] - d[2][c];
-            t[1][c] = d[1][c] + d[2][c];
-            t[2][c] = d[2][c] - d[1][c];
-            t[3][c] = d[1][c] - d[3][c];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {           // (B^T d) B
-            float2 v[4];
-            v[0] = t[i][0] - t[i][2];
-            v[1] = t[i][1] + t[i][2];
-            v[2] = t[i][2] - t[i][1];
-            v[3] = t[i][1] - t[i][3];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) *reinterpret_cast<float2*>(dst + (i * 4 + j) * 32 * kLDV) = v[j];
-        }
-    }
-};
 
 // F(4, 5): wave w = all 8 points x the w-th 32 of the workgroup's 128 outputs.  Input transform B^T d of one (tile, channel pair):
 // 8 float2 taps at src -> the 8 points at dst; thread = (tile tid / 8, channel pair tid % 8).  VERT = false (1x5): tile t = (row
@@ -314,33 +438,31 @@ template <bool VERT> struct Wino15 {
 
 // ---- F(2x2, 3x3): 64 output channels per workgroup, wave w = points (w, 0..3) x both 32-channel halves
 constexpr int kLDX = 32;                                    // output exchange: [wave][column fold][tile][32 channels]
-constexpr int kVF2 = 16 * 32 * kLDV;                        // 10240 floats
-constexpr int kSmem2 = Halo3x3::floats + kVF2;              // 58 240 bytes: two workgroups per CU
 constexpr int kXF = 4 * 2 * 32 * kLDX;                      // 8192 floats
-static_assert(kXF + 2 * 4 * 32 * 2 <= kSmem2, "exchange and statistics must fit");   // reuse the halo / V space after the last slab
+constexpr int kSX = 2 * 4 * 32 * 2;                         // STATS: [32-channel half][wave][channel][sum, sum of squares]
+// two halo buffers; after the last slab the exchange and the statistics reuse the space: 34 816 bytes, two workgroups per CU
+constexpr int kSmem2 = 2 * Halo3x3::floats > kXF + kSX ? 2 * Halo3x3::floats : kXF + kSX;
 
-// NORM: relu(norm(.)) on the operand (wino_slabs).  RES: the residual merge relu(y + res) after the activation, as the direct
+// NORM: relu(norm(.)) on the operand (wino3x3_slabs).  RES: the residual merge relu(y + res) after the activation, as the direct
 // kernel's plain epilogue.  STATS: per (patch, output channel) sum and sum of squares of the stored values, [B][tpi][Cout][2] for
 // ofx_inorm_finalize_part, in a fixed order.  <false, false, false> is the update block's kernel.
 template <bool NORM, bool RES, bool STATS>
 __global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
     __shared__ __attribute__((aligned(16))) float smem[kSmem2];
-    float* const Hs = smem;
-    float* const Vs = smem + Halo3x3::floats;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the weight offsets stay scalar too
     const Patch pt = wino_patch(p);
     f32x16 acc[4][2];
-    wino_slabs<Wino3x3, NORM>(p, pt, Hs, Vs, tid, wave, acc);
+    wino3x3_slabs<NORM>(p, pt, smem, tid, wave, acc);
 
     // ---- output transform and plain epilogue, one 32-channel half at a time through LDS
     const float act_lo = p.act == OFX_ACT_RELU ? 0.0f : -3.402823466e38f;
     float* const X = smem;
-    float* const Sx = smem + kXF;   // STATS: [32-channel half][wave][channel][sum, sum of squares]
+    float* const Sx = smem + kXF;
     const int on = tid & 31, otx = tid >> 5;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        __syncthreads();   // nt 0: every wave's last fragment reads are done; nt 1: the previous half has been read
+        __syncthreads();   // nt 0: every wave's last operand reads are done; nt 1: the previous half has been read
         // column fold (A^T from the right) of this wave's row: t0 = M0 + M1 + M2, t1 = M1 - M2 - M3
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
@@ -440,7 +562,7 @@ __global__ __launch_bounds__(256, 2) void wino15_conv_kernel(const WinoK p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the weight offsets stay scalar too
     const Patch pt = wino_patch(p);
     f32x16 acc[8][1];
-    wino_slabs<T>(p, pt, Hs, Vs, tid, wave, acc);
+    wino_slabs_staged<T>(p, pt, Hs, Vs, tid, wave, acc);
 
     // ---- output transform in registers, then the epilogue.  Element e of the C layout: tile (e & 3) + 8 (e >> 2) + 4 (lane >> 5),
     // output channel lane & 31 of the wave's 32.
