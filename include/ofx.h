@@ -338,6 +338,17 @@ int ofx_local_corr_fwd(const float* fmap1, const float* fmap2, const float* coor
 int ofx_local_corr_bwd(const float* fmap1, const float* fmap2, const float* coords, const float* corr_grad,
                        float* fmap1_grad, float* fmap2_grad, int B, int H1, int W1, int H2, int W2, int C, int N,
                        int r, void* stream);
+/* The engine's volume-free lookup (AlternateCorrBlock.__call__, corr.py:74-91, all levels at once): fmap1 [n1,H1,W1,C];
+ * fmap2_levels: HOST array of `levels` device pointers, level l = [n2,H1>>l,W1>>l,C] (the 2x2-average-pooled maps, once per unique
+ * image); coords [B,H1,W1,2] on the level-0 grid (level l samples at coords / 2^l); idx1 / idx2: DEVICE int arrays, the image of
+ * fmap1 / fmap2 pair b uses -- NULL = image b, all zeros = one image shared by the batch.  Writes columns [0, levels * (2r+1)^2) of
+ * rows [B*H1*W1][ld] (level-major, then x-major as alt_cuda_corr), scaled by 1/sqrt(C); the other columns are not touched.
+ * tiled = 1: the LDS-tiled kernel (csrc/corr_local_tiled.hip; radius 3 or 4, C % 16 == 0, B <= 65535); tiled = 0: one launch of
+ * ofx_local_corr_fwd's per-pixel kernel per level (idx1 = idx2 = NULL only, radius <= 4, C % 4 == 0).  Taps outside a map count as
+ * zero; a pixel whose scaled coordinate is NaN, infinite or beyond 1e7 in magnitude gets zeros. */
+int ofx_local_corr_rows(const float* fmap1, const float* const* fmap2_levels, const int* idx1, const int* idx2,
+                        const float* coords, float* rows, int ld, int B, int H1, int W1, int C, int levels, int radius,
+                        int tiled, void* stream);
 /* 2x2 average pool of an NHWC tensor (AlternateCorrBlock pyramid, corr.py:68-72) */
 int ofx_avgpool2_nhwc(const float* in, float* out, int B, int H, int W, int C, void* stream);
 
@@ -397,13 +408,22 @@ typedef struct ofx_raft ofx_raft;      /* opaque */
  * per-channel scale/shift).  Keys may carry the "module." DataParallel prefix. */
 int ofx_raft_create(const ofx_tensor* tensors, int n, ofx_raft** out);
 int ofx_raft_destroy(ofx_raft* r);
-/* bytes of device workspace needed for a batch of B pairs of HxW images (H,W multiples of 8) */
+/* bytes of device workspace needed for a batch of B pairs of HxW images (H,W multiples of 8), whatever the flags: the larger of the
+ * two correlation layouts (the volume's) */
 size_t ofx_raft_workspace_bytes(const ofx_raft* r, int B, int H, int W);
+/* bytes of the layout a call with these `flags` actually carves (OFX_RAFT_ALT_CORR: no correlation pyramid; OFX_RAFT_SHARED_IMG1/2:
+ * one feature map instead of B; the other flags do not change the layout).  n_images = 0: ofx_raft_forward / _forward_warp;
+ * n_images > 0: the indexed-pairs entry points (the shared flags are invalid there).  A forward call succeeds with a workspace of
+ * exactly this size.  0 = bad arguments.  r may be NULL (the basic network). */
+size_t ofx_raft_workspace_bytes_mode(const ofx_raft* r, int n_images, int B, int H, int W, int flags);
 
 #define OFX_RAFT_BGR          1   /* input images are BGR (calc) instead of RGB (calc_batch)       */
 #define OFX_RAFT_SHARED_IMG2  2   /* image2 is ONE image shared by the whole batch (key frame)     */
 #define OFX_RAFT_SHARED_IMG1  4   /* image1 is ONE image shared by the whole batch                 */
-#define OFX_RAFT_ALT_CORR     8   /* on-the-fly local correlation instead of the volume (alt_cuda_corr) */
+#define OFX_RAFT_ALT_CORR     8   /* on-the-fly local correlation instead of the volume (alt_cuda_corr): every entry point, both
+                                     networks, with the shared-image flags and OFX_RAFT_FLOW_INIT; pooled fmap2 levels exist once per
+                                     unique image.  Runs the LDS-tiled kernel (ofx_local_corr_rows); OFX_LOCAL_CORR_NO_TILED=1 in the
+                                     environment (read once per process) puts it back on the per-pixel kernel */
 #define OFX_RAFT_BF16X3      16   /* opt-in: split-bf16 matrix-core arithmetic for every convolution / the volume */
 #define OFX_RAFT_BF16X6      64   /* opt-in: three-piece split-bf16 arithmetic (OFX_PREC_BF16X6) for every convolution / the volume */
 #define OFX_RAFT_BN_BATCH   128   /* context-encoder BatchNorm on the statistics of the image itself (the reference's RAFT_2 as written:

@@ -101,6 +101,7 @@ SIGNATURES = {
     "ofx_corr_lookup": (_i, [C.POINTER(_p), _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "ofx_local_corr_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "ofx_local_corr_bwd": (_i, [_p] * 6 + [_i] * 8 + [_p]),
+    "ofx_local_corr_rows": (_i, [_p] * 6 + [_i] * 8 + [_p]),
     "ofx_avgpool2_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "ofx_upsample_flow": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "ofx_upsample_flow_warp": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _p]),
@@ -112,6 +113,7 @@ SIGNATURES = {
     "ofx_raft_create": (_i, [C.POINTER(Tensor), _i, C.POINTER(_p)]),
     "ofx_raft_destroy": (_i, [_p]),
     "ofx_raft_workspace_bytes": (_z, [_p, _i, _i, _i]),
+    "ofx_raft_workspace_bytes_mode": (_z, [_p, _i, _i, _i, _i, _i]),
     "ofx_raft_forward": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _z, _p]),
     "ofx_raft_forward_warp": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _f, _p, _p, _z, _p]),
     "ofx_raft_workspace_bytes_pairs": (_z, [_p, _i, _i, _i, _i]),

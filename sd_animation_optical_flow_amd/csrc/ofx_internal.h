@@ -84,6 +84,11 @@ int ofx_attention_flash_launch(const float* q, const float* k, const float* v, c
 int ofx_local_corr_launch(const float* f1, const float* f2, const float* coords, float* out, long sb, long sn,
                           long sc, long sp, int B, int H1, int W1, int H2, int W2, int C, int N, int r, float scale,
                           float cscale, hipStream_t s);
+// corr_local_tiled.hip: the same lookup for all `levels` levels of B pairs in one launch, tap windows staged through LDS per 8x8 tile;
+// f2l[l] = [n2][h >> l][w >> l][C] (host array of device pointers), idx1 / idx2 = device arrays of image indices per pair or null
+// (pair b uses image b); writes columns [0, levels * (2r+1)^2) of the ld-float rows of `out`.  C % 16 == 0, r = 3 or 4
+int ofx_local_corr_tiled_launch(const float* f1, const float* const* f2l, const int* idx1, const int* idx2, const float* coords, float* out,
+                                int ld, int B, int h, int w, int C, int r, int levels, float scale, hipStream_t s);
 // blocked pyramid layout (corr.hip): floats per pixel slice of an hl x wl level; fmap rows -> blocked order
 int ofx_corr_slice_floats_l(int hl, int wl);
 // ofx_corr_lookup that also writes `pad` (<= 47; 4 levels, radius 4 only) zeros behind the features of every output row

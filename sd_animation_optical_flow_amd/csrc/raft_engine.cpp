@@ -631,8 +631,10 @@ static RaftWs carve(void* base, size_t cap, int B, int H, int W, int flags, int 
     w.fmap1 = c.take((size_t)n1 * N * FD);
     w.fmap2 = n2 ? c.take((size_t)n2 * N * FD) : w.fmap1;
     if (flags & OFX_RAFT_ALT_CORR) {
+        // volume-free mode: the pooled levels of fmap2, once per unique image, and no pyramid at all
         w.f2l[0] = w.fmap2;
-        for (int l = 1; l < LEVELS; ++l) w.f2l[l] = c.take((size_t)n2 * (h >> l) * (wd >> l) * FD);
+        for (int l = 1; l < LEVELS; ++l) w.f2l[l] = c.take((size_t)(n_images > 0 ? n_images : n2) * (h >> l) * (wd >> l) * FD);
+        if (n_images == 0) w.idx_dev = (int*)c.take((size_t)B);   // all zeros: the image index of every pair of a shared key frame
     } else {
         w.fmap2b = c.take((size_t)(n_images > 0 ? n_images : n2) * ofx_corr_slice_floats_l(h, wd) * FD);
         for (int l = 0; l < LEVELS; ++l) w.pyr[l] = c.take((size_t)M * ofx_corr_slice_floats_l(h >> l, wd >> l));
@@ -653,14 +655,46 @@ static RaftWs carve(void* base, size_t cap, int B, int H, int W, int flags, int 
     return w;
 }
 
+// Which image of fmap1 / fmap2 each pair of a volume-free lookup reads: device arrays for the tiled kernel (null = pair b reads image
+// b), and the same on the host (arrays of the indexed-pairs call, or the shared flags) for the per-pixel kernel
+struct AltIdx {
+    const int *d1 = nullptr, *d2 = nullptr, *h1 = nullptr, *h2 = nullptr;
+    bool sh1 = false, sh2 = false;
+};
+
+// OFX_LOCAL_CORR_NO_TILED=1: every volume-free lookup of the engine on the per-pixel kernel of ofx_local_corr_fwd (diagnostic)
+static bool local_corr_tiled() {
+    static const bool off = [] { const char* e = getenv("OFX_LOCAL_CORR_NO_TILED"); return e && *e && *e != '0'; }();
+    return !off;
+}
+
+// correlation features of all LEVELS levels at coords, without a volume, into the lookup rows (ld floats per pixel)
+static int alt_lookup(const float* fmap1, float* const* f2l, const AltIdx& ix, const float* coords, float* corr, int ld, int B, int h, int w,
+                      int D, int radius, hipStream_t s) {
+    const float scale = 1.0f / std::sqrt((float)D);
+    if (local_corr_tiled()) return ofx_local_corr_tiled_launch(fmap1, f2l, ix.d1, ix.d2, coords, corr, ld, B, h, w, D, radius, LEVELS, scale, s);
+    const long N = (long)h * w;
+    const int rd2 = (2 * radius + 1) * (2 * radius + 1);
+    const bool indexed = ix.h1 || ix.h2 || ix.sh1 || ix.sh2;
+    for (int l = 0; l < LEVELS; ++l) {
+        const long n2 = (long)(h >> l) * (w >> l) * D;
+        for (int b = 0; b < (indexed ? B : 1); ++b) {   // the per-pixel kernel pairs image b with image b: one launch per indexed pair
+            const long i1 = ix.h1 ? ix.h1[b] : ix.sh1 ? 0 : b, i2 = ix.h2 ? ix.h2[b] : ix.sh2 ? 0 : b;
+            const int st = ofx_local_corr_launch(fmap1 + i1 * N * D, f2l[l] + i2 * n2, coords + (long)b * N * 2, corr + (long)b * N * ld + (long)l * rd2,
+                                                 N * ld, 0, 1, ld, indexed ? 1 : B, h, w, h >> l, w >> l, D, 1, radius, scale, 1.0f / (float)(1 << l), s);
+            if (st) return st;
+        }
+    }
+    return 0;
+}
+
 // everything after the feature / context encoders and the correlation volume: state init, the loop-invariant
 // GRU terms, `iters` refinement iterations, mask head, convex upsample
 // warm: flow_low holds the initial flow (OFX_RAFT_FLOW_INIT); it is read here and overwritten with the final flow at the end
-static int run_recurrence(ofx_raft* r, const RaftWs& ws, int B, int h, int w, int iters, bool alt, bool shared,
+static int run_recurrence(ofx_raft* r, const RaftWs& ws, int B, int h, int w, int iters, bool alt, const AltIdx& aix,
                           float* flow_up, float* flow_low, hipStream_t s, int precision, bool overlap, bool warm,
                           uint8_t* warped = nullptr, float warp_sign = 1.0f, int n_warp = -1) {
     const long N = (long)h * w;
-    const bool sh1 = shared, sh2 = shared;
     int st = 0;
     st = warm ? ofx_init_state_warm(ws.coords1, ws.frows, ws.hx, HX_LD, FLOW_OFF, false, flow_low, B, h, w, s)
               : ofx_init_state(ws.coords1, ws.frows, ws.hx, HX_LD, FLOW_OFF, B, h, w, s);
@@ -687,7 +721,6 @@ static int run_recurrence(ofx_raft* r, const RaftWs& ws, int B, int h, int w, in
     LF.sk_ws = overlap ? ws.sk[1] : ws.sk[0]; LF.sk_bytes = LF.sk_ws ? SK_BYTES : 0;   // its own scratch when it runs concurrently
     auto C = [&](const char* k) -> const ConvW& { return r->convs[k]; };
     const float* pyr_c[LEVELS] = {ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3]};
-    const int rd2 = (2 * RADIUS + 1) * (2 * RADIUS + 1);
     bool fork_on_kernel = false;   // the previous iteration's flow head carries ev_fork
     for (int it = 0; it < iters && !L.st; ++it) {
         // flow features (update.py:93-94) on the side stream, from the flow the previous iteration left
@@ -701,12 +734,7 @@ static int run_recurrence(ofx_raft* r, const RaftWs& ws, int B, int h, int w, in
         if (!alt) {
             L.st = ofx_corr_lookup_pad(pyr_c, ws.coords1, ws.corr, CORR_LD, CORR_LD - CORR_CH, B, h, w, LEVELS, RADIUS, s);
         } else {
-            for (int l = 0; l < LEVELS && !L.st; ++l) {
-                if (sh1 || sh2) { L.st = OFX_EINVAL; break; }   // alt-corr path: per-pair feature maps only
-                L.st = ofx_local_corr_launch(ws.fmap1, ws.f2l[l], ws.coords1, ws.corr + (long)l * rd2, N * CORR_LD, 0, 1,
-                                             CORR_LD, B, h, w, h >> l, w >> l, FD, 1, RADIUS, 1.0f / std::sqrt((float)FD),
-                                             1.0f / (float)(1 << l), s);
-            }
+            L.st = alt_lookup(ws.fmap1, ws.f2l, aix, ws.coords1, ws.corr, CORR_LD, B, h, w, FD, RADIUS, s);
         }
         // motion encoder (update.py:88-97)
         L.conv(C("convc1"), ws.corr, CORR_LD, CORR_LD, nullptr, 0, 0, ws.c1, 256, B, h, w, 1, OFX_ACT_RELU);
@@ -779,6 +807,7 @@ static int raft_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* 
 static int small_detect(const std::map<std::string, HostTensor>& sd);
 static int small_build(ofx_raft* r, const std::map<std::string, HostTensor>& sd);
 static size_t small_workspace_bytes(int B, int H, int W, int n_images);
+static size_t small_workspace_bytes_mode(int B, int H, int W, int flags, int n_images);
 static int small_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* image2, int B, int H, int W, int iters, int flags,
                               float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign, uint8_t* warped, void* workspace,
                               size_t workspace_bytes, void* stream);
@@ -890,6 +919,14 @@ size_t ofx_raft_workspace_bytes(const ofx_raft* r, int B, int H, int W) {
     size_t a = carve(nullptr, 0, B, H, W, 0).bytes;
     size_t b = carve(nullptr, 0, B, H, W, OFX_RAFT_ALT_CORR).bytes;
     return a > b ? a : b;
+}
+
+size_t ofx_raft_workspace_bytes_mode(const ofx_raft* r, int n_images, int B, int H, int W, int flags) {
+    if (n_images < 0 || B <= 0 || H <= 0 || W <= 0 || (H % 8) || (W % 8) || flags < 0 || flags >= 2 * OFX_RAFT_FLOW_INIT) return 0;
+    if (n_images > 0 && (flags & (OFX_RAFT_SHARED_IMG1 | OFX_RAFT_SHARED_IMG2))) return 0;
+    const int layout = flags & (OFX_RAFT_ALT_CORR | OFX_RAFT_SHARED_IMG1 | OFX_RAFT_SHARED_IMG2);
+    if (r && r->variant == 1) return small_workspace_bytes_mode(B, H, W, layout, n_images);
+    return carve(nullptr, 0, B, H, W, layout, n_images).bytes;
 }
 
 int ofx_raft_forward(ofx_raft* r, const uint8_t* image1, const uint8_t* image2, int B, int H, int W, int iters,
@@ -1031,7 +1068,13 @@ static int raft_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* 
         st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
         if (st) return st;
     }
-    st = run_recurrence(r, ws, B, h, w, iters, alt, sh1 || sh2, flow_up, flow_low, s, prec, overlap, flags & OFX_RAFT_FLOW_INIT,
+    AltIdx aix;
+    if (alt && (sh1 || sh2)) {
+        OFX_HIP_CHECK(hipMemsetAsync(ws.idx_dev, 0, sizeof(int) * B, s));
+        aix.d1 = sh1 ? ws.idx_dev : nullptr; aix.d2 = sh2 ? ws.idx_dev : nullptr;
+        aix.sh1 = sh1; aix.sh2 = sh2;
+    }
+    st = run_recurrence(r, ws, B, h, w, iters, alt, aix, flow_up, flow_low, s, prec, overlap, flags & OFX_RAFT_FLOW_INIT,
                         warped, warp_sign);
     if (st) return st;
 
@@ -1081,11 +1124,12 @@ int ofx_raft_forward_pairs_warp(ofx_raft* r, const uint8_t* images, int n_images
         OFX_REQUIRE(ofx_upsample_warp_ok(n_warp, H, W) && (((uintptr_t)warped) & 3u) == 0, OFX_EINVAL);
     }
     OFX_REQUIRE(n_images > 0 && B > 0 && H >= 64 && W >= 64 && (H % 8) == 0 && (W % 8) == 0 && iters >= 1, OFX_EINVAL);
-    OFX_REQUIRE(!(flags & (OFX_RAFT_ALT_CORR | OFX_RAFT_SHARED_IMG1 | OFX_RAFT_SHARED_IMG2)), OFX_EINVAL);
+    OFX_REQUIRE(!(flags & (OFX_RAFT_SHARED_IMG1 | OFX_RAFT_SHARED_IMG2)), OFX_EINVAL);
     OFX_REQUIRE((((uintptr_t)workspace) & 255u) == 0, OFX_EALIGN);
     for (int b = 0; b < B; ++b)
         OFX_REQUIRE(idx1[b] >= 0 && idx1[b] < n_images && idx2[b] >= 0 && idx2[b] < n_images, OFX_EINVAL);
-    RaftWs ws = carve(workspace, workspace_bytes, B, H, W, 0, n_images);
+    const bool alt = flags & OFX_RAFT_ALT_CORR;
+    RaftWs ws = carve(workspace, workspace_bytes, B, H, W, flags & OFX_RAFT_ALT_CORR, n_images);
     OFX_REQUIRE(ws.bytes <= workspace_bytes, OFX_ENOMEM);
     hipStream_t s = (hipStream_t)stream;
     for (int e = 0; e < 3; ++e)
@@ -1122,10 +1166,18 @@ int ofx_raft_forward_pairs_warp(ofx_raft* r, const uint8_t* images, int n_images
     OFX_HIP_CHECK(hipMemcpyAsync(ws.idx_dev, idx1, sizeof(int) * B, hipMemcpyHostToDevice, s));
     st = ofx_ctx_gather(ws.ctx, ws.idx_dev, ws.hx, HX_LD, INP_OFF, HD, B, N, s);
     if (st) return st;
+    AltIdx aix;
+    if (alt) {   // volume-free: the pooled levels of every image once, the pair list on the device for the lookup
+        OFX_HIP_CHECK(hipMemcpyAsync(ws.idx_dev + B, idx2, sizeof(int) * B, hipMemcpyHostToDevice, s));
+        for (int l = 1; l < LEVELS && !st; ++l) st = ofx_avgpool2_nhwc(ws.f2l[l - 1], ws.f2l[l], n_images, h >> (l - 1), w >> (l - 1), FD, s);
+        if (st) return st;
+        aix.d1 = ws.idx_dev; aix.d2 = ws.idx_dev + B;
+        aix.h1 = idx1; aix.h2 = idx2;
+    }
     const long Nb = ofx_corr_slice_floats_l(h, w);
     const long slice1p = ofx_corr_slice_floats_l(h >> 1, w >> 1);
     const bool fused_pairs = ofx_corr_volpool_ok(h, w) && Nb % 128 == 0 && N * slice1p * 4 < (1L << 31) - 64;
-    const int vplanes = volume_planes(flags, h, w, 2L * n_images, ws, (long)B * N, B);
+    const int vplanes = alt ? 0 : volume_planes(flags, h, w, 2L * n_images, ws, (long)B * N, B);
     if (vplanes) {
         // split-bf16 volume: every image split once per role (rows scaled in pixel order / columns in quad order), ONE launch over the
         // pair list through the device-side index arrays
@@ -1135,11 +1187,11 @@ int ofx_raft_forward_pairs_warp(ofx_raft* r, const uint8_t* images, int n_images
         st = ofx_corr_split_planes(ws.fmap1, pl, n_images, h, w, vplanes, 0, 1.0f / std::sqrt((float)FD), s);
         if (!st) st = ofx_corr_split_planes(ws.fmap1, pl + ib * n_images, n_images, h, w, vplanes, 1, 1.0f, s);
         if (!st) st = ofx_corr_vol_split_launch(pl, pl + ib * n_images, ws.idx_dev, ws.idx_dev + B, 0, 0, ws.pyr[0], ws.pyr[1], B, h, w, vplanes, s);
-    } else {
+    } else if (!alt) {
         st = ofx_corr_block_rows(ws.fmap1, ws.fmap2b, n_images, h, w, FD, s);   // every image can be an image2: blocked copy of all
     }
     if (st) return st;
-    for (int b = 0; b < B && !st && !vplanes; ++b) {   // one N x Nb correlation GEMM per pair, straight from the shared feature maps
+    for (int b = 0; b < B && !st && !vplanes && !alt; ++b) {   // one N x Nb correlation GEMM per pair, straight from the shared feature maps
         ofx_conv_desc d{};
         d.in0 = ws.fmap1 + (long)idx1[b] * N * FD; d.ld0 = FD; d.c0 = FD;
         d.w = ws.fmap2b + (long)idx2[b] * Nb * FD;
@@ -1154,13 +1206,13 @@ int ofx_raft_forward_pairs_warp(ofx_raft* r, const uint8_t* images, int n_images
         else
             st = ofx_conv2d_alpha(&d, 1.0f / std::sqrt((float)FD), s);
     }
-    if (!st) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused_pairs || vplanes);
+    if (!st && !alt) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused_pairs || vplanes);
     if (st) return st;
     if (warped) {   // the zero-bordered RGBX copy the warp samples
         st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
         if (st) return st;
     }
-    st = run_recurrence(r, ws, B, h, w, iters, false, false, flow_up, flow_low, s, prec, overlap, flags & OFX_RAFT_FLOW_INIT, warped, warp_sign,
+    st = run_recurrence(r, ws, B, h, w, iters, alt, aix, flow_up, flow_low, s, prec, overlap, flags & OFX_RAFT_FLOW_INIT, warped, warp_sign,
                         n_warp);
     if (st) return st;
     r->bufs.clear();
@@ -1214,6 +1266,7 @@ struct SmallWs {
     float* stats;      // 8 x [chunk][128]: mean / rstd of up to four norms
     float* scratch;    // f64 partial sums of ofx_inorm_stats
     float *fmap1, *fmap2, *f2l[LEVELS], *fmap2b, *ctx;
+    int* idx_dev;      // volume-free mode: image indices per pair (image1's, then image2's) for the tiled lookup
     float* pyr[LEVELS];
     float *hx, *coords1, *flow4, *corr, *corflo, *f1, *z, *rh, *fh;
     void* warp_pad;
@@ -1244,7 +1297,8 @@ SmallWs small_carve(void* base, size_t cap, int B, int H, int W, int flags, int 
     w.fmap2 = n2 ? c.take((size_t)n2 * N * S_FD) : w.fmap1;
     if (flags & OFX_RAFT_ALT_CORR) {
         w.f2l[0] = w.fmap2;
-        for (int l = 1; l < LEVELS; ++l) w.f2l[l] = c.take((size_t)n2 * (h >> l) * (wd >> l) * S_FD);
+        for (int l = 1; l < LEVELS; ++l) w.f2l[l] = c.take((size_t)(n_images > 0 ? n_images : n2) * (h >> l) * (wd >> l) * S_FD);
+        w.idx_dev = (int*)c.take((size_t)2 * B);
     } else {
         w.fmap2b = c.take((size_t)(n_images > 0 ? n_images : n2) * ofx_corr_slice_floats_l(h, wd) * S_FD);
         for (int l = 0; l < LEVELS; ++l) w.pyr[l] = c.take((size_t)M * ofx_corr_slice_floats_l(h >> l, wd >> l));
@@ -1363,7 +1417,7 @@ int small_volume(const float* f1, long a_zs, const float* f2b, long w_zs, float*
 
 // state init, `iters` refinement iterations of SmallUpdateBlock, upflow8 (with the warp of one shared frame for the first n_warp pairs)
 // (warm: flow_low holds the initial flow, OFX_RAFT_FLOW_INIT)
-int small_recurrence(ofx_raft* r, const SmallWs& ws, int B, int h, int w, int iters, bool alt, float* flow_up, float* flow_low, bool warm,
+int small_recurrence(ofx_raft* r, const SmallWs& ws, int B, int h, int w, int iters, bool alt, const AltIdx& aix, float* flow_up, float* flow_low, bool warm,
                      uint8_t* warped, float warp_sign, int n_warp, hipStream_t s) {
     const long N = (long)h * w, M = (long)B * N;
     int st = warm ? ofx_init_state_warm(ws.coords1, ws.flow4, ws.hx, S_HX_LD, S_FLOW_OFF, true, flow_low, B, h, w, s)
@@ -1373,14 +1427,11 @@ int small_recurrence(ofx_raft* r, const SmallWs& ws, int B, int h, int w, int it
     Launcher L{s};
     auto C = [&](const char* k) -> const ConvW& { return r->convs[k]; };
     const float* pyr_c[LEVELS] = {ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3]};
-    const int rd2 = (2 * S_RADIUS + 1) * (2 * S_RADIUS + 1);
     for (int it = 0; it < iters && !L.st; ++it) {
         if (!alt) {
             L.st = ofx_corr_lookup(pyr_c, ws.coords1, ws.corr, S_CORR_LD, B, h, w, LEVELS, S_RADIUS, s);
         } else {
-            for (int l = 0; l < LEVELS && !L.st; ++l)
-                L.st = ofx_local_corr_launch(ws.fmap1, ws.f2l[l], ws.coords1, ws.corr + (long)l * rd2, N * S_CORR_LD, 0, 1, S_CORR_LD, B, h, w,
-                                             h >> l, w >> l, S_FD, 1, S_RADIUS, 1.0f / std::sqrt((float)S_FD), 1.0f / (float)(1 << l), s);
+            L.st = alt_lookup(ws.fmap1, ws.f2l, aix, ws.coords1, ws.corr, S_CORR_LD, B, h, w, S_FD, S_RADIUS, s);
         }
         // SmallMotionEncoder (update.py:70-77): cor_flo = [relu(convc1(corr)) (96) | relu(convf2(relu(convf1(flow)))) (32)]
         L.conv(C("convc1"), ws.corr, S_CORR_LD, S_CORR_LD, nullptr, 0, 0, ws.corflo, 128, B, h, w, 1, OFX_ACT_RELU);
@@ -1502,6 +1553,8 @@ static size_t small_workspace_bytes(int B, int H, int W, int n_images) {
     return a > b ? a : b;
 }
 
+static size_t small_workspace_bytes_mode(int B, int H, int W, int flags, int n_images) { return small_carve(nullptr, 0, B, H, W, flags, n_images).bytes; }
+
 static int small_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* image2, int B, int H, int W, int iters, int flags,
                               float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign, uint8_t* warped, void* workspace,
                               size_t workspace_bytes, void* stream) {
@@ -1510,7 +1563,6 @@ static int small_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t*
     OFX_REQUIRE(!(flags & S_UNSUPPORTED), OFX_EINVAL);
     OFX_REQUIRE((((uintptr_t)workspace) & 255u) == 0, OFX_EALIGN);
     const bool sh1 = flags & OFX_RAFT_SHARED_IMG1, sh2 = flags & OFX_RAFT_SHARED_IMG2, alt = flags & OFX_RAFT_ALT_CORR;
-    OFX_REQUIRE(!(alt && (sh1 || sh2)), OFX_EINVAL);   // alt-corr path: per-pair feature maps only (as for the basic network)
     SmallWs ws = small_carve(workspace, workspace_bytes, B, H, W, flags, 0);
     OFX_REQUIRE(ws.bytes <= workspace_bytes, OFX_ENOMEM);
     hipStream_t s = (hipStream_t)stream;
@@ -1542,7 +1594,13 @@ static int small_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t*
         for (int l = 1; l < LEVELS && !st; ++l) st = ofx_avgpool2_nhwc(ws.f2l[l - 1], ws.f2l[l], n2, h >> (l - 1), w >> (l - 1), S_FD, s);
     }
     if (!st && warped) st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
-    if (!st) st = small_recurrence(r, ws, B, h, w, iters, alt, flow_up, flow_low, flags & OFX_RAFT_FLOW_INIT, warped, warp_sign, -1, s);
+    AltIdx aix;
+    if (!st && alt && (sh1 || sh2)) {
+        OFX_HIP_CHECK(hipMemsetAsync(ws.idx_dev, 0, sizeof(int) * B, s));
+        aix.d1 = sh1 ? ws.idx_dev : nullptr; aix.d2 = sh2 ? ws.idx_dev : nullptr;
+        aix.sh1 = sh1; aix.sh2 = sh2;
+    }
+    if (!st) st = small_recurrence(r, ws, B, h, w, iters, alt, aix, flow_up, flow_low, flags & OFX_RAFT_FLOW_INIT, warped, warp_sign, -1, s);
     if (st) return st;
     small_register(r, ws, n1, n2, M, h, w, alt);
     return 0;
@@ -1556,11 +1614,12 @@ static int small_forward_pairs_impl(ofx_raft* r, const uint8_t* images, int n_im
         OFX_REQUIRE(ofx_upsample_warp_ok(n_warp, H, W) && (((uintptr_t)warped) & 3u) == 0, OFX_EINVAL);
     }
     OFX_REQUIRE(n_images > 0 && B > 0 && H >= 64 && W >= 64 && (H % 8) == 0 && (W % 8) == 0 && iters >= 1, OFX_EINVAL);
-    OFX_REQUIRE(!(flags & (OFX_RAFT_ALT_CORR | OFX_RAFT_SHARED_IMG1 | OFX_RAFT_SHARED_IMG2 | S_UNSUPPORTED)), OFX_EINVAL);
+    OFX_REQUIRE(!(flags & (OFX_RAFT_SHARED_IMG1 | OFX_RAFT_SHARED_IMG2 | S_UNSUPPORTED)), OFX_EINVAL);
+    const bool alt = flags & OFX_RAFT_ALT_CORR;
     OFX_REQUIRE((((uintptr_t)workspace) & 255u) == 0, OFX_EALIGN);
     for (int b = 0; b < B; ++b)
         OFX_REQUIRE(idx1[b] >= 0 && idx1[b] < n_images && idx2[b] >= 0 && idx2[b] < n_images, OFX_EINVAL);
-    SmallWs ws = small_carve(workspace, workspace_bytes, B, H, W, 0, n_images);
+    SmallWs ws = small_carve(workspace, workspace_bytes, B, H, W, flags & OFX_RAFT_ALT_CORR, n_images);
     OFX_REQUIRE(ws.bytes <= workspace_bytes, OFX_ENOMEM);
     hipStream_t s = (hipStream_t)stream;
     const int h = H / 8, w = W / 8, bgr = (flags & OFX_RAFT_BGR) ? 1 : 0;
@@ -1578,14 +1637,22 @@ static int small_forward_pairs_impl(ofx_raft* r, const uint8_t* images, int n_im
         OFX_HIP_CHECK(hipMemcpyAsync(ws.hx + (long)b * N * S_HX_LD, ws.ctx + (long)idx1[b] * N * S_HX_LD, (size_t)N * S_HX_LD * sizeof(float),
                                      hipMemcpyDeviceToDevice, s));
     const long Nb = ofx_corr_slice_floats_l(h, w), slice1 = ofx_corr_slice_floats_l(h >> 1, w >> 1);
-    if (!st) st = ofx_corr_block_rows(ws.fmap1, ws.fmap2b, n_images, h, w, S_FD, s);   // every image can be an image2
+    AltIdx aix;
+    if (!st && alt) {   // volume-free: the pooled levels of every image once, the pair list on the device for the lookup
+        OFX_HIP_CHECK(hipMemcpyAsync(ws.idx_dev, idx1, sizeof(int) * B, hipMemcpyHostToDevice, s));
+        OFX_HIP_CHECK(hipMemcpyAsync(ws.idx_dev + B, idx2, sizeof(int) * B, hipMemcpyHostToDevice, s));
+        for (int l = 1; l < LEVELS && !st; ++l) st = ofx_avgpool2_nhwc(ws.f2l[l - 1], ws.f2l[l], n_images, h >> (l - 1), w >> (l - 1), S_FD, s);
+        aix.d1 = ws.idx_dev; aix.d2 = ws.idx_dev + B;
+        aix.h1 = idx1; aix.h2 = idx2;
+    }
+    if (!st && !alt) st = ofx_corr_block_rows(ws.fmap1, ws.fmap2b, n_images, h, w, S_FD, s);   // every image can be an image2
     bool fused = false;
-    for (int b = 0; b < B && !st; ++b)   // one correlation GEMM per pair, straight from the shared feature maps
+    for (int b = 0; b < B && !st && !alt; ++b)   // one correlation GEMM per pair, straight from the shared feature maps
         st = small_volume(ws.fmap1 + (long)idx1[b] * N * S_FD, 0, ws.fmap2b + (long)idx2[b] * Nb * S_FD, 0, ws.pyr[0] + (long)b * N * Nb,
                           ws.pyr[1] + (long)b * N * slice1, 1, h, w, &fused, s);
-    if (!st) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused);
+    if (!st && !alt) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused);
     if (!st && warped) st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
-    if (!st) st = small_recurrence(r, ws, B, h, w, iters, false, flow_up, flow_low, flags & OFX_RAFT_FLOW_INIT, warped, warp_sign, n_warp, s);
+    if (!st) st = small_recurrence(r, ws, B, h, w, iters, alt, aix, flow_up, flow_low, flags & OFX_RAFT_FLOW_INIT, warped, warp_sign, n_warp, s);
     if (st) return st;
     r->bufs.clear();
     return 0;

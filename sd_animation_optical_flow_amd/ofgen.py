@@ -102,9 +102,9 @@ def forward_interpolate(flow) -> torch.Tensor:
     return out.permute(2, 0, 1).contiguous().cpu()
 
 
-def create_of_algo(ckpt="../DenseMatching/pre_trained_models/PDCNet_plus_m.pth.tar"):
-    """ofgen_keyframe_inpaint.py:73-77."""
-    return _pd.create_of_algo(ckpt)
+def create_of_algo(ckpt="../DenseMatching/pre_trained_models/PDCNet_plus_m.pth.tar", corr: str = "volume"):
+    """ofgen_keyframe_inpaint.py:73-77.  corr (extension): 'local' / 'auto' = volume-free correlation (`RaftEngine`'s `corr`)."""
+    return _pd.create_of_algo(ckpt, corr=corr)
 
 
 def warp_frame(frame, flow, mode: Optional[str] = None, device="cuda") -> np.ndarray:

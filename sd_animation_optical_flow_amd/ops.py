@@ -563,6 +563,45 @@ def local_corr(fmap1: torch.Tensor, fmap2: torch.Tensor, coords: torch.Tensor, r
     return out
 
 
+def local_corr_rows(fmap1: torch.Tensor, fmap2_levels, coords: torch.Tensor, radius: int, rows: torch.Tensor = None, idx1=None, idx2=None,
+                    tiled: bool = True) -> torch.Tensor:
+    """The engine's volume-free lookup, all pyramid levels at once (`ofx_local_corr_rows`): fmap1 f32[n1,H,W,C]; fmap2_levels: list of
+    f32[n2,H>>l,W>>l,C]; coords f32[B,H,W,2] on the level-0 grid; idx1 / idx2: int32 CUDA tensors [B] (image of fmap1 / fmap2 per pair)
+    or None (pair b uses image b).  Writes columns [0, levels * (2r+1)^2) of `rows` f32[B*H*W, ld] (allocated with exactly that many
+    columns when not given) and returns it; the other columns keep their content.  tiled=False: the per-pixel kernel (no indices)."""
+    a = _chk(fmap1, "fmap1", torch.float32)
+    lv = [_chk(f, f"fmap2_levels[{l}]", torch.float32) for l, f in enumerate(fmap2_levels)]
+    c = _chk(coords, "coords", torch.float32)
+    _n1, H, W, Cn = a.shape
+    B = c.shape[0]
+    if tuple(c.shape) != (B, H, W, 2):
+        raise RuntimeError(f"coords must be [B,{H},{W},2], got {tuple(c.shape)}")
+    for l, f in enumerate(lv):
+        if tuple(f.shape[1:]) != (H >> l, W >> l, Cn) or f.shape[0] != lv[0].shape[0]:
+            raise RuntimeError(f"fmap2_levels[{l}] must be [n2,{H >> l},{W >> l},{Cn}], got {tuple(f.shape)}")
+    n_out = len(lv) * (2 * radius + 1) ** 2
+    if rows is None:
+        rows = torch.empty((B * H * W, n_out), dtype=torch.float32, device=a.device)
+    if not rows.is_cuda or rows.dtype != torch.float32 or rows.dim() != 2 or not rows.is_contiguous() or rows.shape[0] != B * H * W or rows.shape[1] < n_out:
+        raise RuntimeError(f"rows must be a contiguous CUDA float32 tensor [{B * H * W}, >= {n_out}]")
+    ix = []
+    for nm, t, n in (("idx1", idx1, a.shape[0]), ("idx2", idx2, lv[0].shape[0])):
+        if t is None:
+            if n < B:
+                raise RuntimeError(f"{nm} is None (pair b uses image b) but there are only {n} images for {B} pairs")
+            ix.append(None)
+            continue
+        t = t.to(device=a.device, dtype=torch.int32).contiguous()
+        if t.numel() != B or int(t.min()) < 0 or int(t.max()) >= n:
+            raise RuntimeError(f"{nm} must hold {B} indices in [0, {n})")
+        ix.append(t)
+    ptrs = (C.c_void_p * len(lv))(*[f.data_ptr() for f in lv])
+    check(_lib.lib().ofx_local_corr_rows(_ptr(a), ptrs, C.c_void_p(ix[0].data_ptr() if ix[0] is not None else 0),
+                                         C.c_void_p(ix[1].data_ptr() if ix[1] is not None else 0), _ptr(c), _ptr(rows), rows.shape[1], B, H, W, Cn,
+                                         len(lv), int(radius), 1 if tiled else 0, _stream()), "ofx_local_corr_rows")
+    return rows
+
+
 def local_corr_backward(fmap1: torch.Tensor, fmap2: torch.Tensor, coords: torch.Tensor, corr_grad: torch.Tensor, radius: int):
     """`alt_cuda_corr.backward` semantics: (fmap1_grad, fmap2_grad) for corr_grad f32[B,N,(2r+1)^2,H1,W1]."""
     a = _chk(fmap1, "fmap1", torch.float32)

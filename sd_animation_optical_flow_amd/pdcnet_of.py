@@ -38,14 +38,15 @@ class PDCNetPlus:
     """Flow + confidence estimator with the duck type of the reference's `PDCNetPlus` (pdcnet_of.py:45-75)."""
 
     def __init__(self, ckpt_path="pre_trained_models/PDCNet_plus_m.pth.tar", device=None, iters: int = 20,
-                 confidence_sigma: float = 3.0, precision: str = "fp32", volume_precision: Optional[str] = None):
+                 confidence_sigma: float = 3.0, precision: str = "fp32", volume_precision: Optional[str] = None, corr: str = "volume"):
         self.state_dict = load_checkpoint(ckpt_path)
+        self.corr = corr                               # extension: 'local' / 'auto' = volume-free correlation (RaftEngine's `corr`)
         self.precision = precision
         self.volume_precision = volume_precision       # extension: 'bf16x6' / 'bf16x3' = ONLY the correlation volume in split-bf16 form
         self.iters = int(iters)
         self.sigma = float(confidence_sigma)
         self.device = torch.device(device) if device is not None else torch.device("cuda")
-        self.network = RaftEngine(self.state_dict, self.device, precision=precision, volume_precision=volume_precision)   # like `.cuda()` at pdcnet_of.py:61
+        self.network = RaftEngine(self.state_dict, self.device, precision=precision, volume_precision=volume_precision, corr=corr)   # like `.cuda()` at pdcnet_of.py:61
 
     def to(self, device):
         """`pdcnet_model.to(device)` (ofgen_keyframe_inpaint.py:555).  Moving re-uploads the weights."""
@@ -56,7 +57,7 @@ class PDCNetPlus:
         new = device.index if device.index is not None else torch.cuda.current_device()
         if cur != new:
             self.device = device
-            self.network = RaftEngine(self.state_dict, device, precision=self.precision, volume_precision=self.volume_precision)
+            self.network = RaftEngine(self.state_dict, device, precision=self.precision, volume_precision=self.volume_precision, corr=self.corr)
         return self
 
     # ---- device-resident core ------------------------------------------------------------------
@@ -97,7 +98,7 @@ class PDCNetPlus:
         B, ns = tgt.shape[0], src.shape[0]
         if not shared and ns != B:
             raise RuntimeError("source / target batch sizes differ")
-        step = max(1, net.max_pairs_now(tgt.shape[1], tgt.shape[2], 2 * B) // 2)      # 32-bit offsets AND the memory free right now
+        step = max(1, net.max_pairs_now(tgt.shape[1], tgt.shape[2], 2 * B, alternate_corr=None) // 2)      # 32-bit offsets AND the memory free right now
         fts, fss, wps = [], [], []
         for b0 in range(0, B, step):
             t = tgt[b0:b0 + step]
@@ -132,7 +133,7 @@ class PDCNetPlus:
         H0, W0 = frames.shape[1], frames.shape[2]
         frames = self.network.pad_to_8(frames.contiguous())
         # one executor call addresses its operands with 32-bit offsets: 113 pairs at 512x768 but 21 at 1920x1080
-        max_flows = self.network.max_pairs_now(frames.shape[1], frames.shape[2], max_flows)   # ... and what fits the free memory
+        max_flows = self.network.max_pairs_now(frames.shape[1], frames.shape[2], max_flows, alternate_corr=None)   # ... and what fits the free memory
         need = {}                                    # directed flow (image1, image2) -> slot
         for s, t in pairs:
             need.setdefault((t, s), len(need))       # flow on t's grid into s
@@ -180,9 +181,10 @@ def _unpad(t: torch.Tensor, H: int, W: int) -> torch.Tensor:
     return t[:, y0:y0 + H, x0:x0 + W].contiguous()
 
 
-def create_of_algo(ckpt, precision: str = "fp32", volume_precision: Optional[str] = None) -> PDCNetPlus:
-    """pdcnet_of.py:77-79.  `precision` / `volume_precision` are extensions (default: the reference's fp32 arithmetic everywhere)."""
-    return PDCNetPlus(ckpt, precision=precision, volume_precision=volume_precision)
+def create_of_algo(ckpt, precision: str = "fp32", volume_precision: Optional[str] = None, corr: str = "volume") -> PDCNetPlus:
+    """pdcnet_of.py:77-79.  `precision` / `volume_precision` / `corr` are extensions (default: the reference's fp32 arithmetic everywhere,
+    on the all-pairs volume; corr='local' / 'auto': the volume-free correlation, see `RaftEngine`)."""
+    return PDCNetPlus(ckpt, precision=precision, volume_precision=volume_precision, corr=corr)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -26,11 +26,12 @@ FLAG_FLOW_INIT = 2048
 VOLUME_PRECISIONS = {None: 0, "fp32": 0, "bf16x3": FLAG_VOL_BF16X3, "bf16x6": FLAG_VOL_BF16X6}
 # floats of the widest row a convolution of one executor call addresses, per network (see pairs_per_call)
 ROW_FLOATS = {"basic": 768, "small": 256}
+CORR_MODES = ("volume", "local", "auto")
 
 
 class RaftEngine:
     def __init__(self, state_dict: Dict[str, torch.Tensor], device: Optional[torch.device] = None, precision: str = "fp32",
-                 cnet_norm: str = "eval", volume_precision: Optional[str] = None):
+                 cnet_norm: str = "eval", volume_precision: Optional[str] = None, corr: str = "volume"):
         """NOTE THE DEFAULT SPLIT: `RaftEngine` (and the `pdcnet_of` surface built on it) defaults to cnet_norm='eval'; `ofgen.RAFT_2`
         -- the reference's RAFT wrapper AS WRITTEN -- passes cnet_norm='batch'.  The two networks differ by more than 1 px of flow:
         build the engine with cnet_norm='batch' to mirror `RAFT_2`.
@@ -48,6 +49,13 @@ class RaftEngine:
         (RAFT/core/corr.py:52-60), every convolution stays exact fp32: the GEMM runs on the bf16 matrix cores from operands pre-split
         into bf16 planes (csrc/corr_split.hip; needs H % 64 == 0 and W % 128 == 0, other shapes silently take the fp32 GEMM).
 
+        corr: the engine's default correlation mode, for calls that do not pass `alternate_corr` themselves (an explicit argument
+        wins).  'volume' (default): the all-pairs volume and its pyramid (RAFT/core/corr.py:13-60).  'local': `alternate_corr=True` on
+        every call -- no volume, the lookup recomputes its (2r+2)^2 dot products per iteration (corr.py:63-91; csrc/corr_local_tiled.hip),
+        workspace ~N instead of ~N^2 floats per pair.  'auto': local exactly for the calls whose batch the volume layout would have to
+        slice to fit the memory budget (`pairs_that_fit(B, H, W) < B`; a single pair whose volume layout does not fit counts as well),
+        volume otherwise.
+
         THE SMALL NETWORK (`raft-small.pth`, RAFT/core/raft.py:29-33): a state_dict with its key set builds it (`.variant == 'small'`;
         `weights.raft_variant` decides, the C side checks again).  It has no BatchNorm, so `cnet_norm` is ignored for it; it runs in
         exact fp32 only -- precision / volume_precision other than 'fp32' raise ValueError -- and every launch stays on the current
@@ -64,8 +72,11 @@ class RaftEngine:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
         if cnet_norm not in CNET_NORMS:
             raise ValueError(f"cnet_norm must be one of {sorted(CNET_NORMS)}")
+        if corr not in CORR_MODES:
+            raise ValueError(f"corr must be one of {CORR_MODES}")
         self.precision = precision
         self.cnet_norm = cnet_norm
+        self.corr = corr
         L = _lib.lib()
         if not torch.cuda.is_available():
             raise RuntimeError("RaftEngine needs a HIP device (no CPU fallback)")
@@ -107,8 +118,16 @@ class RaftEngine:
                 pass
             self._h = None
 
-    def _workspace(self, B: int, H: int, W: int) -> torch.Tensor:
-        need = _lib.lib().ofx_raft_workspace_bytes(self._h, B, H, W)
+    def _need(self, n_images: int, B: int, H: int, W: int, alternate_corr: bool = False, flags: int = 0) -> int:
+        """Workspace bytes of one executor call.  Volume mode: the entry point's classic size (the larger of the two layouts);
+        alternate_corr: the size of the layout the call's flags carve (`ofx_raft_workspace_bytes_mode`)."""
+        L = _lib.lib()
+        if alternate_corr:
+            return L.ofx_raft_workspace_bytes_mode(self._h, n_images, B, H, W, (flags & (FLAG_SHARED_IMG1 | FLAG_SHARED_IMG2)) | FLAG_ALT_CORR)
+        return L.ofx_raft_workspace_bytes_pairs(self._h, n_images, B, H, W) if n_images else L.ofx_raft_workspace_bytes(self._h, B, H, W)
+
+    def _workspace(self, B: int, H: int, W: int, alternate_corr: bool = False, flags: int = 0) -> torch.Tensor:
+        need = self._need(0, B, H, W, alternate_corr, flags)
         if need == 0:
             raise RuntimeError(f"unsupported shape B={B} H={H} W={W} (H, W must be multiples of 8)")
         if self._ws is None or self._ws.numel() < need:
@@ -116,49 +135,27 @@ class RaftEngine:
             self._ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def pairs_that_fit(self, B: int, H: int, W: int) -> int:
-        """Largest batch <= B whose executor workspace (dominated by the all-pairs correlation pyramid: ~1.33 x (H/8 x W/8)^2 floats
-        per pair -- 201 MB at 512x768, 5.6 GB at 1080x1920, 89 GB at 2160x3840) fits the device memory that is free right now
-        (plus this engine's cached workspace and the caching allocator's idle blocks), so that a large batch of large frames is
-        processed in slices instead of failing in the allocator.  `ws_budget_bytes` (attribute) overrides the measured budget."""
-        L = _lib.lib()
-        budget = self.ws_budget_bytes
-        if budget is None and self._ws is not None and L.ofx_raft_workspace_bytes(self._h, B, H, W) <= self._ws.numel():
-            return B                       # the cached workspace already holds this batch: nothing to measure
-        if budget is None:
-            free, _total = torch.cuda.mem_get_info(self.device)
-            idle = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
-            have = self._ws.numel() if self._ws is not None else 0
-            budget = int(0.92 * (free + idle + have))
-        if L.ofx_raft_workspace_bytes(self._h, B, H, W) <= budget:
-            return B
-        lo, hi = 1, B                      # need(b) grows with b: largest b that fits (at least 1: let the allocator speak for itself)
-        while lo < hi:
-            mid = (lo + hi + 1) // 2
-            if L.ofx_raft_workspace_bytes(self._h, mid, H, W) <= budget:
-                lo = mid
-            else:
-                hi = mid - 1
-        return lo
+    def _budget(self) -> int:
+        """`ws_budget_bytes`, else the device memory that is free right now plus this engine's cached workspace and the caching
+        allocator's idle blocks."""
+        if self.ws_budget_bytes is not None:
+            return self.ws_budget_bytes
+        free, _total = torch.cuda.mem_get_info(self.device)
+        idle = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
+        have = self._ws.numel() if self._ws is not None else 0
+        return int(0.92 * (free + idle + have))
 
-    def max_pairs_now(self, H: int, W: int, limit: Optional[int] = None) -> int:
-        """`max_pairs` further bounded by the device memory that is free right now, for the indexed-pairs calls (`forward_pairs`:
-        every pair may bring two images of its own -- the bound assumes so): what `pdcnet_of` slices its batches by."""
-        L = _lib.lib()
-        cap = self.pairs_per_call(H, W)
-        B = cap if limit is None else max(1, min(int(limit), cap))
-        Hp, Wp = (H + 7) // 8 * 8, (W + 7) // 8 * 8
-        need = lambda b: L.ofx_raft_workspace_bytes_pairs(self._h, 2 * b, b, Hp, Wp)
-        budget = self.ws_budget_bytes
-        if budget is None and self._ws is not None and need(B) <= self._ws.numel():
+    def _fits(self, need: int) -> bool:
+        if self.ws_budget_bytes is None and self._ws is not None and need <= self._ws.numel():
+            return True                    # the cached workspace already holds this call: nothing to measure
+        return need <= self._budget()
+
+    def _largest_that_fits(self, B: int, need) -> int:
+        """Largest b <= B with need(b) bytes inside the budget (`_budget`)."""
+        if self._fits(need(B)):
             return B
-        if budget is None:
-            free, _total = torch.cuda.mem_get_info(self.device)
-            idle = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
-            budget = int(0.92 * (free + idle + (self._ws.numel() if self._ws is not None else 0)))
-        lo, hi = 1, B
-        if need(B) <= budget:
-            return B
+        budget = self._budget()
+        lo, hi = 1, B                      # need(b) grows with b: largest b that fits (at least 1: let the allocator speak for itself)
         while lo < hi:
             mid = (lo + hi + 1) // 2
             if need(mid) <= budget:
@@ -166,6 +163,30 @@ class RaftEngine:
             else:
                 hi = mid - 1
         return lo
+
+    def pairs_that_fit(self, B: int, H: int, W: int, alternate_corr: bool = False) -> int:
+        """Largest batch <= B whose executor workspace (dominated by the all-pairs correlation pyramid: ~1.33 x (H/8 x W/8)^2 floats
+        per pair -- 201 MB at 512x768, 5.6 GB at 1080x1920, 89 GB at 2160x3840) fits the device memory that is free right now
+        (plus this engine's cached workspace and the caching allocator's idle blocks), so that a large batch of large frames is
+        processed in slices instead of failing in the allocator.  `ws_budget_bytes` (attribute) overrides the measured budget.
+        alternate_corr=True: by the size of the volume-free layout (no pyramid: ~3 K floats per 1/8-grid pixel and pair)."""
+        return self._largest_that_fits(B, lambda b: self._need(0, b, H, W, alternate_corr))
+
+    def max_pairs_now(self, H: int, W: int, limit: Optional[int] = None, alternate_corr: Optional[bool] = False) -> int:
+        """`max_pairs` further bounded by the device memory that is free right now, for the indexed-pairs calls (`forward_pairs`:
+        every pair may bring two images of its own -- the bound assumes so): what `pdcnet_of` slices its batches by.
+        alternate_corr: False = the volume layout, True = the volume-free one, None = the engine's `corr` default ('auto': the
+        volume-free bound when the volume layout would slice the batch)."""
+        cap = self.pairs_per_call(H, W)
+        B = cap if limit is None else max(1, min(int(limit), cap))
+        Hp, Wp = (H + 7) // 8 * 8, (W + 7) // 8 * 8
+        fit = lambda alt: self._largest_that_fits(B, lambda b: self._need(2 * b, b, Hp, Wp, alt))
+        if alternate_corr is None:
+            if self.corr == "auto":
+                v = fit(False)
+                return v if v >= B else fit(True)
+            alternate_corr = self.corr == "local"
+        return fit(bool(alternate_corr))
 
     @staticmethod
     def max_pairs(H: int, W: int) -> int:
@@ -196,7 +217,7 @@ class RaftEngine:
 
     @torch.no_grad()
     def forward(self, image1: torch.Tensor, image2: torch.Tensor, iters: int = 20, bgr: bool = False,
-                alternate_corr: bool = False, want_low: bool = False, serial: bool = False, separate_stats: bool = False,
+                alternate_corr: Optional[bool] = None, want_low: bool = False, serial: bool = False, separate_stats: bool = False,
                 warp_frame: Optional[torch.Tensor] = None, warp_sign: float = 1.0,
                 want_flow: bool = True, flow_init: Optional[torch.Tensor] = None):
         """image1: uint8 [B,H,W,3] or [H,W,3] (shared by the batch); image2 likewise.  Flow is defined
@@ -209,6 +230,8 @@ class RaftEngine:
         -1 = ofgen.warp_frame's) and returned after the flow: (flow_up[, flow_low], warped u8 [B,H,W,3]) -- bit-identical to
         `ops.warp(warp_frame, flow_up, mode="bilinear")`.  want_flow=False skips writing the full-resolution flow (None is returned in
         its place).
+        alternate_corr: True = no correlation volume (RAFT's alternate_corr, every combination of shared frames, warp and warm
+        start), False = the volume, None (default) = the engine's `corr` mode.
         flow_init: warm start (RAFT.forward(flow_init=...), raft.py:118-119): CUDA f32 [B,Hp/8,Wp/8,2] on the padded 1/8 grid (Hp, Wp =
         the size after pad_to_8), [Hp/8,Wp/8,2] when B == 1 -- the refinement starts at coords0 + flow_init instead of zero flow
         (OFX_RAFT_FLOW_INIT).  Typically `ops.forward_interpolate` of the previous pair's flow_low.  Not modified."""
@@ -235,8 +258,6 @@ class RaftEngine:
             flags |= FLAG_SHARED_IMG1
         if sh2:
             flags |= FLAG_SHARED_IMG2
-        if alternate_corr:
-            flags |= FLAG_ALT_CORR
         if warp_frame is not None:
             if not warp_frame.is_cuda or warp_frame.dtype != torch.uint8 or tuple(warp_frame.shape) != (H, W, 3):
                 raise RuntimeError(f"warp_frame must be a CUDA uint8 tensor [{H},{W},3] (the padded frame size)")
@@ -248,8 +269,14 @@ class RaftEngine:
         if flow_init is not None:
             flow_init = self._check_init(flow_init, B, H, W)
         max_pairs = self.pairs_per_call(H, W)
+        if alternate_corr is None:          # the engine's default mode; 'auto': local exactly when the volume layout would slice this batch
+            Bc = min(B, max_pairs)
+            alternate_corr = self.corr == "local" or (self.corr == "auto" and not self._fits(self._need(0, Bc, H, W)))   # (= pairs_that_fit(Bc) < Bc; one pair that does not fit counts too)
+        alternate_corr = bool(alternate_corr)
+        if alternate_corr:
+            flags |= FLAG_ALT_CORR
         if B > 1:
-            max_pairs = min(max_pairs, self.pairs_that_fit(min(B, max_pairs), H, W))
+            max_pairs = min(max_pairs, self.pairs_that_fit(min(B, max_pairs), H, W, alternate_corr))
         if B > max_pairs:
             outs = []
             for b0 in range(0, B, max_pairs):
@@ -261,7 +288,7 @@ class RaftEngine:
                 outs.append(r if isinstance(r, tuple) else (r,))
             cat = tuple(None if parts[0] is None else torch.cat(parts) for parts in zip(*outs))
             return cat if len(cat) > 1 else cat[0]
-        ws = self._workspace(B, H, W)
+        ws = self._workspace(B, H, W, alternate_corr, flags)
         flow_up = torch.empty((B, H, W, 2), dtype=torch.float32, device=self.device) if want_flow else None
         if flow_init is not None:       # flow_low is in/out: the initial flow in, the final one out
             flow_low = flow_init.clone(memory_format=torch.contiguous_format)
@@ -284,14 +311,16 @@ class RaftEngine:
     @torch.no_grad()
     def forward_pairs(self, images: torch.Tensor, idx1, idx2, iters: int = 20, bgr: bool = False,
                       warp_frame: Optional[torch.Tensor] = None, warp_sign: float = 1.0, n_warp: int = 0,
-                      flow_init: Optional[torch.Tensor] = None):
+                      flow_init: Optional[torch.Tensor] = None, alternate_corr: Optional[bool] = None):
         """images: uint8 [n,H,W,3] on the device (H, W multiples of 8); pair b = (idx1[b], idx2[b]):
         flow b lives on image idx1[b] and points into image idx2[b].  Every image is encoded once however
         many pairs use it (KeyframeConv's N x N sweep).  Returns f32 [B,H,W,2] on the device.
         warp_frame (uint8 [H,W,3], one frame shared by the batch) + n_warp: the first n_warp pairs also get the bilinear
         backward warp of warp_frame along their final flow, produced inside the convex upsample
         (`ofx_raft_forward_pairs_warp`); returns (flow, warped u8 [n_warp,H,W,3]).
-        flow_init: warm start, CUDA f32 [B,H/8,W/8,2], one initial flow per pair in pair order (see `forward`)."""
+        flow_init: warm start, CUDA f32 [B,H/8,W/8,2], one initial flow per pair in pair order (see `forward`).
+        alternate_corr: as in `forward` (None = the engine's `corr` mode; 'auto': local when the volume layout of this call does not
+        fit the memory budget -- this call never slices)."""
         if not images.is_cuda or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
             raise RuntimeError("images must be a CUDA uint8 tensor [n,H,W,3]")
         imgs = images.contiguous()
@@ -307,7 +336,10 @@ class RaftEngine:
         if flow_init is not None:
             flow_low = self._check_init(flow_init, B, H, W).clone(memory_format=torch.contiguous_format)
         L = _lib.lib()
-        need = L.ofx_raft_workspace_bytes_pairs(self._h, n, B, H, W)
+        if alternate_corr is None:
+            alternate_corr = self.corr == "local" or (self.corr == "auto" and not self._fits(self._need(n, B, H, W)))
+        alternate_corr = bool(alternate_corr)
+        need = self._need(n, B, H, W, alternate_corr)
         if need == 0:
             raise RuntimeError(f"unsupported shape n={n} B={B} H={H} W={W}")
         if self._ws is None or self._ws.numel() < need:
@@ -318,6 +350,8 @@ class RaftEngine:
         flags = (FLAG_BGR if bgr else 0) | PRECISIONS[self.precision] | CNET_NORMS[self.cnet_norm] | VOLUME_PRECISIONS[self.volume_precision]
         if flow_low is not None:
             flags |= FLAG_FLOW_INIT
+        if alternate_corr:
+            flags |= FLAG_ALT_CORR
         fl = C.c_void_p(flow_low.data_ptr() if flow_low is not None else 0)
         if warp_frame is None:
             check(L.ofx_raft_forward_pairs(self._h, C.c_void_p(imgs.data_ptr()), n, a1, a2, B, H, W, int(iters), flags,
