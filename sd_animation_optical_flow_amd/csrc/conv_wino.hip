@@ -125,8 +125,10 @@ template <class HALO, bool NORM> struct HaloStage {
     int hpix[HALO::slots];
     unsigned hok = 0;
     int hq;                          // byte offset of this thread's float4 slot (256 % 4 == 0: the same for every k)
-    float4 pa[HALO::slots];
-    float4 pmu, prs;                 // NORM: mean / rstd of this thread's four channels of the slab in flight
+    struct Regs {                    // a slab in flight
+        float4 pa[HALO::slots];
+        float4 pmu, prs;             // NORM: mean / rstd of this thread's four channels
+    } own;
 
     __device__ __forceinline__ HaloStage(const WinoK& p_, const Patch& pt, int tid_) : p(p_), pb(pt.pb), tid(tid_) {
         in1s = p.in1 ? p.in1 : p.in0;
@@ -143,7 +145,9 @@ template <class HALO, bool NORM> struct HaloStage {
         }
         hq = (tid & 3) * 16;
     }
-    __device__ __forceinline__ void issue(int cb) {
+    __device__ __forceinline__ void issue(int cb) { issue(cb, own); }
+    __device__ __forceinline__ void store(float* Hs) const { store(Hs, own); }
+    __device__ __forceinline__ void issue(int cb, Regs& r) {
         const int c = cb * kWBK;
         const bool s0 = c < p.c0;    // wave-uniform
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(s0 ? p.in0 : in1s), (short)0, s0 ? p.bytes0 : bytes1s, 0x00020000);
@@ -153,25 +157,25 @@ template <class HALO, bool NORM> struct HaloStage {
         for (int k = 0; k < HALO::slots; ++k) {
             const int vo = ((hok >> k) & 1u) ? hpix[k] * ldb + hq : kOOB;
             v4i t = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, 0);
-            pa[k] = *reinterpret_cast<float4*>(&t);
+            r.pa[k] = *reinterpret_cast<float4*>(&t);
         }
         if constexpr (NORM) {
             const long at = (long)pb * p.c0 + c + (tid & 3) * 4;
-            pmu = *reinterpret_cast<const float4*>(p.nmean + at);
-            prs = *reinterpret_cast<const float4*>(p.nrstd + at);
+            r.pmu = *reinterpret_cast<const float4*>(p.nmean + at);
+            r.prs = *reinterpret_cast<const float4*>(p.nrstd + at);
         }
     }
-    __device__ __forceinline__ void store(float* Hs) const {
+    __device__ __forceinline__ void store(float* Hs, const Regs& r) const {
 #pragma unroll
         for (int k = 0; k < HALO::slots; ++k) {
             const int i = tid + 256 * k;
             if (HALO::slots * 256 > HALO::items && k == HALO::slots - 1 && i >= HALO::items) break;
-            float4 v = pa[k];
+            float4 v = r.pa[k];
             if constexpr (NORM) {   // as the direct kernel's a_commit (conv.hip): padding is applied to the normalised map
-                v.x = fmaxf((v.x - pmu.x) * prs.x, 0.f);
-                v.y = fmaxf((v.y - pmu.y) * prs.y, 0.f);
-                v.z = fmaxf((v.z - pmu.z) * prs.z, 0.f);
-                v.w = fmaxf((v.w - pmu.w) * prs.w, 0.f);
+                v.x = fmaxf((v.x - r.pmu.x) * r.prs.x, 0.f);
+                v.y = fmaxf((v.y - r.pmu.y) * r.prs.y, 0.f);
+                v.z = fmaxf((v.z - r.pmu.z) * r.prs.z, 0.f);
+                v.w = fmaxf((v.w - r.pmu.w) * r.prs.w, 0.f);
                 if (!((hok >> k) & 1u)) v = make_float4(0.f, 0.f, 0.f, 0.f);
             }
             *reinterpret_cast<float4*>(&Hs[HALO::at(i >> 2) + (i & 3) * 4]) = v;
@@ -349,13 +353,16 @@ __device__ __forceinline__ void wino3x3_slabs(const WinoK& p, const Patch& pt, f
     const int at_a = at0 + ra * HALO::lrow, at_b = at0 + rb * HALO::lrow;
 
     const int CB = p.cin / kWBK;
-    hs.issue(0);
+    // both first halos go out ahead of the first weights: at every arrival at the loop's store the halo is then older than the
+    // eight fragments in flight, and the wait in front of it can leave those in flight (vmcnt retires in issue order)
+    typename HaloStage<HALO, NORM>::Regs h0;
+    hs.issue(0, h0);
+    hs.issue(CB > 1 ? 1 : 0);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) wr[q][nt] = u.load(pt0 + q, blk0 + nt, 0);
-    hs.store(Hs);
-    hs.issue(CB > 1 ? 1 : 0);
+    hs.store(Hs, h0);
     for (int cb = 0; cb < CB; ++cb) {
         const float* const H = Hs + (cb & 1) * HALO::floats;
         __syncthreads();   // slab cb is in H, and every wave has left the other buffer
@@ -380,7 +387,12 @@ __device__ __forceinline__ void wino3x3_slabs(const WinoK& p, const Patch& pt, f
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) {
                     wino_mfma4(acc[q][nt], v[q], wr[q][nt]);
-                    wr[q][nt] = u.load(pt0 + q, blk0 + nt, c8);   // the next step's fragment: three quarters of a step hide the load
+                    wr[q][nt] = u.load(pt0 + q, blk0 + nt, c8);   // the next step's fragment: 28 MFMAs hide the load
+                    // ... and stays here: four MFMAs, then their fragment's reload.  Left free, the scheduler sinks the loads to
+                    // their uses to save registers and every fragment is waited for within 3 MFMAs of its issue
+                    // (profiles/r15_wino_prefetch_isa.txt)
+                    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                 }
         }
     }
