@@ -19,6 +19,7 @@
  *   ofx_generate_mask, ofx_dilate_u8, ofx_expand_mask, ofx_travel_distance, ofx_flow_magnitude, ofx_merge_images,
  *   ofx_mix_frames, ofx_conf_sum
  *   ofx_groupnorm, ofx_softmax_rows, ofx_attention_f32
+ *   ofx_upconv2x, ofx_upsample2x_nearest_f32, ofx_decode_to_u8
  *                               ldm/modules/diffusionmodules/model.py:35-41,152-203 ; ldm/modules/attention.py:314,426
  *                               ofgen_keyframe_inpaint.py:113-133,237-248,306-322,676-688,968-973,995-1027
  *
@@ -160,6 +161,29 @@ int ofx_softmax_rows(float* x, long rows, long ld, int n, float scale, const flo
 size_t ofx_attention_workspace_bytes(int BH, int Nq, int Nk, int D);
 int ofx_attention_f32(const float* q, const float* k, const float* v, const float* bias, long bias_bstride, float* out,
                       int BH, int Nq, int Nk, int D, float scale, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------- first-stage decoder (decode_first_stage / decode_latent) */
+/* `Upsample` of the VAE decoder (ldm/modules/diffusionmodules/model.py:43-58): out = conv3x3(pad 1)(interpolate(x, 2x, nearest)) + bias
+ * without materialising the upsampled map.  Output pixel (2y + py, 2x + px) only sees the 2x2 low-resolution neighbourhood
+ * {y - 1 + py, y + py} x {x - 1 + px, x + px}: four 2x2 convolutions (one per parity) with the 3x3 taps that fall on the same
+ * low-resolution pixel added up beforehand -- 4 multiplies per output instead of 9; the zero padding of the upsampled map coincides
+ * with zero padding of the low-resolution map.
+ * ofx_upconv2x_weight (host): OIHW fp32 3x3 weights -> the four folded operands, summed in float64 and rounded once, as
+ * [4 parities][Cout][4 taps][Cin] floats (the exact index is documented at the definition, vae_dec.hip).  Returns the float count
+ * 16 * Cout * Cin (`out` may be NULL to query it) or OFX_EINVAL.
+ * ofx_upconv2x: x NHWC fp32 [B,H,W,Cin] (dense), w from ofx_upconv2x_weight (device), bias [Cout] or NULL -> out[((b*2H + Y)*2W + X)*ldo + n],
+ * ldo >= Cout, on v_mfma_f32_32x32x2_f32.  Any H, W >= 1 and any Cout; Cin % 4 == 0 and x, w 16-byte aligned (OFX_EALIGN otherwise);
+ * B*2H*2W < 2^31 (OFX_EINVAL beyond: slice the batch; addresses themselves are 64-bit). */
+long ofx_upconv2x_weight(const float* w_oihw, int Cout, int Cin, float* out);
+int ofx_upconv2x(const float* x, const float* w, const float* bias, float* out, int ldo, int B, int H, int W, int Cin, int Cout,
+                 void* stream);
+/* F.interpolate(x, scale_factor=2.0, mode="nearest") of an NHWC fp32 tensor: [B,H,W,C] -> [B,2H,2W,C] (the materialising half of the
+ * unfused pair; the VAE decoder takes it with OFX_VAE_NO_UPCONV=1).  C % 4 == 0, 16-byte aligned; B*2H*2W < 2^31. */
+int ofx_upsample2x_nearest_f32(const float* in, float* out, int B, int H, int W, int C, void* stream);
+/* decode_latent's exit (ofgen_keyframe_inpaint.py:234-235): x f32 NHWC RGB rows of ld >= 3 floats -> out u8 BGR [B,H,W,3] =
+ * (clip(x, -1, 1) * 127.5 + 127.5) truncated toward zero, the product and the sum rounded separately in fp32 (numpy's bits).
+ * x and out 4-byte aligned. */
+int ofx_decode_to_u8(const float* x, int ld, uint8_t* out, int B, int H, int W, void* stream);
 
 /* ---------------------------------------------------------------- key-frame detector */
 /* edges[b] = cv2.dilate(cv2.Canny(V, low, high), ones(ksize, ksize)) for BGR frames u8[B,H,W,3], with V = max(B,G,R)

@@ -1,0 +1,303 @@
+// First-stage (VAE) decoder pieces that the convolution / norm / attention kernels do not cover
+// (ldm/modules/diffusionmodules/model.py:43-58 `Upsample`, ofgen_keyframe_inpaint.py:234-235 `decode_latent`):
+//
+//   ofx_upconv2x              conv3x3(pad 1)(interpolate(x, 2x, nearest)) without the upsampled map: output pixel (2y + py, 2x + px)
+//                             sees only the 2x2 low-resolution neighbourhood rows {y - 1 + py, y + py} x columns {x - 1 + px, x + px},
+//                             with the 3x3 taps that land on the same low-resolution pixel added up beforehand
+//                             (ofx_upconv2x_weight).  Four implicit GEMMs (one per parity, blockIdx.y) of M = B*H*W low-resolution
+//                             pixels, N = Cout, K = 4 * Cin on v_mfma_f32_32x32x2_f32; each scatters its rows to its parity of the
+//                             [B,2H,2W] map.  4 taps per output instead of 9, and the 4x larger map is written once, never read.
+//   ofx_upsample2x_nearest_f32  the materialising upsample (the unfused pair's first half)
+//   ofx_decode_to_u8          f32 RGB in [-1,1] -> u8 BGR, the bits of the reference's numpy expression
+//
+// The GEMM follows conv.hip's general schedule in its plainest form: 256 threads = 2x2 waves, a 128 x BN tile (BN = 128, or 64 for
+// narrow layers), 16-wide K chunks staged k-contiguous in LDS with a 20-float row stride (conflict-free ds_read_b128 fragments, one
+// read feeding four MFMAs; lane half h supplies k = 8 ks + 4 h + s to MFMA s -- the same permutation on both operands), two LDS
+// stages, one barrier per chunk, the next chunk's global loads in flight during the MFMA block.  Addresses are 64-bit; rows past M /
+// Cout, taps in the zero padding and channels past Cin stage zeros.
+#include "ofx_internal.h"
+
+#include <algorithm>
+#include <cstdlib>
+
+namespace {
+
+constexpr int kBK = 16;            // K chunk
+constexpr int kLDK = kBK + 4;      // LDS row stride in floats
+
+struct UpK {
+    const float* x;
+    const float* w;                // [4 parities][Cout][4 taps][Cin]
+    const float* bias;
+    float* out;
+    int B, H, W, Cin, Cout, ldo;
+    int M;                         // B * H * W
+    int ntiles;
+    int cchunks;                   // ceil(Cin / 16)
+};
+
+template <int BN>
+__global__ __launch_bounds__(256) void upconv2x_kernel(const UpK p) {
+    constexpr int BM = 128, WM = 64, WN = BN / 2, TM = WM / 32, TN = WN / 32;
+    constexpr int B_PER = BN / 64;                    // 64 rows of 4 float4 slots per pass of the 256 threads
+    constexpr int STAGE = (BM + BN) * kLDK;
+    __shared__ __attribute__((aligned(16))) float smem[2 * STAGE];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int nt = blockIdx.x % p.ntiles, mt = blockIdx.x / p.ntiles;
+    const int par = blockIdx.y, py = par >> 1, px = par & 1;
+    const int m0 = mt * BM, n0 = nt * BN;
+
+    // staging role: float4 slot kq of rows r0 and r0 + 64; rows permuted inside groups of 16 so that one ds_write_b128 pass
+    // (16 lanes) covers 16 distinct 16-byte bank groups (conv.hip, r0)
+    const int kq = tid & 3, j0 = tid >> 2;
+    const int r0 = (j0 & 3) * 4 + ((j0 >> 2) & 3) + (j0 >> 4) * 16;
+    const int HW = p.H * p.W;
+    int a_b[2], a_y[2], a_x[2];
+    bool a_ok[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int m = m0 + r0 + 64 * i;
+        a_ok[i] = m < p.M;
+        const int mm = a_ok[i] ? m : 0;
+        a_b[i] = mm / HW;
+        const int rem = mm - a_b[i] * HW;
+        a_y[i] = rem / p.W;
+        a_x[i] = rem - a_y[i] * p.W;
+    }
+    const size_t wrow = (size_t)4 * p.Cin;            // floats per output channel of one parity
+    const float* wpar = p.w + (size_t)par * p.Cout * wrow;
+
+    f32x4 ra[2], rb[B_PER];        // native vectors: a select between two of them stays in registers
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    // branch-free: a lane whose float4 does not exist reads the first 16 bytes of the operand instead and keeps zeros
+    auto load = [&](int t, int cb) __attribute__((always_inline)) {
+        const int ty = t >> 1, tx = t & 1;
+        const int c = cb * kBK + kq * 4;
+        const bool cok = c < p.Cin;                   // Cin % 4 == 0: a float4 is inside or outside as a whole
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int iy = a_y[i] - 1 + py + ty, ix = a_x[i] - 1 + px + tx;
+            const bool ok = cok && a_ok[i] && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
+            const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? p.x + (((size_t)a_b[i] * p.H + iy) * p.W + ix) * p.Cin + c : p.x);
+            ra[i] = ok ? v : zero4;
+        }
+#pragma unroll
+        for (int i = 0; i < B_PER; ++i) {
+            const int n = n0 + r0 + 64 * i;
+            const bool ok = cok && n < p.Cout;
+            const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? wpar + (size_t)n * wrow + (size_t)t * p.Cin + c : p.w);
+            rb[i] = ok ? v : zero4;
+        }
+    };
+    auto commit = [&](float* st) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) *reinterpret_cast<f32x4*>(st + (r0 + 64 * i) * kLDK + kq * 4) = ra[i];
+#pragma unroll
+        for (int i = 0; i < B_PER; ++i) *reinterpret_cast<f32x4*>(st + (BM + r0 + 64 * i) * kLDK + kq * 4) = rb[i];
+    };
+
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+    const int NK = 4 * p.cchunks;
+    int t_next = 0, cb_next = 0;
+    auto advance = [&]() __attribute__((always_inline)) {
+        if (++cb_next == p.cchunks) { cb_next = 0; ++t_next; }
+    };
+    load(t_next, cb_next);
+    advance();
+    commit(smem);
+    __syncthreads();
+    const int frow = lane & 31, fk = (lane >> 5) * 4;
+    for (int kt = 0; kt < NK; ++kt) {
+        const bool more = kt + 1 < NK;
+        if (more) {
+            load(t_next, cb_next);
+            advance();
+        }
+        const float* As = smem + (kt & 1) * STAGE;
+        const float* Bs = As + BM * kLDK;
+#pragma unroll
+        for (int ks = 0; ks < kBK / 8; ++ks) {
+            f32x4 a[TM], b[TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const f32x4*>(As + (wm * WM + i * 32 + frow) * kLDK + ks * 8 + fk);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const f32x4*>(Bs + (wn * WN + j * 32 + frow) * kLDK + ks * 8 + fk);
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].x, b[j].x, acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, b[j].y, acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].z, b[j].z, acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, b[j].w, acc[i][j], 0, 0, 0);
+                }
+        }
+        if (more) commit(smem + ((kt + 1) & 1) * STAGE);
+        __syncthreads();
+    }
+
+    // epilogue.  C layout of the 32x32 MFMA: column n = lane & 31, row m = (e & 3) + 8 (e >> 2) + 4 (lane >> 5).  Row m is the
+    // low-resolution pixel (b, y, x); it lands on pixel (2y + py, 2x + px) of the [B, 2H, 2W] map.
+    const int H2 = 2 * p.H, W2 = 2 * p.W;
+    int ncol[TN];
+    float bv[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        ncol[j] = n0 + wn * WN + j * 32 + (lane & 31);
+        bv[j] = (p.bias && ncol[j] < p.Cout) ? p.bias[ncol[j]] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int m = m0 + wm * WM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+            if (m >= p.M) continue;
+            const int b = m / HW;
+            const int rem = m - b * HW;
+            const int y = rem / p.W, x = rem - y * p.W;
+            float* orow = p.out + (((size_t)b * H2 + 2 * y + py) * W2 + 2 * x + px) * p.ldo;
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                if (ncol[j] < p.Cout) orow[ncol[j]] = acc[i][j][e] + bv[j];
+        }
+}
+
+// out[b, Y, X, :] = in[b, Y / 2, X / 2, :], float4 per thread
+__global__ __launch_bounds__(256) void upsample2x_kernel(const float4* __restrict__ in, float4* __restrict__ out, int H, int W, int C4, size_t total) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const int W2 = 2 * W, H2 = 2 * H;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int c = (int)(i % C4);
+        const size_t pix = i / C4;
+        const int X = (int)(pix % W2);
+        const size_t rest = pix / W2;
+        const int Y = (int)(rest % H2);
+        const size_t b = rest / H2;
+        out[i] = in[((b * H + (Y >> 1)) * W + (X >> 1)) * C4 + c];
+    }
+}
+
+// (clip(x, -1, 1) * 127.5 + 127.5) truncated: the product and the sum are rounded separately, as numpy does.  Contraction is switched
+// off for this function: the __fmul_rn / __fadd_rn intrinsics are plain operators here and would fuse into one v_fma_f32, which
+// lands on the other byte for values next to a byte boundary.
+__device__ __forceinline__ unsigned dec_byte(float v) {
+#pragma clang fp contract(off)
+    v = fminf(fmaxf(v, -1.0f), 1.0f);
+    const float prod = v * 127.5f;
+    const float sum = prod + 127.5f;
+    return (unsigned)(int)sum;
+}
+
+// four pixels per thread: 12 output bytes as three 32-bit words (BGR BGR BGR BGR); the last, short group byte by byte
+__global__ __launch_bounds__(256) void decode_to_u8_kernel(const float* __restrict__ x, int ld, uint8_t* __restrict__ out, size_t npix) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t p0 = g * 4;
+    if (p0 >= npix) return;
+    unsigned by[12];
+    const int cnt = (int)(npix - p0 < 4 ? npix - p0 : 4);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float* px = x + (p0 + (q < cnt ? q : 0)) * ld;
+        by[3 * q + 0] = dec_byte(px[2]);
+        by[3 * q + 1] = dec_byte(px[1]);
+        by[3 * q + 2] = dec_byte(px[0]);
+    }
+    if (cnt == 4) {
+        uint32_t* o = reinterpret_cast<uint32_t*>(out + p0 * 3);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o[k] = by[4 * k] | (by[4 * k + 1] << 8) | (by[4 * k + 2] << 16) | (by[4 * k + 3] << 24);
+    } else {
+        for (int k = 0; k < 3 * cnt; ++k) out[p0 * 3 + k] = (uint8_t)by[k];
+    }
+}
+
+}  // namespace
+
+// Operand order: out[((p * Cout + o) * 4 + t) * Cin + c], parity p = 2 py + px of the output pixel (2y + py, 2x + px), tap
+// t = 2 ty + tx over the low-resolution pixel (y - 1 + py + ty, x - 1 + px + tx).  Along each axis the three taps fold as
+//   parity 0: tap 0 = w[0], tap 1 = w[1] + w[2]          parity 1: tap 0 = w[0] + w[1], tap 1 = w[2]
+// (the upsampled rows 2y - 1 | 2y, 2y + 1 are the low-resolution rows y - 1 | y, y, and 2y, 2y + 1 | 2y + 2 are y, y | y + 1); the
+// up-to-four products are summed in float64 and rounded once.
+extern "C" long ofx_upconv2x_weight(const float* w, int Cout, int Cin, float* out) {
+    if (Cout <= 0 || Cin <= 0) return OFX_EINVAL;
+    const long n = 16L * Cout * Cin;
+    if (!out) return n;
+    if (!w) return OFX_EINVAL;
+    // fold[parity][tap][k]: does 3-tap index k belong to folded tap `tap`
+    static const int fold[2][2][3] = {{{1, 0, 0}, {0, 1, 1}}, {{1, 1, 0}, {0, 0, 1}}};
+    for (int py = 0; py < 2; ++py)
+        for (int px = 0; px < 2; ++px)
+            for (int o = 0; o < Cout; ++o)
+                for (int ty = 0; ty < 2; ++ty)
+                    for (int tx = 0; tx < 2; ++tx)
+                        for (int c = 0; c < Cin; ++c) {
+                            const float* g = w + ((size_t)o * Cin + c) * 9;
+                            double s = 0.0;
+                            for (int ky = 0; ky < 3; ++ky)
+                                for (int kx = 0; kx < 3; ++kx)
+                                    if (fold[py][ty][ky] && fold[px][tx][kx]) s += (double)g[ky * 3 + kx];
+                            out[((((size_t)(2 * py + px) * Cout + o) * 4 + 2 * ty + tx)) * Cin + c] = (float)s;
+                        }
+    return n;
+}
+
+extern "C" int ofx_upconv2x(const float* x, const float* w, const float* bias, float* out, int ldo, int B, int H, int W, int Cin,
+                            int Cout, void* stream) {
+    OFX_REQUIRE(x && w && out, OFX_EINVAL);
+    OFX_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && ldo >= Cout, OFX_EINVAL);
+    OFX_REQUIRE(Cin % 4 == 0 && ofx_aligned16(x) && ofx_aligned16(w), OFX_EALIGN);
+    OFX_REQUIRE((((uintptr_t)out) & 3u) == 0 && (!bias || (((uintptr_t)bias) & 3u) == 0), OFX_EALIGN);
+    // rows and pixels are 32-bit ints in the kernel (addresses are 64-bit): the upsampled map must have fewer than 2^31 pixels
+    const long M = (long)B * H * W;
+    OFX_REQUIRE(4 * M < (1L << 31), OFX_EINVAL);
+    UpK k;
+    k.x = x; k.w = w; k.bias = bias; k.out = out;
+    k.B = B; k.H = H; k.W = W; k.Cin = Cin; k.Cout = Cout; k.ldo = ldo;
+    k.M = (int)M;
+    k.cchunks = (Cin + kBK - 1) / kBK;
+    const int bn = Cout <= 64 ? 64 : 128;
+    k.ntiles = (Cout + bn - 1) / bn;
+    const long mtiles = (M + 127) / 128;
+    OFX_REQUIRE(mtiles * k.ntiles < (1L << 31), OFX_EINVAL);
+    hipStream_t s = (hipStream_t)stream;
+    OfxProfScope prof("upconv2x", s);
+    prof.flops(2.0 * 4.0 * (double)M * Cout * 4.0 * Cin);
+    dim3 grid((unsigned)(mtiles * k.ntiles), 4, 1), block(256, 1, 1);
+    if (bn == 64) hipLaunchKernelGGL(upconv2x_kernel<64>, grid, block, 0, s, k);
+    else hipLaunchKernelGGL(upconv2x_kernel<128>, grid, block, 0, s, k);
+    return ofx_launch_status();
+}
+
+extern "C" int ofx_upsample2x_nearest_f32(const float* in, float* out, int B, int H, int W, int C, void* stream) {
+    OFX_REQUIRE(in && out && B > 0 && H > 0 && W > 0 && C > 0, OFX_EINVAL);
+    OFX_REQUIRE(C % 4 == 0 && ofx_aligned16(in) && ofx_aligned16(out), OFX_EALIGN);
+    OFX_REQUIRE(4L * B * H * W < (1L << 31), OFX_EINVAL);
+    const size_t total = (size_t)4 * B * H * W * (C / 4);
+    hipStream_t s = (hipStream_t)stream;
+    OfxProfScope prof("upsample2x_nearest", s);
+    const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 32);
+    hipLaunchKernelGGL(upsample2x_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(in), reinterpret_cast<float4*>(out),
+                       H, W, C / 4, total);
+    return ofx_launch_status();
+}
+
+extern "C" int ofx_decode_to_u8(const float* x, int ld, uint8_t* out, int B, int H, int W, void* stream) {
+    OFX_REQUIRE(x && out && B > 0 && H > 0 && W > 0 && ld >= 3, OFX_EINVAL);
+    OFX_REQUIRE((((uintptr_t)x) & 3u) == 0 && (((uintptr_t)out) & 3u) == 0, OFX_EALIGN);
+    const size_t npix = (size_t)B * H * W;
+    OFX_REQUIRE(npix < ((size_t)1 << 33), OFX_EINVAL);       // one thread per four pixels, at most 2^31 - 1 workgroups
+    hipStream_t s = (hipStream_t)stream;
+    OfxProfScope prof("decode_to_u8", s);
+    const size_t groups = (npix + 3) / 4;
+    hipLaunchKernelGGL(decode_to_u8_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, x, ld, out, npix);
+    return ofx_launch_status();
+}

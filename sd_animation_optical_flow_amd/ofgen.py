@@ -7,6 +7,7 @@ Same names, argument meaning and mutation behaviour as the reference functions t
     forward_interpolate(flow)                        RAFT/core/utils/utils.py:26-53 (+ RAFT_2(warm_start=True))
     warp_frame(frame, flow)          (RAFT convention) ofgen_keyframe_inpaint.py:92-98
     warp_frame_latent(latent, flow)                  ofgen_keyframe_inpaint.py:100-111
+    decode_latent(model, latent)     (model: VaeDecoder) ofgen_keyframe_inpaint.py:234-235 ; ofgen_pixel_inpaint.py:215-216
     of_calc(frame1, frame2, algo)                    ofgen_keyframe_inpaint.py:113-133 ; ofgen.py:45-49 (bare-flow algo -> (flow, v))
     generate_mask(conf, log_conf, thres)             ofgen_keyframe_inpaint.py:317-322  (mutates log_conf)
     create_mask_aux / confidence_to_mask             ofgen_keyframe_inpaint.py:237-248, 292-304
@@ -129,6 +130,16 @@ def warp_frame_latent(latent: torch.Tensor, flow, mode: Optional[str] = None, de
     up = ops.resize_cubic(lat.permute(0, 2, 3, 1).contiguous(), h, w)
     wp = ops.warp(up, fl[None].contiguous(), mode=mode, sign=-1.0)
     return ops.resize_cubic(wp, lh, lw).permute(0, 3, 1, 2).contiguous().cpu()
+
+
+def decode_latent(model, latent) -> np.ndarray:
+    """ofgen_keyframe_inpaint.py:234-235: a [1,4,h,w] latent -> the BGR uint8 frame [8h,8w,3].  `model` is a
+    `vae.VaeDecoder` (the reference passes the whole LDM and uses its first stage only)."""
+    lat = latent if torch.is_tensor(latent) else torch.from_numpy(np.asarray(latent, np.float32))
+    lat = lat.detach().to(torch.float32).to(model.device).contiguous()
+    if lat.dim() != 4 or lat.shape[0] != 1:
+        raise RuntimeError("decode_latent: latent must be [1,4,h,w]")
+    return model.decode_latent(lat)[0].cpu().numpy()
 
 
 def of_calc(frame1, frame2, algo, verbose: bool = False):

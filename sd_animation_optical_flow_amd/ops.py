@@ -701,6 +701,64 @@ def groupnorm(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[tor
     return out
 
 
+def upconv2x_weight(w_oihw: torch.Tensor) -> torch.Tensor:
+    """OIHW fp32 3x3 (CPU) -> the four parity-folded 2x2 operands of `upconv2x` (float64 sums, one rounding) as an fp32 CPU tensor
+    [4, Cout, 4, Cin]: parity 2*py + px of the output pixel, tap 2*ty + tx over the low-resolution pixel
+    (y - 1 + py + ty, x - 1 + px + tx) (ofx_upconv2x_weight)."""
+    w = w_oihw.detach().to(torch.float32).contiguous().cpu()
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise RuntimeError("upconv2x_weight: OIHW 3x3 weights only")
+    co, ci = int(w.shape[0]), int(w.shape[1])
+    return _wino_weight("ofx_upconv2x_weight", w, co, ci).reshape(4, co, 4, ci)
+
+
+def upconv2x(x: torch.Tensor, w_folded: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+             out_off: int = 0) -> torch.Tensor:
+    """conv3x3(pad 1)(nearest 2x upsample of x) + bias in one kernel that never forms the upsampled map: x [B,H,W,Cin],
+    w_folded [4,Cout,4,Cin] from `upconv2x_weight` (on the device) -> [B,2H,2W,Cout].  `out` [B,2H,2W,C >= out_off + Cout]: write
+    channels [out_off, out_off + Cout) of it (a strided row)."""
+    x = _chk(x, "x", torch.float32)
+    w = _chk(w_folded, "w_folded", torch.float32)
+    if x.dim() != 4 or w.dim() != 4 or w.shape[0] != 4 or w.shape[2] != 4 or w.shape[3] != x.shape[3]:
+        raise RuntimeError(f"upconv2x: x [B,H,W,Cin] and w_folded [4,Cout,4,Cin] expected, got {tuple(x.shape)} and {tuple(w.shape)}")
+    B, H, W, ci = x.shape
+    co = int(w.shape[1])
+    b = None if bias is None else _chk(bias, "bias", torch.float32)
+    if b is not None and tuple(b.shape) != (co,):
+        raise RuntimeError(f"upconv2x: bias must be [{co}]")
+    if out is None:
+        out = torch.empty((B, 2 * H, 2 * W, co), dtype=torch.float32, device=x.device)
+    out = _chk(out, "out", torch.float32)
+    if tuple(out.shape[:3]) != (B, 2 * H, 2 * W) or out_off < 0 or out.shape[3] < out_off + co:
+        raise RuntimeError(f"out must be [{B},{2 * H},{2 * W},>= {out_off + co}], got {tuple(out.shape)}")
+    check(_lib.lib().ofx_upconv2x(_ptr(x), _ptr(w), _ptr(b), C.c_void_p(out.data_ptr() + 4 * out_off), out.shape[3], B, H, W, ci, co,
+                                  _stream()), "ofx_upconv2x")
+    return out
+
+
+def upsample2x_nearest(x: torch.Tensor) -> torch.Tensor:
+    """F.interpolate(scale_factor=2.0, mode="nearest") of an NHWC fp32 tensor [B,H,W,C] -> [B,2H,2W,C] (C % 4 == 0)."""
+    x = _chk(x, "x", torch.float32)
+    if x.dim() != 4:
+        raise RuntimeError("upsample2x_nearest: x must be [B,H,W,C]")
+    B, H, W, Cn = x.shape
+    out = torch.empty((B, 2 * H, 2 * W, Cn), dtype=torch.float32, device=x.device)
+    check(_lib.lib().ofx_upsample2x_nearest_f32(_ptr(x), _ptr(out), B, H, W, Cn, _stream()), "ofx_upsample2x_nearest_f32")
+    return out
+
+
+def decode_to_u8(x: torch.Tensor) -> torch.Tensor:
+    """f32 NHWC RGB [B,H,W,C >= 3] (the first three channels are read) -> u8 BGR [B,H,W,3] =
+    (clip(x, -1, 1) * 127.5 + 127.5).astype(uint8), the bits of decode_latent's numpy expression."""
+    x = _chk(x, "x", torch.float32)
+    if x.dim() != 4 or x.shape[3] < 3:
+        raise RuntimeError("decode_to_u8: x must be [B,H,W,C >= 3]")
+    B, H, W, ld = x.shape
+    out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=x.device)
+    check(_lib.lib().ofx_decode_to_u8(_ptr(x), ld, _ptr(out), B, H, W, _stream()), "ofx_decode_to_u8")
+    return out
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bias: Optional[torch.Tensor] = None,
               scale: Optional[float] = None, max_workspace_bytes: int = 8 << 30) -> torch.Tensor:
     """softmax(q k^T * scale + bias) v for fp32 [BH,Nq,D] / [BH,Nk,D] tensors; bias [Nq,Nk] (shared) or [BH,Nq,Nk].

@@ -1,4 +1,4 @@
-"""First-stage (VAE) encoding of the SD-inpaint hand-off on the device.
+"""First-stage (VAE) encoding and decoding of the SD-inpaint hand-off on the device.
 
 `img2img_inpaint` turns the composited frame into `init_latent = get_first_stage_encoding(encode_first_stage(image))`
 (guided_ldm_inpainting.py:302) before the first denoising step.  `encode_first_stage` is `AutoencoderKL.encode`
@@ -12,10 +12,19 @@ cores (`ofx_conv2d`, residual sums as pre-activation addends of the epilogue), G
 installed, model.py:282-290).  State-dict keys are the reference's (`encoder.*`, `quant_conv.*`; the `first_stage_model.`
 prefix of full SD checkpoints is accepted).  No checkpoint ships with the reference tree: parity is pinned with seeded
 weights loaded into the reference's own `Encoder` (tests/golden/make_golden_vae.py).
+
+The way back is `VaeDecoder`: `decode_first_stage` (ldm/models/diffusion/ddpm.py:820-828) = `AutoencoderKL.decode`
+(autoencoder.py: `post_quant_conv` -> `Decoder.forward`, model.py:619-652) of `z / scale_factor`, and `decode_latent`
+(ofgen_keyframe_inpaint.py:234-235), which ends in the BGR byte frame.  Same kernels, plus the decoder's own: each `Upsample`
+(nearest 2x + 3x3 convolution, model.py:43-58) is one `ofx_upconv2x` launch that never forms the upsampled map and contracts 4 taps
+per output instead of 9 (OFX_VAE_NO_UPCONV=1 in the environment, read once per process: `ofx_upsample2x_nearest_f32` +
+`ofx_conv2d` instead), and `ofx_decode_to_u8` makes the bytes.  Pinned the same way (tests/golden/make_golden_vae_decoder.py).
 """
 from __future__ import annotations
 
+import functools
 import math
+import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -83,28 +92,102 @@ def random_vae_state_dict(seed: int = 0, cfg: dict = SD_V1_CONFIG) -> Dict[str, 
     return sd
 
 
-class VaeEncoder:
-    """`AutoencoderKL.encode` + `get_first_stage_encoding` on a HIP device."""
+def decoder_tensors(cfg: dict = SD_V1_CONFIG) -> List[Tuple[str, Tuple[int, ...]]]:
+    """(key, shape) of every tensor of `decoder.*` + `post_quant_conv.*` for a ddconfig, in module order (model.py:546-617: the
+    levels are built from the coarsest down, `up` is indexed from the finest up)."""
+    ch, mult, nres = cfg["ch"], tuple(cfg["ch_mult"]), cfg["num_res_blocks"]
+    out: List[Tuple[str, Tuple[int, ...]]] = []
 
-    def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", cfg: dict = SD_V1_CONFIG, scale_factor: float = SCALE_FACTOR):
+    def conv(name, co, ci, k):
+        out.append((f"{name}.weight", (co, ci, k, k)))
+        out.append((f"{name}.bias", (co,)))
+
+    def norm(name, c):
+        out.append((f"{name}.weight", (c,)))
+        out.append((f"{name}.bias", (c,)))
+
+    def resblock(name, ci, co):
+        norm(f"{name}.norm1", ci)
+        conv(f"{name}.conv1", co, ci, 3)
+        norm(f"{name}.norm2", co)
+        conv(f"{name}.conv2", co, co, 3)
+        if ci != co:
+            conv(f"{name}.nin_shortcut", co, ci, 1)
+
+    block_in = ch * mult[-1]
+    conv("decoder.conv_in", block_in, cfg["z_channels"], 3)
+    resblock("decoder.mid.block_1", block_in, block_in)
+    norm("decoder.mid.attn_1.norm", block_in)
+    for nm in ("q", "k", "v", "proj_out"):
+        conv(f"decoder.mid.attn_1.{nm}", block_in, block_in, 1)
+    resblock("decoder.mid.block_2", block_in, block_in)
+    io = {}
+    for lvl in reversed(range(len(mult))):
+        io[lvl] = (block_in, ch * mult[lvl])
+        block_in = ch * mult[lvl]
+    for lvl in range(len(mult)):
+        ci, co = io[lvl]
+        for j in range(nres + 1):
+            resblock(f"decoder.up.{lvl}.block.{j}", ci if j == 0 else co, co)
+        if lvl != 0:
+            conv(f"decoder.up.{lvl}.upsample.conv", co, co, 3)
+    norm("decoder.norm_out", block_in)
+    conv("decoder.conv_out", cfg.get("out_ch", 3), block_in, 3)
+    conv("post_quant_conv", cfg["z_channels"], cfg["embed_dim"], 1)
+    return out
+
+
+def _random_tensors(tensors, g: torch.Generator) -> Dict[str, torch.Tensor]:
+    sd = {}
+    for key, shape in tensors:
+        if len(shape) == 4:
+            fan_in = shape[1] * shape[2] * shape[3]
+            sd[key] = torch.randn(shape, generator=g) * (1.0 / math.sqrt(fan_in))
+        elif ".norm" in key and key.endswith(".weight"):
+            sd[key] = 1.0 + 0.1 * torch.randn(shape, generator=g)
+        else:
+            sd[key] = 0.05 * torch.randn(shape, generator=g)
+    return sd
+
+
+def random_vae_decoder_state_dict(seed: int = 0, cfg: dict = SD_V1_CONFIG) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for the decoder half of the absent checkpoint, drawn from a generator of its own (the encoder's tensors of
+    `random_vae_state_dict` do not depend on it)."""
+    return _random_tensors(decoder_tensors(cfg), torch.Generator().manual_seed(int(seed) + 104729))
+
+
+@functools.lru_cache(maxsize=None)
+def _no_upconv() -> bool:
+    """OFX_VAE_NO_UPCONV=1 (diagnostic, read once per process): the decoder's Upsample layers run unfused."""
+    return os.environ.get("OFX_VAE_NO_UPCONV", "") not in ("", "0")
+
+
+class _VaeBlocks:
+    """What `Encoder` and `Decoder` share (model.py): weights on the device in the kernels' layouts, and the convolution, GroupNorm,
+    ResnetBlock and AttnBlock calls."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], tensors, device, cfg: dict, scale_factor: float):
         if not torch.cuda.is_available():
-            raise RuntimeError("VaeEncoder needs a HIP device (no CPU fallback)")
+            raise RuntimeError(f"{type(self).__name__} needs a HIP device (no CPU fallback)")
         self.cfg, self.device, self.scale_factor = dict(cfg), torch.device(device), float(scale_factor)
         sd = {}
         for k, v in state_dict.items():
             k = k[len("first_stage_model."):] if k.startswith("first_stage_model.") else k
             sd[k] = v
         self.w: Dict[str, torch.Tensor] = {}
-        for key, shape in encoder_tensors(self.cfg):
+        for key, shape in tensors:
             if key not in sd:
                 raise KeyError(f"VAE checkpoint lacks {key}")
             t = sd[key].detach().to(torch.float32)
             if tuple(t.shape) != tuple(shape):
                 raise ValueError(f"{key}: shape {tuple(t.shape)} != {shape}")
-            if len(shape) == 4:
-                self.w[key] = ops.pack_conv_weight(t).to(self.device)           # [Cout, Kpad], Cin padded to a multiple of 4
-            else:
-                self.w[key] = t.contiguous().to(self.device)
+            self._load(key, t)
+
+    def _load(self, key: str, t: torch.Tensor) -> None:
+        if t.dim() == 4:
+            self.w[key] = ops.pack_conv_weight(t).to(self.device)           # [Cout, Kpad], Cin padded to a multiple of 4
+        else:
+            self.w[key] = t.contiguous().to(self.device)
 
     # ---- building blocks (model.py line numbers) -----------------------------------------------------------
     def _conv(self, name: str, x: torch.Tensor, k: int, stride: int = 1, addend: Optional[torch.Tensor] = None,
@@ -131,6 +214,13 @@ class VaeEncoder:
         v = self._conv(f"{name}.v", hn, 1).reshape(B, H * W, Cn)
         a = ops.attention(q, k, v, None, float(Cn) ** -0.5).reshape(B, H, W, Cn)
         return self._conv(f"{name}.proj_out", a, 1, addend=x)
+
+
+class VaeEncoder(_VaeBlocks):
+    """`AutoencoderKL.encode` + `get_first_stage_encoding` on a HIP device."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", cfg: dict = SD_V1_CONFIG, scale_factor: float = SCALE_FACTOR):
+        super().__init__(state_dict, encoder_tensors(cfg), device, cfg, scale_factor)
 
     def max_batch(self, H: int, W: int) -> int:
         """Images one pass of the encoder can take at this size: the convolution kernel addresses its operands with 32-bit byte
@@ -182,3 +272,89 @@ class VaeEncoder:
     def get_first_stage_encoding(self, image: torch.Tensor, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """`self.get_first_stage_encoding(self.encode_first_stage(image))` (guided_ldm_inpainting.py:302)."""
         return self.scale_factor * self.sample(self.encode_moments(image), noise)
+
+
+class VaeDecoder(_VaeBlocks):
+    """`AutoencoderKL.decode` / `decode_first_stage` / `decode_latent` on a HIP device."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", cfg: dict = SD_V1_CONFIG, scale_factor: float = SCALE_FACTOR):
+        super().__init__(state_dict, decoder_tensors(cfg), device, cfg, scale_factor)
+        # Upsample layers that run fused (level -> bool); OFX_VAE_NO_UPCONV=1 turns every one to the unfused pair
+        self.fused_upsample = {lvl: not _no_upconv() for lvl in range(1, len(self.cfg["ch_mult"]))}
+
+    def _load(self, key: str, t: torch.Tensor) -> None:
+        if key == "decoder.conv_out.weight" and t.shape[0] % 4:
+            # rows of 4 floats for the RGB map (the byte exit reads 16-byte pixels): output channels padded with zero weights
+            t = torch.cat([t, t.new_zeros((4 - t.shape[0] % 4,) + tuple(t.shape[1:]))])
+        elif key == "decoder.conv_out.bias" and t.shape[0] % 4:
+            t = torch.cat([t, t.new_zeros((4 - t.shape[0] % 4,))])
+        super()._load(key, t)
+        if key.endswith(".upsample.conv.weight"):
+            self.w[key + ".folded"] = ops.upconv2x_weight(t).to(self.device)   # [4 parities, Cout, 4 taps, Cin]
+
+    def _upsample(self, lvl: int, x: torch.Tensor) -> torch.Tensor:
+        """Upsample.forward (:52-58): interpolate(scale_factor=2.0, mode="nearest") + 3x3 convolution."""
+        name = f"decoder.up.{lvl}.upsample.conv"
+        if self.fused_upsample[lvl]:
+            return ops.upconv2x(x, self.w[f"{name}.weight.folded"], self.w[f"{name}.bias"])
+        return self._conv(name, ops.upsample2x_nearest(x), 3)
+
+    def max_batch(self, H: int, W: int) -> int:
+        """Frames of HxW pixels one pass of the decoder can take: the convolution kernel addresses its operands with 32-bit byte
+        offsets, so the widest activation must stay under 2 GiB.  That is what the last Upsample writes: the full-resolution map
+        with the `ch * ch_mult[1]` channels of level 1 (256: 5 frames at 512x768, 1 at 1024x1024).  `decode` slices larger batches."""
+        mult = tuple(self.cfg["ch_mult"])
+        widest = 0
+        for lvl in range(len(mult)):
+            c = self.cfg["ch"] * max(mult[lvl], mult[min(lvl + 1, len(mult) - 1)])
+            widest = max(widest, (H >> lvl) * (W >> lvl) * c * 4)
+        return max(1, ((1 << 31) - 4096) // widest)
+
+    @torch.no_grad()
+    def _decode_nhwc(self, z: torch.Tensor) -> torch.Tensor:
+        """z f32 [B,z,h,w] -> the RGB map f32 NHWC [B,8h,8w,4] (channel 3 = 0), one pass."""
+        n_lvl = len(self.cfg["ch_mult"])
+        h = self._conv("post_quant_conv", z.permute(0, 2, 3, 1).contiguous(), 1)          # autoencoder.py decode
+        h = self._conv("decoder.conv_in", h, 3)
+        h = self._resblock("decoder.mid.block_1", h)
+        h = self._attn("decoder.mid.attn_1", h)
+        h = self._resblock("decoder.mid.block_2", h)
+        for lvl in reversed(range(n_lvl)):
+            for j in range(self.cfg["num_res_blocks"] + 1):
+                h = self._resblock(f"decoder.up.{lvl}.block.{j}", h)
+            if lvl != 0:
+                h = self._upsample(lvl, h)
+        return self._conv("decoder.conv_out", self._norm("decoder.norm_out", h, True), 3)
+
+    def _check(self, z: torch.Tensor) -> None:
+        if not torch.is_tensor(z) or not z.is_cuda or z.dtype != torch.float32 or z.dim() != 4 or z.shape[1] != self.cfg["z_channels"]:
+            raise RuntimeError(f"z must be a CUDA float32 tensor [B,{self.cfg['z_channels']},h,w]")
+        if self.cfg["embed_dim"] % 4 or self.cfg["z_channels"] % 4:
+            raise RuntimeError("embed_dim and z_channels must be multiples of 4")
+
+    def _slices(self, z: torch.Tensor, max_batch: Optional[int]):
+        up = 1 << (len(self.cfg["ch_mult"]) - 1)
+        mb = self.max_batch(z.shape[2] * up, z.shape[3] * up)
+        mb = mb if max_batch is None else max(1, min(mb, int(max_batch)))
+        return [z[b0:b0 + mb] for b0 in range(0, z.shape[0], mb)]
+
+    @torch.no_grad()
+    def decode(self, z: torch.Tensor, max_batch: Optional[int] = None) -> torch.Tensor:
+        """z f32 [B,4,h,w] -> image f32 [B,3,8h,8w] = decoder(post_quant_conv(z)) (AutoencoderKL.decode).  Batches beyond
+        `max_batch` (default: what `max_batch()` allows at this size) are decoded in slices (latents are independent)."""
+        self._check(z)
+        nout = self.cfg.get("out_ch", 3)
+        return torch.cat([self._decode_nhwc(p)[..., :nout].permute(0, 3, 1, 2).contiguous() for p in self._slices(z, max_batch)])
+
+    @torch.no_grad()
+    def decode_first_stage(self, z: torch.Tensor, max_batch: Optional[int] = None) -> torch.Tensor:
+        """`decode_first_stage(z)` (ddpm.py:820-828): z = 1. / scale_factor * z, then decode."""
+        self._check(z)
+        return self.decode(1.0 / self.scale_factor * z, max_batch)
+
+    @torch.no_grad()
+    def decode_latent(self, z: torch.Tensor, max_batch: Optional[int] = None) -> torch.Tensor:
+        """`decode_latent(model, latent)` (ofgen_keyframe_inpaint.py:234-235) for a batch: u8 BGR [B,8h,8w,3] on the device =
+        (decode_first_stage(z).clip(-1, 1) * 127.5 + 127.5).astype(uint8), channels reversed."""
+        self._check(z)
+        return torch.cat([ops.decode_to_u8(self._decode_nhwc(p)) for p in self._slices(1.0 / self.scale_factor * z, max_batch)])
