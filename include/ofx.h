@@ -200,7 +200,7 @@ int ofx_abs_diff_sum_u8(const uint8_t* a, long a_bstride, const uint8_t* b, long
                         unsigned long long* sums, int B, long n, void* stream);
 
 /* ---------------------------------------------------------------- implicit-GEMM conv */
-#define OFX_ACT_NONE    0
+#define OFX_ACT_NONE    0   /* max(v, -FLT_MAX): finite sums pass unchanged, a NaN or -inf sum comes out as -FLT_MAX (the plain epilogue does not propagate NaN) */
 #define OFX_ACT_RELU    1
 #define OFX_ACT_SIGMOID 2
 #define OFX_ACT_TANH    3

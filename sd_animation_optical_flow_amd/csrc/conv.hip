@@ -1011,6 +1011,8 @@ __global__ __launch_bounds__(256 * KS, (BK == 16 && KS == 1) ? ((PREC == 3 || PR
         scv[j] = p.scale ? p.scale[nn] : 1.0f;
         shv[j] = p.shift ? p.shift[nn] : 0.0f;
     }
+    // OFX_ACT_NONE is fmaxf(v, -FLT_MAX), not a true identity: a NaN sum comes out as -FLT_MAX (and -inf likewise).  The plain
+    // epilogue does not propagate NaN; a caller that needs it (ofx_attention_f32's fully masked rows) restores it afterwards.
     const float act_lo = p.act == OFX_ACT_RELU ? 0.0f : -3.402823466e38f;
     const float res_lo = has_res ? 0.0f : -3.402823466e38f;
     constexpr bool TRANSC = EPI == kEpiPlainT;            // plain epilogue with sigmoid / tanh

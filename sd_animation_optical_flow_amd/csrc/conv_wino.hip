@@ -468,7 +468,7 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
     wino3x3_slabs<NORM>(p, pt, smem, tid, wave, acc);
 
     // ---- output transform and plain epilogue, one 32-channel half at a time through LDS
-    const float act_lo = p.act == OFX_ACT_RELU ? 0.0f : -3.402823466e38f;
+    const float act_lo = p.act == OFX_ACT_RELU ? 0.0f : -3.402823466e38f;   // OFX_ACT_NONE: a NaN sum becomes -FLT_MAX (see conv.hip)
     float* const X = smem;
     float* const Sx = smem + kXF;
     const int on = tid & 31, otx = tid >> 5;
@@ -582,7 +582,7 @@ __global__ __launch_bounds__(256, 2) void wino15_conv_kernel(const WinoK p) {
     if (n >= p.Cout) return;   // no barrier follows
     const float sc = (p.scale ? p.scale[n] : 1.0f) * p.alpha;
     const float sh = p.shift ? p.shift[n] : 0.0f;
-    const float act_lo = p.act == OFX_ACT_RELU ? 0.0f : -3.402823466e38f;
+    const float act_lo = p.act == OFX_ACT_RELU ? 0.0f : -3.402823466e38f;   // OFX_ACT_NONE: a NaN sum becomes -FLT_MAX (see conv.hip)
     const int hd = p.Cout >> 1;
     const bool r_half = EPI == OFX_EPI_GRU_ZR && pt.nb * 128 >= hd;   // block-uniform (fits: hd % 128 == 0)
     // Four elements (16 outputs) per batch: every global read of the batch is issued before its arithmetic and stores (h is read

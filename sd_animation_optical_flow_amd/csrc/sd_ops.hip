@@ -25,7 +25,6 @@ static inline int gn_slices(int B) { return B >= 4 ? 64 : 256; }
 // per (image, slice) per-channel sums in f64 (same scheme as the instance-norm statistics of net_misc.hip)
 __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict__ x, double* __restrict__ part, long HW, int C, int kSlices) {
     const int cg = C / 4;
-    const int rows = 256 / cg > 0 ? 256 / cg : 1;
     const int b = blockIdx.y, sl = blockIdx.x;
     const long per = (HW + kSlices - 1) / kSlices;
     const long beg = sl * per, end = beg + per < HW ? beg + per : HW;
@@ -64,7 +63,6 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
         }
         __syncthreads();
     }
-    (void)rows;
 }
 
 // one workgroup per image: group statistics -> per-channel scale / shift (y = x * scale + shift).  The 256 threads are
@@ -206,6 +204,18 @@ __global__ __launch_bounds__(256) void transpose_pad_kernel(const float* __restr
     }
 }
 
+// A row whose every key is masked leaves the softmax as NaN (0 * inf), and so must the output row (include/ofx.h).  The GEMM
+// epilogue's identity activation is fmaxf(v, -FLT_MAX), which returns -FLT_MAX for a NaN sum: the rows whose probabilities are NaN
+// are rewritten with that NaN.  One wave per row, four rows per workgroup; p[r][0] stands for the row (the softmax writes the
+// same 0 * inf to every column of such a row and to no other).
+__global__ __launch_bounds__(256) void nan_rows_kernel(const float* __restrict__ p, long ldp, float* __restrict__ out, long rows, int D) {
+    const long r = (long)blockIdx.x * 4 + threadIdx.x / 64;
+    if (r >= rows) return;
+    const float p0 = p[r * ldp];
+    if (p0 == p0) return;
+    for (int d = threadIdx.x % 64; d < D; d += 64) out[r * D + d] = p0;
+}
+
 inline long round_up(long v, long m) { return (v + m - 1) / m * m; }
 
 }  // namespace
@@ -298,7 +308,12 @@ int ofx_attention_f32(const float* q, const float* k, const float* v, const floa
     e.B = 1; e.Hin = 1; e.Win = Nq; e.Hout = 1; e.Wout = Nq; e.Cout = D;
     e.KH = 1; e.KW = 1; e.stride = 1;
     e.act = OFX_ACT_NONE; e.epi = OFX_EPI_PLAIN;
-    return ofx_conv2d(&e, stream);
+    st = ofx_conv2d(&e, stream);
+    if (st) return st;
+    OfxProfScope prof("attn_nan_rows", s);
+    const long rows = (long)BH * Nq;
+    hipLaunchKernelGGL(nan_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, sc, lds, out, rows, D);
+    return ofx_launch_status();
 }
 
 }  // extern "C"

@@ -685,20 +685,43 @@ def sd_handoff(image_bgr: torch.Tensor, reference_bgr: torch.Tensor, image_mask:
 
 
 def groupnorm(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], groups: int = 32, eps: float = 1e-6,
-              silu: bool = False) -> torch.Tensor:
+              silu: bool = False, out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
     """GroupNorm(groups, C, eps, affine) of an NHWC tensor [B,H,W,C] (+ x * sigmoid(x) when silu): `Normalize` /
-    `nonlinearity` of ldm/modules/diffusionmodules/model.py:35-41."""
+    `nonlinearity` of ldm/modules/diffusionmodules/model.py:35-41.  `out`: a float32 tensor of at least x.numel() elements to
+    write (x itself: in place); `scratch`: a uint8 tensor whose whole length is offered as the scratch
+    (ofx_groupnorm_scratch_bytes(B, C) bytes are needed).  Returns a [B,H,W,C] tensor either way: a new one, or a view of
+    the first x.numel() elements of `out`."""
     t = _chk(x, "x", torch.float32)
     B, H, W, Cn = t.shape
     L = _lib.lib()
-    need = L.ofx_groupnorm_scratch_bytes(B, Cn)
-    scratch = torch.empty((need,), dtype=torch.uint8, device=t.device)
-    out = torch.empty_like(t)
+    if scratch is None:
+        scratch = torch.empty((L.ofx_groupnorm_scratch_bytes(B, Cn),), dtype=torch.uint8, device=t.device)
+    scratch = _chk(scratch, "scratch", torch.uint8)
+    if out is None:
+        out = torch.empty_like(t)
+    out = _chk(out, "out", torch.float32)
+    if out.numel() < t.numel():
+        raise RuntimeError(f"out must hold {t.numel()} floats, got {out.numel()}")
     g = None if gamma is None else _chk(gamma, "gamma", torch.float32)
     b = None if beta is None else _chk(beta, "beta", torch.float32)
-    check(L.ofx_groupnorm(_ptr(t), _ptr(g), _ptr(b), _ptr(out), _ptr(scratch), need, B, H * W, Cn, int(groups), float(eps),
+    check(L.ofx_groupnorm(_ptr(t), _ptr(g), _ptr(b), _ptr(out), _ptr(scratch), scratch.numel(), B, H * W, Cn, int(groups), float(eps),
                           1 if silu else 0, _stream()), "ofx_groupnorm")
-    return out
+    return out.view(-1)[:t.numel()].view_as(t)
+
+
+def softmax_rows(x: torch.Tensor, rows: int, ld: int, n: int, scale: float = 1.0, bias: Optional[torch.Tensor] = None,
+                 ld_bias: int = 0, bias_rows: int = 1) -> torch.Tensor:
+    """In place on the float32 buffer `x` (at least rows * ld floats): x[r][0..n) = softmax(x[r][0..n) * scale +
+    bias[r % bias_rows][0..n)), columns n..ld-1 set to 0 (ofx_softmax_rows).  bias: rows of ld_bias floats."""
+    x = _chk(x, "x", torch.float32)
+    if x.numel() < rows * ld:
+        raise RuntimeError(f"x must hold rows * ld = {rows * ld} floats, got {x.numel()}")
+    b = None if bias is None else _chk(bias, "bias", torch.float32)
+    if b is not None and b.numel() < (bias_rows - 1) * ld_bias + n:
+        raise RuntimeError("bias must hold bias_rows rows of ld_bias floats")
+    check(_lib.lib().ofx_softmax_rows(_ptr(x), int(rows), int(ld), int(n), float(scale), _ptr(b), int(ld_bias), int(bias_rows), _stream()),
+          "ofx_softmax_rows")
+    return x
 
 
 def upconv2x_weight(w_oihw: torch.Tensor) -> torch.Tensor:
