@@ -21,6 +21,8 @@
  *   ofx_groupnorm, ofx_softmax_rows, ofx_attention_f32
  *   ofx_upconv2x, ofx_upsample2x_nearest_f32, ofx_decode_to_u8
  *                               ldm/modules/diffusionmodules/model.py:35-41,152-203 ; ldm/modules/attention.py:314,426
+ *   ofx_layernorm, ofx_geglu, ofx_attention_bnhd_f32
+ *                               ldm/modules/attention.py:54-56,326-436,456-469,515-537 (SpatialTransformer)
  *                               ofgen_keyframe_inpaint.py:113-133,237-248,306-322,676-688,968-973,995-1027
  *
  * Layout conventions: images and flow are HWC ("channels-last"); network activations are
@@ -161,6 +163,29 @@ int ofx_softmax_rows(float* x, long rows, long ld, int n, float scale, const flo
 size_t ofx_attention_workspace_bytes(int BH, int Nq, int Nk, int D);
 int ofx_attention_f32(const float* q, const float* k, const float* v, const float* bias, long bias_bstride, float* out,
                       int BH, int Nq, int Nk, int D, float scale, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------- SpatialTransformer (ldm/modules/attention.py:472-537) */
+/* nn.LayerNorm(C) over the last axis of `rows` rows (BasicTransformerBlock.norm1 / norm2 / norm3, attention.py:456-458, applied at
+ * :465-468): out[r][c] = (x[r][c] - mean_r) / sqrt(var_r + eps) * gamma[c] + beta[c], var biased, eps a parameter (the reference's
+ * nn.LayerNorm default is 1e-5).  Rows are ldx / ldo floats apart (ld >= C, ld % 4 == 0: a last-axis slice of a wider tensor is a
+ * valid operand); gamma / beta: [C] or NULL.  C % 4 == 0, C <= 4096 (OFX_EINVAL beyond), pointers 16-byte aligned (OFX_EALIGN).
+ * out == x is allowed.  One wave per row with the row in registers: the mean first, then the sum of squares of the centred values,
+ * both by wave reductions; no LDS, no scratch. */
+int ofx_layernorm(const float* x, int ldx, const float* gamma, const float* beta, float* out, int ldo, int rows, int C, float eps,
+                  void* stream);
+/* GEGLU.forward after its Linear (attention.py:54-56: `x, gate = self.proj(x).chunk(2, dim=-1); return x * F.gelu(gate)`):
+ * out[r][c] = a[r][c] * gelu(a[r][inner + c]) for c < inner, gelu(g) = g/2 * (1 + erf(g / sqrt 2)), the exact form F.gelu defaults
+ * to.  Rows of a are lda >= 2 * inner floats apart, rows of out ldo >= inner; inner, lda, ldo % 4 == 0, 16-byte aligned. */
+int ofx_geglu(const float* a, int lda, float* out, int ldo, int rows, int inner, void* stream);
+/* ofx_attention_f32 on token rows (MemoryEfficientCrossAttention.forward, attention.py:326-436, without its permute + contiguous
+ * copies at :338-345 and :430-435): element (b, n, h, d) of q / k / v / out lives at p[(b * N + n) * ld + h * D + d], N = Nq for q
+ * and out, Nk for k and v -- tokens are rows, the heads sit side by side in a row.  The four strides are independent, each
+ * >= H * D and % 4 == 0, so one [B, N, 3 * H * D] buffer of a fused q|k|v projection is three valid operands with ld = 3 * H * D.
+ * bias: NULL, [Nq,Nk] shared (bias_bstride = 0) or [B*H,Nq,Nk] (bias_bstride = Nq*Nk), batch-head z = b * H + h.  Only the head
+ * sizes of the fused kernel, D in {40, 64, 80, 128, 160}; any other D is OFX_EINVAL (permute and call ofx_attention_f32).  The
+ * same kernel with other addresses: bit-identical to ofx_attention_f32 on the permuted contiguous copies.  No workspace. */
+int ofx_attention_bnhd_f32(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* bias,
+                           long bias_bstride, float* out, int ldo, int B, int H, int Nq, int Nk, int D, float scale, void* stream);
 
 /* ---------------------------------------------------------------- first-stage decoder (decode_first_stage / decode_latent) */
 /* `Upsample` of the VAE decoder (ldm/modules/diffusionmodules/model.py:43-58): out = conv3x3(pad 1)(interpolate(x, 2x, nearest)) + bias

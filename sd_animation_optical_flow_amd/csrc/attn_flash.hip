@@ -37,11 +37,17 @@ struct FlashArgs {
     float scale_log2e;
     int qtiles;
     int xcd_grouped;
+    // STRIDED instantiation only (ofx_attention_bnhd_f32): element (b, n, h, d) at p[(b * N + n) * ld + h * D + d], bh = b * H + h
+    int H;
+    int ldq, ldk, ldv, ldo;
 };
 
 constexpr float kLog2e = 1.4426950408889634f;
 
-template <int D, int BK>
+// STRIDED = false: [BH, N, D] tensors, a batch-head is one contiguous run.  STRIDED = true: tokens are rows of ld floats with the
+// heads side by side in a row (what a fused q|k|v projection GEMM leaves); only the global addresses differ, the arithmetic and
+// its order are the same, so the two instantiations agree bit for bit.
+template <int D, int BK, bool STRIDED>
 __global__ __launch_bounds__(256) void flash_attn_kernel(const FlashArgs a) {
     static_assert(D % 8 == 0 && D <= 160, "head size");
     constexpr int DQ = D / 8;                       // groups of 8 along d: each wave half takes 4 of them
@@ -71,9 +77,13 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const FlashArgs a) {
     const bool qok = qrow < a.Nq;
 
     // the wave's queries, scaled: lane (c, h) keeps q[qrow][8m + 4h + 0..3]
+    // STRIDED: image and head of this batch-head, and the head's column offset in a token row
+    const int img = STRIDED ? bh / a.H : 0;
+    const int hoff = STRIDED ? (bh % a.H) * D : 0;
     float4 qreg[DQ];
     {
-        const float* qp = a.q + ((long)bh * a.Nq + (qok ? qrow : 0)) * D + 4 * h;
+        const float* qp = STRIDED ? a.q + ((long)img * a.Nq + (qok ? qrow : 0)) * a.ldq + hoff + 4 * h
+                                  : a.q + ((long)bh * a.Nq + (qok ? qrow : 0)) * D + 4 * h;
 #pragma unroll
         for (int m = 0; m < DQ; ++m) {
             float4 t = qok ? *reinterpret_cast<const float4*>(qp + 8 * m) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -81,8 +91,8 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const FlashArgs a) {
         }
     }
 
-    const float* kg = a.k + (long)bh * a.Nk * D;
-    const float* vg = a.v + (long)bh * a.Nk * D;
+    const float* kg = STRIDED ? a.k + (long)img * a.Nk * a.ldk + hoff : a.k + (long)bh * a.Nk * D;
+    const float* vg = STRIDED ? a.v + (long)img * a.Nk * a.ldv + hoff : a.v + (long)bh * a.Nk * D;
     const float* bg = a.bias ? a.bias + (long)bh * a.bias_bs + (long)(qok ? qrow : 0) * a.Nk : nullptr;
 
     float4 sk[PER], sv[PER];
@@ -92,9 +102,16 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const FlashArgs a) {
             const int f = tid + 256 * p;
             const int key = f / (D / 4);
             const bool ok = (PER * 256 == NF4 || f < NF4) && k0 + key < a.Nk;
-            // a tile is one contiguous run of BK * D floats
-            sk[p] = ok ? *reinterpret_cast<const float4*>(kg + (long)k0 * D + 4 * f) : make_float4(0.f, 0.f, 0.f, 0.f);
-            sv[p] = ok ? *reinterpret_cast<const float4*>(vg + (long)k0 * D + 4 * f) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (STRIDED) {
+                // a key is D contiguous floats (D / 4 consecutive lanes read one 4 * D-byte run), keys are ld floats apart
+                const int c4 = f % (D / 4);
+                sk[p] = ok ? *reinterpret_cast<const float4*>(kg + (long)(k0 + key) * a.ldk + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+                sv[p] = ok ? *reinterpret_cast<const float4*>(vg + (long)(k0 + key) * a.ldv + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                // a tile is one contiguous run of BK * D floats
+                sk[p] = ok ? *reinterpret_cast<const float4*>(kg + (long)k0 * D + 4 * f) : make_float4(0.f, 0.f, 0.f, 0.f);
+                sv[p] = ok ? *reinterpret_cast<const float4*>(vg + (long)k0 * D + 4 * f) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
         }
     };
     auto store_tile = [&](float* buf) __attribute__((always_inline)) {
@@ -195,7 +212,7 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const FlashArgs a) {
     const float l_tot = l_run + __shfl_xor(l_run, 32);
     const float inv = 1.0f / l_tot;
     if (qok) {
-        float* op = a.out + ((long)bh * a.Nq + qrow) * D;
+        float* op = STRIDED ? a.out + ((long)img * a.Nq + qrow) * a.ldo + hoff : a.out + ((long)bh * a.Nq + qrow) * D;
 #pragma unroll
         for (int tt = 0; tt < DT; ++tt)
 #pragma unroll
@@ -208,15 +225,15 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const FlashArgs a) {
     }
 }
 
-template <int D, int BK>
+template <int D, int BK, bool STRIDED>
 int launch_flash(const FlashArgs& a, hipStream_t s) {
     constexpr int LDK = D + 4, LDV = ((D + 7) / 16) * 16 + 8;
     constexpr size_t lds = 2 * (size_t)(BK * LDK + BK * LDV + 32) * sizeof(float);
     if (lds > 65536) {                               // > 64 KB of dynamic LDS needs the opt-in (per device: set on every launch, it is cheap)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_attn_kernel<D, BK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_attn_kernel<D, BK, STRIDED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL((flash_attn_kernel<D, BK>), dim3((unsigned)(a.BH * a.qtiles)), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((flash_attn_kernel<D, BK, STRIDED>), dim3((unsigned)(a.BH * a.qtiles)), dim3(256), lds, s, a);
     return ofx_launch_status();
 }
 
@@ -224,24 +241,48 @@ int launch_flash(const FlashArgs& a, hipStream_t s) {
 
 bool ofx_attention_flash_ok(int D) { return D == 40 || D == 64 || D == 80 || D == 128 || D == 160; }
 
+static int flash_dispatch(FlashArgs& a, int D, float scale, bool strided, hipStream_t s) {
+    a.scale_log2e = scale * kLog2e;
+    a.qtiles = ofx_cdiv(a.Nq, 128);
+    a.xcd_grouped = (a.BH % 8 == 0) ? 1 : 0;
+    if ((long)a.BH * a.qtiles > 0x7fffffffL) return OFX_EINVAL;
+    OfxProfScope prof(strided ? "attn_flash_bnhd" : "attn_flash", s);
+    prof.flops(4.0 * a.BH * (double)a.Nq * a.Nk * D);
+    if (strided) {
+        switch (D) {
+            case 40: return launch_flash<40, 64, true>(a, s);
+            case 64: return launch_flash<64, 32, true>(a, s);
+            case 80: return launch_flash<80, 32, true>(a, s);
+            case 128: return launch_flash<128, 32, true>(a, s);
+            case 160: return launch_flash<160, 32, true>(a, s);
+        }
+        return OFX_EINVAL;
+    }
+    switch (D) {
+        case 40: return launch_flash<40, 64, false>(a, s);
+        case 64: return launch_flash<64, 32, false>(a, s);
+        case 80: return launch_flash<80, 32, false>(a, s);
+        case 128: return launch_flash<128, 32, false>(a, s);
+        case 160: return launch_flash<160, 32, false>(a, s);
+    }
+    return OFX_EINVAL;
+}
+
 int ofx_attention_flash_launch(const float* q, const float* k, const float* v, const float* bias, long bias_bstride, float* out, int BH, int Nq,
                                int Nk, int D, float scale, hipStream_t s) {
     FlashArgs a{};
     a.q = q; a.k = k; a.v = v; a.bias = bias; a.out = out;
     a.bias_bs = bias_bstride;
     a.BH = BH; a.Nq = Nq; a.Nk = Nk;
-    a.scale_log2e = scale * kLog2e;
-    a.qtiles = ofx_cdiv(Nq, 128);
-    a.xcd_grouped = (BH % 8 == 0) ? 1 : 0;
-    if ((long)BH * a.qtiles > 0x7fffffffL) return OFX_EINVAL;
-    OfxProfScope prof("attn_flash", s);
-    prof.flops(4.0 * BH * (double)Nq * Nk * D);
-    switch (D) {
-        case 40: return launch_flash<40, 64>(a, s);
-        case 64: return launch_flash<64, 32>(a, s);
-        case 80: return launch_flash<80, 32>(a, s);
-        case 128: return launch_flash<128, 32>(a, s);
-        case 160: return launch_flash<160, 32>(a, s);
-    }
-    return OFX_EINVAL;
+    return flash_dispatch(a, D, scale, false, s);
+}
+
+int ofx_attention_flash_bnhd_launch(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* bias,
+                                    long bias_bstride, float* out, int ldo, int B, int H, int Nq, int Nk, int D, float scale, hipStream_t s) {
+    FlashArgs a{};
+    a.q = q; a.k = k; a.v = v; a.bias = bias; a.out = out;
+    a.bias_bs = bias_bstride;
+    a.BH = B * H; a.Nq = Nq; a.Nk = Nk;
+    a.H = H; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    return flash_dispatch(a, D, scale, true, s);
 }

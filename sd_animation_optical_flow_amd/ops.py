@@ -814,6 +814,108 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bias: Optional[
 
 
 # --------------------------------------------------------------------------------------
+# SpatialTransformer pieces (ldm/modules/attention.py:438-537): LayerNorm, GEGLU, attention on token rows
+# --------------------------------------------------------------------------------------
+def _rows_view(t: torch.Tensor, name: str) -> Tuple[int, int, int]:
+    """(rows, C, ld) of a float32 CUDA tensor [..., C] whose leading dimensions flatten to rows `ld` floats apart: a contiguous
+    tensor, or a last-axis slice of a wider contiguous one."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() < 1 or t.numel() == 0:
+        raise RuntimeError(f"{name} must be a non-empty CUDA float32 tensor")
+    Cn = int(t.shape[-1])
+    ld, span = Cn, None
+    for i in range(t.dim() - 2, -1, -1):
+        if t.shape[i] == 1:
+            continue
+        if span is None:
+            ld = int(t.stride(i))
+        elif t.stride(i) != span:
+            raise RuntimeError(f"{name} must be contiguous, or a last-axis slice of a contiguous tensor")
+        span = int(t.stride(i)) * int(t.shape[i])
+    if (Cn > 1 and t.stride(-1) != 1) or ld < Cn:
+        raise RuntimeError(f"{name} must be contiguous, or a last-axis slice of a contiguous tensor")
+    return t.numel() // Cn, Cn, ld
+
+
+def layernorm(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float = 1e-5,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nn.LayerNorm(C) over the last axis (biased variance; `ofx_layernorm`, one wave per row).  x: [..., C] float32, contiguous or a
+    last-axis slice of a wider contiguous tensor (rows `stride(-2)` floats apart); C % 4 == 0, C <= 4096.  `out`: the same shape
+    (x itself: in place), also possibly a slice; a new contiguous tensor otherwise."""
+    rows, Cn, ldx = _rows_view(x, "x")
+    if out is None:
+        out = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+    _, _, ldo = _rows_view(out, "out")
+    if tuple(out.shape) != tuple(x.shape):
+        raise RuntimeError(f"out must be {tuple(x.shape)}, got {tuple(out.shape)}")
+    g = None if gamma is None else _chk(gamma, "gamma", torch.float32)
+    b = None if beta is None else _chk(beta, "beta", torch.float32)
+    for nm, t in (("gamma", g), ("beta", b)):
+        if t is not None and tuple(t.shape) != (Cn,):
+            raise RuntimeError(f"{nm} must be [{Cn}]")
+    check(_lib.lib().ofx_layernorm(_ptr(x), ldx, _ptr(g), _ptr(b), _ptr(out), ldo, rows, Cn, float(eps), _stream()), "ofx_layernorm")
+    return out
+
+
+def geglu(a: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """GEGLU.forward after its Linear (attention.py:54-56): a [..., 2 * inner] -> a[..., :inner] * gelu(a[..., inner:]), gelu in the
+    exact erf form (`ofx_geglu`).  a and `out` [..., inner]: contiguous or last-axis slices of wider tensors; inner % 4 == 0."""
+    rows, two, lda = _rows_view(a, "a")
+    if two % 2:
+        raise RuntimeError("geglu: the last axis holds the values and the gates, an even count")
+    inner = two // 2
+    shape = tuple(a.shape[:-1]) + (inner,)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=a.device)
+    _, _, ldo = _rows_view(out, "out")
+    if tuple(out.shape) != shape:
+        raise RuntimeError(f"out must be {shape}, got {tuple(out.shape)}")
+    check(_lib.lib().ofx_geglu(_ptr(a), lda, _ptr(out), ldo, rows, inner, _stream()), "ofx_geglu")
+    return out
+
+
+def _bnhd(t: torch.Tensor, name: str) -> int:
+    """The row stride of a [B,N,H*D] operand of `attention_bnhd`: dense along the last axis, rows stride(1) floats apart, images
+    N rows apart."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 3:
+        raise RuntimeError(f"{name} must be a CUDA float32 tensor [B,N,H*D]")
+    B, N, W = t.shape
+    ld = int(t.stride(1)) if N > 1 else (int(t.stride(0)) if B > 1 else W)
+    if (W > 1 and t.stride(2) != 1) or ld < W or (B > 1 and t.stride(0) != N * ld):
+        raise RuntimeError(f"{name} must be contiguous, or a last-axis slice of a contiguous [B,N,wider] tensor")
+    return ld
+
+
+def attention_bnhd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, bias: Optional[torch.Tensor] = None,
+                   scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`attention` on token rows: q [B,Nq,H*D], k / v [B,Nk,H*D] with the heads side by side in a row, as a projection GEMM leaves
+    them -- contiguous tensors, or last-axis slices of wider ones (the three thirds of one fused q|k|v buffer); the row stride is
+    read from stride(1).  bias [Nq,Nk] or [B*H,Nq,Nk]; scale defaults to D^-0.5.  Returns `out` [B,Nq,H*D] (new and contiguous when
+    not given), bit for bit what `attention` gives on the permuted contiguous copies.  Head sizes the fused kernel takes only
+    (`ofx_attention_bnhd_f32`: D in 40 / 64 / 80 / 128 / 160, OFX_EINVAL otherwise)."""
+    ldq, ldk, ldv = _bnhd(q, "q"), _bnhd(k, "k"), _bnhd(v, "v")
+    B, Nq, W = q.shape
+    Nk = k.shape[1]
+    H = int(heads)
+    if H <= 0 or W % H or tuple(k.shape) != (B, Nk, W) or tuple(v.shape) != (B, Nk, W):
+        raise RuntimeError("attention_bnhd: q [B,Nq,H*D], k / v [B,Nk,H*D] expected")
+    D = W // H
+    per_bh = bias is not None and bias.dim() == 3
+    if bias is not None:
+        bias = _chk(bias, "bias", torch.float32)
+        if tuple(bias.shape) not in ((Nq, Nk), (B * H, Nq, Nk)):
+            raise RuntimeError("attention_bnhd: bias must be [Nq,Nk] or [B*H,Nq,Nk]")
+    if out is None:
+        out = torch.empty((B, Nq, W), dtype=torch.float32, device=q.device)
+    ldo = _bnhd(out, "out")
+    if tuple(out.shape) != (B, Nq, W):
+        raise RuntimeError(f"out must be {(B, Nq, W)}, got {tuple(out.shape)}")
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    check(_lib.lib().ofx_attention_bnhd_f32(_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(bias), Nq * Nk if per_bh else 0, _ptr(out), ldo,
+                                            B, H, Nq, Nk, D, scale, _stream()), "ofx_attention_bnhd_f32")
+    return out
+
+
+# --------------------------------------------------------------------------------------
 # key-frame detector (SURVEY f4)
 # --------------------------------------------------------------------------------------
 def detect_edges(frames_bgr: torch.Tensor, ksize: int) -> torch.Tensor:

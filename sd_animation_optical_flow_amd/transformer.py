@@ -1,0 +1,328 @@
+"""`SpatialTransformer` of the reference's UNet on the device, with the K/V history of reference frames.
+
+ldm/modules/attention.py is the one UNet file the reference rewrote: `SpatialTransformer.forward` (:515-537) ->
+`BasicTransformerBlock._forward` (:464-469) -> `MemoryEfficientCrossAttention.forward` (:326-436).  Its self-attention hands back
+its own K/V (`kv_hist`, :353) and can attend to the K/V of reference frames instead (`ref_kv_hists`, :358-369): the mechanism behind
+`generate_ai_frame_with_ref_self_attn` and `VideoData.put_kv / get_kv`.
+
+Everything runs through the C ABI of libofx.so on NHWC fp32: GroupNorm(32, eps 1e-6) (`ofx_groupnorm`), `proj_in` / `proj_out` and
+every Linear as 1x1 `ofx_conv2d` GEMMs on the fp32 matrix cores (biases and the residual sums in the epilogue), LayerNorm
+(`ofx_layernorm`), GEGLU (`ofx_geglu`) and the fused attention kernel on token rows (`ofx_attention_bnhd_f32`), which reads q / k / v
+where the projection GEMM left them: the NHWC output of `proj_in` already is the token matrix [B, h*w, inner], `to_q | to_k | to_v`
+of the self-attention are one GEMM into one [B, N, 3*inner] buffer whose thirds are the attention's operands, and no activation is
+permuted or copied between layouts anywhere but at the NCHW edges of `forward`.  The K/V history stays on the device, as
+[B, N, inner] tensors (`to_reference_layout` gives the reference's [(b h), n, d]).
+
+OFX_ST_TORCH_GLUE=1 in the environment (read once per process; the A/B baseline and a diagnostic): LayerNorm and GEGLU through
+torch.nn.functional, attention through permute + `ops.attention`, i.e. the glue this module replaces.  Head sizes the fused kernel
+does not take (`FUSED_HEAD_SIZES`) go the permute + `ops.attention` way on their own.
+
+State-dict keys are the reference's (`use_linear=False`, the conv `proj_in` / `proj_out` that guided_ldm_*_v15.yaml builds); a
+full-checkpoint prefix such as `model.diffusion_model.input_blocks.1.1.` goes through `prefix`.  No checkpoint ships with the
+reference tree: parity is pinned with seeded weights loaded into the reference's own module
+(tests/golden/make_golden_transformer.py).
+"""
+from __future__ import annotations
+
+import functools
+import math
+import os
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+import torch.nn.functional as F
+
+from . import ops
+
+FUSED_HEAD_SIZES = (40, 64, 80, 128, 160)      # ofx_attention_flash_ok (csrc/attn_flash.hip)
+
+
+def spatial_transformer_tensors(in_channels: int, n_heads: int, d_head: int, context_dim: Optional[int], depth: int = 1
+                                ) -> List[Tuple[str, Tuple[int, ...]]]:
+    """(key, shape) of every tensor of a `SpatialTransformer(in_channels, n_heads, d_head, depth, context_dim=context_dim)` with
+    use_linear=False, in the module's own order (26 per depth-1 module).  context_dim None: the cross-attention's K / V read the
+    tokens themselves (attention.py:208)."""
+    inner = n_heads * d_head
+    ctx = inner if context_dim is None else int(context_dim)
+    out: List[Tuple[str, Tuple[int, ...]]] = []
+
+    def wb(name, *shape):
+        out.append((f"{name}.weight", tuple(shape)))
+        out.append((f"{name}.bias", (shape[0],)))
+
+    def attn(name, kv_dim):
+        out.append((f"{name}.to_q.weight", (inner, inner)))
+        out.append((f"{name}.to_k.weight", (inner, kv_dim)))
+        out.append((f"{name}.to_v.weight", (inner, kv_dim)))
+        wb(f"{name}.to_out.0", inner, inner)
+
+    wb("norm", in_channels)
+    wb("proj_in", inner, in_channels, 1, 1)
+    for i in range(depth):
+        blk = f"transformer_blocks.{i}"
+        attn(f"{blk}.attn1", inner)
+        wb(f"{blk}.ff.net.0.proj", 8 * inner, inner)            # FeedForward(mult=4, glu=True): values and gates
+        wb(f"{blk}.ff.net.2", inner, 4 * inner)
+        attn(f"{blk}.attn2", ctx)
+        for n in ("norm1", "norm2", "norm3"):
+            wb(f"{blk}.{n}", inner)
+    wb("proj_out", in_channels, inner, 1, 1)
+    return out
+
+
+def random_spatial_transformer_state_dict(seed: int, in_channels: int, n_heads: int, d_head: int, context_dim: Optional[int],
+                                          depth: int = 1) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for the absent checkpoint: fan-in-scaled normal weights, norm scales around 1, small biases.  `proj_out` is
+    NOT zeroed (the reference zero-initialises it before training, :506; zeroed, the module would be the identity)."""
+    g = torch.Generator().manual_seed(int(seed) + 15485863)
+    sd = {}
+    for key, shape in spatial_transformer_tensors(in_channels, n_heads, d_head, context_dim, depth):
+        if len(shape) >= 2:
+            sd[key] = torch.randn(shape, generator=g) * (1.0 / math.sqrt(shape[1]))
+        elif key.split(".")[-2].startswith("norm") and key.endswith(".weight"):
+            sd[key] = 1.0 + 0.1 * torch.randn(shape, generator=g)
+        else:
+            sd[key] = 0.05 * torch.randn(shape, generator=g)
+    return sd
+
+
+@functools.lru_cache(maxsize=None)
+def _torch_glue() -> bool:
+    """OFX_ST_TORCH_GLUE=1 (A/B baseline and diagnostic, read once per process): LayerNorm / GEGLU through torch.nn.functional and
+    attention through permute + `ops.attention`."""
+    return os.environ.get("OFX_ST_TORCH_GLUE", "") not in ("", "0")
+
+
+def to_reference_layout(t: torch.Tensor, heads: int) -> torch.Tensor:
+    """[B, N, heads*d] -> the reference's [(b h), n, d] (attention.py:338-345)."""
+    B, N, inner = t.shape
+    return t.reshape(B, N, heads, inner // heads).permute(0, 2, 1, 3).reshape(B * heads, N, inner // heads).contiguous()
+
+
+def from_reference_layout(t: torch.Tensor, heads: int) -> torch.Tensor:
+    """The reference's [(b h), n, d] -> [B, N, heads*d]."""
+    BH, N, d = t.shape
+    return t.reshape(BH // heads, heads, N, d).permute(0, 2, 1, 3).reshape(BH // heads, N, heads * d).contiguous()
+
+
+def plan_reference_kv(shapes: Sequence[Tuple[Tuple[int, ...], Tuple[int, ...]]], B: int, N: int, heads: int, d_head: int
+                      ) -> Tuple[str, int, List[bool]]:
+    """What attention.py:358-369 does with reference K/V of these (k shape, v shape) pairs for a batch of B images of N tokens,
+    decided from the shapes alone (no device): ("all", tokens, ...) -- every image attends to the references' `tokens` keys and not
+    to its own; ("positive", N, ...) -- references of batch B - 1 with exactly N tokens in total replace the K/V of images 1..B-1,
+    image 0 (the unconditional half) keeps its own (`k[nhead:] = k2`).  The third item says per entry whether it is in the
+    reference's [(b h), n, d] layout (last dimension d_head) rather than [b, n, heads*d_head].  Any other combination is a
+    ValueError (the reference fails there with a shape error)."""
+    inner = heads * d_head
+    if not shapes:
+        raise ValueError("reference_kv is empty")
+    batches, tokens, ref_layout = [], 0, []
+    for i, (ks, vs) in enumerate(shapes):
+        ks, vs = tuple(int(s) for s in ks), tuple(int(s) for s in vs)
+        if ks != vs or len(ks) != 3 or min(ks) <= 0:
+            raise ValueError(f"reference_kv[{i}]: k and v must be 3-D tensors of one shape, got {ks} and {vs}")
+        if ks[2] == inner:
+            ref_layout.append(False)
+            batches.append(ks[0])
+        elif ks[2] == d_head and ks[0] % heads == 0:
+            ref_layout.append(True)
+            batches.append(ks[0] // heads)
+        else:
+            raise ValueError(f"reference_kv[{i}]: last dimension {ks[2]} is neither heads * d_head = {inner} ([b, n, h*d]) nor "
+                             f"d_head = {d_head} ([(b h), n, d])")
+        tokens += ks[1]
+    if len(set(batches)) != 1:
+        raise ValueError(f"reference_kv entries have different batch sizes {batches}")
+    b = batches[0]
+    if b == B:
+        return "all", tokens, ref_layout
+    if b == B - 1 and tokens == N:
+        return "positive", tokens, ref_layout
+    raise ValueError(f"reference_kv of batch {b} with {tokens} tokens does not fit {B} images of {N} tokens: batch {B} (any token "
+                     f"count), or batch {B - 1} with exactly {N} tokens")
+
+
+class SpatialTransformer:
+    """`ldm.modules.attention.SpatialTransformer` (use_linear=False, inference) on a HIP device."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], n_heads: int, d_head: int, device="cuda", prefix: str = "",
+                 use_linear: bool = False):
+        if use_linear:
+            raise NotImplementedError("use_linear=True (Linear proj_in / proj_out) is not what guided_ldm_*_v15.yaml builds")
+        if not torch.cuda.is_available():
+            raise RuntimeError("SpatialTransformer needs a HIP device (no CPU fallback)")
+        self.device = torch.device(device)
+        self.heads, self.d_head, self.inner = int(n_heads), int(d_head), int(n_heads) * int(d_head)
+        sd = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
+        if "norm.weight" not in sd or "proj_in.weight" not in sd:
+            raise KeyError(f"SpatialTransformer checkpoint lacks {prefix}norm.weight / {prefix}proj_in.weight")
+        self.in_channels = int(sd["norm.weight"].shape[0])
+        self.depth = 1 + max([int(k.split(".")[1]) for k in sd if k.startswith("transformer_blocks.")], default=-1)
+        kkey = "transformer_blocks.0.attn2.to_k.weight"
+        if self.depth < 1 or kkey not in sd:
+            raise KeyError(f"SpatialTransformer checkpoint lacks {prefix}{kkey}")
+        self.context_dim = int(sd[kkey].shape[1]) if sd[kkey].dim() == 2 else -1
+        if self.in_channels % 32 or self.inner % 4 or self.context_dim % 4:
+            raise ValueError("in_channels must be a multiple of 32 (GroupNorm), n_heads * d_head and context_dim multiples of 4")
+        t32: Dict[str, torch.Tensor] = {}
+        for key, shape in spatial_transformer_tensors(self.in_channels, self.heads, self.d_head, self.context_dim, self.depth):
+            if key not in sd:
+                raise KeyError(f"SpatialTransformer checkpoint lacks {prefix}{key}")
+            t = sd[key].detach().to(torch.float32).cpu()
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{prefix}{key}: shape {tuple(t.shape)} != {shape}")
+            t32[key] = t
+        # weights are laid out once: every Linear a 1x1 convolution operand [Cout, Kpad]; to_q | to_k | to_v of the self-attention
+        # (no bias, one input) one [3*inner, inner] operand, to_k | to_v of the cross-attention one [2*inner, context_dim] operand
+        self.w: Dict[str, torch.Tensor] = {}
+
+        def gemm(name, *parts):
+            w = torch.cat([t32[p].reshape(t32[p].shape[0], t32[p].shape[1], 1, 1) for p in parts])
+            self.w[name] = ops.pack_conv_weight(w).to(self.device)
+
+        for key, t in t32.items():
+            if t.dim() == 1:
+                self.w[key] = t.contiguous().to(self.device)
+        gemm("proj_in.weight", "proj_in.weight")
+        gemm("proj_out.weight", "proj_out.weight")
+        for i in range(self.depth):
+            b = f"transformer_blocks.{i}"
+            gemm(f"{b}.attn1.to_qkv.weight", f"{b}.attn1.to_q.weight", f"{b}.attn1.to_k.weight", f"{b}.attn1.to_v.weight")
+            gemm(f"{b}.attn2.to_q.weight", f"{b}.attn2.to_q.weight")
+            gemm(f"{b}.attn2.to_kv.weight", f"{b}.attn2.to_k.weight", f"{b}.attn2.to_v.weight")
+            for n in ("attn1.to_out.0", "attn2.to_out.0", "ff.net.0.proj", "ff.net.2"):
+                gemm(f"{b}.{n}.weight", f"{b}.{n}.weight")
+        self.torch_glue = _torch_glue()
+        self.fused_attention = (not self.torch_glue) and self.d_head in FUSED_HEAD_SIZES
+
+    # ---- building blocks ------------------------------------------------------------------------------------------
+    def _gemm(self, name: str, x: torch.Tensor, bias: bool = False, addend: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [B, N, K] -> x W^T (+ bias) (+ addend) [B, N, Cout]: a 1x1 convolution over the token rows."""
+        B, N, K = x.shape
+        w = self.w[f"{name}.weight"]
+        co = w.shape[0]
+        out = ops.conv2d_nhwc(x.view(B, 1, N, K), w, 1, 1, co, shift=self.w[f"{name}.bias"] if bias else None,
+                              addend=None if addend is None else addend.view(B, 1, N, co))
+        return out.view(B, N, co)
+
+    def _layernorm(self, name: str, x: torch.Tensor) -> torch.Tensor:
+        if self.torch_glue:
+            return F.layer_norm(x, (x.shape[-1],), self.w[f"{name}.weight"], self.w[f"{name}.bias"], 1e-5)
+        return ops.layernorm(x, self.w[f"{name}.weight"], self.w[f"{name}.bias"], 1e-5)
+
+    def _geglu(self, a: torch.Tensor) -> torch.Tensor:
+        if self.torch_glue:
+            v, gate = a.chunk(2, dim=-1)
+            return (v * F.gelu(gate)).contiguous()
+        return ops.geglu(a)
+
+    def _attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """q [B,Nq,inner], k / v [B,Nk,inner] (possibly slices of wider GEMM outputs) -> [B,Nq,inner], written to `out` when given."""
+        if self.fused_attention:
+            return ops.attention_bnhd(q, k, v, self.heads, out=out)
+        # the glue this module replaces (attention.py:338-345, :430-435): [(b h), n, d] copies in, one copy out
+        B, Nq, _ = q.shape
+        o = ops.attention(*(to_reference_layout(t, self.heads) for t in (q, k, v)))
+        o = o.view(B, self.heads, Nq, self.d_head).permute(0, 2, 1, 3).reshape(B, Nq, self.inner)
+        if out is None:
+            return o.contiguous()
+        out.copy_(o)
+        return out
+
+    def _reference_kv(self, reference_kv, B: int, N: int):
+        """-> None, or (mode, k, v) on the device in our layout, entries concatenated along tokens (attention.py:361-362)."""
+        if not reference_kv:
+            return None
+        entries = [tuple(e) for e in reference_kv]
+        if any(len(e) not in (2, 3) for e in entries):
+            raise ValueError("reference_kv entries are (k, v) or (k, v, layer) tuples")
+        mode, _, ref_layout = plan_reference_kv([(e[0].shape, e[1].shape) for e in entries], B, N, self.heads, self.d_head)
+        ks, vs = [], []
+        for e, rl in zip(entries, ref_layout):
+            for t, dst in ((e[0], ks), (e[1], vs)):
+                t = t.to(device=self.device, dtype=torch.float32)
+                dst.append(from_reference_layout(t, self.heads) if rl else t.contiguous())
+        k = ks[0] if len(ks) == 1 else torch.cat(ks, dim=1)
+        v = vs[0] if len(vs) == 1 else torch.cat(vs, dim=1)
+        return mode, k, v
+
+    def _block(self, i: int, x: torch.Tensor, context: Optional[torch.Tensor], ref) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+        """BasicTransformerBlock._forward (:464-469) on tokens x [B, N, inner]."""
+        b = f"transformer_blocks.{i}"
+        inner = self.inner
+        B, N, _ = x.shape
+        # self-attention: one GEMM for q | k | v, the attention reads its thirds in place
+        qkv = self._gemm(f"{b}.attn1.to_qkv", self._layernorm(f"{b}.norm1", x))
+        q, k, v = qkv[..., :inner], qkv[..., inner:2 * inner], qkv[..., 2 * inner:]
+        kv_hist = (k.contiguous(), v.contiguous())                 # the block's own K/V, recorded before any replacement (:353)
+        if ref is None:
+            a = self._attention(q, k, v)
+        elif ref[0] == "all":
+            a = self._attention(q, ref[1], ref[2])                 # k = k2, v = v2 (:368-369)
+        else:
+            # k[nhead:] = k2 (:365-366): image 0 on its own K/V, images 1.. on the references'; two launches into one buffer
+            a = torch.empty((B, N, inner), dtype=torch.float32, device=x.device)
+            self._attention(q[:1], k[:1], v[:1], out=a[:1])
+            self._attention(q[1:], ref[1], ref[2], out=a[1:])
+        x = self._gemm(f"{b}.attn1.to_out.0", a, bias=True, addend=x)
+        # cross-attention (a second self-attention without context, :467)
+        hn = self._layernorm(f"{b}.norm2", x)
+        src = hn if context is None else context
+        kv = self._gemm(f"{b}.attn2.to_kv", src)
+        a = self._attention(self._gemm(f"{b}.attn2.to_q", hn), kv[..., :inner], kv[..., inner:])
+        x = self._gemm(f"{b}.attn2.to_out.0", a, bias=True, addend=x)
+        # feed-forward: Linear -> GEGLU -> Linear (:59-76)
+        g = self._geglu(self._gemm(f"{b}.ff.net.0.proj", self._layernorm(f"{b}.norm3", x), bias=True))
+        x = self._gemm(f"{b}.ff.net.2", g, bias=True, addend=x)
+        return x, kv_hist
+
+    def _contexts(self, context, B: int) -> List[Optional[torch.Tensor]]:
+        """One context per block: a tensor serves every block (the reference indexes a list, :517-518, :530)."""
+        ctxs = list(context) if isinstance(context, (list, tuple)) else [context] * self.depth
+        if len(ctxs) != self.depth:
+            raise ValueError(f"{len(ctxs)} contexts for {self.depth} blocks")
+        out = []
+        for c in ctxs:
+            if c is None:
+                if self.context_dim != self.inner:
+                    raise ValueError(f"context=None needs context_dim == n_heads * d_head, this module has {self.context_dim}")
+                out.append(None)
+                continue
+            if not torch.is_tensor(c) or not c.is_cuda or c.dtype != torch.float32 or c.dim() != 3 or c.shape[0] != B or c.shape[2] != self.context_dim:
+                raise RuntimeError(f"context must be a CUDA float32 tensor [{B},M,{self.context_dim}]")
+            out.append(c.contiguous())
+        return out
+
+    @torch.no_grad()
+    def forward_nhwc(self, x: torch.Tensor, context=None, reference_kv=()) -> Tuple[torch.Tensor, List[Tuple[torch.Tensor, torch.Tensor]]]:
+        """`forward` on NHWC: x f32 [B,h,w,C] on the device -> (out [B,h,w,C], kv_hists)."""
+        if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[3] != self.in_channels:
+            raise RuntimeError(f"x must be a CUDA float32 tensor with {self.in_channels} channels")
+        x = x.contiguous()
+        B, h, w, _ = x.shape
+        N = h * w
+        if B * N * 8 * self.inner * 4 >= (1 << 31):
+            raise RuntimeError("the feed-forward activation would pass 2 GiB (32-bit byte offsets in the GEMM): slice the batch")
+        ctxs = self._contexts(context, B)
+        ref = self._reference_kv(reference_kv, B, N)               # raises before any launch
+        t = ops.groupnorm(x, self.w["norm.weight"], self.w["norm.bias"], 32, 1e-6, False)
+        t = ops.conv2d_nhwc(t, self.w["proj_in.weight"], 1, 1, self.inner, shift=self.w["proj_in.bias"]).view(B, N, self.inner)
+        kv_hists = []
+        for i in range(self.depth):
+            t, kv = self._block(i, t, ctxs[i], ref)
+            kv_hists.append(kv)
+        out = ops.conv2d_nhwc(t.view(B, h, w, self.inner), self.w["proj_out.weight"], 1, 1, self.in_channels,
+                              shift=self.w["proj_out.bias"], addend=x)
+        return out, kv_hists
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor, context=None, reference_kv=()) -> Tuple[torch.Tensor, List[Tuple[torch.Tensor, torch.Tensor]]]:
+        """SpatialTransformer.forward (:515-537): x f32 [B,C,h,w] on the device, context [B,M,context_dim] or None, reference_kv a
+        sequence of (k, v) or (k, v, layer) -> (x + proj_out(blocks(proj_in(norm(x)))), kv_hists); kv_hists[i] = the own
+        self-attention (k, v) of block i, contiguous device tensors [B, h*w, inner]."""
+        if not torch.is_tensor(x) or x.dim() != 4:
+            raise RuntimeError("x must be a CUDA float32 tensor [B,C,h,w]")
+        out, kv = self.forward_nhwc(x.permute(0, 2, 3, 1).contiguous(), context, reference_kv)
+        return out.permute(0, 3, 1, 2).contiguous(), kv
+
+    __call__ = forward
