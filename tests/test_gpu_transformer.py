@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import flash_attn_check as FC    # noqa: E402
 import sd_ops_check as SC        # noqa: E402
 import transformer_check as TC   # noqa: E402
 
@@ -235,8 +236,11 @@ def test_attention_bnhd_is_bit_identical_to_attention_on_permuted_copies(cuda, B
     assert torch.equal(_permuted(wide[..., 4:4 + H * D], H), ops.attention(_permuted(q, H), _permuted(k, H), _permuted(v, H), bz, 0.2))
     assert bool((wide[..., :4] == 7.0).all()) and bool((wide[..., 4 + H * D:] == 7.0).all())
     if (D, bias) == (40, "shared"):
-        # and against float64 within the bound of the attention tests (sd_ops_check.at_reference)
-        ref64, bound = SC.at_reference(_permuted(q, H).cpu(), _permuted(k, H).cpu(), _permuted(v, H).cpu(), bz.cpu(), float(D) ** -0.5)
+        # and against float64 within the bound derived for the fused kernel (flash_attn_check.fa_reference), capped by the bound of
+        # the unfused kernel this check used before, so that it asks no less than it did
+        operands = (_permuted(q, H).cpu(), _permuted(k, H).cpu(), _permuted(v, H).cpu(), bz.cpu(), float(D) ** -0.5)
+        ref64, bound = FC.fa_reference(*operands)
+        bound = torch.minimum(bound, SC.at_reference(*operands)[1])
         ratio = SC._worst((_permuted(out, H).cpu().double() - ref64).abs(), bound)
         print(f"attention_bnhd vs float64: worst err / bound {ratio:.4f}")
         assert ratio <= 1.0
