@@ -297,6 +297,24 @@ typedef struct ofx_conv_desc {
 #define OFX_CONV_TILE_WINOGRAD 1
 
 int ofx_conv2d(const ofx_conv_desc* d, void* stream);
+/* What the launcher would do with `d`, without doing it: the validation and the plan of ofx_conv2d (stats_cap_floats = 0), of
+ * ofx_conv2d_stats with room for stats_cap_floats floats, or (want_pool != 0, internal) of the correlation-volume GEMM that also
+ * writes pyramid level 1.  Only the numbers of `d` and whether its pointers are set and aligned are looked at: no operand is read
+ * and no device is needed.  Returns what the launch would return for an invalid descriptor, and OFX_EINVAL for a GEMM whose
+ * output extent is beyond 2 GiB (it runs in row ranges, each with a plan of its own).  In `tile` terms: a direct launch runs the
+ * BM x BN tile with chunk length BK that `tile` = BK*1000000 + BM*1000 + BN names, `ks` = 2 being its 2000000000 marker. */
+typedef struct ofx_conv_plan {
+    int path;                /* 0 direct implicit-GEMM kernel, 1 fused Winograd F(2x2,3x3), 2 fused Winograd F(4,5); 1 / 2: only
+                                `stats_rows` below is meaningful */
+    int bm, bn, wm, wn, bk;  /* workgroup tile, wave tile, K chunk */
+    int prec;                /* arithmetic of the kernel: OFX_PREC_*, after the split-bf16 modes have mapped the tile onto theirs */
+    int ks;                  /* 2: paired K pipelines (64x64 tile on small grids), else 1 */
+    int ksplit;              /* > 1: split-K over that many workgroups per tile (needs splitk_ws) */
+    int mode;                /* A-side schedule: 0 general gather, 1 scalar chunk coordinates, 2 halo patch */
+    int mtiles, ntiles, group_m;   /* grid = mtiles * ntiles * ksplit workgroups per z; group_m: M-tiles per raster group */
+    int stats_rows;          /* rows per image ofx_conv2d_stats would report, 0: not produced */
+} ofx_conv_plan;
+int ofx_conv2d_plan(const ofx_conv_desc* d, size_t stats_cap_floats, int want_pool, ofx_conv_plan* out);
 /* host-side helper: OIHW fp32 -> packed [Cout][Kpad] with Cin padded to cin_pad (>= Cin, %4==0).
  * Returns Kpad (or negative error).  `out` may be NULL to query the size. */
 long ofx_pack_conv_weight(const float* w_oihw, int Cout, int Cin, int KH, int KW, int cin_pad,

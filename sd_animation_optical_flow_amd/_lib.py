@@ -46,6 +46,12 @@ class ConvDesc(C.Structure):
     ]
 
 
+class ConvPlan(C.Structure):
+    """Mirror of `ofx_conv_plan` (include/ofx.h)."""
+    _fields_ = [(n, C.c_int) for n in ("path", "bm", "bn", "wm", "wn", "bk", "prec", "ks", "ksplit", "mode", "mtiles", "ntiles",
+                                       "group_m", "stats_rows")]
+
+
 class Tensor(C.Structure):
     """Mirror of `ofx_tensor`."""
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("ndim", C.c_int), ("shape", C.c_long * 4)]
@@ -74,6 +80,7 @@ SIGNATURES = {
     "ofx_fb_confidence": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p]),
     "ofx_warp_and_mask": (_i, [_p, _l, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _i, _p]),
     "ofx_conv2d": (_i, [C.POINTER(ConvDesc), _p]),
+    "ofx_conv2d_plan": (_i, [C.POINTER(ConvDesc), _z, _i, C.POINTER(ConvPlan)]),
     "ofx_pack_conv_weight": (_l, [_p, _i, _i, _i, _i, _i, _p]),
     "ofx_wino_conv_weight": (_l, [_p, _i, _i, _p]),
     "ofx_wino15_conv_weight": (_l, [_p, _i, _i, _i, _i, _p]),

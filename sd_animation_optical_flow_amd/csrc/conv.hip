@@ -1181,32 +1181,40 @@ __global__ __launch_bounds__(256 * KS, (BK == 16 && KS == 1) ? ((PREC == 3 || PR
     else epilogue(std::false_type{});
 }
 
+// The instantiated (tile, arithmetic, pipeline) combinations with a halo-patch (MODE 2) / a scalar-coordinate (MODE 1) form
+constexpr bool tile_has_patch(int BM, int BN, int BK, int PREC, int KS, bool SK) {
+    return KS == 1 && ((PREC == 0 && BM == 128 && BK == 16 && !SK && (BN == 64 || BN == 96 || BN == 128 || BN == 192)) || (PREC == 0 && BM == 64 && BN == 64 && BK == 32) ||
+                       (PREC == 0 && BM == 256 && BN == 64 && BK == 16 && !SK) ||
+                       ((PREC == 1 || PREC == 2 || PREC == 3 || PREC == 4) && BM == 128 && BK == 16 && !SK && (BN == 64 || BN == 128)));
+}
+constexpr bool tile_has_scalar(int BN, int PREC) { return PREC == 0 && BN != 192; }   // the 128x192 tile measured 0.8 % slower with scalar chunk coordinates
+
 template <int BM, int BN, int WM, int WN, int BK, int PREC, int KS, bool SK, int UK>
-int launch_tile_uk(const ConvK& k, int epi, bool norm, int nz, hipStream_t s) {
+int launch_tile_uk(const ConvK& k, int epi, bool norm, int nz, hipStream_t s, hipEvent_t ev) {
     dim3 grid((unsigned)(k.mtiles * k.ntiles * (k.ksplit > 1 ? k.ksplit : 1)), (unsigned)nz, 1);
     dim3 block(256 * KS, 1, 1);
     switch (epi) {
         case OFX_EPI_PLAIN:
             if (k.act >= OFX_ACT_SIGMOID) {
                 if (norm) return OFX_EINVAL;   // fused-norm producer layers are followed by ReLU / identity only
-                OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, kEpiPlainT, false, BK, PREC, KS, SK, UK>), grid, block, s, k);
+                OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, kEpiPlainT, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
             } else if (norm) {
-                OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_PLAIN, true, BK, PREC, KS, SK, UK>), grid, block, s, k);
+                OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_PLAIN, true, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
             } else {
-                OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_PLAIN, false, BK, PREC, KS, SK, UK>), grid, block, s, k);
+                OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_PLAIN, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
             }
             break;
-        case OFX_EPI_GRU_ZR: OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_GRU_ZR, false, BK, PREC, KS, SK, UK>), grid, block, s, k); break;
-        case OFX_EPI_GRU_Q: OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_GRU_Q, false, BK, PREC, KS, SK, UK>), grid, block, s, k); break;
+        case OFX_EPI_GRU_ZR: OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_GRU_ZR, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k); break;
+        case OFX_EPI_GRU_Q: OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_GRU_Q, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k); break;
         case OFX_EPI_FLOW:
             if constexpr (UK != 2) {
-                OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_FLOW, false, BK, PREC, KS, SK, UK>), grid, block, s, k);
+                OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_FLOW, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
                 break;
             }
             return OFX_EINVAL;
         case kEpiVolPool:
             if constexpr (BM == 128 && BN == 128 && BK == 16 && KS == 1 && !SK && UK != 2) {
-                OFX_LAUNCH((igemm_kernel<128, 128, 64, 64, kEpiVolPool, false, 16, PREC, 1, false, UK>), grid, block, s, k);
+                OFX_LAUNCH((igemm_kernel<128, 128, 64, 64, kEpiVolPool, false, 16, PREC, 1, false, UK>), grid, block, s, ev, k);
                 break;
             }
             return OFX_EINVAL;
@@ -1215,72 +1223,291 @@ int launch_tile_uk(const ConvK& k, int epi, bool norm, int nz, hipStream_t s) {
     return ofx_launch_status();
 }
 
+// One instantiated tile: the A-side schedule the plan chose arrives in k.patch / k.uk
 template <int BM, int BN, int WM, int WN, int BK, int PREC = 0, int KS = 1, bool SK = false>
-int launch_tile(const ConvK& k, int epi, bool norm, int nz, hipStream_t s) {
-    if constexpr (KS == 1 && ((PREC == 0 && BM == 128 && BK == 16 && !SK && (BN == 64 || BN == 96 || BN == 128 || BN == 192)) || (PREC == 0 && BM == 64 && BN == 64 && BK == 32) ||
-                              (PREC == 0 && BM == 256 && BN == 64 && BK == 16 && !SK) ||
-                              ((PREC == 1 || PREC == 2 || PREC == 3 || PREC == 4) && BM == 128 && BK == 16 && !SK && (BN == 64 || BN == 128)))) {
-        if (k.patch && epi != OFX_EPI_FLOW && epi != kEpiVolPool) return launch_tile_uk<BM, BN, WM, WN, BK, PREC, KS, SK, 2>(k, epi, norm, nz, s);
+int launch_tile(const ConvK& k, int epi, bool norm, int nz, hipStream_t s, hipEvent_t ev) {
+    if constexpr (tile_has_patch(BM, BN, BK, PREC, KS, SK)) {
+        if (k.patch) return launch_tile_uk<BM, BN, WM, WN, BK, PREC, KS, SK, 2>(k, epi, norm, nz, s, ev);
     }
-    if constexpr (PREC == 0 && BN != 192) {   // the 128x192 tile measured 0.8 % slower with scalar chunk coordinates
-        if (k.uk) return launch_tile_uk<BM, BN, WM, WN, BK, PREC, KS, SK, 1>(k, epi, norm, nz, s);
+    if constexpr (tile_has_scalar(BN, PREC)) {
+        if (k.uk) return launch_tile_uk<BM, BN, WM, WN, BK, PREC, KS, SK, 1>(k, epi, norm, nz, s, ev);
     }
-    return launch_tile_uk<BM, BN, WM, WN, BK, PREC, KS, SK, 0>(k, epi, norm, nz, s);
+    return launch_tile_uk<BM, BN, WM, WN, BK, PREC, KS, SK, 0>(k, epi, norm, nz, s, ev);
 }
 
-}  // namespace
-
-namespace {
-struct VolPool {            // set by ofx_conv2d_volpool around one ofx_conv2d_alpha call (same thread)
-    bool on = false;
-    float* out = nullptr;
-    long zs = 0;
-    int wb0 = 0, wb1 = 0, slice1 = 0;
+// Every instantiated (BM, BN, WM, WN, BK, PREC, KS, SK): what a plan may name, and how it is launched
+struct TileInst {
+    int bm, bn, wm, wn, bk, prec, ks;
+    bool sk;
+    int (*launch)(const ConvK&, int epi, bool norm, int nz, hipStream_t, hipEvent_t);
 };
-thread_local VolPool tl_pool;
-
-// Instance-norm statistics from the accumulators (set by ofx_conv2d_stats around one ofx_conv2d call): every wave of a tile writes
-// the per-channel sum and sum of squares of its WM rows; a finalize kernel adds them per image in a fixed order.  Saves the
-// statistics pass over the tensor the convolution has just written.
-struct StatsReq {
-    bool on = false;
-    float* part = nullptr;
-    size_t cap_floats = 0;
-    int rows_per_image = 0;     // out: 0 = not produced (the caller falls back to ofx_inorm_stats)
+#define OFX_TILE(BM, BN, WM, WN, BK, PREC, KS, SK) {BM, BN, WM, WN, BK, PREC, KS, SK, &launch_tile<BM, BN, WM, WN, BK, PREC, KS, SK>}
+const TileInst kTiles[] = {
+#ifndef OFX_CONV_LEAN   // experiment builds (tools/build_variant.sh): fp32 only -- a third of the instantiations, a third of the compile time
+    // split-bf16 matrix-core paths (opt-in): three tiles per arithmetic
+    OFX_TILE(128, 128, 64, 64, 16, 3, 1, false), OFX_TILE(128, 128, 64, 64, 16, 2, 1, false), OFX_TILE(128, 128, 64, 64, 16, 1, 1, false),
+    OFX_TILE(128, 128, 64, 64, 16, 4, 1, false), OFX_TILE(128, 64, 64, 32, 16, 4, 1, false),  OFX_TILE(64, 64, 32, 32, 16, 4, 1, false),
+    OFX_TILE(128, 64, 64, 32, 16, 3, 1, false),  OFX_TILE(64, 64, 32, 32, 16, 3, 1, false),   OFX_TILE(128, 128, 64, 64, 32, 1, 1, false),
+    OFX_TILE(128, 64, 64, 32, 16, 2, 1, false),  OFX_TILE(128, 64, 64, 32, 16, 1, 1, false),  OFX_TILE(64, 64, 32, 32, 16, 2, 1, false),
+    OFX_TILE(64, 64, 32, 32, 16, 1, 1, false),
+#endif
+    // BK = 16 keeps LDS at 40 KB and registers under 128 for the 128x128 tile -> 4 workgroups per CU (3 for 128x192); the
+    // extra resident wave per SIMD hides the commit/barrier/issue phases better than a longer chunk does
+    // (measured +4..10 % on every shape).  The 64x64 tile is only chosen for grids that under-fill the
+    // machine (one workgroup per CU or fewer): there each chunk's load latency is exposed and the longer
+    // chunk wins (+8..20 % at one 512x768 pair).
+    OFX_TILE(128, 128, 64, 64, 16, 0, 1, false), OFX_TILE(256, 64, 64, 64, 16, 0, 1, false),  OFX_TILE(128, 192, 64, 96, 16, 0, 1, false),
+    OFX_TILE(128, 96, 32, 96, 16, 0, 1, false),  OFX_TILE(128, 64, 64, 32, 16, 0, 1, false),  OFX_TILE(128, 128, 64, 64, 32, 0, 1, false),
+    OFX_TILE(128, 64, 64, 32, 32, 0, 1, false),  OFX_TILE(128, 32, 32, 32, 32, 0, 1, false),  OFX_TILE(64, 64, 32, 32, 16, 0, 1, false),
+    OFX_TILE(64, 64, 32, 32, 32, 0, 1, true),    OFX_TILE(64, 64, 32, 32, 32, 0, 2, false),   OFX_TILE(64, 64, 32, 32, 32, 0, 1, false),
 };
-thread_local StatsReq tl_stats;
-}  // namespace
+#undef OFX_TILE
 
-extern "C" int ofx_conv2d(const ofx_conv_desc* d, void* stream) { return ofx_conv2d_alpha(d, 1.0f, stream); }
+// ---- knobs: the diagnostic environment switches of the launcher, read once.  A value that does not parse or is out of range
+// (negative counts, a cover below 1) falls back to the default.
+struct ConvKnobs {
+    bool no_wino = false, no_wino15 = false;   // OFX_CONV_NO_WINOGRAD (both fused kernels) / OFX_CONV_NO_WINOGRAD15 (F(4,5) only)
+    bool old_small = false;                    // OFX_CONV_OLD_SMALL_TILES: A/B switch, the round-4 small-grid rule
+    bool no_splitk = false;                    // OFX_NO_SPLITK
+    long sk_max_tiles = 2048;                  // OFX_SK_MAX_TILES: largest 64x64 grid that may split K
+    bool no_uk = false, no_patch = false;      // OFX_CONV_NO_UK / OFX_CONV_NO_PATCH: never the scalar-coordinate / halo-patch schedule
+    double patch_max_waste = 1.09;             // OFX_PATCH_MAX_WASTE: largest cover of a map by overhanging patches
+    long vol_group_m = 0;                      // OFX_VOL_GROUP_M: raster probe, M-tiles per group of the wide-N volume GEMM (0: the rule)
+    long pair_max = 320;                       // OFX_CONV_PAIR_MAX: largest grid that pairs the 64x64 pipelines (0: never)
+};
 
-// ofx_conv2d that also leaves, when the launch qualifies, the per-wave (sum, sum of squares) of every output channel in `part`
-// ([B][rows_per_image][Cout][2] floats) for ofx_inorm_finalize_part; *rows_per_image = 0 means "not produced".
-int ofx_conv2d_stats(const ofx_conv_desc* d, float* part, size_t part_floats, int* rows_per_image, void* stream) {
-    tl_stats.on = true;
-    tl_stats.part = part;
-    tl_stats.cap_floats = part_floats;
-    tl_stats.rows_per_image = 0;
-    const int st = ofx_conv2d_alpha(d, 1.0f, stream);
-    *rows_per_image = st ? 0 : tl_stats.rows_per_image;
-    tl_stats = StatsReq{};
-    return st;
+const ConvKnobs& conv_knobs() {
+    static const ConvKnobs knobs = [] {
+        auto flag = [](const char* name) { return getenv(name) != nullptr; };
+        auto number = [](const char* name, double lo, double hi, double dflt) {   // the whole string a number in [lo, hi], else dflt
+            const char* e = getenv(name);
+            char* end = nullptr;
+            const double v = e ? strtod(e, &end) : 0.0;
+            return e && end != e && !*end && v >= lo && v <= hi ? v : dflt;
+        };
+        ConvKnobs k;
+        k.no_wino = flag("OFX_CONV_NO_WINOGRAD");
+        k.no_wino15 = k.no_wino || flag("OFX_CONV_NO_WINOGRAD15");
+        k.old_small = flag("OFX_CONV_OLD_SMALL_TILES");
+        k.no_splitk = flag("OFX_NO_SPLITK");
+        k.no_uk = flag("OFX_CONV_NO_UK");
+        k.no_patch = flag("OFX_CONV_NO_PATCH");
+        auto count = [&](const char* name, long dflt) { const double v = number(name, 0, 0x7FFFFFFF, dflt); return v == (long)v ? (long)v : dflt; };
+        k.sk_max_tiles = count("OFX_SK_MAX_TILES", k.sk_max_tiles);
+        k.patch_max_waste = number("OFX_PATCH_MAX_WASTE", 1.0, 1e30, k.patch_max_waste);
+        k.vol_group_m = count("OFX_VOL_GROUP_M", k.vol_group_m);
+        k.pair_max = count("OFX_CONV_PAIR_MAX", k.pair_max);
+        return k;
+    }();
+    return knobs;
 }
 
-// Correlation volume in the blocked layout + pyramid level 1 from the accumulators (corr.hip decides when it applies:
-// 128x128 tiles, h % 8 == 0 and w % 16 == 0 so that level 1 is tiled by whole blocks; any arithmetic).  pool_out: level 1,
-// [nz][M][slice1]; wb0 / wb1: blocks per slice row of level 0 / 1.
-int ofx_conv2d_volpool(const ofx_conv_desc* d, float alpha, float* pool_out, long pool_zs, int wb0, int wb1, int slice1, void* stream) {
-    OFX_REQUIRE(d && pool_out && wb0 > 0 && wb1 > 0 && slice1 > 0, OFX_EINVAL);
-    OFX_REQUIRE(d->epi == OFX_EPI_PLAIN && d->act == OFX_ACT_NONE && !d->res && !d->addend && !d->nmean &&
-                    !d->scale && !d->shift && d->Cout % 128 == 0 && d->tile == 0,
-                OFX_EINVAL);
-    tl_pool.on = true; tl_pool.out = pool_out; tl_pool.zs = pool_zs; tl_pool.wb0 = wb0; tl_pool.wb1 = wb1; tl_pool.slice1 = slice1;
-    const int st = ofx_conv2d_alpha(d, alpha, stream);
-    tl_pool = VolPool{};
-    return st;
+// ---- plan: everything a launch needs that is not a pointer.  conv_plan is a pure function of the descriptor's numbers (and of which
+// of its pointers are set), the extras and the knobs: no HIP call, no environment, no global state.
+enum { kPathIgemm = 0, kPathWino3x3 = 1, kPathWino15 = 2 };
+struct ConvPlan : ofx_conv_plan {   // the public fields (ofx.h: path, tile, arithmetic, schedule, grid, statistics rows) and ...
+    int inst = -1;                  // direct kernels: the row of kTiles that bm ... ks and ksplit > 1 name
+    const char* name = nullptr;     // family of the per-layer profile
+    double flops = 0.0;             // executed by the launch
+};
+
+int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, ConvPlan* p) {
+    *p = ConvPlan{};
+    p->ks = p->ksplit = p->group_m = 1;
+    const int nz = d->nz > 1 ? d->nz : 1, cin = d->c0 + d->c1;
+    const int K = d->KH * d->KW * cin, Kpad = ((K + kKAlign - 1) / kKAlign) * kKAlign;
+    const long M = (long)d->B * d->Hout * d->Wout;
+    const bool want_stats = x.stats_rows != nullptr, pool = x.pool.out != nullptr, fp32 = d->precision == OFX_PREC_FP32;
+    p->name = nz > 1 ? "igemm_corr_volume"
+              : d->epi == OFX_EPI_GRU_ZR ? "igemm_conv_gru_zr"
+              : d->epi == OFX_EPI_GRU_Q  ? "igemm_conv_gru_q"
+              : d->epi == OFX_EPI_FLOW   ? "igemm_conv_flow"
+                                         : "igemm_conv";
+
+    // ---- fused Winograd (conv_wino.hip): F(2x2,3x3) for the update block's and the encoders' stride-1 3x3 layers (4 instead of 9
+    // multiplies per output; residual merge, fused instance norm and epilogue statistics included) and F(4,5) for the SepConvGRU's
+    // 1x5 / 5x1 layers (2 instead of 5, GRU gate epilogues included).  Only on grids that fill the chip (ofx_conv_wino_pays):
+    // smaller grids, the single pair among them, keep the direct kernels and their small-grid schedules.
+    const bool force = d->tile == OFX_CONV_TILE_WINOGRAD;
+    const bool one_d = (d->KH == 1 && d->KW == 5) || (d->KH == 5 && d->KW == 1);
+    if (force || (d->tile == 0 && !(one_d ? kn.no_wino15 : kn.no_wino) && d->wino_w)) {
+        // asked for statistics: only where the fused kernel leaves them (one row per 8x16 patch), in the caller's room
+        const int srows = want_stats ? ofx_conv_wino_stats_rows(d) : 0;
+        const bool stats_ok = !want_stats || (srows > 0 && (size_t)d->B * srows * d->Cout * 2 <= x.stats_cap);
+        const bool fits = nz == 1 && stats_ok && !pool && ofx_conv_wino_fits(d);
+        if (force && !fits) return OFX_EINVAL;
+        if (fits && (force || ofx_conv_wino_pays(d))) {
+            p->path = one_d ? kPathWino15 : kPathWino3x3;
+            p->stats_rows = srows;
+            p->flops = ofx_conv_wino_flops(d);
+            return 0;
+        }
+    }
+    p->flops = 2.0 * (double)M * d->Cout * K * nz;
+
+    // ---- tile selection
+    int bm, bn;
+    if (d->tile) {
+        bm = (d->tile % 1000000) / 1000;
+        bn = d->tile % 1000;
+    } else {
+        auto waste = [&](int t) { return (double)(((d->Cout + t - 1) / t) * t) / d->Cout; };
+        if (d->Cout <= 32) bn = 32;
+        else if (waste(128) <= 1.13 && !(waste(192) <= 1.0 && waste(128) > 1.05 && fp32 && !d->nmean && d->epi == OFX_EPI_PLAIN)) bn = 128;   // (576 channels: 3 x 192, not 4.5 x 128)
+        else if (waste(192) <= 1.05 && fp32 && !d->nmean && d->epi != OFX_EPI_FLOW) bn = 192;   // 192-channel layers: one 128x192 tile instead of 128x64 x 3
+        else if (waste(96) <= 1.05 && fp32 && d->epi == OFX_EPI_PLAIN) bn = 96;   // 96-channel encoder stage
+        else if (waste(64) <= 1.13) bn = 64;
+        else if (waste(32) < waste(64) - 0.1) bn = 32;
+        else bn = 64;
+        bm = 128;
+        // Grids that do not fill the chip (B = 1 ... ~16 frames at 512x768).  Measured over every layer shape of the network at
+        // B = 1, 2, 4, 8, 16, 32 (tools/small_batch_tune.py, profiles/r05_small_batch_tune.txt): a 128-row tile keeps its rate down
+        // to THREE workgroups per CU (768 on this part) and loses to the next smaller tile below that -- so take the largest tile
+        // whose grid still has 768 workgroups: 128x192 -> 128x96 -> 128x64 for the 192-channel layer, 128x128 -> 128x64 for the
+        // 128- / 256-channel ones, and only then the 64x64 small-grid tile (with split-K / paired pipelines below).  The old rule
+        // (64x64 below 1024 blocks of the 128-row tile) gave up 8-16 % per layer at B = 4 ... 16.
+        const long mt128 = (M + 127) / 128;
+        auto blocks_of = [&](int t) { return mt128 * ((d->Cout + t - 1) / t) * nz; };
+        constexpr long kFill = 768;                  // three workgroups per CU
+        const long blocks128 = blocks_of(bn);
+        if (kn.old_small) {
+            if (bn == 96 && blocks128 < 1024) bn = 32;
+            if (bn >= 64 && blocks128 < 1024) bm = 64;
+            if (bm == 64 && bn >= 128) bn = 64;
+        } else if (bn >= 64 && blocks128 < kFill) {
+            if (bn == 192 && d->epi == OFX_EPI_PLAIN && blocks_of(96) >= kFill) bn = 96;
+            else if (bn >= 128 && blocks_of(64) >= kFill) bn = 64;
+            else if (bn == 96) bn = 32;              // no small-grid variant of the 96-wide tile
+            else { bm = 64; bn = 64; }               // 64x64: the chip is filled by splitting K instead (below)
+        }
+    }
+    int mtiles = (int)((M + bm - 1) / bm), ntiles = (d->Cout + bn - 1) / bn;
+    // split-K (fp32, 64x64 tiles, single z): a grid of a few hundred tiles leaves a 256-CU part with a half-empty
+    // second round (384 tiles = 1.5 per CU: the makespan is 2 tiles); S splits make 384*S shorter work items that
+    // balance.  Needs caller scratch: 64 KiB of counters + tiles * S * 64*64 floats.
+    if (!kn.no_splitk && d->splitk_ws && fp32 && bm == 64 && bn == 64 && nz == 1 && d->tile == 0) {
+        const long tiles = (long)mtiles * ntiles;
+        const int nk32 = Kpad / 32;
+        // work per CU in tile units if the tiles are cut S ways: ceil(tiles * S / 256) / S -- take the S that
+        // minimises it (ties: fewer splits), with at least six 32-wide chunks per split
+        int S = 1;
+        // (tiles up to 2048: with five workgroups per CU resident, `convc2` of four frames -- 1152 tiles = 4.5 per CU -- runs as
+        // 2304 half-K workgroups: 24.15 -> 23.98 ms per four frames; the scratch bound below still applies)
+        if (tiles <= kn.sk_max_tiles && nk32 >= 12) {
+            const double base = (double)((tiles + 255) / 256);
+            double best = base;
+            for (int c = 2; c <= 4; ++c) {
+                if (nk32 / c < 6) break;
+                const double span = (double)((tiles * c + 255) / 256) / c;
+                // a split must buy more balance than its seam costs: 4 % of the unsplit span per split (round 6: 960 tiles cut four
+                // ways for a nominal 4 -> 3.75 ran 7 % SLOWER than unsplit -- `conv` / GRU q of five frames; 1152 tiles cut in two
+                // for 5 -> 4.5 gained 3 %; the single pair's layers gain 25-37 %)
+                if (span < best - 1e-9 && span < base * (1.0 - 0.04 * c) + 1e-9) { best = span; S = c; }
+            }
+        }
+        const size_t need = 65536 + (size_t)tiles * S * 64 * 64 * sizeof(float);
+        if (S > 1 && tiles * sizeof(int) <= 65536 && need <= d->splitk_ws_bytes && ofx_aligned16(d->splitk_ws)) p->ksplit = S;
+    }
+    // tile = BK*1e6 + BM*1e3 + BN overrides the chunk length of the tile (see kTiles for the rule)
+    const int tile_bk = (d->tile % 1000000000) / 1000000;
+    const int bk = tile_bk ? tile_bk : ((bn == 32 || bm == 64) ? 32 : 16);
+    // uniform-K fast path: every chunk of this launch's BK inside one tap and one segment (the 16-float flow rows of convf1 qualify
+    // with BK = 16; a caller-forced tile keeps the conservative multiple-of-32 rule)
+    // (`bk` is the BK of the fp32 tile; the split-bf16 remap further down changes tiles, but only PREC == 0 has the
+    // scalar-coordinate schedule, so `uk` is never read for a tile it was not derived from)
+    const int ukm = d->tile ? 32 : bk;
+    const bool uk = !kn.no_uk && fp32 && cin % ukm == 0 && (d->c1 == 0 || d->c0 % ukm == 0);
+    // halo-patch kernel: stride-1 3x3 / 1x5 / 5x1, "same" padding, the map a whole number of 8x16 patches, whole 16-channel slabs
+    const bool shape_ok = (d->KH == 3 && d->KW == 3) || one_d;
+    const bool same = d->stride == 1 && d->padH == d->KH / 2 && d->padW == d->KW / 2 && d->Hin == d->Hout && d->Win == d->Wout;
+    const bool big = (bm == 128 || (bm == 256 && bn == 64)) && bk == 16, small = bm == 64 && bn == 64 && bk == 32;   // 8x16 (16x16) patches / 8x8 patches (small grids, split-K)
+    const int pw = big ? 16 : 8, ph = bm == 256 ? 16 : 8;
+    auto cover = [&](int h, int w) { return (double)(((d->Hin + h - 1) / h) * h) * (double)(((d->Win + w - 1) / w) * w) / ((double)d->Hin * d->Win); };
+    // the 128-row tiles also take maps that are not whole patches (the last patch of a row / column hangs over: its outside
+    // pixels stage zeros and are masked in the epilogue); the small tile, whose grid feeds the split-K choice above, does not
+    const bool whole = d->Hin % ph == 0 && d->Win % pw == 0;
+    // ... as long as the overhang is cheap: the rows of a patch outside the map are multiplied like any others (a 68 x 120 map --
+    // 544x960 frames -- is 9 x 8 patches = 72 x 128 pixels: 1.13x the work).  Beyond a cover of OFX_PATCH_MAX_WASTE (default 1.09) a
+    // layer takes the scalar-coordinate / general kernels, which compute no row twice.  Measured, 16 frames, whole forward
+    // (tools/odd_sizes.py, patch kernel -> general kernels): cover 1.07 (720x1280) 218 -> 227 ms, 1.13 (544x960) 137 -> 117,
+    // 1.19 (600x800) 133 -> 117, 1.32 (776x520) 122 -> 107: the crossover sits near 1.09
+    const bool no_patch_here = kn.no_patch || (!whole && d->tile == 0 && cover(ph, pw) > kn.patch_max_waste);   // (a forced tile keeps the patch kernel: the tests' way in)
+    bool patch = !no_patch_here && fp32 && shape_ok && same && (whole || big) && cin % bk == 0 && (d->c1 == 0 || d->c0 % bk == 0) &&
+                 (!d->nmean || d->c1 == 0) && nz == 1 && (big || small) && (bn == 64 || bn == 96 || bn == 128 || bn == 192) && d->epi != OFX_EPI_FLOW;
+    if (patch && bm == 128 && bn == 64 && d->tile == 0 && d->Hin % 16 == 0 && d->Win % 16 == 0 && M / 256 >= (kn.old_small ? 4096 : 768)) {
+        // 64-channel layers: 16x16 patches (256x64 tile, 64x64 per wave) halve the weight staging per MFMA: 136 -> 139-143 TF on
+        // large grids, and ahead of the 128x64 tile from three workgroups per CU on (round 5 sweep: 110 vs 133 us at 768
+        // workgroups, 217 vs 232 at 1536; round 4 switched at 4096)
+        bm = 256;
+        mtiles = (int)(M / 256);
+    } else if (patch && !whole) {
+        mtiles = d->B * ((d->Hin + ph - 1) / ph) * ((d->Win + 15) / 16);
+    }
+    int prec = d->precision;
+    if (!fp32) {
+#ifdef OFX_CONV_LEAN
+        return OFX_EINVAL;
+#endif
+        // split-bf16 matrix-core path (opt-in): three tiles; every other choice is mapped onto them (the ragged
+        // N of a 96- or 2-channel layer is zero-filled by the descriptors)
+        if (bm == 64) bn = 64;
+        else if (bn != 64) bn = 128;
+        ntiles = (d->Cout + bn - 1) / bn;
+        // bf16x3 on the halo patch (128-row tiles, BK = 16): the fp32 -> (hi, lo) conversion of the A side then runs once per
+        // 16-channel slab instead of once per tap
+        const bool whole16 = d->Hin % 8 == 0 && d->Win % 16 == 0;
+        patch = !kn.no_patch && (whole16 || d->tile != 0 || cover(8, 16) <= kn.patch_max_waste) && shape_ok && same && cin % 16 == 0 &&
+                (d->c1 == 0 || d->c0 % 16 == 0) && (!d->nmean || d->c1 == 0) && nz == 1 && bm == 128 && tile_bk != 32 && d->epi != OFX_EPI_FLOW;
+        mtiles = patch && !whole16 ? d->B * ((d->Hin + 7) / 8) * ((d->Win + 15) / 16) : (int)((M + bm - 1) / bm);
+    }
+    // statistics from the accumulators: raw outputs only, tiles that stay inside one image; of the tile the launch ends up with
+    if (want_stats) {
+        const int waves_m = (bm == 256 && bn == 64) ? 4 : (bm == 128 && (bn == 128 || bn == 64 || bn == 192)) ? 2 : (bm == 128 && (bn == 96 || bn == 32)) ? 4
+                            : (bm == 64 && bn == 64) ? 2 : 0;
+        const long hw = (long)d->Hout * d->Wout;
+        const bool ok = waves_m && d->epi == OFX_EPI_PLAIN && d->act == OFX_ACT_NONE && !d->res && nz == 1 && mtiles % d->B == 0 && (patch || hw % bm == 0);
+        const long rows = ok ? (long)(mtiles / d->B) * waves_m : 0;
+        if (ok && (size_t)d->B * rows * d->Cout * 2 <= x.stats_cap) p->stats_rows = (int)rows;
+    }
+    // ---- the instantiation: which BK each tile exists with, the pipeline variant of the small tile
+    int lbk = 16, ks = 1;
+    if (pool) {   // the blocked correlation volume with pyramid level 1 out of the accumulators, in any arithmetic
+        bm = bn = 128;
+        mtiles = (int)((M + 127) / 128);
+        ntiles = (d->Cout + 127) / 128;
+        p->ksplit = 1;
+        if (prec == OFX_PREC_BF16X6_W) prec = OFX_PREC_BF16X6;   // (its B operand is data, never pre-split)
+    } else if (!fp32) {
+        if (prec == OFX_PREC_BF16X3 && bm == 128 && bn == 128 && tile_bk == 32) lbk = 32;
+    } else if (bm == 128 && bn == 32) {
+        lbk = 32;
+    } else if (!(bm == 256 && bn == 64) && !(bm == 128 && (bn == 192 || bn == 96))) {
+        lbk = bk == 16 ? 16 : 32;
+        if (bm == 64 && bn == 64 && lbk == 32 && p->ksplit == 1) {
+            // a grid of at most ~2 workgroups per CU is latency-bound: pair the pipelines (tile + 2e9 forces it, an explicit tile without that forbids it)
+            // (round 5: up to 320 blocks, not 640 -- at 384 blocks, `convc1` on one 512x768 pair, the plain tile is ahead: 8.76 -> 8.62 ms per pair)
+            const long blocks = (long)mtiles * ntiles * nz;
+            if (d->tile >= 2000000000 || (d->tile < 1000000 && blocks <= kn.pair_max && Kpad >= 8 * 32)) ks = 2;
+        }
+    }
+    const bool sk = p->ksplit > 1;
+    for (int i = 0; i < (int)(sizeof kTiles / sizeof kTiles[0]) && p->inst < 0; ++i) {
+        const TileInst& t = kTiles[i];
+        if (t.bm == bm && t.bn == bn && t.bk == lbk && t.prec == prec && t.ks == ks && t.sk == sk) p->inst = i;
+    }
+    OFX_REQUIRE(p->inst >= 0, OFX_EINVAL);
+    const TileInst& t = kTiles[p->inst];
+    p->bm = bm; p->bn = bn; p->wm = t.wm; p->wn = t.wn; p->bk = lbk; p->prec = prec; p->ks = ks;
+    p->mode = (patch && !pool && tile_has_patch(bm, bn, lbk, prec, ks, sk)) ? 2 : (uk && tile_has_scalar(bn, prec)) ? 1 : 0;
+    p->mtiles = mtiles; p->ntiles = ntiles;
+    p->group_m = (pool && fp32 && kn.vol_group_m > 0) ? (int)kn.vol_group_m : ntiles >= 8 ? 8 : 1;
+    return 0;
 }
 
-extern "C" int ofx_conv2d_alpha(const ofx_conv_desc* d, float alpha, void* stream) {
+// ---- validation: every check of a descriptor and its extras, none of an operand's contents.  *split_rows > 0: the epilogue extent
+// is beyond 32-bit byte offsets and the call runs in parts of that many rows, each validated on its own.
+int conv_validate(const ofx_conv_desc* d, const ConvExtra& x, long* split_rows) {
+    *split_rows = 0;
     OFX_REQUIRE(d != nullptr, OFX_EINVAL);
     OFX_REQUIRE(d->in0 && d->w, OFX_EINVAL);
     OFX_REQUIRE(d->c0 > 0 && d->c0 % 4 == 0 && d->ld0 % 4 == 0, OFX_EALIGN);
@@ -1302,41 +1529,51 @@ extern "C" int ofx_conv2d_alpha(const ofx_conv_desc* d, float alpha, void* strea
     // OFX_PREC_BF16X6_W: the kernel finds the lo pieces of the pre-split matrix at w + Cout * Kpad * 4 -- true only for the WHOLE matrix
     // `ofx_split_conv_weight3` converted (Cout = its row count) of ONE problem; a batched GEMM advances w per problem
     if (d->precision == OFX_PREC_BF16X6_W) OFX_REQUIRE(nz == 1, OFX_EINVAL);
-    {
-        // The epilogue addresses out / res / addend / aux_* with 32-bit byte offsets (descriptor extent
-        // M * ld * 4).  A pure GEMM (1x1, stride 1, no padding, plain epilogue -- the correlation volume of a
-        // large frame is the case that gets here) is split along M; anything else must be sliced by the caller.
-        int ld_epi = std::max(d->Cout, d->out ? d->ldo : 0);
-        if (d->res) ld_epi = std::max(ld_epi, d->ldres);
-        if (d->addend) ld_epi = std::max(ld_epi, d->ldadd);
-        if (d->aux_h) ld_epi = std::max(ld_epi, d->ldh);
-        const long Mtot = (long)d->B * d->Hout * d->Wout;
-        const long lim = (1L << 31) - 64;
-        if (Mtot * ld_epi * 4 >= lim) {
-            const bool gemm = d->KH == 1 && d->KW == 1 && d->stride == 1 && d->padH == 0 && d->padW == 0 &&
-                              d->epi == OFX_EPI_PLAIN && !d->nmean && d->Hout == d->Hin && d->Wout == d->Win;
-            OFX_REQUIRE(gemm, OFX_EINVAL);
-            const long rows = std::max<long>(128, ((lim / ((long)ld_epi * 4)) / 128 - 1) * 128);
-            OFX_REQUIRE(rows * ld_epi * 4 < lim, OFX_EINVAL);
-            for (long r0 = 0; r0 < Mtot; r0 += rows) {
-                ofx_conv_desc part = *d;
-                const long n = std::min(rows, Mtot - r0);
-                part.B = 1; part.Hin = part.Hout = 1; part.Win = part.Wout = (int)n;
-                part.in0 = d->in0 + r0 * d->ld0;
-                if (d->in1) part.in1 = d->in1 + r0 * d->ld1;
-                part.out = d->out + r0 * d->ldo;
-                if (d->res) part.res = d->res + r0 * d->ldres;
-                if (d->addend) part.addend = d->addend + r0 * d->ldadd;
-                const VolPool saved = tl_pool;
-                if (saved.on) tl_pool.out = saved.out + r0 * saved.slice1;
-                const int st = ofx_conv2d_alpha(&part, alpha, stream);
-                tl_pool = saved;
-                if (st) return st;
-            }
-            return 0;
-        }
+    const long M = (long)d->B * d->Hout * d->Wout, lim = (1L << 31) - 64;
+    if (x.pool.out) {
+        // Correlation volume in the blocked layout + pyramid level 1 from the accumulators (corr.hip decides when it applies:
+        // 128x128 tiles, h % 8 == 0 and w % 16 == 0 so that level 1 is tiled by whole blocks; any arithmetic)
+        OFX_REQUIRE(x.pool.wb0 > 0 && x.pool.wb1 > 0 && x.pool.slice1 > 0 && !x.stats_rows, OFX_EINVAL);
+        OFX_REQUIRE(d->epi == OFX_EPI_PLAIN && d->act == OFX_ACT_NONE && !d->res && !d->addend && !d->nmean && !d->scale && !d->shift && d->Cout % 128 == 0 && d->tile == 0, OFX_EINVAL);
     }
+    // The epilogue addresses out / res / addend / aux_* with 32-bit byte offsets (descriptor extent
+    // M * ld * 4).  A pure GEMM (1x1, stride 1, no padding, plain epilogue -- the correlation volume of a
+    // large frame is the case that gets here) is split along M; anything else must be sliced by the caller.
+    int ld_epi = std::max(d->Cout, d->out ? d->ldo : 0);
+    if (d->res) ld_epi = std::max(ld_epi, d->ldres);
+    if (d->addend) ld_epi = std::max(ld_epi, d->ldadd);
+    if (d->aux_h) ld_epi = std::max(ld_epi, d->ldh);
+    if (M * ld_epi * 4 >= lim) {
+        const bool gemm = d->KH == 1 && d->KW == 1 && d->stride == 1 && d->padH == 0 && d->padW == 0 &&
+                          d->epi == OFX_EPI_PLAIN && !d->nmean && d->Hout == d->Hin && d->Wout == d->Win;
+        OFX_REQUIRE(gemm, OFX_EINVAL);
+        *split_rows = std::max<long>(128, ((lim / ((long)ld_epi * 4)) / 128 - 1) * 128);
+        return *split_rows * ld_epi * 4 < lim ? 0 : OFX_EINVAL;
+    }
+    const long npix_in = (long)d->B * d->Hin * d->Win;
+    OFX_REQUIRE(M < (1L << 31) && npix_in < (1L << 31), OFX_EINVAL);
+    // 32-bit byte offsets through buffer descriptors: every operand extent must stay below 2 GiB
+    const long Kpad = ((long)d->KH * d->KW * (d->c0 + d->c1) + kKAlign - 1) / kKAlign * kKAlign;
+    const long ext0 = ((npix_in - 1) * d->ld0 + d->c0) * 4, ext1 = d->in1 ? ((npix_in - 1) * d->ld1 + d->c1) * 4 : 0;
+    OFX_REQUIRE(ext0 < lim && ext1 < lim && d->Cout * Kpad * 4 < lim, OFX_EINVAL);
+    OFX_REQUIRE(Kpad < 65536, OFX_EINVAL);                       // umulhi division is exact in this range
+    // a K chunk never straddles the two segments: not at c0 inside a tap, nor at the wrap from one tap's last channels (in1) to the
+    // next tap's first (in0) -- the general schedule picks one segment per chunk (issue: readfirstlane), so c1 must be whole chunks too
+    if (d->in1) OFX_REQUIRE(d->c0 % kKAlign == 0 && d->c1 % kKAlign == 0, OFX_EALIGN);
+    if (x.pool.out) OFX_REQUIRE(M * (long)x.pool.slice1 * 4 < lim, OFX_EINVAL);
+    switch (d->epi) {
+        case OFX_EPI_PLAIN: OFX_REQUIRE(d->out != nullptr && d->ldo >= d->Cout && (!d->res || d->ldres >= d->Cout), OFX_EINVAL); break;
+        case OFX_EPI_GRU_ZR: OFX_REQUIRE(d->aux_z && d->aux_rh && d->aux_h && d->Cout % 2 == 0 && d->ldh >= d->Cout / 2, OFX_EINVAL); break;
+        case OFX_EPI_GRU_Q: OFX_REQUIRE(d->aux_z && d->aux_h && d->ldh >= d->Cout, OFX_EINVAL); break;
+        case OFX_EPI_FLOW: OFX_REQUIRE(d->aux_coords && d->aux_h && d->aux_flow4 && d->Cout == 2, OFX_EINVAL); break;
+        default: return OFX_EINVAL;
+    }
+    return 0;
+}
 
+// The kernel's argument block of a validated descriptor under a plan
+ConvK conv_args(const ofx_conv_desc* d, const ConvExtra& x, const ConvPlan& p) {
+    const int nz = d->nz > 1 ? d->nz : 1;
     ConvK k;
     k.in0 = d->in0; k.in1 = d->in1; k.w = d->w; k.scale = d->scale; k.shift = d->shift; k.addend = d->addend;
     k.out = d->out; k.res = d->res; k.nmean = d->nmean; k.nrstd = d->nrstd;
@@ -1346,300 +1583,99 @@ extern "C" int ofx_conv2d_alpha(const ofx_conv_desc* d, float alpha, void* strea
     k.ld0 = d->ld0; k.c0 = d->c0; k.ld1 = d->ld1; k.c1 = d->c1; k.cin = d->c0 + d->c1;
     k.ldo = d->ldo; k.ldres = d->ldres; k.ldh = d->ldh; k.ldadd = d->ldadd;
     k.Hin = d->Hin; k.Win = d->Win; k.Hout = d->Hout; k.Wout = d->Wout; k.Cout = d->Cout;
-    k.KW = d->KW; k.stride = d->stride; k.padH = d->padH; k.padW = d->padW;
-    k.K = d->KH * d->KW * k.cin;
-    k.Kpad = ((k.K + kKAlign - 1) / kKAlign) * kKAlign;
-    const long M = (long)d->B * d->Hout * d->Wout;
-    OFX_REQUIRE(M < (1L << 31) && (long)d->B * d->Hin * d->Win < (1L << 31), OFX_EINVAL);
-    k.M = (int)M;
-    k.act = d->act;
-    k.alpha = alpha;
+    k.KH = d->KH; k.KW = d->KW; k.stride = d->stride; k.padH = d->padH; k.padW = d->padW;
+    k.K = d->KH * d->KW * k.cin; k.Kpad = ((k.K + kKAlign - 1) / kKAlign) * kKAlign; k.M = d->B * d->Hout * d->Wout;
+    k.act = d->act; k.alpha = x.alpha;
     auto magic = [](int dv) -> unsigned { return dv <= 1 ? 0u : (unsigned)(((1ull << 32) + dv - 1) / dv); };
-    k.magic_cin = magic(k.cin);
-    k.magic_kw = magic(d->KW);
-    k.kw1_mask = d->KW == 1 ? 0xFFFFFFFFu : 0u;
-    // 32-bit byte offsets through buffer descriptors: every operand extent must stay below 2 GiB
+    k.magic_cin = magic(k.cin); k.magic_kw = magic(d->KW); k.kw1_mask = d->KW == 1 ? 0xFFFFFFFFu : 0u;
     const long npix_in = (long)d->B * d->Hin * d->Win;
-    const long ext0 = ((npix_in - 1) * d->ld0 + d->c0) * 4, ext1 = d->in1 ? ((npix_in - 1) * d->ld1 + d->c1) * 4 : 0;
-    const long extw = (long)d->Cout * k.Kpad * 4;
-    OFX_REQUIRE(ext0 < (1L << 31) - 64 && ext1 < (1L << 31) - 64 && extw < (1L << 31) - 64, OFX_EINVAL);
-    OFX_REQUIRE(k.Kpad < 65536, OFX_EINVAL);                       // umulhi division is exact in this range
-    // a K chunk never straddles the two segments: not at c0 inside a tap, nor at the wrap from one tap's last channels (in1) to the
-    // next tap's first (in0) -- the general schedule picks one segment per chunk (issue: readfirstlane), so c1 must be whole chunks too
-    if (d->in1) OFX_REQUIRE(d->c0 % kKAlign == 0 && d->c1 % kKAlign == 0, OFX_EALIGN);
-    k.bytes0 = (int)ext0; k.bytes1 = (int)ext1; k.bytesw = (int)extw;
-    k.pool_out = tl_pool.on ? tl_pool.out : nullptr; k.pool_zs = tl_pool.zs; k.pool_wb0 = tl_pool.wb0; k.pool_wb1 = tl_pool.wb1;
-    k.pool_slice1 = tl_pool.slice1;
-    if (tl_pool.on) OFX_REQUIRE(M * (long)tl_pool.slice1 * 4 < (1L << 31) - 64, OFX_EINVAL);
+    k.bytes0 = (int)(((npix_in - 1) * d->ld0 + d->c0) * 4);
+    k.bytes1 = d->in1 ? (int)(((npix_in - 1) * d->ld1 + d->c1) * 4) : 0;
+    k.bytesw = (int)((long)d->Cout * k.Kpad * 4);
+    k.pool_out = x.pool.out; k.pool_zs = x.pool.zs; k.pool_wb0 = x.pool.wb0; k.pool_wb1 = x.pool.wb1; k.pool_slice1 = x.pool.slice1;
+    k.mtiles = p.mtiles; k.ntiles = p.ntiles; k.group_m = p.group_m;
+    k.ksplit = p.ksplit;                                     // caller scratch: 64 KiB of arrival counters, then the partial tiles
+    k.sk_count = p.ksplit > 1 ? (int*)d->splitk_ws : nullptr;
+    k.sk_part = p.ksplit > 1 ? (float*)((char*)d->splitk_ws + 65536) : nullptr;
+    k.uk = p.mode == 1; k.patch = p.mode == 2;
+    k.stats = p.stats_rows ? x.stats_part : nullptr;
+    return k;
+}
 
-    switch (d->epi) {
-        case OFX_EPI_PLAIN:
-            OFX_REQUIRE(d->out != nullptr && d->ldo >= d->Cout, OFX_EINVAL);
-            if (d->res) OFX_REQUIRE(d->ldres >= d->Cout, OFX_EINVAL);
-            break;
-        case OFX_EPI_GRU_ZR:
-            OFX_REQUIRE(d->aux_z && d->aux_rh && d->aux_h && d->Cout % 2 == 0 && d->ldh >= d->Cout / 2, OFX_EINVAL);
-            break;
-        case OFX_EPI_GRU_Q:
-            OFX_REQUIRE(d->aux_z && d->aux_h && d->ldh >= d->Cout, OFX_EINVAL);
-            break;
-        case OFX_EPI_FLOW:
-            OFX_REQUIRE(d->aux_coords && d->aux_h && d->aux_flow4 && d->Cout == 2, OFX_EINVAL);
-            break;
-        default: return OFX_EINVAL;
-    }
+}  // namespace
 
-    // ---- fused Winograd (conv_wino.hip): F(2x2,3x3) for the update block's and the encoders' stride-1 3x3 layers (4 instead of 9
-    // multiplies per output; residual merge, fused instance norm and epilogue statistics included) and F(4,5) for the SepConvGRU's
-    // 1x5 / 5x1 layers (2 instead of 5, GRU gate epilogues included).  Only on grids that fill the chip (ofx_conv_wino_pays):
-    // smaller grids, the single pair among them, keep the direct kernels and their small-grid schedules.
-    {
-        static const bool no_wino = getenv("OFX_CONV_NO_WINOGRAD") != nullptr;
-        static const bool no_wino15 = no_wino || getenv("OFX_CONV_NO_WINOGRAD15") != nullptr;
-        const bool force = d->tile == OFX_CONV_TILE_WINOGRAD;
-        const bool one_d = (d->KH == 1 && d->KW == 5) || (d->KH == 5 && d->KW == 1);
-        if (force || (d->tile == 0 && !(one_d ? no_wino15 : no_wino) && d->wino_w)) {
-            // asked for statistics: only where the fused kernel leaves them (one row per 8x16 patch), in the caller's room
-            const int srows = tl_stats.on ? ofx_conv_wino_stats_rows(d) : 0;
-            const bool stats_ok = !tl_stats.on || (srows > 0 && (size_t)d->B * srows * d->Cout * 2 <= tl_stats.cap_floats);
-            const bool fits = nz == 1 && stats_ok && !tl_pool.on && ofx_conv_wino_fits(d);
-            if (force && !fits) return OFX_EINVAL;
-            if (fits && (force || ofx_conv_wino_pays(d))) {
-                OfxProfScope prof(d->epi == OFX_EPI_GRU_ZR ? "igemm_conv_gru_zr" : d->epi == OFX_EPI_GRU_Q ? "igemm_conv_gru_q" : "igemm_conv",
-                                  (hipStream_t)stream);   // the convolution families of the per-layer profile
-                prof.flops(ofx_conv_wino_flops(d));
-                if (tl_stats.on) tl_stats.rows_per_image = srows;
-                return ofx_conv_wino_launch(d, alpha, tl_stats.on ? tl_stats.part : nullptr, (hipStream_t)stream);
-            }
+// The one entry of the convolution launcher (ofx_internal.h): validate -> run in parts or plan -> fill the arguments -> launch.
+int ofx_conv2d_ex(const ofx_conv_desc* d, const ConvExtra* extra, hipStream_t s) {
+    const ConvExtra x = extra ? *extra : ConvExtra{};
+    if (x.stats_rows) *x.stats_rows = 0;
+    if (x.stop_taken) *x.stop_taken = false;
+    long split_rows = 0;
+    int st = conv_validate(d, x, &split_rows);
+    if (st) return st;
+    if (split_rows) {   // a pure GEMM beyond 2 GiB: row ranges of the same problem, the stop event on the last; no statistics
+        const long Mtot = (long)d->B * d->Hout * d->Wout;
+        for (long r0 = 0; r0 < Mtot && !st; r0 += split_rows) {
+            ofx_conv_desc part = *d;
+            const long n = std::min(split_rows, Mtot - r0);
+            part.B = 1; part.Hin = part.Hout = 1; part.Win = part.Wout = (int)n;
+            part.in0 = d->in0 + r0 * d->ld0;
+            if (d->in1) part.in1 = d->in1 + r0 * d->ld1;
+            part.out = d->out + r0 * d->ldo;
+            if (d->res) part.res = d->res + r0 * d->ldres;
+            if (d->addend) part.addend = d->addend + r0 * d->ldadd;
+            ConvExtra px;
+            px.alpha = x.alpha;
+            px.pool = x.pool;
+            if (x.pool.out) px.pool.out = x.pool.out + r0 * x.pool.slice1;
+            if (r0 + split_rows >= Mtot) { px.stop_event = x.stop_event; px.stop_taken = x.stop_taken; }
+            st = ofx_conv2d_ex(&part, &px, s);
         }
+        return st;
     }
-
-    // ---- tile selection
-    int bm, bn;
-    if (d->tile) {
-        bm = (d->tile % 1000000) / 1000;
-        bn = d->tile % 1000;
+    ConvPlan p;
+    if ((st = conv_plan(d, x, conv_knobs(), &p))) return st;
+    OfxProfScope prof(p.name, s);
+    prof.flops(p.flops);
+    if (p.path != kPathIgemm) {
+        st = ofx_conv_wino_launch(d, x.alpha, x.stats_rows ? x.stats_part : nullptr, s, x.stop_event);
     } else {
-        auto waste = [&](int t) { return (double)(((d->Cout + t - 1) / t) * t) / d->Cout; };
-        if (d->Cout <= 32) bn = 32;
-        else if (waste(128) <= 1.13 && !(waste(192) <= 1.0 && waste(128) > 1.05 && d->precision == OFX_PREC_FP32 && !d->nmean && d->epi == OFX_EPI_PLAIN)) bn = 128;   // (576 channels: 3 x 192, not 4.5 x 128)
-        else if (waste(192) <= 1.05 && d->precision == OFX_PREC_FP32 && !d->nmean && d->epi != OFX_EPI_FLOW) bn = 192;   // 192-channel layers: one 128x192 tile instead of 128x64 x 3
-        else if (waste(96) <= 1.05 && d->precision == OFX_PREC_FP32 && d->epi == OFX_EPI_PLAIN) bn = 96;   // 96-channel encoder stage
-        else if (waste(64) <= 1.13) bn = 64;
-        else if (waste(32) < waste(64) - 0.1) bn = 32;
-        else bn = 64;
-        bm = 128;
-        // Grids that do not fill the chip (B = 1 ... ~16 frames at 512x768).  Measured over every layer shape of the network at
-        // B = 1, 2, 4, 8, 16, 32 (tools/small_batch_tune.py, profiles/r05_small_batch_tune.txt): a 128-row tile keeps its rate down
-        // to THREE workgroups per CU (768 on this part) and loses to the next smaller tile below that -- so take the largest tile
-        // whose grid still has 768 workgroups: 128x192 -> 128x96 -> 128x64 for the 192-channel layer, 128x128 -> 128x64 for the
-        // 128- / 256-channel ones, and only then the 64x64 small-grid tile (with split-K / paired pipelines below).  The old rule
-        // (64x64 below 1024 blocks of the 128-row tile) gave up 8-16 % per layer at B = 4 ... 16.
-        const long mt128 = (M + 127) / 128;
-        auto blocks_of = [&](int t) { return mt128 * ((d->Cout + t - 1) / t) * nz; };
-        static const bool old_small = getenv("OFX_CONV_OLD_SMALL_TILES") != nullptr;      // A/B switch: the round-4 rule
-        constexpr long kFill = 768;                  // three workgroups per CU
-        const long blocks128 = blocks_of(bn);
-        if (old_small) {
-            if (bn == 96 && blocks128 < 1024) bn = 32;
-            if (bn >= 64 && blocks128 < 1024) bm = 64;
-            if (bm == 64 && bn >= 128) bn = 64;
-        } else if (bn >= 64 && blocks128 < kFill) {
-            if (bn == 192 && d->epi == OFX_EPI_PLAIN && blocks_of(96) >= kFill) bn = 96;
-            else if (bn >= 128 && blocks_of(64) >= kFill) bn = 64;
-            else if (bn == 96) bn = 32;              // no small-grid variant of the 96-wide tile
-            else { bm = 64; bn = 64; }               // 64x64: the chip is filled by splitting K instead (below)
-        }
+        const bool pool = x.pool.out != nullptr;
+        st = kTiles[p.inst].launch(conv_args(d, x, p), pool ? kEpiVolPool : d->epi, !pool && d->nmean != nullptr, d->nz > 1 ? d->nz : 1, s, x.stop_event);
     }
-    k.mtiles = (int)((M + bm - 1) / bm);
-    k.ntiles = (d->Cout + bn - 1) / bn;
-    k.group_m = k.ntiles >= 8 ? 8 : 1;
-    // split-K (fp32, 64x64 tiles, single z): a grid of a few hundred tiles leaves a 256-CU part with a half-empty
-    // second round (384 tiles = 1.5 per CU: the makespan is 2 tiles); S splits make 384*S shorter work items that
-    // balance.  Needs caller scratch: 64 KiB of counters + tiles * S * 64*64 floats.
-    k.ksplit = 1; k.sk_part = nullptr; k.sk_count = nullptr;
-    static const bool dbg_no_sk = getenv("OFX_NO_SPLITK") != nullptr;
-    if (!dbg_no_sk && d->splitk_ws && d->precision == OFX_PREC_FP32 && bm == 64 && bn == 64 && nz == 1 && d->tile == 0) {
-        const long tiles = (long)k.mtiles * k.ntiles;
-        const int nk32 = (int)(k.Kpad / 32);
-        // work per CU in tile units if the tiles are cut S ways: ceil(tiles * S / 256) / S -- take the S that
-        // minimises it (ties: fewer splits), with at least six 32-wide chunks per split
-        int S = 1;
-        // (tiles up to 2048: with five workgroups per CU resident, `convc2` of four frames -- 1152 tiles = 4.5 per CU -- runs as
-        // 2304 half-K workgroups: 24.15 -> 23.98 ms per four frames; the scratch bound below still applies.  OFX_SK_MAX_TILES overrides)
-        static const char* skt_env = getenv("OFX_SK_MAX_TILES");
-        const long sk_max_tiles = skt_env ? atol(skt_env) : 2048;
-        if (tiles <= sk_max_tiles && nk32 >= 12) {
-            const double base = (double)((tiles + 255) / 256);
-            double best = base;
-            for (int c = 2; c <= 4; ++c) {
-                if (nk32 / c < 6) break;
-                const double span = (double)((tiles * c + 255) / 256) / c;
-                // a split must buy more balance than its seam costs: 4 % of the unsplit span per split (round 6: 960 tiles cut four
-                // ways for a nominal 4 -> 3.75 ran 7 % SLOWER than unsplit -- `conv` / GRU q of five frames; 1152 tiles cut in two
-                // for 5 -> 4.5 gained 3 %; the single pair's layers gain 25-37 %)
-                if (span < best - 1e-9 && span < base * (1.0 - 0.04 * c) + 1e-9) { best = span; S = c; }
-            }
-        }
-        const size_t need = 65536 + (size_t)tiles * S * 64 * 64 * sizeof(float);
-        if (S > 1 && tiles * sizeof(int) <= 65536 && need <= d->splitk_ws_bytes && ofx_aligned16(d->splitk_ws)) {
-            k.ksplit = S;
-            k.sk_count = (int*)d->splitk_ws;
-            k.sk_part = (float*)((char*)d->splitk_ws + 65536);
-        }
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const bool norm = d->nmean != nullptr;
-    const char* pname = nz > 1 ? "igemm_corr_volume"
-                       : d->epi == OFX_EPI_GRU_ZR ? "igemm_conv_gru_zr"
-                       : d->epi == OFX_EPI_GRU_Q  ? "igemm_conv_gru_q"
-                       : d->epi == OFX_EPI_FLOW   ? "igemm_conv_flow"
-                                                  : "igemm_conv";
-    OfxProfScope prof(pname, s);
-    prof.flops(2.0 * (double)M * d->Cout * k.K * nz);
-    // BK = 16 keeps LDS at 40 KB and registers under 128 for the 128x128 tile -> 4 workgroups per CU (3 for 128x192); the
-    // extra resident wave per SIMD hides the commit/barrier/issue phases better than a longer chunk does
-    // (measured +4..10 % on every shape).  The 64x64 tile is only chosen for grids that under-fill the
-    // machine (one workgroup per CU or fewer): there each chunk's load latency is exposed and the longer
-    // chunk wins (+8..20 % at one 512x768 pair).  tile = BK*1e6 + BM*1e3 + BN overrides.
-    const int tile_bk = (d->tile % 1000000000) / 1000000;
-    const int bk = tile_bk ? tile_bk : ((bn == 32 || bm == 64) ? 32 : 16);
-    // uniform-K fast path: every chunk of this launch's BK inside one tap and one segment (the 16-float flow rows of convf1 qualify
-    // with BK = 16; a caller-forced tile keeps the conservative multiple-of-32 rule)
-    static const bool no_uk = getenv("OFX_CONV_NO_UK") != nullptr;
-    // (`bk` is the BK of the fp32 tile launched below; the split-bf16 remap further down changes tiles, but launch_tile takes the
-    // scalar-coordinate schedule for PREC == 0 only, so `uk` is never read for a tile it was not derived from)
-    const int ukm = d->tile ? 32 : bk;
-    k.uk = (!no_uk && d->precision == OFX_PREC_FP32 && k.cin % ukm == 0 && (d->c1 == 0 || d->c0 % ukm == 0)) ? 1 : 0;
-    // halo-patch kernel: stride-1 3x3 / 1x5 / 5x1, "same" padding, the map a whole number of 8x16 patches, whole 16-channel slabs
-    static const bool no_patch = getenv("OFX_CONV_NO_PATCH") != nullptr;
-    const bool shape_ok = (d->KH == 3 && d->KW == 3) || (d->KH == 1 && d->KW == 5) || (d->KH == 5 && d->KW == 1);
-    k.KH = d->KH;
-    const bool big = (bm == 128 || (bm == 256 && bn == 64)) && bk == 16, small = bm == 64 && bn == 64 && bk == 32;   // 8x16 (16x16) patches / 8x8 patches (small grids, split-K)
-    const int pw = big ? 16 : 8, ph = bm == 256 ? 16 : 8;
-    // the 128-row tiles also take maps that are not whole patches (the last patch of a row / column hangs over: its outside
-    // pixels stage zeros and are masked in the epilogue); the small tile, whose grid feeds the split-K choice above, does not
-    const bool whole = d->Hin % ph == 0 && d->Win % pw == 0;
-    // ... as long as the overhang is cheap: the rows of a patch outside the map are multiplied like any others (a 68 x 120 map --
-    // 544x960 frames -- is 9 x 8 patches = 72 x 128 pixels: 1.13x the work).  Beyond a cover of OFX_PATCH_MAX_WASTE (default 1.09) a
-    // layer takes the scalar-coordinate / general kernels, which compute no row twice.  Measured, 16 frames, whole forward
-    // (tools/odd_sizes.py, patch kernel -> general kernels): cover 1.07 (720x1280) 218 -> 227 ms, 1.13 (544x960) 137 -> 117,
-    // 1.19 (600x800) 133 -> 117, 1.32 (776x520) 122 -> 107: the crossover sits near 1.09
-    static const char* waste_env = getenv("OFX_PATCH_MAX_WASTE");
-    static const double max_waste = waste_env ? atof(waste_env) : 1.09;
-    const double patch_waste = (double)(((d->Hin + ph - 1) / ph) * ph) * (double)(((d->Win + pw - 1) / pw) * pw) / ((double)d->Hin * d->Win);
-    const bool no_patch_here = no_patch || (!whole && d->tile == 0 && patch_waste > max_waste);   // (a forced tile keeps the patch kernel: the tests' way in)
-    k.patch = (!no_patch_here && d->precision == OFX_PREC_FP32 && shape_ok && d->stride == 1 && d->padH == d->KH / 2 && d->padW == d->KW / 2 &&
-               d->Hin == d->Hout && d->Win == d->Wout && (whole || big) && k.cin % bk == 0 &&
-               (d->c1 == 0 || d->c0 % bk == 0) && (!d->nmean || d->c1 == 0) && nz == 1 && (big || small) &&
-               (bn == 64 || bn == 96 || bn == 128 || bn == 192) && d->epi != OFX_EPI_FLOW)
-                  ? 1 : 0;
-    static const bool old_p256 = getenv("OFX_CONV_OLD_SMALL_TILES") != nullptr;
-    if (k.patch && bm == 128 && bn == 64 && d->tile == 0 && d->Hin % 16 == 0 && d->Win % 16 == 0 && M / 256 >= (old_p256 ? 4096 : 768)) {
-        // 64-channel layers: 16x16 patches (256x64 tile, 64x64 per wave) halve the weight staging per MFMA: 136 -> 139-143 TF on
-        // large grids, and ahead of the 128x64 tile from three workgroups per CU on (round 5 sweep: 110 vs 133 us at 768
-        // workgroups, 217 vs 232 at 1536; round 4 switched at 4096)
-        bm = 256;
-        k.mtiles = (int)(M / 256);
-    } else
-    if (k.patch && !whole) k.mtiles = d->B * ((d->Hin + ph - 1) / ph) * ((d->Win + 15) / 16);
-    // statistics from the accumulators (ofx_conv2d_stats): raw outputs only, tiles that stay inside one image.  Called once the tile
-    // of the launch is final (the split-bf16 modes remap it below).
-    k.stats = nullptr;
-    auto setup_stats = [&](int tbm, int tbn) {
-        k.stats = nullptr;
-        if (!tl_stats.on) return;
-        tl_stats.rows_per_image = 0;
-        const int waves_m = (tbm == 256 && tbn == 64) ? 4 : (tbm == 128 && (tbn == 128 || tbn == 64 || tbn == 192)) ? 2 : (tbm == 128 && (tbn == 96 || tbn == 32)) ? 4
-                            : (tbm == 64 && tbn == 64) ? 2 : 0;
-        const long hw = (long)d->Hout * d->Wout;
-        const bool ok = waves_m && d->epi == OFX_EPI_PLAIN && d->act == OFX_ACT_NONE && !d->res && nz == 1 &&
-                        k.mtiles % d->B == 0 && (k.patch || hw % tbm == 0);
-        const long rows = ok ? (long)(k.mtiles / d->B) * waves_m : 0;
-        if (ok && (size_t)d->B * rows * d->Cout * 2 <= tl_stats.cap_floats) {
-            k.stats = tl_stats.part;
-            tl_stats.rows_per_image = (int)rows;
-        }
-    };
-    if (d->precision == OFX_PREC_FP32) setup_stats(bm, bn);
-#ifdef OFX_CONV_LEAN   // experiment builds (tools/build_variant.sh): fp32 only -- a third of the instantiations, a third of the compile time
-    if (d->precision != OFX_PREC_FP32) return OFX_EINVAL;
-#else
-    if (d->precision != OFX_PREC_FP32) {
-        // split-bf16 matrix-core path (opt-in): three tiles; every other choice is mapped onto them (the ragged
-        // N of a 96- or 2-channel layer is zero-filled by the descriptors)
-        if (bm == 64) bn = 64;
-        else if (bn != 64) bn = 128;
-        k.ntiles = (d->Cout + bn - 1) / bn;
-        k.group_m = k.ntiles >= 8 ? 8 : 1;
-        // bf16x3 on the halo patch (128-row tiles, BK = 16): the fp32 -> (hi, lo) conversion of the A side then runs once per
-        // 16-channel slab instead of once per tap
-        const bool whole16 = d->Hin % 8 == 0 && d->Win % 16 == 0;
-        const double waste16 = (double)(((d->Hin + 7) / 8) * 8) * (double)(((d->Win + 15) / 16) * 16) / ((double)d->Hin * d->Win);
-        k.patch = (!no_patch && (whole16 || d->tile != 0 || waste16 <= max_waste) && shape_ok && d->stride == 1 && d->padH == d->KH / 2 && d->padW == d->KW / 2 && d->Hin == d->Hout &&
-                   d->Win == d->Wout && k.cin % 16 == 0 && (d->c1 == 0 || d->c0 % 16 == 0) && (!d->nmean || d->c1 == 0) && nz == 1 &&
-                   bm == 128 && tile_bk != 32 && d->epi != OFX_EPI_FLOW)
-                      ? 1 : 0;
-        k.mtiles = k.patch && !whole16 ? d->B * ((d->Hin + 7) / 8) * ((d->Win + 15) / 16) : (int)((M + bm - 1) / bm);
-        setup_stats(bm, bn);
-        if (tl_pool.on) {   // the blocked correlation volume with pyramid level 1 out of the accumulators, in the split arithmetic
-            k.mtiles = (int)((M + 127) / 128);
-            k.ntiles = (d->Cout + 127) / 128;
-            k.group_m = k.ntiles >= 8 ? 8 : 1;
-            k.ksplit = 1;
-            if (d->precision == OFX_PREC_BF16X6 || d->precision == OFX_PREC_BF16X6_W) return launch_tile<128, 128, 64, 64, 16, 3>(k, kEpiVolPool, false, nz, s);   // (its B operand is data, never pre-split)
-            if (d->precision == OFX_PREC_BF16X3_W) return launch_tile<128, 128, 64, 64, 16, 2>(k, kEpiVolPool, false, nz, s);
-            return launch_tile<128, 128, 64, 64, 16, 1>(k, kEpiVolPool, false, nz, s);
-        }
-        if (d->precision == OFX_PREC_BF16X6_W) {       // bf16x6 with the weights pre-split (ofx_split_conv_weight3)
-            if (bm == 128 && bn == 128) return launch_tile<128, 128, 64, 64, 16, 4>(k, d->epi, norm, nz, s);
-            if (bm == 128 && bn == 64) return launch_tile<128, 64, 64, 32, 16, 4>(k, d->epi, norm, nz, s);
-            if (bm == 64 && bn == 64) return launch_tile<64, 64, 32, 32, 16, 4>(k, d->epi, norm, nz, s);
-            return OFX_EINVAL;
-        }
-        if (d->precision == OFX_PREC_BF16X6) {
-            if (bm == 128 && bn == 128) return launch_tile<128, 128, 64, 64, 16, 3>(k, d->epi, norm, nz, s);
-            if (bm == 128 && bn == 64) return launch_tile<128, 64, 64, 32, 16, 3>(k, d->epi, norm, nz, s);
-            if (bm == 64 && bn == 64) return launch_tile<64, 64, 32, 32, 16, 3>(k, d->epi, norm, nz, s);
-            return OFX_EINVAL;
-        }
-        const bool wsplit = d->precision == OFX_PREC_BF16X3_W;
-        if (bm == 128 && bn == 128 && tile_bk == 32 && !wsplit) return launch_tile<128, 128, 64, 64, 32, 1>(k, d->epi, norm, nz, s);
-        if (bm == 128 && bn == 128) return wsplit ? launch_tile<128, 128, 64, 64, 16, 2>(k, d->epi, norm, nz, s) : launch_tile<128, 128, 64, 64, 16, 1>(k, d->epi, norm, nz, s);
-        if (bm == 128 && bn == 64) return wsplit ? launch_tile<128, 64, 64, 32, 16, 2>(k, d->epi, norm, nz, s) : launch_tile<128, 64, 64, 32, 16, 1>(k, d->epi, norm, nz, s);
-        if (bm == 64 && bn == 64) return wsplit ? launch_tile<64, 64, 32, 32, 16, 2>(k, d->epi, norm, nz, s) : launch_tile<64, 64, 32, 32, 16, 1>(k, d->epi, norm, nz, s);
-        return OFX_EINVAL;
-    }
-#endif
-    if (tl_pool.on) {
-        k.mtiles = (int)((M + 127) / 128);
-        k.ntiles = (d->Cout + 127) / 128;
-        k.group_m = k.ntiles >= 8 ? 8 : 1;
-        static const char* gm_env = getenv("OFX_VOL_GROUP_M");      // raster probe: M-tiles per group of the wide-N volume GEMM
-        if (gm_env && atoi(gm_env) > 0) k.group_m = atoi(gm_env);
-        k.ksplit = 1;
-        return launch_tile<128, 128, 64, 64, 16>(k, kEpiVolPool, false, nz, s);
-    }
-    if (bm == 256 && bn == 64) return launch_tile<256, 64, 64, 64, 16>(k, d->epi, norm, nz, s);
-    if (bm == 128 && bn == 192) return launch_tile<128, 192, 64, 96, 16>(k, d->epi, norm, nz, s);
-    if (bm == 128 && bn == 96) return launch_tile<128, 96, 32, 96, 16>(k, d->epi, norm, nz, s);
-    if (bm == 128 && bn == 128 && bk == 16) return launch_tile<128, 128, 64, 64, 16>(k, d->epi, norm, nz, s);
-    if (bm == 128 && bn == 64 && bk == 16) return launch_tile<128, 64, 64, 32, 16>(k, d->epi, norm, nz, s);
-    if (bm == 128 && bn == 128) return launch_tile<128, 128, 64, 64, 32>(k, d->epi, norm, nz, s);
-    if (bm == 128 && bn == 64) return launch_tile<128, 64, 64, 32, 32>(k, d->epi, norm, nz, s);
-    if (bm == 128 && bn == 32) return launch_tile<128, 32, 32, 32, 32>(k, d->epi, norm, nz, s);
-    if (bm == 64 && bn == 64 && bk == 16) return launch_tile<64, 64, 32, 32, 16>(k, d->epi, norm, nz, s);
-    // a grid of at most ~2 workgroups per CU is latency-bound: pair the pipelines (tile + 2e9 forces it, an explicit tile without that forbids it)
-    const long blocks = (long)k.mtiles * k.ntiles * nz;
-    if (k.ksplit > 1) return launch_tile<64, 64, 32, 32, 32, 0, 1, true>(k, d->epi, norm, nz, s);
-    // (round 5: up to 320 blocks, not 640 -- at 384 blocks, `convc1` on one 512x768 pair, the plain tile is ahead: 8.76 -> 8.62 ms per
-    // pair; OFX_CONV_PAIR_MAX=<blocks> overrides, 0 = never)
-    static const char* pair_env = getenv("OFX_CONV_PAIR_MAX");
-    const long pair_max = pair_env ? atol(pair_env) : 320;
-    const bool pair = d->tile >= 2000000000 || (d->tile < 1000000 && blocks <= pair_max && k.Kpad >= 8 * 32);
-    if (bm == 64 && bn == 64 && pair) return launch_tile<64, 64, 32, 32, 32, 0, 2>(k, d->epi, norm, nz, s);
-    if (bm == 64 && bn == 64) return launch_tile<64, 64, 32, 32, 32>(k, d->epi, norm, nz, s);
-    return OFX_EINVAL;
+    if (st) return st;
+    if (x.stats_rows) *x.stats_rows = p.stats_rows;
+    if (x.stop_taken) *x.stop_taken = x.stop_event != nullptr;
+    return 0;
+}
+
+extern "C" int ofx_conv2d(const ofx_conv_desc* d, void* stream) { return ofx_conv2d_ex(d, nullptr, (hipStream_t)stream); }
+
+// Instance-norm statistics from the accumulators: every wave of a tile writes the per-channel sum and sum of squares of its WM rows
+// ([B][rows_per_image][Cout][2] floats in `part`); a finalize kernel adds them per image in a fixed order.  Saves the statistics
+// pass over the tensor the convolution has just written.  *rows_per_image = 0: not produced (the caller falls back to ofx_inorm_stats).
+int ofx_conv2d_stats(const ofx_conv_desc* d, float* part, size_t part_floats, int* rows_per_image, void* stream) {
+    OFX_REQUIRE(rows_per_image != nullptr, OFX_EINVAL);
+    ConvExtra x;
+    x.stats_part = part; x.stats_cap = part_floats; x.stats_rows = rows_per_image;
+    return ofx_conv2d_ex(d, &x, (hipStream_t)stream);
+}
+
+// The plan ofx_conv2d (stats_cap_floats = 0) / ofx_conv2d_stats (its part_floats) / the volume GEMM with the fused level 1
+// (want_pool) would run `d` with: the launcher's own validation and conv_plan, no operand read, no HIP call.
+extern "C" int ofx_conv2d_plan(const ofx_conv_desc* d, size_t stats_cap_floats, int want_pool, ofx_conv_plan* out) {
+    OFX_REQUIRE(out != nullptr, OFX_EINVAL);
+    int rows = 0;
+    ConvExtra x;
+    if (stats_cap_floats) { x.stats_cap = stats_cap_floats; x.stats_rows = &rows; }
+    if (want_pool) { x.pool.out = reinterpret_cast<float*>(uintptr_t(16)); x.pool.wb0 = x.pool.wb1 = x.pool.slice1 = 1; }   // (never dereferenced)
+    long split_rows = 0;
+    int st = conv_validate(d, x, &split_rows);
+    if (!st && split_rows) st = OFX_EINVAL;   // run in parts: no single plan
+    ConvPlan p;
+    if (!st) st = conv_plan(d, x, conv_knobs(), &p);
+    if (st) return st;
+    *out = p;   // (its ofx_conv_plan part)
+    return 0;
 }
 
 namespace {

@@ -548,15 +548,15 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
     }
 }
 
-int launch3x3(const WinoK& k, dim3 grid, dim3 block, hipStream_t s) {
+int launch3x3(const WinoK& k, dim3 grid, dim3 block, hipStream_t s, hipEvent_t ev) {
     const int v = (k.nmean ? 4 : 0) | (k.res ? 2 : 0) | (k.stats ? 1 : 0);
     switch (v) {
-        case 0: OFX_LAUNCH((wino_conv_kernel<false, false, false>), grid, block, s, k); break;
-        case 1: OFX_LAUNCH((wino_conv_kernel<false, false, true>), grid, block, s, k); break;
-        case 2: OFX_LAUNCH((wino_conv_kernel<false, true, false>), grid, block, s, k); break;
-        case 4: OFX_LAUNCH((wino_conv_kernel<true, false, false>), grid, block, s, k); break;
-        case 5: OFX_LAUNCH((wino_conv_kernel<true, false, true>), grid, block, s, k); break;
-        case 6: OFX_LAUNCH((wino_conv_kernel<true, true, false>), grid, block, s, k); break;
+        case 0: OFX_LAUNCH((wino_conv_kernel<false, false, false>), grid, block, s, ev, k); break;
+        case 1: OFX_LAUNCH((wino_conv_kernel<false, false, true>), grid, block, s, ev, k); break;
+        case 2: OFX_LAUNCH((wino_conv_kernel<false, true, false>), grid, block, s, ev, k); break;
+        case 4: OFX_LAUNCH((wino_conv_kernel<true, false, false>), grid, block, s, ev, k); break;
+        case 5: OFX_LAUNCH((wino_conv_kernel<true, false, true>), grid, block, s, ev, k); break;
+        case 6: OFX_LAUNCH((wino_conv_kernel<true, true, false>), grid, block, s, ev, k); break;
         default: return OFX_EINVAL;   // statistics are of raw outputs: never with a residual merge
     }
     return ofx_launch_status();
@@ -633,11 +633,11 @@ __global__ __launch_bounds__(256, 2) void wino15_conv_kernel(const WinoK p) {
 }
 
 template <bool VERT>
-int launch15(const WinoK& k, int epi, dim3 grid, dim3 block, hipStream_t s) {
+int launch15(const WinoK& k, int epi, dim3 grid, dim3 block, hipStream_t s, hipEvent_t ev) {
     switch (epi) {
-        case OFX_EPI_PLAIN: OFX_LAUNCH((wino15_conv_kernel<VERT, OFX_EPI_PLAIN>), grid, block, s, k); break;
-        case OFX_EPI_GRU_ZR: OFX_LAUNCH((wino15_conv_kernel<VERT, OFX_EPI_GRU_ZR>), grid, block, s, k); break;
-        case OFX_EPI_GRU_Q: OFX_LAUNCH((wino15_conv_kernel<VERT, OFX_EPI_GRU_Q>), grid, block, s, k); break;
+        case OFX_EPI_PLAIN: OFX_LAUNCH((wino15_conv_kernel<VERT, OFX_EPI_PLAIN>), grid, block, s, ev, k); break;
+        case OFX_EPI_GRU_ZR: OFX_LAUNCH((wino15_conv_kernel<VERT, OFX_EPI_GRU_ZR>), grid, block, s, ev, k); break;
+        case OFX_EPI_GRU_Q: OFX_LAUNCH((wino15_conv_kernel<VERT, OFX_EPI_GRU_Q>), grid, block, s, ev, k); break;
         default: return OFX_EINVAL;
     }
     return ofx_launch_status();
@@ -691,9 +691,9 @@ double ofx_conv_wino_flops(const ofx_conv_desc* d) {
     return 2.0 * wino_points(d) * ((double)d->B * d->Hout * d->Wout / 4.0) * (double)(d->c0 + d->c1) * d->Cout;
 }
 
-// The caller has validated the descriptor (ofx_conv2d_alpha) and ofx_conv_wino_fits(d).  stats: null, or room for the partial
+// The caller has validated the descriptor (ofx_conv2d_ex) and ofx_conv_wino_fits(d).  stats: null, or room for the partial
 // sums of ofx_conv_wino_stats_rows(d) > 0 rows per image (the caller has checked the size).
-int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, float* stats, hipStream_t s) {
+int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, float* stats, hipStream_t s, hipEvent_t stop_event) {
     OFX_REQUIRE(!stats || ofx_conv_wino_stats_rows(d) > 0, OFX_EINVAL);
     WinoK k;
     k.in0 = d->in0; k.in1 = d->in1; k.u = d->wino_w; k.scale = d->scale; k.shift = d->shift; k.addend = d->addend; k.out = d->out;
@@ -717,8 +717,8 @@ int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, float* stats, hipS
     k.bytes0 = (int)ext0; k.bytes1 = (int)ext1; k.bytesu = (int)extu;
     k.alpha = alpha;
     const dim3 grid((unsigned)(k.mtiles * k.nblk), 1, 1), block(256, 1, 1);
-    if (is_3x3(d)) return launch3x3(k, grid, block, s);
-    return d->KH == 5 ? launch15<true>(k, d->epi, grid, block, s) : launch15<false>(k, d->epi, grid, block, s);
+    if (is_3x3(d)) return launch3x3(k, grid, block, s, stop_event);
+    return d->KH == 5 ? launch15<true>(k, d->epi, grid, block, s, stop_event) : launch15<false>(k, d->epi, grid, block, s, stop_event);
 }
 
 namespace {

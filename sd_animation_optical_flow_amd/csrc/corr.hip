@@ -719,11 +719,11 @@ int ofx_corr_volume(const float* f1, const float* f2, float* const* pyr, int B, 
         d.B = 1; d.Hin = h; d.Win = w; d.Hout = h; d.Wout = w; d.Cout = (int)Nb;
         d.KH = 1; d.KW = 1; d.stride = 1; d.padH = 0; d.padW = 0;
         d.act = OFX_ACT_NONE; d.epi = OFX_EPI_PLAIN;
-        if (fused)   // level 1 from the accumulators: level 0 is not read again
-            st = ofx_conv2d_volpool(&d, 1.0f / sqrtf((float)D), pyr[1], N * ofx_corr_slice_floats_l(h >> 1, w >> 1), (w + 7) >> 3,
-                                    ((w >> 1) + 7) >> 3, ofx_corr_slice_floats_l(h >> 1, w >> 1), stream);
-        else
-            st = ofx_conv2d_alpha(&d, 1.0f / sqrtf((float)D), stream);   // D = 256 -> exactly /16
+        ConvExtra x;
+        x.alpha = 1.0f / sqrtf((float)D);   // D = 256 -> exactly /16
+        const int slice1 = ofx_corr_slice_floats_l(h >> 1, w >> 1);
+        if (fused) x.pool = {pyr[1], N * slice1, (w + 7) >> 3, ((w >> 1) + 7) >> 3, slice1};   // level 1 from the accumulators: level 0 is not read again
+        st = ofx_conv2d_ex(&d, &x, s);
     }
     const hipError_t fe = hipFreeAsync(f2b, s);
     if (st) return st;

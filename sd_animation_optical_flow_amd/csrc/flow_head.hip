@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256, 2) void flow_head_kernel(const FlowHeadArgs a)
 }  // namespace
 
 int ofx_flow_head_launch(const float* x, int ldx, const float* w, int Kpad, const float* bias, float* coords1, float* hx_flow,
-                         int ldh, float* frows, int B, int h, int w_, hipStream_t s) {
+                         int ldh, float* frows, int B, int h, int w_, hipStream_t s, hipEvent_t stop_event) {
     FlowHeadArgs a;
     a.x = x; a.w = w; a.bias = bias; a.coords1 = coords1; a.hx_flow = hx_flow; a.frows = frows;
     a.ldx = ldx; a.ldh = ldh; a.Kpad = Kpad; a.h = h; a.w_ = w_;
@@ -175,11 +175,11 @@ int ofx_flow_head_launch(const float* x, int ldx, const float* w, int Kpad, cons
     if (strips <= 1024) {
         // a single pair has 192 strips: as four-wave workgroups they would sit on 48 of the 256 CUs, each wave waiting on its own 60
         // dependent-latency loads; one wave per workgroup spreads them over the chip (12.6 -> 11.1 us per launch on one 512x768 pair)
-        OFX_LAUNCH(flow_head_kernel, dim3((unsigned)strips), dim3(64), s, a);
+        OFX_LAUNCH(flow_head_kernel, dim3((unsigned)strips), dim3(64), s, stop_event, a);
         return ofx_launch_status();
     }
     const int blocks = (int)std::min<long>((strips + 3) / 4, 256L * 16);   // one strip per wavefront, grid-stride beyond 16 workgroups per CU
-    OFX_LAUNCH(flow_head_kernel, dim3(blocks), dim3(256), s, a);
+    OFX_LAUNCH(flow_head_kernel, dim3(blocks), dim3(256), s, stop_event, a);
     return ofx_launch_status();
 }
 

@@ -32,19 +32,17 @@ struct OfxProfScope {
     void flops(double f);   // executed FLOPs of the bracketed launch (reported by ofx_prof_collect)
 };
 
-// One-shot completion event for the NEXT convolution / flow-head launch of this thread: the launcher hands it to
-// hipExtLaunchKernelGGL as the kernel's own stop event, so the dependency edge to another stream rides on the dispatch packet's
-// completion signal instead of a marker packet behind it (hipEventRecord): the caller's stream does not stall on the marker.
-// The launcher that consumes it clears it; a caller that finds it still set after the call records the event the plain way.
-extern thread_local hipEvent_t ofx_tl_stop_event;
+// Stop event of a launch (`ev`, may be null): the launcher hands it to hipExtLaunchKernelGGL as the kernel's own stop event, so
+// the dependency edge to another stream rides on the dispatch packet's completion signal instead of a marker packet behind it
+// (hipEventRecord): the caller's stream does not stall on the marker.  A launcher that takes a `stop_event` gives it to the LAST
+// kernel it launches, so the event never fires before the call's work is done; a caller whose event was not taken (the call
+// failed, or reports so through ConvExtra::stop_taken) records it the plain way.
 #ifdef __HIPCC__
 #include <hip/hip_ext.h>
-#define OFX_LAUNCH(kern, grid, block, s, ...)                                                      \
+#define OFX_LAUNCH(kern, grid, block, s, ev, ...)                                                  \
     do {                                                                                           \
-        hipEvent_t ofx_ev_ = ofx_tl_stop_event;                                                    \
-        if (ofx_ev_) {                                                                             \
-            ofx_tl_stop_event = nullptr;                                                           \
-            hipExtLaunchKernelGGL(kern, grid, block, 0, s, nullptr, ofx_ev_, 0, __VA_ARGS__);      \
+        if (ev) {                                                                                  \
+            hipExtLaunchKernelGGL(kern, grid, block, 0, s, nullptr, ev, 0, __VA_ARGS__);           \
         } else {                                                                                   \
             hipLaunchKernelGGL(kern, grid, block, 0, s, __VA_ARGS__);                              \
         }                                                                                          \
@@ -56,17 +54,30 @@ static inline int ofx_launch_status() {
     return (int)e;
 }
 
-// conv.hip: ofx_conv2d with an extra scalar multiplier on the accumulator (out = act(acc*alpha*scale + shift))
-extern "C" int ofx_conv2d_alpha(const ofx_conv_desc* d, float alpha, void* stream);
+// conv.hip: what a convolution call takes and gives besides its descriptor.  Everything is explicit: nothing travels between a
+// caller and the launcher except through these fields.
+struct ConvExtra {
+    float alpha = 1.0f;              // extra scalar multiplier on the accumulator: out = act(acc * alpha * scale + shift)
+    // the blocked correlation volume GEMM that also writes pyramid level 1 from its accumulators (out != null asks for it):
+    // out = level 1, [nz][M][slice1] at zs floats per z; wb0 / wb1 = blocks per slice row of level 0 / 1
+    struct Pool { float* out = nullptr; long zs = 0; int wb0 = 0, wb1 = 0, slice1 = 0; } pool;
+    // instance-norm partial sums out of the epilogue (stats_rows != null asks for them): room for stats_cap floats in stats_part;
+    // *stats_rows = rows per image written there, 0 = not produced
+    float* stats_part = nullptr;
+    size_t stats_cap = 0;
+    int* stats_rows = nullptr;
+    hipEvent_t stop_event = nullptr;   // rides on the last kernel launch of the call (see OFX_LAUNCH)
+    bool* stop_taken = nullptr;        // optional out: a launch took stop_event (false: record it with hipEventRecord)
+};
+// The one entry of the convolution launcher; ofx_conv2d / ofx_conv2d_stats are ofx_conv2d_ex with the matching extras (null: none)
+int ofx_conv2d_ex(const ofx_conv_desc* d, const ConvExtra* extra, hipStream_t s);
 // conv_wino.hip: the fused Winograd paths of ofx_conv2d, F(2x2,3x3) for 3x3 and F(4,5) for 1x5 / 5x1 layers, picked from KH / KW
 // (shape test, whether the grid is large enough to take it, rows per image of its epilogue statistics, executed FLOPs, launch)
 bool ofx_conv_wino_fits(const ofx_conv_desc* d);
 bool ofx_conv_wino_pays(const ofx_conv_desc* d);
 int ofx_conv_wino_stats_rows(const ofx_conv_desc* d);
 double ofx_conv_wino_flops(const ofx_conv_desc* d);
-int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, float* stats, hipStream_t s);
-// conv.hip: the blocked correlation volume GEMM that also writes pyramid level 1 from its accumulators
-int ofx_conv2d_volpool(const ofx_conv_desc* d, float alpha, float* pool_out, long pool_zs, int wb0, int wb1, int slice1, void* stream);
+int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, float* stats, hipStream_t s, hipEvent_t stop_event);
 
 // net_misc.hip: the per-image reduction of ofx_conv2d_stats' partials (ofx.h, ofx_inorm_finalize) with an optional
 // gamma / beta (both or neither): an affine folded into the (mean, rstd) pair, (x - mean') * rstd' = (x - mu) * rs * gamma + beta
@@ -133,7 +144,7 @@ int ofx_init_state_warm(float* coords1, float* frows, float* hx, int ldh, int fl
                         int w, hipStream_t s);
 int ofx_coords_to_flow(const float* coords1, float* flow, int B, int h, int w, hipStream_t s);
 int ofx_flow_head_launch(const float* x, int ldx, const float* w, int Kpad, const float* bias, float* coords1, float* hx_flow,
-                         int ldh, float* frows, int B, int h, int w_, hipStream_t s);
+                         int ldh, float* frows, int B, int h, int w_, hipStream_t s, hipEvent_t stop_event = nullptr);
 int ofx_ctx_gather(const float* ctx, const int* idx_dev, float* hx, int ldh, int off2, int half, int B, long N, hipStream_t s);
 
 // ---- device helpers --------------------------------------------------------------------

@@ -377,12 +377,15 @@ struct Launcher {
     float* stats_part = nullptr;     // consumed by the next conv(): instance-norm partial sums out of its epilogue (conv.hip)
     size_t stats_floats = 0;
     int stats_rows = 0;              // set by that conv(): rows per image in stats_part, 0 = not produced
+    hipEvent_t stop_event = nullptr; // consumed by the next conv(): rides on its kernel's dispatch packet (Streams::arm_*)
+    bool stop_taken = false;         // set by that conv(): the kernel carries the event (false: take the plain edge)
     // generic conv launch; all pointer plumbing in one place
     void conv(const ConvW& c, const float* in0, int ld0, int c0, const float* in1, int ld1, int c1, float* out, int ldo,
               int B, int Hin, int Win, int stride, int act, int epi = OFX_EPI_PLAIN, const float* res = nullptr,
               int ldres = 0, const float* nmean = nullptr, const float* nrstd = nullptr, float* aux_z = nullptr,
               float* aux_rh = nullptr, float* aux_h = nullptr, int ldh = 0, float* aux_coords = nullptr,
               float* aux_flow4 = nullptr, int row_off = 0, int rows = 0) {
+        stop_taken = false;
         if (st) return;
         ofx_conv_desc d{};
         d.in0 = in0; d.ld0 = ld0; d.c0 = c0;
@@ -412,10 +415,12 @@ struct Launcher {
         d.wino_w = row_off == 0 && rows == 0 ? c.wino : nullptr;
         if (c0 + c1 != c.cin_pad) { st = OFX_EKEY; return; }
         ofx_prof_set_tag(c.name.c_str());
+        ConvExtra x;
+        x.stats_part = stats_part; x.stats_cap = stats_floats; x.stats_rows = stats_part ? &stats_rows : nullptr;
+        x.stop_event = stop_event; x.stop_taken = &stop_taken;
         stats_rows = 0;
-        if (stats_part) st = ofx_conv2d_stats(&d, stats_part, stats_floats, &stats_rows, s);
-        else st = ofx_conv2d(&d, s);
-        stats_part = nullptr;
+        st = ofx_conv2d_ex(&d, &x, s);
+        stats_part = nullptr; stop_event = nullptr;
         ofx_prof_set_tag(nullptr);
     }
 };
@@ -437,17 +442,13 @@ struct Streams {
         OFX_HIP_CHECK(hipStreamWaitEvent(main, r->ev_join[i], 0));
         return 0;
     }
-    // The same two edges with the event riding on a kernel's own dispatch packet (ofx_tl_stop_event, ofx_internal.h) instead of a
-    // marker packet behind it: arm_*() before the launch that ends the producing chain, *_armed() where fork() / join() would stand.
+    // The same two edges with the event riding on a kernel's own dispatch packet (OFX_LAUNCH, ofx_internal.h) instead of a marker
+    // packet behind it: arm_*() gives the event (or null) for the launch that ends the producing chain, *_armed() stands where
+    // fork() / join() would when that launch took it.
     // On a single 512x768 pair the marker of fork() held the caller's stream for ~7 us per iteration (profiles/r05_single_pair_gap_pairs.txt).
     static bool stop_events() { static const bool off = getenv("OFX_NO_STOP_EVENT") != nullptr; return !off; }
-    bool arm_fork() const { if (!on || !stop_events()) return false; ofx_tl_stop_event = r->ev_fork; return true; }
-    bool arm_join(int i) const { if (!on || !stop_events()) return false; ofx_tl_stop_event = r->ev_join[i]; return true; }
-    static bool taken() {   // did the launcher hand the armed event to its kernel?  (if not: disarm, the caller takes the plain edge)
-        const bool t = ofx_tl_stop_event == nullptr;
-        ofx_tl_stop_event = nullptr;
-        return t;
-    }
+    hipEvent_t arm_fork() const { return on && stop_events() ? r->ev_fork : nullptr; }
+    hipEvent_t arm_join(int i) const { return on && stop_events() ? r->ev_join[i] : nullptr; }
     int fork_armed(int i) const { OFX_HIP_CHECK(hipStreamWaitEvent(r->aux[i], r->ev_fork, 0)); return 0; }
     int join_armed(int i) const { OFX_HIP_CHECK(hipStreamWaitEvent(main, r->ev_join[i], 0)); return 0; }
 };
@@ -726,9 +727,9 @@ static int run_recurrence(ofx_raft* r, const RaftWs& ws, int B, int h, int w, in
         // flow features (update.py:93-94) on the side stream, from the flow the previous iteration left
         if ((L.st = fork_on_kernel ? S.fork_armed(0) : S.fork(0))) break;
         LF.conv(C("convf1"), ws.frows, FROW, FROW, nullptr, 0, 0, ws.f1, 128, B, h, w, 1, OFX_ACT_RELU);   // 7x1 over the flow rows
-        const bool join_armed = S.arm_join(0);
+        LF.stop_event = S.arm_join(0);
         LF.conv(C("convf2"), ws.f1, 128, 128, nullptr, 0, 0, ws.corflo + 192, 256, B, h, w, 1, OFX_ACT_RELU);
-        const bool join_on_kernel = join_armed && Streams::taken();
+        const bool join_on_kernel = LF.stop_taken;
         if ((L.st = LF.st)) break;
         // correlation features at the current estimate
         if (!alt) {
@@ -757,10 +758,10 @@ static int run_recurrence(ofx_raft* r, const RaftWs& ws, int B, int h, int w, in
         L.conv(C("fh1"), ws.hx, HX_LD, HD, nullptr, 0, 0, ws.c1, 256, B, h, w, 1, OFX_ACT_RELU);
         if (!L.st) {   // 256 -> 2 channels: dedicated reduction kernel instead of a 1/16-utilised GEMM tile
             const ConvW& f2 = C("fh2");
-            const bool fork_armed = it + 1 < iters && S.arm_fork();
+            const hipEvent_t fork_ev = it + 1 < iters ? S.arm_fork() : nullptr;
             L.st = ofx_flow_head_launch(ws.c1, 256, f2.w, (int)f2.kpad, f2.shift, ws.coords1, ws.hx + FLOW_OFF, HX_LD, ws.frows, B, h,
-                                        w, s);
-            fork_on_kernel = fork_armed && Streams::taken();
+                                        w, s, fork_ev);
+            fork_on_kernel = fork_ev && !L.st;   // the flow head has one launch: it took the event unless the call failed
         }
     }
     // mask head (update.py:122-125,135) on the final hidden state, then convex upsample
@@ -1052,10 +1053,10 @@ static int raft_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* 
         // of the GEMM's accumulators when it can (whole-block level 1): level 0 is then never read back
         const long slice1 = ofx_corr_slice_floats_l(h >> 1, w >> 1);
         const bool fused = ofx_corr_volpool_ok(h, w) && Nb % 128 == 0 && N * slice1 * 4 < (1L << 31) - 64;   // (every arithmetic since round 4)
-        if (fused)
-            st = ofx_conv2d_volpool(&d, 1.0f / std::sqrt((float)FD), ws.pyr[1], N * slice1, (w + 7) >> 3, ((w >> 1) + 7) >> 3, (int)slice1, s);
-        else
-            st = ofx_conv2d_alpha(&d, 1.0f / std::sqrt((float)FD), s);
+        ConvExtra x;
+        x.alpha = 1.0f / std::sqrt((float)FD);
+        if (fused) x.pool = {ws.pyr[1], N * slice1, (w + 7) >> 3, ((w >> 1) + 7) >> 3, (int)slice1};
+        st = ofx_conv2d_ex(&d, &x, s);
         if (!st) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused);
         if (st) return st;
     } else {
@@ -1200,11 +1201,10 @@ int ofx_raft_forward_pairs_warp(ofx_raft* r, const uint8_t* images, int n_images
         d.KH = 1; d.KW = 1; d.stride = 1;
         d.act = OFX_ACT_NONE; d.epi = OFX_EPI_PLAIN;
         d.precision = prec;
-        if (fused_pairs)
-            st = ofx_conv2d_volpool(&d, 1.0f / std::sqrt((float)FD), ws.pyr[1] + (long)b * N * slice1p, 0, (w + 7) >> 3, ((w >> 1) + 7) >> 3,
-                                    (int)slice1p, s);
-        else
-            st = ofx_conv2d_alpha(&d, 1.0f / std::sqrt((float)FD), s);
+        ConvExtra x;
+        x.alpha = 1.0f / std::sqrt((float)FD);
+        if (fused_pairs) x.pool = {ws.pyr[1] + (long)b * N * slice1p, 0, (w + 7) >> 3, ((w >> 1) + 7) >> 3, (int)slice1p};
+        st = ofx_conv2d_ex(&d, &x, s);
     }
     if (!st && !alt) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused_pairs || vplanes);
     if (st) return st;
@@ -1410,9 +1410,10 @@ int small_volume(const float* f1, long a_zs, const float* f2b, long w_zs, float*
     d.KH = 1; d.KW = 1; d.stride = 1;
     d.act = OFX_ACT_NONE; d.epi = OFX_EPI_PLAIN;
     *fused = ofx_corr_volpool_ok(h, w) && Nb % 128 == 0 && N * slice1 * 4 < (1L << 31) - 64;
-    const float alpha = 1.0f / std::sqrt((float)S_FD);
-    if (*fused) return ofx_conv2d_volpool(&d, alpha, l1, N * slice1, (w + 7) >> 3, ((w >> 1) + 7) >> 3, (int)slice1, s);
-    return ofx_conv2d_alpha(&d, alpha, s);
+    ConvExtra x;
+    x.alpha = 1.0f / std::sqrt((float)S_FD);
+    if (*fused) x.pool = {l1, N * slice1, (w + 7) >> 3, ((w >> 1) + 7) >> 3, (int)slice1};
+    return ofx_conv2d_ex(&d, &x, s);
 }
 
 // state init, `iters` refinement iterations of SmallUpdateBlock, upflow8 (with the warp of one shared frame for the first n_warp pairs)

@@ -56,7 +56,8 @@ EPS_NORM = 1e-5
 FIRST_ORDER_LIMIT = 2e-4
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# the launcher's rule, restated (conv.hip: the tile selection of ofx_conv2d_alpha, the halo-patch test and setup_stats)
+# the launcher's rule, restated (conv.hip: conv_plan -- tile selection, halo-patch test, statistics rows).  The library answers the
+# same question itself (ofx_conv2d_plan, include/ofx.h); tests/test_conv_plan_host.py holds the two against each other on the host.
 
 # tile code (tile = pair * 2e9 + BK * 1e6 + BM * 1e3 + BN) -> WM, the output rows of a tile one wave owns
 WAVE_ROWS = {(256, 64): 64, (128, 128): 64, (128, 64): 64, (128, 192): 64, (128, 96): 32, (128, 32): 32, (64, 64): 32}
@@ -123,7 +124,9 @@ def split_k(tiles, kpad):
 def plan(B, H, W, cin, cout, kh, kw, stride=1, tile=0, norm=False, precision="fp32", act=None, res=False, splitk=False):
     """What the direct-kernel launcher does with a single-segment plain-epilogue layer: the tile, the A-side schedule
     ('general', 'scalar' or 'patch'), the patch size, the K splits (`splitk`: a workspace of any size is offered) and the partial
-    rows per image ofx_conv2d_stats reports (0: none)."""
+    rows per image ofx_conv2d_stats reports (0: none).  An independent restatement: the authority is the launcher's own
+    answer, ofx_conv2d_plan (include/ofx.h), which tests/test_conv_plan_host.py compares this with field by field; `bk` is the
+    chunk length of the kernel that runs."""
     Ho, Wo = out_size(H, W, kh, kw, stride)
     M = B * Ho * Wo
     fp32 = precision == "fp32"
@@ -153,6 +156,8 @@ def plan(B, H, W, cin, cout, kh, kw, stride=1, tile=0, norm=False, precision="fp
         whole = H % 8 == 0 and W % 16 == 0
         cover = (_cdiv(H, 8) * 8) * (_cdiv(W, 16) * 16) / (H * W)
         patch = ((whole or tile != 0 or cover <= PATCH_MAX_WASTE) and shape_ok and same and cin % 16 == 0 and bm == 128 and tile_bk != 32)
+        # ... which exist with 16-wide chunks only, but for the 128x128 tile of the on-the-fly bf16x3 split (a forced BK = 32)
+        bk = 32 if (precision == "bf16x3" and (bm, bn) == (128, 128) and tile_bk == 32) else 16
     mt_img = _cdiv(H, ph) * _cdiv(W, pw) if patch else None
     waves_m = WAVES_M.get((bm, bn), 0)
     hw = Ho * Wo

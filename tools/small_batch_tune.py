@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Tile sweep of the update-block / encoder convolutions at SMALL batches (B = 1 ... 32 frames at 512x768): which tile each layer wants
 when the grid does not fill the chip.  Per (layer, B): the launcher's own choice (tile 0, with split-K scratch like the executor's)
-and every forced tile that applies.  Feeds the selection rule in conv.hip (`ofx_conv2d_alpha`, tile selection).
+and every forced tile that applies.  Feeds the selection rule in conv.hip (`conv_plan`, tile selection).
     python tools/small_batch_tune.py [B ...]"""
 import ctypes as C, os, sys
 import torch
