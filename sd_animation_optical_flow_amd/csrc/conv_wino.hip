@@ -217,9 +217,14 @@ __device__ __forceinline__ void wino_mfma4(f32x16& acc, const float4& a, const f
 // P transform points from ALG::pt0(wave) on and NT 32-channel blocks of u from ALG::blk0(nb, wave) on; and its input transform,
 // built from (Hs, Vs, tid, wave), whose call transforms the calling thread's (tile, channel pair) from the halo in Hs into Vs
 // ([point][tile][channel] at row stride kLDV).  The wave's point-wise products accumulate into acc, weights one slab ahead in
-// registers.  It shares the halo geometry, the patch remap and the operand order with wino3x3_slabs but spells its staging and
-// weight loads out: routed through HaloStage / WinoU the compiler schedules the 5x1 kernels 1.5-4 % slower
-// (profiles/r13_wino_rows_kernel_stats.txt), and this text compiles to the instructions the GRU layers were measured with.
+// registers: each fragment is reloaded straight behind the four MFMAs that consumed it and the scheduler is held to that
+// (sched_group_barrier, as in wino3x3_slabs), so a load has 60 MFMAs and the next slab's staging to arrive in.  Every halo issue
+// precedes the weight loads it shares the queue with (prologue: halo, then the fragments in the order of their use; loop: the
+// next halo ahead of the products), so the wait in front of the LDS store is a counted one that leaves the weights in flight.
+// The A operands are read two fragments (8 MFMAs) ahead.  tests/test_wino15_isa_schedule.py holds the compiled loop to this.
+// It shares the halo geometry, the patch remap and the operand order with wino3x3_slabs but spells its staging and weight loads
+// out: routed through HaloStage / WinoU the compiler scheduled the 5x1 kernels 1.5-4 % slower
+// (profiles/r13_wino_rows_kernel_stats.txt).
 template <class ALG>
 __device__ __forceinline__ void wino_slabs_staged(const WinoK& p, const Patch& pt, float* Hs, float* Vs, int tid, int wave,
                                            f32x16 (&acc)[ALG::P][ALG::NT]) {
@@ -264,15 +269,13 @@ __device__ __forceinline__ void wino_slabs_staged(const WinoK& p, const Patch& p
     const int wlane = lane * 16;
     const int pt0 = ALG::pt0(wave), blk0 = ALG::blk0(pt.nb, wave);
     float4 wr[P][NT][2];
-    auto w_issue = [&](int q, int cb) __attribute__((always_inline)) {
+    auto w_issue = [&](int q, int ks, int cb) __attribute__((always_inline)) {
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const int so = (((pt0 + q) * p.nb32 + blk0 + nt) * c8n + 2 * cb + ks) * 1024;   // scalar
-                v4i t = __builtin_amdgcn_raw_buffer_load_b128(rsu, wlane, so, 0);
-                wr[q][nt][ks] = *reinterpret_cast<float4*>(&t);
-            }
+        for (int nt = 0; nt < NT; ++nt) {
+            const int so = (((pt0 + q) * p.nb32 + blk0 + nt) * c8n + 2 * cb + ks) * 1024;   // scalar
+            v4i t = __builtin_amdgcn_raw_buffer_load_b128(rsu, wlane, so, 0);
+            wr[q][nt][ks] = *reinterpret_cast<float4*>(&t);
+        }
     };
 
 #pragma unroll
@@ -286,10 +289,21 @@ __device__ __forceinline__ void wino_slabs_staged(const WinoK& p, const Patch& p
     // A fragment: tile = lane & 31, channels 8 ks + 4 (lane >> 5) + 0..3 (the k order the weights are stored in)
     const float* const afrag = Vs + (pt0 * 32 + (lane & 31)) * kLDV + 4 * (lane >> 5);
 
+    auto a_read = [&](int i) __attribute__((always_inline)) {
+        return *reinterpret_cast<const float4*>(afrag + (i >> 1) * 32 * kLDV + 8 * (i & 1));
+    };
+
     const int CB = p.cin / kWBK;
     a_issue(0);
+    // the first slab's fragments in the order of their use, and kept in it: vmcnt retires in issue order, so a fragment that the
+    // scheduler moved behind its successors would be waited for together with all of them at every trip of the loop
 #pragma unroll
-    for (int q = 0; q < P; ++q) w_issue(q, 0);
+    for (int q = 0; q < P; ++q)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            w_issue(q, ks, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
     for (int cb = 0; cb < CB; ++cb) {
         const int nx = cb + 1 < CB ? cb + 1 : cb;   // the last slab re-issues itself: no branch, loads stay in bounds
 #pragma unroll
@@ -306,21 +320,30 @@ __device__ __forceinline__ void wino_slabs_staged(const WinoK& p, const Patch& p
         // ... and is issued ahead of them: left free, the scheduler sinks these loads below most of the MFMAs, and the next slab's
         // LDS store then waits for them (profiles/r09_wino_shared_ab.txt)
         __builtin_amdgcn_sched_barrier(0);
+        // fragment i = (point i / 2, 8-channel step i % 2); its A operand is read two fragments (8 MFMAs) ahead
+        float4 a[2 * P];
+        a[0] = a_read(0);
+        a[1] = a_read(1);
+        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
 #pragma unroll
-        for (int q = 0; q < P; ++q) {
+        for (int i = 0; i < 2 * P; ++i) {
+            const int q = i >> 1, ks = i & 1;
+            if (i + 2 < 2 * P) a[i + 2] = a_read(i + 2);
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const float4 a = *reinterpret_cast<const float4*>(afrag + q * 32 * kLDV + 8 * ks);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const float4 b = wr[q][nt][ks];
-                    acc[q][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[q][nt], 0, 0, 0);
-                    acc[q][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[q][nt], 0, 0, 0);
-                    acc[q][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc[q][nt], 0, 0, 0);
-                    acc[q][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc[q][nt], 0, 0, 0);
-                }
+            for (int nt = 0; nt < NT; ++nt) {
+                const float4 b = wr[q][nt][ks];
+                acc[q][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].x, b.x, acc[q][nt], 0, 0, 0);
+                acc[q][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, b.y, acc[q][nt], 0, 0, 0);
+                acc[q][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].z, b.z, acc[q][nt], 0, 0, 0);
+                acc[q][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, b.w, acc[q][nt], 0, 0, 0);
             }
-            w_issue(q, nx);   // this point's fragments for the next slab: the rest of the slab hides the load
+            // this fragment's reload for the next slab goes straight behind the MFMAs that consumed it, 60 MFMAs ahead of its next
+            // use, and stays there: left free, the scheduler sinks all sixteen reloads below the slab's last MFMAs and the next slab
+            // waits for them at its first (profiles/r19_wino15_prefetch_isa.txt)
+            w_issue(q, ks, nx);
+            if (i + 2 < 2 * P) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 4 * NT, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, NT, 0);
         }
     }
 }

@@ -12,6 +12,8 @@ distinct address on a busy bank within a group adds one cycle):
 
 usage: python tools/lds_bank_model.py            the report kept as profiles/r13_lds_bank_model.txt
        python tools/lds_bank_model.py --search   every conflict-free pixel-pair layout of the 3x3 halo, smallest first
+       python tools/lds_bank_model.py --wino15   the layouts of the F(4, 5) kernels' transformed tile, kept as
+                                                 profiles/r19_wino15_lds_bank_model.txt
 """
 import sys
 
@@ -123,7 +125,8 @@ def rows_3x3(t, at):
     t.add("operand reads of the halo (2 rows x 4 columns)", "ds_read_b128", rd)
 
 
-def staged_15(t, vert, ldv_at):
+def staged_15(t, vert, vs_at):
+    """vs_at(point, tile, channel) -> float index in Vs of a transformed value (channel a multiple of 2 or 4)"""
     W, H, ldh = (16, 12, 16) if vert else (20, 8, 20)
     at = lambda y, x: (y * W + x) * ldh
     t.add(f"halo staging ({H} x {W} pixels)", "ds_write_b128", stage_writes(at, W, H))
@@ -133,13 +136,51 @@ def staged_15(t, vert, ldv_at):
     for wave in range(4):
         for j in range(8):
             rd.append(lambda lane, wave=wave, j=j: base(wave * 8 + (lane >> 3)) * ldh + 2 * (lane & 7) + j * tap)
-            wr.append(lambda lane, wave=wave, j=j: ldv_at(j, wave * 8 + (lane >> 3)) + 2 * (lane & 7))
+            wr.append(lambda lane, wave=wave, j=j: vs_at(j, wave * 8 + (lane >> 3), 2 * (lane & 7)))
         for q in range(8):
             for ks in range(2):
-                fr.append(lambda lane, q=q, ks=ks: ldv_at(q, lane & 31) + 4 * (lane >> 5) + 8 * ks)
+                fr.append(lambda lane, q=q, ks=ks: vs_at(q, lane & 31, 4 * (lane >> 5) + 8 * ks))
     t.add("transform reads of the halo", "ds_read_b64", rd)
     t.add("transform writes of Vs", "ds_write_b64", wr)
     t.add("A fragments from Vs", "ds_read_b128", fr)
+
+
+def vs_rows(ldv, pts=None):
+    """[point][tile][channel] at row stride ldv, points pts floats apart (32 rows by default)"""
+    pts = 32 * ldv if pts is None else pts
+    return lambda q, tile, c: q * pts + tile * ldv + c
+
+
+def vs_swizzled(q, tile, c):
+    """tools/experiments/wino15_vs_swizzle.diff: rows of 16 floats, the row's four channel quads permuted by (tile / 4) % 4"""
+    return (q * 32 + tile) * 16 + 4 * ((c >> 2) ^ ((tile >> 2) & 3)) + (c & 3)
+
+
+def wino15():
+    print("# tools/lds_bank_model.py --wino15: LDS cycles of one workgroup and slab of the F(4, 5) kernels, by the layout of Vs")
+    tot = {}
+    for name, vs in (("row stride 20 (kLDV of csrc/conv_wino.hip)", vs_rows(20)),
+                     ("row stride 16, channel quad ^ (tile / 4) % 4 (tools/experiments/wino15_vs_swizzle.diff)", vs_swizzled)):
+        for vert, o in ((False, "1x5"), (True, "5x1")):
+            print(f"\n## F(4, 5) {o}: Vs at {name}")
+            t = Tally()
+            staged_15(t, vert, vs)
+            tot[name, o] = t.show()
+    print("\n## every plain row stride (a multiple of 4 floats, whole float4 reads) up to 80 KB of LDS, points 32 rows (+ pad) apart:")
+    print("## modelled conflict cycles of (Vs writes, A fragments), the same in both orientations")
+    best = None
+    for ldv in range(16, 68, 4):
+        for pad in range(0, 36, 4):
+            t = Tally()
+            staged_15(t, False, vs_rows(ldv, 32 * ldv + pad))
+            w, f = t.rows[2][4], t.rows[3][4]
+            if best is None or w + f < best[0]:
+                best = (w + f, ldv, pad)
+            if pad == 0:
+                print(f"  row stride {ldv:>2}: writes {w:>4}  fragments {f:>4}")
+    print(f"  the best plain layout: row stride {best[1]}, point pad {best[2]}: {best[0]} conflict cycles -- no plain stride serves both:")
+    print("  the ds_write_b64 wants two neighbouring tiles' 16 floats in disjoint halves of 32 banks (stride = 16 mod 32), the")
+    print("  ds_read_b128 wants 16 tiles' float4 in 16 different bank quads (stride = 4 mod 8, not 0 mod 16).  The swizzle gives both.")
 
 
 def plain(ldh, W=18):
@@ -164,6 +205,9 @@ def search():
 
 
 def main():
+    if "--wino15" in sys.argv:
+        wino15()
+        return
     if "--search" in sys.argv:
         print("# conflict-free pixel-pair layouts of the 10 x 18 halo (staging ds_write_b128 and operand ds_read_b128), smallest first")
         search()
@@ -184,7 +228,7 @@ def main():
     for vert, name in ((False, "1x5"), (True, "5x1")):
         print(f"\n## F(4, 5) {name}: transform through Vs at row stride 20")
         t = Tally()
-        staged_15(t, vert, lambda q, tile: (q * 32 + tile) * kLDV)
+        staged_15(t, vert, vs_rows(kLDV))
         t.show()
 
 
