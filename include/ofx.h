@@ -24,6 +24,8 @@
  *   ofx_layernorm, ofx_geglu, ofx_attention_bnhd_f32
  *                               ldm/modules/attention.py:54-56,326-436,456-469,515-537 (SpatialTransformer)
  *                               ofgen_keyframe_inpaint.py:113-133,237-248,306-322,676-688,968-973,995-1027
+ *   ofx_groupnorm_cat, ofx_emb_linear, ofx_timestep_embedding
+ *                               ldm/modules/diffusionmodules/openaimodel.py:220-226,257-277,530-534,757-793 ; util.py:154-174
  *
  * Layout conventions: images and flow are HWC ("channels-last"); network activations are
  * NHWC fp32; a flow field is f32[H,W,2] = (dx, dy) exactly as `algo.calc` returns it
@@ -209,6 +211,39 @@ int ofx_upsample2x_nearest_f32(const float* in, float* out, int B, int H, int W,
  * (clip(x, -1, 1) * 127.5 + 127.5) truncated toward zero, the product and the sum rounded separately in fp32 (numpy's bits).
  * x and out 4-byte aligned. */
 int ofx_decode_to_u8(const float* x, int ld, uint8_t* out, int B, int H, int W, void* stream);
+
+/* ---------------------------------------------------------------- UNet (ldm/modules/diffusionmodules/openaimodel.py:415-793) */
+/* GroupNorm over a channel concatenation with a per-image, per-channel term folded in: what `ResBlock._forward` needs twice
+ * (openaimodel.py:257-277).  `in_layers` of an output block normalises th.cat([h, hs.pop()], dim=1) (:786, groups straddle the
+ * seam: 1280 + 640 channels are 60 per group), `out_layers` normalises h + emb_out[b, c] (:275-276):
+ *   out[b][p][c] = act(GN_groups(cat(x0, x1)[b][p][:] + e[b][:])[c] * gamma[c] + beta[c]),   act = x * sigmoid(x) when silu
+ * x0 [B,HW,C0] with rows ld0 floats apart, x1 [B,HW,C1] with rows ld1 apart or NULL with C1 = 0, e [B][C0 + C1] with rows lde
+ * apart or NULL (a slice of one buffer that holds every emb projection is a valid operand), gamma / beta [C0 + C1] or NULL, out
+ * dense [B,HW,C0 + C1].  C0, C1, ld0, ld1 % 4 == 0 and x0, x1, e, out, scratch 16-byte aligned (OFX_EALIGN); (C0 + C1) % groups
+ * == 0, ld0 >= C0, ld1 >= C1, lde >= C0 + C1, B <= 65535 (OFX_EINVAL).  out may alias x0 only when C1 = 0 and ld0 = C0; any other
+ * overlap of out with x0 or x1 is OFX_EINVAL.  The three stages and the summation order of ofx_groupnorm (per-channel f64 sums
+ * S_c, Q_c per image slice, one workgroup per image, a float4 apply); e enters in the second stage only, in f64: the sums of
+ * x + e over n pixels are S_c + n e and Q_c + 2 e S_c + n e^2, and (x + e) * scale + shift = x * scale + (shift + e * scale), so
+ * the shifted map is never written.  With C1 = 0, ld0 = C0 and e = NULL the result is bit-identical to ofx_groupnorm.
+ * scratch: ofx_groupnorm_cat_scratch_bytes(B, C0 + C1) bytes. */
+size_t ofx_groupnorm_cat_scratch_bytes(int B, int C);
+int ofx_groupnorm_cat(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, const float* e, int lde,
+                      const float* gamma, const float* beta, float* out, void* scratch, size_t scratch_bytes, int B, long HW,
+                      int groups, float eps, int silu, void* stream);
+/* The Linear layers of the timestep path on a handful of rows (`time_embed`, openaimodel.py:530-534, and `emb_layers` of every
+ * ResBlock, :220-226, applied at :266 and :771):  out[b][n] = sum_k s(x[b][k]) * w[n][k] + bias[n],  s = x * sigmoid(x) when silu_in
+ * (the nn.SiLU in front of the Linear), the identity otherwise.  x [B][K] with rows ldx apart, w the checkpoint's own row-major
+ * [N][K] (not packed), bias [N] or NULL, out rows ldo >= N apart (columns N..ldo-1 are not touched).  B <= 16 (OFX_EINVAL beyond:
+ * slice the rows); K, ldx % 4 == 0 and x, w 16-byte aligned (OFX_EALIGN); any N.  The rows go to LDS once (SiLU on the way in), one
+ * wave per output column reads its weight row with float4 loads and reduces across the wave in a fixed order: weight-read bound,
+ * no matrix cores. */
+int ofx_emb_linear(const float* x, int ldx, const float* w, const float* bias, float* out, int ldo, int B, int K, int N, int silu_in,
+                   void* stream);
+/* `timestep_embedding` (ldm/modules/diffusionmodules/util.py:154-174, repeat_only=False): out[b][j] = cos(t[b] * freqs[j]) and
+ * out[b][half + j] = sin(t[b] * freqs[j]) for j < half = dim / 2; an odd dim gets a zero last column (:170-171).  t [B] fp32 on the
+ * device (fractional timesteps are legal), freqs [half] fp32 on the device: the table the reference builds on the CPU and moves
+ * (:165-167).  out dense [B][dim].  The product is one fp32 multiplication, sinf / cosf the accurate ones (arguments reach 1e3). */
+int ofx_timestep_embedding(const float* t, const float* freqs, float* out, int B, int dim, void* stream);
 
 /* ---------------------------------------------------------------- key-frame detector */
 /* edges[b] = cv2.dilate(cv2.Canny(V, low, high), ones(ksize, ksize)) for BGR frames u8[B,H,W,3], with V = max(B,G,R)

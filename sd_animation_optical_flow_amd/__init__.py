@@ -8,7 +8,8 @@ Modules: `pdcnet_of`, `ofgen`, `alt_cuda_corr` (the reference's names; `ofgen.ke
 `workspace` (`VideoData` / `VideoFrameIndices`: the reference's on-disk workspace), `raft` (the native executor's handle),
 `clip` (frame-parallel sharding + key-frame broadcast), `handoff` + `vae` + `attention` (SD-inpaint inputs, first-stage
 latent and `memory_efficient_attention` on the device), `transformer` (the UNet's `SpatialTransformer` with reference-frame K/V
-history), `keyframes` (Canny-based key-frame detector), `ops` (one wrapper per
+history), `unet` (the reference's `UNetModel` / `ControlledUnetModel` around it: `control` residuals in, K/V history in and
+out), `keyframes` (Canny-based key-frame detector), `ops` (one wrapper per
 C-ABI entry point), `_lib` (ctypes binding).  The repository root carries two shims named as the reference imports them:
 `alt_cuda_corr` and `xformers`.
 """

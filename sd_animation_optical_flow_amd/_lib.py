@@ -109,6 +109,10 @@ SIGNATURES = {
     "ofx_upconv2x": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "ofx_upsample2x_nearest_f32": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "ofx_decode_to_u8": (_i, [_p, _i, _p, _i, _i, _i, _p]),
+    "ofx_groupnorm_cat_scratch_bytes": (_z, [_i, _i]),
+    "ofx_groupnorm_cat": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _p, _p, _p, _p, _z, _i, _l, _i, _f, _i, _p]),
+    "ofx_emb_linear": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "ofx_timestep_embedding": (_i, [_p, _p, _p, _i, _i, _p]),
     "ofx_corr_slice_floats": (_i, [_i, _i]),
     "ofx_corr_volume": (_i, [_p, _p, C.POINTER(_p), _i, _i, _i, _i, _i, _p]),
     "ofx_corr_volume_split": (_i, [_p, _p, C.POINTER(_p), _i, _i, _i, _i, _i, _i, _i, _p]),

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import json
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -912,6 +913,111 @@ def attention_bnhd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
     scale = float(D) ** -0.5 if scale is None else float(scale)
     check(_lib.lib().ofx_attention_bnhd_f32(_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(bias), Nq * Nk if per_bh else 0, _ptr(out), ldo,
                                             B, H, Nq, Nk, D, scale, _stream()), "ofx_attention_bnhd_f32")
+    return out
+
+
+# --------------------------------------------------------------------------------------
+# UNet pieces (ldm/modules/diffusionmodules/openaimodel.py:257-277, :530-534, :757-793; util.py:154-174)
+# --------------------------------------------------------------------------------------
+def _nhwc_seg(t: torch.Tensor, name: str) -> Tuple[int, int, int, int, int]:
+    """(B, H, W, C, ld) of a float32 CUDA tensor [B,H,W,C]: contiguous, or a channel slice of a wider contiguous tensor."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 4:
+        raise RuntimeError(f"{name} must be a CUDA float32 tensor [B,H,W,C]")
+    _, Cn, ld = _rows_view(t, name)
+    return int(t.shape[0]), int(t.shape[1]), int(t.shape[2]), Cn, ld
+
+
+def groupnorm_cat(x0: torch.Tensor, x1: Optional[torch.Tensor], gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor],
+                  e: Optional[torch.Tensor] = None, groups: int = 32, eps: float = 1e-6, silu: bool = False,
+                  out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """GroupNorm(groups, C0 + C1, eps, affine) of th.cat([x0, x1], channels) + e[b, c] (+ x * sigmoid(x) when silu) without forming
+    the concatenation or the shifted map: `in_layers` / `out_layers` of `ResBlock._forward` (openaimodel.py:257-277) behind
+    `th.cat([h, hs.pop()], dim=1)` (:786) and `h + emb_out` (:275).  x0 [B,H,W,C0], x1 [B,H,W,C1] or None: float32 NHWC, contiguous
+    or channel slices of wider contiguous tensors; e [B, C0 + C1] or None, contiguous or a column slice of a wider [B, n] tensor;
+    gamma / beta [C0 + C1] or None.  C0, C1 and the row strides are multiples of 4.  `out`: a contiguous [B,H,W,C0 + C1] tensor (x0
+    itself, in place, only when x1 is None and x0 is contiguous); `scratch`: a uint8 tensor of at least
+    ofx_groupnorm_cat_scratch_bytes(B, C0 + C1) bytes.  With x1 = e = None the bits are `groupnorm`'s (`ofx_groupnorm_cat`)."""
+    B, H, W, C0, ld0 = _nhwc_seg(x0, "x0")
+    C1, ld1 = 0, 0
+    if x1 is not None:
+        B1, H1, W1, C1, ld1 = _nhwc_seg(x1, "x1")
+        if (B1, H1, W1) != (B, H, W):
+            raise RuntimeError(f"x1 must be [{B},{H},{W},C1], got {tuple(x1.shape)}")
+    Cn = C0 + C1
+    lde = 0
+    if e is not None:
+        if not isinstance(e, torch.Tensor) or e.dim() != 2 or tuple(e.shape) != (B, Cn):
+            raise RuntimeError(f"e must be a CUDA float32 tensor [{B},{Cn}]")
+        _, _, lde = _rows_view(e, "e")
+    L = _lib.lib()
+    if scratch is None:
+        scratch = torch.empty((L.ofx_groupnorm_cat_scratch_bytes(B, Cn),), dtype=torch.uint8, device=x0.device)
+    scratch = _chk(scratch, "scratch", torch.uint8)
+    if out is None:
+        out = torch.empty((B, H, W, Cn), dtype=torch.float32, device=x0.device)
+    out = _chk(out, "out", torch.float32)
+    if tuple(out.shape) != (B, H, W, Cn):
+        raise RuntimeError(f"out must be {(B, H, W, Cn)}, got {tuple(out.shape)}")
+    g = None if gamma is None else _chk(gamma, "gamma", torch.float32)
+    b = None if beta is None else _chk(beta, "beta", torch.float32)
+    for nm, t in (("gamma", g), ("beta", b)):
+        if t is not None and tuple(t.shape) != (Cn,):
+            raise RuntimeError(f"{nm} must be [{Cn}]")
+    check(L.ofx_groupnorm_cat(_ptr(x0), ld0, C0, _ptr(x1), ld1, C1, _ptr(e), lde, _ptr(g), _ptr(b), _ptr(out), _ptr(scratch),
+                              scratch.numel(), B, H * W, int(groups), float(eps), 1 if silu else 0, _stream()), "ofx_groupnorm_cat")
+    return out
+
+
+EMB_LINEAR_ROWS = 16      # rows per launch of ofx_emb_linear
+
+
+def emb_linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, silu_in: bool = False,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`nn.Linear` on a handful of rows, behind `nn.SiLU` when silu_in: `time_embed` and the `emb_layers` of the UNet
+    (openaimodel.py:530-534, :220-226).  x [B, K] float32 (contiguous or a column slice), w [N, K] as the checkpoint holds it, bias
+    [N] or None -> out [B, N]: a new contiguous tensor, or `out` (possibly a column slice of a wider tensor, whose other columns are
+    left alone).  K % 4 == 0.  `ofx_emb_linear` takes 16 rows a launch; more rows are sliced here."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise RuntimeError("x must be a CUDA float32 tensor [B, K]")
+    B, K, ldx = _rows_view(x, "x")
+    w = _chk(w, "w", torch.float32)
+    if w.dim() != 2 or w.shape[1] != K:
+        raise RuntimeError(f"w must be [N, {K}], got {tuple(w.shape)}")
+    N = int(w.shape[0])
+    bb = None if bias is None else _chk(bias, "bias", torch.float32)
+    if bb is not None and tuple(bb.shape) != (N,):
+        raise RuntimeError(f"bias must be [{N}]")
+    if out is None:
+        out = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    if not isinstance(out, torch.Tensor) or out.dim() != 2 or tuple(out.shape) != (B, N):
+        raise RuntimeError(f"out must be a CUDA float32 tensor [{B}, {N}]")
+    _, _, ldo = _rows_view(out, "out")
+    fn = _lib.lib().ofx_emb_linear
+    for r0 in range(0, B, EMB_LINEAR_ROWS):
+        nb = min(EMB_LINEAR_ROWS, B - r0)
+        check(fn(C.c_void_p(x.data_ptr() + 4 * r0 * ldx), ldx, _ptr(w), _ptr(bb), C.c_void_p(out.data_ptr() + 4 * r0 * ldo), ldo, nb, K, N,
+                 1 if silu_in else 0, _stream()), "ofx_emb_linear")
+    return out
+
+
+def timestep_freqs(dim: int, max_period: float = 10000.0) -> torch.Tensor:
+    """The frequency table of `timestep_embedding` in the reference's own arithmetic (util.py:165-167): fp32 on the CPU,
+    exp(-log(max_period) * arange(half) / half), half = dim // 2.  Move it to the device once."""
+    half = int(dim) // 2
+    return torch.exp(-math.log(max_period) * torch.arange(start=0, end=half, dtype=torch.float32) / half) if half else torch.zeros((0,))
+
+
+def timestep_embedding(t: torch.Tensor, freqs: torch.Tensor, dim: int) -> torch.Tensor:
+    """`timestep_embedding(timesteps, dim)` (util.py:154-174): t float32 [B] on the device (fractional values are legal), freqs
+    [dim // 2] from `timestep_freqs` on the device -> [B, dim] = cos(t f) | sin(t f) (| a zero column when dim is odd)."""
+    t = _chk(t, "t", torch.float32)
+    f = _chk(freqs, "freqs", torch.float32)
+    dim = int(dim)
+    if t.dim() != 1 or t.numel() == 0 or dim <= 0 or tuple(f.shape) != (dim // 2,):
+        raise RuntimeError(f"timestep_embedding: t [B] and freqs [{dim // 2}] expected, got {tuple(t.shape)} and {tuple(f.shape)}")
+    out = torch.empty((t.shape[0], dim), dtype=torch.float32, device=t.device)
+    check(_lib.lib().ofx_timestep_embedding(_ptr(t), _ptr(f) if dim >= 2 else None, _ptr(out), int(t.shape[0]), dim, _stream()),
+          "ofx_timestep_embedding")
     return out
 
 
