@@ -328,8 +328,23 @@ typedef struct ofx_conv_desc {
                                                     plain (ReLU / identity, optional addend) or GRU gate epilogue, runs the fused
                                                     1D Winograd F(4,5) kernel on grids that fill the chip (OFX_CONV_NO_WINOGRAD or
                                                     OFX_CONV_NO_WINOGRAD15: never); OFX_CONV_TILE_WINOGRAD forces it as above. */
+    const float* wino4_w;                        /* optional (3x3 layers): the operand of ofx_wino44_conv_weight.  When set, a
+                                                    layer runs the fused Winograd F(4x4,3x3) kernel (2.25 multiplies per output;
+                                                    a larger rounding error than F(2x2,3x3)) if all of
+                                                    these hold:
+                                                    - fp32, stride 1, 'same' padding, a map of whole 16x32 patches;
+                                                    - plain epilogue, ReLU or identity, no addend, `res` or fused norm, and not
+                                                      under ofx_conv2d_stats;
+                                                    - the grid fills whole rounds of the chip (at least 768 workgroups of one
+                                                      16x32 patch x 64 output channels).
+                                                    Otherwise, or with OFX_CONV_NO_WINOGRAD4 (or OFX_CONV_NO_WINOGRAD) in the
+                                                    environment, the layer runs as `wino_w` and the rules above decide.
+                                                    tile = OFX_CONV_TILE_WINOGRAD4 forces it at any grid size and is rejected
+                                                    (OFX_EINVAL) when the layer does not qualify; a forced launch takes two
+                                                    segments of whole 16-channel slabs (every other launch: 32).  NULL: as before. */
 } ofx_conv_desc;
 #define OFX_CONV_TILE_WINOGRAD 1
+#define OFX_CONV_TILE_WINOGRAD4 2
 
 int ofx_conv2d(const ofx_conv_desc* d, void* stream);
 /* What the launcher would do with `d`, without doing it: the validation and the plan of ofx_conv2d (stats_cap_floats = 0), of
@@ -339,8 +354,8 @@ int ofx_conv2d(const ofx_conv_desc* d, void* stream);
  * output extent is beyond 2 GiB (it runs in row ranges, each with a plan of its own).  In `tile` terms: a direct launch runs the
  * BM x BN tile with chunk length BK that `tile` = BK*1000000 + BM*1000 + BN names, `ks` = 2 being its 2000000000 marker. */
 typedef struct ofx_conv_plan {
-    int path;                /* 0 direct implicit-GEMM kernel, 1 fused Winograd F(2x2,3x3), 2 fused Winograd F(4,5); 1 / 2: only
-                                `stats_rows` below is meaningful */
+    int path;                /* 0 direct implicit-GEMM kernel, 1 fused Winograd F(2x2,3x3), 2 fused Winograd F(4,5), 3 fused Winograd
+                                F(4x4,3x3); 1 / 2 / 3: only `stats_rows` below is meaningful (3: always 0) */
     int bm, bn, wm, wn, bk;  /* workgroup tile, wave tile, K chunk */
     int prec;                /* arithmetic of the kernel: OFX_PREC_*, after the split-bf16 modes have mapped the tile onto theirs */
     int ks;                  /* 2: paired K pipelines (64x64 tile on small grids), else 1 */
@@ -369,6 +384,11 @@ long ofx_wino_conv_weight(const float* w_oihw, int Cout, int Cin, float* out);
  * rounded up to 128][Cin] in the kernel's operand order (the exact index is documented at the definition, conv_wino.hip).
  * Cin % 16 == 0.  Returns the float count (`out` may be NULL to query it) or OFX_EINVAL. */
 long ofx_wino15_conv_weight(const float* w_oihw, int Cout, int Cin, int KH, int KW, float* out);
+/* Host-side: OIHW fp32 3x3 weights -> the Winograd F(4x4,3x3) operand of ofx_conv_desc.wino4_w: U = G g G^T per channel pair
+ * over the points {0, 1, -1, 2, -2, inf}, computed in float64 and rounded once, stored [36 points][Cout rounded up to 64][Cin]
+ * in the kernel's operand order (the exact index is documented at the definition, conv_wino.hip).  Cin % 16 == 0.  Returns the
+ * float count (`out` may be NULL to query it) or OFX_EINVAL. */
+long ofx_wino44_conv_weight(const float* w_oihw, int Cout, int Cin, float* out);
 /* The same for the three-piece arithmetic (OFX_PREC_BF16X6_W): `out` holds 1.5 * n_floats floats -- first the [hi x4 | mid x4] groups
  * (16 bytes per four consecutive k), then the [lo x4] groups (8 bytes per four k); hi + mid + lo = x exactly unless lo underflows.
  * The whole matrix [Cout][Kpad] must be converted in one call (the lo groups are addressed from its end): a convolution that uses it

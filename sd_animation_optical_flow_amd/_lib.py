@@ -43,6 +43,7 @@ class ConvDesc(C.Structure):
         ("act", C.c_int), ("epi", C.c_int), ("tile", C.c_int), ("precision", C.c_int),
         ("splitk_ws", C.c_void_p), ("splitk_ws_bytes", C.c_size_t),
         ("wino_w", C.c_void_p),
+        ("wino4_w", C.c_void_p),
     ]
 
 
@@ -84,6 +85,7 @@ SIGNATURES = {
     "ofx_pack_conv_weight": (_l, [_p, _i, _i, _i, _i, _i, _p]),
     "ofx_wino_conv_weight": (_l, [_p, _i, _i, _p]),
     "ofx_wino15_conv_weight": (_l, [_p, _i, _i, _i, _i, _p]),
+    "ofx_wino44_conv_weight": (_l, [_p, _i, _i, _p]),
     "ofx_split_conv_weight": (_i, [_p, _l, _p]),
     "ofx_split_conv_weight3": (_i, [_p, _l, _p]),
     "ofx_gaussian_blur_u8": (_i, [_p, _p, _p, _i, _i, _i, _f, _p]),

@@ -1267,6 +1267,7 @@ const TileInst kTiles[] = {
 // (negative counts, a cover below 1) falls back to the default.
 struct ConvKnobs {
     bool no_wino = false, no_wino15 = false;   // OFX_CONV_NO_WINOGRAD (both fused kernels) / OFX_CONV_NO_WINOGRAD15 (F(4,5) only)
+    bool no_wino44 = false;                    // OFX_CONV_NO_WINOGRAD4: A/B switch, the 3x3 layers stay on F(2x2,3x3)
     bool old_small = false;                    // OFX_CONV_OLD_SMALL_TILES: A/B switch, the round-4 small-grid rule
     bool no_splitk = false;                    // OFX_NO_SPLITK
     long sk_max_tiles = 2048;                  // OFX_SK_MAX_TILES: largest 64x64 grid that may split K
@@ -1288,6 +1289,7 @@ const ConvKnobs& conv_knobs() {
         ConvKnobs k;
         k.no_wino = flag("OFX_CONV_NO_WINOGRAD");
         k.no_wino15 = k.no_wino || flag("OFX_CONV_NO_WINOGRAD15");
+        k.no_wino44 = k.no_wino || flag("OFX_CONV_NO_WINOGRAD4");
         k.old_small = flag("OFX_CONV_OLD_SMALL_TILES");
         k.no_splitk = flag("OFX_NO_SPLITK");
         k.no_uk = flag("OFX_CONV_NO_UK");
@@ -1304,7 +1306,7 @@ const ConvKnobs& conv_knobs() {
 
 // ---- plan: everything a launch needs that is not a pointer.  conv_plan is a pure function of the descriptor's numbers (and of which
 // of its pointers are set), the extras and the knobs: no HIP call, no environment, no global state.
-enum { kPathIgemm = 0, kPathWino3x3 = 1, kPathWino15 = 2 };
+enum { kPathIgemm = 0, kPathWino3x3 = 1, kPathWino15 = 2, kPathWino44 = 3 };
 struct ConvPlan : ofx_conv_plan {   // the public fields (ofx.h: path, tile, arithmetic, schedule, grid, statistics rows) and ...
     int inst = -1;                  // direct kernels: the row of kTiles that bm ... ks and ksplit > 1 name
     const char* name = nullptr;     // family of the per-layer profile
@@ -1328,6 +1330,19 @@ int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, C
     // multiplies per output; residual merge, fused instance norm and epilogue statistics included) and F(4,5) for the SepConvGRU's
     // 1x5 / 5x1 layers (2 instead of 5, GRU gate epilogues included).  Only on grids that fill the chip (ofx_conv_wino_pays):
     // smaller grids, the single pair among them, keep the direct kernels and their small-grid schedules.
+    // F(4x4,3x3) (2.25 multiplies per output) is a route of its own with its own operand and error class: the update block's
+    // plain 3x3 layers, where its one-workgroup-per-CU grid fills whole rounds of the chip (ofx_conv_wino44_pays); a descriptor
+    // without wino4_w plans exactly as before.
+    const bool force4 = d->tile == OFX_CONV_TILE_WINOGRAD4;
+    if (force4 || (d->tile == 0 && !kn.no_wino44 && d->wino4_w)) {
+        const bool fits = nz == 1 && !want_stats && !pool && ofx_conv_wino44_fits(d);
+        if (force4 && !fits) return OFX_EINVAL;
+        if (fits && (force4 || ofx_conv_wino44_pays(d))) {
+            p->path = kPathWino44;
+            p->flops = ofx_conv_wino44_flops(d);
+            return 0;
+        }
+    }
     const bool force = d->tile == OFX_CONV_TILE_WINOGRAD;
     const bool one_d = (d->KH == 1 && d->KW == 5) || (d->KH == 5 && d->KW == 1);
     if (force || (d->tile == 0 && !(one_d ? kn.no_wino15 : kn.no_wino) && d->wino_w)) {
@@ -1559,7 +1574,9 @@ int conv_validate(const ofx_conv_desc* d, const ConvExtra& x, long* split_rows) 
     OFX_REQUIRE(Kpad < 65536, OFX_EINVAL);                       // umulhi division is exact in this range
     // a K chunk never straddles the two segments: not at c0 inside a tap, nor at the wrap from one tap's last channels (in1) to the
     // next tap's first (in0) -- the general schedule picks one segment per chunk (issue: readfirstlane), so c1 must be whole chunks too
-    if (d->in1) OFX_REQUIRE(d->c0 % kKAlign == 0 && d->c1 % kKAlign == 0, OFX_EALIGN);
+    // (a forced F(4x4,3x3) launch never reaches those schedules -- it runs its kernel or is rejected -- and its own shape test asks
+    // for whole 16-channel slabs; every other launch, the forced F(2x2,3x3) / F(4,5) ones included, keeps the rule)
+    if (d->in1 && d->tile != OFX_CONV_TILE_WINOGRAD4) OFX_REQUIRE(d->c0 % kKAlign == 0 && d->c1 % kKAlign == 0, OFX_EALIGN);
     if (x.pool.out) OFX_REQUIRE(M * (long)x.pool.slice1 * 4 < lim, OFX_EINVAL);
     switch (d->epi) {
         case OFX_EPI_PLAIN: OFX_REQUIRE(d->out != nullptr && d->ldo >= d->Cout && (!d->res || d->ldres >= d->Cout), OFX_EINVAL); break;
@@ -1636,7 +1653,9 @@ int ofx_conv2d_ex(const ofx_conv_desc* d, const ConvExtra* extra, hipStream_t s)
     if ((st = conv_plan(d, x, conv_knobs(), &p))) return st;
     OfxProfScope prof(p.name, s);
     prof.flops(p.flops);
-    if (p.path != kPathIgemm) {
+    if (p.path == kPathWino44) {
+        st = ofx_conv_wino44_launch(d, x.alpha, s, x.stop_event);
+    } else if (p.path != kPathIgemm) {
         st = ofx_conv_wino_launch(d, x.alpha, x.stats_rows ? x.stats_part : nullptr, s, x.stop_event);
     } else {
         const bool pool = x.pool.out != nullptr;

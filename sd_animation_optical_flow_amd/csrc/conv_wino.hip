@@ -98,7 +98,7 @@ struct Patch {
 };
 
 // the XCD remap of conv.hip: the output blocks of one patch run back to back on one XCD (shared halo in its L2)
-__device__ __forceinline__ Patch wino_patch(const WinoK& p) {
+template <int PH = 8, int PW = 16> __device__ __forceinline__ Patch wino_patch(const WinoK& p) {
     const int nblk = p.mtiles * p.nblk;
     const int bid = blockIdx.x;
     const int q8 = nblk >> 3, r8 = nblk & 7;
@@ -108,7 +108,7 @@ __device__ __forceinline__ Patch wino_patch(const WinoK& p) {
     const int pb = mt / p.tpi;
     const int trem = mt - pb * p.tpi;
     const int py = trem / p.tpr;
-    return {nb, pb, py * 8, (trem - py * p.tpr) * 16};
+    return {nb, pb, py * PH, (trem - py * p.tpr) * PW};
 }
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -425,6 +425,7 @@ __device__ __forceinline__ float2 f2(float a, float b) { return make_float2(a, b
 __device__ __forceinline__ float2 operator+(float2 a, float2 b) { return f2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 operator-(float2 a, float2 b) { return f2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ float2 operator*(float s, float2 a) { return f2(s * a.x, s * a.y); }
+__device__ __forceinline__ float2 fma2(float s, float2 a, float2 b) { return f2(__builtin_fmaf(s, a.x, b.x), __builtin_fmaf(s, a.y, b.y)); }
 
 // F(4, 5): wave w = all 8 points x the w-th 32 of the workgroup's 128 outputs.  Input transform B^T d of one (tile, channel pair):
 // 8 float2 taps at src -> the 8 points at dst; thread = (tile tid / 8, channel pair tid % 8).  VERT = false (1x5): tile t = (row
@@ -666,6 +667,243 @@ int launch15(const WinoK& k, int epi, dim3 grid, dim3 block, hipStream_t s, hipE
     return ofx_launch_status();
 }
 
+// ---- F(4x4, 3x3): 36 point products per 16 outputs (2.25 multiplies per output), points {0, 1, -1, 2, -2, inf} (Lavin & Gray's
+// matrices).  A workgroup of twelve waves owns a 16x32-pixel output patch -- 32 tiles of 4x4 -- and 64 output channels; wave
+// (i, nt) owns row i of the 6x6 point grid and the nt-th 32 output channels: six accumulators.  Row i of B^T d needs at most four
+// of the window's six rows (kRow44), so as in wino3x3_slabs each lane forms its own A operands in registers straight from the
+// halo: per column of the window a four-term row combination, then the six column points.  The halo (18 x 34 pixels) is staged
+// per 8-channel slab, double-buffered, one barrier per slab; a lane handles its four channels of the slab as two float2 halves
+// (the register budget of three waves per SIMD, 168, does not hold the float4 form next to 96 accumulators).  The weights run one
+// slab ahead in registers, each fragment reloaded behind the MFMAs that consumed it.  Update block's plain epilogue only.
+//
+// Halo layout: a pixel's 8 channels are contiguous, the pixels (x, .. x + 3), x % 4 == 0, 32 contiguous floats, quads 34 floats
+// apart, rows 308.  The operand ds_read_b64 of a half-wave (32 tiles: 8 along x, four pixels apart, 4 along y, four rows apart)
+// then falls on 32 different bank pairs: 34 tx mod 64 = {0, 4, 8, 12, 34, 38, 42, 46}, 4 * 308 ty mod 64 = {0, 16, 32, 48}.
+struct Halo44 {
+    static constexpr int W = 34, H = 18;
+    static constexpr int lquad = 34, lrow = 308;
+    static constexpr int floats = H * lrow;                 // 5544
+    static constexpr int items = W * H * 2;                 // float4 pieces per slab: 1224
+    static constexpr int threads = 768;
+    static constexpr int slots = (items + threads - 1) / threads;   // 2
+    __device__ __host__ static constexpr int at(int y, int x) { return y * lrow + (x >> 2) * lquad + (x & 3) * 8; }
+};
+constexpr int kLDX4 = 40;                                   // output exchange: [wave][column fold b][16 tiles][32 channels at 40]
+constexpr int kXF4 = 12 * 4 * 16 * kLDX4;                   // 30 720 floats: half the patch's tiles at a time
+constexpr int kSmem44 = (2 * Halo44::floats > kXF4 ? 2 * Halo44::floats : kXF4) * 4;   // bytes: 122 880, one workgroup per CU
+
+__global__ __launch_bounds__(768, 1) void wino44_conv_kernel(const WinoK p) {
+    extern __shared__ __attribute__((aligned(16))) float smem44[];
+    using HALO = Halo44;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the weight offsets and the row coefficients stay scalar
+    const int wi = wave >> 1, nt = wave & 1;
+    const Patch pt = wino_patch<16, 32>(p);
+
+    // ---- halo staging: item i = tid + 768 k = (pixel i / 2, float4 slot i % 2), pixels row-major over the halo
+    const float* in1s = p.in1 ? p.in1 : p.in0;
+    const int bytes1s = p.in1 ? p.bytes1 : p.bytes0;
+    // Registers are what this kernel is short of (96 accumulators at three waves per SIMD), so a thread keeps its first pixel's halo
+    // coordinates only, in one register, and works the addresses of both items out again at every slab: item 1 is 384 pixels = 11
+    // rows and 10 pixels on.  (The empty asm keeps the compiler from hoisting that arithmetic out of the loop and spilling it.)
+    static_assert(HALO::slots == 2 && HALO::threads / 2 == 11 * HALO::W + 10, "item 1 = item 0 + 11 rows + 10 pixels");
+    const int hpack = (tid << 16) | (((tid >> 1) / HALO::W) * 64 + (tid >> 1) % HALO::W);   // (and the thread's number: the one register the loop keeps)
+    auto h_coords = [&](int k, int& hy, int& hx, int& t) __attribute__((always_inline)) {
+        int pk = hpack;
+        asm volatile("" : "+v"(pk));
+        t = pk >> 16;
+        hy = (pk >> 6) & 63;
+        hx = pk & 63;
+        if (k) {
+            hx += 10;
+            hy += 11;
+            if (hx >= HALO::W) { hx -= HALO::W; ++hy; }
+        }
+    };
+    auto h_issue = [&](int cb, float4 (&r)[HALO::slots]) __attribute__((always_inline)) {
+        const int c = cb * 8;
+        const bool s0 = c < p.c0;    // wave-uniform
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(s0 ? p.in0 : in1s), (short)0, s0 ? p.bytes0 : bytes1s, 0x00020000);
+        const int so = (s0 ? c : c - p.c0) * 4;
+        const int ldb = (s0 ? p.ld0 : p.ld1) * 4;
+#pragma unroll
+        for (int k = 0; k < HALO::slots; ++k) {
+            int hy, hx, t_;
+            h_coords(k, hy, hx, t_);
+            const int gy = pt.y0 - 1 + hy, gx = pt.x0 - 1 + hx;
+            const bool ok = (k == 0 || t_ < HALO::items - HALO::threads) && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
+            // (float4 slot t_ % 2 of the pixel: 768 % 2 == 0, the same for both items)
+            const int vo = ok ? ((pt.pb * p.H + gy) * p.W + gx) * ldb + (t_ & 1) * 16 : kOOB;
+            v4i t = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, 0);
+            r[k] = *reinterpret_cast<float4*>(&t);
+        }
+    };
+    auto h_store = [&](float* Hs, const float4 (&r)[HALO::slots]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < HALO::slots; ++k) {
+            int hy, hx, t_;
+            h_coords(k, hy, hx, t_);
+            if (k == 0 || t_ < HALO::items - HALO::threads) {   // (quads 34 floats apart: 8-byte aligned)
+                float* const at = Hs + HALO::at(hy, hx) + (t_ & 1) * 4;
+                *reinterpret_cast<float2*>(at) = f2(r[k].x, r[k].y);
+                *reinterpret_cast<float2*>(at + 2) = f2(r[k].z, r[k].w);
+            }
+        }
+    };
+
+    // ---- row i of B^T d: t = c0 d[r0] + c1 d[r1] + c2 d[r2] + c3 d[r3] (rows 0 and 5 have three terms: the last row again, times 0)
+    // Rows 0 and 5 take rows (0, 2, 4) of the window from row 0 / 1 on, rows 1 .. 4 take rows (0, 1, 2, 3) from row 1 on: one
+    // address register and a wave-uniform branch around the reads.
+    const bool outer = wi == 0 || wi == 5;
+    float c0, c1, c2, c3;
+    switch (wi) {
+        case 1: c0 = -4.f; c1 = -4.f; c2 = 1.f; c3 = 1.f; break;
+        case 2: c0 = 4.f; c1 = -4.f; c2 = -1.f; c3 = 1.f; break;
+        case 3: c0 = -2.f; c1 = -1.f; c2 = 2.f; c3 = 1.f; break;
+        case 4: c0 = 2.f; c1 = -1.f; c2 = -2.f; c3 = 1.f; break;
+        default: c0 = 4.f; c1 = -5.f; c2 = 1.f; c3 = 0.f; break;   // rows 0 and 5
+    }
+    const int tile = lane & 31;
+    const int at0 = HALO::at(4 * (tile >> 3) + (wi == 0 ? 0 : 1), 4 * (tile & 7)) + 4 * (lane >> 5);
+
+    // the weights: point 6 i + j, 32-channel block blk, 8-channel chunk cb, half s -> one contiguous 512-byte fragment, 8 bytes per
+    // lane (ofx_wino44_conv_weight); step (cb, s) = 2 cb + s
+    const __amdgpu_buffer_rsrc_t rsu = __builtin_amdgcn_make_buffer_rsrc((void*)p.u, (short)0, p.bytesu, 0x00020000);
+    const int c8n = p.cin >> 3;
+    const int fr0 = (6 * wi * p.nb32 + 2 * pt.nb + nt) * c8n * 2, frq = p.nb32 * c8n * 2;   // fragments: point row's first, per point
+    auto w_load = [&](int j, int step) __attribute__((always_inline)) {
+        typedef int v2i __attribute__((ext_vector_type(2)));
+        int ln = hpack;   // (worked out again at every load, for a register: see h_coords)
+        asm volatile("" : "+v"(ln));
+        v2i t = __builtin_amdgcn_raw_buffer_load_b64(rsu, ((ln >> 16) & 63) * 8, (fr0 + j * frq + step) * 512, 0);
+        return *reinterpret_cast<float2*>(&t);
+    };
+    f32x16 acc[6][1];
+    wino_zero(acc);
+    float2 wr[6];
+
+    float* const Hs = smem44;
+    const int CB = p.cin >> 3;
+    float4 h0[HALO::slots], hn[HALO::slots];
+    h_issue(0, h0);
+    h_issue(CB > 1 ? 1 : 0, hn);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) wr[j] = w_load(j, 0);
+    h_store(Hs, h0);
+    const float* const H0 = Hs + at0;
+    // two slabs per trip (whole 16-channel slabs: CB is even), so that the buffer of each is a constant offset
+#pragma clang loop unroll(disable)
+    for (int cb2 = 0; cb2 < CB; cb2 += 2)
+#pragma unroll
+    for (int par = 0; par < 2; ++par) {
+        const int cb = cb2 + par;
+        const int hb = par * HALO::floats;
+        __syncthreads();   // slab cb is in buffer par, and every wave has left the other buffer
+        h_store(Hs + (1 - par) * HALO::floats, hn);
+        // the last slabs re-issue the last one (and store it where nothing reads it): no branch, loads stay in bounds
+        h_issue(cb + 2 < CB ? cb + 2 : CB - 1, hn);
+        __builtin_amdgcn_sched_barrier(0);   // the loads go ahead of the products, as in wino3x3_slabs
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            float2 t[6];
+            if (outer) {
+#pragma unroll
+                for (int c = 0; c < 6; ++c) {
+                    const float* const d = H0 + hb + HALO::at(0, c) + 2 * s;
+                    const float2 d0 = *reinterpret_cast<const float2*>(d), d1 = *reinterpret_cast<const float2*>(d + 2 * HALO::lrow);
+                    const float2 d2 = *reinterpret_cast<const float2*>(d + 4 * HALO::lrow);
+                    t[c] = f2(__builtin_fmaf(c1, d1.x, __builtin_fmaf(c0, d0.x, d2.x)), __builtin_fmaf(c1, d1.y, __builtin_fmaf(c0, d0.y, d2.y)));
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < 6; ++c) {
+                    const float* const d = H0 + hb + HALO::at(0, c) + 2 * s;
+                    const float2 d0 = *reinterpret_cast<const float2*>(d), d1 = *reinterpret_cast<const float2*>(d + HALO::lrow);
+                    const float2 d2 = *reinterpret_cast<const float2*>(d + 2 * HALO::lrow), d3 = *reinterpret_cast<const float2*>(d + 3 * HALO::lrow);
+                    t[c] = f2(__builtin_fmaf(c3, d3.x, __builtin_fmaf(c2, d2.x, __builtin_fmaf(c1, d1.x, c0 * d0.x))),
+                              __builtin_fmaf(c3, d3.y, __builtin_fmaf(c2, d2.y, __builtin_fmaf(c1, d1.y, c0 * d0.y))));
+                }
+            }
+            // the six column points of the row: the same combinations along the window's columns, one channel at a time
+            const int nx = 2 * cb + s + 1 < 2 * CB ? 2 * cb + s + 1 : 2 * cb + s;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                float x[6];
+#pragma unroll
+                for (int c = 0; c < 6; ++c) x[c] = e ? t[c].y : t[c].x;
+                const float A = __builtin_fmaf(-4.f, x[2], x[4]), Bq = __builtin_fmaf(-4.f, x[1], x[3]), C = x[4] - x[2], D = x[3] - x[1];
+                const float v[6] = {__builtin_fmaf(4.f, x[0], __builtin_fmaf(-5.f, x[2], x[4])), A + Bq, A - Bq, __builtin_fmaf(2.f, D, C),
+                                    __builtin_fmaf(-2.f, D, C), __builtin_fmaf(4.f, x[1], __builtin_fmaf(-5.f, x[3], x[5]))};
+#pragma unroll
+                for (int j = 0; j < 6; ++j) {
+                    acc[j][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[j], e ? wr[j].y : wr[j].x, acc[j][0], 0, 0, 0);
+                    if (e) {
+                        // the next step's fragment goes into the registers these MFMAs have just read, ten MFMAs ahead of its use,
+                        // and stays there (as in wino3x3_slabs: left free, the scheduler sinks the loads to their uses)
+                        wr[j] = w_load(j, nx);
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                    }
+                }
+            }
+        }
+    }
+
+    // ---- output transform and plain epilogue.  A^T (4x6) along the column in registers, the six rows meet in LDS, half of the
+    // patch's tiles (two tile rows) at a time: X[wave][b][tile][channel].  Element e of the C layout: tile (e & 3) + 8 (e >> 2) +
+    // 4 (lane >> 5), output channel lane & 31 of the wave's 32.
+    const float act_lo = p.act == OFX_ACT_RELU ? 0.0f : -3.402823466e38f;   // OFX_ACT_NONE: a NaN sum becomes -FLT_MAX (see conv.hip)
+    float* const X = smem44;
+    int tid2 = hpack;
+    asm volatile("" : "+v"(tid2));
+    tid2 >>= 16;
+    const int lane2 = tid2 & 63, on = tid2 & 31, grp = tid2 >> 5;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        __syncthreads();   // half 0: every wave's last operand reads are done; half 1: the first half has been read
+#pragma unroll
+        for (int eh = 0; eh < 8; ++eh) {
+            const int e = 8 * half + eh;
+            const int tl = (e & 3) + 8 * ((e >> 2) & 1) + 4 * (lane2 >> 5);
+            const float m0 = acc[0][0][e], m1 = acc[1][0][e], m2 = acc[2][0][e], m3 = acc[3][0][e], m4 = acc[4][0][e], m5 = acc[5][0][e];
+            const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
+            float* const x = X + (wave * 4 * 16 + tl) * kLDX4 + (lane2 & 31);
+            x[0 * 16 * kLDX4] = m0 + s12 + s34;
+            x[1 * 16 * kLDX4] = d12 + 2.0f * d34;
+            x[2 * 16 * kLDX4] = s12 + 4.0f * s34;
+            x[3 * 16 * kLDX4] = d12 + 8.0f * d34 + m5;
+        }
+        __syncthreads();
+        // unit = (32-channel half, tile, output row pair {0, 2} or {1, 3}): 64 units over the 24 half-waves
+        for (int un = grp; un < 64; un += 24) {
+            const int ap = (un >> 1) & 1, rest = un >> 2;
+            const int tl = (rest & 7) * 2 + (un & 1), ont = rest >> 3;
+            const int oc = pt.nb * 64 + ont * 32 + on;
+            if (oc >= p.Cout) continue;
+            const float sc = (p.scale ? p.scale[oc] : 1.0f) * p.alpha;
+            const float sh = p.shift ? p.shift[oc] : 0.0f;
+            const int oy = pt.y0 + 4 * (2 * half + (tl >> 3)) + ap, ox = pt.x0 + 4 * (tl & 7);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                float x[5];   // rows ap .. ap + 4 of the point grid
+#pragma unroll
+                for (int k = 0; k < 5; ++k) x[k] = X[((((ap + k) * 2 + ont) * 4 + b) * 16 + tl) * kLDX4 + on];
+                float ya, yb;   // output rows ap and ap + 2
+                if (ap == 0) {
+                    ya = x[0] + (x[1] + x[2]) + (x[3] + x[4]);
+                    yb = (x[1] + x[2]) + 4.0f * (x[3] + x[4]);
+                } else {
+                    ya = (x[0] - x[1]) + 2.0f * (x[2] - x[3]);
+                    yb = (x[0] - x[1]) + 8.0f * (x[2] - x[3]) + x[4];
+                }
+                const long pix = ((long)pt.pb * p.H + oy) * p.W + ox + b;
+                p.out[pix * p.ldo + oc] = fmaxf(ya * sc + sh, act_lo);
+                p.out[(pix + 2L * p.W) * p.ldo + oc] = fmaxf(yb * sc + sh, act_lo);
+            }
+        }
+    }
+}
+
 bool is_3x3(const ofx_conv_desc* d) { return d->KH == 3 && d->KW == 3; }
 bool is_1d(int KH, int KW) { return (KH == 1 && KW == 5) || (KH == 5 && KW == 1); }
 int wino_points(const ofx_conv_desc* d) { return is_3x3(d) ? 16 : 8; }
@@ -744,6 +982,68 @@ int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, float* stats, hipS
     return d->KH == 5 ? launch15<true>(k, d->epi, grid, block, s, stop_event) : launch15<false>(k, d->epi, grid, block, s, stop_event);
 }
 
+// ---- F(4x4, 3x3), the second route of the 3x3 layers (ofx_conv_desc.wino4_w).  Shape test: the update block's kernel only -- fp32,
+// stride 1, 'same' 3x3, a map of whole 16x32 patches, whole 16-channel slabs, the plain epilogue (ReLU or identity, scale / shift,
+// strided destination) with no addend, residual or fused norm.
+bool ofx_conv_wino44_fits(const ofx_conv_desc* d) {
+    const int cin = d->c0 + d->c1;
+    return is_3x3(d) && d->padH == 1 && d->padW == 1 && d->epi == OFX_EPI_PLAIN && d->out != nullptr && d->ldo >= d->Cout &&
+           (d->act == OFX_ACT_NONE || d->act == OFX_ACT_RELU) && !d->addend && !d->res && !d->nmean && !d->nrstd &&
+           d->precision == OFX_PREC_FP32 && d->nz <= 1 && d->stride == 1 && d->Hout == d->Hin && d->Wout == d->Win &&
+           d->Hin % 16 == 0 && d->Win % 32 == 0 && cin % kWBK == 0 && d->c0 % kWBK == 0 &&
+           d->wino4_w != nullptr && ofx_aligned16(d->wino4_w);
+}
+
+// Whether F(4x4) beats F(2x2) on this grid: at least kWino44MinGroups workgroups (16x32 patches x 64-channel blocks), three for
+// each of the chip's 256 CUs, where its workgroups run one per CU.  Measured per layer shape at B = 4 ... 64
+// (profiles/r21_wino44_gate.txt): it wins at 768, 864, 1152, 1536, 2304 and 3072 workgroups and loses or
+// ties at every measured grid of 576 or fewer.  Of the grids that end in a nearly empty round only 864 was measured.
+constexpr long kWino44MinGroups = 768;
+bool ofx_conv_wino44_pays(const ofx_conv_desc* d) {
+    const long patches = (long)d->B * (d->Hin / 16) * (d->Win / 32);
+    return patches * ((d->Cout + 63) / 64) >= kWino44MinGroups;
+}
+
+// 36 point products per 16-output tile, input channel and output channel (x 2 FLOPs)
+double ofx_conv_wino44_flops(const ofx_conv_desc* d) {
+    return 2.0 * 36.0 * ((double)d->B * d->Hout * d->Wout / 16.0) * (double)(d->c0 + d->c1) * d->Cout;
+}
+
+// The caller has validated the descriptor (ofx_conv2d_ex) and ofx_conv_wino44_fits(d).
+int ofx_conv_wino44_launch(const ofx_conv_desc* d, float alpha, hipStream_t s, hipEvent_t stop_event) {
+    WinoK k{};
+    k.in0 = d->in0; k.in1 = d->in1; k.u = d->wino4_w; k.scale = d->scale; k.shift = d->shift; k.out = d->out;
+    k.ld0 = d->ld0; k.c0 = d->c0; k.ld1 = d->ld1; k.cin = d->c0 + d->c1; k.ldo = d->ldo;
+    k.H = d->Hin; k.W = d->Win; k.Cout = d->Cout; k.act = d->act;
+    k.nblk = (d->Cout + 63) / 64;
+    k.nb32 = 2 * k.nblk;
+    k.tpr = d->Win / 32;
+    k.tpi = (d->Hin / 16) * k.tpr;
+    const long mtiles = (long)d->B * k.tpi;
+    const long npix = (long)d->B * d->Hin * d->Win;
+    const long ext0 = ((npix - 1) * d->ld0 + d->c0) * 4, ext1 = d->in1 ? ((npix - 1) * d->ld1 + d->c1) * 4 : 0;
+    const long extu = 36L * k.nb32 * 32 * k.cin * 4;   // (fragments of 512 bytes)
+    OFX_REQUIRE(ext0 < (1L << 31) - 64 && ext1 < (1L << 31) - 64 && extu < (1L << 31) - 64, OFX_EINVAL);
+    OFX_REQUIRE(mtiles * k.nblk < (1L << 31) && npix * d->ldo < (1L << 31), OFX_EINVAL);
+    k.mtiles = (int)mtiles;
+    k.bytes0 = (int)ext0; k.bytes1 = (int)ext1; k.bytesu = (int)extu;
+    k.alpha = alpha;
+    // more than 64 KB of LDS: allowed once per device (as corr_split.hip)
+    static bool allowed[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return OFX_EINVAL;
+    if (!allowed[dev]) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino44_conv_kernel),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kSmem44);
+        if (e != hipSuccess) return (int)e;
+        allowed[dev] = true;
+    }
+    const dim3 grid((unsigned)(k.mtiles * k.nblk), 1, 1), block(768, 1, 1);
+    if (stop_event) hipExtLaunchKernelGGL(wino44_conv_kernel, grid, block, kSmem44, s, nullptr, stop_event, 0, k);
+    else hipLaunchKernelGGL(wino44_conv_kernel, grid, block, kSmem44, s, k);
+    return ofx_launch_status();
+}
+
 namespace {
 
 // Host: U = T g per (output, input) channel pair of OIHW weights w (`taps` contiguous floats per pair) in float64 (`xf` writes the
@@ -805,4 +1105,34 @@ extern "C" long ofx_wino15_conv_weight(const float* w, int Cout, int Cin, int KH
             for (int t = 0; t < 5; ++t) u[q] += G[q][t] * (double)g[t];
         }
     });
+}
+
+// 3x3, F(4x4): U = G g G^T over the points {0, 1, -1, 2, -2, inf}, point (i, j) = 6 i + j, in float64, rounded once; Cout rounded
+// up to 64 (NB = 2 * ceil(Cout / 64) blocks of 32, padded output channels zero).  The kernel's operand order, 512-byte fragments
+// of one point, 32 outputs and a half step of four channels: [36][NB][Cin / 8][2][2][32][2], i.e. point q, output channel
+// o = 32 nb + n, input channel c = 8 c8 + 4 h + 2 s + e at float ((((q * NB + nb) * Cin / 8 + c8) * 2 + s) * 2 + h) * 64 + 2 n + e.
+extern "C" long ofx_wino44_conv_weight(const float* w, int Cout, int Cin, float* out) {
+    OFX_REQUIRE(Cout > 0 && Cin > 0 && Cin % kWBK == 0, OFX_EINVAL);
+    const int nb32 = 2 * ((Cout + 63) / 64);
+    const long n = 36L * nb32 * 32 * Cin;
+    if (!out) return n;
+    OFX_REQUIRE(w != nullptr, OFX_EINVAL);
+    std::memset(out, 0, (size_t)n * sizeof(float));
+    static const double G[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
+                                   {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
+    for (int o = 0; o < Cout; ++o)
+        for (int c = 0; c < Cin; ++c) {
+            const float* g = w + ((size_t)o * Cin + c) * 9;
+            double gg[6][3];   // G g
+            for (int i = 0; i < 6; ++i)
+                for (int x = 0; x < 3; ++x) gg[i][x] = G[i][0] * g[x] + G[i][1] * g[3 + x] + G[i][2] * g[6 + x];
+            for (int i = 0; i < 6; ++i)
+                for (int j = 0; j < 6; ++j) {
+                    const double u = gg[i][0] * G[j][0] + gg[i][1] * G[j][1] + gg[i][2] * G[j][2];
+                    const long q = 6 * i + j;
+                    const long at = ((((q * nb32 + o / 32) * (Cin / 8) + c / 8) * 2 + (c % 4) / 2) * 2 + (c % 8) / 4) * 64 + 2 * (o % 32) + c % 2;
+                    out[at] = (float)u;
+                }
+        }
+    return n;
 }

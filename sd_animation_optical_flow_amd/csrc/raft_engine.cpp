@@ -39,6 +39,7 @@ struct ConvW {
     float* wino = nullptr;    // stride-1 3x3 layers (update block, mask.0, the encoders' residual stages): the Winograd F(2x2,3x3)
                               // operand (ofx_wino_conv_weight); the GRU's
                               // per-iteration 1x5 / 5x1 layers: the F(4,5) operand (ofx_wino15_conv_weight); or null
+    float* wino4 = nullptr;   // the update block's 3x3 layers and mask.0: the Winograd F(4x4,3x3) operand (ofx_wino44_conv_weight), or null
     int cout = 0, cin = 0, cin_pad = 0, kh = 0, kw = 0;
     long kpad = 0;
     std::string name;         // layer label for the per-layer profile (ofx_prof_enable(2))
@@ -241,9 +242,9 @@ int add_conv(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const std
 // the Winograd operand of an already added 3x3 (F(2x2,3x3), U = G g G^T) or 1x5 / 5x1 (F(4,5), U = G g) layer, made of the input
 // channels `sel` (empty: all) of one or more checkpoint convolutions stacked along Cout in the given order (the GRU's z | r): the
 // same rows and channels as its direct packing.  conv.hip takes the fused Winograd kernel with it when the grid fills the chip; the
-// direct packing stays for every other launch.
+// direct packing stays for every other launch.  wino4: a 3x3 layer gets the F(4x4,3x3) operand as well.
 int add_wino(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const std::vector<std::string>& names, const std::vector<int>& sel,
-             const std::string& store_as) {
+             const std::string& store_as, bool wino4 = false) {
     ConvW& c = r->convs[store_as];
     const int ci = c.cin, taps = c.kh * c.kw;
     const bool k3x3 = c.kh == 3 && c.kw == 3, k1d = (c.kh == 1 && c.kw == 5) || (c.kh == 5 && c.kw == 1);
@@ -271,7 +272,15 @@ int add_wino(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const std
     std::vector<float> u((size_t)n);
     const long st = xf(g.data(), u.data());
     if (st < 0) return (int)st;
-    return upload(r, u, &c.wino);
+    int up = upload(r, u, &c.wino);
+    if (up || !k3x3 || !wino4) return up;
+    // the update block's 3x3 layers: the F(4x4,3x3) operand next to it (conv.hip takes it where its grid pays)
+    const long n4 = ofx_wino44_conv_weight(nullptr, c.cout, ci, nullptr);
+    if (n4 < 0) return (int)n4;
+    std::vector<float> u4((size_t)n4);
+    const long st4 = ofx_wino44_conv_weight(g.data(), c.cout, ci, u4.data());
+    if (st4 < 0) return (int)st4;
+    return upload(r, u4, &c.wino4);
 }
 
 // `as`: name the packed layers are stored under.  "cnetb" = the context encoder's convolutions WITHOUT the folded running
@@ -413,6 +422,7 @@ struct Launcher {
         d.precision = wsplit3 ? OFX_PREC_BF16X6_W : wsplit ? OFX_PREC_BF16X3_W : precision;
         d.splitk_ws = sk_ws; d.splitk_ws_bytes = sk_bytes;
         d.wino_w = row_off == 0 && rows == 0 ? c.wino : nullptr;
+        d.wino4_w = row_off == 0 && rows == 0 ? c.wino4 : nullptr;
         if (c0 + c1 != c.cin_pad) { st = OFX_EKEY; return; }
         ofx_prof_set_tag(c.name.c_str());
         ConvExtra x;
@@ -852,7 +862,7 @@ int ofx_raft_create(const ofx_tensor* tensors, int n, ofx_raft** out) {
     const char* ub = "update_block.";
     if (!st) st = add_conv(r, sd, std::string(ub) + "encoder.convc1", "convc1", CORR_LD, "", 1.f);   // input rows padded to 336 (zero weights)
     if (!st) st = add_conv(r, sd, std::string(ub) + "encoder.convc2", "convc2", 0, "", 1.f);
-    if (!st) st = add_wino(r, sd, {std::string(ub) + "encoder.convc2"}, {}, "convc2");
+    if (!st) st = add_wino(r, sd, {std::string(ub) + "encoder.convc2"}, {}, "convc2", true);
     std::vector<float> wf1;   // must outlive add_conv below
     if (!st) {
         // convf1 (7x7 on the 2-channel flow, update.py:93) as a 7x1 convolution over the 16-float flow rows the flow head leaves
@@ -877,16 +887,16 @@ int ofx_raft_create(const ofx_tensor* tensors, int n, ofx_raft** out) {
         }
     }
     if (!st) st = add_conv(r, sd, std::string(ub) + "encoder.convf2", "convf2", 0, "", 1.f);
-    if (!st) st = add_wino(r, sd, {std::string(ub) + "encoder.convf2"}, {}, "convf2");
+    if (!st) st = add_wino(r, sd, {std::string(ub) + "encoder.convf2"}, {}, "convf2", true);
     if (!st) st = add_conv(r, sd, std::string(ub) + "encoder.conv", "conv", 0, "", 1.f);
-    if (!st) st = add_wino(r, sd, {std::string(ub) + "encoder.conv"}, {}, "conv");
+    if (!st) st = add_wino(r, sd, {std::string(ub) + "encoder.conv"}, {}, "conv", true);
     if (!st) st = build_gru(r, sd, "1");
     if (!st) st = build_gru(r, sd, "2");
     if (!st) st = add_conv(r, sd, std::string(ub) + "flow_head.conv1", "fh1", 0, "", 1.f);
-    if (!st) st = add_wino(r, sd, {std::string(ub) + "flow_head.conv1"}, {}, "fh1");
+    if (!st) st = add_wino(r, sd, {std::string(ub) + "flow_head.conv1"}, {}, "fh1", true);
     if (!st) st = add_conv(r, sd, std::string(ub) + "flow_head.conv2", "fh2", 0, "", 1.f);
     if (!st) st = add_conv(r, sd, std::string(ub) + "mask.0", "mask0", 0, "", 1.f);
-    if (!st) st = add_wino(r, sd, {std::string(ub) + "mask.0"}, {}, "mask0");
+    if (!st) st = add_wino(r, sd, {std::string(ub) + "mask.0"}, {}, "mask0", true);
     if (!st) st = add_conv(r, sd, std::string(ub) + "mask.2", "mask2", 0, "", 0.25f);
     for (int i = 0; i < 2 && !st; ++i) {
         if (hipStreamCreateWithFlags(&r->aux[i], hipStreamNonBlocking) != hipSuccess) st = OFX_ENODEV;

@@ -21,6 +21,7 @@ WARP_MODES = {"bilinear": 0, "bicubic": 1, "cv2_cubic": 2}
 ACTS = {None: 0, "none": 0, "relu": 1, "sigmoid": 2, "tanh": 3}
 EPI_PLAIN, EPI_GRU_ZR, EPI_GRU_Q, EPI_FLOW = 0, 1, 2, 3
 TILE_WINOGRAD = 1      # conv2d_nhwc(tile=): force the fused Winograd kernel, F(2x2,3x3) or F(4,5) (OFX_CONV_TILE_WINOGRAD)
+TILE_WINOGRAD4 = 2     # conv2d_nhwc(tile=): force the fused Winograd F(4x4,3x3) kernel (OFX_CONV_TILE_WINOGRAD4)
 
 
 def _stream() -> C.c_void_p:
@@ -262,6 +263,17 @@ def wino_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
     return _wino_weight("ofx_wino_conv_weight", w, co, ci)
 
 
+def wino44_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
+    """OIHW fp32 3x3 (CPU) -> the Winograd F(4x4,3x3) operand U = G g G^T over the points {0, 1, -1, 2, -2, inf} (float64, one
+    rounding) as a flat fp32 CPU tensor in the fused kernel's order (ofx_wino44_conv_weight); pass it to
+    conv2d_nhwc(..., wino4_w=)."""
+    w = w_oihw.detach().to(torch.float32).contiguous().cpu()
+    co, ci, kh, kw = w.shape
+    if (kh, kw) != (3, 3):
+        raise RuntimeError("wino44_conv_weight: 3x3 weights only")
+    return _wino_weight("ofx_wino44_conv_weight", w, co, ci)
+
+
 def wino15_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
     """OIHW fp32 1x5 or 5x1 (CPU) -> the 1D Winograd F(4,5) operand U = G g (float64, one rounding) as a flat fp32 CPU tensor
     in the fused kernel's order (ofx_wino15_conv_weight); pass it to conv2d_nhwc(..., wino_w=)."""
@@ -295,13 +307,14 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
                 precision: str = "fp32", splitk_ws: Optional[torch.Tensor] = None, pad: Optional[Tuple[int, int]] = None,
                 out_hw: Optional[Tuple[int, int]] = None, addend: Optional[torch.Tensor] = None,
                 wino_w: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_off: int = 0,
-                stats_part: Optional[torch.Tensor] = None):
+                stats_part: Optional[torch.Tensor] = None, wino4_w: Optional[torch.Tensor] = None):
     """Plain-epilogue convolution: x [B,H,W,C0] (+ optional second channel segment x2 [B,H,W,C1]),
     'same' padding (k//2) unless `pad` = (top, left) is given; `out_hw` overrides the output size (taps beyond the
     input read zeros: pad (0, 0) with out_hw = (H/2, W/2) is the VAE's F.pad(x, (0,1,0,1)) + stride-2 convolution).
     `addend` [B,Hout,Wout,cout] is added before the activation (`res` adds after it and applies ReLU).
     `wino_w` (wino_conv_weight / wino15_conv_weight, on the device) lets a qualifying 3x3 / 1x5 / 5x1 layer run the fused
-    Winograd kernel (tile = TILE_WINOGRAD forces it).  `out` [B,Hout,Wout,C >= out_off + cout]: write channels
+    Winograd kernel (tile = TILE_WINOGRAD forces it); `wino4_w` (wino44_conv_weight) lets a qualifying plain 3x3 layer run the
+    F(4x4,3x3) kernel where its grid pays (tile = TILE_WINOGRAD4 forces it).  `out` [B,Hout,Wout,C >= out_off + cout]: write channels
     [out_off, out_off + cout) of it.  `stats_part` (f32 on the device): run ofx_conv2d_stats, which leaves the per-channel
     (sum, sum of squares) partials of the outputs there when the launch can produce them ([B][rows][cout][2]; see inorm_finalize).
     Returns [B,Hout,Wout,cout], or `out`; with `stats_part`, (that, rows per image), rows = 0 when none were produced."""
@@ -326,6 +339,8 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
     d.out, d.ldo = out.data_ptr() + 4 * out_off, out.shape[3]
     if wino_w is not None:
         d.wino_w = _chk(wino_w, "wino_w", torch.float32).data_ptr()
+    if wino4_w is not None:
+        d.wino4_w = _chk(wino4_w, "wino4_w", torch.float32).data_ptr()
     if addend is not None:
         addend = _chk(addend, "addend", torch.float32)
         if tuple(addend.shape) != (B, Ho, Wo, cout):

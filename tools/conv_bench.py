@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the implicit-GEMM kernel on the update-block / encoder shapes (B=64 @512x768).
-usage: python tools/conv_bench.py [libofx variant .so ...]"""
+usage: python tools/conv_bench.py [libofx variant .so ...]
+CONV_BENCH_WINO4=1: the Winograd F(4x4,3x3) kernel against F(2x2,3x3) over the batch sizes that set its gate."""
 import ctypes as C, sys, os, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -61,6 +62,10 @@ if os.environ.get("CONV_BENCH_WINO"):    # the fused Winograd F(2x2,3x3) kernel 
         ("3x3 128->64", 64, 64, 96, 128, 64, 3, 3, 1, 0),
     ]
     TILES = [0, 1]
+if os.environ.get("CONV_BENCH_WINO4"):   # F(4x4,3x3) (tile 2) against F(2x2,3x3) (tile 1) on the update block's 3x3 layers over the batch: the gate
+    SHAPES = [(f"B{b} 3x3 {ci}->{co}", b, 64, 96, ci, co, 3, 3, 1, 0)
+              for ci, co in ((256, 192), (128, 256), (256, 126), (128, 64)) for b in (4, 8, 16, 24, 64)]
+    TILES = [1, 2]
 if os.environ.get("CONV_BENCH_WINO_ENC"):   # ... and on the encoders' stride-1 3x3 layers (65 images) with the epilogues they run, and mask.0
     # 11th field, the epilogue: relu (cnet conv1, mask.0), res (cnet conv2: relu, then relu(y + res)), stats (fnet conv1: identity with
     # the instance-norm partial sums, ofx_conv2d_stats), norm+stats (fnet conv2: relu(norm(x)) on the operand, partial sums)
@@ -100,6 +105,10 @@ def run(libpath):
                 from sd_animation_optical_flow_amd import ops
                 u = ops.wino_conv_weight(torch.randn((co, ci, 3, 3)) * 0.02).cuda()
                 d.wino_w = u.data_ptr()
+            if tile == 2:   # ... and the F(4x4,3x3) operand
+                from sd_animation_optical_flow_amd import ops
+                u = ops.wino44_conv_weight(torch.randn((co, ci, 3, 3)) * 0.02).cuda()
+                d.wino4_w = u.data_ptr()
             d.B, d.Hin, d.Win, d.Hout, d.Wout, d.Cout = B, H, W, H // st, W // st, co
             d.KH, d.KW, d.stride, d.padH, d.padW = kh, kw, st, kh // 2, kw // 2
             d.act, d.epi, d.tile = (0 if "stats" in epi else 1), 0, tile
