@@ -669,16 +669,21 @@ int launch15(const WinoK& k, int epi, dim3 grid, dim3 block, hipStream_t s, hipE
 
 // ---- F(4x4, 3x3): 36 point products per 16 outputs (2.25 multiplies per output), points {0, 1, -1, 2, -2, inf} (Lavin & Gray's
 // matrices).  A workgroup of twelve waves owns a 16x32-pixel output patch -- 32 tiles of 4x4 -- and 64 output channels; wave
-// (i, nt) owns row i of the 6x6 point grid and the nt-th 32 output channels: six accumulators.  Row i of B^T d needs at most four
-// of the window's six rows (kRow44), so as in wino3x3_slabs each lane forms its own A operands in registers straight from the
-// halo: per column of the window a four-term row combination, then the six column points.  The halo (18 x 34 pixels) is staged
-// per 8-channel slab, double-buffered, one barrier per slab; a lane handles its four channels of the slab as two float2 halves
-// (the register budget of three waves per SIMD, 168, does not hold the float4 form next to 96 accumulators).  The weights run one
-// slab ahead in registers, each fragment reloaded behind the MFMAs that consumed it.  Update block's plain epilogue only.
+// (i, nt) owns row i of the 6x6 point grid and the nt-th 32 output channels: six accumulators.  The input transform B^T d B is
+// split by what it costs.  Its row half -- row i of B^T d, a four-term combination of the window's rows per column and
+// channel -- would be worked out by every row-wave and twice over the channel halves, each halo value read from LDS eight times:
+// it is computed once per workgroup, a slab ahead, and staged in LDS as T (as F(4, 5) stages its transform).  Its column half --
+// the six column points, twelve operations per channel -- is not redundant and stays in registers: a lane reads the six window
+// columns of its wave's row of T and folds them into its A operands.  The halo (18 x 34 pixels) and T are staged per 8-channel
+// slab, both double-buffered, one barrier per slab (the order of a trip: at the slab loop); a lane handles its four channels of
+// the slab as two float2 halves (the register budget of three waves per SIMD, 168, does not hold the float4 form next to 96
+// accumulators).  The weights run one slab ahead in registers, each fragment reloaded behind the MFMAs that consumed it.  Update
+// block's plain epilogue only.
 //
 // Halo layout: a pixel's 8 channels are contiguous, the pixels (x, .. x + 3), x % 4 == 0, 32 contiguous floats, quads 34 floats
-// apart, rows 308.  The operand ds_read_b64 of a half-wave (32 tiles: 8 along x, four pixels apart, 4 along y, four rows apart)
-// then falls on 32 different bank pairs: 34 tx mod 64 = {0, 4, 8, 12, 34, 38, 42, 46}, 4 * 308 ty mod 64 = {0, 16, 32, 48}.
+// apart, rows 308.  T keeps the layout of a halo row per (point row, tile row), 336 floats apart.  The operand ds_read_b64 of a
+// half-wave (32 tiles: 8 along x, four pixels apart, 4 along y) then falls on 32 different bank pairs: 34 tx mod 64 = {0, 4, 8,
+// 12, 34, 38, 42, 46}, 336 ty mod 64 = {0, 16, 32, 48} (tools/lds_bank_model.py --wino44).
 struct Halo44 {
     static constexpr int W = 34, H = 18;
     static constexpr int lquad = 34, lrow = 308;
@@ -687,10 +692,17 @@ struct Halo44 {
     static constexpr int threads = 768;
     static constexpr int slots = (items + threads - 1) / threads;   // 2
     __device__ __host__ static constexpr int at(int y, int x) { return y * lrow + (x >> 2) * lquad + (x & 3) * 8; }
+    // The row-transformed slab T[point row i][tile row ty][x][8 channels]: row i of B^T d for the windows of tile row ty, pixels
+    // laid out as in a halo row.  A (i, ty) row every 336 floats, 16 mod 64: the operand ds_read_b64 of a half-wave falls on 32
+    // different bank pairs as before (34 tx mod 64 as above, 336 ty mod 64 = {0, 16, 32, 48}).
+    static constexpr int ltrow = 336;
+    static constexpr int tfloats = 6 * 4 * ltrow;           // 8064
+    static constexpr int titems = 4 * W * 4;                // (tile row, x, channel pair): 544, one thread each
 };
 constexpr int kLDX4 = 40;                                   // output exchange: [wave][column fold b][16 tiles][32 channels at 40]
 constexpr int kXF4 = 12 * 4 * 16 * kLDX4;                   // 30 720 floats: half the patch's tiles at a time
-constexpr int kSmem44 = (2 * Halo44::floats > kXF4 ? 2 * Halo44::floats : kXF4) * 4;   // bytes: 122 880, one workgroup per CU
+constexpr int kStage44 = 2 * (Halo44::floats + Halo44::tfloats);   // raw halo and T, both double-buffered: 27 216 floats
+constexpr int kSmem44 = (kStage44 > kXF4 ? kStage44 : kXF4) * 4;   // bytes: 122 880, one workgroup per CU
 
 __global__ __launch_bounds__(768, 1) void wino44_conv_kernel(const WinoK p) {
     extern __shared__ __attribute__((aligned(16))) float smem44[];
@@ -703,23 +715,20 @@ __global__ __launch_bounds__(768, 1) void wino44_conv_kernel(const WinoK p) {
     // ---- halo staging: item i = tid + 768 k = (pixel i / 2, float4 slot i % 2), pixels row-major over the halo
     const float* in1s = p.in1 ? p.in1 : p.in0;
     const int bytes1s = p.in1 ? p.bytes1 : p.bytes0;
-    // Registers are what this kernel is short of (96 accumulators at three waves per SIMD), so a thread keeps its first pixel's halo
-    // coordinates only, in one register, and works the addresses of both items out again at every slab: item 1 is 384 pixels = 11
-    // rows and 10 pixels on.  (The empty asm keeps the compiler from hoisting that arithmetic out of the loop and spilling it.)
+    // A thread keeps, for each of its two items, the pixel's index in the map (-1: out of the map, or no item) and its place in
+    // the halo image: with the row transform staged, the 168 registers of three waves per SIMD hold them next to 96 accumulators.
+    // Item 1 is 384 pixels = 11 rows and 10 pixels on.
     static_assert(HALO::slots == 2 && HALO::threads / 2 == 11 * HALO::W + 10, "item 1 = item 0 + 11 rows + 10 pixels");
-    const int hpack = (tid << 16) | (((tid >> 1) / HALO::W) * 64 + (tid >> 1) % HALO::W);   // (and the thread's number: the one register the loop keeps)
-    auto h_coords = [&](int k, int& hy, int& hx, int& t) __attribute__((always_inline)) {
-        int pk = hpack;
-        asm volatile("" : "+v"(pk));
-        t = pk >> 16;
-        hy = (pk >> 6) & 63;
-        hx = pk & 63;
-        if (k) {
-            hx += 10;
-            hy += 11;
-            if (hx >= HALO::W) { hx -= HALO::W; ++hy; }
-        }
-    };
+    int hpix[HALO::slots], hat[HALO::slots];
+#pragma unroll
+    for (int k = 0; k < HALO::slots; ++k) {
+        const int px = (tid >> 1) + k * (HALO::threads / 2);
+        const int hy = px / HALO::W, hx = px - hy * HALO::W;
+        const int gy = pt.y0 - 1 + hy, gx = pt.x0 - 1 + hx;
+        const bool item = k == 0 || tid < HALO::items - HALO::threads;
+        hpix[k] = item && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W ? (pt.pb * p.H + gy) * p.W + gx : -1;
+        hat[k] = item ? HALO::at(hy, hx) + (tid & 1) * 4 : -1;   // (float4 slot tid % 2 of the pixel: 768 % 2 == 0, the same for both)
+    }
     auto h_issue = [&](int cb, float4 (&r)[HALO::slots]) __attribute__((always_inline)) {
         const int c = cb * 8;
         const bool s0 = c < p.c0;    // wave-uniform
@@ -728,43 +737,57 @@ __global__ __launch_bounds__(768, 1) void wino44_conv_kernel(const WinoK p) {
         const int ldb = (s0 ? p.ld0 : p.ld1) * 4;
 #pragma unroll
         for (int k = 0; k < HALO::slots; ++k) {
-            int hy, hx, t_;
-            h_coords(k, hy, hx, t_);
-            const int gy = pt.y0 - 1 + hy, gx = pt.x0 - 1 + hx;
-            const bool ok = (k == 0 || t_ < HALO::items - HALO::threads) && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
-            // (float4 slot t_ % 2 of the pixel: 768 % 2 == 0, the same for both items)
-            const int vo = ok ? ((pt.pb * p.H + gy) * p.W + gx) * ldb + (t_ & 1) * 16 : kOOB;
+            const int vo = hpix[k] >= 0 ? hpix[k] * ldb + (tid & 1) * 16 : kOOB;
             v4i t = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, 0);
             r[k] = *reinterpret_cast<float4*>(&t);
         }
     };
     auto h_store = [&](float* Hs, const float4 (&r)[HALO::slots]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int k = 0; k < HALO::slots; ++k) {
-            int hy, hx, t_;
-            h_coords(k, hy, hx, t_);
-            if (k == 0 || t_ < HALO::items - HALO::threads) {   // (quads 34 floats apart: 8-byte aligned)
-                float* const at = Hs + HALO::at(hy, hx) + (t_ & 1) * 4;
+        for (int k = 0; k < HALO::slots; ++k)
+            if (k == 0 || hat[k] >= 0) {   // (quads 34 floats apart: 8-byte aligned)
+                float* const at = Hs + hat[k];
                 *reinterpret_cast<float2*>(at) = f2(r[k].x, r[k].y);
                 *reinterpret_cast<float2*>(at + 2) = f2(r[k].z, r[k].w);
             }
-        }
     };
 
-    // ---- row i of B^T d: t = c0 d[r0] + c1 d[r1] + c2 d[r2] + c3 d[r3] (rows 0 and 5 have three terms: the last row again, times 0)
-    // Rows 0 and 5 take rows (0, 2, 4) of the window from row 0 / 1 on, rows 1 .. 4 take rows (0, 1, 2, 3) from row 1 on: one
-    // address register and a wave-uniform branch around the reads.
-    const bool outer = wi == 0 || wi == 5;
-    float c0, c1, c2, c3;
-    switch (wi) {
-        case 1: c0 = -4.f; c1 = -4.f; c2 = 1.f; c3 = 1.f; break;
-        case 2: c0 = 4.f; c1 = -4.f; c2 = -1.f; c3 = 1.f; break;
-        case 3: c0 = -2.f; c1 = -1.f; c2 = 2.f; c3 = 1.f; break;
-        case 4: c0 = 2.f; c1 = -1.f; c2 = -2.f; c3 = 1.f; break;
-        default: c0 = 4.f; c1 = -5.f; c2 = 1.f; c3 = 0.f; break;   // rows 0 and 5
-    }
+    // ---- the row pass: row i of B^T d, i = 0 .. 5, for the windows of tile row ty, once per workgroup.  Thread `tid` < 544 owns
+    // (ty, x, channel pair): the window's six halo rows 4 ty .. 4 ty + 5 at pixel x, six results.  Rows 1 .. 4 take halo rows
+    // 1 .. 4, t = c0 d1 + c1 d2 + c2 d3 + c3 d4; rows 0 and 5 take rows (0, 2, 4) and (1, 3, 5), t = 4 d0 - 5 d1 + d2.  The
+    // expressions keep the form and the operand order they had when every wave worked its own row out: the same bits.
+    const int rpx = tid >> 2, rty = rpx / HALO::W, rx = rpx - rty * HALO::W;
+    const int rxo = (rx >> 2) * HALO::lquad + (rx & 3) * 8 + (tid & 3) * 2;
+    const int rin = tid < HALO::titems ? 4 * rty * HALO::lrow + rxo : -1, rout = rty * HALO::ltrow + rxo;
+    auto row_pass = [&](const float* Rs, float* Ts, bool on) __attribute__((always_inline)) {
+        if (rin >= 0 && on) {
+            const float* const d = Rs + rin;
+            float* const o = Ts + rout;
+            float2 r[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) r[k] = *reinterpret_cast<const float2*>(d + k * HALO::lrow);
+            __builtin_amdgcn_sched_barrier(0);   // all six reads in flight before the first result is stored
+            auto outer = [](float d0, float d1, float d2) { return __builtin_fmaf(-5.f, d1, __builtin_fmaf(4.f, d0, d2)); };
+            auto inner = [](float c0, float c1, float c2, float c3, float d0, float d1, float d2, float d3) {
+                return __builtin_fmaf(c3, d3, __builtin_fmaf(c2, d2, __builtin_fmaf(c1, d1, c0 * d0)));
+            };
+#define OFX_ROW44(i, EX, EY) *reinterpret_cast<float2*>(o + (i) * 4 * HALO::ltrow) = f2(EX, EY)
+            OFX_ROW44(0, outer(r[0].x, r[2].x, r[4].x), outer(r[0].y, r[2].y, r[4].y));
+            OFX_ROW44(1, inner(-4.f, -4.f, 1.f, 1.f, r[1].x, r[2].x, r[3].x, r[4].x), inner(-4.f, -4.f, 1.f, 1.f, r[1].y, r[2].y, r[3].y, r[4].y));
+            OFX_ROW44(2, inner(4.f, -4.f, -1.f, 1.f, r[1].x, r[2].x, r[3].x, r[4].x), inner(4.f, -4.f, -1.f, 1.f, r[1].y, r[2].y, r[3].y, r[4].y));
+            OFX_ROW44(3, inner(-2.f, -1.f, 2.f, 1.f, r[1].x, r[2].x, r[3].x, r[4].x), inner(-2.f, -1.f, 2.f, 1.f, r[1].y, r[2].y, r[3].y, r[4].y));
+            OFX_ROW44(4, inner(2.f, -1.f, -2.f, 1.f, r[1].x, r[2].x, r[3].x, r[4].x), inner(2.f, -1.f, -2.f, 1.f, r[1].y, r[2].y, r[3].y, r[4].y));
+            OFX_ROW44(5, outer(r[1].x, r[3].x, r[5].x), outer(r[1].y, r[3].y, r[5].y));
+#undef OFX_ROW44
+        }
+    };
+    // the product side: wave (i, nt) reads row i of T only, one float2 per window column and half-step
     const int tile = lane & 31;
-    const int at0 = HALO::at(4 * (tile >> 3) + (wi == 0 ? 0 : 1), 4 * (tile & 7)) + 4 * (lane >> 5);
+    const int at0 = (wi * 4 + (tile >> 3)) * HALO::ltrow + (tile & 7) * HALO::lquad + 4 * (lane >> 5);
+    auto t_read = [&](const float* Tw, int s, float2 (&t)[6]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) t[c] = *reinterpret_cast<const float2*>(Tw + HALO::at(0, c) + 2 * s);
+    };
 
     // the weights: point 6 i + j, 32-channel block blk, 8-channel chunk cb, half s -> one contiguous 512-byte fragment, 8 bytes per
     // lane (ofx_wino44_conv_weight); step (cb, s) = 2 cb + s
@@ -773,70 +796,90 @@ __global__ __launch_bounds__(768, 1) void wino44_conv_kernel(const WinoK p) {
     const int fr0 = (6 * wi * p.nb32 + 2 * pt.nb + nt) * c8n * 2, frq = p.nb32 * c8n * 2;   // fragments: point row's first, per point
     auto w_load = [&](int j, int step) __attribute__((always_inline)) {
         typedef int v2i __attribute__((ext_vector_type(2)));
-        int ln = hpack;   // (worked out again at every load, for a register: see h_coords)
-        asm volatile("" : "+v"(ln));
-        v2i t = __builtin_amdgcn_raw_buffer_load_b64(rsu, ((ln >> 16) & 63) * 8, (fr0 + j * frq + step) * 512, 0);
+        v2i t = __builtin_amdgcn_raw_buffer_load_b64(rsu, lane * 8, (fr0 + j * frq + step) * 512, 0);
         return *reinterpret_cast<float2*>(&t);
     };
     f32x16 acc[6][1];
     wino_zero(acc);
     float2 wr[6];
 
+    // LDS: raw halo slabs R[2], then T[2].  Trip k, after its barrier: raw slab k + 2 goes from registers into R[k % 2] (last read
+    // by the row pass of trip k - 1), the loads of slab k + 3 are issued, the row pass takes raw slab k + 1 (stored in trip k - 1)
+    // from R[(k + 1) % 2] into T[(k + 1) % 2] (last read by the products of trip k - 1), and the products of slab k read
+    // T[k % 2]: one barrier per slab.
     float* const Hs = smem44;
+    float* const Ts = smem44 + 2 * HALO::floats;
     const int CB = p.cin >> 3;
     float4 h0[HALO::slots], hn[HALO::slots];
     h_issue(0, h0);
-    h_issue(CB > 1 ? 1 : 0, hn);
+    h_issue(1, hn);
+    h_store(Hs, h0);
+    h_store(Hs + HALO::floats, hn);
+    h_issue(CB > 2 ? 2 : CB - 1, hn);
+    // (the weights after the last halo loads, as in the loop: the first trip's halo wait then leaves them in flight too)
 #pragma unroll
     for (int j = 0; j < 6; ++j) wr[j] = w_load(j, 0);
-    h_store(Hs, h0);
-    const float* const H0 = Hs + at0;
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+    row_pass(Hs, Ts, true);
+    const float* const T0 = Ts + at0;
+    // the six column points of a row: the same combinations along the window's columns, one channel at a time
+    auto fold = [&](const float2 (&t)[6], float (&v)[2][6]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            float x[6];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) x[c] = e ? t[c].y : t[c].x;
+            const float A = __builtin_fmaf(-4.f, x[2], x[4]), Bq = __builtin_fmaf(-4.f, x[1], x[3]), C = x[4] - x[2], D = x[3] - x[1];
+            v[e][0] = __builtin_fmaf(4.f, x[0], __builtin_fmaf(-5.f, x[2], x[4]));
+            v[e][1] = A + Bq;
+            v[e][2] = A - Bq;
+            v[e][3] = __builtin_fmaf(2.f, D, C);
+            v[e][4] = __builtin_fmaf(-2.f, D, C);
+            v[e][5] = __builtin_fmaf(4.f, x[1], __builtin_fmaf(-5.f, x[3], x[5]));
+        }
+    };
     // two slabs per trip (whole 16-channel slabs: CB is even), so that the buffer of each is a constant offset
 #pragma clang loop unroll(disable)
     for (int cb2 = 0; cb2 < CB; cb2 += 2)
 #pragma unroll
     for (int par = 0; par < 2; ++par) {
         const int cb = cb2 + par;
-        const int hb = par * HALO::floats;
-        __syncthreads();   // slab cb is in buffer par, and every wave has left the other buffer
-        h_store(Hs + (1 - par) * HALO::floats, hn);
+        __syncthreads();   // slab cb's T is in buffer par, raw slab cb + 1 in the other raw buffer, and every wave has left the rest
+        float2 t[2][6];
+        t_read(T0 + par * HALO::tfloats, 0, t[0]);
+        h_store(Hs + par * HALO::floats, hn);
         // the last slabs re-issue the last one (and store it where nothing reads it): no branch, loads stay in bounds
-        h_issue(cb + 2 < CB ? cb + 2 : CB - 1, hn);
-        __builtin_amdgcn_sched_barrier(0);   // the loads go ahead of the products, as in wino3x3_slabs
+        h_issue(cb + 3 < CB ? cb + 3 : CB - 1, hn);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            float2 t[6];
-            if (outer) {
-#pragma unroll
-                for (int c = 0; c < 6; ++c) {
-                    const float* const d = H0 + hb + HALO::at(0, c) + 2 * s;
-                    const float2 d0 = *reinterpret_cast<const float2*>(d), d1 = *reinterpret_cast<const float2*>(d + 2 * HALO::lrow);
-                    const float2 d2 = *reinterpret_cast<const float2*>(d + 4 * HALO::lrow);
-                    t[c] = f2(__builtin_fmaf(c1, d1.x, __builtin_fmaf(c0, d0.x, d2.x)), __builtin_fmaf(c1, d1.y, __builtin_fmaf(c0, d0.y, d2.y)));
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < 6; ++c) {
-                    const float* const d = H0 + hb + HALO::at(0, c) + 2 * s;
-                    const float2 d0 = *reinterpret_cast<const float2*>(d), d1 = *reinterpret_cast<const float2*>(d + HALO::lrow);
-                    const float2 d2 = *reinterpret_cast<const float2*>(d + 2 * HALO::lrow), d3 = *reinterpret_cast<const float2*>(d + 3 * HALO::lrow);
-                    t[c] = f2(__builtin_fmaf(c3, d3.x, __builtin_fmaf(c2, d2.x, __builtin_fmaf(c1, d1.x, c0 * d0.x))),
-                              __builtin_fmaf(c3, d3.y, __builtin_fmaf(c2, d2.y, __builtin_fmaf(c1, d1.y, c0 * d0.y))));
-                }
+            float v[2][6];
+            if (s == 1) __builtin_amdgcn_sched_barrier(0);   // (its operands are waited for behind the first half's MFMAs)
+            fold(t[s], v);
+            if (s == 0) {
+                // the second half-step's six reads go under the first one's MFMAs
+                __builtin_amdgcn_sched_barrier(0);
+                t_read(T0 + par * HALO::tfloats, 1, t[1]);
+                __builtin_amdgcn_sched_barrier(0);
             }
-            // the six column points of the row: the same combinations along the window's columns, one channel at a time
+            if (s == 1) {
+                // The row pass of the next slab (not of the one past the last) sits between the two half-steps: its wave has twelve
+                // MFMAs queued and the SIMD's other waves have the matrix pipe.  The second half's operands are folded first
+                // (the empty asm keeps the fold on this side of the branch), so that no MFMA waits for the LDS stores behind it.
+#pragma unroll
+                for (int e = 0; e < 2; ++e)
+#pragma unroll
+                    for (int j = 0; j < 6; ++j) asm volatile("" : "+v"(v[e][j]));
+                row_pass(Hs + (1 - par) * HALO::floats, Ts + (1 - par) * HALO::tfloats, cb + 1 < CB);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             const int nx = 2 * cb + s + 1 < 2 * CB ? 2 * cb + s + 1 : 2 * cb + s;
 #pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                float x[6];
-#pragma unroll
-                for (int c = 0; c < 6; ++c) x[c] = e ? t[c].y : t[c].x;
-                const float A = __builtin_fmaf(-4.f, x[2], x[4]), Bq = __builtin_fmaf(-4.f, x[1], x[3]), C = x[4] - x[2], D = x[3] - x[1];
-                const float v[6] = {__builtin_fmaf(4.f, x[0], __builtin_fmaf(-5.f, x[2], x[4])), A + Bq, A - Bq, __builtin_fmaf(2.f, D, C),
-                                    __builtin_fmaf(-2.f, D, C), __builtin_fmaf(4.f, x[1], __builtin_fmaf(-5.f, x[3], x[5]))};
+            for (int e = 0; e < 2; ++e)
 #pragma unroll
                 for (int j = 0; j < 6; ++j) {
-                    acc[j][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[j], e ? wr[j].y : wr[j].x, acc[j][0], 0, 0, 0);
+                    acc[j][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[e][j], e ? wr[j].y : wr[j].x, acc[j][0], 0, 0, 0);
                     if (e) {
                         // the next step's fragment goes into the registers these MFMAs have just read, ten MFMAs ahead of its use,
                         // and stays there (as in wino3x3_slabs: left free, the scheduler sinks the loads to their uses)
@@ -845,7 +888,6 @@ __global__ __launch_bounds__(768, 1) void wino44_conv_kernel(const WinoK p) {
                         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                     }
                 }
-            }
         }
     }
 
@@ -854,9 +896,7 @@ __global__ __launch_bounds__(768, 1) void wino44_conv_kernel(const WinoK p) {
     // 4 (lane >> 5), output channel lane & 31 of the wave's 32.
     const float act_lo = p.act == OFX_ACT_RELU ? 0.0f : -3.402823466e38f;   // OFX_ACT_NONE: a NaN sum becomes -FLT_MAX (see conv.hip)
     float* const X = smem44;
-    int tid2 = hpack;
-    asm volatile("" : "+v"(tid2));
-    tid2 >>= 16;
+    const int tid2 = tid;
     const int lane2 = tid2 & 63, on = tid2 & 31, grp = tid2 >> 5;
 #pragma unroll
     for (int half = 0; half < 2; ++half) {

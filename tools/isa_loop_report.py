@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """What the compiler made of a kernel's main loop: compile one .hip file of csrc/ to gfx950 assembly with the Makefile's flags and
 report, per kernel, on the loop that holds the most MFMAs -- instruction counts, and for every `s_waitcnt vmcnt` how many MFMAs
-lie between the issue of the youngest load it retires and the wait (a prefetch that the scheduler sank to its use shows as 0-3).
+lie between the issue of the youngest load it retires and the wait (a prefetch that the scheduler sank to its use shows as 0-3),
+and the same for every `s_waitcnt lgkmcnt` and the youngest and the oldest LDS read it retires.
 
 usage: python tools/isa_loop_report.py [conv_wino.hip] [--filter SUBSTRING] [--asm FILE.s]
 
@@ -9,7 +10,8 @@ Only matrix (v_mfma), vector-memory, LDS (ds_) and s_waitcnt / s_barrier instruc
 loop its shape.  Loads are told apart by their buffer descriptor: the SGPR quad that most of the loop's buffer loads use is the
 weights', any other the halo's; global / flat loads are counted as "other".  vmcnt retires in issue order, so a wait for N
 outstanding retires everything but the N youngest; the loop is walked three times and the third pass is reported, so loads issued
-in one iteration and retired in the next are seen.  Registers, scratch and LDS come from the compiler's resource remarks
+in one iteration and retired in the next are seen.  LDS operations return in issue order too (lgkmcnt; a loop with scalar
+memory loads, which do not, is not what this is for), reads and writes in one queue.  Registers, scratch and LDS come from the compiler's resource remarks
 (tools/kres.py)."""
 import argparse, os, re, subprocess, sys, tempfile
 
@@ -124,12 +126,13 @@ def analyse(seq):
     rep = {"mfma": sum(map(is_mfma, seq)), "weight_loads": 0, "halo_loads": 0, "other_loads": 0,
            "lds_reads": sum(t.startswith("ds_read") or t.startswith("ds_load") for t in seq),
            "lds_writes": sum(t.startswith("ds_write") or t.startswith("ds_store") for t in seq),
-           "barriers": sum(t.startswith("s_barrier") for t in seq), "waits": [], "halo_store_wait": None}
+           "barriers": sum(t.startswith("s_barrier") for t in seq), "waits": [], "lds_waits": [], "halo_store_wait": None}
     for t in seq:
         if is_load(t):
             rep[kind(t) + "_loads"] += 1
 
     fifo, mf, last_wait = [], 0, None   # outstanding vector-memory operations, oldest first: (kind, MFMAs issued before it)
+    lfifo = []                          # ... and outstanding LDS operations: ("read" / "write", MFMAs issued before it)
     for trip in range(3):
         seen_write = False
         for t in seq:
@@ -141,6 +144,18 @@ def analyse(seq):
                 if trip == 2 and not seen_write and last_wait is not None:
                     rep["halo_store_wait"] = last_wait
                 seen_write = True
+                lfifo.append(("write", mf))
+            elif t.startswith("ds_read") or t.startswith("ds_load"):
+                lfifo.append(("read", mf))
+            m = re.search(r"lgkmcnt\((\d+)\)", t) if t.startswith("s_waitcnt") else None
+            if m:
+                n = int(m.group(1))
+                gone, lfifo = (lfifo[:len(lfifo) - n], lfifo[len(lfifo) - n:]) if len(lfifo) > n else ([], lfifo)
+                reads = [g[1] for g in gone if g[0] == "read"]
+                if trip == 2 and gone:
+                    rep["lds_waits"].append({"lgkmcnt": n, "at_mfma": mf - base, "retired": len(gone), "reads": len(reads),
+                                             "read_distance": mf - reads[-1] if reads else None,
+                                             "oldest_read_distance": mf - reads[0] if reads else None})
             m = re.search(r"vmcnt\((\d+)\)", t) if t.startswith("s_waitcnt") else None
             if m:
                 n = int(m.group(1))
@@ -157,12 +172,14 @@ def analyse(seq):
         base = mf
     wd = [w["weight_distance"] for w in rep["waits"] if w.get("weight_distance") is not None]
     rep["min_weight_distance"] = min(wd) if wd else None
+    rd = [w["oldest_read_distance"] for w in rep["lds_waits"] if w["reads"]]
+    rep["max_read_distance"] = max(rd) if rd else None
     return rep
 
 
 def report(src=None, asm=None, name_filter=None):
-    """-> [{kernel, mfma, weight_loads, halo_loads, other_loads, lds_reads, lds_writes, barriers, waits, halo_store_wait,
-    min_weight_distance, vgpr, agpr, scratch, lds}] for every kernel with a loop that holds MFMAs"""
+    """-> [{kernel, mfma, weight_loads, halo_loads, other_loads, lds_reads, lds_writes, barriers, waits, lds_waits, halo_store_wait,
+    min_weight_distance, max_read_distance, vgpr, agpr, scratch, lds}] for every kernel with a loop that holds MFMAs"""
     rows = []
     if asm is None:
         asm, rows = compile_asm(src)
@@ -211,6 +228,11 @@ def main():
         hw = r["halo_store_wait"]
         print(f"  last vmcnt wait before the loop's first LDS store: {'none' if hw is None else f'vmcnt({hw})'}")
         print(f"  weight loads: nearest wait {r['min_weight_distance']} MFMAs after issue")
+        for w in r["lds_waits"]:
+            what = (f"{w['reads']} reads, the youngest issued {w['read_distance']} MFMAs earlier, the oldest {w['oldest_read_distance']}"
+                    if w["reads"] else "writes only")
+            print(f"  after MFMA {w['at_mfma']:>3}: lgkmcnt({w['lgkmcnt']}) retires {w['retired']:>2} LDS operations: {what}")
+        print(f"  LDS reads: farthest wait {r['max_read_distance']} MFMAs after issue")
 
 
 if __name__ == "__main__":

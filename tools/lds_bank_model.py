@@ -14,6 +14,8 @@ usage: python tools/lds_bank_model.py            the report kept as profiles/r13
        python tools/lds_bank_model.py --search   every conflict-free pixel-pair layout of the 3x3 halo, smallest first
        python tools/lds_bank_model.py --wino15   the layouts of the F(4, 5) kernels' transformed tile, kept as
                                                  profiles/r19_wino15_lds_bank_model.txt
+       python tools/lds_bank_model.py --wino44   the F(4x4, 3x3) kernel: operands from the halo against the row transform staged
+                                                 in LDS, kept as profiles/r22_wino44_rowstage_lds_bank_model.txt
 """
 import sys
 
@@ -183,6 +185,66 @@ def wino15():
     print("  ds_read_b128 wants 16 tiles' float4 in 16 different bank quads (stride = 4 mod 8, not 0 mod 16).  The swizzle gives both.")
 
 
+def wino44():
+    """F(4x4, 3x3): twelve waves, wave = (point row i, channel half nt), lane = (tile lane & 31, channel group lane >> 5); halo
+    18 x 34 pixels of 8 channels, quads of four pixels 34 floats apart, rows 308 (Halo44 of csrc/conv_wino.hip)"""
+    W, lq, lrow, ltrow = 34, 34, 308, 336
+    at = lambda y, x: y * lrow + (x >> 2) * lq + (x & 3) * 8
+
+    def staging(t):
+        wr = []
+        for k in range(2):
+            for wave in range(12):
+                def f(lane, k=k, wave=wave):
+                    i = wave * 64 + lane + 768 * k
+                    return None if i >= W * 18 * 2 else at((i >> 1) // W, (i >> 1) % W) + 4 * (i & 1)
+                wr.append(f)
+                wr.append(lambda lane, f=f: None if f(lane) is None else f(lane) + 2)
+        t.add("halo staging (18 x 34 pixels, two float2 per item)", "ds_write_b64", wr)
+
+    print("# tools/lds_bank_model.py --wino44: LDS cycles of one workgroup (twelve waves) and 8-channel slab of the F(4x4, 3x3) kernel")
+    print("# (single ds_read_b64 / ds_write_b64; the compiler pairs neighbouring ones into ds_read2_b64 / ds_write2_b64)")
+    print("\n## operands from the halo: every wave reads the three or four window rows of its point row, per column and half-step")
+    t = Tally()
+    staging(t)
+    rd = []
+    for wi in range(6):
+        rows = (0, 2, 4) if wi == 0 else (1, 3, 5) if wi == 5 else (1, 2, 3, 4)
+        for nt in range(2):
+            for s in range(2):
+                for c in range(6):
+                    for r in rows:
+                        rd.append(lambda lane, s=s, c=c, r=r: at(4 * ((lane & 31) >> 3) + r, 4 * (lane & 7) + c) + 4 * (lane >> 5) + 2 * s)
+    t.add("operand reads of the halo", "ds_read_b64", rd)
+    t.show()
+    print(f"\n## the row transform staged: T[point row][tile row][x][8 channels], rows {ltrow} floats apart; thread < 544 = (tile row, x, channel pair)")
+    t = Tally()
+    staging(t)
+
+    def item(i):
+        if i >= 4 * W * 4:
+            return None
+        ty, x = (i >> 2) // W, (i >> 2) % W
+        return ty, (x >> 2) * lq + (x & 3) * 8 + (i & 3) * 2
+    rd, wr = [], []
+    for wave in range(9):
+        for k in range(6):
+            rd.append(lambda lane, wave=wave, k=k: None if item(wave * 64 + lane) is None else
+                      (4 * item(wave * 64 + lane)[0] + k) * lrow + item(wave * 64 + lane)[1])
+            wr.append(lambda lane, wave=wave, k=k: None if item(wave * 64 + lane) is None else
+                      (4 * k + item(wave * 64 + lane)[0]) * ltrow + item(wave * 64 + lane)[1])
+    t.add("row pass: reads of the halo", "ds_read_b64", rd)
+    t.add("row pass: writes of T", "ds_write_b64", wr)
+    rd = []
+    for wi in range(6):
+        for nt in range(2):
+            for s in range(2):
+                for c in range(6):
+                    rd.append(lambda lane, wi=wi, s=s, c=c: (4 * wi + ((lane & 31) >> 3)) * ltrow + (lane & 7) * lq + at(0, c) + 4 * (lane >> 5) + 2 * s)
+    t.add("operand reads of T (the wave's own row)", "ds_read_b64", rd)
+    t.show()
+
+
 def plain(ldh, W=18):
     return lambda y, x: (y * W + x) * ldh
 
@@ -207,6 +269,9 @@ def search():
 def main():
     if "--wino15" in sys.argv:
         wino15()
+        return
+    if "--wino44" in sys.argv:
+        wino44()
         return
     if "--search" in sys.argv:
         print("# conflict-free pixel-pair layouts of the 10 x 18 halo (staging ds_write_b128 and operand ds_read_b128), smallest first")
