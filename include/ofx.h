@@ -283,6 +283,22 @@ int ofx_abs_diff_sum_u8(const uint8_t* a, long a_bstride, const uint8_t* b, long
 #define OFX_PREC_BF16X6 3     /* opt-in: fp32 operands split into THREE bf16 pieces (exact), the six products of weight >= 2^-16
                                  on the bf16 matrix cores, fp32 accumulate: fp32-level accuracy (dropped terms < 2^-23), not the
                                  bit pattern of an fmaf chain */
+#define OFX_PREC_F16 5        /* opt-in: both operands rounded fp32 -> fp16 (round-to-nearest-even) as they are staged, ONE product per
+                                 operand pair on v_mfma_f32_32x32x16_f16, fp32 accumulate -- the arithmetic torch.autocast gives the
+                                 reference's diffusion stage.  Activations, weights ([Cout][Kpad] fp32, converted in the kernel) and
+                                 the epilogue stay fp32.  Error: 2^-11 relative per operand, i.e. ~2^-10 * sum |x||w| per output.
+                                 Range: an operand beyond +-65504 becomes an infinity, as the convert instruction makes it and as
+                                 autocast does (the result is then inf / NaN; the identity epilogue stores +-FLT_MAX for them).
+                                 Subnormals: operands below 2^-14 in magnitude become fp16 subnormals (multiples of 2^-24) and
+                                 the matrix core multiplies them as such -- nothing is flushed (held by the small-magnitude case
+                                 of tests/f16_check.py; were they flushed, that case's bound would need the extra term
+                                 K * 2^-14 * max |other operand|).
+                                 Serves the plain epilogue only (identity / ReLU / sigmoid / tanh with scale, shift, addend, res,
+                                 two segments, out / ldo, stride), tiles 128x128, 128x64 and 64x64, BK 16 or 32, the halo-patch
+                                 schedule included.  OFX_EINVAL, from ofx_conv2d and ofx_conv2d_plan alike and before any launch:
+                                 the GRU / flow epilogues, nmean / nrstd, ofx_conv2d_stats, nz > 1, the pooled correlation
+                                 volume, a split-K workspace (splitk_ws != NULL) and the paired-pipeline tile marker.  wino_w /
+                                 wino4_w are ignored, as under the split-bf16 modes */
 
 typedef struct ofx_conv_desc {
     /* input: NHWC fp32, up to two channel segments (torch.cat along C without materialising) */
@@ -304,7 +320,7 @@ typedef struct ofx_conv_desc {
     int tile;                                    /* 0 = auto; else [2000000000 +] BK*1000000 + BM*1000 + BN, e.g. 16128128;
                                                     tiles 128x{32,64,128,192}, 64x64; BK 16 or 32; the 2e9 marker selects the
                                                     paired-pipeline variant of the 64x64 / BK 32 tile (small grids) */
-    int precision;                               /* OFX_PREC_FP32 (default, exact fp32 MFMA) or OFX_PREC_BF16X3 */
+    int precision;                               /* OFX_PREC_FP32 (default, exact fp32 MFMA) or one of the opt-in OFX_PREC_* above */
     void* splitk_ws;                             /* optional device scratch (256-byte aligned) for split-K on small grids: */
     size_t splitk_ws_bytes;                      /* partial tiles + per-tile arrival counters.  The first 64 KiB hold the
                                                     counters and must be ZERO before the first use (the kernel leaves them
@@ -393,7 +409,7 @@ long ofx_wino44_conv_weight(const float* w_oihw, int Cout, int Cin, float* out);
  * (16 bytes per four consecutive k), then the [lo x4] groups (8 bytes per four k); hi + mid + lo = x exactly unless lo underflows.
  * The whole matrix [Cout][Kpad] must be converted in one call (the lo groups are addressed from its end): a convolution that uses it
  * passes d->Cout = that row count and d->nz <= 1 (a row slice or a batched GEMM would read the lo groups from the wrong place;
- * ofx_conv2d returns OFX_EINVAL for nz > 1, and for a precision outside OFX_PREC_FP32 .. OFX_PREC_BF16X6_W). */
+ * ofx_conv2d returns OFX_EINVAL for nz > 1, and for a precision outside OFX_PREC_FP32 .. OFX_PREC_F16). */
 int ofx_split_conv_weight3(const float* packed, long n_floats, float* out);
 
 /* instance norm statistics over HW per (b,c): mean and 1/sqrt(var+eps) (biased var), NHWC input with rows of ld >= C floats

@@ -10,8 +10,9 @@
 //
 // Arithmetic (template PREC):
 //   PREC = 0  exact fp32: v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate, bit-identical to an fmaf
-//             chain, 157 TFLOP/s peak = the roofline of this kernel).  The reference runs fp32
-//             (mixed_precision=False, ofgen_keyframe_inpaint.py:57); this is the default everywhere.
+//             chain, 157 TFLOP/s peak = the roofline of this kernel).  The reference runs RAFT in fp32
+//             (mixed_precision=False, ofgen_keyframe_inpaint.py:57); this is the default everywhere.  Its Stable Diffusion
+//             stage it runs under torch.autocast (ofgen.py:104): that arithmetic is PREC = 5.
 //   PREC = 3  opt-in "bf16x6": three bf16 pieces per operand (hi + mid + lo = the fp32 value exactly: 3 x 8 mantissa
 //             bits), the six products of weight >= 2^-16 (hh, hm, mh, mm, hl, lh) on v_mfma_f32_32x32x16_bf16 with fp32
 //             accumulation: what is dropped (ml, lm, ll) is below 2^-23 relative, i.e. fp32 rounding level, at 2.7x the
@@ -21,6 +22,11 @@
 //   PREC = 1  opt-in "bf16x3": every operand is split at LDS-commit time into hi = bf16(x) and
 //             lo = bf16(x - hi); hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16, f32 accumulate
 //             (~16 mantissa bits per product; measured flow EPE ~1e-4 px after 20 iterations).
+//   PREC = 5  opt-in "fp16" (OFX_PREC_F16; `UNetModel(precision="fp16")`): both operands rounded fp32 -> fp16 (round-to-nearest-even,
+//             v_cvt_pk_f16_f32) at LDS-commit time, ONE v_mfma_f32_32x32x16_f16 per (i, j) and 16 k, fp32 accumulate: the pattern of
+//             PREC = 1 with one piece instead of two -- the same ROWB rows, row permutation and b128 fragment reads -- at half the
+//             LDS bytes and a third of the MFMAs.  Plain epilogue only; tiles 128x128, 128x64 and 64x64, all three with the halo
+//             patch (16-channel slabs) and the scalar-coordinate schedule; BK 16 or 32 off the patch.  Range and subnormals: ofx.h.
 //
 // Tiling (64-wide wavefronts): 256 threads = 4 waves per workgroup, a BMxBN output tile, BK = 16 or
 // 32.  Both operands are staged k-contiguous in LDS with a row stride of BK+4 floats (20 / 36), which
@@ -112,10 +118,24 @@ constexpr int kKAlign = 32;   // packed weights are zero-padded along K to this 
 // channel offset, and the input is fetched ~5x less often.  K is walked channel-slab-major (slab, tap) instead of tap-major: the
 // same products in another summation order.  Why it matters: the rate of the general kernel follows the A bytes staged per MFMA
 // (DESIGN.md section 4), which this cuts by the number of taps.
+// PREC = 5 (fp16): workgroups per CU the compiler is asked to leave room for, per tile.  The rule follows what the tiles compile to
+// (profiles/r23_unet_f16_rate.txt, section 3): 128x128 needs 118-128 VGPRs at BK 16 and 142-150 at BK 32 -- asked for more than
+// three it spills (152-340 bytes of scratch per lane at five); 128x64 and 64x64 fit five to eight waves per SIMD on their own.
+// -DOFX_F16_OCC=n builds another arm for every tile (tools/build_variant.sh); that file says which arms were timed.
+constexpr int f16_occupancy(int BM, int BN) {
+#ifdef OFX_F16_OCC
+    return OFX_F16_OCC;
+#else
+    return (BM == 128 && BN == 128) ? 3 : 4;
+#endif
+}
+
 template <int BM, int BN, int WM, int WN, int EPI, bool NORM, int BK, int PREC, int KS = 1, bool SK = false, int MODE = 0>
-__global__ __launch_bounds__(256 * KS, (BK == 16 && KS == 1) ? ((PREC == 3 || PREC == 4) ? 2 : (PREC == 0 && BM <= 128 && BN <= 128 && !NORM && EPI != OFX_EPI_FLOW) ? 4 : 3) : 1) void igemm_kernel(const ConvK p) {
+__global__ __launch_bounds__(256 * KS, PREC == OFX_PREC_F16 ? f16_occupancy(BM, BN) : (BK == 16 && KS == 1) ? ((PREC == 3 || PREC == 4) ? 2 : (PREC == 0 && BM <= 128 && BN <= 128 && !NORM && EPI != OFX_EPI_FLOW) ? 4 : 3) : 1) void igemm_kernel(const ConvK p) {
     constexpr bool UK = MODE == 1, PATCH = MODE == 2;
     constexpr bool X6 = PREC == 3 || PREC == 4;           // three bf16 pieces per operand, six products
+    constexpr bool F16 = PREC == OFX_PREC_F16;            // one fp16 piece per operand, one product
+    static_assert(!F16 || (!NORM && KS == 1 && !SK && (EPI == OFX_EPI_PLAIN || EPI == kEpiPlainT)), "fp16: the plain epilogue only, one pipeline, no split-K");
     // halo patch rows staged per channel slab, rounded up to whole groups of 16: 8x16 patches 12 x 16 / 10 x 18 / 8 x 20 -> 192,
     // 8x8 patches (the 64-row tile) 12 x 8 / 10 x 10 / 8 x 12 -> 112
     // (the 256-row tile: 16x16 patches, 20 x 16 / 18 x 18 / 16 x 20 -> 336)
@@ -133,7 +153,7 @@ __global__ __launch_bounds__(256 * KS, (BK == 16 && KS == 1) ? ((PREC == 3 || PR
     // PREC = 1 (bf16x3): every fp32 operand element is staged as two bf16 values hi = bf16(x), lo = bf16(x - hi)
     // (same 4 bytes per element); rows are BK bf16 + 16 B of padding (48 B / 80 B: conflict-free b128 reads)
     constexpr int ROWB = BK * 2 + 16;                       // bytes per staged bf16 row
-    constexpr int NPC = X6 ? 3 : 2;                         // bf16 pieces per operand element
+    constexpr int NPC = X6 ? 3 : F16 ? 1 : 2;               // 16-bit pieces per operand element
     constexpr int STAGE = PREC ? ((BM + BN_ST) * ROWB * NPC) / 4 : (BM + BN_ST) * LDK;   // floats per stage
     // BSWZ (the fp32 64-row patch tile, i.e. the small-grid schedule): the two weight stages are UNPADDED 128-byte rows whose eight
     // 16-byte slots are XOR-swizzled with (row >> 1) & 7 -- 16 consecutive rows of one slot then cover the 64 banks exactly (row parity
@@ -148,7 +168,7 @@ __global__ __launch_bounds__(256 * KS, (BK == 16 && KS == 1) ? ((PREC == 3 || PR
     static_assert((BM / WM) * (BN / WN) == 4, "4 waves per workgroup");
     static_assert(KS == 1 || KS == 2, "one or two pipelines");
     static_assert(KS == 1 || 2 * STAGE * KS >= 256 * TM * TN * 16, "accumulator exchange must fit the staging buffers");
-    __shared__ __attribute__((aligned(16))) float smem_all[!PATCH ? 2 * STAGE * KS : BSWZ ? kPatchRows * LDK + 2 * BN_ST * BK : PREC == 0 ? (kPatchRows + 2 * BN_ST) * LDK : (kPatchRows + 2 * BN_ST) * (X6 ? 3 : 2) * (ROWB / 4)];
+    __shared__ __attribute__((aligned(16))) float smem_all[!PATCH ? 2 * STAGE * KS : BSWZ ? kPatchRows * LDK + 2 * BN_ST * BK : PREC == 0 ? (kPatchRows + 2 * BN_ST) * LDK : (kPatchRows + 2 * BN_ST) * NPC * (ROWB / 4)];
     const int grp = KS == 1 ? 0 : (int)(threadIdx.x >> 8);      // pipeline this thread belongs to
     float* const smem = smem_all + grp * (2 * STAGE);
 
@@ -271,9 +291,10 @@ __global__ __launch_bounds__(256 * KS, (BK == 16 && KS == 1) ? ((PREC == 3 || PR
     }
 
     if constexpr (PATCH) {
-        static_assert(!PATCH || (PREC <= 4 && KS == 1 && ((BM == 128 && (WM == 64 || WM == 32) && BK == 16 && !SK) || (PREC == 0 && BM == 64 && WM == 32 && BK == 32) ||
+        static_assert(!PATCH || (PREC <= 5 && KS == 1 && ((BM == 128 && (WM == 64 || WM == 32) && BK == 16 && !SK) || (PREC == 0 && BM == 64 && WM == 32 && BK == 32) ||
+                                                         (F16 && BM == 64 && WM == 32 && BK == 16) ||
                                                          (PREC == 0 && BM == 256 && WM == 64 && BK == 16 && !SK))),
-                      "patch mode: 128-row tiles with 16-channel slabs (fp32 or bf16x3), or the fp32 64x64 small-grid tile with 32-channel slabs (split-K allowed)");
+                      "patch mode: 128-row tiles with 16-channel slabs (fp32, split bf16 or fp16), the fp32 64x64 small-grid tile with 32-channel slabs (split-K allowed), or the fp16 64x64 tile with 16-channel slabs");
         static_assert(!PATCH || (EPI != OFX_EPI_FLOW && EPI != kEpiVolPool), "patch mode: plain / GRU epilogues");
         typedef int v4i __attribute__((ext_vector_type(4)));
         const int PWH = kPW + p.KW - 1;                      // halo patch width in pixels
@@ -289,7 +310,7 @@ __global__ __launch_bounds__(256 * KS, (BK == 16 && KS == 1) ? ((PREC == 3 || PR
         constexpr int APIECE = kPatchRows * AROWF;           // floats per A piece
         constexpr int BPIECE = BN_ST * (BSWZ ? BK : AROWF);
         float* const Apatch = smem_all;
-        constexpr int NPIECE = PREC == 0 ? 1 : X6 ? 3 : 2;
+        constexpr int NPIECE = PREC == 0 ? 1 : NPC;
         float* const Bst = smem_all + NPIECE * APIECE;
         constexpr int BSTAGE = NPIECE * BPIECE;
         // the (row, float4 slot) pairs this thread stages per slab; rows permuted like r0 (conflict-free ds_write_b128)
@@ -354,6 +375,13 @@ __global__ __launch_bounds__(256 * KS, (BK == 16 && KS == 1) ? ((PREC == 3 || PR
             *reinterpret_cast<b4*>(hi_row) = hh;
             *reinterpret_cast<b4*>(lo_row) = ll;
         };
+        // fp32 -> fp16, round-to-nearest-even (v_cvt_pk_f16_f32); beyond +-65504 the result is an infinity
+        auto cvt_store = [&](char* row, float4 v) __attribute__((always_inline)) {
+            typedef float f4 __attribute__((ext_vector_type(4)));
+            typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+            const f4 x = {v.x, v.y, v.z, v.w};
+            *reinterpret_cast<h4*>(row) = __builtin_convertvector(x, h4);
+        };
         // fp32 -> (hi, mid, lo) bf16 triple (bf16x6)
         auto split_store3 = [&](char* hi_row, char* mid_row, char* lo_row, float4 v) __attribute__((always_inline)) {
             typedef float f4 __attribute__((ext_vector_type(4)));
@@ -407,7 +435,8 @@ __global__ __launch_bounds__(256 * KS, (BK == 16 && KS == 1) ? ((PREC == 3 || PR
                     *reinterpret_cast<float4*>(&Apatch[alds0 + q * SROWS * LDK]) = v;
                 } else {
                     char* hi = reinterpret_cast<char*>(Apatch) + alds0 + q * SROWS * ROWB;
-                    if constexpr (X6) split_store3(hi, hi + APIECE * 4, hi + 2 * APIECE * 4, v);
+                    if constexpr (F16) cvt_store(hi, v);
+                    else if constexpr (X6) split_store3(hi, hi + APIECE * 4, hi + 2 * APIECE * 4, v);
                     else split_store(hi, hi + APIECE * 4, v);
                 }
             }
@@ -441,7 +470,9 @@ __global__ __launch_bounds__(256 * KS, (BK == 16 && KS == 1) ? ((PREC == 3 || PR
 #define OFX_B_COMMIT(i) \
     if constexpr (B_PER > i) { \
         const int o = (r0 + RPG * i) * ROWB + kq * 8; \
-        if constexpr (PREC == 2) { \
+        if constexpr (F16) { \
+            cvt_store(b_hi + o, rb##i); \
+        } else if constexpr (PREC == 2) { \
             *reinterpret_cast<float2*>(b_hi + o) = make_float2(rb##i.x, rb##i.y); \
             *reinterpret_cast<float2*>(b_lo + o) = make_float2(rb##i.z, rb##i.w); \
         } else if constexpr (PREC == 4) { \
@@ -460,7 +491,21 @@ __global__ __launch_bounds__(256 * KS, (BK == 16 && KS == 1) ? ((PREC == 3 || PR
         };
 
         auto step = [&](int c, int ky, int kx) __attribute__((always_inline)) {
-            if constexpr (X6) {
+            if constexpr (F16) {
+                // fp16 on the patch: one piece per operand, one v_mfma_f32_32x32x16_f16 per (i, j) and tap of the 16-channel slab
+                typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+                const char* a0 = reinterpret_cast<const char*>(Apatch) + (ky * PWH + kx) * ROWB;
+                const char* b0 = reinterpret_cast<const char*>(Bst + (c & 1) * BSTAGE);
+                f16x8 fa[TM], fb[TN];
+#pragma unroll
+                for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const f16x8*>(a0 + afr[i]);
+#pragma unroll
+                for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const f16x8*>(b0 + bfr[j]);
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+            } else if constexpr (X6) {
                 // bf16x6 on the patch: pieces (hi, mid, lo) in that order; the six products of weight >= 2^-16, smallest first
                 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
                 const char* a0 = reinterpret_cast<const char*>(Apatch) + (ky * PWH + kx) * ROWB;
@@ -717,8 +762,25 @@ __global__ __launch_bounds__(256 * KS, (BK == 16 && KS == 1) ? ((PREC == 3 || PR
         *reinterpret_cast<b4*>(lo_row) = l;
     };
 
+    // fp32 -> fp16, round-to-nearest-even (v_cvt_pk_f16_f32); beyond +-65504 the result is an infinity
+    auto cvt_store = [&](char* row, float4 v) __attribute__((always_inline)) {
+        typedef float f4 __attribute__((ext_vector_type(4)));
+        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+        const f4 x = {v.x, v.y, v.z, v.w};
+        *reinterpret_cast<h4*>(row) = __builtin_convertvector(x, h4);
+    };
+
     auto commit = [&](float* stage) __attribute__((always_inline)) {
-        if constexpr (X6) {
+        if constexpr (F16) {
+            char* a0 = reinterpret_cast<char*>(stage);
+            char* b0 = a0 + BM * ROWB;
+#pragma unroll
+            for (int i = 0; i < A_PER; ++i) cvt_store(a0 + (r0 + RPG * i) * ROWB + kq * 8, norm_a(i));
+#define OFX_B_COMMIT(i) \
+    if constexpr (B_PER > i) cvt_store(b0 + (r0 + RPG * i) * ROWB + kq * 8, rb##i);
+            OFX_B_COMMIT(0) OFX_B_COMMIT(1) OFX_B_COMMIT(2) OFX_B_COMMIT(3)
+#undef OFX_B_COMMIT
+        } else if constexpr (X6) {
             char* a0 = reinterpret_cast<char*>(stage);
             char* b0 = a0 + 3 * BM * ROWB;
 #pragma unroll
@@ -807,6 +869,25 @@ __global__ __launch_bounds__(256 * KS, (BK == 16 && KS == 1) ? ((PREC == 3 || PR
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].z, fb[j].z, acc[i][j], 0, 0, 0);
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].w, fb[j].w, acc[i][j], 0, 0, 0);
                     }
+            }
+        } else if constexpr (F16) {
+            // fp16: acc += a*b on v_mfma_f32_32x32x16_f16 (fp32 accumulate), the fragment mapping of the bf16 paths: lane l supplies
+            // row (l & 31) and the 8 consecutive k of group (l >> 5)
+            typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+            const char* a0 = reinterpret_cast<const char*>(smem + (kt & 1) * STAGE);
+            const char* b0 = a0 + BM * ROWB;
+#pragma unroll
+            for (int ks = 0; ks < BK / 16; ++ks) {
+                f16x8 fa[TM], fb[TN];
+                const int ko = ks * 32 + (lane >> 5) * 16;
+#pragma unroll
+                for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const f16x8*>(a0 + (wm * WM + i * 32 + frag_row) * ROWB + ko);
+#pragma unroll
+                for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const f16x8*>(b0 + (wn * WN + j * 32 + frag_row) * ROWB + ko);
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[j], acc[i][j], 0, 0, 0);
             }
         } else if constexpr (X6) {
             // bf16x6: the six products of weight >= 2^-16, smallest first, fp32 accumulate
@@ -1185,14 +1266,21 @@ __global__ __launch_bounds__(256 * KS, (BK == 16 && KS == 1) ? ((PREC == 3 || PR
 constexpr bool tile_has_patch(int BM, int BN, int BK, int PREC, int KS, bool SK) {
     return KS == 1 && ((PREC == 0 && BM == 128 && BK == 16 && !SK && (BN == 64 || BN == 96 || BN == 128 || BN == 192)) || (PREC == 0 && BM == 64 && BN == 64 && BK == 32) ||
                        (PREC == 0 && BM == 256 && BN == 64 && BK == 16 && !SK) ||
-                       ((PREC == 1 || PREC == 2 || PREC == 3 || PREC == 4) && BM == 128 && BK == 16 && !SK && (BN == 64 || BN == 128)));
+                       ((PREC == 1 || PREC == 2 || PREC == 3 || PREC == 4 || PREC == OFX_PREC_F16) && BM == 128 && BK == 16 && !SK && (BN == 64 || BN == 128)) ||
+                       (PREC == OFX_PREC_F16 && BM == 64 && BN == 64 && BK == 16 && !SK));   // fp16: also the 64x64 tile, on 8x8 patches
 }
-constexpr bool tile_has_scalar(int BN, int PREC) { return PREC == 0 && BN != 192; }   // the 128x192 tile measured 0.8 % slower with scalar chunk coordinates
+constexpr bool tile_has_scalar(int BN, int PREC) { return (PREC == 0 && BN != 192) || PREC == OFX_PREC_F16; }   // the 128x192 tile measured 0.8 % slower with scalar chunk coordinates
 
 template <int BM, int BN, int WM, int WN, int BK, int PREC, int KS, bool SK, int UK>
 int launch_tile_uk(const ConvK& k, int epi, bool norm, int nz, hipStream_t s, hipEvent_t ev) {
     dim3 grid((unsigned)(k.mtiles * k.ntiles * (k.ksplit > 1 ? k.ksplit : 1)), (unsigned)nz, 1);
     dim3 block(256 * KS, 1, 1);
+    if constexpr (PREC == OFX_PREC_F16) {   // the plain epilogue only (conv_validate has rejected the rest): nothing else is instantiated
+        if (epi != OFX_EPI_PLAIN || norm) return OFX_EINVAL;
+        if (k.act >= OFX_ACT_SIGMOID) OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, kEpiPlainT, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
+        else OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_PLAIN, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
+        return ofx_launch_status();
+    } else
     switch (epi) {
         case OFX_EPI_PLAIN:
             if (k.act >= OFX_ACT_SIGMOID) {
@@ -1250,6 +1338,11 @@ const TileInst kTiles[] = {
     OFX_TILE(128, 64, 64, 32, 16, 3, 1, false),  OFX_TILE(64, 64, 32, 32, 16, 3, 1, false),   OFX_TILE(128, 128, 64, 64, 32, 1, 1, false),
     OFX_TILE(128, 64, 64, 32, 16, 2, 1, false),  OFX_TILE(128, 64, 64, 32, 16, 1, 1, false),  OFX_TILE(64, 64, 32, 32, 16, 2, 1, false),
     OFX_TILE(64, 64, 32, 32, 16, 1, 1, false),
+    // fp16 (opt-in, the UNet's precision="fp16"): the same three tiles.  The halo patch walks 16-channel slabs (BK = 16); off it
+    // (general / scalar-coordinate schedules) the plan takes BK = 32, and BK = 16 is the other arm of that choice, reached by a
+    // forced tile (tile = 16e6 + ...) or OFX_CONV_F16_BK=16
+    OFX_TILE(128, 128, 64, 64, 16, 5, 1, false), OFX_TILE(128, 64, 64, 32, 16, 5, 1, false),  OFX_TILE(64, 64, 32, 32, 16, 5, 1, false),
+    OFX_TILE(128, 128, 64, 64, 32, 5, 1, false), OFX_TILE(128, 64, 64, 32, 32, 5, 1, false),  OFX_TILE(64, 64, 32, 32, 32, 5, 1, false),
 #endif
     // BK = 16 keeps LDS at 40 KB and registers under 128 for the 128x128 tile -> 4 workgroups per CU (3 for 128x192); the
     // extra resident wave per SIMD hides the commit/barrier/issue phases better than a longer chunk does
@@ -1275,6 +1368,7 @@ struct ConvKnobs {
     double patch_max_waste = 1.09;             // OFX_PATCH_MAX_WASTE: largest cover of a map by overhanging patches
     long vol_group_m = 0;                      // OFX_VOL_GROUP_M: raster probe, M-tiles per group of the wide-N volume GEMM (0: the rule)
     long pair_max = 320;                       // OFX_CONV_PAIR_MAX: largest grid that pairs the 64x64 pipelines (0: never)
+    long f16_bk = 0;                           // OFX_CONV_F16_BK: A/B switch, 16 or 32 = the chunk length of every fp16 launch off the halo patch (0: the rule)
 };
 
 const ConvKnobs& conv_knobs() {
@@ -1299,6 +1393,8 @@ const ConvKnobs& conv_knobs() {
         k.patch_max_waste = number("OFX_PATCH_MAX_WASTE", 1.0, 1e30, k.patch_max_waste);
         k.vol_group_m = count("OFX_VOL_GROUP_M", k.vol_group_m);
         k.pair_max = count("OFX_CONV_PAIR_MAX", k.pair_max);
+        k.f16_bk = count("OFX_CONV_F16_BK", 0);
+        if (k.f16_bk != 16 && k.f16_bk != 32) k.f16_bk = 0;
         return k;
     }();
     return knobs;
@@ -1319,7 +1415,7 @@ int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, C
     const int nz = d->nz > 1 ? d->nz : 1, cin = d->c0 + d->c1;
     const int K = d->KH * d->KW * cin, Kpad = ((K + kKAlign - 1) / kKAlign) * kKAlign;
     const long M = (long)d->B * d->Hout * d->Wout;
-    const bool want_stats = x.stats_rows != nullptr, pool = x.pool.out != nullptr, fp32 = d->precision == OFX_PREC_FP32;
+    const bool want_stats = x.stats_rows != nullptr, pool = x.pool.out != nullptr, fp32 = d->precision == OFX_PREC_FP32, f16 = d->precision == OFX_PREC_F16;
     p->name = nz > 1 ? "igemm_corr_volume"
               : d->epi == OFX_EPI_GRU_ZR ? "igemm_conv_gru_zr"
               : d->epi == OFX_EPI_GRU_Q  ? "igemm_conv_gru_q"
@@ -1428,8 +1524,9 @@ int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, C
     const int bk = tile_bk ? tile_bk : ((bn == 32 || bm == 64) ? 32 : 16);
     // uniform-K fast path: every chunk of this launch's BK inside one tap and one segment (the 16-float flow rows of convf1 qualify
     // with BK = 16; a caller-forced tile keeps the conservative multiple-of-32 rule)
-    // (`bk` is the BK of the fp32 tile; the split-bf16 remap further down changes tiles, but only PREC == 0 has the
-    // scalar-coordinate schedule, so `uk` is never read for a tile it was not derived from)
+    // (`bk` is the BK of the fp32 tile; the split-bf16 remap further down changes tiles, but of those arithmetics only fp16 has the
+    // scalar-coordinate schedule, and it derives its own flag from its own tile below: `uk` is never read for a tile it was not
+    // derived from)
     const int ukm = d->tile ? 32 : bk;
     const bool uk = !kn.no_uk && fp32 && cin % ukm == 0 && (d->c1 == 0 || d->c0 % ukm == 0);
     // halo-patch kernel: stride-1 3x3 / 1x5 / 5x1, "same" padding, the map a whole number of 8x16 patches, whole 16-channel slabs
@@ -1470,10 +1567,12 @@ int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, C
         ntiles = (d->Cout + bn - 1) / bn;
         // bf16x3 on the halo patch (128-row tiles, BK = 16): the fp32 -> (hi, lo) conversion of the A side then runs once per
         // 16-channel slab instead of once per tap
-        const bool whole16 = d->Hin % 8 == 0 && d->Win % 16 == 0;
-        patch = !kn.no_patch && (whole16 || d->tile != 0 || cover(8, 16) <= kn.patch_max_waste) && shape_ok && same && cin % 16 == 0 &&
-                (d->c1 == 0 || d->c0 % 16 == 0) && (!d->nmean || d->c1 == 0) && nz == 1 && bm == 128 && tile_bk != 32 && d->epi != OFX_EPI_FLOW;
-        mtiles = patch && !whole16 ? d->B * ((d->Hin + 7) / 8) * ((d->Win + 15) / 16) : (int)((M + bm - 1) / bm);
+        // (fp16 also has the 64x64 tile there, on 8x8 patches)
+        const int pw16 = bm == 64 ? 8 : 16;
+        const bool whole16 = d->Hin % 8 == 0 && d->Win % pw16 == 0;
+        patch = !kn.no_patch && (whole16 || d->tile != 0 || cover(8, pw16) <= kn.patch_max_waste) && shape_ok && same && cin % 16 == 0 &&
+                (d->c1 == 0 || d->c0 % 16 == 0) && (!d->nmean || d->c1 == 0) && nz == 1 && (bm == 128 || (f16 && bm == 64)) && tile_bk != 32 && d->epi != OFX_EPI_FLOW;
+        mtiles = patch && !whole16 ? d->B * ((d->Hin + 7) / 8) * ((d->Win + pw16 - 1) / pw16) : (int)((M + bm - 1) / bm);
     }
     // statistics from the accumulators: raw outputs only, tiles that stay inside one image; of the tile the launch ends up with
     if (want_stats) {
@@ -1494,6 +1593,10 @@ int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, C
         if (prec == OFX_PREC_BF16X6_W) prec = OFX_PREC_BF16X6;   // (its B operand is data, never pre-split)
     } else if (!fp32) {
         if (prec == OFX_PREC_BF16X3 && bm == 128 && bn == 128 && tile_bk == 32) lbk = 32;
+        // fp16: the chunk length off the halo patch (its slabs are 16 channels) -- a forced tile's, the A/B switch's, else the rule.
+        // BK = 32 halves the barriers per MFMA at 8 KB more LDS per workgroup; a K of a single 16-wide chunk has nothing to gain from
+        // it.  OFX_CONV_F16_BK is the A/B switch of this rule (profiles/r23_unet_f16_rate.txt, section 2)
+        if (f16 && !patch) lbk = tile_bk ? tile_bk : kn.f16_bk ? (int)kn.f16_bk : K > 16 ? 32 : 16;
     } else if (bm == 128 && bn == 32) {
         lbk = 32;
     } else if (!(bm == 256 && bn == 64) && !(bm == 128 && (bn == 192 || bn == 96))) {
@@ -1505,6 +1608,8 @@ int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, C
             if (d->tile >= 2000000000 || (d->tile < 1000000 && blocks <= kn.pair_max && Kpad >= 8 * 32)) ks = 2;
         }
     }
+    // fp16 takes the scalar-coordinate schedule by the chunk length of ITS tile (the 1x1 GEMMs of the transformers, the strided layers)
+    const bool uk16 = f16 && !kn.no_uk && cin % lbk == 0 && (d->c1 == 0 || d->c0 % lbk == 0);
     const bool sk = p->ksplit > 1;
     for (int i = 0; i < (int)(sizeof kTiles / sizeof kTiles[0]) && p->inst < 0; ++i) {
         const TileInst& t = kTiles[i];
@@ -1513,7 +1618,7 @@ int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, C
     OFX_REQUIRE(p->inst >= 0, OFX_EINVAL);
     const TileInst& t = kTiles[p->inst];
     p->bm = bm; p->bn = bn; p->wm = t.wm; p->wn = t.wn; p->bk = lbk; p->prec = prec; p->ks = ks;
-    p->mode = (patch && !pool && tile_has_patch(bm, bn, lbk, prec, ks, sk)) ? 2 : (uk && tile_has_scalar(bn, prec)) ? 1 : 0;
+    p->mode = (patch && !pool && tile_has_patch(bm, bn, lbk, prec, ks, sk)) ? 2 : ((uk || uk16) && tile_has_scalar(bn, prec)) ? 1 : 0;
     p->mtiles = mtiles; p->ntiles = ntiles;
     p->group_m = (pool && fp32 && kn.vol_group_m > 0) ? (int)kn.vol_group_m : ntiles >= 8 ? 8 : 1;
     return 0;
@@ -1540,7 +1645,11 @@ int conv_validate(const ofx_conv_desc* d, const ConvExtra& x, long* split_rows) 
     }
     if (d->addend) OFX_REQUIRE(d->ldadd >= d->Cout, OFX_EINVAL);
     const int nz = d->nz > 1 ? d->nz : 1;
-    OFX_REQUIRE(d->precision >= OFX_PREC_FP32 && d->precision <= OFX_PREC_BF16X6_W, OFX_EINVAL);
+    OFX_REQUIRE(d->precision >= OFX_PREC_FP32 && d->precision <= OFX_PREC_F16, OFX_EINVAL);
+    // OFX_PREC_F16 serves the plain epilogue of one convolution: no gate / flow epilogue, fused norm, epilogue statistics, pooled
+    // volume, batched GEMM, split-K workspace or paired pipelines (none of those kernels is instantiated in this arithmetic)
+    if (d->precision == OFX_PREC_F16)
+        OFX_REQUIRE(d->epi == OFX_EPI_PLAIN && !d->nmean && !x.stats_rows && !x.pool.out && nz == 1 && !d->splitk_ws && d->tile < 2000000000, OFX_EINVAL);
     // OFX_PREC_BF16X6_W: the kernel finds the lo pieces of the pre-split matrix at w + Cout * Kpad * 4 -- true only for the WHOLE matrix
     // `ofx_split_conv_weight3` converted (Cout = its row count) of ONE problem; a batched GEMM advances w per problem
     if (d->precision == OFX_PREC_BF16X6_W) OFX_REQUIRE(nz == 1, OFX_EINVAL);

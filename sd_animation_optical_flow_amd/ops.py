@@ -300,6 +300,12 @@ def split_conv_weight3(w_packed: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# conv2d_nhwc(precision=) -> OFX_PREC_*.  *_w: the weight comes from split_conv_weight / split_conv_weight3.  "fp16": both operands
+# rounded to half as they are staged, fp32 accumulate (OFX_PREC_F16; plain fp32 [Cout, Kpad] weights, fp32 activations and epilogue;
+# no nmean / stats_part / splitk_ws)
+CONV_PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16x3_w": 2, "bf16x6": 3, "bf16x6_w": 4, "fp16": 5}
+
+
 def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout: int, *, stride: int = 1,
                 shift: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None, act: Optional[str] = None,
                 x2: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
@@ -317,6 +323,7 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
     F(4x4,3x3) kernel where its grid pays (tile = TILE_WINOGRAD4 forces it).  `out` [B,Hout,Wout,C >= out_off + cout]: write channels
     [out_off, out_off + cout) of it.  `stats_part` (f32 on the device): run ofx_conv2d_stats, which leaves the per-channel
     (sum, sum of squares) partials of the outputs there when the launch can produce them ([B][rows][cout][2]; see inorm_finalize).
+    `precision`: a key of CONV_PRECISIONS (default exact fp32).
     Returns [B,Hout,Wout,cout], or `out`; with `stats_part`, (that, rows per image), rows = 0 when none were produced."""
     x = _chk(x, "x", torch.float32)
     B, H, W, c0 = x.shape
@@ -355,7 +362,7 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
     d.B, d.Hin, d.Win, d.Hout, d.Wout, d.Cout = B, H, W, Ho, Wo, cout
     d.KH, d.KW, d.stride, d.padH, d.padW = kh, kw, stride, ph, pw
     d.act, d.epi, d.tile = ACTS[act], EPI_PLAIN, tile
-    d.precision = {"fp32": 0, "bf16x3": 1, "bf16x3_w": 2, "bf16x6": 3, "bf16x6_w": 4}[precision]   # *_w: weight from split_conv_weight(3)
+    d.precision = CONV_PRECISIONS[precision]
     if splitk_ws is not None:       # uint8 scratch whose first 64 KiB are zero (see ofx_conv_desc.splitk_ws): allows split-K
         ws = _chk(splitk_ws, "splitk_ws", torch.uint8)
         d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), ws.numel()

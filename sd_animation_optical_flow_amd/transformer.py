@@ -13,6 +13,12 @@ of the self-attention are one GEMM into one [B, N, 3*inner] buffer whose thirds 
 permuted or copied between layouts anywhere but at the NCHW edges of `forward`.  The K/V history stays on the device, as
 [B, N, inner] tensors (`to_reference_layout` gives the reference's [(b h), n, d]).
 
+`precision=` ("fp32" default, "fp16", "bf16x3", "bf16x6") chooses the arithmetic of the GEMMs alone: `proj_in` / `proj_out`, the
+q / k / v / out projections and the two feed-forward GEMMs.  "fp16" rounds both operands of each to half as the kernel stages them
+and accumulates in fp32 (what torch.autocast gives the reference's Linears); the split-bf16 modes are the launcher's existing ones.
+GroupNorm, LayerNorm, GEGLU, the attention (softmax included) and every activation in memory stay fp32 in every precision -- closer
+to float64 than autocast, which also rounds each layer's output and runs attention in half.
+
 OFX_ST_TORCH_GLUE=1 in the environment (read once per process; the A/B baseline and a diagnostic): LayerNorm and GEGLU through
 torch.nn.functional, attention through permute + `ops.attention`, i.e. the glue this module replaces.  Head sizes the fused kernel
 does not take (`FUSED_HEAD_SIZES`) go the permute + `ops.attention` way on their own.
@@ -35,6 +41,14 @@ import torch.nn.functional as F
 from . import ops
 
 FUSED_HEAD_SIZES = (40, 64, 80, 128, 160)      # ofx_attention_flash_ok (csrc/attn_flash.hip)
+# `precision=` of SpatialTransformer / UNetModel: the arithmetic of every `ops.conv2d_nhwc` contraction (weights stay plain fp32)
+MODEL_PRECISIONS = ("fp32", "fp16", "bf16x3", "bf16x6")
+
+
+def check_precision(precision) -> str:
+    if precision not in MODEL_PRECISIONS:
+        raise ValueError(f"precision must be one of {MODEL_PRECISIONS}, got {precision!r}")
+    return precision
 
 
 def spatial_transformer_tensors(in_channels: int, n_heads: int, d_head: int, context_dim: Optional[int], depth: int = 1
@@ -146,7 +160,8 @@ class SpatialTransformer:
     """`ldm.modules.attention.SpatialTransformer` (use_linear=False, inference) on a HIP device."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], n_heads: int, d_head: int, device="cuda", prefix: str = "",
-                 use_linear: bool = False):
+                 use_linear: bool = False, precision: str = "fp32"):
+        self.precision = check_precision(precision)                # before the checkpoint is looked at or a device asked for
         if use_linear:
             raise NotImplementedError("use_linear=True (Linear proj_in / proj_out) is not what guided_ldm_*_v15.yaml builds")
         if not torch.cuda.is_available():
@@ -202,7 +217,7 @@ class SpatialTransformer:
         w = self.w[f"{name}.weight"]
         co = w.shape[0]
         out = ops.conv2d_nhwc(x.view(B, 1, N, K), w, 1, 1, co, shift=self.w[f"{name}.bias"] if bias else None,
-                              addend=None if addend is None else addend.view(B, 1, N, co))
+                              addend=None if addend is None else addend.view(B, 1, N, co), precision=self.precision)
         return out.view(B, N, co)
 
     def _layernorm(self, name: str, x: torch.Tensor) -> torch.Tensor:
@@ -306,13 +321,14 @@ class SpatialTransformer:
         ctxs = self._contexts(context, B)
         ref = self._reference_kv(reference_kv, B, N)               # raises before any launch
         t = ops.groupnorm(x, self.w["norm.weight"], self.w["norm.bias"], 32, 1e-6, False)
-        t = ops.conv2d_nhwc(t, self.w["proj_in.weight"], 1, 1, self.inner, shift=self.w["proj_in.bias"]).view(B, N, self.inner)
+        t = ops.conv2d_nhwc(t, self.w["proj_in.weight"], 1, 1, self.inner, shift=self.w["proj_in.bias"],
+                            precision=self.precision).view(B, N, self.inner)
         kv_hists = []
         for i in range(self.depth):
             t, kv = self._block(i, t, ctxs[i], ref)
             kv_hists.append(kv)
         out = ops.conv2d_nhwc(t.view(B, h, w, self.inner), self.w["proj_out.weight"], 1, 1, self.in_channels,
-                              shift=self.w["proj_out.bias"], addend=x)
+                              shift=self.w["proj_out.bias"], addend=x, precision=self.precision)
         return out, kv_hists
 
     @torch.no_grad()

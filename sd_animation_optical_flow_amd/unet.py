@@ -28,6 +28,16 @@ Two deliberate differences from the reference:
 Not built (NotImplementedError): use_scale_shift_norm, resblock_updown, num_classes, use_linear_in_transformer, AttentionBlock
 (use_spatial_transformer=False), conv_resample=False, dims != 2.
 
+`UNetModel(precision=)` ("fp32" default, "fp16", "bf16x3", "bf16x6"; `model.precision`) is the arithmetic of every `ofx_conv2d`
+of the model: the 3x3, 1x1 and stride-2 convolutions, `skip_connection`, and through `SpatialTransformer(precision=)` `proj_in` /
+`proj_out`, the q / k / v / out projections and the feed-forward GEMMs.  "fp16" is the reference's own mode for this stage (it runs
+under torch.autocast): both operands of a contraction rounded to half as the kernel stages them, one product on the fp16 matrix
+cores, fp32 accumulation.  These stay fp32 in every precision: `ops.upconv2x` (Upsample), attention and its softmax, GroupNorm,
+LayerNorm, GEGLU, the timestep path (`ops.timestep_embedding`, `ops.emb_linear`), every weight and every activation in memory --
+so the model is closer to float64 than autocast, which also rounds each layer's output to half and runs attention in half.
+"bf16x3" / "bf16x6" are the launcher's split-bf16 kernels on the fly.  The default is bit for bit what the model computed before
+the argument existed.
+
 OFX_UNET_TORCH_GLUE=1 in the environment (read once per process; the A/B baseline and a diagnostic): the composition that was
 possible before `groupnorm_cat` / `emb_linear` / `timestep_embedding` existed -- `torch.cat` + `ops.groupnorm`, the emb term as a
 torch broadcast add, the timestep path through torch.nn.functional.
@@ -46,7 +56,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .transformer import SpatialTransformer, plan_reference_kv, spatial_transformer_tensors
+from .transformer import MODEL_PRECISIONS, SpatialTransformer, check_precision, plan_reference_kv, spatial_transformer_tensors
 
 # `unet_config` of guided_ldm_inpaint_v15.yaml (in_channels 9) / guided_ldm_v15.yaml (in_channels 4)
 SD_V15_UNET = dict(in_channels=9, out_channels=4, model_channels=320, attention_resolutions=(4, 2, 1), num_res_blocks=2,
@@ -205,9 +215,12 @@ def route_reference_kv(reference_kv, n_transformers: int) -> List[list]:
 
 
 class UNetModel:
-    """`ldm.modules.diffusionmodules.openaimodel.UNetModel` with `ControlledUnetModel.forward` (inference, fp32) on a HIP device."""
+    """`ldm.modules.diffusionmodules.openaimodel.UNetModel` with `ControlledUnetModel.forward` (inference) on a HIP device.
+    `precision`: the arithmetic of the convolutions and GEMMs, one of MODEL_PRECISIONS (module docstring); everything else is fp32."""
 
-    def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: dict = SD_V15_UNET, device="cuda", prefix: str = "model.diffusion_model."):
+    def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: dict = SD_V15_UNET, device="cuda", prefix: str = "model.diffusion_model.",
+                 precision: str = "fp32"):
+        self.precision = check_precision(precision)                # before the checkpoint is looked at or a device asked for
         self.layout = unet_layout(cfg)
         self.cfg = self.layout["cfg"]
         c = self.cfg
@@ -240,7 +253,7 @@ class UNetModel:
             kind, name = l[0], l[1]
             if kind == "st":
                 sub = {k[len(name) + 1:]: v for k, v in t32.items() if k.startswith(name + ".")}
-                self.st[name] = SpatialTransformer(sub, l[3], l[4], device=self.device)
+                self.st[name] = SpatialTransformer(sub, l[3], l[4], device=self.device, precision=self.precision)
             elif kind == "res":
                 emb_w.append(t32[f"{name}.emb_layers.1.weight"])
                 emb_b.append(t32[f"{name}.emb_layers.1.bias"])
@@ -267,7 +280,8 @@ class UNetModel:
     def _conv(self, name: str, x: torch.Tensor, k: int, stride: int = 1, addend: Optional[torch.Tensor] = None,
               x2: Optional[torch.Tensor] = None) -> torch.Tensor:
         w = self.w[f"{name}.weight"]
-        return ops.conv2d_nhwc(x, w, k, k, w.shape[0], stride=stride, shift=self.w[f"{name}.bias"], addend=addend, x2=x2)
+        return ops.conv2d_nhwc(x, w, k, k, w.shape[0], stride=stride, shift=self.w[f"{name}.bias"], addend=addend, x2=x2,
+                               precision=self.precision)
 
     def _norm(self, name: str, x: torch.Tensor, x1: Optional[torch.Tensor] = None, e: Optional[torch.Tensor] = None,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:

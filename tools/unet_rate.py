@@ -16,11 +16,16 @@ library for `--reps` more forwards: ms per forward and launches per forward by k
 cat / add / linear, the control additions) are not in that table; their time is in the ms per forward.  The event pairs serialise
 the launches, so the table's sum exceeds the timed figure's share.
 
+--precision A,B,...: compare `UNetModel(precision=)` values instead (each of "fp32", "fp16", "bf16x3", "bf16x6"; the default path, no
+glue), in alternating fresh processes, rounds and statistics as above; the first one named is the baseline of the ratios, and every
+variant gets its launch table.  The fp32 row is measured in the same session as the others, never copied.
+
 --sincos-probe PATH: also run the cosf / sinf probe (tools/sincos_probe.hip, built beforehand) over the arguments of the
 timestep-embedding test grid (tests/unet_check.sincos_arguments) and report the device's worst error against float64 in units of
 2^-24: Y_SINCOS.
 
     python tools/unet_rate.py [--out profiles/r20_unet_rate.txt] [--sincos-probe ./sincos_probe]
+    python tools/unet_rate.py --precision fp32,bf16x3,fp16 [--out profiles/r23_unet_f16_rate.txt]
 """
 import argparse
 import json
@@ -41,19 +46,19 @@ KINDS = (("convolutions and the transformers' GEMMs", ("igemm_conv",)), ("upconv
          ("geglu", ("geglu",)))
 
 
-def child(reps: int, warmup: int, profile: bool) -> None:
+def child(reps: int, warmup: int, profile: bool, precision: str) -> None:
     import torch
     from sd_animation_optical_flow_amd import ops
     from sd_animation_optical_flow_amd import unet as UN
     assert torch.cuda.is_available(), "a GPU is needed: nothing here is measured on the host"
     cfg = UN.SD_V15_UNET
-    model = UN.UNetModel(UN.random_unet_state_dict(0, cfg), cfg, prefix="")
+    model = UN.UNetModel(UN.random_unet_state_dict(0, cfg), cfg, prefix="", precision=precision)
     g = torch.Generator().manual_seed(20)
     x = torch.randn((BATCH, LAT_H, LAT_W, cfg["in_channels"]), generator=g).cuda()
     t = torch.tensor([981.0, 981.0]).cuda()
     ctx = torch.randn((BATCH, CTX_TOKENS, cfg["context_dim"]), generator=g).cuda()
     out, hist = model.forward_nhwc(x, t, ctx)
-    res = {"glue": UN._torch_glue(), "checksum": float(out.double().abs().mean()), "transformers": len(hist)}
+    res = {"glue": UN._torch_glue(), "precision": model.precision, "checksum": float(out.double().abs().mean()), "transformers": len(hist)}
     for _ in range(warmup):
         model.forward_nhwc(x, t, ctx)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -96,6 +101,63 @@ def measure_sincos(probe: str) -> str:
             f"float32 cos / sin on the host over the same arguments: {float(host[0].max()):.3f} / {float(host[1].max()):.3f})\n")
 
 
+def kernel_table(label: str, k: dict, reps: int) -> list:
+    lines = [f"{label}: the library's launches per forward, event profiler over {reps} forwards"]
+    tot_ms, tot_n = 0.0, 0.0
+    rows = [(lab, names) for lab, names in KINDS]
+    rows.append(("the rest", tuple(n for n in k if not any(n in names for _, names in KINDS))))
+    for lab, names in rows:
+        ms = sum(k[n]["ms"] for n in names if n in k) / reps
+        n = sum(k[n]["calls"] for n in names if n in k) / reps
+        tot_ms, tot_n = tot_ms + ms, tot_n + n
+        if n:
+            lines.append(f"  {lab:44s} {ms:9.3f} ms  {n:7.1f} launches  {1e3 * ms / n:8.1f} us each")
+    lines.append(f"  {'all':44s} {tot_ms:9.3f} ms  {tot_n:7.1f} launches")
+    lines.append("")
+    return lines
+
+
+def run_child(a, rnd: int, env: dict, precision: str) -> dict:
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--reps", str(a.reps), "--warmup", str(a.warmup), "--child-precision", precision]
+    if rnd == a.rounds - 1:
+        cmd.append("--profile")
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420)
+    if r.returncode != 0:
+        sys.exit(f"child failed ({r.returncode}); nothing further is started\n{r.stdout}\n{r.stderr}")
+    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+
+
+def compare_precisions(a) -> str:
+    precs = [p.strip() for p in a.precision.split(",") if p.strip()]
+    runs = {p: [] for p in precs}
+    for rnd in range(a.rounds):
+        for p in precs:
+            res = run_child(a, rnd, dict(os.environ, OFX_UNET_TORCH_GLUE="0"), p)
+            assert res["precision"] == p and not res["glue"]
+            runs[p].append(res)
+            print(f"round {rnd} {p}: {res['ms']:.3f} ms", flush=True)
+    stat = lambda v: f"{sum(v) / len(v):8.3f} [{min(v):7.3f} .. {max(v):7.3f}]"
+    ms = {p: [r["ms"] for r in runs[p]] for p in precs}
+    mean = {p: sum(v) / len(v) for p, v in ms.items()}
+    base = precs[0]
+    lines = [f"UNetModel.forward_nhwc(precision=), SD v1.5 configuration (in_channels 9, {runs[base][0]['transformers']} transformers), seeded "
+             f"weights, batch {BATCH}, latent {LAT_H} x {LAT_W}, context {CTX_TOKENS} x 768; ms per forward, device events over {a.reps} forwards, "
+             f"mean of {a.rounds} rounds [fastest .. slowest], the precisions in alternating fresh processes of one session", ""]
+    for p in precs:
+        lines.append(f"  {p:7s} {stat(ms[p])} ms   mean |out| {runs[p][0]['checksum']:.6f}")
+    lines.append("")
+    for p in precs[1:]:
+        clear = max(ms[p]) < min(ms[base]) or min(ms[p]) > max(ms[base])
+        lines.append(f"  {base} / {p} = {mean[base] / mean[p]:.3f}   ({'the brackets do not overlap' if clear else 'THE BRACKETS OVERLAP: inside the run-to-run spread'})")
+    for i, p in enumerate(precs[1:], 1):
+        for q in precs[i + 1:]:
+            lines.append(f"  {p} / {q} = {mean[p] / mean[q]:.3f}")
+    lines.append("")
+    for p in precs:
+        lines += kernel_table(p, runs[p][-1].get("kernels", {}), a.reps)
+    return "\n".join(lines)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -105,21 +167,23 @@ def main() -> None:
     ap.add_argument("--sincos-probe")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--precision", help="comma-separated UNetModel precisions to compare, the baseline first (e.g. fp32,bf16x3,fp16)")
+    ap.add_argument("--child-precision", default="fp32")
     a = ap.parse_args()
     if a.child:
-        child(a.reps, a.warmup, a.profile)
+        child(a.reps, a.warmup, a.profile, a.child_precision)
+        return
+    if a.precision:
+        text = compare_precisions(a)
+        print(text)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(text + "\n")
         return
     runs = {False: [], True: []}
     for rnd in range(a.rounds):
         for glue in (False, True):
-            env = dict(os.environ, OFX_UNET_TORCH_GLUE="1" if glue else "0")
-            cmd = [sys.executable, os.path.abspath(__file__), "--child", "--reps", str(a.reps), "--warmup", str(a.warmup)]
-            if rnd == a.rounds - 1:
-                cmd.append("--profile")
-            r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420)
-            if r.returncode != 0:
-                sys.exit(f"child failed ({r.returncode}); nothing further is started\n{r.stdout}\n{r.stderr}")
-            res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+            res = run_child(a, rnd, dict(os.environ, OFX_UNET_TORCH_GLUE="1" if glue else "0"), "fp32")
             assert res["glue"] == glue
             runs[glue].append(res)
             print(f"round {rnd} {'glue' if glue else 'default'}: {res['ms']:.3f} ms", flush=True)
@@ -133,20 +197,7 @@ def main() -> None:
              f"  default {stat(dv)} ms", f"  glue    {stat(gv)} ms", f"  glue / default = {sum(gv) / sum(dv):.3f}",
              f"  mean |out|: default {runs[False][0]['checksum']:.6f}, glue {runs[True][0]['checksum']:.6f}", ""]
     for glue in (False, True):
-        k = runs[glue][-1].get("kernels", {})
-        lines.append(f"{'glue' if glue else 'default'}: the library's launches per forward, event profiler over {a.reps} forwards")
-        seen, tot_ms, tot_n = set(), 0.0, 0.0
-        rows = [(label, names) for label, names in KINDS]
-        rows.append(("the rest", tuple(n for n in k if not any(n in names for _, names in KINDS))))
-        for label, names in rows:
-            ms = sum(k[n]["ms"] for n in names if n in k) / a.reps
-            n = sum(k[n]["calls"] for n in names if n in k) / a.reps
-            seen.update(names)
-            tot_ms, tot_n = tot_ms + ms, tot_n + n
-            if n:
-                lines.append(f"  {label:44s} {ms:9.3f} ms  {n:7.1f} launches  {1e3 * ms / n:8.1f} us each")
-        lines.append(f"  {'all':44s} {tot_ms:9.3f} ms  {tot_n:7.1f} launches")
-        lines.append("")
+        lines += kernel_table("glue" if glue else "default", runs[glue][-1].get("kernels", {}), a.reps)
     if a.sincos_probe:
         lines.append(measure_sincos(a.sincos_probe))
     text = "\n".join(lines)
