@@ -18,10 +18,10 @@
  *   ofx_warp_*                  pdcnet_of.py:34-42 ; ofgen_keyframe_inpaint.py:92-98 (cv2.remap)
  *   ofx_generate_mask, ofx_dilate_u8, ofx_expand_mask, ofx_travel_distance, ofx_flow_magnitude, ofx_merge_images,
  *   ofx_mix_frames, ofx_conf_sum
- *   ofx_groupnorm, ofx_softmax_rows, ofx_attention_f32
+ *   ofx_groupnorm, ofx_softmax_rows, ofx_attention_f32, ofx_attention_prec
  *   ofx_upconv2x, ofx_upsample2x_nearest_f32, ofx_decode_to_u8
  *                               ldm/modules/diffusionmodules/model.py:35-41,152-203 ; ldm/modules/attention.py:314,426
- *   ofx_layernorm, ofx_geglu, ofx_attention_bnhd_f32
+ *   ofx_layernorm, ofx_geglu, ofx_attention_bnhd_f32, ofx_attention_bnhd_prec
  *                               ldm/modules/attention.py:54-56,326-436,456-469,515-537 (SpatialTransformer)
  *                               ofgen_keyframe_inpaint.py:113-133,237-248,306-322,676-688,968-973,995-1027
  *   ofx_groupnorm_cat, ofx_emb_linear, ofx_timestep_embedding
@@ -165,6 +165,22 @@ int ofx_softmax_rows(float* x, long rows, long ld, int n, float scale, const flo
 size_t ofx_attention_workspace_bytes(int BH, int Nq, int Nk, int D);
 int ofx_attention_f32(const float* q, const float* k, const float* v, const float* bias, long bias_bstride, float* out,
                       int BH, int Nq, int Nk, int D, float scale, void* workspace, size_t workspace_bytes, void* stream);
+/* ofx_attention_f32 with the arithmetic of the two matrix products chosen by `precision` (an OFX_PREC_* value, defined below with
+ * the convolutions' modes: 0 and 5 here).
+ *   OFX_PREC_FP32 (0)  ofx_attention_f32 itself, bit for bit (called through).
+ *   OFX_PREC_F16 (5)   opt-in, the fused head sizes D in {40, 64, 80, 128, 160} only -- any other D is OFX_EINVAL before any launch,
+ *       there is no unfused fp16 path; no workspace.  q, k and v stay fp32 in memory; each element is rounded to fp16 once, to
+ *       nearest even (v_cvt_pk_f16_f32), as it is staged; q is rounded UNSCALED.  Magnitudes beyond 65504 become infinities, as
+ *       under torch.autocast; subnormals are not flushed.  K Q^T runs on v_mfma_f32_32x32x16_f16 with fp32 accumulation (D = 40 as
+ *       48 with zero pad columns); the logit is fma(score, scale * log2 e, bias * log2 e) in fp32, so neither the scale nor the bias
+ *       passes through fp16.  The maximum, v_exp_f32, the running sum l (summed from the fp32 probabilities BEFORE they are
+ *       rounded), the O accumulators, the rescale and 1 / l are fp32.  P is rounded to fp16 (nearest even) for P V, also with fp32
+ *       accumulation.  Error on top of the fp32 kernel's: the operand roundings (2^-11 relative each; the tests compare against
+ *       float64 on the rounded operands, where they vanish) and 2^-11 sum_j p_j |v_jd| + 2^-25 sum_j |v_jd| for the rounding of P.
+ *   any other value    OFX_EINVAL before any launch. */
+int ofx_attention_prec(const float* q, const float* k, const float* v, const float* bias, long bias_bstride, float* out,
+                       int BH, int Nq, int Nk, int D, float scale, int precision, void* workspace, size_t workspace_bytes,
+                       void* stream);
 
 /* ---------------------------------------------------------------- SpatialTransformer (ldm/modules/attention.py:472-537) */
 /* nn.LayerNorm(C) over the last axis of `rows` rows (BasicTransformerBlock.norm1 / norm2 / norm3, attention.py:456-458, applied at
@@ -188,6 +204,12 @@ int ofx_geglu(const float* a, int lda, float* out, int ldo, int rows, int inner,
  * same kernel with other addresses: bit-identical to ofx_attention_f32 on the permuted contiguous copies.  No workspace. */
 int ofx_attention_bnhd_f32(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* bias,
                            long bias_bstride, float* out, int ldo, int B, int H, int Nq, int Nk, int D, float scale, void* stream);
+/* ofx_attention_bnhd_f32 with `precision` as in ofx_attention_prec: OFX_PREC_FP32 calls through, bit for bit; OFX_PREC_F16 is the fp16
+ * matrix-core kernel on the same addresses (bit-identical to ofx_attention_prec on the permuted contiguous copies); any other
+ * value is OFX_EINVAL before any launch.  The argument checks of ofx_attention_bnhd_f32 apply unchanged. */
+int ofx_attention_bnhd_prec(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* bias,
+                            long bias_bstride, float* out, int ldo, int B, int H, int Nq, int Nk, int D, float scale, int precision,
+                            void* stream);
 
 /* ---------------------------------------------------------------- first-stage decoder (decode_first_stage / decode_latent) */
 /* `Upsample` of the VAE decoder (ldm/modules/diffusionmodules/model.py:43-58): out = conv3x3(pad 1)(interpolate(x, 2x, nearest)) + bias

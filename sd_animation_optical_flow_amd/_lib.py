@@ -104,9 +104,11 @@ SIGNATURES = {
     "ofx_softmax_rows": (_i, [_p, C.c_long, C.c_long, _i, C.c_float, _p, C.c_long, C.c_long, _p]),
     "ofx_attention_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "ofx_attention_f32": (_i, [_p, _p, _p, _p, C.c_long, _p, _i, _i, _i, _i, C.c_float, _p, C.c_size_t, _p]),
+    "ofx_attention_prec": (_i, [_p, _p, _p, _p, C.c_long, _p, _i, _i, _i, _i, C.c_float, _i, _p, C.c_size_t, _p]),
     "ofx_layernorm": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _f, _p]),
     "ofx_geglu": (_i, [_p, _i, _p, _i, _i, _i, _p]),
     "ofx_attention_bnhd_f32": (_i, [_p, _i, _p, _i, _p, _i, _p, _l, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
+    "ofx_attention_bnhd_prec": (_i, [_p, _i, _p, _i, _p, _i, _p, _l, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
     "ofx_upconv2x_weight": (_l, [_p, _i, _i, _p]),
     "ofx_upconv2x": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "ofx_upsample2x_nearest_f32": (_i, [_p, _p, _i, _i, _i, _i, _p]),

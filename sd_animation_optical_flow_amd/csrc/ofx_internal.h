@@ -91,13 +91,15 @@ int ofx_inorm_finalize_part(const float* part, float* mean, float* rstd, int B, 
 int ofx_inorm_stats_affine(const float* x, int ld, float* mean, float* rstd, float* scratch, int B, long HW, int C, float eps,
                            const float* gamma, const float* beta, hipStream_t stream);
 
-// attn_flash.hip: fused attention for the UNet's head sizes (no workspace)
+// attn_flash.hip: fused attention for the UNet's head sizes (no workspace).  precision: OFX_PREC_FP32 or OFX_PREC_F16 (the fp16
+// matrix-core kernel, ofx_attention_prec); anything else is OFX_EINVAL before any launch
 bool ofx_attention_flash_ok(int D);
 int ofx_attention_flash_launch(const float* q, const float* k, const float* v, const float* bias, long bias_bstride, float* out, int BH, int Nq,
-                               int Nk, int D, float scale, hipStream_t s);
+                               int Nk, int D, float scale, int precision, hipStream_t s);
 // the same kernel on token rows with the heads side by side (ofx_attention_bnhd_f32, transformer.hip validates the arguments)
 int ofx_attention_flash_bnhd_launch(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* bias,
-                                    long bias_bstride, float* out, int ldo, int B, int H, int Nq, int Nk, int D, float scale, hipStream_t s);
+                                    long bias_bstride, float* out, int ldo, int B, int H, int Nq, int Nk, int D, float scale, int precision,
+                                    hipStream_t s);
 
 // corr.hip / net_misc.hip: internal launchers used by the RAFT engine
 int ofx_local_corr_launch(const float* f1, const float* f2, const float* coords, float* out, long sb, long sn,

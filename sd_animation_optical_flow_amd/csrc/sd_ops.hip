@@ -270,7 +270,7 @@ int ofx_attention_f32(const float* q, const float* k, const float* v, const floa
     OFX_REQUIRE(q && k && v && out && BH > 0 && Nq > 0 && Nk > 0 && D > 0, OFX_EINVAL);
     OFX_REQUIRE(D % 4 == 0 && ofx_aligned16(q) && ofx_aligned16(k) && ofx_aligned16(v) && ofx_aligned16(out), OFX_EALIGN);
     if (ofx_attention_flash_ok(D))
-        return ofx_attention_flash_launch(q, k, v, bias, bias_bstride, out, BH, Nq, Nk, D, scale, (hipStream_t)stream);
+        return ofx_attention_flash_launch(q, k, v, bias, bias_bstride, out, BH, Nq, Nk, D, scale, OFX_PREC_FP32, (hipStream_t)stream);
     OFX_REQUIRE(workspace && ofx_aligned16(workspace), OFX_EALIGN);
     OFX_REQUIRE(workspace_bytes >= ofx_attention_workspace_bytes(BH, Nq, Nk, D), OFX_ENOMEM);
     hipStream_t s = (hipStream_t)stream;
@@ -314,6 +314,16 @@ int ofx_attention_f32(const float* q, const float* k, const float* v, const floa
     const long rows = (long)BH * Nq;
     hipLaunchKernelGGL(nan_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, sc, lds, out, rows, D);
     return ofx_launch_status();
+}
+
+int ofx_attention_prec(const float* q, const float* k, const float* v, const float* bias, long bias_bstride, float* out, int BH, int Nq, int Nk,
+                       int D, float scale, int precision, void* workspace, size_t workspace_bytes, void* stream) {
+    if (precision == OFX_PREC_FP32) return ofx_attention_f32(q, k, v, bias, bias_bstride, out, BH, Nq, Nk, D, scale, workspace, workspace_bytes, stream);
+    OFX_REQUIRE(precision == OFX_PREC_F16, OFX_EINVAL);
+    OFX_REQUIRE(q && k && v && out && BH > 0 && Nq > 0 && Nk > 0 && D > 0, OFX_EINVAL);
+    OFX_REQUIRE(ofx_attention_flash_ok(D), OFX_EINVAL);            // there is no unfused fp16 path
+    OFX_REQUIRE(ofx_aligned16(q) && ofx_aligned16(k) && ofx_aligned16(v) && ofx_aligned16(out), OFX_EALIGN);
+    return ofx_attention_flash_launch(q, k, v, bias, bias_bstride, out, BH, Nq, Nk, D, scale, OFX_PREC_F16, (hipStream_t)stream);
 }
 
 }  // extern "C"

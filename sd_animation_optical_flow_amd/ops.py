@@ -805,11 +805,29 @@ def decode_to_u8(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# attention(precision=) / attention_bnhd(precision=) -> OFX_PREC_* of ofx_attention_prec / ofx_attention_bnhd_prec.  "fp16": q, k, v and
+# the probabilities rounded to half (nearest even) as the kernel stages them, both products on the fp16 matrix cores with fp32
+# accumulation, softmax, scale and bias in fp32 (include/ofx.h); the fused head sizes only, tensors stay fp32 in memory.
+ATTENTION_PRECISIONS = {"fp32": 0, "fp16": 5}
+ATTENTION_FUSED_HEAD_SIZES = (40, 64, 80, 128, 160)
+
+
+def check_attention_precision(precision, name: str = "precision") -> str:
+    if not isinstance(precision, str) or precision not in ATTENTION_PRECISIONS:
+        raise ValueError(f"{name} must be one of {tuple(ATTENTION_PRECISIONS)}, got {precision!r}")
+    return precision
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bias: Optional[torch.Tensor] = None,
-              scale: Optional[float] = None, max_workspace_bytes: int = 8 << 30) -> torch.Tensor:
+              scale: Optional[float] = None, max_workspace_bytes: int = 8 << 30, precision: str = "fp32") -> torch.Tensor:
     """softmax(q k^T * scale + bias) v for fp32 [BH,Nq,D] / [BH,Nk,D] tensors; bias [Nq,Nk] (shared) or [BH,Nq,Nk].
     scale defaults to D^-0.5.  Batch-heads are processed in slices that keep the score matrix under
-    `max_workspace_bytes`."""
+    `max_workspace_bytes`.  precision: "fp32" (default, `ofx_attention_f32`) or "fp16" (`ofx_attention_prec`, the fused head sizes
+    40 / 64 / 80 / 128 / 160 only: any other D is a ValueError, there is no unfused fp16 path)."""
+    check_attention_precision(precision)                           # before a device is touched
+    if precision == "fp16":
+        if not isinstance(q, torch.Tensor) or q.dim() != 3 or int(q.shape[-1]) not in ATTENTION_FUSED_HEAD_SIZES:
+            raise ValueError(f'attention: precision="fp16" needs q [BH,Nq,D] with D in {ATTENTION_FUSED_HEAD_SIZES}')
     q = _chk(q, "q", torch.float32)
     k = _chk(k, "k", torch.float32)
     v = _chk(v, "v", torch.float32)
@@ -831,8 +849,13 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bias: Optional[
     for z0 in range(0, BH, step):
         n = min(step, BH - z0)
         bz = None if bias is None else (bias[z0:z0 + n] if per_bh else bias)
-        check(L.ofx_attention_f32(_ptr(q[z0:z0 + n]), _ptr(k[z0:z0 + n]), _ptr(v[z0:z0 + n]), _ptr(bz), Nq * Nk if per_bh else 0,
-                                  _ptr(out[z0:z0 + n]), n, Nq, Nk, D, scale, _ptr(ws), ws.numel(), _stream()), "ofx_attention_f32")
+        if precision == "fp32":
+            check(L.ofx_attention_f32(_ptr(q[z0:z0 + n]), _ptr(k[z0:z0 + n]), _ptr(v[z0:z0 + n]), _ptr(bz), Nq * Nk if per_bh else 0,
+                                      _ptr(out[z0:z0 + n]), n, Nq, Nk, D, scale, _ptr(ws), ws.numel(), _stream()), "ofx_attention_f32")
+        else:
+            check(L.ofx_attention_prec(_ptr(q[z0:z0 + n]), _ptr(k[z0:z0 + n]), _ptr(v[z0:z0 + n]), _ptr(bz), Nq * Nk if per_bh else 0,
+                                       _ptr(out[z0:z0 + n]), n, Nq, Nk, D, scale, ATTENTION_PRECISIONS[precision], _ptr(ws), ws.numel(),
+                                       _stream()), "ofx_attention_prec")
     return out
 
 
@@ -909,12 +932,14 @@ def _bnhd(t: torch.Tensor, name: str) -> int:
 
 
 def attention_bnhd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, bias: Optional[torch.Tensor] = None,
-                   scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   scale: Optional[float] = None, out: Optional[torch.Tensor] = None, precision: str = "fp32") -> torch.Tensor:
     """`attention` on token rows: q [B,Nq,H*D], k / v [B,Nk,H*D] with the heads side by side in a row, as a projection GEMM leaves
     them -- contiguous tensors, or last-axis slices of wider ones (the three thirds of one fused q|k|v buffer); the row stride is
     read from stride(1).  bias [Nq,Nk] or [B*H,Nq,Nk]; scale defaults to D^-0.5.  Returns `out` [B,Nq,H*D] (new and contiguous when
     not given), bit for bit what `attention` gives on the permuted contiguous copies.  Head sizes the fused kernel takes only
-    (`ofx_attention_bnhd_f32`: D in 40 / 64 / 80 / 128 / 160, OFX_EINVAL otherwise)."""
+    (`ofx_attention_bnhd_f32`: D in 40 / 64 / 80 / 128 / 160, OFX_EINVAL otherwise).  precision: "fp32" (default) or "fp16"
+    (`ofx_attention_bnhd_prec`, as in `attention`); anything else is a ValueError before a device is touched."""
+    check_attention_precision(precision)
     ldq, ldk, ldv = _bnhd(q, "q"), _bnhd(k, "k"), _bnhd(v, "v")
     B, Nq, W = q.shape
     Nk = k.shape[1]
@@ -933,8 +958,13 @@ def attention_bnhd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
     if tuple(out.shape) != (B, Nq, W):
         raise RuntimeError(f"out must be {(B, Nq, W)}, got {tuple(out.shape)}")
     scale = float(D) ** -0.5 if scale is None else float(scale)
-    check(_lib.lib().ofx_attention_bnhd_f32(_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(bias), Nq * Nk if per_bh else 0, _ptr(out), ldo,
-                                            B, H, Nq, Nk, D, scale, _stream()), "ofx_attention_bnhd_f32")
+    if precision == "fp32":
+        check(_lib.lib().ofx_attention_bnhd_f32(_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(bias), Nq * Nk if per_bh else 0, _ptr(out), ldo,
+                                                B, H, Nq, Nk, D, scale, _stream()), "ofx_attention_bnhd_f32")
+    else:
+        check(_lib.lib().ofx_attention_bnhd_prec(_ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(bias), Nq * Nk if per_bh else 0, _ptr(out),
+                                                 ldo, B, H, Nq, Nk, D, scale, ATTENTION_PRECISIONS[precision], _stream()),
+              "ofx_attention_bnhd_prec")
     return out
 
 

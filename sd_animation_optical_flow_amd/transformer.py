@@ -19,6 +19,12 @@ and accumulates in fp32 (what torch.autocast gives the reference's Linears); the
 GroupNorm, LayerNorm, GEGLU, the attention (softmax included) and every activation in memory stay fp32 in every precision -- closer
 to float64 than autocast, which also rounds each layer's output and runs attention in half.
 
+`attention_precision=` ("fp32" default, "fp16") is separate and chooses the arithmetic of the fused attention kernel alone
+(`ofx_attention_bnhd_prec`): "fp16" rounds q, k, v and the probabilities to half as the kernel stages them and runs both products
+on the fp16 matrix cores with fp32 accumulation; the softmax, the scale and the tensors in memory stay fp32, and `kv_hists` -- taken
+before the attention -- are exactly what they are without it.  It exists on the fused route only: with OFX_ST_TORCH_GLUE=1, or a head
+size outside `FUSED_HEAD_SIZES`, "fp16" is a ValueError at construction (no silent fallback).
+
 OFX_ST_TORCH_GLUE=1 in the environment (read once per process; the A/B baseline and a diagnostic): LayerNorm and GEGLU through
 torch.nn.functional, attention through permute + `ops.attention`, i.e. the glue this module replaces.  Head sizes the fused kernel
 does not take (`FUSED_HEAD_SIZES`) go the permute + `ops.attention` way on their own.
@@ -160,8 +166,14 @@ class SpatialTransformer:
     """`ldm.modules.attention.SpatialTransformer` (use_linear=False, inference) on a HIP device."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], n_heads: int, d_head: int, device="cuda", prefix: str = "",
-                 use_linear: bool = False, precision: str = "fp32"):
+                 use_linear: bool = False, precision: str = "fp32", attention_precision: str = "fp32"):
         self.precision = check_precision(precision)                # before the checkpoint is looked at or a device asked for
+        self.attention_precision = ops.check_attention_precision(attention_precision, "attention_precision")
+        if self.attention_precision != "fp32":                     # the fused kernel only: no unfused fp16 path, no silent fallback
+            if _torch_glue():
+                raise ValueError(f"attention_precision={attention_precision!r} does not combine with OFX_ST_TORCH_GLUE=1")
+            if int(d_head) not in FUSED_HEAD_SIZES:
+                raise ValueError(f"attention_precision={attention_precision!r} needs d_head in {FUSED_HEAD_SIZES}, got {d_head}")
         if use_linear:
             raise NotImplementedError("use_linear=True (Linear proj_in / proj_out) is not what guided_ldm_*_v15.yaml builds")
         if not torch.cuda.is_available():
@@ -234,7 +246,7 @@ class SpatialTransformer:
     def _attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """q [B,Nq,inner], k / v [B,Nk,inner] (possibly slices of wider GEMM outputs) -> [B,Nq,inner], written to `out` when given."""
         if self.fused_attention:
-            return ops.attention_bnhd(q, k, v, self.heads, out=out)
+            return ops.attention_bnhd(q, k, v, self.heads, out=out, precision=self.attention_precision)
         # the glue this module replaces (attention.py:338-345, :430-435): [(b h), n, d] copies in, one copy out
         B, Nq, _ = q.shape
         o = ops.attention(*(to_reference_layout(t, self.heads) for t in (q, k, v)))

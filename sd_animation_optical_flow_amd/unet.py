@@ -50,13 +50,14 @@ from __future__ import annotations
 import functools
 import math
 import os
+import warnings
 from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
 
 from . import ops
-from .transformer import MODEL_PRECISIONS, SpatialTransformer, check_precision, plan_reference_kv, spatial_transformer_tensors
+from .transformer import FUSED_HEAD_SIZES, MODEL_PRECISIONS, SpatialTransformer, check_precision, plan_reference_kv, spatial_transformer_tensors
 
 # `unet_config` of guided_ldm_inpaint_v15.yaml (in_channels 9) / guided_ldm_v15.yaml (in_channels 4)
 SD_V15_UNET = dict(in_channels=9, out_channels=4, model_channels=320, attention_resolutions=(4, 2, 1), num_res_blocks=2,
@@ -216,11 +217,17 @@ def route_reference_kv(reference_kv, n_transformers: int) -> List[list]:
 
 class UNetModel:
     """`ldm.modules.diffusionmodules.openaimodel.UNetModel` with `ControlledUnetModel.forward` (inference) on a HIP device.
-    `precision`: the arithmetic of the convolutions and GEMMs, one of MODEL_PRECISIONS (module docstring); everything else is fp32."""
+    `precision`: the arithmetic of the convolutions and GEMMs, one of MODEL_PRECISIONS (module docstring); everything else is fp32,
+    unless `attention_precision="fp16"` hands the attention of all the transformers to the fp16 matrix-core kernel
+    (`SpatialTransformer(attention_precision=)`; the K/V a transformer records is unchanged by it).  That kernel exists for the head
+    sizes 40 / 64 / 80 / 128 / 160 -- all 16 transformers of SD v1.5.  In a configuration with another head size (the test
+    configuration u0 has a 192-wide middle head) that transformer keeps fp32 attention: a UserWarning names it at construction and
+    `attention_precision_of` maps every transformer to the mode it runs.  A SpatialTransformer built directly raises instead."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: dict = SD_V15_UNET, device="cuda", prefix: str = "model.diffusion_model.",
-                 precision: str = "fp32"):
+                 precision: str = "fp32", attention_precision: str = "fp32"):
         self.precision = check_precision(precision)                # before the checkpoint is looked at or a device asked for
+        self.attention_precision = ops.check_attention_precision(attention_precision, "attention_precision")
         self.layout = unet_layout(cfg)
         self.cfg = self.layout["cfg"]
         c = self.cfg
@@ -253,7 +260,10 @@ class UNetModel:
             kind, name = l[0], l[1]
             if kind == "st":
                 sub = {k[len(name) + 1:]: v for k, v in t32.items() if k.startswith(name + ".")}
-                self.st[name] = SpatialTransformer(sub, l[3], l[4], device=self.device, precision=self.precision)
+                # the fp16 attention kernel exists for the fused head sizes only (all 16 transformers of SD v1.5: 40 / 80 / 160).  A
+                # transformer with another head size keeps fp32 attention, and says so: a warning below, `attention_precision_of`
+                ap = self.attention_precision if int(l[4]) in FUSED_HEAD_SIZES else "fp32"
+                self.st[name] = SpatialTransformer(sub, l[3], l[4], device=self.device, precision=self.precision, attention_precision=ap)
             elif kind == "res":
                 emb_w.append(t32[f"{name}.emb_layers.1.weight"])
                 emb_b.append(t32[f"{name}.emb_layers.1.bias"])
@@ -261,6 +271,11 @@ class UNetModel:
                 off += l[3]
         self.n_transformers = len(self.st)
         self.st_order = [l for l in _layers(self.layout) if l[0] == "st"]
+        self.attention_precision_of = {name: st.attention_precision for name, st in self.st.items()}
+        kept = [name for name, ap in self.attention_precision_of.items() if ap != self.attention_precision]
+        if kept:
+            warnings.warn(f"attention_precision={self.attention_precision!r}: the fused kernel does not take the head size of {kept} "
+                          f"(fused: {FUSED_HEAD_SIZES}); their attention stays fp32 (UNetModel.attention_precision_of)", stacklevel=2)
         for key, t in t32.items():
             if any(key.startswith(n + ".") for n in self.st) or ".emb_layers." in key:
                 continue

@@ -20,12 +20,17 @@ the launches, so the table's sum exceeds the timed figure's share.
 glue), in alternating fresh processes, rounds and statistics as above; the first one named is the baseline of the ratios, and every
 variant gets its launch table.  The fp32 row is measured in the same session as the others, never copied.
 
+--attention-precision A,B: with it every --precision is run with each `UNetModel(attention_precision=)` named ("fp32", "fp16"), e.g.
+--precision fp32,fp16 --attention-precision fp32,fp16 is the four-way comparison fp32+attn-fp32 (the baseline), fp32+attn-fp16,
+fp16+attn-fp32, fp16+attn-fp16.
+
 --sincos-probe PATH: also run the cosf / sinf probe (tools/sincos_probe.hip, built beforehand) over the arguments of the
 timestep-embedding test grid (tests/unet_check.sincos_arguments) and report the device's worst error against float64 in units of
 2^-24: Y_SINCOS.
 
     python tools/unet_rate.py [--out profiles/r20_unet_rate.txt] [--sincos-probe ./sincos_probe]
     python tools/unet_rate.py --precision fp32,bf16x3,fp16 [--out profiles/r23_unet_f16_rate.txt]
+    python tools/unet_rate.py --precision fp32,fp16 --attention-precision fp32,fp16
 """
 import argparse
 import json
@@ -39,26 +44,27 @@ sys.path.insert(0, ROOT)
 
 BATCH, LAT_H, LAT_W, CTX_TOKENS = 2, 64, 96, 77
 KINDS = (("convolutions and the transformers' GEMMs", ("igemm_conv",)), ("upconv2x", ("upconv2x",)),
-         ("attention", ("attn_flash", "attn_flash_bnhd", "softmax_rows", "attn_pack", "attn_nan_rows")),
+         ("attention", ("attn_flash", "attn_flash_bnhd", "attn_flash_f16", "attn_flash_bnhd_f16", "softmax_rows", "attn_pack", "attn_nan_rows")),
          ("groupnorm_cat partial sums", ("groupnorm_cat_partial",)), ("groupnorm_cat finalize", ("groupnorm_cat_finalize",)),
          ("groupnorm_cat apply", ("groupnorm_cat_apply",)), ("groupnorm (ofx_groupnorm)", ("groupnorm_stats", "groupnorm_apply")),
          ("emb_linear", ("emb_linear",)), ("timestep_embedding", ("timestep_embedding",)), ("layernorm", ("layernorm",)),
          ("geglu", ("geglu",)))
 
 
-def child(reps: int, warmup: int, profile: bool, precision: str) -> None:
+def child(reps: int, warmup: int, profile: bool, precision: str, attention_precision: str = "fp32") -> None:
     import torch
     from sd_animation_optical_flow_amd import ops
     from sd_animation_optical_flow_amd import unet as UN
     assert torch.cuda.is_available(), "a GPU is needed: nothing here is measured on the host"
     cfg = UN.SD_V15_UNET
-    model = UN.UNetModel(UN.random_unet_state_dict(0, cfg), cfg, prefix="", precision=precision)
+    model = UN.UNetModel(UN.random_unet_state_dict(0, cfg), cfg, prefix="", precision=precision, attention_precision=attention_precision)
+    assert set(model.attention_precision_of.values()) == {attention_precision}       # all 16 transformers of SD v1.5 take it
     g = torch.Generator().manual_seed(20)
     x = torch.randn((BATCH, LAT_H, LAT_W, cfg["in_channels"]), generator=g).cuda()
     t = torch.tensor([981.0, 981.0]).cuda()
     ctx = torch.randn((BATCH, CTX_TOKENS, cfg["context_dim"]), generator=g).cuda()
     out, hist = model.forward_nhwc(x, t, ctx)
-    res = {"glue": UN._torch_glue(), "precision": model.precision, "checksum": float(out.double().abs().mean()), "transformers": len(hist)}
+    res = {"glue": UN._torch_glue(), "precision": model.precision, "attention_precision": model.attention_precision, "checksum": float(out.double().abs().mean()), "transformers": len(hist)}
     for _ in range(warmup):
         model.forward_nhwc(x, t, ctx)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -117,8 +123,9 @@ def kernel_table(label: str, k: dict, reps: int) -> list:
     return lines
 
 
-def run_child(a, rnd: int, env: dict, precision: str) -> dict:
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--reps", str(a.reps), "--warmup", str(a.warmup), "--child-precision", precision]
+def run_child(a, rnd: int, env: dict, precision: str, attention_precision: str = "fp32") -> dict:
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--reps", str(a.reps), "--warmup", str(a.warmup), "--child-precision", precision,
+           "--child-attention-precision", attention_precision]
     if rnd == a.rounds - 1:
         cmd.append("--profile")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420)
@@ -128,12 +135,18 @@ def run_child(a, rnd: int, env: dict, precision: str) -> dict:
 
 
 def compare_precisions(a) -> str:
-    precs = [p.strip() for p in a.precision.split(",") if p.strip()]
+    precs = [p.strip() for p in (a.precision or "fp32").split(",") if p.strip()]
+    if a.attention_precision:                                       # every precision with every attention precision, e.g. "fp16+attn-fp16"
+        aps = [p.strip() for p in a.attention_precision.split(",") if p.strip()]
+        variants = {f"{p}+attn-{q}": (p, q) for p in precs for q in aps}
+    else:
+        variants = {p: (p, "fp32") for p in precs}
+    precs = list(variants)
     runs = {p: [] for p in precs}
     for rnd in range(a.rounds):
         for p in precs:
-            res = run_child(a, rnd, dict(os.environ, OFX_UNET_TORCH_GLUE="0"), p)
-            assert res["precision"] == p and not res["glue"]
+            res = run_child(a, rnd, dict(os.environ, OFX_UNET_TORCH_GLUE="0"), *variants[p])
+            assert (res["precision"], res["attention_precision"]) == variants[p] and not res["glue"]
             runs[p].append(res)
             print(f"round {rnd} {p}: {res['ms']:.3f} ms", flush=True)
     stat = lambda v: f"{sum(v) / len(v):8.3f} [{min(v):7.3f} .. {max(v):7.3f}]"
@@ -144,7 +157,7 @@ def compare_precisions(a) -> str:
              f"weights, batch {BATCH}, latent {LAT_H} x {LAT_W}, context {CTX_TOKENS} x 768; ms per forward, device events over {a.reps} forwards, "
              f"mean of {a.rounds} rounds [fastest .. slowest], the precisions in alternating fresh processes of one session", ""]
     for p in precs:
-        lines.append(f"  {p:7s} {stat(ms[p])} ms   mean |out| {runs[p][0]['checksum']:.6f}")
+        lines.append(f"  {p:15s} {stat(ms[p])} ms   mean |out| {runs[p][0]['checksum']:.6f}")
     lines.append("")
     for p in precs[1:]:
         clear = max(ms[p]) < min(ms[base]) or min(ms[p]) > max(ms[base])
@@ -168,12 +181,15 @@ def main() -> None:
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--precision", help="comma-separated UNetModel precisions to compare, the baseline first (e.g. fp32,bf16x3,fp16)")
+    ap.add_argument("--attention-precision", help="comma-separated UNetModel attention_precision values (fp32,fp16): every --precision is "
+                                                  "run with each of them, the variants named e.g. fp16+attn-fp16")
     ap.add_argument("--child-precision", default="fp32")
+    ap.add_argument("--child-attention-precision", default="fp32")
     a = ap.parse_args()
     if a.child:
-        child(a.reps, a.warmup, a.profile, a.child_precision)
+        child(a.reps, a.warmup, a.profile, a.child_precision, a.child_attention_precision)
         return
-    if a.precision:
+    if a.precision or a.attention_precision:
         text = compare_precisions(a)
         print(text)
         if a.out:
