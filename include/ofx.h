@@ -371,8 +371,11 @@ typedef struct ofx_conv_desc {
                                                     a larger rounding error than F(2x2,3x3)) if all of
                                                     these hold:
                                                     - fp32, stride 1, 'same' padding, a map of whole 16x32 patches;
-                                                    - plain epilogue, ReLU or identity, no addend, `res` or fused norm, and not
-                                                      under ofx_conv2d_stats;
+                                                    - plain epilogue, ReLU or identity, no addend;
+                                                    - `res`, a fused norm (`nmean` / `nrstd`, single input segment, at most 1744
+                                                      channels) and ofx_conv2d_stats are taken by the kernel's fused variants
+                                                      under the rules of `wino_w` above, the partials one row per 16x32 patch
+                                                      (plan path 4; a descriptor with none of them: the plain kernel, path 3);
                                                     - the grid fills whole rounds of the chip (at least 768 workgroups of one
                                                       16x32 patch x 64 output channels).
                                                     Otherwise, or with OFX_CONV_NO_WINOGRAD4 (or OFX_CONV_NO_WINOGRAD) in the
@@ -393,7 +396,9 @@ int ofx_conv2d(const ofx_conv_desc* d, void* stream);
  * BM x BN tile with chunk length BK that `tile` = BK*1000000 + BM*1000 + BN names, `ks` = 2 being its 2000000000 marker. */
 typedef struct ofx_conv_plan {
     int path;                /* 0 direct implicit-GEMM kernel, 1 fused Winograd F(2x2,3x3), 2 fused Winograd F(4,5), 3 fused Winograd
-                                F(4x4,3x3); 1 / 2 / 3: only `stats_rows` below is meaningful (3: always 0) */
+                                F(4x4,3x3), the plain kernel, 4 F(4x4,3x3) with a residual merge, a fused norm or statistics (a
+                                descriptor with `res`, `nmean` or under ofx_conv2d_stats never plans to 3); 1 / 2 / 3 / 4: only
+                                `stats_rows` below is meaningful (3: always 0) */
     int bm, bn, wm, wn, bk;  /* workgroup tile, wave tile, K chunk */
     int prec;                /* arithmetic of the kernel: OFX_PREC_*, after the split-bf16 modes have mapped the tile onto theirs */
     int ks;                  /* 2: paired K pipelines (64x64 tile on small grids), else 1 */

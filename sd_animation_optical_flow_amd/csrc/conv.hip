@@ -1402,7 +1402,7 @@ const ConvKnobs& conv_knobs() {
 
 // ---- plan: everything a launch needs that is not a pointer.  conv_plan is a pure function of the descriptor's numbers (and of which
 // of its pointers are set), the extras and the knobs: no HIP call, no environment, no global state.
-enum { kPathIgemm = 0, kPathWino3x3 = 1, kPathWino15 = 2, kPathWino44 = 3 };
+enum { kPathIgemm = 0, kPathWino3x3 = 1, kPathWino15 = 2, kPathWino44 = 3, kPathWino44Fused = 4 };
 struct ConvPlan : ofx_conv_plan {   // the public fields (ofx.h: path, tile, arithmetic, schedule, grid, statistics rows) and ...
     int inst = -1;                  // direct kernels: the row of kTiles that bm ... ks and ksplit > 1 name
     const char* name = nullptr;     // family of the per-layer profile
@@ -1426,15 +1426,21 @@ int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, C
     // multiplies per output; residual merge, fused instance norm and epilogue statistics included) and F(4,5) for the SepConvGRU's
     // 1x5 / 5x1 layers (2 instead of 5, GRU gate epilogues included).  Only on grids that fill the chip (ofx_conv_wino_pays):
     // smaller grids, the single pair among them, keep the direct kernels and their small-grid schedules.
-    // F(4x4,3x3) (2.25 multiplies per output) is a route of its own with its own operand and error class: the update block's
-    // plain 3x3 layers, where its one-workgroup-per-CU grid fills whole rounds of the chip (ofx_conv_wino44_pays); a descriptor
-    // without wino4_w plans exactly as before.
+    // F(4x4,3x3) (2.25 multiplies per output) is a route of its own with its own operand and error class, where its
+    // one-workgroup-per-CU grid fills whole rounds of the chip (ofx_conv_wino44_pays): path 3, the plain kernel, for plain 3x3
+    // layers (the update block's, the context encoder's conv1); path 4, its fused variants, for a descriptor with a residual
+    // merge, a fused norm or requested statistics (the encoders' other layers; statistics as path 1, one row per 16x32 patch).
+    // A descriptor without wino4_w plans exactly as before.
     const bool force4 = d->tile == OFX_CONV_TILE_WINOGRAD4;
     if (force4 || (d->tile == 0 && !kn.no_wino44 && d->wino4_w)) {
-        const bool fits = nz == 1 && !want_stats && !pool && ofx_conv_wino44_fits(d);
+        const bool fused = want_stats || d->res || d->nmean || d->nrstd;
+        const int srows = want_stats ? ofx_conv_wino44_stats_rows(d) : 0;
+        const bool stats_ok = !want_stats || (srows > 0 && (size_t)d->B * srows * d->Cout * 2 <= x.stats_cap);
+        const bool fits = nz == 1 && !pool && (fused ? stats_ok && ofx_conv_wino44_fused_fits(d) : ofx_conv_wino44_fits(d));
         if (force4 && !fits) return OFX_EINVAL;
         if (fits && (force4 || ofx_conv_wino44_pays(d))) {
-            p->path = kPathWino44;
+            p->path = fused ? kPathWino44Fused : kPathWino44;
+            p->stats_rows = srows;
             p->flops = ofx_conv_wino44_flops(d);
             return 0;
         }
@@ -1762,8 +1768,8 @@ int ofx_conv2d_ex(const ofx_conv_desc* d, const ConvExtra* extra, hipStream_t s)
     if ((st = conv_plan(d, x, conv_knobs(), &p))) return st;
     OfxProfScope prof(p.name, s);
     prof.flops(p.flops);
-    if (p.path == kPathWino44) {
-        st = ofx_conv_wino44_launch(d, x.alpha, s, x.stop_event);
+    if (p.path == kPathWino44 || p.path == kPathWino44Fused) {
+        st = ofx_conv_wino44_launch(d, x.alpha, p.stats_rows ? x.stats_part : nullptr, s, x.stop_event);
     } else if (p.path != kPathIgemm) {
         st = ofx_conv_wino_launch(d, x.alpha, x.stats_rows ? x.stats_part : nullptr, s, x.stop_event);
     } else {

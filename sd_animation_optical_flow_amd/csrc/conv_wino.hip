@@ -677,8 +677,14 @@ int launch15(const WinoK& k, int epi, dim3 grid, dim3 block, hipStream_t s, hipE
 // columns of its wave's row of T and folds them into its A operands.  The halo (18 x 34 pixels) and T are staged per 8-channel
 // slab, both double-buffered, one barrier per slab (the order of a trip: at the slab loop); a lane handles its four channels of
 // the slab as two float2 halves (the register budget of three waves per SIMD, 168, does not hold the float4 form next to 96
-// accumulators).  The weights run one slab ahead in registers, each fragment reloaded behind the MFMAs that consumed it.  Update
-// block's plain epilogue only.
+// accumulators).  The weights run one slab ahead in registers, each fragment reloaded behind the MFMAs that consumed it.
+//
+// wino44_conv_kernel is the plain kernel (the update block's layers, the context encoder's conv1).  wino44_fused_kernel<NORM, RES,
+// STATS> shares its body (conv_wino44_body.inl) and adds the encoders' options under the contracts of wino_conv_kernel.  NORM: the
+// operand is relu((x - mean) * rstd) of image pt.pb (single segment), applied as the halo is stored, the padding that of the
+// normalised map; the image's means and rstds are staged once in the LDS the slab staging leaves free (kNorm44 floats), since the
+// registers of three waves per SIMD do not hold them across a slab.  RES: relu(y + res) after the activation.  STATS: per (16x32
+// patch, output channel) the sum and the sum of squares of the stored values, [B][tpi][Cout][2], in a fixed order.
 //
 // Halo layout: a pixel's 8 channels are contiguous, the pixels (x, .. x + 3), x % 4 == 0, 32 contiguous floats, quads 34 floats
 // apart, rows 308.  T keeps the layout of a halo row per (point row, tile row), 336 floats apart.  The operand ds_read_b64 of a
@@ -703,245 +709,22 @@ constexpr int kLDX4 = 40;                                   // output exchange: 
 constexpr int kXF4 = 12 * 4 * 16 * kLDX4;                   // 30 720 floats: half the patch's tiles at a time
 constexpr int kStage44 = 2 * (Halo44::floats + Halo44::tfloats);   // raw halo and T, both double-buffered: 27 216 floats
 constexpr int kSmem44 = (kStage44 > kXF4 ? kStage44 : kXF4) * 4;   // bytes: 122 880, one workgroup per CU
+// NORM: behind the staged slabs, per four channels [mean x 4 | rstd x 4]; most input channels that fit (a multiple of 16)
+constexpr int kNorm44 = kSmem44 / 4 - kStage44;             // 3504 floats
+constexpr int kNorm44MaxCin = kNorm44 / 2 / kWBK * kWBK;    // 1744
+constexpr int kSX4 = 2 * 24 * 32 * 2;                       // STATS: [32-channel half][half-wave][channel][sum, sum of squares]
+static_assert(kNorm44 >= 0 && kSX4 <= kXF4, "the fused options live in the plain kernel's LDS");
 
 __global__ __launch_bounds__(768, 1) void wino44_conv_kernel(const WinoK p) {
     extern __shared__ __attribute__((aligned(16))) float smem44[];
-    using HALO = Halo44;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the weight offsets and the row coefficients stay scalar
-    const int wi = wave >> 1, nt = wave & 1;
-    const Patch pt = wino_patch<16, 32>(p);
+    constexpr bool NORM = false, RES = false, STATS = false;
+#include "conv_wino44_body.inl"
+}
 
-    // ---- halo staging: item i = tid + 768 k = (pixel i / 2, float4 slot i % 2), pixels row-major over the halo
-    const float* in1s = p.in1 ? p.in1 : p.in0;
-    const int bytes1s = p.in1 ? p.bytes1 : p.bytes0;
-    // A thread keeps, for each of its two items, the pixel's index in the map (-1: out of the map, or no item) and its place in
-    // the halo image: with the row transform staged, the 168 registers of three waves per SIMD hold them next to 96 accumulators.
-    // Item 1 is 384 pixels = 11 rows and 10 pixels on.
-    static_assert(HALO::slots == 2 && HALO::threads / 2 == 11 * HALO::W + 10, "item 1 = item 0 + 11 rows + 10 pixels");
-    int hpix[HALO::slots], hat[HALO::slots];
-#pragma unroll
-    for (int k = 0; k < HALO::slots; ++k) {
-        const int px = (tid >> 1) + k * (HALO::threads / 2);
-        const int hy = px / HALO::W, hx = px - hy * HALO::W;
-        const int gy = pt.y0 - 1 + hy, gx = pt.x0 - 1 + hx;
-        const bool item = k == 0 || tid < HALO::items - HALO::threads;
-        hpix[k] = item && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W ? (pt.pb * p.H + gy) * p.W + gx : -1;
-        hat[k] = item ? HALO::at(hy, hx) + (tid & 1) * 4 : -1;   // (float4 slot tid % 2 of the pixel: 768 % 2 == 0, the same for both)
-    }
-    auto h_issue = [&](int cb, float4 (&r)[HALO::slots]) __attribute__((always_inline)) {
-        const int c = cb * 8;
-        const bool s0 = c < p.c0;    // wave-uniform
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(s0 ? p.in0 : in1s), (short)0, s0 ? p.bytes0 : bytes1s, 0x00020000);
-        const int so = (s0 ? c : c - p.c0) * 4;
-        const int ldb = (s0 ? p.ld0 : p.ld1) * 4;
-#pragma unroll
-        for (int k = 0; k < HALO::slots; ++k) {
-            const int vo = hpix[k] >= 0 ? hpix[k] * ldb + (tid & 1) * 16 : kOOB;
-            v4i t = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so, 0);
-            r[k] = *reinterpret_cast<float4*>(&t);
-        }
-    };
-    auto h_store = [&](float* Hs, const float4 (&r)[HALO::slots]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int k = 0; k < HALO::slots; ++k)
-            if (k == 0 || hat[k] >= 0) {   // (quads 34 floats apart: 8-byte aligned)
-                float* const at = Hs + hat[k];
-                *reinterpret_cast<float2*>(at) = f2(r[k].x, r[k].y);
-                *reinterpret_cast<float2*>(at + 2) = f2(r[k].z, r[k].w);
-            }
-    };
-
-    // ---- the row pass: row i of B^T d, i = 0 .. 5, for the windows of tile row ty, once per workgroup.  Thread `tid` < 544 owns
-    // (ty, x, channel pair): the window's six halo rows 4 ty .. 4 ty + 5 at pixel x, six results.  Rows 1 .. 4 take halo rows
-    // 1 .. 4, t = c0 d1 + c1 d2 + c2 d3 + c3 d4; rows 0 and 5 take rows (0, 2, 4) and (1, 3, 5), t = 4 d0 - 5 d1 + d2.  The
-    // expressions keep the form and the operand order they had when every wave worked its own row out: the same bits.
-    const int rpx = tid >> 2, rty = rpx / HALO::W, rx = rpx - rty * HALO::W;
-    const int rxo = (rx >> 2) * HALO::lquad + (rx & 3) * 8 + (tid & 3) * 2;
-    const int rin = tid < HALO::titems ? 4 * rty * HALO::lrow + rxo : -1, rout = rty * HALO::ltrow + rxo;
-    auto row_pass = [&](const float* Rs, float* Ts, bool on) __attribute__((always_inline)) {
-        if (rin >= 0 && on) {
-            const float* const d = Rs + rin;
-            float* const o = Ts + rout;
-            float2 r[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) r[k] = *reinterpret_cast<const float2*>(d + k * HALO::lrow);
-            __builtin_amdgcn_sched_barrier(0);   // all six reads in flight before the first result is stored
-            auto outer = [](float d0, float d1, float d2) { return __builtin_fmaf(-5.f, d1, __builtin_fmaf(4.f, d0, d2)); };
-            auto inner = [](float c0, float c1, float c2, float c3, float d0, float d1, float d2, float d3) {
-                return __builtin_fmaf(c3, d3, __builtin_fmaf(c2, d2, __builtin_fmaf(c1, d1, c0 * d0)));
-            };
-#define OFX_ROW44(i, EX, EY) *reinterpret_cast<float2*>(o + (i) * 4 * HALO::ltrow) = f2(EX, EY)
-            OFX_ROW44(0, outer(r[0].x, r[2].x, r[4].x), outer(r[0].y, r[2].y, r[4].y));
-            OFX_ROW44(1, inner(-4.f, -4.f, 1.f, 1.f, r[1].x, r[2].x, r[3].x, r[4].x), inner(-4.f, -4.f, 1.f, 1.f, r[1].y, r[2].y, r[3].y, r[4].y));
-            OFX_ROW44(2, inner(4.f, -4.f, -1.f, 1.f, r[1].x, r[2].x, r[3].x, r[4].x), inner(4.f, -4.f, -1.f, 1.f, r[1].y, r[2].y, r[3].y, r[4].y));
-            OFX_ROW44(3, inner(-2.f, -1.f, 2.f, 1.f, r[1].x, r[2].x, r[3].x, r[4].x), inner(-2.f, -1.f, 2.f, 1.f, r[1].y, r[2].y, r[3].y, r[4].y));
-            OFX_ROW44(4, inner(2.f, -1.f, -2.f, 1.f, r[1].x, r[2].x, r[3].x, r[4].x), inner(2.f, -1.f, -2.f, 1.f, r[1].y, r[2].y, r[3].y, r[4].y));
-            OFX_ROW44(5, outer(r[1].x, r[3].x, r[5].x), outer(r[1].y, r[3].y, r[5].y));
-#undef OFX_ROW44
-        }
-    };
-    // the product side: wave (i, nt) reads row i of T only, one float2 per window column and half-step
-    const int tile = lane & 31;
-    const int at0 = (wi * 4 + (tile >> 3)) * HALO::ltrow + (tile & 7) * HALO::lquad + 4 * (lane >> 5);
-    auto t_read = [&](const float* Tw, int s, float2 (&t)[6]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) t[c] = *reinterpret_cast<const float2*>(Tw + HALO::at(0, c) + 2 * s);
-    };
-
-    // the weights: point 6 i + j, 32-channel block blk, 8-channel chunk cb, half s -> one contiguous 512-byte fragment, 8 bytes per
-    // lane (ofx_wino44_conv_weight); step (cb, s) = 2 cb + s
-    const __amdgpu_buffer_rsrc_t rsu = __builtin_amdgcn_make_buffer_rsrc((void*)p.u, (short)0, p.bytesu, 0x00020000);
-    const int c8n = p.cin >> 3;
-    const int fr0 = (6 * wi * p.nb32 + 2 * pt.nb + nt) * c8n * 2, frq = p.nb32 * c8n * 2;   // fragments: point row's first, per point
-    auto w_load = [&](int j, int step) __attribute__((always_inline)) {
-        typedef int v2i __attribute__((ext_vector_type(2)));
-        v2i t = __builtin_amdgcn_raw_buffer_load_b64(rsu, lane * 8, (fr0 + j * frq + step) * 512, 0);
-        return *reinterpret_cast<float2*>(&t);
-    };
-    f32x16 acc[6][1];
-    wino_zero(acc);
-    float2 wr[6];
-
-    // LDS: raw halo slabs R[2], then T[2].  Trip k, after its barrier: raw slab k + 2 goes from registers into R[k % 2] (last read
-    // by the row pass of trip k - 1), the loads of slab k + 3 are issued, the row pass takes raw slab k + 1 (stored in trip k - 1)
-    // from R[(k + 1) % 2] into T[(k + 1) % 2] (last read by the products of trip k - 1), and the products of slab k read
-    // T[k % 2]: one barrier per slab.
-    float* const Hs = smem44;
-    float* const Ts = smem44 + 2 * HALO::floats;
-    const int CB = p.cin >> 3;
-    float4 h0[HALO::slots], hn[HALO::slots];
-    h_issue(0, h0);
-    h_issue(1, hn);
-    h_store(Hs, h0);
-    h_store(Hs + HALO::floats, hn);
-    h_issue(CB > 2 ? 2 : CB - 1, hn);
-    // (the weights after the last halo loads, as in the loop: the first trip's halo wait then leaves them in flight too)
-#pragma unroll
-    for (int j = 0; j < 6; ++j) wr[j] = w_load(j, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();
-    row_pass(Hs, Ts, true);
-    const float* const T0 = Ts + at0;
-    // the six column points of a row: the same combinations along the window's columns, one channel at a time
-    auto fold = [&](const float2 (&t)[6], float (&v)[2][6]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            float x[6];
-#pragma unroll
-            for (int c = 0; c < 6; ++c) x[c] = e ? t[c].y : t[c].x;
-            const float A = __builtin_fmaf(-4.f, x[2], x[4]), Bq = __builtin_fmaf(-4.f, x[1], x[3]), C = x[4] - x[2], D = x[3] - x[1];
-            v[e][0] = __builtin_fmaf(4.f, x[0], __builtin_fmaf(-5.f, x[2], x[4]));
-            v[e][1] = A + Bq;
-            v[e][2] = A - Bq;
-            v[e][3] = __builtin_fmaf(2.f, D, C);
-            v[e][4] = __builtin_fmaf(-2.f, D, C);
-            v[e][5] = __builtin_fmaf(4.f, x[1], __builtin_fmaf(-5.f, x[3], x[5]));
-        }
-    };
-    // two slabs per trip (whole 16-channel slabs: CB is even), so that the buffer of each is a constant offset
-#pragma clang loop unroll(disable)
-    for (int cb2 = 0; cb2 < CB; cb2 += 2)
-#pragma unroll
-    for (int par = 0; par < 2; ++par) {
-        const int cb = cb2 + par;
-        __syncthreads();   // slab cb's T is in buffer par, raw slab cb + 1 in the other raw buffer, and every wave has left the rest
-        float2 t[2][6];
-        t_read(T0 + par * HALO::tfloats, 0, t[0]);
-        h_store(Hs + par * HALO::floats, hn);
-        // the last slabs re-issue the last one (and store it where nothing reads it): no branch, loads stay in bounds
-        h_issue(cb + 3 < CB ? cb + 3 : CB - 1, hn);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            float v[2][6];
-            if (s == 1) __builtin_amdgcn_sched_barrier(0);   // (its operands are waited for behind the first half's MFMAs)
-            fold(t[s], v);
-            if (s == 0) {
-                // the second half-step's six reads go under the first one's MFMAs
-                __builtin_amdgcn_sched_barrier(0);
-                t_read(T0 + par * HALO::tfloats, 1, t[1]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (s == 1) {
-                // The row pass of the next slab (not of the one past the last) sits between the two half-steps: its wave has twelve
-                // MFMAs queued and the SIMD's other waves have the matrix pipe.  The second half's operands are folded first
-                // (the empty asm keeps the fold on this side of the branch), so that no MFMA waits for the LDS stores behind it.
-#pragma unroll
-                for (int e = 0; e < 2; ++e)
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) asm volatile("" : "+v"(v[e][j]));
-                row_pass(Hs + (1 - par) * HALO::floats, Ts + (1 - par) * HALO::tfloats, cb + 1 < CB);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            const int nx = 2 * cb + s + 1 < 2 * CB ? 2 * cb + s + 1 : 2 * cb + s;
-#pragma unroll
-            for (int e = 0; e < 2; ++e)
-#pragma unroll
-                for (int j = 0; j < 6; ++j) {
-                    acc[j][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[e][j], e ? wr[j].y : wr[j].x, acc[j][0], 0, 0, 0);
-                    if (e) {
-                        // the next step's fragment goes into the registers these MFMAs have just read, ten MFMAs ahead of its use,
-                        // and stays there (as in wino3x3_slabs: left free, the scheduler sinks the loads to their uses)
-                        wr[j] = w_load(j, nx);
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    }
-                }
-        }
-    }
-
-    // ---- output transform and plain epilogue.  A^T (4x6) along the column in registers, the six rows meet in LDS, half of the
-    // patch's tiles (two tile rows) at a time: X[wave][b][tile][channel].  Element e of the C layout: tile (e & 3) + 8 (e >> 2) +
-    // 4 (lane >> 5), output channel lane & 31 of the wave's 32.
-    const float act_lo = p.act == OFX_ACT_RELU ? 0.0f : -3.402823466e38f;   // OFX_ACT_NONE: a NaN sum becomes -FLT_MAX (see conv.hip)
-    float* const X = smem44;
-    const int tid2 = tid;
-    const int lane2 = tid2 & 63, on = tid2 & 31, grp = tid2 >> 5;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        __syncthreads();   // half 0: every wave's last operand reads are done; half 1: the first half has been read
-#pragma unroll
-        for (int eh = 0; eh < 8; ++eh) {
-            const int e = 8 * half + eh;
-            const int tl = (e & 3) + 8 * ((e >> 2) & 1) + 4 * (lane2 >> 5);
-            const float m0 = acc[0][0][e], m1 = acc[1][0][e], m2 = acc[2][0][e], m3 = acc[3][0][e], m4 = acc[4][0][e], m5 = acc[5][0][e];
-            const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-            float* const x = X + (wave * 4 * 16 + tl) * kLDX4 + (lane2 & 31);
-            x[0 * 16 * kLDX4] = m0 + s12 + s34;
-            x[1 * 16 * kLDX4] = d12 + 2.0f * d34;
-            x[2 * 16 * kLDX4] = s12 + 4.0f * s34;
-            x[3 * 16 * kLDX4] = d12 + 8.0f * d34 + m5;
-        }
-        __syncthreads();
-        // unit = (32-channel half, tile, output row pair {0, 2} or {1, 3}): 64 units over the 24 half-waves
-        for (int un = grp; un < 64; un += 24) {
-            const int ap = (un >> 1) & 1, rest = un >> 2;
-            const int tl = (rest & 7) * 2 + (un & 1), ont = rest >> 3;
-            const int oc = pt.nb * 64 + ont * 32 + on;
-            if (oc >= p.Cout) continue;
-            const float sc = (p.scale ? p.scale[oc] : 1.0f) * p.alpha;
-            const float sh = p.shift ? p.shift[oc] : 0.0f;
-            const int oy = pt.y0 + 4 * (2 * half + (tl >> 3)) + ap, ox = pt.x0 + 4 * (tl & 7);
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                float x[5];   // rows ap .. ap + 4 of the point grid
-#pragma unroll
-                for (int k = 0; k < 5; ++k) x[k] = X[((((ap + k) * 2 + ont) * 4 + b) * 16 + tl) * kLDX4 + on];
-                float ya, yb;   // output rows ap and ap + 2
-                if (ap == 0) {
-                    ya = x[0] + (x[1] + x[2]) + (x[3] + x[4]);
-                    yb = (x[1] + x[2]) + 4.0f * (x[3] + x[4]);
-                } else {
-                    ya = (x[0] - x[1]) + 2.0f * (x[2] - x[3]);
-                    yb = (x[0] - x[1]) + 8.0f * (x[2] - x[3]) + x[4];
-                }
-                const long pix = ((long)pt.pb * p.H + oy) * p.W + ox + b;
-                p.out[pix * p.ldo + oc] = fmaxf(ya * sc + sh, act_lo);
-                p.out[(pix + 2L * p.W) * p.ldo + oc] = fmaxf(yb * sc + sh, act_lo);
-            }
-        }
-    }
+template <bool NORM, bool RES, bool STATS>
+__global__ __launch_bounds__(768, 1) void wino44_fused_kernel(const WinoK p) {
+    extern __shared__ __attribute__((aligned(16))) float smem44[];
+#include "conv_wino44_body.inl"
 }
 
 bool is_3x3(const ofx_conv_desc* d) { return d->KH == 3 && d->KW == 3; }
@@ -1022,9 +805,9 @@ int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, float* stats, hipS
     return d->KH == 5 ? launch15<true>(k, d->epi, grid, block, s, stop_event) : launch15<false>(k, d->epi, grid, block, s, stop_event);
 }
 
-// ---- F(4x4, 3x3), the second route of the 3x3 layers (ofx_conv_desc.wino4_w).  Shape test: the update block's kernel only -- fp32,
-// stride 1, 'same' 3x3, a map of whole 16x32 patches, whole 16-channel slabs, the plain epilogue (ReLU or identity, scale / shift,
-// strided destination) with no addend, residual or fused norm.
+// ---- F(4x4, 3x3), the second route of the 3x3 layers (ofx_conv_desc.wino4_w).  Shape test of the plain kernel -- fp32, stride 1,
+// 'same' 3x3, a map of whole 16x32 patches, whole 16-channel slabs, the plain epilogue (ReLU or identity, scale / shift, strided
+// destination) with no addend, residual or fused norm.
 bool ofx_conv_wino44_fits(const ofx_conv_desc* d) {
     const int cin = d->c0 + d->c1;
     return is_3x3(d) && d->padH == 1 && d->padW == 1 && d->epi == OFX_EPI_PLAIN && d->out != nullptr && d->ldo >= d->Cout &&
@@ -1034,10 +817,28 @@ bool ofx_conv_wino44_fits(const ofx_conv_desc* d) {
            d->wino4_w != nullptr && ofx_aligned16(d->wino4_w);
 }
 
+// ... and of the fused variants (the encoders' layers): the same shape rules, with the residual merge relu(y + res) and / or
+// relu(norm(.)) fused into the operand under the rules of ofx_conv_wino_fits (single segment, aligned mean / rstd), over as many
+// input channels as the kernel stages means and rstds for.
+bool ofx_conv_wino44_fused_fits(const ofx_conv_desc* d) {
+    ofx_conv_desc plain = *d;
+    plain.res = plain.nmean = plain.nrstd = nullptr;
+    return ofx_conv_wino44_fits(&plain) && (!d->res || d->ldres >= d->Cout) && (d->nmean != nullptr) == (d->nrstd != nullptr) &&
+           (!d->nmean || (!d->in1 && d->c0 <= kNorm44MaxCin && ofx_aligned16(d->nmean) && ofx_aligned16(d->nrstd)));
+}
+
+// Rows per image of the instance-norm partial sums the fused F(4x4) kernel leaves for a fitting `d` (one per 16x32 patch), or 0
+// when it cannot produce them: raw outputs only (identity, no residual), as ofx_conv_wino_stats_rows.
+int ofx_conv_wino44_stats_rows(const ofx_conv_desc* d) {
+    return is_3x3(d) && d->act == OFX_ACT_NONE && !d->res ? (d->Hin / 16) * (d->Win / 32) : 0;
+}
+
 // Whether F(4x4) beats F(2x2) on this grid: at least kWino44MinGroups workgroups (16x32 patches x 64-channel blocks), three for
 // each of the chip's 256 CUs, where its workgroups run one per CU.  Measured per layer shape at B = 4 ... 64
 // (profiles/r21_wino44_gate.txt): it wins at 768, 864, 1152, 1536, 2304 and 3072 workgroups and loses or
 // ties at every measured grid of 576 or fewer.  Of the grids that end in a nearly empty round only 864 was measured.
+// The encoders' stages with their fused variants (profiles/r25_enc_wino44_gate.txt): wins at every grid from 768 on (x1.24 - x1.45),
+// loses at 96 and wins by less at 192 and 384; the same gate.
 constexpr long kWino44MinGroups = 768;
 bool ofx_conv_wino44_pays(const ofx_conv_desc* d) {
     const long patches = (long)d->B * (d->Hin / 16) * (d->Win / 32);
@@ -1049,10 +850,36 @@ double ofx_conv_wino44_flops(const ofx_conv_desc* d) {
     return 2.0 * 36.0 * ((double)d->B * d->Hout * d->Wout / 16.0) * (double)(d->c0 + d->c1) * d->Cout;
 }
 
-// The caller has validated the descriptor (ofx_conv2d_ex) and ofx_conv_wino44_fits(d).
-int ofx_conv_wino44_launch(const ofx_conv_desc* d, float alpha, hipStream_t s, hipEvent_t stop_event) {
+namespace {
+
+// more than 64 KB of LDS: allowed once per kernel and device (as corr_split.hip).  The kernel is a template argument, not a
+// function argument: the six kernels have one pointer type, and each needs flags of its own.
+template <void (*KERNEL)(WinoK)> int launch44(const WinoK& k, hipStream_t s, hipEvent_t stop_event) {
+    void (*const kernel)(WinoK) = KERNEL;
+    static bool allowed[64] = {};   // (one array per instantiation, i.e. per kernel)
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return OFX_EINVAL;
+    if (!allowed[dev]) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kSmem44);
+        if (e != hipSuccess) return (int)e;
+        allowed[dev] = true;
+    }
+    const dim3 grid((unsigned)(k.mtiles * k.nblk), 1, 1), block(768, 1, 1);
+    if (stop_event) hipExtLaunchKernelGGL(kernel, grid, block, kSmem44, s, nullptr, stop_event, 0, k);
+    else hipLaunchKernelGGL(kernel, grid, block, kSmem44, s, k);
+    return ofx_launch_status();
+}
+
+}  // namespace
+
+// The caller has validated the descriptor (ofx_conv2d_ex) and ofx_conv_wino44_fits(d), or ofx_conv_wino44_fused_fits(d) for one
+// with `res`, `nmean` or statistics.  stats: null, or room for the partial sums of ofx_conv_wino44_stats_rows(d) > 0 rows per
+// image (the caller has checked the size).
+int ofx_conv_wino44_launch(const ofx_conv_desc* d, float alpha, float* stats, hipStream_t s, hipEvent_t stop_event) {
+    OFX_REQUIRE(!stats || ofx_conv_wino44_stats_rows(d) > 0, OFX_EINVAL);
     WinoK k{};
     k.in0 = d->in0; k.in1 = d->in1; k.u = d->wino4_w; k.scale = d->scale; k.shift = d->shift; k.out = d->out;
+    k.res = d->res; k.nmean = d->nmean; k.nrstd = d->nrstd; k.stats = stats; k.ldres = d->ldres;
     k.ld0 = d->ld0; k.c0 = d->c0; k.ld1 = d->ld1; k.cin = d->c0 + d->c1; k.ldo = d->ldo;
     k.H = d->Hin; k.W = d->Win; k.Cout = d->Cout; k.act = d->act;
     k.nblk = (d->Cout + 63) / 64;
@@ -1068,20 +895,15 @@ int ofx_conv_wino44_launch(const ofx_conv_desc* d, float alpha, hipStream_t s, h
     k.mtiles = (int)mtiles;
     k.bytes0 = (int)ext0; k.bytes1 = (int)ext1; k.bytesu = (int)extu;
     k.alpha = alpha;
-    // more than 64 KB of LDS: allowed once per device (as corr_split.hip)
-    static bool allowed[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return OFX_EINVAL;
-    if (!allowed[dev]) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino44_conv_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kSmem44);
-        if (e != hipSuccess) return (int)e;
-        allowed[dev] = true;
+    switch ((k.nmean ? 4 : 0) | (k.res ? 2 : 0) | (k.stats ? 1 : 0)) {
+        case 0: return launch44<&wino44_conv_kernel>(k, s, stop_event);
+        case 1: return launch44<&wino44_fused_kernel<false, false, true>>(k, s, stop_event);
+        case 2: return launch44<&wino44_fused_kernel<false, true, false>>(k, s, stop_event);
+        case 4: return launch44<&wino44_fused_kernel<true, false, false>>(k, s, stop_event);
+        case 5: return launch44<&wino44_fused_kernel<true, false, true>>(k, s, stop_event);
+        case 6: return launch44<&wino44_fused_kernel<true, true, false>>(k, s, stop_event);
+        default: return OFX_EINVAL;   // statistics are of raw outputs: never with a residual merge
     }
-    const dim3 grid((unsigned)(k.mtiles * k.nblk), 1, 1), block(768, 1, 1);
-    if (stop_event) hipExtLaunchKernelGGL(wino44_conv_kernel, grid, block, kSmem44, s, nullptr, stop_event, 0, k);
-    else hipLaunchKernelGGL(wino44_conv_kernel, grid, block, kSmem44, s, k);
-    return ofx_launch_status();
 }
 
 namespace {

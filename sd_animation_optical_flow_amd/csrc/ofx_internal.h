@@ -78,11 +78,14 @@ bool ofx_conv_wino_pays(const ofx_conv_desc* d);
 int ofx_conv_wino_stats_rows(const ofx_conv_desc* d);
 double ofx_conv_wino_flops(const ofx_conv_desc* d);
 int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, float* stats, hipStream_t s, hipEvent_t stop_event);
-// ... and F(4x4,3x3), the second route of the update block's 3x3 layers (ofx_conv_desc.wino4_w)
+// ... and F(4x4,3x3), the second route of the 3x3 layers (ofx_conv_desc.wino4_w): the plain kernel (_fits) and its fused variants
+// with a residual merge, a fused norm or epilogue statistics (_fused_fits, _stats_rows)
 bool ofx_conv_wino44_fits(const ofx_conv_desc* d);
+bool ofx_conv_wino44_fused_fits(const ofx_conv_desc* d);
+int ofx_conv_wino44_stats_rows(const ofx_conv_desc* d);
 bool ofx_conv_wino44_pays(const ofx_conv_desc* d);
 double ofx_conv_wino44_flops(const ofx_conv_desc* d);
-int ofx_conv_wino44_launch(const ofx_conv_desc* d, float alpha, hipStream_t s, hipEvent_t stop_event);
+int ofx_conv_wino44_launch(const ofx_conv_desc* d, float alpha, float* stats, hipStream_t s, hipEvent_t stop_event);
 
 // net_misc.hip: the per-image reduction of ofx_conv2d_stats' partials (ofx.h, ofx_inorm_finalize) with an optional
 // gamma / beta (both or neither): an affine folded into the (mean, rstd) pair, (x - mean') * rstd' = (x - mu) * rs * gamma + beta

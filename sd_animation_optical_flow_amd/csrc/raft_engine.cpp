@@ -39,7 +39,7 @@ struct ConvW {
     float* wino = nullptr;    // stride-1 3x3 layers (update block, mask.0, the encoders' residual stages): the Winograd F(2x2,3x3)
                               // operand (ofx_wino_conv_weight); the GRU's
                               // per-iteration 1x5 / 5x1 layers: the F(4,5) operand (ofx_wino15_conv_weight); or null
-    float* wino4 = nullptr;   // the update block's 3x3 layers and mask.0: the Winograd F(4x4,3x3) operand (ofx_wino44_conv_weight), or null
+    float* wino4 = nullptr;   // the update block's 3x3 layers, mask.0 and the encoders' stride-1 3x3 layers: the Winograd F(4x4,3x3) operand (ofx_wino44_conv_weight), or null
     int cout = 0, cin = 0, cin_pad = 0, kh = 0, kw = 0;
     long kpad = 0;
     std::string name;         // layer label for the per-layer profile (ofx_prof_enable(2))
@@ -274,7 +274,7 @@ int add_wino(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const std
     if (st < 0) return (int)st;
     int up = upload(r, u, &c.wino);
     if (up || !k3x3 || !wino4) return up;
-    // the update block's 3x3 layers: the F(4x4,3x3) operand next to it (conv.hip takes it where its grid pays)
+    // the update block's and the encoders' 3x3 layers: the F(4x4,3x3) operand next to it (conv.hip takes it where its grid pays)
     const long n4 = ofx_wino44_conv_weight(nullptr, c.cout, ci, nullptr);
     if (n4 < 0) return (int)n4;
     std::vector<float> u4((size_t)n4);
@@ -316,13 +316,14 @@ int build_encoder(ofx_raft* r, const std::map<std::string, HostTensor>& sd, cons
             st = add_conv(r, sd, p + ".conv2", pa + ".conv2", 0, B(pb + ".norm2"), 1.f);
             if (!st) st = A(pb + ".norm2");
             if (st) return st;
-            // the stride-1 3x3 layers also get the Winograd F(2x2,3x3) operand: every conv2, and conv1 but for the first block of
-            // a strided stage (conv.hip takes the fused kernel when the grid fills the chip).  OFX_CONV_NO_WINOGRAD_ENC, read once per
-            // process at the first engine build: never here
+            // the stride-1 3x3 layers also get the Winograd F(2x2,3x3) and F(4x4,3x3) operands: every conv2, and conv1 but for the
+            // first block of a strided stage (conv.hip takes a fused kernel when the grid fills the chip: F(4x4) from 768 workgroups
+            // of a 16x32 patch on, with the fused norm, residual merge and statistics of the F(2x2) kernel).
+            // OFX_CONV_NO_WINOGRAD_ENC, read once per process at the first engine build: never here
             static const bool no_wino_enc = getenv("OFX_CONV_NO_WINOGRAD_ENC") != nullptr;
             if (!no_wino_enc) {
-                if (li == 1 || bi == 1) st = add_wino(r, sd, {p + ".conv1"}, {}, pa + ".conv1");
-                if (!st) st = add_wino(r, sd, {p + ".conv2"}, {}, pa + ".conv2");
+                if (li == 1 || bi == 1) st = add_wino(r, sd, {p + ".conv1"}, {}, pa + ".conv1", true);
+                if (!st) st = add_wino(r, sd, {p + ".conv2"}, {}, pa + ".conv2", true);
                 if (st) return st;
             }
             if (li > 1 && bi == 0) {

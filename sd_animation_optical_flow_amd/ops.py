@@ -319,8 +319,8 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
     input read zeros: pad (0, 0) with out_hw = (H/2, W/2) is the VAE's F.pad(x, (0,1,0,1)) + stride-2 convolution).
     `addend` [B,Hout,Wout,cout] is added before the activation (`res` adds after it and applies ReLU).
     `wino_w` (wino_conv_weight / wino15_conv_weight, on the device) lets a qualifying 3x3 / 1x5 / 5x1 layer run the fused
-    Winograd kernel (tile = TILE_WINOGRAD forces it); `wino4_w` (wino44_conv_weight) lets a qualifying plain 3x3 layer run the
-    F(4x4,3x3) kernel where its grid pays (tile = TILE_WINOGRAD4 forces it).  `out` [B,Hout,Wout,C >= out_off + cout]: write channels
+    Winograd kernel (tile = TILE_WINOGRAD forces it); `wino4_w` (wino44_conv_weight) lets a qualifying 3x3 layer run the
+    F(4x4,3x3) kernel where its grid pays (tile = TILE_WINOGRAD4 forces it), `res`, `nmean` / `nrstd` and `stats_part` included.  `out` [B,Hout,Wout,C >= out_off + cout]: write channels
     [out_off, out_off + cout) of it.  `stats_part` (f32 on the device): run ofx_conv2d_stats, which leaves the per-channel
     (sum, sum of squares) partials of the outputs there when the launch can produce them ([B][rows][cout][2]; see inorm_finalize).
     `precision`: a key of CONV_PRECISIONS (default exact fp32).

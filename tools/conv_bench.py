@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the implicit-GEMM kernel on the update-block / encoder shapes (B=64 @512x768).
 usage: python tools/conv_bench.py [libofx variant .so ...]
-CONV_BENCH_WINO4=1: the Winograd F(4x4,3x3) kernel against F(2x2,3x3) over the batch sizes that set its gate."""
+CONV_BENCH_WINO4=1: the Winograd F(4x4,3x3) kernel against F(2x2,3x3) over the batch sizes that set its gate;
+CONV_BENCH_WINO4_ENC=1: the same on the encoders' stages, fused norm, statistics and residual merge included."""
 import ctypes as C, sys, os, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -73,10 +74,18 @@ if os.environ.get("CONV_BENCH_WINO_ENC"):   # ... and on the encoders' stride-1 
               for c, s, H, W in ((64, 2, 384, 256), (96, 4, 192, 128), (128, 8, 96, 64)) for e in ("relu", "res", "stats", "norm+stats")]
     SHAPES.append(("mask.0 3x3 128->256", 64, 64, 96, 128, 256, 3, 3, 1, 0))
     TILES = [0, 1]
+if os.environ.get("CONV_BENCH_WINO4_ENC"):  # F(4x4,3x3) (tile 2: the plain kernel and its fused variants) against F(2x2,3x3) (tile 1) on the
+    # encoders' three stages over the batch, with the epilogues they run there: the gate of plan path 4
+    SHAPES = [(f"B{b} enc {c}->{c} {H}x{W} {e}", b, H, W, c, c, 3, 3, 1, 0, e)
+              for c, H, W in ((64, 384, 256), (96, 192, 128), (128, 96, 64)) for e in ("relu", "norm+stats", "res") for b in (4, 8, 16, 64)]
+    TILES = [1, 2]
 if os.environ.get('CONV_BENCH_TILES'):
     TILES = [int(t) for t in os.environ['CONV_BENCH_TILES'].split(',')]
 if os.environ.get("CONV_BENCH_ONLY"):
     SHAPES = [x for x in SHAPES if os.environ["CONV_BENCH_ONLY"] in x[0]]
+
+
+NAME_W = max([24] + [len(x[0]) for x in SHAPES])   # (24: the layout of the committed tables; the encoder gate's names are longer)
 
 
 def run(libpath):
@@ -139,7 +148,7 @@ def run(libpath):
             ms = e0.elapsed_time(e1) / n
             fl = 2.0 * B * (H // st) * (W // st) * co * K   # direct-convolution FLOPs for every tile (Winograd: "effective" rate)
             extra = f"  stats rows {rows.value}" if part is not None else ""
-            print(f"  {name:<24} tile {tile:>9} {ms:8.3f} ms  {fl / ms / 1e9:7.1f} TFLOP/s{extra}")
+            print(f"  {name:<{NAME_W}} tile {tile:>9} {ms:8.3f} ms  {fl / ms / 1e9:7.1f} TFLOP/s{extra}")
 if __name__ == "__main__":
     libs = sys.argv[1:] or [_lib.LIB_PATH]
     for l in libs:
