@@ -1402,7 +1402,6 @@ const ConvKnobs& conv_knobs() {
 
 // ---- plan: everything a launch needs that is not a pointer.  conv_plan is a pure function of the descriptor's numbers (and of which
 // of its pointers are set), the extras and the knobs: no HIP call, no environment, no global state.
-enum { kPathIgemm = 0, kPathWino3x3 = 1, kPathWino15 = 2, kPathWino44 = 3, kPathWino44Fused = 4 };
 struct ConvPlan : ofx_conv_plan {   // the public fields (ofx.h: path, tile, arithmetic, schedule, grid, statistics rows) and ...
     int inst = -1;                  // direct kernels: the row of kTiles that bm ... ks and ksplit > 1 name
     const char* name = nullptr;     // family of the per-layer profile
@@ -1422,44 +1421,22 @@ int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, C
               : d->epi == OFX_EPI_FLOW   ? "igemm_conv_flow"
                                          : "igemm_conv";
 
-    // ---- fused Winograd (conv_wino.hip): F(2x2,3x3) for the update block's and the encoders' stride-1 3x3 layers (4 instead of 9
-    // multiplies per output; residual merge, fused instance norm and epilogue statistics included) and F(4,5) for the SepConvGRU's
-    // 1x5 / 5x1 layers (2 instead of 5, GRU gate epilogues included).  Only on grids that fill the chip (ofx_conv_wino_pays):
-    // smaller grids, the single pair among them, keep the direct kernels and their small-grid schedules.
-    // F(4x4,3x3) (2.25 multiplies per output) is a route of its own with its own operand and error class, where its
-    // one-workgroup-per-CU grid fills whole rounds of the chip (ofx_conv_wino44_pays): path 3, the plain kernel, for plain 3x3
-    // layers (the update block's, the context encoder's conv1); path 4, its fused variants, for a descriptor with a residual
-    // merge, a fused norm or requested statistics (the encoders' other layers; statistics as path 1, one row per 16x32 patch).
-    // A descriptor without wino4_w plans exactly as before.
-    const bool force4 = d->tile == OFX_CONV_TILE_WINOGRAD4;
-    if (force4 || (d->tile == 0 && !kn.no_wino44 && d->wino4_w)) {
-        const bool fused = want_stats || d->res || d->nmean || d->nrstd;
-        const int srows = want_stats ? ofx_conv_wino44_stats_rows(d) : 0;
-        const bool stats_ok = !want_stats || (srows > 0 && (size_t)d->B * srows * d->Cout * 2 <= x.stats_cap);
-        const bool fits = nz == 1 && !pool && (fused ? stats_ok && ofx_conv_wino44_fused_fits(d) : ofx_conv_wino44_fits(d));
-        if (force4 && !fits) return OFX_EINVAL;
-        if (fits && (force4 || ofx_conv_wino44_pays(d))) {
-            p->path = fused ? kPathWino44Fused : kPathWino44;
-            p->stats_rows = srows;
-            p->flops = ofx_conv_wino44_flops(d);
-            return 0;
-        }
+    // ---- fused Winograd (conv_wino.hip), before any direct kernel: F(4x4,3x3) (2.25 multiplies per output) and F(2x2,3x3) (4
+    // instead of 9) for the update block's and the encoders' stride-1 3x3 layers, residual merge, fused instance norm and epilogue
+    // statistics included, and F(4,5) for the SepConvGRU's 1x5 / 5x1 layers (2 instead of 5, GRU gate epilogues included).
+    // ofx_conv_wino_choose holds the whole rule -- which route fits, whether its grid fills the chip enough to pay (smaller grids,
+    // the single pair among them, keep the direct kernels and their small-grid schedules), what a forced tile or a switch does:
+    // path 1 F(2x2,3x3), 2 F(4,5), 3 the plain F(4x4,3x3) kernel, 4 its fused variants (a residual merge, a fused norm or
+    // requested statistics).  A descriptor with neither wino_w nor wino4_w plans as if the routes did not exist.
+    OfxWinoChoice wino;
+    if (int st = ofx_conv_wino_choose(d, want_stats, x.stats_cap, pool, kn.no_wino, kn.no_wino15, kn.no_wino44, &wino)) return st;
+    if (wino.path != kPathIgemm) {
+        p->path = wino.path;
+        p->stats_rows = wino.stats_rows;
+        p->flops = wino.flops;
+        return 0;
     }
-    const bool force = d->tile == OFX_CONV_TILE_WINOGRAD;
     const bool one_d = (d->KH == 1 && d->KW == 5) || (d->KH == 5 && d->KW == 1);
-    if (force || (d->tile == 0 && !(one_d ? kn.no_wino15 : kn.no_wino) && d->wino_w)) {
-        // asked for statistics: only where the fused kernel leaves them (one row per 8x16 patch), in the caller's room
-        const int srows = want_stats ? ofx_conv_wino_stats_rows(d) : 0;
-        const bool stats_ok = !want_stats || (srows > 0 && (size_t)d->B * srows * d->Cout * 2 <= x.stats_cap);
-        const bool fits = nz == 1 && stats_ok && !pool && ofx_conv_wino_fits(d);
-        if (force && !fits) return OFX_EINVAL;
-        if (fits && (force || ofx_conv_wino_pays(d))) {
-            p->path = one_d ? kPathWino15 : kPathWino3x3;
-            p->stats_rows = srows;
-            p->flops = ofx_conv_wino_flops(d);
-            return 0;
-        }
-    }
     p->flops = 2.0 * (double)M * d->Cout * K * nz;
 
     // ---- tile selection
@@ -1768,10 +1745,8 @@ int ofx_conv2d_ex(const ofx_conv_desc* d, const ConvExtra* extra, hipStream_t s)
     if ((st = conv_plan(d, x, conv_knobs(), &p))) return st;
     OfxProfScope prof(p.name, s);
     prof.flops(p.flops);
-    if (p.path == kPathWino44 || p.path == kPathWino44Fused) {
-        st = ofx_conv_wino44_launch(d, x.alpha, p.stats_rows ? x.stats_part : nullptr, s, x.stop_event);
-    } else if (p.path != kPathIgemm) {
-        st = ofx_conv_wino_launch(d, x.alpha, x.stats_rows ? x.stats_part : nullptr, s, x.stop_event);
+    if (p.path != kPathIgemm) {
+        st = ofx_conv_wino_launch(d, p.path, x.alpha, p.stats_rows ? x.stats_part : nullptr, s, x.stop_event);
     } else {
         const bool pool = x.pool.out != nullptr;
         st = kTiles[p.inst].launch(conv_args(d, x, p), pool ? kEpiVolPool : d->epi, !pool && d->nmean != nullptr, d->nz > 1 ? d->nz : 1, s, x.stop_event);

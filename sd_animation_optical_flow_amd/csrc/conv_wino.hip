@@ -9,10 +9,19 @@
 //                                                          output instead of 9
 //   F(4, 5):      y = A^T [ (G g) (.) (B^T d) ]           4 outputs from 8 inputs, points {0, 1, -1, 2, -2, 1/2, -1/2, inf}, 8 point
 //                                                          products: 2 multiplies per output instead of 5
+//   F(4x4, 3x3):  the 2D form over {0, 1, -1, 2, -2, inf}   4x4 outputs from a 6x6 input tile, 36 point products: 2.25 multiplies
+//                                                          per output, with an operand (ofx_conv_desc.wino4_w) and an error
+//                                                          class of its own
 //   (Lavin & Gray, "Fast Algorithms for Convolutional Neural Networks", 2016; Toom-Cook)
 //
+// Three algorithms, eighteen kernels (six fused-option or epilogue variants each), and one host section behind the kernels: a
+// table with a row per algorithm (kAlgs: patch, tile arithmetic, operand, grid gate, what it admits, its kernels), and on it the
+// two entries the launcher knows -- ofx_conv_wino_choose, the pure rule "which route, if any, takes this descriptor", and
+// ofx_conv_wino_launch.  Nothing outside this file names an algorithm.
+//
 // Everything between the input and the output stays on chip -- the unfused form (transformed input and output through HBM) costs as
-// much traffic as it saves multiplies ("Winograd").  Both kernels share one scaffold:
+// much traffic as it saves multiplies ("Winograd").  F(4x4, 3x3) is described at its kernels (Halo44, below);
+// F(2x2, 3x3) and F(4, 5) share one scaffold:
 //   * a workgroup owns one 8x16-pixel output patch -- 32 tiles of 2x2, 1x4 (1x5 layers, along W) or 4x1 (5x1 layers, along H) --
 //     and 64 (2D) or 128 (1D) output channels;
 //   * per 16-channel slab the input halo is staged in LDS once (buffer descriptors return the zero padding);
@@ -68,26 +77,27 @@ struct Halo3x3 : HaloGeom<18, 10, -1, -1> {
     __device__ static int at(int pix) { return at(pix / W, pix % W); }
 };
 
+// The argument block of all eighteen kernels (host: wino_args fills it from a descriptor and a row of kAlgs)
 struct WinoK {
     const float* in0;
     const float* in1;
-    const float* u;          // ofx_wino_conv_weight / ofx_wino15_conv_weight layout
+    const float* u;          // ofx_wino_conv_weight / ofx_wino15_conv_weight / ofx_wino44_conv_weight layout, by algorithm
     const float* scale;
     const float* shift;
-    const float* addend;     // 1D kernel only, as the GRU pointers below
-    const float* res;        // 3x3 kernel only: residual merge relu(y + res)
-    const float* nmean;      // 3x3 kernel only: relu((x - mean) * rstd) on the operand, [B][c0]
+    const float* addend;     // F(4, 5) only, as the GRU pointers below
+    const float* res;        // the 3x3 algorithms only: residual merge relu(y + res)
+    const float* nmean;      // the 3x3 algorithms only: relu((x - mean) * rstd) on the operand, [B][c0]
     const float* nrstd;
-    float* stats;            // 3x3 kernel only: per-patch (sum, sum of squares) of every output channel, [B][tpi][Cout][2]
+    float* stats;            // the 3x3 algorithms only: per-patch (sum, sum of squares) of every output channel, [B][tpi][Cout][2]
     float* out;
     float* aux_z;
     float* aux_rh;
     float* aux_h;
     int ld0, c0, ld1, cin, ldo, ldadd, ldh, ldres;
     int H, W, Cout, act;
-    int nblk;                // output blocks of 64 (2D) or 128 (1D) channels
+    int nblk;                // output blocks of 64 (3x3) or 128 (F(4, 5)) channels
     int nb32;                // 32-channel blocks of u
-    int tpr, tpi, mtiles;    // patches per image row / per image, patches in all
+    int tpr, tpi, mtiles;    // patches (8x16; F(4x4, 3x3): 16x32) per image row / per image, patches in all
     int bytes0, bytes1, bytesu;
     float alpha;
 };
@@ -572,20 +582,6 @@ __global__ __launch_bounds__(256, 2) void wino_conv_kernel(const WinoK p) {
     }
 }
 
-int launch3x3(const WinoK& k, dim3 grid, dim3 block, hipStream_t s, hipEvent_t ev) {
-    const int v = (k.nmean ? 4 : 0) | (k.res ? 2 : 0) | (k.stats ? 1 : 0);
-    switch (v) {
-        case 0: OFX_LAUNCH((wino_conv_kernel<false, false, false>), grid, block, s, ev, k); break;
-        case 1: OFX_LAUNCH((wino_conv_kernel<false, false, true>), grid, block, s, ev, k); break;
-        case 2: OFX_LAUNCH((wino_conv_kernel<false, true, false>), grid, block, s, ev, k); break;
-        case 4: OFX_LAUNCH((wino_conv_kernel<true, false, false>), grid, block, s, ev, k); break;
-        case 5: OFX_LAUNCH((wino_conv_kernel<true, false, true>), grid, block, s, ev, k); break;
-        case 6: OFX_LAUNCH((wino_conv_kernel<true, true, false>), grid, block, s, ev, k); break;
-        default: return OFX_EINVAL;   // statistics are of raw outputs: never with a residual merge
-    }
-    return ofx_launch_status();
-}
-
 // ---- F(4, 5): 128 output channels per workgroup, wave w = all 8 points x 32 channels
 template <bool VERT, int EPI>
 __global__ __launch_bounds__(256, 2) void wino15_conv_kernel(const WinoK p) {
@@ -656,17 +652,6 @@ __global__ __launch_bounds__(256, 2) void wino15_conv_kernel(const WinoK p) {
     }
 }
 
-template <bool VERT>
-int launch15(const WinoK& k, int epi, dim3 grid, dim3 block, hipStream_t s, hipEvent_t ev) {
-    switch (epi) {
-        case OFX_EPI_PLAIN: OFX_LAUNCH((wino15_conv_kernel<VERT, OFX_EPI_PLAIN>), grid, block, s, ev, k); break;
-        case OFX_EPI_GRU_ZR: OFX_LAUNCH((wino15_conv_kernel<VERT, OFX_EPI_GRU_ZR>), grid, block, s, ev, k); break;
-        case OFX_EPI_GRU_Q: OFX_LAUNCH((wino15_conv_kernel<VERT, OFX_EPI_GRU_Q>), grid, block, s, ev, k); break;
-        default: return OFX_EINVAL;
-    }
-    return ofx_launch_status();
-}
-
 // ---- F(4x4, 3x3): 36 point products per 16 outputs (2.25 multiplies per output), points {0, 1, -1, 2, -2, inf} (Lavin & Gray's
 // matrices).  A workgroup of twelve waves owns a 16x32-pixel output patch -- 32 tiles of 4x4 -- and 64 output channels; wave
 // (i, nt) owns row i of the 6x6 point grid and the nt-th 32 output channels: six accumulators.  The input transform B^T d B is
@@ -727,183 +712,190 @@ __global__ __launch_bounds__(768, 1) void wino44_fused_kernel(const WinoK p) {
 #include "conv_wino44_body.inl"
 }
 
-bool is_3x3(const ofx_conv_desc* d) { return d->KH == 3 && d->KW == 3; }
+// ---- host: one row per algorithm, the rule that picks a route for a descriptor, the launch
+
+using WinoKernel = void (*)(WinoK);
+
+// The kernels of an algorithm by launch variant.  3x3: NORM * 4 + RES * 2 + STATS (statistics are of raw outputs: never with a
+// residual merge); F(4, 5): VERT * 3 + epilogue.
+const WinoKernel kKernels22[8] = {wino_conv_kernel<false, false, false>, wino_conv_kernel<false, false, true>,
+                                  wino_conv_kernel<false, true, false>,  nullptr,
+                                  wino_conv_kernel<true, false, false>,  wino_conv_kernel<true, false, true>,
+                                  wino_conv_kernel<true, true, false>,   nullptr};
+const WinoKernel kKernels15[8] = {wino15_conv_kernel<true, OFX_EPI_PLAIN>,  wino15_conv_kernel<true, OFX_EPI_GRU_ZR>,
+                                  wino15_conv_kernel<true, OFX_EPI_GRU_Q>,  wino15_conv_kernel<false, OFX_EPI_PLAIN>,
+                                  wino15_conv_kernel<false, OFX_EPI_GRU_ZR>, wino15_conv_kernel<false, OFX_EPI_GRU_Q>,
+                                  nullptr,                                  nullptr};
+const WinoKernel kKernels44[8] = {wino44_conv_kernel,                       wino44_fused_kernel<false, false, true>,
+                                  wino44_fused_kernel<false, true, false>,  nullptr,
+                                  wino44_fused_kernel<true, false, false>,  wino44_fused_kernel<true, false, true>,
+                                  wino44_fused_kernel<true, true, false>,   nullptr};
+
+struct WinoAlg {
+    bool one_d;                        // the layers it serves: 1x5 / 5x1, else 3x3
+    int ph, pw;                        // output patch of a workgroup
+    int points, outputs;               // point products and outputs per tile (the FLOPs it executes)
+    int cblk;                          // output channels per workgroup
+    int threads, dyn_lds;              // per workgroup; LDS bytes asked for at the launch (0: the kernel's own static arrays)
+    const float* ofx_conv_desc::*u;    // its pre-transformed weights
+    int tile;                          // the ofx_conv_desc.tile value that forces it
+    long min_grid;                     // the grid gate: at least this many patches, or (per_block) patches x channel blocks,
+    bool per_block;                    //   for the route to be taken unforced
+    // What it admits besides the plain epilogue.  gates: an addend and the GRU gate epilogues, and none of the fused options; else
+    // the fused options of the 3x3 kernels -- residual merge, relu(norm(.)) on the operand, epilogue statistics -- and no addend
+    bool gates;
+    bool norm_pair;                    // nmean and nrstd both or neither (else: a lone nrstd is ignored)
+    int norm_max_cin;                  // most input channels under a fused norm
+    int path, path_fused;              // ofx_conv_plan.path, without and with a fused option (statistics included)
+    const WinoKernel* kernels;
+};
+
+// In the order of preference.  The grid gates:
+//   F(4x4, 3x3) against F(2x2, 3x3): at least 768 workgroups, three for each of the chip's 256 CUs, where its workgroups run one
+//     per CU.  Measured per layer shape at B = 4 ... 64 (profiles/r21_wino44_gate.txt): it wins at 768, 864,
+//     1152, 1536, 2304 and 3072 workgroups and loses or ties at every measured grid of 576 or fewer.  Of the grids that end in a
+//     nearly empty round only 864 was measured.  The encoders' stages with their fused variants
+//     (profiles/r25_enc_wino44_gate.txt): wins at every grid from 768 on (x1.24 - x1.45), loses at 96 and wins by less at 192 and
+//     384; the same gate.
+//   F(2x2, 3x3) and F(4, 5) against the direct kernels and their small-grid schedules: 3x3, at least four workgroups per CU (two
+//     rounds at its two per CU); 1x5 / 5x1, at least one 8x16 patch per CU (from six 512x768 pairs on; in isolation the kernel
+//     already beat the direct one at four).
+const WinoAlg kAlgs[] = {
+    // F(4x4, 3x3); under a fused norm, as many input channels as the kernel stages means and rstds for
+    {false, 16, 32, 36, 16, 64, 768, kSmem44, &ofx_conv_desc::wino4_w, OFX_CONV_TILE_WINOGRAD4, 768, true,
+     false, true, kNorm44MaxCin, kPathWino44, kPathWino44Fused, kKernels44},
+    // F(2x2, 3x3)
+    {false, 8, 16, 16, 4, 64, 256, 0, &ofx_conv_desc::wino_w, OFX_CONV_TILE_WINOGRAD, 1024, true,
+     false, false, 0x7FFFFFFF, kPathWino3x3, kPathWino3x3, kKernels22},
+    // F(4, 5)
+    {true, 8, 16, 8, 4, 128, 256, 0, &ofx_conv_desc::wino_w, OFX_CONV_TILE_WINOGRAD, 256, false,
+     true, false, 0, kPathWino15, kPathWino15, kKernels15},
+};
+constexpr int kNumAlgs = sizeof kAlgs / sizeof kAlgs[0];
+
 bool is_1d(int KH, int KW) { return (KH == 1 && KW == 5) || (KH == 5 && KW == 1); }
-int wino_points(const ofx_conv_desc* d) { return is_3x3(d) ? 16 : 8; }
-int wino_cblk(const ofx_conv_desc* d) { return is_3x3(d) ? 64 : 128; }   // output channels per workgroup
 
-}  // namespace
-
-// Shape test: fp32, one problem, stride 1, 3x3 (pad 1, 1), 1x5 (pad 0, 2) or 5x1 (pad 2, 0) keeping the map size, a map of whole
-// 8x16 patches, 16-channel slabs that never straddle the two input segments.  Epilogues: 3x3, plain without addend, optionally
-// with the residual merge relu(y + res) and / or relu(norm(.)) fused into the operand (single segment: the encoders' layers);
-// 1x5 / 5x1, no fused norm or residual, plain (optional addend) or a GRU gate epilogue whose z | r split falls on a 128-channel
-// block boundary.  Plain: ReLU or identity.
-bool ofx_conv_wino_fits(const ofx_conv_desc* d) {
+// Shape test of row `a`: fp32, one problem, stride 1, 3x3 (pad 1, 1), 1x5 (pad 0, 2) or 5x1 (pad 2, 0) keeping the map size, a map
+// of whole patches, 16-channel slabs that never straddle the two input segments, the row's operand set and aligned.  Epilogues:
+// plain (ReLU or identity, scale / shift, strided destination); the 3x3 rows without addend, optionally with the residual merge
+// relu(y + res) and / or relu(norm(.)) fused into the operand (single segment, aligned mean / rstd: the encoders' layers); F(4, 5)
+// with no fused norm or residual, plain (optional addend) or a GRU gate epilogue whose z | r split falls on a 128-channel block
+// boundary.
+bool wino_fits(const WinoAlg& a, const ofx_conv_desc* d) {
     const int cin = d->c0 + d->c1;
+    const float* const u = d->*a.u;
     const bool plain = d->epi == OFX_EPI_PLAIN && d->out != nullptr && d->ldo >= d->Cout && (d->act == OFX_ACT_NONE || d->act == OFX_ACT_RELU);
-    bool shape_epi = false;
-    if (is_3x3(d)) {
-        shape_epi = d->padH == 1 && d->padW == 1 && plain && !d->addend && (!d->res || d->ldres >= d->Cout) &&
-                    (!d->nmean || (d->nrstd && !d->in1 && ofx_aligned16(d->nmean) && ofx_aligned16(d->nrstd)));
-    } else if (is_1d(d->KH, d->KW)) {
-        shape_epi = d->padH == d->KH / 2 && d->padW == d->KW / 2 && !d->nmean && !d->res &&
-                    (plain || (d->epi == OFX_EPI_GRU_ZR && (d->Cout / 2) % 128 == 0) || d->epi == OFX_EPI_GRU_Q);
+    const bool shape = a.one_d ? is_1d(d->KH, d->KW) : d->KH == 3 && d->KW == 3;
+    bool epi;
+    if (a.gates) {
+        epi = !d->nmean && !d->res && (plain || (d->epi == OFX_EPI_GRU_ZR && (d->Cout / 2) % a.cblk == 0) || d->epi == OFX_EPI_GRU_Q);
+    } else {
+        epi = plain && !d->addend && (!d->res || d->ldres >= d->Cout) && (!a.norm_pair || (d->nmean != nullptr) == (d->nrstd != nullptr)) &&
+              (!d->nmean || (d->nrstd && !d->in1 && d->c0 <= a.norm_max_cin && ofx_aligned16(d->nmean) && ofx_aligned16(d->nrstd)));
     }
-    return shape_epi && d->precision == OFX_PREC_FP32 && (d->nz <= 1) && d->stride == 1 && d->Hout == d->Hin && d->Wout == d->Win &&
-           d->Hin % 8 == 0 && d->Win % 16 == 0 && cin % kWBK == 0 && d->c0 % kWBK == 0 &&
-           d->wino_w != nullptr && ofx_aligned16(d->wino_w);
+    return shape && epi && d->padH == d->KH / 2 && d->padW == d->KW / 2 && d->precision == OFX_PREC_FP32 && d->nz <= 1 && d->stride == 1 &&
+           d->Hout == d->Hin && d->Wout == d->Win && d->Hin % a.ph == 0 && d->Win % a.pw == 0 && cin % kWBK == 0 && d->c0 % kWBK == 0 &&
+           u != nullptr && ofx_aligned16(u);
 }
 
-// Rows per image of the instance-norm partial sums the fused kernel leaves for a fitting `d` (one per 8x16 patch), or 0 when it
-// cannot produce them: 3x3 raw outputs only (identity, no residual), as the direct kernel's epilogue statistics.
-int ofx_conv_wino_stats_rows(const ofx_conv_desc* d) {
-    return is_3x3(d) && d->act == OFX_ACT_NONE && !d->res ? (d->Hin / 8) * (d->Win / 16) : 0;
+// Rows per image of the instance-norm partial sums row `a` leaves for a fitting `d` (one per patch), or 0 when it cannot produce
+// them: the 3x3 rows, raw outputs only (identity, no residual), as the direct kernel's epilogue statistics.
+int wino_stats_rows(const WinoAlg& a, const ofx_conv_desc* d) {
+    return !a.gates && d->act == OFX_ACT_NONE && !d->res ? (d->Hin / a.ph) * (d->Win / a.pw) : 0;
 }
 
-// Whether the grid fills the chip enough for the fused kernel to beat the direct kernels and their small-grid schedules: 3x3, at
-// least four workgroups per CU (two rounds at its two per CU); 1x5 / 5x1, at least one 8x16 patch per CU (from six 512x768 pairs on;
-// in isolation the kernel already beat the direct one at four).
-bool ofx_conv_wino_pays(const ofx_conv_desc* d) {
-    const long patches = (long)d->B * (d->Hin / 8) * (d->Win / 16);
-    return is_3x3(d) ? patches * ((d->Cout + 63) / 64) >= 1024 : patches >= 256;
-}
-
-// Multiplies the fused kernel executes for `d` (x 2 FLOPs): 16 (3x3) or 8 (1D) point products per 4-output tile, input channel and
-// output channel
-double ofx_conv_wino_flops(const ofx_conv_desc* d) {
-    return 2.0 * wino_points(d) * ((double)d->B * d->Hout * d->Wout / 4.0) * (double)(d->c0 + d->c1) * d->Cout;
-}
-
-// The caller has validated the descriptor (ofx_conv2d_ex) and ofx_conv_wino_fits(d).  stats: null, or room for the partial
-// sums of ofx_conv_wino_stats_rows(d) > 0 rows per image (the caller has checked the size).
-int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, float* stats, hipStream_t s, hipEvent_t stop_event) {
-    OFX_REQUIRE(!stats || ofx_conv_wino_stats_rows(d) > 0, OFX_EINVAL);
-    WinoK k;
-    k.in0 = d->in0; k.in1 = d->in1; k.u = d->wino_w; k.scale = d->scale; k.shift = d->shift; k.addend = d->addend; k.out = d->out;
+// The argument block of a fitting descriptor.  Byte extents and the grid stay below 2^31 (32-bit offsets through buffer
+// descriptors); the 3x3 rows also ask that of the destination's float count, the F(4, 5) row does not.
+int wino_args(const WinoAlg& a, const ofx_conv_desc* d, float alpha, float* stats, WinoK* out) {
+    WinoK k{};
+    k.in0 = d->in0; k.in1 = d->in1; k.u = d->*a.u; k.scale = d->scale; k.shift = d->shift; k.addend = d->addend; k.out = d->out;
     k.res = d->res; k.nmean = d->nmean; k.nrstd = d->nrstd; k.stats = stats;
     k.aux_z = d->aux_z; k.aux_rh = d->aux_rh; k.aux_h = d->aux_h;
     k.ld0 = d->ld0; k.c0 = d->c0; k.ld1 = d->ld1; k.cin = d->c0 + d->c1; k.ldo = d->ldo; k.ldadd = d->ldadd; k.ldh = d->ldh;
     k.ldres = d->ldres;
     k.H = d->Hin; k.W = d->Win; k.Cout = d->Cout; k.act = d->act;
-    const int cblk = wino_cblk(d);
-    k.nblk = (d->Cout + cblk - 1) / cblk;
-    k.nb32 = cblk / 32 * k.nblk;
-    k.tpr = d->Win / 16;
-    k.tpi = (d->Hin / 8) * k.tpr;
+    k.nblk = (d->Cout + a.cblk - 1) / a.cblk;
+    k.nb32 = a.cblk / 32 * k.nblk;
+    k.tpr = d->Win / a.pw;
+    k.tpi = (d->Hin / a.ph) * k.tpr;
     const long mtiles = (long)d->B * k.tpi;
     const long npix = (long)d->B * d->Hin * d->Win;
     const long ext0 = ((npix - 1) * d->ld0 + d->c0) * 4, ext1 = d->in1 ? ((npix - 1) * d->ld1 + d->c1) * 4 : 0;
-    const long extu = (long)wino_points(d) * k.nb32 * 32 * k.cin * 4;
+    const long extu = (long)a.points * k.nb32 * 32 * k.cin * 4;
     OFX_REQUIRE(ext0 < (1L << 31) - 64 && ext1 < (1L << 31) - 64 && extu < (1L << 31) - 64, OFX_EINVAL);
-    OFX_REQUIRE(mtiles * k.nblk < (1L << 31) && (!is_3x3(d) || npix * d->ldo < (1L << 31)), OFX_EINVAL);
+    OFX_REQUIRE(mtiles * k.nblk < (1L << 31) && (a.one_d || npix * d->ldo < (1L << 31)), OFX_EINVAL);
     k.mtiles = (int)mtiles;
     k.bytes0 = (int)ext0; k.bytes1 = (int)ext1; k.bytesu = (int)extu;
     k.alpha = alpha;
-    const dim3 grid((unsigned)(k.mtiles * k.nblk), 1, 1), block(256, 1, 1);
-    if (is_3x3(d)) return launch3x3(k, grid, block, s, stop_event);
-    return d->KH == 5 ? launch15<true>(k, d->epi, grid, block, s, stop_event) : launch15<false>(k, d->epi, grid, block, s, stop_event);
+    *out = k;
+    return 0;
 }
 
-// ---- F(4x4, 3x3), the second route of the 3x3 layers (ofx_conv_desc.wino4_w).  Shape test of the plain kernel -- fp32, stride 1,
-// 'same' 3x3, a map of whole 16x32 patches, whole 16-channel slabs, the plain epilogue (ReLU or identity, scale / shift, strided
-// destination) with no addend, residual or fused norm.
-bool ofx_conv_wino44_fits(const ofx_conv_desc* d) {
-    const int cin = d->c0 + d->c1;
-    return is_3x3(d) && d->padH == 1 && d->padW == 1 && d->epi == OFX_EPI_PLAIN && d->out != nullptr && d->ldo >= d->Cout &&
-           (d->act == OFX_ACT_NONE || d->act == OFX_ACT_RELU) && !d->addend && !d->res && !d->nmean && !d->nrstd &&
-           d->precision == OFX_PREC_FP32 && d->nz <= 1 && d->stride == 1 && d->Hout == d->Hin && d->Wout == d->Win &&
-           d->Hin % 16 == 0 && d->Win % 32 == 0 && cin % kWBK == 0 && d->c0 % kWBK == 0 &&
-           d->wino4_w != nullptr && ofx_aligned16(d->wino4_w);
-}
-
-// ... and of the fused variants (the encoders' layers): the same shape rules, with the residual merge relu(y + res) and / or
-// relu(norm(.)) fused into the operand under the rules of ofx_conv_wino_fits (single segment, aligned mean / rstd), over as many
-// input channels as the kernel stages means and rstds for.
-bool ofx_conv_wino44_fused_fits(const ofx_conv_desc* d) {
-    ofx_conv_desc plain = *d;
-    plain.res = plain.nmean = plain.nrstd = nullptr;
-    return ofx_conv_wino44_fits(&plain) && (!d->res || d->ldres >= d->Cout) && (d->nmean != nullptr) == (d->nrstd != nullptr) &&
-           (!d->nmean || (!d->in1 && d->c0 <= kNorm44MaxCin && ofx_aligned16(d->nmean) && ofx_aligned16(d->nrstd)));
-}
-
-// Rows per image of the instance-norm partial sums the fused F(4x4) kernel leaves for a fitting `d` (one per 16x32 patch), or 0
-// when it cannot produce them: raw outputs only (identity, no residual), as ofx_conv_wino_stats_rows.
-int ofx_conv_wino44_stats_rows(const ofx_conv_desc* d) {
-    return is_3x3(d) && d->act == OFX_ACT_NONE && !d->res ? (d->Hin / 16) * (d->Win / 32) : 0;
-}
-
-// Whether F(4x4) beats F(2x2) on this grid: at least kWino44MinGroups workgroups (16x32 patches x 64-channel blocks), three for
-// each of the chip's 256 CUs, where its workgroups run one per CU.  Measured per layer shape at B = 4 ... 64
-// (profiles/r21_wino44_gate.txt): it wins at 768, 864, 1152, 1536, 2304 and 3072 workgroups and loses or
-// ties at every measured grid of 576 or fewer.  Of the grids that end in a nearly empty round only 864 was measured.
-// The encoders' stages with their fused variants (profiles/r25_enc_wino44_gate.txt): wins at every grid from 768 on (x1.24 - x1.45),
-// loses at 96 and wins by less at 192 and 384; the same gate.
-constexpr long kWino44MinGroups = 768;
-bool ofx_conv_wino44_pays(const ofx_conv_desc* d) {
-    const long patches = (long)d->B * (d->Hin / 16) * (d->Win / 32);
-    return patches * ((d->Cout + 63) / 64) >= kWino44MinGroups;
-}
-
-// 36 point products per 16-output tile, input channel and output channel (x 2 FLOPs)
-double ofx_conv_wino44_flops(const ofx_conv_desc* d) {
-    return 2.0 * 36.0 * ((double)d->B * d->Hout * d->Wout / 16.0) * (double)(d->c0 + d->c1) * d->Cout;
-}
-
-namespace {
-
-// more than 64 KB of LDS: allowed once per kernel and device (as corr_split.hip).  The kernel is a template argument, not a
-// function argument: the six kernels have one pointer type, and each needs flags of its own.
-template <void (*KERNEL)(WinoK)> int launch44(const WinoK& k, hipStream_t s, hipEvent_t stop_event) {
-    void (*const kernel)(WinoK) = KERNEL;
-    static bool allowed[64] = {};   // (one array per instantiation, i.e. per kernel)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return OFX_EINVAL;
-    if (!allowed[dev]) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kSmem44);
-        if (e != hipSuccess) return (int)e;
-        allowed[dev] = true;
+// Launch variant `v` of row `a`, the stop event (may be null) riding on the kernel (OFX_LAUNCH).  More than 64 KB of LDS is allowed
+// once per kernel and device (as corr_split.hip).
+int wino_launch_kernel(const WinoAlg& a, int v, const WinoK& k, hipStream_t s, hipEvent_t stop_event) {
+    const WinoKernel kernel = v >= 0 && v < 8 ? a.kernels[v] : nullptr;
+    OFX_REQUIRE(kernel != nullptr, OFX_EINVAL);
+    if (a.dyn_lds > 65536) {
+        static bool allowed[64][kNumAlgs][8] = {};
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return OFX_EINVAL;
+        bool& ok = allowed[dev][&a - kAlgs][v];
+        if (!ok) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, a.dyn_lds);
+            if (e != hipSuccess) return (int)e;
+            ok = true;
+        }
     }
-    const dim3 grid((unsigned)(k.mtiles * k.nblk), 1, 1), block(768, 1, 1);
-    if (stop_event) hipExtLaunchKernelGGL(kernel, grid, block, kSmem44, s, nullptr, stop_event, 0, k);
-    else hipLaunchKernelGGL(kernel, grid, block, kSmem44, s, k);
+    const dim3 grid((unsigned)(k.mtiles * k.nblk), 1, 1), block(a.threads, 1, 1);
+    if (stop_event) hipExtLaunchKernelGGL(kernel, grid, block, a.dyn_lds, s, nullptr, stop_event, 0, k);
+    else hipLaunchKernelGGL(kernel, grid, block, a.dyn_lds, s, k);
     return ofx_launch_status();
 }
 
 }  // namespace
 
-// The caller has validated the descriptor (ofx_conv2d_ex) and ofx_conv_wino44_fits(d), or ofx_conv_wino44_fused_fits(d) for one
-// with `res`, `nmean` or statistics.  stats: null, or room for the partial sums of ofx_conv_wino44_stats_rows(d) > 0 rows per
-// image (the caller has checked the size).
-int ofx_conv_wino44_launch(const ofx_conv_desc* d, float alpha, float* stats, hipStream_t s, hipEvent_t stop_event) {
-    OFX_REQUIRE(!stats || ofx_conv_wino44_stats_rows(d) > 0, OFX_EINVAL);
-    WinoK k{};
-    k.in0 = d->in0; k.in1 = d->in1; k.u = d->wino4_w; k.scale = d->scale; k.shift = d->shift; k.out = d->out;
-    k.res = d->res; k.nmean = d->nmean; k.nrstd = d->nrstd; k.stats = stats; k.ldres = d->ldres;
-    k.ld0 = d->ld0; k.c0 = d->c0; k.ld1 = d->ld1; k.cin = d->c0 + d->c1; k.ldo = d->ldo;
-    k.H = d->Hin; k.W = d->Win; k.Cout = d->Cout; k.act = d->act;
-    k.nblk = (d->Cout + 63) / 64;
-    k.nb32 = 2 * k.nblk;
-    k.tpr = d->Win / 32;
-    k.tpi = (d->Hin / 16) * k.tpr;
-    const long mtiles = (long)d->B * k.tpi;
-    const long npix = (long)d->B * d->Hin * d->Win;
-    const long ext0 = ((npix - 1) * d->ld0 + d->c0) * 4, ext1 = d->in1 ? ((npix - 1) * d->ld1 + d->c1) * 4 : 0;
-    const long extu = 36L * k.nb32 * 32 * k.cin * 4;   // (fragments of 512 bytes)
-    OFX_REQUIRE(ext0 < (1L << 31) - 64 && ext1 < (1L << 31) - 64 && extu < (1L << 31) - 64, OFX_EINVAL);
-    OFX_REQUIRE(mtiles * k.nblk < (1L << 31) && npix * d->ldo < (1L << 31), OFX_EINVAL);
-    k.mtiles = (int)mtiles;
-    k.bytes0 = (int)ext0; k.bytes1 = (int)ext1; k.bytesu = (int)extu;
-    k.alpha = alpha;
-    switch ((k.nmean ? 4 : 0) | (k.res ? 2 : 0) | (k.stats ? 1 : 0)) {
-        case 0: return launch44<&wino44_conv_kernel>(k, s, stop_event);
-        case 1: return launch44<&wino44_fused_kernel<false, false, true>>(k, s, stop_event);
-        case 2: return launch44<&wino44_fused_kernel<false, true, false>>(k, s, stop_event);
-        case 4: return launch44<&wino44_fused_kernel<true, false, false>>(k, s, stop_event);
-        case 5: return launch44<&wino44_fused_kernel<true, false, true>>(k, s, stop_event);
-        case 6: return launch44<&wino44_fused_kernel<true, true, false>>(k, s, stop_event);
-        default: return OFX_EINVAL;   // statistics are of raw outputs: never with a residual merge
+// Which Winograd route, if any, takes a validated descriptor: pure (no HIP call, no environment, no global state).  The rows are
+// tried in their order of preference.  A row is a candidate when its tile value forces it, or under the launcher's own rule
+// (tile = 0) when its switch is not off and its operand is set; it takes the layer when the layer fits it (wino_fits, no pooled
+// volume, and for requested statistics a row that leaves them and room for them) and, unforced, its grid gate holds.  Any other
+// layer goes on to the direct kernels (path 0) -- F(4, 5) never produces statistics, so a request for them does -- except under a
+// forced tile, which runs its route or is rejected.
+int ofx_conv_wino_choose(const ofx_conv_desc* d, bool want_stats, size_t stats_cap, bool pool, bool no_wino, bool no_wino15, bool no_wino44,
+                         OfxWinoChoice* c) {
+    *c = OfxWinoChoice{};
+    const bool off[kNumAlgs] = {no_wino44, no_wino, no_wino15};   // (in the order of kAlgs)
+    const bool one_d = is_1d(d->KH, d->KW);
+    for (int i = 0; i < kNumAlgs; ++i) {
+        const WinoAlg& a = kAlgs[i];
+        const bool force = d->tile == a.tile;
+        if (a.one_d != one_d || !(force || (d->tile == 0 && !off[i] && d->*a.u))) continue;
+        const int srows = want_stats ? wino_stats_rows(a, d) : 0;
+        const bool stats_ok = !want_stats || (srows > 0 && (size_t)d->B * srows * d->Cout * 2 <= stats_cap);
+        if (!(stats_ok && !pool && wino_fits(a, d))) continue;
+        const long patches = (long)d->B * (d->Hin / a.ph) * (d->Win / a.pw);
+        if (!force && patches * (a.per_block ? (d->Cout + a.cblk - 1) / a.cblk : 1) < a.min_grid) continue;
+        c->path = want_stats || d->res || d->nmean || d->nrstd ? a.path_fused : a.path;
+        c->stats_rows = srows;
+        // multiplies x 2: `points` point products per tile of `outputs` outputs, input channel and output channel
+        c->flops = 2.0 * a.points * ((double)d->B * d->Hout * d->Wout / a.outputs) * (double)(d->c0 + d->c1) * d->Cout;
+        return 0;
     }
+    return d->tile == OFX_CONV_TILE_WINOGRAD || d->tile == OFX_CONV_TILE_WINOGRAD4 ? OFX_EINVAL : 0;
+}
+
+// The launch of the route ofx_conv_wino_choose gave for `d` (path != 0).  stats: null, or the room the choice was made with, for
+// its stats_rows > 0 rows per image.
+int ofx_conv_wino_launch(const ofx_conv_desc* d, int path, float alpha, float* stats, hipStream_t s, hipEvent_t stop_event) {
+    const WinoAlg* a = nullptr;
+    for (const WinoAlg& row : kAlgs)
+        if (path == row.path || path == row.path_fused) a = &row;
+    OFX_REQUIRE(a && (!stats || wino_stats_rows(*a, d) > 0), OFX_EINVAL);
+    WinoK k;
+    if (int st = wino_args(*a, d, alpha, stats, &k)) return st;
+    const int v = a->gates ? (d->epi >= OFX_EPI_PLAIN && d->epi <= OFX_EPI_GRU_Q ? (d->KH == 5 ? 0 : 3) + d->epi : -1)
+                           : (k.nmean ? 4 : 0) | (k.res ? 2 : 0) | (k.stats ? 1 : 0);
+    return wino_launch_kernel(*a, v, k, s, stop_event);
 }
 
 namespace {

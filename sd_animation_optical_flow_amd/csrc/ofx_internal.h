@@ -71,21 +71,21 @@ struct ConvExtra {
 };
 // The one entry of the convolution launcher; ofx_conv2d / ofx_conv2d_stats are ofx_conv2d_ex with the matching extras (null: none)
 int ofx_conv2d_ex(const ofx_conv_desc* d, const ConvExtra* extra, hipStream_t s);
-// conv_wino.hip: the fused Winograd paths of ofx_conv2d, F(2x2,3x3) for 3x3 and F(4,5) for 1x5 / 5x1 layers, picked from KH / KW
-// (shape test, whether the grid is large enough to take it, rows per image of its epilogue statistics, executed FLOPs, launch)
-bool ofx_conv_wino_fits(const ofx_conv_desc* d);
-bool ofx_conv_wino_pays(const ofx_conv_desc* d);
-int ofx_conv_wino_stats_rows(const ofx_conv_desc* d);
-double ofx_conv_wino_flops(const ofx_conv_desc* d);
-int ofx_conv_wino_launch(const ofx_conv_desc* d, float alpha, float* stats, hipStream_t s, hipEvent_t stop_event);
-// ... and F(4x4,3x3), the second route of the 3x3 layers (ofx_conv_desc.wino4_w): the plain kernel (_fits) and its fused variants
-// with a residual merge, a fused norm or epilogue statistics (_fused_fits, _stats_rows)
-bool ofx_conv_wino44_fits(const ofx_conv_desc* d);
-bool ofx_conv_wino44_fused_fits(const ofx_conv_desc* d);
-int ofx_conv_wino44_stats_rows(const ofx_conv_desc* d);
-bool ofx_conv_wino44_pays(const ofx_conv_desc* d);
-double ofx_conv_wino44_flops(const ofx_conv_desc* d);
-int ofx_conv_wino44_launch(const ofx_conv_desc* d, float alpha, float* stats, hipStream_t s, hipEvent_t stop_event);
+// ofx_conv_plan.path (ofx.h): the direct kernels, or a fused Winograd route of conv_wino.hip
+enum { kPathIgemm = 0, kPathWino3x3 = 1, kPathWino15 = 2, kPathWino44 = 3, kPathWino44Fused = 4 };
+// conv_wino.hip: the fused Winograd routes of ofx_conv2d -- F(4x4,3x3), F(2x2,3x3) and F(4,5), a table row each -- behind two
+// entries.  The rule: which route takes a validated descriptor, given whether epilogue statistics are wanted (and the room for
+// them, in floats), whether the pooled volume is, and the launcher's three switches (conv_knobs).  Pure: no HIP call, no
+// environment, no global state.  Returns 0 with path = 0 (none: the direct kernels), or with the path, the rows per image of its
+// statistics and the FLOPs it executes; OFX_EINVAL for a forced tile (OFX_CONV_TILE_WINOGRAD*) whose route does not take `d`.
+struct OfxWinoChoice {
+    int path = kPathIgemm, stats_rows = 0;
+    double flops = 0.0;
+};
+int ofx_conv_wino_choose(const ofx_conv_desc* d, bool want_stats, size_t stats_cap, bool pool, bool no_wino, bool no_wino15, bool no_wino44,
+                         OfxWinoChoice* c);
+// ... and the launch of a chosen path (stats: null, or the room the choice was made with)
+int ofx_conv_wino_launch(const ofx_conv_desc* d, int path, float alpha, float* stats, hipStream_t s, hipEvent_t stop_event);
 
 // net_misc.hip: the per-image reduction of ofx_conv2d_stats' partials (ofx.h, ofx_inorm_finalize) with an optional
 // gamma / beta (both or neither): an affine folded into the (mean, rstd) pair, (x - mean') * rstd' = (x - mu) * rs * gamma + beta

@@ -92,7 +92,7 @@ def test_plan_agrees_with_the_python_restatement():
 
 
 def _wino_expected(B, H, W, cin, cout, kh, kw, stride):
-    """ofx_conv_wino_fits && ofx_conv_wino_pays for an fp32 plain ReLU / identity layer with 'same' padding and an aligned
+    """Whether ofx_conv_wino_choose takes an fp32 plain ReLU / identity layer with 'same' padding and an aligned
     operand, from their documented conditions: stride 1, a map of whole 8x16 patches, whole 16-channel slabs; then 3x3: at least
     1024 (patch, 64-channel block) workgroups; 1x5 / 5x1: at least 256 patches."""
     fits = (kh, kw) in ((3, 3), (1, 5), (5, 1)) and stride == 1 and H % 8 == 0 and W % 16 == 0 and cin % 16 == 0

@@ -82,7 +82,7 @@ VARIANTS = [(False, False, False), (False, False, True), (False, True, False), (
 @pytest.mark.parametrize("c,H,W", [(64, 32, 64), (96, 24, 48), (128, 16, 32)])
 @pytest.mark.parametrize("norm,res,stats", VARIANTS)
 def test_unit_normal_data_through_the_six_variants(cuda, c, H, W, norm, res, stats):
-    """<NORM, RES, STATS> as launch3x3 selects them: fused relu(norm(.)) on the operand, the residual merge, the epilogue
+    """<NORM, RES, STATS> as ofx_conv_wino_launch selects them: fused relu(norm(.)) on the operand, the residual merge, the epilogue
     statistics (raw outputs: identity activation).  |out - float64| <= 2e-5 everywhere, borders included."""
     ops = _ops()
     B = 2

@@ -514,7 +514,7 @@ LAYERS = {   # name: (kh, kw, cin, cout)
 
 
 def route_fused(kh, kw, B, H, W, cout):
-    """ofx_conv_wino_fits / ofx_conv_wino_pays as documented, for a plain fp32 stride-1 'same' layer with the operand given and the
+    """ofx_conv_wino_choose (its shape test and grid gates) as documented, for a plain fp32 stride-1 'same' layer with the operand given and the
     automatic tile: whole 8x16 patches, then 3x3 at >= 1024 workgroups of 64 output channels, 1x5 / 5x1 at >= 256 patches."""
     if H % 8 or W % 16:
         return False

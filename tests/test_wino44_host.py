@@ -93,7 +93,7 @@ def _plan(d, stats=0):
     return st, p.path
 
 
-GATE = 768   # workgroups: 16x32 patches x 64-channel blocks (ofx_conv_wino44_pays)
+GATE = 768   # workgroups: 16x32 patches x 64-channel blocks (the F(4x4,3x3) row's grid gate in conv_wino.hip)
 
 
 def test_plan_takes_path_3_where_it_fits_and_pays():
