@@ -26,6 +26,7 @@
  *                               ofgen_keyframe_inpaint.py:113-133,237-248,306-322,676-688,968-973,995-1027
  *   ofx_groupnorm_cat, ofx_emb_linear, ofx_timestep_embedding
  *                               ldm/modules/diffusionmodules/openaimodel.py:220-226,257-277,530-534,757-793 ; util.py:154-174
+ *   ofx_ddim_step               guided_ldm_inpainting.py:28-137,337-338 ; guided_ldm.py:82-89,123
  *
  * Layout conventions: images and flow are HWC ("channels-last"); network activations are
  * NHWC fp32; a flow field is f32[H,W,2] = (dx, dy) exactly as `algo.calc` returns it
@@ -266,6 +267,37 @@ int ofx_emb_linear(const float* x, int ldx, const float* w, const float* bias, f
  * device (fractional timesteps are legal), freqs [half] fp32 on the device: the table the reference builds on the CPU and moves
  * (:165-167).  out dense [B][dim].  The product is one fp32 multiplication, sinf / cosf the accurate ones (arguments reach 1e3). */
 int ofx_timestep_embedding(const float* t, const float* freqs, float* out, int B, int dim, void* stream);
+
+/* ---------------------------------------------------------------- sampler (guided_ldm_inpainting.py:28-137, guided_ldm.py:30-158) */
+/* The scalars of one DDIM step, fp32 as the reference forms them: cfg = unconditional_guidance_scale, sqrt_at = sqrt(ddim_alphas
+ * [index]), sqrt_1m_at = ddim_sqrt_one_minus_alphas[index], sqrt_aprev = sqrt(ddim_alphas_prev[index]), dir_coef = sqrt(1 - a_prev -
+ * sigma_t^2), sigma_t = ddim_sigmas[index] * temperature, g = the scalar guidance strength, sa / s1 = sqrt_alphas_cumprod /
+ * sqrt_one_minus_alphas_cumprod at the DDPM timestep of the NEXT step (what its q_sample reads). */
+typedef struct ofx_ddim_coef {
+    float cfg, sqrt_at, sqrt_1m_at, sqrt_aprev, dir_coef, sigma_t, g, sa, s1;
+} ofx_ddim_coef;
+#define OFX_DDIM_STEP       0   /* the whole chain below */
+#define OFX_DDIM_BLEND_ONLY 1   /* xp = x, then the blend: the blend before the first step and img2img_inpaint's final one */
+/* One guided DDIM step and the mask blend that opens the next one, per pixel row of C floats (C % 4 == 0), in this order:
+ *   e    = eps_u + cfg * (eps_c - eps_u)                       eps_u NULL: e = eps_c (no classifier-free guidance)
+ *   pred = (x - sqrt_1m_at * e) / sqrt_at
+ *   with guidance:  pred = pred * (1 - g) + guidance * g       g = gmap[row] when gmap is given, coef->g otherwise
+ *                   e    = (x - sqrt_at * pred) / sqrt_1m_at
+ *   xp   = sqrt_aprev * pred + dir_coef * e  [+ sigma_t * step_noise]
+ *   with nmask:     xp = (1 - nmask) * (sa * init + s1 * blend_noise) + nmask * xp      blend_noise NULL needs s1 == 0
+ *   out0[row] = xp;   out1[row] = xp when given;   pred_out[row] = pred when given
+ * OFX_DDIM_BLEND_ONLY skips everything above the blend (xp = x): eps_c, eps_u, guidance, gmap, step_noise and pred_out must be
+ * NULL and nmask given.  Every tensor is [rows][C] with its rows ld* floats apart (eps_c and eps_u share lde), so a channel slice of
+ * a wider NHWC buffer is a valid operand: out0 / out1 are meant to be channels 0..C-1 of the two halves of the UNet's padded
+ * input, and only those C floats of a row are written.  gmap is [rows].  ld* % 4 == 0, C % 4 == 0 and 16-byte aligned pointers
+ * (OFX_EALIGN); NULL x / out0 / coef (eps_c in OFX_DDIM_STEP), init without nmask or the reverse, gmap without guidance, ld < C,
+ * rows <= 0, an unknown mode (OFX_EINVAL).  out0 and out1 may each be exactly x (same pointer and row stride: a thread reads its
+ * float4 of every operand before it writes); any other overlap between an output and an input or between two outputs is
+ * OFX_EINVAL.  All of this is checked before the launch. */
+int ofx_ddim_step(const float* x, int ldx, const float* eps_c, const float* eps_u, int lde, const float* guidance, int ldg,
+                  const float* gmap, const float* step_noise, int ldsn, const float* init, int ldi, const float* nmask, int ldm,
+                  const float* blend_noise, int ldbn, float* out0, int ldo0, float* out1, int ldo1, float* pred_out, int ldp,
+                  const ofx_ddim_coef* coef, int mode, long rows, int C, void* stream);
 
 /* ---------------------------------------------------------------- key-frame detector */
 /* edges[b] = cv2.dilate(cv2.Canny(V, low, high), ones(ksize, ksize)) for BGR frames u8[B,H,W,3], with V = max(B,G,R)

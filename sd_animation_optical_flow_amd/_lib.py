@@ -53,6 +53,11 @@ class ConvPlan(C.Structure):
                                        "group_m", "stats_rows")]
 
 
+class DdimCoef(C.Structure):
+    """Mirror of `ofx_ddim_coef` (include/ofx.h)."""
+    _fields_ = [(n, C.c_float) for n in ("cfg", "sqrt_at", "sqrt_1m_at", "sqrt_aprev", "dir_coef", "sigma_t", "g", "sa", "s1")]
+
+
 class Tensor(C.Structure):
     """Mirror of `ofx_tensor`."""
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("ndim", C.c_int), ("shape", C.c_long * 4)]
@@ -117,6 +122,7 @@ SIGNATURES = {
     "ofx_groupnorm_cat": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _p, _p, _p, _p, _z, _i, _l, _i, _f, _i, _p]),
     "ofx_emb_linear": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "ofx_timestep_embedding": (_i, [_p, _p, _p, _i, _i, _p]),
+    "ofx_ddim_step": (_i, [_p, _i, _p, _p, _i, _p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, C.POINTER(DdimCoef), _i, _l, _i, _p]),
     "ofx_corr_slice_floats": (_i, [_i, _i]),
     "ofx_corr_volume": (_i, [_p, _p, C.POINTER(_p), _i, _i, _i, _i, _i, _p]),
     "ofx_corr_volume_split": (_i, [_p, _p, C.POINTER(_p), _i, _i, _i, _i, _i, _i, _i, _p]),

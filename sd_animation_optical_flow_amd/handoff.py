@@ -12,7 +12,7 @@ bit-exact to Pillow for the integer steps (GaussianBlur, Image.composite, the de
     conditioning_image  f32 [B,3,H,W]    image * (1 - conditioning_mask), the VAE encoder's input   (:145-149)
     conditioning_mask_latent f32 [B,1,h,w]  nearest-neighbour resize of conditioning_mask           (:151)
 
-The VAE / UNet / sampler that consume these are out of scope.
+`vae.VaeEncoder`, `unet.UNetModel` and `sampler.img2img_inpaint` consume these on the device.
 """
 from __future__ import annotations
 

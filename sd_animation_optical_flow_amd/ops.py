@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import json
 import math
-from typing import List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -1071,6 +1071,55 @@ def timestep_embedding(t: torch.Tensor, freqs: torch.Tensor, dim: int) -> torch.
     check(_lib.lib().ofx_timestep_embedding(_ptr(t), _ptr(f) if dim >= 2 else None, _ptr(out), int(t.shape[0]), dim, _stream()),
           "ofx_timestep_embedding")
     return out
+
+
+# --------------------------------------------------------------------------------------
+# sampler (guided_ldm_inpainting.py:28-137, guided_ldm.py:30-158)
+# --------------------------------------------------------------------------------------
+DDIM_COEF_FIELDS = ("cfg", "sqrt_at", "sqrt_1m_at", "sqrt_aprev", "dir_coef", "sigma_t", "g", "sa", "s1")
+
+
+def ddim_step(x: torch.Tensor, coef: Dict[str, float], eps_c: Optional[torch.Tensor] = None, eps_u: Optional[torch.Tensor] = None,
+              guidance: Optional[torch.Tensor] = None, gmap: Optional[torch.Tensor] = None, step_noise: Optional[torch.Tensor] = None,
+              init: Optional[torch.Tensor] = None, nmask: Optional[torch.Tensor] = None, blend_noise: Optional[torch.Tensor] = None,
+              out0: Optional[torch.Tensor] = None, out1: Optional[torch.Tensor] = None, pred_out: Optional[torch.Tensor] = None,
+              blend_only: bool = False) -> torch.Tensor:
+    """One guided DDIM step and the mask blend that opens the next one in one launch (`ofx_ddim_step`, whose header comment gives the
+    chain).  Every tensor is float32 on the device, [..., C] with C % 4 == 0 and the same leading shape, contiguous or a channel slice
+    of a wider contiguous tensor (channels 0..3 of the UNet's 12-wide NHWC input, say); gmap is a contiguous per-pixel map of the
+    leading shape.  coef: the fields of `ofx_ddim_coef` (DDIM_COEF_FIELDS); a field left out is 0.  blend_only: skip the DDIM part
+    (xp = x); eps_c is required otherwise.  out0 defaults to a new contiguous tensor; out0 / out1 may each be x itself.  -> out0."""
+    rows, Cn, ldx = _rows_view(x, "x")
+    lead = tuple(x.shape[:-1])
+    unknown = set(coef) - set(DDIM_COEF_FIELDS)
+    if unknown:
+        raise RuntimeError(f"coef has unknown fields {sorted(unknown)}")
+    if not blend_only and eps_c is None:
+        raise RuntimeError("eps_c is required unless blend_only")
+
+    def view(t, name):
+        if t is None:
+            return 0
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != lead + (Cn,):
+            raise RuntimeError(f"{name} must be a CUDA float32 tensor {lead + (Cn,)}")
+        return _rows_view(t, name)[2]
+
+    lde = view(eps_c, "eps_c")
+    if eps_u is not None and view(eps_u, "eps_u") != lde:
+        raise RuntimeError("eps_u must have the row stride of eps_c")
+    if gmap is not None:
+        gmap = _chk(gmap, "gmap", torch.float32)
+        if tuple(gmap.shape) != lead:
+            raise RuntimeError(f"gmap must be {lead}, got {tuple(gmap.shape)}")
+    if out0 is None:
+        out0 = torch.empty(lead + (Cn,), dtype=torch.float32, device=x.device)
+    k = _lib.DdimCoef(**{f: float(v) for f, v in coef.items()})
+    check(_lib.lib().ofx_ddim_step(_ptr(x), ldx, _ptr(eps_c), _ptr(eps_u), lde, _ptr(guidance), view(guidance, "guidance"), _ptr(gmap),
+                                   _ptr(step_noise), view(step_noise, "step_noise"), _ptr(init), view(init, "init"), _ptr(nmask),
+                                   view(nmask, "nmask"), _ptr(blend_noise), view(blend_noise, "blend_noise"), _ptr(out0),
+                                   view(out0, "out0"), _ptr(out1), view(out1, "out1"), _ptr(pred_out), view(pred_out, "pred_out"),
+                                   C.byref(k), 1 if blend_only else 0, rows, Cn, _stream()), "ofx_ddim_step")
+    return out0
 
 
 # --------------------------------------------------------------------------------------

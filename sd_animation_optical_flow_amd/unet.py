@@ -405,13 +405,20 @@ class UNetModel:
 
     @torch.no_grad()
     def forward_nhwc(self, x: torch.Tensor, timesteps: torch.Tensor, context: Optional[torch.Tensor] = None, control=None,
-                     only_mid_control: bool = False, reference_kv=()) -> Tuple[torch.Tensor, List[Tuple[torch.Tensor, torch.Tensor]]]:
-        """`forward` without the two edge permutes: x f32 [B,H,W,in_channels] on the device -> (eps [B,H,W,out_channels], kv_hists)."""
-        if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[3] != self.in_channels:
-            raise RuntimeError(f"x must be a CUDA float32 tensor with {self.in_channels} channels")
+                     only_mid_control: bool = False, reference_kv=(), *,
+                     padded: bool = False) -> Tuple[torch.Tensor, List[Tuple[torch.Tensor, torch.Tensor]]]:
+        """`forward` without the two edge permutes: x f32 [B,H,W,in_channels] on the device -> (eps [B,H,W,out_channels], kv_hists).
+        padded=True: x is the first convolution's own operand, [B,H,W,in_pad] contiguous with channels in_channels..in_pad-1 zero
+        (the caller's duty; they meet zero weights, but a NaN there would spread), and is read in place: no allocation and no copy
+        here, which is how `sampler.GuidedDDIMSampler.decode` keeps one input buffer for a whole loop.  x is not written to."""
+        cin = self.in_pad if padded else self.in_channels
+        if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[3] != cin:
+            raise RuntimeError(f"x must be a CUDA float32 tensor with {cin} channels")
+        if padded and not x.is_contiguous():
+            raise RuntimeError("padded=True takes a contiguous [B,H,W,in_pad] tensor")
         B, H, W, _ = x.shape
         ref_by_st, ctl = self._check_inputs(B, H, W, timesteps, context, control, reference_kv)
-        if self.in_pad != self.in_channels:
+        if not padded and self.in_pad != self.in_channels:
             xp = torch.zeros((B, H, W, self.in_pad), dtype=torch.float32, device=x.device)     # Cin padded to a multiple of 4
             xp[..., :self.in_channels] = x
             x = xp
