@@ -27,6 +27,7 @@
  *   ofx_groupnorm_cat, ofx_emb_linear, ofx_timestep_embedding
  *                               ldm/modules/diffusionmodules/openaimodel.py:220-226,257-277,530-534,757-793 ; util.py:154-174
  *   ofx_ddim_step               guided_ldm_inpainting.py:28-137,337-338 ; guided_ldm.py:82-89,123
+ *   ofx_conv3x3_silu            controlnet.py:164-180 (ControlNet.input_hint_block)
  *
  * Layout conventions: images and flow are HWC ("channels-last"); network activations are
  * NHWC fp32; a flow field is f32[H,W,2] = (dx, dy) exactly as `algo.calc` returns it
@@ -267,6 +268,21 @@ int ofx_emb_linear(const float* x, int ldx, const float* w, const float* bias, f
  * device (fractional timesteps are legal), freqs [half] fp32 on the device: the table the reference builds on the CPU and moves
  * (:165-167).  out dense [B][dim].  The product is one fp32 multiplication, sinf / cosf the accurate ones (arguments reach 1e3). */
 int ofx_timestep_embedding(const float* t, const float* freqs, float* out, int B, int dim, void* stream);
+
+/* ---------------------------------------------------------------- ControlNet (controlnet.py:65-322) */
+/* One layer of `input_hint_block` (controlnet.py:164-180): a 3x3 convolution, padding 1, stride 1 or 2, with bias and nn.SiLU in
+ * the epilogue:   y = sum_{ky,kx,c} x[b][oy*stride - 1 + ky][ox*stride - 1 + kx][c] * w[n][(ky*3 + kx)*Cin + c] + bias[n],
+ *   out[((b*Hout + oy)*Wout + ox)*ldo + n] = silu ? y * sigmoid(y) : y,      Hout = (H - 1)/stride + 1, Wout = (W - 1)/stride + 1
+ * x NHWC fp32 [B,H,W,Cin] with pixel rows ldx floats apart, taps outside the image read zeros; w is ofx_pack_conv_weight's operand
+ * with cin_pad = Cin, rows ldw >= 9*Cin floats apart (its Kpad); a 3-channel hint is padded to Cin = 4 with zero weights.  bias
+ * [Cout] or NULL.  Only columns [0, Cout) of an output row are written.  Exact fp32 on v_mfma_f32_16x16x4_f32 (output pixels on
+ * the M side, 16 channels on the N side, so Cout = 16 fills the instruction), the halo patch and the weights through LDS.  The
+ * sum runs in (channel chunk, ky, kx, channel) order on two levels: a fused multiply-add chain per chunk of 8 channels (4 when
+ * Cin % 8 != 0), the chunk sums added in order.  The sigmoid is the one of ofx_groupnorm's SiLU.  Checked before any launch: OFX_EINVAL for a NULL x / w / out, a stride other than 1 or 2, a non-positive
+ * size, Cin % 4 != 0, Cout % 16 != 0, ldx < Cin, ldo < Cout, ldw < 9*Cin, B*H*W >= 2^31 (slice the batch; addresses themselves
+ * are 64-bit); OFX_EALIGN for ldx, ldo or ldw % 4 != 0 or x, w, out not 16-byte aligned. */
+int ofx_conv3x3_silu(const float* x, int ldx, int Cin, const float* w, int ldw, const float* bias, float* out, int ldo, int Cout,
+                     int B, int H, int W, int stride, int silu, void* stream);
 
 /* ---------------------------------------------------------------- sampler (guided_ldm_inpainting.py:28-137, guided_ldm.py:30-158) */
 /* The scalars of one DDIM step, fp32 as the reference forms them: cfg = unconditional_guidance_scale, sqrt_at = sqrt(ddim_alphas

@@ -782,6 +782,35 @@ def upconv2x(x: torch.Tensor, w_folded: torch.Tensor, bias: Optional[torch.Tenso
     return out
 
 
+def conv3x3_silu(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], cout: int, stride: int = 1, silu: bool = True,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """silu(conv3x3(x, padding 1, stride 1 | 2) + bias) in one kernel (ofx_conv3x3_silu; a layer of ControlNet's hint stem):
+    x [B,H,W,C] NHWC fp32 on the device -- C >= Cin, the channels beyond Cin are skipped (a strided row) -- and w
+    `pack_conv_weight`'s [cout, Kpad] of a [cout, Cin', 3, 3] weight on the device, Cin = Cin' rounded up to a multiple of 4 (the
+    padding meets zero weights) = the one multiple of 4 whose Kpad this is (Kpad grows by 32, 9 Cin by 36).  silu=False: no activation.
+    -> [B,Hout,Wout,cout], Hout = (H - 1) // stride + 1; `out` [B,Hout,Wout,C' >= cout]: columns [0, cout) of it are written."""
+    x = _chk(x, "x", torch.float32)
+    w = _chk(w, "w", torch.float32)
+    if x.dim() != 4 or w.dim() != 2 or w.shape[0] != cout:
+        raise RuntimeError(f"conv3x3_silu: x [B,H,W,C] and w [{cout},Kpad] expected, got {tuple(x.shape)} and {tuple(w.shape)}")
+    B, H, W, ldx = x.shape
+    cin = int(w.shape[1]) // 9 // 4 * 4
+    if cin <= 0 or -(-9 * cin // 32) * 32 != w.shape[1] or ldx < cin:
+        raise RuntimeError(f"conv3x3_silu: w {tuple(w.shape)} is not a packed 3x3 weight over at most the {ldx} channels of x")
+    b = None if bias is None else _chk(bias, "bias", torch.float32)
+    if b is not None and tuple(b.shape) != (cout,):
+        raise RuntimeError(f"conv3x3_silu: bias must be [{cout}]")
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if out is None:
+        out = torch.empty((B, Ho, Wo, cout), dtype=torch.float32, device=x.device)
+    out = _chk(out, "out", torch.float32)
+    if out.dim() != 4 or tuple(out.shape[:3]) != (B, Ho, Wo) or out.shape[3] < cout:
+        raise RuntimeError(f"out must be [{B},{Ho},{Wo},>= {cout}], got {tuple(out.shape)}")
+    check(_lib.lib().ofx_conv3x3_silu(_ptr(x), int(ldx), cin, _ptr(w), int(w.shape[1]), _ptr(b), _ptr(out), int(out.shape[3]), int(cout),
+                                      B, H, W, int(stride), int(bool(silu)), _stream()), "ofx_conv3x3_silu")
+    return out
+
+
 def upsample2x_nearest(x: torch.Tensor) -> torch.Tensor:
     """F.interpolate(scale_factor=2.0, mode="nearest") of an NHWC fp32 tensor [B,H,W,C] -> [B,2H,2W,C] (C % 4 == 0)."""
     x = _chk(x, "x", torch.float32)

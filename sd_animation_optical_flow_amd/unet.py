@@ -42,6 +42,8 @@ OFX_UNET_TORCH_GLUE=1 in the environment (read once per process; the A/B baselin
 possible before `groupnorm_cat` / `emb_linear` / `timestep_embedding` existed -- `torch.cat` + `ops.groupnorm`, the emb term as a
 torch broadcast add, the timestep path through torch.nn.functional.
 
+`UNetTrunk` is the part of the model `controlnet.ControlNet` shares: weight loading, the timestep path, `resblock`, `_block`.
+
 No checkpoint ships with the reference tree: parity is pinned with seeded weights loaded into the reference's own module
 (tests/golden/make_golden_unet.py).
 """
@@ -215,39 +217,49 @@ def route_reference_kv(reference_kv, n_transformers: int) -> List[list]:
     return [[(f[j][0], f[j][1]) for f in frames] for j in range(n_transformers)]
 
 
-class UNetModel:
-    """`ldm.modules.diffusionmodules.openaimodel.UNetModel` with `ControlledUnetModel.forward` (inference) on a HIP device.
-    `precision`: the arithmetic of the convolutions and GEMMs, one of MODEL_PRECISIONS (module docstring); everything else is fp32,
-    unless `attention_precision="fp16"` hands the attention of all the transformers to the fp16 matrix-core kernel
-    (`SpatialTransformer(attention_precision=)`; the K/V a transformer records is unchanged by it).  That kernel exists for the head
-    sizes 40 / 64 / 80 / 128 / 160 -- all 16 transformers of SD v1.5.  In a configuration with another head size (the test
-    configuration u0 has a 192-wide middle head) that transformer keeps fp32 attention: a UserWarning names it at construction and
-    `attention_precision_of` maps every transformer to the mode it runs.  A SpatialTransformer built directly raises instead."""
+class UNetTrunk:
+    """What `UNetModel` and `controlnet.ControlNet` share: the checkpoint check and the weight loading (`_setup`), the timestep path
+    (`emb_projections`), `resblock` and `_block`.  A subclass names its module tree (`_layout`), its tensors (`_tensors`) and the
+    layers it runs (`_trunk_layers`); ControlNet's trunk is the `input` and `middle` halves of the same layout, key for key."""
+    _what = "UNet"
 
-    def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: dict = SD_V15_UNET, device="cuda", prefix: str = "model.diffusion_model.",
-                 precision: str = "fp32", attention_precision: str = "fp32"):
+    @staticmethod
+    def _layout(cfg):
+        return unet_layout(cfg)
+
+    @staticmethod
+    def _tensors(c):
+        return unet_tensors(c)
+
+    def _trunk_layers(self) -> List[tuple]:
+        return _layers(self.layout)
+
+    def _setup(self, state_dict: Dict[str, torch.Tensor], cfg: dict, device, prefix: str, precision: str,
+               attention_precision: str) -> Dict[str, torch.Tensor]:
+        """Everything `__init__` does; -> the checked fp32 CPU tensors by key (for what a subclass loads beyond `self.w`)."""
         self.precision = check_precision(precision)                # before the checkpoint is looked at or a device asked for
         self.attention_precision = ops.check_attention_precision(attention_precision, "attention_precision")
-        self.layout = unet_layout(cfg)
+        self.layout = self._layout(cfg)
         self.cfg = self.layout["cfg"]
         c = self.cfg
         mc = int(c["model_channels"])
         if mc % 32 or any((int(m) * mc) % 32 for m in c["channel_mult"]):
             raise ValueError("model_channels and every level's channels must be multiples of 32 (GroupNorm(32); the two channel "
                              "segments of a skip convolution)")
-        for l in _layers(self.layout):
+        layers = self._trunk_layers()
+        for l in layers:
             if l[0] == "res" and len(l) == 6 and l[2] == l[3]:
                 raise NotImplementedError(f"{l[1]}: an identity skip over a concatenation is not built")
         t32: Dict[str, torch.Tensor] = {}
-        for key, shape in unet_tensors(c):                         # the checkpoint is checked before the device is asked for
+        for key, shape in self._tensors(c):                        # the checkpoint is checked before the device is asked for
             if prefix + key not in state_dict:
-                raise KeyError(f"UNet checkpoint lacks {prefix}{key}")
+                raise KeyError(f"{self._what} checkpoint lacks {prefix}{key}")
             t = state_dict[prefix + key].detach().to(torch.float32).cpu()
             if tuple(t.shape) != tuple(shape):
                 raise ValueError(f"{prefix}{key}: shape {tuple(t.shape)} != {shape}")
             t32[key] = t
         if not torch.cuda.is_available():
-            raise RuntimeError("UNetModel needs a HIP device (no CPU fallback)")
+            raise RuntimeError(f"{type(self).__name__} needs a HIP device (no CPU fallback)")
         self.device = torch.device(device)
         self.in_channels, self.out_channels, self.model_channels = int(c["in_channels"]), int(c["out_channels"]), mc
         self.in_pad = (self.in_channels + 3) // 4 * 4
@@ -256,7 +268,7 @@ class UNetModel:
         self.st: Dict[str, SpatialTransformer] = {}
         emb_w, emb_b, off = [], [], 0
         self.emb_slice: Dict[str, Tuple[int, int]] = {}            # ResBlock name -> (first column, columns) of the emb projections
-        for l in _layers(self.layout):
+        for l in layers:
             kind, name = l[0], l[1]
             if kind == "st":
                 sub = {k[len(name) + 1:]: v for k, v in t32.items() if k.startswith(name + ".")}
@@ -270,12 +282,12 @@ class UNetModel:
                 self.emb_slice[name] = (off, l[3])
                 off += l[3]
         self.n_transformers = len(self.st)
-        self.st_order = [l for l in _layers(self.layout) if l[0] == "st"]
+        self.st_order = [l for l in layers if l[0] == "st"]
         self.attention_precision_of = {name: st.attention_precision for name, st in self.st.items()}
         kept = [name for name, ap in self.attention_precision_of.items() if ap != self.attention_precision]
         if kept:
             warnings.warn(f"attention_precision={self.attention_precision!r}: the fused kernel does not take the head size of {kept} "
-                          f"(fused: {FUSED_HEAD_SIZES}); their attention stays fp32 (UNetModel.attention_precision_of)", stacklevel=2)
+                          f"(fused: {FUSED_HEAD_SIZES}); their attention stays fp32 ({type(self).__name__}.attention_precision_of)", stacklevel=3)
         for key, t in t32.items():
             if any(key.startswith(n + ".") for n in self.st) or ".emb_layers." in key:
                 continue
@@ -290,6 +302,7 @@ class UNetModel:
         self.w["emb_layers.bias"] = torch.cat(emb_b).contiguous().to(self.device)
         self.w["freqs"] = ops.timestep_freqs(mc).to(self.device)
         self.torch_glue = _torch_glue()
+        return t32
 
     # ---- building blocks ------------------------------------------------------------------------------------------
     def _conv(self, name: str, x: torch.Tensor, k: int, stride: int = 1, addend: Optional[torch.Tensor] = None,
@@ -361,6 +374,20 @@ class UNetModel:
             else:
                 h = ops.upconv2x(h, self.w[f"{name}.conv.weight.folded"], self.w[f"{name}.conv.bias"])   # Upsample (:93-121)
         return h
+
+
+class UNetModel(UNetTrunk):
+    """`ldm.modules.diffusionmodules.openaimodel.UNetModel` with `ControlledUnetModel.forward` (inference) on a HIP device.
+    `precision`: the arithmetic of the convolutions and GEMMs, one of MODEL_PRECISIONS (module docstring); everything else is fp32,
+    unless `attention_precision="fp16"` hands the attention of all the transformers to the fp16 matrix-core kernel
+    (`SpatialTransformer(attention_precision=)`; the K/V a transformer records is unchanged by it).  That kernel exists for the head
+    sizes 40 / 64 / 80 / 128 / 160 -- all 16 transformers of SD v1.5.  In a configuration with another head size (the test
+    configuration u0 has a 192-wide middle head) that transformer keeps fp32 attention: a UserWarning names it at construction and
+    `attention_precision_of` maps every transformer to the mode it runs.  A SpatialTransformer built directly raises instead."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: dict = SD_V15_UNET, device="cuda", prefix: str = "model.diffusion_model.",
+                 precision: str = "fp32", attention_precision: str = "fp32"):
+        self._setup(state_dict, cfg, device, prefix, precision, attention_precision)
 
     def _check_inputs(self, B, H, W, timesteps, context, control, reference_kv):
         """Every check that needs no launch; -> (per-transformer reference K/V, control as NHWC views or None)."""
