@@ -41,6 +41,11 @@
 //              runs, conflict-free; LDK = DP + 8 halves = 4 * odd dwords, conflict-free for b128 reads as in the fp32 kernel.
 //              LDV >= 32 * DT, so tiles with d >= D read inside their own row (rows of O^T that are never stored).
 //   Two workgroups per CU (__launch_bounds__(256, 2)): one wave's softmax runs under the other's MFMAs.
+//
+// The two kernels share the raster (flash_raster) and nothing else on purpose: the bias / ragged mask, the online-softmax step and
+// the output epilogue stay written out in both.  Forceinline helpers for any of them change the compiled instruction stream, and the
+// softmax step as a helper moves register allocation in 12 of the 20 instantiations (flash_attn_kernel<40, 64, false>: 160 -> 176
+// registers, occupancy 3 -> 2).  The raster helper leaves all 20 instruction-identical.
 #include "ofx_internal.h"
 
 #include <cmath>
@@ -67,6 +72,19 @@ struct FlashArgs {
 
 constexpr float kLog2e = 1.4426950408889634f;
 
+// the workgroup's batch-head and tile of 128 queries (both kernels)
+__device__ __forceinline__ void flash_raster(const FlashArgs& a, int& bh, int& qt) {
+    if (a.xcd_grouped) {
+        // consecutive workgroup ids go round the 8 XCDs: give every XCD whole batch-heads so that their K / V stay in its L2
+        const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
+        bh = (slot / a.qtiles) * 8 + xcd;
+        qt = slot % a.qtiles;
+    } else {
+        bh = blockIdx.x / a.qtiles;
+        qt = blockIdx.x % a.qtiles;
+    }
+}
+
 // STRIDED = false: [BH, N, D] tensors, a batch-head is one contiguous run.  STRIDED = true: tokens are rows of ld floats with the
 // heads side by side in a row (what a fused q|k|v projection GEMM leaves); only the global addresses differ, the arithmetic and
 // its order are the same, so the two instantiations agree bit for bit.
@@ -87,15 +105,7 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const FlashArgs a) {
     const int c = lane & 31, h = lane >> 5;
 
     int bh, qt;
-    if (a.xcd_grouped) {
-        // consecutive workgroup ids go round the 8 XCDs: give every XCD whole batch-heads so that their K / V stay in its L2
-        const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-        bh = (slot / a.qtiles) * 8 + xcd;
-        qt = slot % a.qtiles;
-    } else {
-        bh = blockIdx.x / a.qtiles;
-        qt = blockIdx.x % a.qtiles;
-    }
+    flash_raster(a, bh, qt);
     const int qrow = qt * 128 + wave * 32 + c;
     const bool qok = qrow < a.Nq;
 
@@ -300,14 +310,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_f16_kernel(const FlashArgs 
     const int c = lane & 31, h = lane >> 5;
 
     int bh, qt;
-    if (a.xcd_grouped) {
-        const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-        bh = (slot / a.qtiles) * 8 + xcd;
-        qt = slot % a.qtiles;
-    } else {
-        bh = blockIdx.x / a.qtiles;
-        qt = blockIdx.x % a.qtiles;
-    }
+    flash_raster(a, bh, qt);
     const int qrow = qt * 128 + wave * 32 + c;
     const bool qok = qrow < a.Nq;
 
@@ -497,7 +500,29 @@ int launch_flash_f16(const FlashArgs& a, hipStream_t s) {
 
 }  // namespace
 
-bool ofx_attention_flash_ok(int D) { return D == 40 || D == 64 || D == 80 || D == 128 || D == 160; }
+// The fused head sizes and the keys per K / V tile of each: the one list behind ofx_attention_flash_ok and every dispatch
+#define OFX_FLASH_SIZES(X) X(40, 64) X(64, 32) X(80, 32) X(128, 32) X(160, 32)
+
+bool ofx_attention_flash_ok(int D) {
+#define X(d, bk) if (D == d) return true;
+    OFX_FLASH_SIZES(X)
+#undef X
+    return false;
+}
+
+// the launch of head size D from the list, for one kernel family and one addressing
+template <bool F16, bool STRIDED>
+static int flash_launch_d(const FlashArgs& a, int D, hipStream_t s) {
+    switch (D) {
+#define X(d, bk)                                                            \
+    case d:                                                                 \
+        if constexpr (F16) return launch_flash_f16<d, bk, STRIDED>(a, s);   \
+        else return launch_flash<d, bk, STRIDED>(a, s);
+        OFX_FLASH_SIZES(X)
+#undef X
+    }
+    return OFX_EINVAL;
+}
 
 static int flash_dispatch(FlashArgs& a, int D, float scale, bool strided, int precision, hipStream_t s) {
     if (precision != OFX_PREC_FP32 && precision != OFX_PREC_F16) return OFX_EINVAL;
@@ -508,45 +533,11 @@ static int flash_dispatch(FlashArgs& a, int D, float scale, bool strided, int pr
     if (precision == OFX_PREC_F16) {
         OfxProfScope prof(strided ? "attn_flash_bnhd_f16" : "attn_flash_f16", s);
         prof.flops(4.0 * a.BH * (double)a.Nq * a.Nk * D);
-        if (strided) {
-            switch (D) {
-                case 40: return launch_flash_f16<40, 64, true>(a, s);
-                case 64: return launch_flash_f16<64, 32, true>(a, s);
-                case 80: return launch_flash_f16<80, 32, true>(a, s);
-                case 128: return launch_flash_f16<128, 32, true>(a, s);
-                case 160: return launch_flash_f16<160, 32, true>(a, s);
-            }
-            return OFX_EINVAL;
-        }
-        switch (D) {
-            case 40: return launch_flash_f16<40, 64, false>(a, s);
-            case 64: return launch_flash_f16<64, 32, false>(a, s);
-            case 80: return launch_flash_f16<80, 32, false>(a, s);
-            case 128: return launch_flash_f16<128, 32, false>(a, s);
-            case 160: return launch_flash_f16<160, 32, false>(a, s);
-        }
-        return OFX_EINVAL;
+        return strided ? flash_launch_d<true, true>(a, D, s) : flash_launch_d<true, false>(a, D, s);
     }
     OfxProfScope prof(strided ? "attn_flash_bnhd" : "attn_flash", s);
     prof.flops(4.0 * a.BH * (double)a.Nq * a.Nk * D);
-    if (strided) {
-        switch (D) {
-            case 40: return launch_flash<40, 64, true>(a, s);
-            case 64: return launch_flash<64, 32, true>(a, s);
-            case 80: return launch_flash<80, 32, true>(a, s);
-            case 128: return launch_flash<128, 32, true>(a, s);
-            case 160: return launch_flash<160, 32, true>(a, s);
-        }
-        return OFX_EINVAL;
-    }
-    switch (D) {
-        case 40: return launch_flash<40, 64, false>(a, s);
-        case 64: return launch_flash<64, 32, false>(a, s);
-        case 80: return launch_flash<80, 32, false>(a, s);
-        case 128: return launch_flash<128, 32, false>(a, s);
-        case 160: return launch_flash<160, 32, false>(a, s);
-    }
-    return OFX_EINVAL;
+    return strided ? flash_launch_d<false, true>(a, D, s) : flash_launch_d<false, false>(a, D, s);
 }
 
 int ofx_attention_flash_launch(const float* q, const float* k, const float* v, const float* bias, long bias_bstride, float* out, int BH, int Nq,

@@ -94,6 +94,14 @@ int ofx_inorm_finalize_part(const float* part, float* mean, float* rstd, int B, 
 int ofx_inorm_stats_affine(const float* x, int ld, float* mean, float* rstd, float* scratch, int B, long HW, int C, float eps,
                            const float* gamma, const float* beta, hipStream_t stream);
 
+// sd_ops.hip: the GroupNorm of ofx_groupnorm and ofx_groupnorm_cat (unet.hip), which validate -- nothing is checked here.  Carves
+// `scratch` (ofx_groupnorm_scratch_bytes(B, C0 + C1)) into partial sums / scale / shift and launches partial -> finalize -> apply
+// under the three profiler scope names.  One segment: x1 = null, C1 = 0; no per-image term: e = null (one dense segment without e
+// runs the kernels' DENSE1 instantiation, whichever entry point asks)
+int ofx_groupnorm_launch(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, const float* e, int lde, const float* gamma,
+                         const float* beta, float* out, void* scratch, int B, long HW, int groups, float eps, int silu,
+                         const char* const scope[3], hipStream_t s);
+
 // attn_flash.hip: fused attention for the UNet's head sizes (no workspace).  precision: OFX_PREC_FP32 or OFX_PREC_F16 (the fp16
 // matrix-core kernel, ofx_attention_prec); anything else is OFX_EINVAL before any launch
 bool ofx_attention_flash_ok(int D);

@@ -12,6 +12,14 @@
 //                        workspace (1 GiB for the VAE's 16384-token mid block at 1024x1024: 288 GB of HBM make the
 //                        unfused form the simple and exact one).  The UNet's head sizes are routed to the fused kernel of
 //                        attn_flash.hip instead.
+//
+// The GroupNorm kernels also serve ofx_groupnorm_cat (unet.hip), whose input is the concatenation of two strided segments plus a
+// per-image term e[b][c]; ofx_groupnorm is the case of one dense segment and no e.  e enters in the finalize stage alone.  A slice
+// of n pixels whose channel sums are (S, Q) has, for x + e, the sums
+//     S' = S + n e,        Q' = Q + 2 e S + n e^2
+// in f64 (e is a float, so 2 e S and n e^2 carry one f64 rounding each), and since
+//     (x + e) * scale + shift = x * scale + (shift + e * scale)
+// the apply stage needs no e: its shift was folded in f64 and rounded once.
 #include "ofx_internal.h"
 
 #include <algorithm>
@@ -22,8 +30,16 @@ namespace {
 // slices of an image summed by separate workgroups: few images -> many slices, so that the statistics pass fills the chip
 static inline int gn_slices(int B) { return B >= 4 ? 64 : 256; }
 
-// per (image, slice) per-channel sums in f64 (same scheme as the instance-norm statistics of net_misc.hip)
-__global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict__ x, double* __restrict__ part, long HW, int C, int kSlices) {
+// DENSE1 in the three kernels below: one dense segment (x1 null, ld0 = C0 = C) and no e, what ofx_groupnorm always has.  Only the
+// addresses are simpler then (and the e terms are gone); the statements that add are the same ones, so the bits do not depend on it.
+// It exists for speed alone: on the general instantiation ofx_groupnorm takes about 1 us longer per call, 0.5 - 1.5 % at the VAE
+// decoder's maps (profiles/groupnorm_fold_ab.txt).
+
+// per (image, slice) per-channel sums in f64 (same scheme as the instance-norm statistics of net_misc.hip).  Two sources: float4
+// column c4 of the concatenation comes from x0 when 4 c4 < C0, else from x1 (C0 % 4 == 0: a float4 never straddles the seam)
+template <bool DENSE1>
+__global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict__ x0, int ld0, int C0, const float* __restrict__ x1, int ld1,
+                                                         double* __restrict__ part, long HW, int C, int kSlices) {
     const int cg = C / 4;
     const int b = blockIdx.y, sl = blockIdx.x;
     const long per = (HW + kSlices - 1) / kSlices;
@@ -36,9 +52,11 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
         const int tc = threadIdx.x % ncg, tr = threadIdx.x / ncg;
         double s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
         if (tr < rws) {
-            const float* base = x + ((long)b * HW) * C + (c0 + tc) * 4;
+            const int ch = (c0 + tc) * 4;
+            const long ld = DENSE1 ? C : ch < C0 ? ld0 : ld1;
+            const float* base = (DENSE1 || ch < C0 ? x0 + ch : x1 + (ch - C0)) + ((long)b * HW) * ld;
             for (long i = beg + tr; i < end; i += rws) {
-                const float4 v = *reinterpret_cast<const float4*>(base + i * C);
+                const float4 v = *reinterpret_cast<const float4*>(base + i * ld);
                 s[0] += v.x; s[1] += v.y; s[2] += v.z; s[3] += v.w;
                 q[0] += (double)v.x * v.x; q[1] += (double)v.y * v.y; q[2] += (double)v.z * v.z; q[3] += (double)v.w * v.w;
             }
@@ -67,15 +85,21 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
 
 // one workgroup per image: group statistics -> per-channel scale / shift (y = x * scale + shift).  The 256 threads are
 // dealt to the groups (256 / groups threads each, every one summing its share of the slices in a fixed order, then one
-// thread per group adding the shares in index order: deterministic).
-__global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restrict__ part, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, float* __restrict__ scale,
-                                                          float* __restrict__ shift, long HW, int C, int groups, float eps, int kSlices) {
+// thread per group adding the shares in index order: deterministic).  With e, every (slice, channel) pair of sums is moved to
+// the sums of x + e before it is added (header), and the shift takes e * scale; the thread layout and the order of the
+// additions are the same with and without it.
+template <bool DENSE1>
+__global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restrict__ part, const float* __restrict__ e, int lde,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          float* __restrict__ scale, float* __restrict__ shift, long HW, int C, int groups,
+                                                          float eps, int kSlices) {
     __shared__ double rs[256], rq[256];
     __shared__ double gmu[256], grs[256];
     const int b = blockIdx.x;
     const int cpg = C / groups;
     const int tpg = groups >= 256 ? 1 : 256 / groups;          // threads per group
+    const long per = (HW + kSlices - 1) / kSlices;
+    const float* eb = !DENSE1 && e ? e + (long)b * lde : nullptr;
     for (int g0 = 0; g0 < groups; g0 += 256 / tpg) {
         const int gl = threadIdx.x / tpg, sub = threadIdx.x - gl * tpg;
         const int g = g0 + gl;
@@ -83,9 +107,19 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restri
         if (g < groups)
             for (int sl = sub; sl < kSlices; sl += tpg) {
                 const double* o = part + (((long)b * kSlices + sl) * C + g * cpg) * 2;
-                for (int c = 0; c < cpg; ++c) {
-                    s += o[2 * c];
-                    q += o[2 * c + 1];
+                if (eb) {
+                    const long beg = sl * per, end = beg + per < HW ? beg + per : HW;
+                    const double n = end > beg ? (double)(end - beg) : 0.0;         // pixels of this slice
+                    for (int c = 0; c < cpg; ++c) {
+                        const double ec = (double)eb[g * cpg + c];
+                        s += o[2 * c] + n * ec;
+                        q += o[2 * c + 1] + 2.0 * ec * o[2 * c] + n * ec * ec;
+                    }
+                } else {
+                    for (int c = 0; c < cpg; ++c) {
+                        s += o[2 * c];
+                        q += o[2 * c + 1];
+                    }
                 }
             }
         rs[threadIdx.x] = s;
@@ -110,21 +144,28 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restri
             if (g2 >= 0 && g2 < 256 / tpg) {
                 const double r = grs[g2] * (double)(gamma ? gamma[c] : 1.f);
                 scale[(long)b * C + c] = (float)r;
-                shift[(long)b * C + c] = (float)((double)(beta ? beta[c] : 0.f) - gmu[g2] * r);
+                if (eb)
+                    shift[(long)b * C + c] = (float)((double)(beta ? beta[c] : 0.f) - (gmu[g2] - (double)eb[c]) * r);
+                else
+                    shift[(long)b * C + c] = (float)((double)(beta ? beta[c] : 0.f) - gmu[g2] * r);
             }
         }
         __syncthreads();
     }
 }
 
-__global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__ x, const float* __restrict__ scale,
-                                                       const float* __restrict__ shift, float* __restrict__ out, long HW, int C,
-                                                       long total4, int silu) {
+// reads the two segments, writes the dense concatenation; out may be x0 (one dense segment, in place), so it is not __restrict__
+template <bool DENSE1>
+__global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__ x0, int ld0, int C0, const float* __restrict__ x1, int ld1,
+                                                       const float* __restrict__ scale, const float* __restrict__ shift, float* out, long HW,
+                                                       int C, long total4, int silu) {
     const int cg = C / 4;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long)gridDim.x * blockDim.x) {
         const int c = (int)(i % cg) * 4;
-        const long b = (i / cg) / HW;
-        const float4 v = reinterpret_cast<const float4*>(x)[i];
+        const long row = i / cg;
+        const long b = row / HW;
+        const float* src = DENSE1 ? x0 + 4 * i : c < C0 ? x0 + row * ld0 + c : x1 + row * ld1 + (c - C0);
+        const float4 v = *reinterpret_cast<const float4*>(src);
         const float4 sc = *reinterpret_cast<const float4*>(scale + b * C + c);
         const float4 sh = *reinterpret_cast<const float4*>(shift + b * C + c);
         float4 y = make_float4(fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w));
@@ -220,6 +261,41 @@ inline long round_up(long v, long m) { return (v + m - 1) / m * m; }
 
 }  // namespace
 
+template <bool DENSE1>
+static int groupnorm_launch(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, const float* e, int lde, const float* gamma,
+                            const float* beta, float* out, void* scratch, int B, long HW, int groups, float eps, int silu,
+                            const char* const scope[3], hipStream_t s) {
+    const int C = C0 + C1;
+    const int kSlices = gn_slices(B);
+    double* part = reinterpret_cast<double*>(scratch);
+    float* scale = reinterpret_cast<float*>(part + (size_t)B * kSlices * C * 2);
+    float* shift = scale + (size_t)B * C;
+    {
+        OfxProfScope prof(scope[0], s);
+        hipLaunchKernelGGL(gn_partial_kernel<DENSE1>, dim3(kSlices, B), dim3(256), 0, s, x0, ld0, C0, x1, ld1, part, HW, C, kSlices);
+    }
+    {
+        OfxProfScope prof(scope[1], s);
+        hipLaunchKernelGGL(gn_finalize_kernel<DENSE1>, dim3(B), dim3(256), 0, s, part, e, lde, gamma, beta, scale, shift, HW, C, groups, eps,
+                           kSlices);
+    }
+    int st = ofx_launch_status();
+    if (st) return st;
+    const long total4 = (long)B * HW * (C / 4);
+    OfxProfScope prof(scope[2], s);
+    hipLaunchKernelGGL(gn_apply_kernel<DENSE1>, dim3((unsigned)std::min<long>((total4 + 255) / 256, 65536)), dim3(256), 0, s, x0, ld0, C0, x1,
+                       ld1, scale, shift, out, HW, C, total4, silu);
+    return ofx_launch_status();
+}
+
+int ofx_groupnorm_launch(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, const float* e, int lde, const float* gamma,
+                         const float* beta, float* out, void* scratch, int B, long HW, int groups, float eps, int silu,
+                         const char* const scope[3], hipStream_t s) {
+    const bool dense1 = !x1 && !e && ld0 == C0;
+    return (dense1 ? groupnorm_launch<true> : groupnorm_launch<false>)(x0, ld0, C0, x1, ld1, C1, e, lde, gamma, beta, out, scratch, B, HW, groups,
+                                                                        eps, silu, scope, s);
+}
+
 extern "C" {
 
 size_t ofx_groupnorm_scratch_bytes(int B, int C) { return (size_t)B * gn_slices(B) * C * 2 * sizeof(double) + (size_t)B * C * 2 * sizeof(float); }
@@ -229,23 +305,8 @@ int ofx_groupnorm(const float* x, const float* gamma, const float* beta, float* 
     OFX_REQUIRE(x && out && scratch && B > 0 && B <= 65535 && HW > 0 && C > 0 && groups > 0 && C % groups == 0, OFX_EINVAL);
     OFX_REQUIRE(C % 4 == 0 && ofx_aligned16(x) && ofx_aligned16(out) && ofx_aligned16(scratch), OFX_EALIGN);
     OFX_REQUIRE(scratch_bytes >= ofx_groupnorm_scratch_bytes(B, C), OFX_ENOMEM);
-    hipStream_t s = (hipStream_t)stream;
-    const int kSlices = gn_slices(B);
-    double* part = reinterpret_cast<double*>(scratch);
-    float* scale = reinterpret_cast<float*>(part + (size_t)B * kSlices * C * 2);
-    float* shift = scale + (size_t)B * C;
-    {
-        OfxProfScope prof("groupnorm_stats", s);
-        hipLaunchKernelGGL(gn_partial_kernel, dim3(kSlices, B), dim3(256), 0, s, x, part, HW, C, kSlices);
-        hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, s, part, gamma, beta, scale, shift, HW, C, groups, eps, kSlices);
-    }
-    int st = ofx_launch_status();
-    if (st) return st;
-    const long total4 = (long)B * HW * (C / 4);
-    OfxProfScope prof("groupnorm_apply", s);
-    hipLaunchKernelGGL(gn_apply_kernel, dim3((unsigned)std::min<long>((total4 + 255) / 256, 65536)), dim3(256), 0, s, x, scale, shift, out, HW,
-                       C, total4, silu);
-    return ofx_launch_status();
+    static const char* const scope[3] = {"groupnorm_stats", "groupnorm_stats", "groupnorm_apply"};
+    return ofx_groupnorm_launch(x, C, C, nullptr, 0, 0, nullptr, 0, gamma, beta, out, scratch, B, HW, groups, eps, silu, scope, (hipStream_t)stream);
 }
 
 int ofx_softmax_rows(float* x, long rows, long ld, int n, float scale, const float* bias, long ld_bias, long bias_rows, void* stream) {
@@ -265,12 +326,15 @@ size_t ofx_attention_workspace_bytes(int BH, int Nq, int Nk, int D) {
     return (size_t)BH * ((size_t)Nk * kp + (size_t)Nq * lds + (size_t)D * vp) * sizeof(float) + 1024;
 }
 
-int ofx_attention_f32(const float* q, const float* k, const float* v, const float* bias, long bias_bstride, float* out, int BH, int Nq, int Nk,
-                      int D, float scale, void* workspace, size_t workspace_bytes, void* stream) {
+// The checks and the routing of both entry points.  OFX_PREC_F16 exists for the fused head sizes alone (they are multiples of 4), and
+// says so before the alignment is looked at.
+static int attention_checked(const float* q, const float* k, const float* v, const float* bias, long bias_bstride, float* out, int BH, int Nq,
+                             int Nk, int D, float scale, int precision, void* workspace, size_t workspace_bytes, void* stream) {
     OFX_REQUIRE(q && k && v && out && BH > 0 && Nq > 0 && Nk > 0 && D > 0, OFX_EINVAL);
+    OFX_REQUIRE(precision == OFX_PREC_FP32 || ofx_attention_flash_ok(D), OFX_EINVAL);            // there is no unfused fp16 path
     OFX_REQUIRE(D % 4 == 0 && ofx_aligned16(q) && ofx_aligned16(k) && ofx_aligned16(v) && ofx_aligned16(out), OFX_EALIGN);
     if (ofx_attention_flash_ok(D))
-        return ofx_attention_flash_launch(q, k, v, bias, bias_bstride, out, BH, Nq, Nk, D, scale, OFX_PREC_FP32, (hipStream_t)stream);
+        return ofx_attention_flash_launch(q, k, v, bias, bias_bstride, out, BH, Nq, Nk, D, scale, precision, (hipStream_t)stream);
     OFX_REQUIRE(workspace && ofx_aligned16(workspace), OFX_EALIGN);
     OFX_REQUIRE(workspace_bytes >= ofx_attention_workspace_bytes(BH, Nq, Nk, D), OFX_ENOMEM);
     hipStream_t s = (hipStream_t)stream;
@@ -316,14 +380,15 @@ int ofx_attention_f32(const float* q, const float* k, const float* v, const floa
     return ofx_launch_status();
 }
 
+int ofx_attention_f32(const float* q, const float* k, const float* v, const float* bias, long bias_bstride, float* out, int BH, int Nq, int Nk,
+                      int D, float scale, void* workspace, size_t workspace_bytes, void* stream) {
+    return attention_checked(q, k, v, bias, bias_bstride, out, BH, Nq, Nk, D, scale, OFX_PREC_FP32, workspace, workspace_bytes, stream);
+}
+
 int ofx_attention_prec(const float* q, const float* k, const float* v, const float* bias, long bias_bstride, float* out, int BH, int Nq, int Nk,
                        int D, float scale, int precision, void* workspace, size_t workspace_bytes, void* stream) {
-    if (precision == OFX_PREC_FP32) return ofx_attention_f32(q, k, v, bias, bias_bstride, out, BH, Nq, Nk, D, scale, workspace, workspace_bytes, stream);
-    OFX_REQUIRE(precision == OFX_PREC_F16, OFX_EINVAL);
-    OFX_REQUIRE(q && k && v && out && BH > 0 && Nq > 0 && Nk > 0 && D > 0, OFX_EINVAL);
-    OFX_REQUIRE(ofx_attention_flash_ok(D), OFX_EINVAL);            // there is no unfused fp16 path
-    OFX_REQUIRE(ofx_aligned16(q) && ofx_aligned16(k) && ofx_aligned16(v) && ofx_aligned16(out), OFX_EALIGN);
-    return ofx_attention_flash_launch(q, k, v, bias, bias_bstride, out, BH, Nq, Nk, D, scale, OFX_PREC_F16, (hipStream_t)stream);
+    OFX_REQUIRE(precision == OFX_PREC_FP32 || precision == OFX_PREC_F16, OFX_EINVAL);
+    return attention_checked(q, k, v, bias, bias_bstride, out, BH, Nq, Nk, D, scale, precision, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -112,30 +112,28 @@ int ofx_geglu(const float* a, int lda, float* out, int ldo, int rows, int inner,
     return ofx_launch_status();
 }
 
-int ofx_attention_bnhd_f32(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* bias, long bias_bstride,
-                           float* out, int ldo, int B, int H, int Nq, int Nk, int D, float scale, void* stream) {
+// the checks of both entry points; precision is OFX_PREC_FP32 or OFX_PREC_F16 here
+static int attention_bnhd_checked(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* bias, long bias_bstride,
+                                  float* out, int ldo, int B, int H, int Nq, int Nk, int D, float scale, int precision, void* stream) {
     OFX_REQUIRE(q && k && v && out && B > 0 && H > 0 && Nq > 0 && Nk > 0 && ofx_attention_flash_ok(D), OFX_EINVAL);
     OFX_REQUIRE((long)B * H <= 0x7fffffffL, OFX_EINVAL);
     const long hd = (long)H * D;
     OFX_REQUIRE(ldq >= hd && ldk >= hd && ldv >= hd && ldo >= hd, OFX_EINVAL);
     OFX_REQUIRE(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && ofx_aligned16(q) && ofx_aligned16(k) && ofx_aligned16(v) &&
                     ofx_aligned16(out) && (uintptr_t)bias % 4 == 0, OFX_EALIGN);
-    return ofx_attention_flash_bnhd_launch(q, ldq, k, ldk, v, ldv, bias, bias_bstride, out, ldo, B, H, Nq, Nk, D, scale, OFX_PREC_FP32,
+    return ofx_attention_flash_bnhd_launch(q, ldq, k, ldk, v, ldv, bias, bias_bstride, out, ldo, B, H, Nq, Nk, D, scale, precision,
                                            (hipStream_t)stream);
+}
+
+int ofx_attention_bnhd_f32(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* bias, long bias_bstride,
+                           float* out, int ldo, int B, int H, int Nq, int Nk, int D, float scale, void* stream) {
+    return attention_bnhd_checked(q, ldq, k, ldk, v, ldv, bias, bias_bstride, out, ldo, B, H, Nq, Nk, D, scale, OFX_PREC_FP32, stream);
 }
 
 int ofx_attention_bnhd_prec(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* bias, long bias_bstride,
                             float* out, int ldo, int B, int H, int Nq, int Nk, int D, float scale, int precision, void* stream) {
-    if (precision == OFX_PREC_FP32) return ofx_attention_bnhd_f32(q, ldq, k, ldk, v, ldv, bias, bias_bstride, out, ldo, B, H, Nq, Nk, D, scale, stream);
-    OFX_REQUIRE(precision == OFX_PREC_F16, OFX_EINVAL);
-    OFX_REQUIRE(q && k && v && out && B > 0 && H > 0 && Nq > 0 && Nk > 0 && ofx_attention_flash_ok(D), OFX_EINVAL);
-    OFX_REQUIRE((long)B * H <= 0x7fffffffL, OFX_EINVAL);
-    const long hd = (long)H * D;
-    OFX_REQUIRE(ldq >= hd && ldk >= hd && ldv >= hd && ldo >= hd, OFX_EINVAL);
-    OFX_REQUIRE(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && ofx_aligned16(q) && ofx_aligned16(k) && ofx_aligned16(v) &&
-                    ofx_aligned16(out) && (uintptr_t)bias % 4 == 0, OFX_EALIGN);
-    return ofx_attention_flash_bnhd_launch(q, ldq, k, ldk, v, ldv, bias, bias_bstride, out, ldo, B, H, Nq, Nk, D, scale, OFX_PREC_F16,
-                                           (hipStream_t)stream);
+    OFX_REQUIRE(precision == OFX_PREC_FP32 || precision == OFX_PREC_F16, OFX_EINVAL);
+    return attention_bnhd_checked(q, ldq, k, ldk, v, ldv, bias, bias_bstride, out, ldo, B, H, Nq, Nk, D, scale, precision, stream);
 }
 
 }  // extern "C"

@@ -6,160 +6,14 @@
 //   ofx_emb_linear           `time_embed` (:530-534) and the `emb_layers` of every ResBlock (:220-226): SiLU + Linear on B rows
 //   ofx_timestep_embedding   ldm/modules/diffusionmodules/util.py:154-174
 //
-// ofx_groupnorm_cat keeps the three stages of ofx_groupnorm (sd_ops.hip) and its summation order, statement by statement: with one
-// dense segment and no e the two give the same bits.  The per-image term e enters in the finalize stage alone.  A slice of n pixels
-// whose channel sums are (S, Q) has, for x + e, the sums
-//     S' = S + n e,        Q' = Q + 2 e S + n e^2
-// in f64 (e is a float, so 2 e S and n e^2 carry one f64 rounding each), and since
-//     (x + e) * scale + shift = x * scale + (shift + e * scale)
-// the apply stage is the one of ofx_groupnorm with a shift that was folded in f64 and rounded once.
+// ofx_groupnorm_cat validates here and runs the GroupNorm kernels of sd_ops.hip (ofx_groupnorm_launch), the ones ofx_groupnorm runs:
+// with one dense segment and no e the two entry points launch the same kernels on the same arguments.
 #include "ofx_internal.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
-
-// the slicing rule of ofx_groupnorm (sd_ops.hip: gn_slices)
-static inline int gnc_slices(int B) { return B >= 4 ? 64 : 256; }
-
-// gn_partial_kernel of sd_ops.hip with two sources: float4 column c4 of the concatenation comes from x0 when 4 c4 < C0, else from x1
-// (C0 % 4 == 0: a float4 never straddles the seam)
-__global__ __launch_bounds__(256) void gnc_partial_kernel(const float* __restrict__ x0, int ld0, int C0, const float* __restrict__ x1, int ld1,
-                                                          double* __restrict__ part, long HW, int C, int kSlices) {
-    const int cg = C / 4;
-    const int b = blockIdx.y, sl = blockIdx.x;
-    const long per = (HW + kSlices - 1) / kSlices;
-    const long beg = sl * per, end = beg + per < HW ? beg + per : HW;
-    __shared__ double red[256 * 8];
-    // channel groups beyond 256 threads (C > 1024) are walked in passes
-    for (int c0 = 0; c0 < cg; c0 += 256) {
-        const int ncg = min(256, cg - c0);
-        const int rws = 256 / ncg;
-        const int tc = threadIdx.x % ncg, tr = threadIdx.x / ncg;
-        double s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
-        if (tr < rws) {
-            const int ch = (c0 + tc) * 4;
-            const long ld = ch < C0 ? ld0 : ld1;
-            const float* base = (ch < C0 ? x0 + ch : x1 + (ch - C0)) + ((long)b * HW) * ld;
-            for (long i = beg + tr; i < end; i += rws) {
-                const float4 v = *reinterpret_cast<const float4*>(base + i * ld);
-                s[0] += v.x; s[1] += v.y; s[2] += v.z; s[3] += v.w;
-                q[0] += (double)v.x * v.x; q[1] += (double)v.y * v.y; q[2] += (double)v.z * v.z; q[3] += (double)v.w * v.w;
-            }
-        }
-        for (int k = 0; k < 4; ++k) {
-            red[threadIdx.x * 8 + k] = s[k];
-            red[threadIdx.x * 8 + 4 + k] = q[k];
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < ncg) {
-            double ts[4] = {0, 0, 0, 0}, tq[4] = {0, 0, 0, 0};
-            for (int r = 0; r < rws; ++r)
-                for (int k = 0; k < 4; ++k) {
-                    ts[k] += red[(r * ncg + threadIdx.x) * 8 + k];
-                    tq[k] += red[(r * ncg + threadIdx.x) * 8 + 4 + k];
-                }
-            double* o = part + (((long)b * kSlices + sl) * C + (c0 + threadIdx.x) * 4) * 2;
-            for (int k = 0; k < 4; ++k) {
-                o[k * 2] = ts[k];
-                o[k * 2 + 1] = tq[k];
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// gn_finalize_kernel of sd_ops.hip; with e, every (slice, channel) pair of sums is moved to the sums of x + e before it is added
-// (header), and the shift takes e * scale.  The thread layout and the order of the additions are unchanged.
-__global__ __launch_bounds__(256) void gnc_finalize_kernel(const double* __restrict__ part, const float* __restrict__ e, int lde,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           float* __restrict__ scale, float* __restrict__ shift, long HW, int C, int groups,
-                                                           float eps, int kSlices) {
-    __shared__ double rs[256], rq[256];
-    __shared__ double gmu[256], grs[256];
-    const int b = blockIdx.x;
-    const int cpg = C / groups;
-    const int tpg = groups >= 256 ? 1 : 256 / groups;          // threads per group
-    const long per = (HW + kSlices - 1) / kSlices;
-    const float* eb = e ? e + (long)b * lde : nullptr;
-    for (int g0 = 0; g0 < groups; g0 += 256 / tpg) {
-        const int gl = threadIdx.x / tpg, sub = threadIdx.x - gl * tpg;
-        const int g = g0 + gl;
-        double s = 0, q = 0;
-        if (g < groups)
-            for (int sl = sub; sl < kSlices; sl += tpg) {
-                const double* o = part + (((long)b * kSlices + sl) * C + g * cpg) * 2;
-                if (eb) {
-                    const long beg = sl * per, end = beg + per < HW ? beg + per : HW;
-                    const double n = end > beg ? (double)(end - beg) : 0.0;         // pixels of this slice
-                    for (int c = 0; c < cpg; ++c) {
-                        const double ec = (double)eb[g * cpg + c];
-                        s += o[2 * c] + n * ec;
-                        q += o[2 * c + 1] + 2.0 * ec * o[2 * c] + n * ec * ec;
-                    }
-                } else {
-                    for (int c = 0; c < cpg; ++c) {
-                        s += o[2 * c];
-                        q += o[2 * c + 1];
-                    }
-                }
-            }
-        rs[threadIdx.x] = s;
-        rq[threadIdx.x] = q;
-        __syncthreads();
-        if (sub == 0 && g < groups) {
-            s = 0; q = 0;
-            for (int k = 0; k < tpg; ++k) {
-                s += rs[threadIdx.x + k];
-                q += rq[threadIdx.x + k];
-            }
-            const double n = (double)HW * cpg;
-            const double mu = s / n;
-            double var = q / n - mu * mu;
-            if (var < 0) var = 0;
-            gmu[gl] = mu;
-            grs[gl] = 1.0 / sqrt(var + (double)eps);
-        }
-        __syncthreads();
-        for (int c = threadIdx.x; c < C; c += 256) {
-            const int g2 = c / cpg - g0;
-            if (g2 >= 0 && g2 < 256 / tpg) {
-                const double r = grs[g2] * (double)(gamma ? gamma[c] : 1.f);
-                scale[(long)b * C + c] = (float)r;
-                if (eb)
-                    shift[(long)b * C + c] = (float)((double)(beta ? beta[c] : 0.f) - (gmu[g2] - (double)eb[c]) * r);
-                else
-                    shift[(long)b * C + c] = (float)((double)(beta ? beta[c] : 0.f) - gmu[g2] * r);
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// gn_apply_kernel of sd_ops.hip reading the two segments, writing the dense concatenation
-__global__ __launch_bounds__(256) void gnc_apply_kernel(const float* __restrict__ x0, int ld0, int C0, const float* __restrict__ x1, int ld1,
-                                                        const float* __restrict__ scale, const float* __restrict__ shift, float* out, long HW,
-                                                        int C, long total4, int silu) {
-    const int cg = C / 4;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % cg) * 4;
-        const long row = i / cg;
-        const long b = row / HW;
-        const float* src = c < C0 ? x0 + row * ld0 + c : x1 + row * ld1 + (c - C0);
-        const float4 v = *reinterpret_cast<const float4*>(src);
-        const float4 sc = *reinterpret_cast<const float4*>(scale + b * C + c);
-        const float4 sh = *reinterpret_cast<const float4*>(shift + b * C + c);
-        float4 y = make_float4(fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w));
-        if (silu) {
-            y.x = y.x / (1.0f + expf(-y.x));
-            y.y = y.y / (1.0f + expf(-y.y));
-            y.z = y.z / (1.0f + expf(-y.z));
-            y.w = y.w / (1.0f + expf(-y.w));
-        }
-        reinterpret_cast<float4*>(out)[i] = y;
-    }
-}
 
 // ---- ofx_emb_linear ------------------------------------------------------------------------------------------------------------
 constexpr int EL_ROWS = 16;         // rows (B) at most
@@ -257,7 +111,7 @@ extern "C" {
 
 size_t ofx_groupnorm_cat_scratch_bytes(int B, int C) {
     if (B <= 0 || C <= 0) return 0;
-    return (size_t)B * gnc_slices(B) * C * 2 * sizeof(double) + (size_t)B * C * 2 * sizeof(float);
+    return ofx_groupnorm_scratch_bytes(B, C);
 }
 
 int ofx_groupnorm_cat(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, const float* e, int lde, const float* gamma,
@@ -276,26 +130,8 @@ int ofx_groupnorm_cat(const float* x0, int ld0, int C0, const float* x1, int ld1
     const bool in_place = out == x0 && C1 == 0 && ld0 == C0;
     OFX_REQUIRE(in_place || !overlaps(out, rows * C, x0, (rows - 1) * ld0 + C0), OFX_EINVAL);
     OFX_REQUIRE(!x1 || !overlaps(out, rows * C, x1, (rows - 1) * ld1 + C1), OFX_EINVAL);
-    hipStream_t s = (hipStream_t)stream;
-    const int kSlices = gnc_slices(B);
-    double* part = reinterpret_cast<double*>(scratch);
-    float* scale = reinterpret_cast<float*>(part + (size_t)B * kSlices * C * 2);
-    float* shift = scale + (size_t)B * C;
-    {
-        OfxProfScope prof("groupnorm_cat_partial", s);
-        hipLaunchKernelGGL(gnc_partial_kernel, dim3(kSlices, B), dim3(256), 0, s, x0, ld0, C0, x1, ld1, part, HW, C, kSlices);
-    }
-    {
-        OfxProfScope prof("groupnorm_cat_finalize", s);
-        hipLaunchKernelGGL(gnc_finalize_kernel, dim3(B), dim3(256), 0, s, part, e, lde, gamma, beta, scale, shift, HW, C, groups, eps, kSlices);
-    }
-    int st = ofx_launch_status();
-    if (st) return st;
-    const long total4 = (long)B * HW * (C / 4);
-    OfxProfScope prof("groupnorm_cat_apply", s);
-    hipLaunchKernelGGL(gnc_apply_kernel, dim3((unsigned)std::min<long>((total4 + 255) / 256, 65536)), dim3(256), 0, s, x0, ld0, C0, x1, ld1, scale,
-                       shift, out, HW, C, total4, silu);
-    return ofx_launch_status();
+    static const char* const scope[3] = {"groupnorm_cat_partial", "groupnorm_cat_finalize", "groupnorm_cat_apply"};
+    return ofx_groupnorm_launch(x0, ld0, C0, x1, ld1, C1, e, lde, gamma, beta, out, scratch, B, HW, groups, eps, silu, scope, (hipStream_t)stream);
 }
 
 int ofx_emb_linear(const float* x, int ldx, const float* w, const float* bias, float* out, int ldo, int B, int K, int N, int silu_in,
