@@ -28,6 +28,8 @@
  *                               ldm/modules/diffusionmodules/openaimodel.py:220-226,257-277,530-534,757-793 ; util.py:154-174
  *   ofx_ddim_step               guided_ldm_inpainting.py:28-137,337-338 ; guided_ldm.py:82-89,123
  *   ofx_conv3x3_silu            controlnet.py:164-180 (ControlNet.input_hint_block)
+ *   ofx_clip_embed, ofx_quick_gelu
+ *                               hack.py:32-70 (_hacked_clip_forward) ; ldm/modules/encoders/modules.py (FrozenCLIPEmbedder)
  *
  * Layout conventions: images and flow are HWC ("channels-last"); network activations are
  * NHWC fp32; a flow field is f32[H,W,2] = (dx, dy) exactly as `algo.calc` returns it
@@ -283,6 +285,26 @@ int ofx_timestep_embedding(const float* t, const float* freqs, float* out, int B
  * are 64-bit); OFX_EALIGN for ldx, ldo or ldw % 4 != 0 or x, w, out not 16-byte aligned. */
 int ofx_conv3x3_silu(const float* x, int ldx, int Cin, const float* w, int ldw, const float* bias, float* out, int ldo, int Cout,
                      int B, int H, int W, int stride, int silu, void* stream);
+
+/* ---------------------------------------------------------------- CLIP text encoder (hack.py:32-70, FrozenCLIPEmbedder) */
+/* CLIPTextEmbeddings.forward, the entry of the text transformer `_hacked_clip_forward` feeds its 77-token chunks to (hack.py:42-47,
+ * :66-67):   out[r][c] = tok[ids[r]][c] + pos[r % T][c],   r < rows, c < C     (one fp32 addition, so bit-identical to torch's)
+ * ids [rows] int32 on the device (the reference feeds torch.IntTensor, hack.py:64), rows = sequences * T in sequence-major order;
+ * tok [vocab][C] and pos [>= T][C], the checkpoint's own row-major token_embedding / position_embedding tensors, not packed; out
+ * rows ldo >= C floats apart, columns C..ldo-1 are not touched.  An id outside [0, vocab) reads nothing: its output row is all
+ * quiet NaN and every other row is unaffected (no clamp).  OFX_EINVAL for a NULL pointer, rows < 0, T, C or vocab <= 0, ldo < C;
+ * OFX_EALIGN for C or ldo % 4 != 0, tok, pos or out not 16-byte aligned, ids not 4-byte aligned; all before any HIP call.
+ * rows == 0 is a successful no-op.  One float4 per lane per trip, a wave on 64 consecutive float4 of a row (256-float runs of
+ * both tables and of the output), grid-stride over rows * C / 4 with 64-bit indices: any row count, at most 65536 workgroups. */
+int ofx_clip_embed(const int32_t* ids, const float* tok, const float* pos, float* out, int ldo, long rows, int T, int C, int vocab,
+                   void* stream);
+/* quick_gelu over token rows, the activation of CLIPMLP (hidden_act "quick_gelu", what FrozenCLIPEmbedder's checkpoint is):
+ *   out[r][c] = x[r][c] * sigmoid(1.702f * x[r][c]),   c < n,   evaluated as x / (1 + expf(-(1.702f * x))) in fp32 with the accurate
+ * expf and an IEEE division.  Finite for every finite x: where the exponential overflows (x < -52.1) the quotient is -0.  Rows of
+ * x / out are ldx / ldo >= n floats apart (a last-axis slice is a valid operand), columns n.. are not touched; out == x is allowed.
+ * OFX_EINVAL for a NULL pointer, rows < 0, n <= 0, ldx < n or ldo < n; OFX_EALIGN for n, ldx or ldo % 4 != 0 or a pointer not
+ * 16-byte aligned; all before any HIP call.  rows == 0 is a successful no-op.  The same one-float4-per-lane grid-stride loop. */
+int ofx_quick_gelu(const float* x, int ldx, float* out, int ldo, long rows, int n, void* stream);
 
 /* ---------------------------------------------------------------- sampler (guided_ldm_inpainting.py:28-137, guided_ldm.py:30-158) */
 /* The scalars of one DDIM step, fp32 as the reference forms them: cfg = unconditional_guidance_scale, sqrt_at = sqrt(ddim_alphas

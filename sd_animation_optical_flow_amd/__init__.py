@@ -10,7 +10,8 @@ Modules: `pdcnet_of`, `ofgen`, `alt_cuda_corr` (the reference's names; `ofgen.ke
 latent and `memory_efficient_attention` on the device), `transformer` (the UNet's `SpatialTransformer` with reference-frame K/V
 history), `unet` (the reference's `UNetModel` / `ControlledUnetModel` around it: `control` residuals in, K/V history in and
 out), `controlnet` (the reference's `ControlNet`, `SingleControlNet` and `apply_multi_controlnet`: the `control` residuals from a
-hint image), `keyframes` (Canny-based key-frame detector), `ops` (one wrapper per
+hint image), `text_encoder` (the reference's hacked `FrozenCLIPEmbedder`: prompt tokens to the `context` tensors),
+`keyframes` (Canny-based key-frame detector), `ops` (one wrapper per
 C-ABI entry point), `_lib` (ctypes binding).  The repository root carries two shims named as the reference imports them:
 `alt_cuda_corr` and `xformers`.
 """

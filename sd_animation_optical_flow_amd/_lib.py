@@ -124,6 +124,8 @@ SIGNATURES = {
     "ofx_timestep_embedding": (_i, [_p, _p, _p, _i, _i, _p]),
     "ofx_ddim_step": (_i, [_p, _i, _p, _p, _i, _p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, C.POINTER(DdimCoef), _i, _l, _i, _p]),
     "ofx_conv3x3_silu": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "ofx_clip_embed": (_i, [_p, _p, _p, _p, _i, _l, _i, _i, _i, _p]),
+    "ofx_quick_gelu": (_i, [_p, _i, _p, _i, _l, _i, _p]),
     "ofx_corr_slice_floats": (_i, [_i, _i]),
     "ofx_corr_volume": (_i, [_p, _p, C.POINTER(_p), _i, _i, _i, _i, _i, _p]),
     "ofx_corr_volume_split": (_i, [_p, _p, C.POINTER(_p), _i, _i, _i, _i, _i, _i, _i, _p]),

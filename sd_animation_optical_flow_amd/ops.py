@@ -998,6 +998,46 @@ def attention_bnhd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
 
 
 # --------------------------------------------------------------------------------------
+# CLIP text encoder pieces (hack.py:32-70): the token + position embedding and quick_gelu
+# --------------------------------------------------------------------------------------
+def clip_embed(ids: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, T: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """CLIPTextEmbeddings.forward (`ofx_clip_embed`): ids int32 [...] on the device, flattened to rows in sequence-major order; tok
+    [vocab,C] and pos [>=T,C] float32, contiguous -> out[r] = tok[ids[r]] + pos[r % T], float32 [..., C] (new and contiguous when not
+    given; `out` may be a last-axis slice of a wider tensor).  C % 4 == 0.  A row whose id is outside [0, vocab) comes out all NaN."""
+    ids = _chk(ids, "ids", torch.int32)
+    tok = _chk(tok, "tok", torch.float32)
+    pos = _chk(pos, "pos", torch.float32)
+    T = int(T)
+    if tok.dim() != 2 or pos.dim() != 2 or pos.shape[1] != tok.shape[1] or T <= 0 or pos.shape[0] < T:
+        raise RuntimeError("clip_embed: tok [vocab,C] and pos [>=T,C] expected")
+    vocab, Cn = (int(s) for s in tok.shape)
+    rows = ids.numel()
+    shape = tuple(ids.shape) + (Cn,)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=ids.device)
+    if tuple(out.shape) != shape:
+        raise RuntimeError(f"out must be {shape}, got {tuple(out.shape)}")
+    if rows == 0:
+        return out
+    _, _, ldo = _rows_view(out, "out")
+    check(_lib.lib().ofx_clip_embed(_ptr(ids), _ptr(tok), _ptr(pos), _ptr(out), ldo, rows, T, Cn, vocab, _stream()), "ofx_clip_embed")
+    return out
+
+
+def quick_gelu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x * sigmoid(1.702 x) over the last axis' rows (`ofx_quick_gelu`).  x and `out` [..., n] float32: contiguous or last-axis slices
+    of wider tensors; n % 4 == 0.  `out`: the same shape (x itself: in place); a new contiguous tensor otherwise."""
+    rows, n, ldx = _rows_view(x, "x")
+    if out is None:
+        out = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+    _, _, ldo = _rows_view(out, "out")
+    if tuple(out.shape) != tuple(x.shape):
+        raise RuntimeError(f"out must be {tuple(x.shape)}, got {tuple(out.shape)}")
+    check(_lib.lib().ofx_quick_gelu(_ptr(x), ldx, _ptr(out), ldo, rows, n, _stream()), "ofx_quick_gelu")
+    return out
+
+
+# --------------------------------------------------------------------------------------
 # UNet pieces (ldm/modules/diffusionmodules/openaimodel.py:257-277, :530-534, :757-793; util.py:154-174)
 # --------------------------------------------------------------------------------------
 def _nhwc_seg(t: torch.Tensor, name: str) -> Tuple[int, int, int, int, int]:

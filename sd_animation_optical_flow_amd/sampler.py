@@ -332,7 +332,7 @@ def img2img_inpaint(unet, vae_encoder, vae_decoder, image_bgr, reference_bgr, ma
                     reference_kv=(), sampler: Optional[GuidedDDIMSampler] = None):
     """`GuidedLDM.img2img_inpaint` with a reference frame (guided_ldm_inpainting.py:262-345), eta = 0: image_bgr / reference_bgr
     uint8 [H,W,3] (cv2 channel order) and mask uint8 [H,W] (255 = repaint) as `handoff.prepare_inpaint_inputs` takes them, context /
-    unconditional_context [1,M,context_dim] device tensors (the text encoder is not built) ->
+    unconditional_context [1,M,context_dim] device tensors (`text_encoder.ClipTextEncoder.conditioning` makes both from a prompt pair) ->
         (x_samples clipped to [-1,1] f32 [1,3,H,W],  image f32 [1,3,H,W],  init_latent_decoded clipped)
     The chain: prepare_inpaint_inputs; init_latent = encode(image); c_concat = cat(conditioning_mask_latent, encode(conditioning
     _image)); t_enc = int(min(strength, 0.999) * steps); stochastic_encode(init_latent, t_enc); decode with nmask = latmask; the final
