@@ -346,6 +346,17 @@ int ofx_ddim_step(const float* x, int ldx, const float* eps_c, const float* eps_
 size_t ofx_detect_edges_scratch_bytes(int B, int H, int W);
 int ofx_detect_edges(const uint8_t* frames_bgr, uint8_t* edges, void* scratch, size_t scratch_bytes, int B, int H,
                      int W, int ksize, void* stream);
+/* edges[b] = cv2.Canny(images[b], low, high) (aperture 3, L2gradient=false) for u8 [B,H,W] (channels 1) or [B,H,W,3]
+ * (channels 3) images: what ControlNet's 'canny' detector computes (extract_control, controlnet.py:343-347).  The 3x3 Sobel
+ * runs per channel and a pixel keeps the (dx, dy, |dx|+|dy|) of the channel with the largest norm, the lowest channel on a
+ * tie; then the suppression and hysteresis stages of ofx_detect_edges (they are shared), m > low a candidate, m > high
+ * strong; low > high are swapped.  edges: u8 [B,H,W], 255 or 0, no dilation.  scratch: ofx_canny_u8_scratch_bytes(B,H,W)
+ * bytes, 256-byte aligned; like ofx_detect_edges the call SYNCHRONISES the stream once per batch of 8 sweeps.  Checked
+ * before any launch: NULL pointers, channels not 1 or 3, B outside 1..65535, H or W <= 0 (OFX_EINVAL), a misaligned
+ * (OFX_EALIGN) or too small (OFX_ENOMEM) scratch.  Parity: OpenCV's algorithm restated; unpinned. */
+size_t ofx_canny_u8_scratch_bytes(int B, int H, int W);
+int ofx_canny_u8(const uint8_t* images, int channels, uint8_t* edges, void* scratch, size_t scratch_bytes, int B, int H,
+                 int W, int low, int high, void* stream);
 /* sums[b] = sum_i |a[b*a_bstride + i] - b_[b*b_bstride + i]|, i < n (mean_pixel_distance's numerator, :143-150);
  * a stride of 0 compares every image with one shared image.  sums: device u64[B]. */
 int ofx_abs_diff_sum_u8(const uint8_t* a, long a_bstride, const uint8_t* b, long b_bstride,

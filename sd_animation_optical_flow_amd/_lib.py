@@ -98,6 +98,8 @@ SIGNATURES = {
     "ofx_sd_handoff": (_i, [_p] * 9 + [_i] * 5 + [_p]),
     "ofx_detect_edges_scratch_bytes": (_z, [_i, _i, _i]),
     "ofx_detect_edges": (_i, [_p, _p, _p, _z, _i, _i, _i, _i, _p]),
+    "ofx_canny_u8_scratch_bytes": (_z, [_i, _i, _i]),
+    "ofx_canny_u8": (_i, [_p, _i, _p, _p, _z, _i, _i, _i, _i, _i, _p]),
     "ofx_abs_diff_sum_u8": (_i, [_p, _l, _p, _l, _p, _i, _l, _p]),
     "ofx_inorm_stats": (_i, [_p, _i, _p, _p, _p, _i, _l, _i, _f, _p]),
     "ofx_conv2d_stats": (_i, [C.POINTER(ConvDesc), _p, _z, _p, _p]),

@@ -25,8 +25,11 @@ ControlNet's own:
 `c.net is None` triggers loading a checkpoint by model name and computing the residuals (:414-419); here `c.net` is a `ControlNet`
 (or any callable with its `forward` signature) the caller built, and the residuals are computed when `c.result is None`.
 
-Not built: the detectors that produce a condition (`cv2.Canny` on a colour frame; `apply_hed`, whose module is missing from the
-reference tree), loading a checkpoint by model name, and everything `unet._check_cfg` refuses (dims != 2 among it).
+The 'canny' detector is `canny_condition`: `cv2.Canny` on a grey or colour frame through `ops.canny` (csrc/keyframe.hip), the edge
+map staying on the device.  `ControlSchedule` carries the nets' guidance windows into the sampler's loop.
+
+Not built: `apply_hed` (its module is missing from the reference tree), loading a checkpoint by model name, and everything
+`unet._check_cfg` refuses (dims != 2 among it).
 
 OFX_CNET_TORCH_GLUE=1 in the environment (read once per process; the A/B baseline and a diagnostic): the hint stem through
 torch.nn.functional.conv2d + F.silu on NCHW.  The trunk is unaffected.
@@ -242,8 +245,8 @@ def make_hint(model: str, condition, args: Optional[dict] = None, device="cuda")
         'canny' / 'hed'   condition u8 [H,W], an edge map   -> three equal channels of v / 255
         'inpaint'         condition u8 [H,W,3] and args['mask'] u8 [H,W]   -> -1.0 where mask > 127, else v / 255
     Batch 1: `ControlNet.forward` broadcasts it (the reference repeats an edge map to n = 2 and stacks one inpaint map).  The
-    detectors that make an edge map are out of scope: `cv2.Canny` on a colour frame with args' thresholds, and `apply_hed`, whose
-    module is missing from the reference tree.  Plain torch ops: once per frame."""
+    edge map of 'canny' comes from `canny_condition` (`cv2.Canny` on the frame with args' thresholds); `apply_hed`, whose module is
+    missing from the reference tree, is not built.  Plain torch ops: once per frame."""
     cond = torch.as_tensor(np.ascontiguousarray(condition) if isinstance(condition, np.ndarray) else condition)
     if cond.dtype != torch.uint8:
         raise ValueError(f"make_hint: the condition must be uint8, got {cond.dtype}")
@@ -264,6 +267,16 @@ def make_hint(model: str, condition, args: Optional[dict] = None, device="cuda")
         v[mask.to(device) > 127] = -255.0                          # :363: -1 after the division is the inpaint value
         return (v / 255.0).permute(2, 0, 1)[None].contiguous()
     raise NotImplementedError(f"make_hint: model {model!r} is not built (the reference builds 'canny', 'hed' and 'inpaint')")
+
+
+def canny_condition(frame, low_threshold, high_threshold, device="cuda") -> torch.Tensor:
+    """The detector half of `extract_control` for 'canny' (:343-347): `cv2.Canny(frame, low_threshold, high_threshold)` through
+    `ops.canny`.  frame u8 [H,W] or [H,W,3] (cv2 channel order), numpy or tensor -> the edge map u8 [H,W] on `device`, 255 or 0:
+    what `SingleControlNet.condition` and `make_hint('canny', ...)` take.  A frame already on the device is not copied."""
+    f = torch.as_tensor(np.ascontiguousarray(frame) if isinstance(frame, np.ndarray) else frame)
+    if f.dtype != torch.uint8 or f.dim() not in (2, 3) or (f.dim() == 3 and f.shape[2] != 3):
+        raise ValueError(f"canny_condition: the frame must be uint8 [H,W] or [H,W,3], got {f.dtype} {tuple(f.shape)}")
+    return ops.canny(f.to(device).contiguous()[None], low_threshold, high_threshold)[0]
 
 
 def control_weight(c: SingleControlNet, denoise_percentage: float) -> float:
@@ -296,3 +309,34 @@ def apply_multi_controlnet(x_noisy: torch.Tensor, t: torch.Tensor, cond_txt: Opt
         for i, r in enumerate(c.result):
             controls[i].add_(r, alpha=w)
     return controls
+
+
+class ControlSchedule:
+    """The guidance windows of `apply_multi_controlnet` inside the sampler's loop: a callable `control(i, p)` for
+    `GuidedDDIMSampler.decode(control=)`.  Its value at iteration i is `apply_multi_controlnet`'s mix of the nets' cached `result`s at
+    the loop's denoise percentage p, or None when every weight is 0 there.  The mix is recomputed only when the tuple of
+    `control_weight(c, p)` changes, so a window that closes costs one mix, not one per step; `mixes` counts them.  Every net must
+    hold a `result` (ValueError): the caller runs `apply_multi_controlnet` once per frame, which computes and caches them."""
+
+    def __init__(self, nets: Sequence[SingleControlNet]):
+        self.nets = list(nets)
+        if not self.nets:
+            raise ValueError("ControlSchedule: no control nets")
+        for c in self.nets:
+            if c.result is None:
+                raise ValueError(f"ControlSchedule: SingleControlNet(model={c.model!r}) has no cached result: run "
+                                 "apply_multi_controlnet once for this frame first")
+        self.mixes = 0
+        self._weights: Optional[Tuple[float, ...]] = None
+        self._value: Optional[List[torch.Tensor]] = None
+
+    def __call__(self, i: int, p: float) -> Optional[List[torch.Tensor]]:
+        weights = tuple(control_weight(c, p) for c in self.nets)
+        if weights != self._weights:
+            self._weights = weights
+            if any(weights):
+                self._value = apply_multi_controlnet(None, None, None, p, self.nets)     # every result is cached: no net runs
+                self.mixes += 1
+            else:
+                self._value = None
+        return self._value

@@ -5,6 +5,10 @@
 // replicated borders, L1 magnitude, the 15-bit fixed-point tan(22.5) direction test, hysteresis); the thresholds
 // come from the exact median through a 256-bin histogram.  PARITY UNPINNED (no OpenCV in the reference tree or in
 // this image): the kernels are held bit-exactly to oracle/keyframe_oracle.py.
+//
+// ofx_canny_u8 is cv2.Canny itself on 1- or 3-channel images with the caller's thresholds (the detector of ControlNet's 'canny'
+// conditions, controlnet.py:343-347): its own gradient front end -- per channel, the strongest channel per pixel -- in front of the
+// same suppression body and the same hysteresis sweeps, no histogram and no dilation.  Held to tests/canny_check.py.
 #include "ofx_internal.h"
 
 namespace {
@@ -50,28 +54,46 @@ __global__ void kf_thresholds_kernel(const unsigned* __restrict__ hist, int* __r
     thr[2 * b + 1] = high;
 }
 
+// 3x3 Sobel with replicated borders of pixel (y, x) of an image with CH interleaved 8-bit channels.  With 3 channels the pixel
+// keeps the (dx, dy) of the channel with the largest |dx| + |dy|; channels are scanned in memory order and a later one replaces an
+// earlier one only when its norm is strictly larger (canny.cpp), so a tie keeps the lowest channel.  Returns the norm.
+template <int CH>
+__device__ __forceinline__ int kf_sobel(const uint8_t* __restrict__ L, int H, int W, int y, int x, int& dx, int& dy) {
+    const int ym = max(y - 1, 0), yp = min(y + 1, H - 1), xm = max(x - 1, 0), xp = min(x + 1, W - 1);   // BORDER_REPLICATE
+    const uint8_t *r0 = L + (long)ym * W * CH, *r1 = L + (long)y * W * CH, *r2 = L + (long)yp * W * CH;
+    int m = -1;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        const int a00 = r0[xm * CH + c], a01 = r0[x * CH + c], a02 = r0[xp * CH + c];
+        const int a10 = r1[xm * CH + c], a12 = r1[xp * CH + c];
+        const int a20 = r2[xm * CH + c], a21 = r2[x * CH + c], a22 = r2[xp * CH + c];
+        const int cx = (a02 + 2 * a12 + a22) - (a00 + 2 * a10 + a20);
+        const int cy = (a20 + 2 * a21 + a22) - (a00 + 2 * a01 + a02);
+        const int cm = abs(cx) + abs(cy);
+        if (cm > m) { m = cm; dx = cx; dy = cy; }
+    }
+    return m;
+}
+
 // Sobel + L1 magnitude into an LDS tile with a one-pixel apron (zero outside the image), then non-maximum
-// suppression: map = 2 strong, 0 candidate, 1 none.
+// suppression: map = 2 strong, 0 candidate, 1 none.  The thresholds of image b are thr[2b], thr[2b+1] (the key-frame detector's,
+// from the median) or, with thr null, the arguments low <= high (ofx_canny_u8).
 constexpr int kCW = 32, kCH = 8;
-__global__ __launch_bounds__(256) void kf_canny_map_kernel(const uint8_t* __restrict__ lum, const int* __restrict__ thr,
+template <int CH>
+__global__ __launch_bounds__(256) void kf_canny_map_kernel(const uint8_t* __restrict__ img, const int* __restrict__ thr, int low, int high,
                                                            uint8_t* __restrict__ map, int H, int W) {
     __shared__ int smag[kCH + 2][kCW + 2];
     __shared__ short sdx[kCH][kCW], sdy[kCH][kCW];
     const long b = blockIdx.z;
-    const uint8_t* L = lum + b * (long)H * W;
+    const uint8_t* L = img + b * (long)H * W * CH;
     const int x0 = blockIdx.x * kCW, y0 = blockIdx.y * kCH;
     for (int i = threadIdx.x; i < (kCH + 2) * (kCW + 2); i += 256) {
         const int ly = i / (kCW + 2), lx = i - ly * (kCW + 2);
         const int y = y0 + ly - 1, x = x0 + lx - 1;
         int m = 0;
         if ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) {
-            const int ym = max(y - 1, 0), yp = min(y + 1, H - 1), xm = max(x - 1, 0), xp = min(x + 1, W - 1);   // BORDER_REPLICATE
-            const int a00 = L[(long)ym * W + xm], a01 = L[(long)ym * W + x], a02 = L[(long)ym * W + xp];
-            const int a10 = L[(long)y * W + xm], a12 = L[(long)y * W + xp];
-            const int a20 = L[(long)yp * W + xm], a21 = L[(long)yp * W + x], a22 = L[(long)yp * W + xp];
-            const int dx = (a02 + 2 * a12 + a22) - (a00 + 2 * a10 + a20);
-            const int dy = (a20 + 2 * a21 + a22) - (a00 + 2 * a01 + a02);
-            m = abs(dx) + abs(dy);
+            int dx = 0, dy = 0;
+            m = kf_sobel<CH>(L, H, W, y, x, dx, dy);
             if (ly >= 1 && ly <= kCH && lx >= 1 && lx <= kCW) {
                 sdx[ly - 1][lx - 1] = (short)dx;
                 sdy[ly - 1][lx - 1] = (short)dy;
@@ -83,7 +105,7 @@ __global__ __launch_bounds__(256) void kf_canny_map_kernel(const uint8_t* __rest
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int x = x0 + tx, y = y0 + ty;
     if (x >= W || y >= H) return;
-    const int low = thr[2 * b], high = thr[2 * b + 1];
+    if (thr != nullptr) { low = thr[2 * b]; high = thr[2 * b + 1]; }
     const int m = smag[ty + 1][tx + 1];
     uint8_t out = 1;
     if (m > low) {
@@ -220,9 +242,79 @@ KfScratch kf_carve(void* base, int B, int H, int W) {
     return s;
 }
 
+// hysteresis of both entry points: sweep until nothing changes.  kSweepBatch sweeps per host check (a 4-byte copy + one stream
+// synchronisation per batch); flag[k] = "sweep k of the batch moved something", a converged sweep leaves 0 and every later
+// sweep of the batch retires at once.  flag: kSweepBatch ints of scratch.  One profiler scope per batch, so a profile's call
+// count is the number of batches an input took.
+int kf_hysteresis(uint8_t* map, int* flag, int B, int H, int W, hipStream_t st) {
+    for (int it = 0; it < 4 * (H + W); it += kSweepBatch) {
+        OFX_HIP_CHECK(hipMemsetAsync(flag, 0, kSweepBatch * sizeof(int), st));
+        {
+            OfxProfScope prof("hysteresis_batch", st);
+            for (int k = 0; k < kSweepBatch; ++k)
+                hipLaunchKernelGGL(kf_hysteresis_kernel, dim3(ofx_cdiv(W, kHT), ofx_cdiv(H, kHT), B), dim3(256), 0, st, map, H, W,
+                                   k == 0 ? (const int*)nullptr : (const int*)(flag + k - 1), flag + k);
+        }
+        int host_flag = 0;
+        OFX_HIP_CHECK(hipMemcpyAsync(&host_flag, flag + kSweepBatch - 1, sizeof(int), hipMemcpyDeviceToHost, st));
+        OFX_HIP_CHECK(hipStreamSynchronize(st));
+        if (!host_flag) break;
+    }
+    return 0;
+}
+
+// ofx_canny_u8's scratch: the suppression map and the sweep flags
+struct CannyScratch {
+    uint8_t* map;
+    int* flag;
+    size_t bytes;
+};
+CannyScratch canny_carve(void* base, int B, int H, int W) {
+    CannyScratch s{};
+    const size_t n = ((size_t)B * H * W + 255) / 256 * 256;
+    s.map = (uint8_t*)base;
+    s.flag = (int*)((char*)base + n);
+    s.bytes = n + 256;
+    return s;
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t ofx_canny_u8_scratch_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return canny_carve(nullptr, B, H, W).bytes;
+}
+
+int ofx_canny_u8(const uint8_t* images, int channels, uint8_t* edges, void* scratch, size_t scratch_bytes, int B, int H, int W, int low,
+                 int high, void* stream) {
+    OFX_REQUIRE(images && edges && scratch && H > 0 && W > 0, OFX_EINVAL);
+    OFX_REQUIRE((channels == 1 || channels == 3) && B >= 1 && B <= 65535, OFX_EINVAL);
+    OFX_REQUIRE((long)W * channels <= 0x7fffffffL && ofx_cdiv(H, kCH) <= 65535, OFX_EINVAL);     // the kernels' int column offsets, grid.y
+    OFX_REQUIRE((((uintptr_t)scratch) & 255u) == 0, OFX_EALIGN);
+    CannyScratch s = canny_carve(scratch, B, H, W);
+    OFX_REQUIRE(s.bytes <= scratch_bytes, OFX_ENOMEM);
+    if (low > high) { const int t = low; low = high; high = t; }   // cv::Canny swaps
+    hipStream_t st = (hipStream_t)stream;
+    const long total = (long)B * H * W;
+    {
+        OfxProfScope prof("canny_map", st);
+        const dim3 grid(ofx_cdiv(W, kCW), ofx_cdiv(H, kCH), B);
+        if (channels == 3)
+            hipLaunchKernelGGL(kf_canny_map_kernel<3>, grid, dim3(256), 0, st, images, (const int*)nullptr, low, high, s.map, H, W);
+        else
+            hipLaunchKernelGGL(kf_canny_map_kernel<1>, grid, dim3(256), 0, st, images, (const int*)nullptr, low, high, s.map, H, W);
+    }
+    {
+        const int rc = kf_hysteresis(s.map, s.flag, B, H, W, st);
+        if (rc) return rc;
+    }
+    // 255 * (map == 2): the row pass of the dilation at radius 0
+    const int g = (int)std::min<long>((total + 255) / 256, 256L * 32);
+    hipLaunchKernelGGL(kf_dilate_rows_kernel, dim3(g), dim3(256), 0, st, s.map, edges, H, W, 0, total);
+    return ofx_launch_status();
+}
 
 size_t ofx_detect_edges_scratch_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
@@ -244,20 +336,11 @@ int ofx_detect_edges(const uint8_t* frames_bgr, uint8_t* edges, void* scratch, s
         const int gx = (int)std::min<long>((HW + 255) / 256, 1024);
         hipLaunchKernelGGL(kf_value_hist_kernel, dim3(gx, B), dim3(256), 0, st, frames_bgr, s.lum, s.hist, HW);
         hipLaunchKernelGGL(kf_thresholds_kernel, dim3(B), dim3(64), 0, st, s.hist, s.thr, HW);
-        hipLaunchKernelGGL(kf_canny_map_kernel, dim3(ofx_cdiv(W, kCW), ofx_cdiv(H, kCH), B), dim3(256), 0, st, s.lum, s.thr, s.map, H, W);
+        hipLaunchKernelGGL(kf_canny_map_kernel<1>, dim3(ofx_cdiv(W, kCW), ofx_cdiv(H, kCH), B), dim3(256), 0, st, s.lum, s.thr, 0, 0, s.map, H, W);
     }
-    // hysteresis: sweep until nothing changes.  kSweepBatch sweeps per host check (a 4-byte copy + one stream
-    // synchronisation per batch); flags[k] = "sweep k of the batch moved something", a converged sweep leaves 0 and
-    // every later sweep of the batch retires at once
-    for (int it = 0; it < 4 * (H + W); it += kSweepBatch) {
-        OFX_HIP_CHECK(hipMemsetAsync(s.flag, 0, kSweepBatch * sizeof(int), st));
-        for (int k = 0; k < kSweepBatch; ++k)
-            hipLaunchKernelGGL(kf_hysteresis_kernel, dim3(ofx_cdiv(W, kHT), ofx_cdiv(H, kHT), B), dim3(256), 0, st, s.map, H, W,
-                               k == 0 ? (const int*)nullptr : (const int*)(s.flag + k - 1), s.flag + k);
-        int host_flag = 0;
-        OFX_HIP_CHECK(hipMemcpyAsync(&host_flag, s.flag + kSweepBatch - 1, sizeof(int), hipMemcpyDeviceToHost, st));
-        OFX_HIP_CHECK(hipStreamSynchronize(st));
-        if (!host_flag) break;
+    {
+        const int rc = kf_hysteresis(s.map, s.flag, B, H, W, st);
+        if (rc) return rc;
     }
     const int r = ksize / 2;
     const int g = (int)std::min<long>((total + 255) / 256, 256L * 32);

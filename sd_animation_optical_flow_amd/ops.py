@@ -1208,6 +1208,23 @@ def detect_edges(frames_bgr: torch.Tensor, ksize: int) -> torch.Tensor:
     return out
 
 
+def canny(images: torch.Tensor, low, high) -> torch.Tensor:
+    """`cv2.Canny(image, low, high)` (aperture 3, L1 gradient) per image: uint8 [B,H,W] or [B,H,W,3] (any channel order: the
+    strongest channel wins per pixel) -> uint8 [B,H,W], 255 or 0.  The thresholds are numbers and are floored (cvFloor), and
+    swapped when low > high, as cv::Canny does."""
+    f = _chk(images, "images", torch.uint8)
+    if f.dim() not in (3, 4) or (f.dim() == 4 and f.shape[3] != 3):
+        raise RuntimeError(f"images must be uint8 [B,H,W] or [B,H,W,3], got {tuple(f.shape)}")
+    B, H, W = f.shape[:3]
+    lo, hi = int(math.floor(low)), int(math.floor(high))
+    L = _lib.lib()
+    need = L.ofx_canny_u8_scratch_bytes(B, H, W)
+    scratch = torch.empty((need,), dtype=torch.uint8, device=f.device)
+    out = torch.empty((B, H, W), dtype=torch.uint8, device=f.device)
+    check(L.ofx_canny_u8(_ptr(f), 3 if f.dim() == 4 else 1, _ptr(out), _ptr(scratch), need, B, H, W, lo, hi, _stream()), "ofx_canny_u8")
+    return out
+
+
 def abs_diff_sum_u8(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """a: uint8 [B,...]; b: same shape or one image [...] shared by the batch -> int64 [B] sums of |a - b|."""
     x = _chk(a, "a", torch.uint8)

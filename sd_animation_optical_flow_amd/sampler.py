@@ -3,6 +3,7 @@
     GuidedDDIMSample.p_sample_ddim / decode      guided_ldm_inpainting.py:28-137   (mask blend, guidance only gates it)
     GuidedDDIMSample.p_sample_ddim / decode      guided_ldm.py:30-158              (latent guidance of pred_x0)
     GuidedLDM.img2img_inpaint                    guided_ldm_inpainting.py:262-345
+    GuidedLDM.img2img                            guided_ldm_inpainting.py:185-259 (mask None), guided_ldm.py:166-219 (latent guidance)
     DDIMSampler.make_schedule, stochastic_encode ldm/models/diffusion/ddim.py:23-52, :301-314
     DDPM.register_schedule, q_sample             ldm/models/diffusion/ddpm.py:138-160, :356-359
     DiffusionWrapper.forward ("hybrid")          ddpm.py:1404-1407
@@ -184,6 +185,9 @@ class GuidedDDIMSampler:
         on the device (q_sample noise only when nmask is given, first; the DDIM noise only when eta > 0).
         control / reference_kv go to every UNet call unchanged and must be at the UNet's batch (2B with classifier-free guidance);
         neither they nor any latent passed in is written to.  callback(i) runs after step i.
+        control may also be a callable control(i, p), called right before the UNet call of iteration i with `decode_plan`'s p: it
+        returns what control= takes, a list at the UNet's batch or None, and each distinct object it returns is validated
+        (`unet._check_inputs`) before it is used.  `controlnet.ControlSchedule` is one: the nets' guidance windows.
         `self.last_kv_hists` is the K/V history of the LAST UNet call -- the final step (index 0), the least noisy latent, at the
         UNet's batch (unconditional rows first).  The reference's driver stores one history per frame and its tree has no code that
         defines which step's; the last call is what a loop that keeps overwriting one variable leaves behind.
@@ -266,7 +270,8 @@ class GuidedDDIMSampler:
             if (blend and qn is None) or (eta_on and dn is None):
                 raise ValueError("step_noise lacks a tensor this run needs")
         ts_all = torch.tensor([[float(step)] * UB for _, _, step, _ in plan], dtype=torch.float32)
-        unet._check_inputs(UB, h, w, ts_all[0], None, control, reference_kv)         # raises on a bad control / reference_kv / size
+        control_fn = control if callable(control) else None                           # control(i, p): validated as it is returned
+        unet._check_inputs(UB, h, w, ts_all[0], None, None if control_fn else control, reference_kv)   # raises on a bad control / reference_kv / size
         # ---- setup: the only allocations and layout changes of the loop
         if step_noise is None and n_noise:
             drawn = torch.randn((n_noise, t_start, B, Cz, h, w), generator=generator, device=dev, dtype=torch.float32)
@@ -300,7 +305,13 @@ class GuidedDDIMSampler:
             k, kw = blend_args(0)
             ops.ddim_step(x0v, k, out0=x0v, out1=x1v, blend_only=True, **kw)
         kv: List[Tuple[torch.Tensor, torch.Tensor]] = []
+        checked: list = []                                                            # the distinct objects control(i, p) has returned
         for i, (p, index, step, gs) in enumerate(plan):
+            if control_fn is not None:
+                control = control_fn(i, p)
+                if control is not None and not any(control is c for c in checked):
+                    unet._check_inputs(UB, h, w, ts_all[i], None, control, ())
+                    checked.append(control)
             eps, kv = unet.forward_nhwc(buf, ts_all[i], ctx_in, control, False, reference_kv, padded=True)
             k = step_coefficients(sched, index, temperature)
             k["cfg"] = float(unconditional_guidance_scale)
@@ -379,3 +390,73 @@ def img2img_inpaint(unet, vae_encoder, vae_decoder, image_bgr, reference_bgr, ma
     x_samples = vae_decoder.decode_first_stage(decoded)
     init_latent_decoded = vae_decoder.decode_first_stage(init_latent).clip(-1, 1)
     return torch.clip(x_samples, -1, 1), image, init_latent_decoded
+
+
+def _bgr_image(frame_bgr, name: str, device) -> torch.Tensor:
+    """u8 [H,W,3] or [B,H,W,3] in cv2 channel order, numpy or tensor -> f32 [B,3,H,W] RGB, x / 127.5 - 1, computed on the device
+    (`frame_rgb.astype(np.float32) / 127.5 - 1.`, ofgen_keyframe_inpaint.py:204)."""
+    t = frame_bgr if torch.is_tensor(frame_bgr) else torch.from_numpy(np.ascontiguousarray(frame_bgr))
+    if t.dtype != torch.uint8 or t.dim() not in (3, 4) or t.shape[-1] != 3:
+        raise RuntimeError(f"{name} must be uint8 [H,W,3] or [B,H,W,3]")
+    t = t.to(device)
+    if t.dim() == 3:
+        t = t[None]
+    return t.flip(-1).permute(0, 3, 1, 2).float().contiguous() / 127.5 - 1.0
+
+
+@torch.no_grad()
+def img2img(unet, vae_encoder, vae_decoder, image_bgr, context: torch.Tensor, unconditional_context: Optional[torch.Tensor], *,
+            denoising_strength: float, ddim_steps: int = 50, target_bgr=None, guidance_schedule_func: Callable = lambda p: 0.1,
+            unconditional_guidance_scale: float = 7.0, noise: Optional[Dict[str, torch.Tensor]] = None,
+            generator: Optional[torch.Generator] = None, control=None, reference_kv=(),
+            sampler: Optional[GuidedDDIMSampler] = None) -> torch.Tensor:
+    """`GuidedLDM.img2img`, eta = 0: the seed key frames of the live driver and the guided frames of `ofgen.py`.  image_bgr /
+    target_bgr uint8 [H,W,3] or [B,H,W,3] (cv2 channel order; several frames side by side in one wide image are one image), context
+    / unconditional_context [B,M,context_dim] device tensors -> x_samples f32 [B,3,H,W] clipped to [-1,1].
+        target_bgr None    guided_ldm_inpainting.py:185-259 with mask None: init_latent = encode(image); t_enc = int(min(strength,
+                           0.999) * steps); stochastic_encode; decode without nmask or c_concat; decode_first_stage; clip
+        target_bgr given   guided_ldm.py:166-219 with guidance_space='latent': the target's latent is `decode(guidance=)` and
+                           guidance_schedule_func returns a float or a device map at latent size, as `decode` takes them
+    noise: explicit tensors [B,4,h,w] under the keys "init" and "target" (the encoder samples) and "x1" (stochastic_encode's); a key
+    left out is drawn from `generator` on the device, in that order (init, target, x1), each with one torch.randn; "target" is
+    drawn only when a target is given.  control (a list or a callable, as `decode` takes) and reference_kv go to `decode`.
+    `sampler`: a GuidedDDIMSampler over `unet` to reuse; its `last_kv_hists` is what the driver stores per key frame.
+    t_enc == 0 and a UNet whose in_channels is not 4 (there is no c_concat on this path) are ValueErrors before any launch.  No
+    launch of its own: the loop is `decode`, around it two (or three) VAE passes."""
+    t_enc = int(min(denoising_strength, 0.999) * ddim_steps)
+    if t_enc <= 0:
+        raise ValueError(f"denoising_strength={denoising_strength} at {ddim_steps} steps gives t_enc = 0: no step to run")
+    if unet.in_channels != 4:
+        raise ValueError(f"img2img runs the UNet on the latent alone: in_channels must be 4, got {unet.in_channels} (a hybrid UNet "
+                         "is img2img_inpaint's)")
+    noise = dict(noise or {})
+    unknown = set(noise) - {"init", "target", "x1"}
+    if unknown:
+        raise ValueError(f"noise has unknown keys {sorted(unknown)}")
+    if target_bgr is None and "target" in noise:
+        raise ValueError("noise['target'] without target_bgr")
+    smp = sampler if sampler is not None else GuidedDDIMSampler(unet)
+    smp.make_schedule(ddim_steps, 0.0)
+    dev = unet.device
+    image = _bgr_image(image_bgr, "image_bgr", dev)
+    target = None if target_bgr is None else _bgr_image(target_bgr, "target_bgr", dev)
+    if target is not None and tuple(target.shape) != tuple(image.shape):
+        raise RuntimeError(f"target_bgr {tuple(target.shape)} does not match image_bgr {tuple(image.shape)}")
+    B, _, H, W = image.shape
+    shape = (B, 4, H // 8, W // 8)
+
+    def draw(key):
+        if key in noise:
+            return _latent(noise[key], f"noise[{key!r}]", shape)
+        return torch.randn(shape, generator=generator, device=dev, dtype=torch.float32)
+
+    n_init = draw("init")
+    n_target = draw("target") if target is not None else None
+    n_x1 = draw("x1")
+    init_latent = vae_encoder.get_first_stage_encoding(image, n_init)
+    target_latent = None if target is None else vae_encoder.get_first_stage_encoding(target, n_target)
+    x1 = smp.stochastic_encode(init_latent, t_enc, n_x1)
+    decoded, _ = smp.decode(x1, context, t_enc, unconditional_context=unconditional_context,
+                            unconditional_guidance_scale=unconditional_guidance_scale, guidance=target_latent,
+                            guidance_schedule_func=guidance_schedule_func, control=control, reference_kv=reference_kv)
+    return torch.clip(vae_decoder.decode_first_stage(decoded), -1, 1)
