@@ -8,8 +8,8 @@
     apply_multi_controlnet                 controlnet.py:412-432
 
 The trunk is the encoder half of the UNet -- `unet_layout(cfg)["input"]` and `["middle"]`, with identical state-dict keys -- and
-runs through the code `UNetModel` runs (`unet.UNetTrunk`: the weight loading, `emb_projections`, `resblock`, `_block`).  What is
-ControlNet's own:
+runs through the code `UNetModel` runs (`unet.UNetTrunk`: the weight loading, `emb_projections`, `resblock`, `_block`, the input
+checks both share; loading and packing themselves are `modelbase`'s).  What is ControlNet's own:
   * the hint stem, eight 3x3 convolutions with nn.SiLU between them (strides 1,1,2,1,2,1,2,1; 8x down): one `ops.conv3x3_silu`
     launch per layer (csrc/controlnet.hip), the last with silu=False.  The 3-channel hint is padded to 4 channels that meet zero
     weights (`ops.pack_conv_weight`).
@@ -39,9 +39,6 @@ No checkpoint ships with the reference tree: parity is pinned with seeded weight
 """
 from __future__ import annotations
 
-import functools
-import math
-import os
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
@@ -50,6 +47,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from .modelbase import env_flag, is_f32_cuda, pad_channels4, random_tensors, wb
 from .unet import UNetTrunk, route_reference_kv, unet_layout, unet_tensors
 
 # the arguments of `get_controlnet_instance` (controlnet.py:376-390)
@@ -84,14 +82,13 @@ def controlnet_tensors(cfg: dict = SD_V15_CONTROLNET) -> List[Tuple[str, Tuple[i
     lay = controlnet_layout(cfg)
     trunk = unet_tensors(lay["cfg"])
     part = lambda p: [(k, s) for k, s in trunk if k.startswith(p)]
-    conv = lambda name, cout, cin, k: [(f"{name}.weight", (cout, cin, k, k)), (f"{name}.bias", (cout,))]
     out = part("time_embed.") + part("input_blocks.")
     for name, ch in lay["zero"][:-1]:
-        out += conv(name, ch, ch, 1)
+        wb(out, name, ch, ch, 1, 1)
     for name, cin, cout, _ in lay["hint"]:
-        out += conv(name, cout, cin, 3)
+        wb(out, name, cout, cin, 3, 3)
     out += part("middle_block.")
-    out += conv(lay["zero"][-1][0], lay["zero"][-1][1], lay["zero"][-1][1], 1)
+    wb(out, lay["zero"][-1][0], lay["zero"][-1][1], lay["zero"][-1][1], 1, 1)
     return out
 
 
@@ -100,22 +97,12 @@ def random_controlnet_state_dict(seed: int, cfg: dict = SD_V15_CONTROLNET) -> Di
     around 1, small biases.  The convolutions the reference wraps in `zero_module` (`zero_convs.*`, `input_hint_block.14`,
     `middle_block_out`, and the trunk's `out_layers.3` / `proj_out`) are NOT zeroed: zeroed, every residual would be zero (the
     reason unet.py gives)."""
-    g = torch.Generator().manual_seed(int(seed) + 49979687)
-    sd = {}
-    for key, shape in controlnet_tensors(cfg):
-        if len(shape) >= 2:
-            sd[key] = torch.randn(shape, generator=g) * (1.0 / math.sqrt(math.prod(shape[1:])))
-        elif key.endswith(".weight"):                              # every 1-D weight is a norm's scale
-            sd[key] = 1.0 + 0.1 * torch.randn(shape, generator=g)
-        else:
-            sd[key] = 0.05 * torch.randn(shape, generator=g)
-    return sd
+    return random_tensors(controlnet_tensors(cfg), int(seed) + 49979687)
 
 
-@functools.lru_cache(maxsize=None)
 def _torch_glue() -> bool:
     """OFX_CNET_TORCH_GLUE=1 (A/B baseline and diagnostic, read once per process): the hint stem through torch.nn.functional."""
-    return os.environ.get("OFX_CNET_TORCH_GLUE", "") not in ("", "0")
+    return env_flag("OFX_CNET_TORCH_GLUE")
 
 
 class ControlNet(UNetTrunk):
@@ -149,8 +136,7 @@ class ControlNet(UNetTrunk):
     def hint_stem(self, hint: torch.Tensor) -> torch.Tensor:
         """`input_hint_block` (:164-180, :305): hint f32 [b,hint_channels,8h,8w] on the device -> guided_hint [b,h,w,model_channels]
         NHWC."""
-        if (not torch.is_tensor(hint) or not hint.is_cuda or hint.dtype != torch.float32 or hint.dim() != 4
-                or hint.shape[1] != self.hint_channels):
+        if not is_f32_cuda(hint, 4) or hint.shape[1] != self.hint_channels:
             raise RuntimeError(f"hint must be a CUDA float32 tensor [b,{self.hint_channels},H,W]")
         if self.stem_glue:
             g = hint
@@ -159,9 +145,7 @@ class ControlNet(UNetTrunk):
                 if i != len(self.layout["hint"]) - 1:
                     g = F.silu(g)
             return g.permute(0, 2, 3, 1).contiguous()
-        b, _, H, W = hint.shape
-        g = torch.zeros((b, H, W, self.hint_pad), dtype=torch.float32, device=hint.device)     # Cin padded to a multiple of 4
-        g[..., :self.hint_channels] = hint.permute(0, 2, 3, 1)
+        g = pad_channels4(hint.permute(0, 2, 3, 1), self.hint_channels)
         for i, (name, _, cout, stride) in enumerate(self.layout["hint"]):
             g = ops.conv3x3_silu(g, self.w[f"{name}.weight"], self.w[f"{name}.bias"], cout, stride=stride,
                                  silu=i != len(self.layout["hint"]) - 1)
@@ -169,26 +153,17 @@ class ControlNet(UNetTrunk):
 
     def _check_inputs(self, x, hint, timesteps, context):
         """Every check that needs no launch."""
-        if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != self.in_channels:
+        if not is_f32_cuda(x, 4) or x.shape[1] != self.in_channels:
             raise RuntimeError(f"x must be a CUDA float32 tensor [B,{self.in_channels},H,W]")
         B, _, H, W = x.shape
-        if (not torch.is_tensor(hint) or not hint.is_cuda or hint.dtype != torch.float32 or hint.dim() != 4
-                or hint.shape[1] != self.hint_channels or hint.shape[0] not in (1, B)):
+        if not is_f32_cuda(hint, 4) or hint.shape[1] != self.hint_channels or hint.shape[0] not in (1, B):
             raise RuntimeError(f"hint must be a CUDA float32 tensor [1 or {B},{self.hint_channels},H,W]")
         if H % self.divisor or W % self.divisor:
             raise ValueError(f"the latent's H and W must be multiples of {self.divisor}, got {H}x{W}")
         if tuple(hint.shape[2:]) != (HINT_SCALE * H, HINT_SCALE * W):
             raise ValueError(f"the hint must be {HINT_SCALE}x the latent: {HINT_SCALE * H}x{HINT_SCALE * W} for a {H}x{W} latent, got "
                              f"{hint.shape[2]}x{hint.shape[3]} (the reference fails in h += guided_hint)")
-        if not torch.is_tensor(timesteps) or timesteps.dim() != 1 or timesteps.shape[0] != B:
-            raise RuntimeError(f"timesteps must be a tensor [{B}]")
-        cd = int(self.cfg["context_dim"])
-        if context is not None and (not torch.is_tensor(context) or not context.is_cuda or context.dtype != torch.float32
-                                    or context.dim() != 3 or context.shape[0] != B or context.shape[2] != cd):
-            raise RuntimeError(f"context must be a CUDA float32 tensor [{B},M,{cd}]")
-        widest = 2 * max(int(m) for m in self.cfg["channel_mult"][:1]) * self.model_channels
-        if B * H * W * widest * 4 >= (1 << 31):
-            raise RuntimeError("an activation would pass 2 GiB (32-bit byte offsets in the convolution): slice the batch")
+        self._check_common(B, H, W, timesteps, context)
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor, hint: torch.Tensor, timesteps: torch.Tensor, context: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
@@ -198,12 +173,7 @@ class ControlNet(UNetTrunk):
         self._check_inputs(x, hint, timesteps, context)
         B = x.shape[0]
         guided = self.hint_stem(hint)
-        h = x.permute(0, 2, 3, 1)
-        if self.in_pad != self.in_channels:
-            xp = torch.zeros((B,) + tuple(h.shape[1:3]) + (self.in_pad,), dtype=torch.float32, device=x.device)
-            xp[..., :self.in_channels] = h
-            h = xp
-        h = h.contiguous()
+        h = pad_channels4(x.permute(0, 2, 3, 1), self.in_channels)
         emb_all = self.emb_projections(timesteps)
         ref_by_st = route_reference_kv((), self.n_transformers)
         kv_hists: list = []

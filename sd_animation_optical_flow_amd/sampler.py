@@ -31,6 +31,7 @@ import torch
 
 from . import ops
 from .handoff import prepare_inpaint_inputs
+from .modelbase import is_f32_cuda
 
 _NOT_BUILT = ("use_original_steps", "score_corrector", "quantize_denoised", "noise_dropout", "dynamic_threshold")
 
@@ -99,7 +100,7 @@ def decode_plan(sched: Dict[str, object], t_start: int, guidance_schedule_func: 
 
 
 def _latent(t, name, shape=None) -> torch.Tensor:
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or (shape is not None and tuple(t.shape) != tuple(shape)):
+    if not is_f32_cuda(t, 4) or (shape is not None and tuple(t.shape) != tuple(shape)):
         raise RuntimeError(f"{name} must be a CUDA float32 tensor {'[B,C,h,w]' if shape is None else tuple(shape)}")
     return t
 
@@ -238,7 +239,7 @@ class GuidedDDIMSampler:
         cd = int(unet.cfg["context_dim"])
 
         def ctx(t, name):
-            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 3 or t.shape[0] != B or t.shape[2] != cd:
+            if not is_f32_cuda(t, 3) or t.shape[0] != B or t.shape[2] != cd:
                 raise RuntimeError(f"{name} must be a CUDA float32 tensor [{B},M,{cd}]")
             return t
 
@@ -262,8 +263,7 @@ class GuidedDDIMSampler:
                 raise ValueError("step_noise: one tensor [t_start,B,4,h,w] (the q_sample noise), and with eta > 0 a 2-tuple whose second "
                                  "tensor is the DDIM noise")
             for t in parts:
-                if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32
-                                      or tuple(t.shape) != (t_start, B, Cz, h, w)):
+                if t is not None and (not is_f32_cuda(t, 5) or tuple(t.shape) != (t_start, B, Cz, h, w)):
                     raise RuntimeError(f"step_noise must be CUDA float32 [{t_start},{B},{Cz},{h},{w}]")
             qn = parts[0]
             dn = parts[1] if eta_on else None

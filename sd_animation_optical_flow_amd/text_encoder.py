@@ -27,6 +27,9 @@ bit-identical to `dedupe=False`: the GEMM's tile and split-K choice may depend o
 Only what guided_ldm_*_v15.yaml's FrozenCLIPEmbedder loads is built: quick_gelu, causal, pre-LN.  Not built: the BPE tokenizer
 (`encode` takes any object with the transformers tokenizer's call interface), the tagger, FrozenOpenCLIPEmbedder / T5.
 
+The checkpoint check (`load_clip_text_tensors` over `modelbase.load_tensors`), the packing of the weights and the GEMM call are
+`modelbase`'s, shared with the other SD-stage models; the two embedding tables are this module's own.
+
 OFX_CLIP_TORCH_GLUE=1 in the environment (read once per process; the A/B baseline and a diagnostic): the embedding and quick_gelu
 through torch ops instead of the two kernels.
 
@@ -35,15 +38,13 @@ No checkpoint ships with the reference tree: parity is pinned with seeded weight
 """
 from __future__ import annotations
 
-import functools
-import math
-import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
 
 from . import ops
+from .modelbase import DeviceModel, check_activation_bytes, env_flag, load_tensors, random_tensors, wb
 
 # CLIPTextConfig of openai/clip-vit-large-patch14, the `version` FrozenCLIPEmbedder defaults to
 SD_V15_CLIP_TEXT = dict(vocab=49408, width=768, heads=12, layers=12, intermediate=3072, positions=77)
@@ -84,36 +85,22 @@ def clip_text_tensors(cfg: dict = SD_V15_CLIP_TEXT) -> List[Tuple[str, Tuple[int
     W, I = c["width"], c["intermediate"]
     out: List[Tuple[str, Tuple[int, ...]]] = [("embeddings.token_embedding.weight", (c["vocab"], W)),
                                               ("embeddings.position_embedding.weight", (c["positions"], W))]
-
-    def wb(name, *shape):
-        out.append((f"{name}.weight", tuple(shape)))
-        out.append((f"{name}.bias", (shape[0],)))
-
     for i in range(c["layers"]):
         l = f"encoder.layers.{i}"
         for p in ("k_proj", "v_proj", "q_proj", "out_proj"):
-            wb(f"{l}.self_attn.{p}", W, W)
-        wb(f"{l}.layer_norm1", W)
-        wb(f"{l}.mlp.fc1", I, W)
-        wb(f"{l}.mlp.fc2", W, I)
-        wb(f"{l}.layer_norm2", W)
-    wb("final_layer_norm", W)
+            wb(out, f"{l}.self_attn.{p}", W, W)
+        wb(out, f"{l}.layer_norm1", W)
+        wb(out, f"{l}.mlp.fc1", I, W)
+        wb(out, f"{l}.mlp.fc2", W, I)
+        wb(out, f"{l}.layer_norm2", W)
+    wb(out, "final_layer_norm", W)
     return out
 
 
 def random_clip_text_state_dict(seed: int, cfg: dict = SD_V15_CLIP_TEXT) -> Dict[str, torch.Tensor]:
     """Seeded stand-in for the absent checkpoint, built like `random_controlnet_state_dict`: fan-in-scaled normal matrices (the two
     embedding tables among them), norm scales around 1, small biases."""
-    g = torch.Generator().manual_seed(int(seed) + 86028121)
-    sd = {}
-    for key, shape in clip_text_tensors(cfg):
-        if len(shape) >= 2:
-            sd[key] = torch.randn(shape, generator=g) * (1.0 / math.sqrt(math.prod(shape[1:])))
-        elif key.endswith(".weight"):                              # every 1-D weight is a LayerNorm's scale
-            sd[key] = 1.0 + 0.1 * torch.randn(shape, generator=g)
-        else:
-            sd[key] = 0.05 * torch.randn(shape, generator=g)
-    return sd
+    return random_tensors(clip_text_tensors(cfg), int(seed) + 86028121)
 
 
 def load_clip_text_tensors(state_dict: Dict[str, torch.Tensor], cfg: dict = SD_V15_CLIP_TEXT,
@@ -122,18 +109,9 @@ def load_clip_text_tensors(state_dict: Dict[str, torch.Tensor], cfg: dict = SD_V
     following `text_model.` (SD checkpoints carry it; the CLIPTextModel of transformers 5 does not).  `embeddings.position_ids` is
     ignored.  KeyError for a missing key, ValueError for a wrong shape.  Needs no device."""
     want = clip_text_tensors(cfg)
-    sd = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
-    if any(k.startswith("text_model.") for k in sd):
-        sd = {k[len("text_model."):]: v for k, v in sd.items() if k.startswith("text_model.")}
-    t32: Dict[str, torch.Tensor] = {}
-    for key, shape in want:
-        if key not in sd:
-            raise KeyError(f"CLIP text checkpoint lacks {prefix}[text_model.]{key}")
-        t = sd[key].detach().to(torch.float32).cpu()
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{prefix}{key}: shape {tuple(t.shape)} != {shape}")
-        t32[key] = t
-    return t32
+    if any(k.startswith(prefix + "text_model.") for k in state_dict):
+        prefix += "text_model."
+    return load_tensors(state_dict, want, prefix, "CLIP text")
 
 
 def chunk_tokens(raw: Sequence[Sequence[int]], bos: int, eos: int, pad: int, chunks: int = CHUNKS, chunk_len: int = CHUNK_LEN
@@ -159,13 +137,12 @@ def tokenize_prompts(texts: Sequence[str], tokenizer) -> torch.Tensor:
     return chunk_tokens(raw, tokenizer.bos_token_id, tokenizer.eos_token_id, tokenizer.pad_token_id)
 
 
-@functools.lru_cache(maxsize=None)
 def _torch_glue() -> bool:
     """OFX_CLIP_TORCH_GLUE=1 (A/B baseline and diagnostic, read once per process): the embedding and quick_gelu through torch ops."""
-    return os.environ.get("OFX_CLIP_TORCH_GLUE", "") not in ("", "0")
+    return env_flag("OFX_CLIP_TORCH_GLUE")
 
 
-class ClipTextEncoder:
+class ClipTextEncoder(DeviceModel):
     """`FrozenCLIPEmbedder` under `hack.hack_everything(clip_skip)` (inference) on a HIP device."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: dict = SD_V15_CLIP_TEXT, device="cuda",
@@ -181,29 +158,21 @@ class ClipTextEncoder:
         # clip_skip > 1, of the last layer's output otherwise; layers past the one used are not run
         self.layers_run = self.layers if self.clip_skip <= 1 else self.layers + 1 - self.clip_skip
         self.dedupe = bool(dedupe)
+        self.precision = "fp32"                                    # the arithmetic of every `_gemm`
         t32 = load_clip_text_tensors(state_dict, c, prefix)
-        if not torch.cuda.is_available():
-            raise RuntimeError("ClipTextEncoder needs a HIP device (no CPU fallback)")
-        self.device = torch.device(device)
+        self._use_device(device)
         # weights are laid out once: every Linear a packed 1x1 convolution operand [Cout, Kpad]; q_proj | k_proj | v_proj one
         # [3*width, width] operand with one concatenated bias; the two embedding tables stay the checkpoint's row-major tensors
-        self.w: Dict[str, torch.Tensor] = {}
-
-        def gemm(name, *parts):
-            w = torch.cat([t32[f"{p}.weight"].reshape(t32[f"{p}.weight"].shape[0], -1, 1, 1) for p in parts])
-            self.w[f"{name}.weight"] = ops.pack_conv_weight(w).to(self.device)
-            self.w[f"{name}.bias"] = torch.cat([t32[f"{p}.bias"] for p in parts]).contiguous().to(self.device)
-
         self.tok = t32["embeddings.token_embedding.weight"].contiguous().to(self.device)
         self.pos = t32["embeddings.position_embedding.weight"].contiguous().to(self.device)
         for i in range(self.layers):
             l = f"encoder.layers.{i}"
-            gemm(f"{l}.self_attn.qkv", f"{l}.self_attn.q_proj", f"{l}.self_attn.k_proj", f"{l}.self_attn.v_proj")
+            self._put_gemm(f"{l}.self_attn.qkv", t32, f"{l}.self_attn.q_proj", f"{l}.self_attn.k_proj", f"{l}.self_attn.v_proj", bias=True)
             for n in ("self_attn.out_proj", "mlp.fc1", "mlp.fc2"):
-                gemm(f"{l}.{n}", f"{l}.{n}")
+                self._put_gemm(f"{l}.{n}", t32, f"{l}.{n}", bias=True)
         for key, t in t32.items():
             if t.dim() == 1 and ("layer_norm" in key):
-                self.w[key] = t.contiguous().to(self.device)
+                self._put(key, t)
         self.torch_glue = _torch_glue()
         self._causal: Dict[int, torch.Tensor] = {}
         self.embed_calls = 0           # how often the embedding ran, and the rows (sequences * T) of its last run: what `dedupe` saves
@@ -215,15 +184,6 @@ class ClipTextEncoder:
         if T not in self._causal:
             self._causal[T] = torch.full((T, T), float("-inf"), dtype=torch.float32).triu(1).to(self.device)
         return self._causal[T]
-
-    def _gemm(self, name: str, x: torch.Tensor, addend: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x [S, T, K] -> x W^T + bias (+ addend) [S, T, Cout]: a 1x1 convolution over the token rows."""
-        S, T, K = x.shape
-        w = self.w[f"{name}.weight"]
-        co = w.shape[0]
-        out = ops.conv2d_nhwc(x.view(S, 1, T, K), w, 1, 1, co, shift=self.w[f"{name}.bias"],
-                              addend=None if addend is None else addend.view(S, 1, T, co))
-        return out.view(S, T, co)
 
     def _layernorm(self, name: str, x: torch.Tensor) -> torch.Tensor:
         return ops.layernorm(x, self.w[f"{name}.weight"], self.w[f"{name}.bias"], LN_EPS)
@@ -245,11 +205,11 @@ class ClipTextEncoder:
         """CLIPEncoderLayer.forward on x [S, T, width]: the 8 launches of the module docstring."""
         l = f"encoder.layers.{i}"
         W = self.width
-        qkv = self._gemm(f"{l}.self_attn.qkv", self._layernorm(f"{l}.layer_norm1", x))
+        qkv = self._gemm(f"{l}.self_attn.qkv", self._layernorm(f"{l}.layer_norm1", x), True)
         a = ops.attention_bnhd(qkv[..., :W], qkv[..., W:2 * W], qkv[..., 2 * W:], self.heads, bias=bias, scale=self.d_head ** -0.5)
-        x = self._gemm(f"{l}.self_attn.out_proj", a, addend=x)
-        m = self._gemm(f"{l}.mlp.fc1", self._layernorm(f"{l}.layer_norm2", x))
-        return self._gemm(f"{l}.mlp.fc2", self._quick_gelu_(m), addend=x)
+        x = self._gemm(f"{l}.self_attn.out_proj", a, True, addend=x)
+        m = self._gemm(f"{l}.mlp.fc1", self._layernorm(f"{l}.layer_norm2", x), True)
+        return self._gemm(f"{l}.mlp.fc2", self._quick_gelu_(m), True, addend=x)
 
     # ---- forward --------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -281,8 +241,8 @@ class ClipTextEncoder:
         S, T = dev_ids.shape
         if S == 0 or T == 0 or T > self.positions:
             raise ValueError(f"ids [S,T] need S >= 1 and 1 <= T <= {self.positions}, got {(S, T)}")
-        if S * T * max(self.cfg["intermediate"], 3 * self.width) * 4 >= (1 << 31):
-            raise RuntimeError("an activation would pass 2 GiB (32-bit byte offsets in the GEMM): slice the sequences")
+        check_activation_bytes(S * T * max(self.cfg["intermediate"], 3 * self.width) * 4,
+                               "an activation would pass 2 GiB (32-bit byte offsets in the GEMM): slice the sequences")
         bias = self.causal_bias(T)
         x = self._embed(dev_ids)
         hs = [x]

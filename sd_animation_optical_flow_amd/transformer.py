@@ -30,21 +30,20 @@ torch.nn.functional, attention through permute + `ops.attention`, i.e. the glue 
 does not take (`FUSED_HEAD_SIZES`) go the permute + `ops.attention` way on their own.
 
 State-dict keys are the reference's (`use_linear=False`, the conv `proj_in` / `proj_out` that guided_ldm_*_v15.yaml builds); a
-full-checkpoint prefix such as `model.diffusion_model.input_blocks.1.1.` goes through `prefix`.  No checkpoint ships with the
+full-checkpoint prefix such as `model.diffusion_model.input_blocks.1.1.` goes through `prefix`.  The checkpoint check, the packing
+of the weights (several Linears side by side as one 1x1 operand) and the GEMM call are `modelbase`'s.  No checkpoint ships with the
 reference tree: parity is pinned with seeded weights loaded into the reference's own module
 (tests/golden/make_golden_transformer.py).
 """
 from __future__ import annotations
 
-import functools
-import math
-import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
 
 from . import ops
+from .modelbase import DeviceModel, check_activation_bytes, env_flag, is_f32_cuda, load_tensors, random_tensors, wb
 
 FUSED_HEAD_SIZES = (40, 64, 80, 128, 160)      # ofx_attention_flash_ok (csrc/attn_flash.hip)
 # `precision=` of SpatialTransformer / UNetModel: the arithmetic of every `ops.conv2d_nhwc` contraction (weights stay plain fp32)
@@ -66,27 +65,23 @@ def spatial_transformer_tensors(in_channels: int, n_heads: int, d_head: int, con
     ctx = inner if context_dim is None else int(context_dim)
     out: List[Tuple[str, Tuple[int, ...]]] = []
 
-    def wb(name, *shape):
-        out.append((f"{name}.weight", tuple(shape)))
-        out.append((f"{name}.bias", (shape[0],)))
-
     def attn(name, kv_dim):
         out.append((f"{name}.to_q.weight", (inner, inner)))
         out.append((f"{name}.to_k.weight", (inner, kv_dim)))
         out.append((f"{name}.to_v.weight", (inner, kv_dim)))
-        wb(f"{name}.to_out.0", inner, inner)
+        wb(out, f"{name}.to_out.0", inner, inner)
 
-    wb("norm", in_channels)
-    wb("proj_in", inner, in_channels, 1, 1)
+    wb(out, "norm", in_channels)
+    wb(out, "proj_in", inner, in_channels, 1, 1)
     for i in range(depth):
         blk = f"transformer_blocks.{i}"
         attn(f"{blk}.attn1", inner)
-        wb(f"{blk}.ff.net.0.proj", 8 * inner, inner)            # FeedForward(mult=4, glu=True): values and gates
-        wb(f"{blk}.ff.net.2", inner, 4 * inner)
+        wb(out, f"{blk}.ff.net.0.proj", 8 * inner, inner)       # FeedForward(mult=4, glu=True): values and gates
+        wb(out, f"{blk}.ff.net.2", inner, 4 * inner)
         attn(f"{blk}.attn2", ctx)
         for n in ("norm1", "norm2", "norm3"):
-            wb(f"{blk}.{n}", inner)
-    wb("proj_out", in_channels, inner, 1, 1)
+            wb(out, f"{blk}.{n}", inner)
+    wb(out, "proj_out", in_channels, inner, 1, 1)
     return out
 
 
@@ -94,23 +89,16 @@ def random_spatial_transformer_state_dict(seed: int, in_channels: int, n_heads: 
                                           depth: int = 1) -> Dict[str, torch.Tensor]:
     """Seeded stand-in for the absent checkpoint: fan-in-scaled normal weights, norm scales around 1, small biases.  `proj_out` is
     NOT zeroed (the reference zero-initialises it before training, :506; zeroed, the module would be the identity)."""
-    g = torch.Generator().manual_seed(int(seed) + 15485863)
-    sd = {}
-    for key, shape in spatial_transformer_tensors(in_channels, n_heads, d_head, context_dim, depth):
-        if len(shape) >= 2:
-            sd[key] = torch.randn(shape, generator=g) * (1.0 / math.sqrt(shape[1]))
-        elif key.split(".")[-2].startswith("norm") and key.endswith(".weight"):
-            sd[key] = 1.0 + 0.1 * torch.randn(shape, generator=g)
-        else:
-            sd[key] = 0.05 * torch.randn(shape, generator=g)
-    return sd
+    return random_tensors(spatial_transformer_tensors(in_channels, n_heads, d_head, context_dim, depth), int(seed) + 15485863)
 
 
-@functools.lru_cache(maxsize=None)
 def _torch_glue() -> bool:
     """OFX_ST_TORCH_GLUE=1 (A/B baseline and diagnostic, read once per process): LayerNorm / GEGLU through torch.nn.functional and
     attention through permute + `ops.attention`."""
-    return os.environ.get("OFX_ST_TORCH_GLUE", "") not in ("", "0")
+    return env_flag("OFX_ST_TORCH_GLUE")
+
+
+_torch_glue.cache_clear = env_flag.cache_clear                     # the switch stays clearable where a test changes the environment
 
 
 def to_reference_layout(t: torch.Tensor, heads: int) -> torch.Tensor:
@@ -162,7 +150,7 @@ def plan_reference_kv(shapes: Sequence[Tuple[Tuple[int, ...], Tuple[int, ...]]],
                      f"count), or batch {B - 1} with exactly {N} tokens")
 
 
-class SpatialTransformer:
+class SpatialTransformer(DeviceModel):
     """`ldm.modules.attention.SpatialTransformer` (use_linear=False, inference) on a HIP device."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], n_heads: int, d_head: int, device="cuda", prefix: str = "",
@@ -176,9 +164,7 @@ class SpatialTransformer:
                 raise ValueError(f"attention_precision={attention_precision!r} needs d_head in {FUSED_HEAD_SIZES}, got {d_head}")
         if use_linear:
             raise NotImplementedError("use_linear=True (Linear proj_in / proj_out) is not what guided_ldm_*_v15.yaml builds")
-        if not torch.cuda.is_available():
-            raise RuntimeError("SpatialTransformer needs a HIP device (no CPU fallback)")
-        self.device = torch.device(device)
+        self._use_device(device)                                   # this class asks for the device before it reads the checkpoint
         self.heads, self.d_head, self.inner = int(n_heads), int(d_head), int(n_heads) * int(d_head)
         sd = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
         if "norm.weight" not in sd or "proj_in.weight" not in sd:
@@ -191,47 +177,26 @@ class SpatialTransformer:
         self.context_dim = int(sd[kkey].shape[1]) if sd[kkey].dim() == 2 else -1
         if self.in_channels % 32 or self.inner % 4 or self.context_dim % 4:
             raise ValueError("in_channels must be a multiple of 32 (GroupNorm), n_heads * d_head and context_dim multiples of 4")
-        t32: Dict[str, torch.Tensor] = {}
-        for key, shape in spatial_transformer_tensors(self.in_channels, self.heads, self.d_head, self.context_dim, self.depth):
-            if key not in sd:
-                raise KeyError(f"SpatialTransformer checkpoint lacks {prefix}{key}")
-            t = sd[key].detach().to(torch.float32).cpu()
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError(f"{prefix}{key}: shape {tuple(t.shape)} != {shape}")
-            t32[key] = t
+        t32 = load_tensors(state_dict, spatial_transformer_tensors(self.in_channels, self.heads, self.d_head, self.context_dim, self.depth),
+                           prefix, "SpatialTransformer")
         # weights are laid out once: every Linear a 1x1 convolution operand [Cout, Kpad]; to_q | to_k | to_v of the self-attention
         # (no bias, one input) one [3*inner, inner] operand, to_k | to_v of the cross-attention one [2*inner, context_dim] operand
-        self.w: Dict[str, torch.Tensor] = {}
-
-        def gemm(name, *parts):
-            w = torch.cat([t32[p].reshape(t32[p].shape[0], t32[p].shape[1], 1, 1) for p in parts])
-            self.w[name] = ops.pack_conv_weight(w).to(self.device)
-
         for key, t in t32.items():
             if t.dim() == 1:
-                self.w[key] = t.contiguous().to(self.device)
-        gemm("proj_in.weight", "proj_in.weight")
-        gemm("proj_out.weight", "proj_out.weight")
+                self._put(key, t)
+        self._put_gemm("proj_in", t32, "proj_in")
+        self._put_gemm("proj_out", t32, "proj_out")
         for i in range(self.depth):
             b = f"transformer_blocks.{i}"
-            gemm(f"{b}.attn1.to_qkv.weight", f"{b}.attn1.to_q.weight", f"{b}.attn1.to_k.weight", f"{b}.attn1.to_v.weight")
-            gemm(f"{b}.attn2.to_q.weight", f"{b}.attn2.to_q.weight")
-            gemm(f"{b}.attn2.to_kv.weight", f"{b}.attn2.to_k.weight", f"{b}.attn2.to_v.weight")
+            self._put_gemm(f"{b}.attn1.to_qkv", t32, f"{b}.attn1.to_q", f"{b}.attn1.to_k", f"{b}.attn1.to_v")
+            self._put_gemm(f"{b}.attn2.to_q", t32, f"{b}.attn2.to_q")
+            self._put_gemm(f"{b}.attn2.to_kv", t32, f"{b}.attn2.to_k", f"{b}.attn2.to_v")
             for n in ("attn1.to_out.0", "attn2.to_out.0", "ff.net.0.proj", "ff.net.2"):
-                gemm(f"{b}.{n}.weight", f"{b}.{n}.weight")
+                self._put_gemm(f"{b}.{n}", t32, f"{b}.{n}")
         self.torch_glue = _torch_glue()
         self.fused_attention = (not self.torch_glue) and self.d_head in FUSED_HEAD_SIZES
 
     # ---- building blocks ------------------------------------------------------------------------------------------
-    def _gemm(self, name: str, x: torch.Tensor, bias: bool = False, addend: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x [B, N, K] -> x W^T (+ bias) (+ addend) [B, N, Cout]: a 1x1 convolution over the token rows."""
-        B, N, K = x.shape
-        w = self.w[f"{name}.weight"]
-        co = w.shape[0]
-        out = ops.conv2d_nhwc(x.view(B, 1, N, K), w, 1, 1, co, shift=self.w[f"{name}.bias"] if bias else None,
-                              addend=None if addend is None else addend.view(B, 1, N, co), precision=self.precision)
-        return out.view(B, N, co)
-
     def _layernorm(self, name: str, x: torch.Tensor) -> torch.Tensor:
         if self.torch_glue:
             return F.layer_norm(x, (x.shape[-1],), self.w[f"{name}.weight"], self.w[f"{name}.bias"], 1e-5)
@@ -279,7 +244,7 @@ class SpatialTransformer:
         inner = self.inner
         B, N, _ = x.shape
         # self-attention: one GEMM for q | k | v, the attention reads its thirds in place
-        qkv = self._gemm(f"{b}.attn1.to_qkv", self._layernorm(f"{b}.norm1", x))
+        qkv = self._gemm(f"{b}.attn1.to_qkv", self._layernorm(f"{b}.norm1", x), False)
         q, k, v = qkv[..., :inner], qkv[..., inner:2 * inner], qkv[..., 2 * inner:]
         kv_hist = (k.contiguous(), v.contiguous())                 # the block's own K/V, recorded before any replacement (:353)
         if ref is None:
@@ -291,16 +256,16 @@ class SpatialTransformer:
             a = torch.empty((B, N, inner), dtype=torch.float32, device=x.device)
             self._attention(q[:1], k[:1], v[:1], out=a[:1])
             self._attention(q[1:], ref[1], ref[2], out=a[1:])
-        x = self._gemm(f"{b}.attn1.to_out.0", a, bias=True, addend=x)
+        x = self._gemm(f"{b}.attn1.to_out.0", a, True, addend=x)
         # cross-attention (a second self-attention without context, :467)
         hn = self._layernorm(f"{b}.norm2", x)
         src = hn if context is None else context
-        kv = self._gemm(f"{b}.attn2.to_kv", src)
-        a = self._attention(self._gemm(f"{b}.attn2.to_q", hn), kv[..., :inner], kv[..., inner:])
-        x = self._gemm(f"{b}.attn2.to_out.0", a, bias=True, addend=x)
+        kv = self._gemm(f"{b}.attn2.to_kv", src, False)
+        a = self._attention(self._gemm(f"{b}.attn2.to_q", hn, False), kv[..., :inner], kv[..., inner:])
+        x = self._gemm(f"{b}.attn2.to_out.0", a, True, addend=x)
         # feed-forward: Linear -> GEGLU -> Linear (:59-76)
-        g = self._geglu(self._gemm(f"{b}.ff.net.0.proj", self._layernorm(f"{b}.norm3", x), bias=True))
-        x = self._gemm(f"{b}.ff.net.2", g, bias=True, addend=x)
+        g = self._geglu(self._gemm(f"{b}.ff.net.0.proj", self._layernorm(f"{b}.norm3", x), True))
+        x = self._gemm(f"{b}.ff.net.2", g, True, addend=x)
         return x, kv_hist
 
     def _contexts(self, context, B: int) -> List[Optional[torch.Tensor]]:
@@ -315,7 +280,7 @@ class SpatialTransformer:
                     raise ValueError(f"context=None needs context_dim == n_heads * d_head, this module has {self.context_dim}")
                 out.append(None)
                 continue
-            if not torch.is_tensor(c) or not c.is_cuda or c.dtype != torch.float32 or c.dim() != 3 or c.shape[0] != B or c.shape[2] != self.context_dim:
+            if not is_f32_cuda(c, 3) or c.shape[0] != B or c.shape[2] != self.context_dim:
                 raise RuntimeError(f"context must be a CUDA float32 tensor [{B},M,{self.context_dim}]")
             out.append(c.contiguous())
         return out
@@ -323,16 +288,18 @@ class SpatialTransformer:
     @torch.no_grad()
     def forward_nhwc(self, x: torch.Tensor, context=None, reference_kv=()) -> Tuple[torch.Tensor, List[Tuple[torch.Tensor, torch.Tensor]]]:
         """`forward` on NHWC: x f32 [B,h,w,C] on the device -> (out [B,h,w,C], kv_hists)."""
-        if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[3] != self.in_channels:
+        if not is_f32_cuda(x, 4) or x.shape[3] != self.in_channels:
             raise RuntimeError(f"x must be a CUDA float32 tensor with {self.in_channels} channels")
         x = x.contiguous()
         B, h, w, _ = x.shape
         N = h * w
-        if B * N * 8 * self.inner * 4 >= (1 << 31):
-            raise RuntimeError("the feed-forward activation would pass 2 GiB (32-bit byte offsets in the GEMM): slice the batch")
+        check_activation_bytes(B * N * 8 * self.inner * 4,
+                               "the feed-forward activation would pass 2 GiB (32-bit byte offsets in the GEMM): slice the batch")
         ctxs = self._contexts(context, B)
         ref = self._reference_kv(reference_kv, B, N)               # raises before any launch
         t = ops.groupnorm(x, self.w["norm.weight"], self.w["norm.bias"], 32, 1e-6, False)
+        # proj_in / proj_out stay direct calls with constant keys: this forward is host-enqueue bound at the UNet's sizes, and
+        # `_conv` would add two name lookups to each (profiles/r30_model_base_rate.txt was measured with these lines)
         t = ops.conv2d_nhwc(t, self.w["proj_in.weight"], 1, 1, self.inner, shift=self.w["proj_in.bias"],
                             precision=self.precision).view(B, N, self.inner)
         kv_hists = []

@@ -43,15 +43,14 @@ possible before `groupnorm_cat` / `emb_linear` / `timestep_embedding` existed --
 torch broadcast add, the timestep path through torch.nn.functional.
 
 `UNetTrunk` is the part of the model `controlnet.ControlNet` shares: weight loading, the timestep path, `resblock`, `_block`.
+The checkpoint check, the packing of the weights, `_conv` and the seeded stand-in weights are `modelbase`'s, shared with the other
+SD-stage models; the `.folded` upsample operands and the side-by-side `emb_layers` are this module's own.
 
 No checkpoint ships with the reference tree: parity is pinned with seeded weights loaded into the reference's own module
 (tests/golden/make_golden_unet.py).
 """
 from __future__ import annotations
 
-import functools
-import math
-import os
 import warnings
 from typing import Dict, List, Optional, Tuple
 
@@ -59,6 +58,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from .modelbase import DeviceModel, check_activation_bytes, env_flag, is_f32_cuda, load_tensors, pad_channels4, random_tensors, wb
 from .transformer import FUSED_HEAD_SIZES, MODEL_PRECISIONS, SpatialTransformer, check_precision, plan_reference_kv, spatial_transformer_tensors
 
 # `unet_config` of guided_ldm_inpaint_v15.yaml (in_channels 9) / guided_ldm_v15.yaml (in_channels 4)
@@ -148,35 +148,30 @@ def unet_tensors(cfg: dict = SD_V15_UNET) -> List[Tuple[str, Tuple[int, ...]]]:
     c = lay["cfg"]
     mc, ted = int(c["model_channels"]), 4 * int(c["model_channels"])
     out: List[Tuple[str, Tuple[int, ...]]] = []
-
-    def wb(name, *shape):
-        out.append((f"{name}.weight", tuple(shape)))
-        out.append((f"{name}.bias", (shape[0],)))
-
-    wb("time_embed.0", ted, mc)
-    wb("time_embed.2", ted, ted)
+    wb(out, "time_embed.0", ted, mc)
+    wb(out, "time_embed.2", ted, ted)
     for l in _layers(lay):
         kind, name = l[0], l[1]
         if kind == "conv":
-            wb(name, l[3], l[2], 3, 3)
+            wb(out, name, l[3], l[2], 3, 3)
         elif kind == "res":
             cin, cout = l[2], l[3]
-            wb(f"{name}.in_layers.0", cin)
-            wb(f"{name}.in_layers.2", cout, cin, 3, 3)
-            wb(f"{name}.emb_layers.1", cout, ted)
-            wb(f"{name}.out_layers.0", cout)
-            wb(f"{name}.out_layers.3", cout, cout, 3, 3)
+            wb(out, f"{name}.in_layers.0", cin)
+            wb(out, f"{name}.in_layers.2", cout, cin, 3, 3)
+            wb(out, f"{name}.emb_layers.1", cout, ted)
+            wb(out, f"{name}.out_layers.0", cout)
+            wb(out, f"{name}.out_layers.3", cout, cout, 3, 3)
             if cin != cout:
-                wb(f"{name}.skip_connection", cout, cin, 1, 1)
+                wb(out, f"{name}.skip_connection", cout, cin, 1, 1)
         elif kind == "st":
             out.extend((f"{name}.{k}", s) for k, s in
                        spatial_transformer_tensors(l[2], l[3], l[4], int(c["context_dim"]), int(c["transformer_depth"])))
         elif kind == "down":
-            wb(f"{name}.op", l[2], l[2], 3, 3)
+            wb(out, f"{name}.op", l[2], l[2], 3, 3)
         else:
-            wb(f"{name}.conv", l[2], l[2], 3, 3)
-    wb("out.0", mc)
-    wb("out.2", int(c["out_channels"]), mc, 3, 3)
+            wb(out, f"{name}.conv", l[2], l[2], 3, 3)
+    wb(out, "out.0", mc)
+    wb(out, "out.2", int(c["out_channels"]), mc, 3, 3)
     return out
 
 
@@ -184,23 +179,13 @@ def random_unet_state_dict(seed: int, cfg: dict = SD_V15_UNET) -> Dict[str, torc
     """Seeded stand-in for the absent checkpoint: fan-in-scaled normal weights, norm scales around 1, small biases.  The
     convolutions the reference wraps in `zero_module` (`out_layers.3`, `out.2`, every `proj_out`) are NOT zeroed: zeroed, every
     ResBlock and transformer would be the identity and the model's output zero (the reason transformer.py gives)."""
-    g = torch.Generator().manual_seed(int(seed) + 32452843)
-    sd = {}
-    for key, shape in unet_tensors(cfg):
-        if len(shape) >= 2:
-            sd[key] = torch.randn(shape, generator=g) * (1.0 / math.sqrt(math.prod(shape[1:])))
-        elif key.endswith(".weight"):                              # every 1-D weight is a norm's scale
-            sd[key] = 1.0 + 0.1 * torch.randn(shape, generator=g)
-        else:
-            sd[key] = 0.05 * torch.randn(shape, generator=g)
-    return sd
+    return random_tensors(unet_tensors(cfg), int(seed) + 32452843)
 
 
-@functools.lru_cache(maxsize=None)
 def _torch_glue() -> bool:
     """OFX_UNET_TORCH_GLUE=1 (A/B baseline and diagnostic, read once per process): torch.cat + `ops.groupnorm`, the emb term as a
     torch broadcast add, the timestep path through torch.nn.functional."""
-    return os.environ.get("OFX_UNET_TORCH_GLUE", "") not in ("", "0")
+    return env_flag("OFX_UNET_TORCH_GLUE")
 
 
 def route_reference_kv(reference_kv, n_transformers: int) -> List[list]:
@@ -217,10 +202,11 @@ def route_reference_kv(reference_kv, n_transformers: int) -> List[list]:
     return [[(f[j][0], f[j][1]) for f in frames] for j in range(n_transformers)]
 
 
-class UNetTrunk:
-    """What `UNetModel` and `controlnet.ControlNet` share: the checkpoint check and the weight loading (`_setup`), the timestep path
-    (`emb_projections`), `resblock` and `_block`.  A subclass names its module tree (`_layout`), its tensors (`_tensors`) and the
-    layers it runs (`_trunk_layers`); ControlNet's trunk is the `input` and `middle` halves of the same layout, key for key."""
+class UNetTrunk(DeviceModel):
+    """What `UNetModel` and `controlnet.ControlNet` share: the checkpoint check and the weight loading (`_setup`, through
+    `modelbase`), the checks of what both take (`_check_common`), the timestep path (`emb_projections`), `resblock` and `_block`.
+    A subclass names its module tree (`_layout`), its tensors (`_tensors`) and the layers it runs (`_trunk_layers`); ControlNet's
+    trunk is the `input` and `middle` halves of the same layout, key for key."""
     _what = "UNet"
 
     @staticmethod
@@ -250,21 +236,11 @@ class UNetTrunk:
         for l in layers:
             if l[0] == "res" and len(l) == 6 and l[2] == l[3]:
                 raise NotImplementedError(f"{l[1]}: an identity skip over a concatenation is not built")
-        t32: Dict[str, torch.Tensor] = {}
-        for key, shape in self._tensors(c):                        # the checkpoint is checked before the device is asked for
-            if prefix + key not in state_dict:
-                raise KeyError(f"{self._what} checkpoint lacks {prefix}{key}")
-            t = state_dict[prefix + key].detach().to(torch.float32).cpu()
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError(f"{prefix}{key}: shape {tuple(t.shape)} != {shape}")
-            t32[key] = t
-        if not torch.cuda.is_available():
-            raise RuntimeError(f"{type(self).__name__} needs a HIP device (no CPU fallback)")
-        self.device = torch.device(device)
+        t32 = load_tensors(state_dict, self._tensors(c), prefix, self._what)   # the checkpoint is checked before the device is asked for
+        self._use_device(device)
         self.in_channels, self.out_channels, self.model_channels = int(c["in_channels"]), int(c["out_channels"]), mc
         self.in_pad = (self.in_channels + 3) // 4 * 4
         self.divisor = 2 ** (len(c["channel_mult"]) - 1)
-        self.w: Dict[str, torch.Tensor] = {}
         self.st: Dict[str, SpatialTransformer] = {}
         emb_w, emb_b, off = [], [], 0
         self.emb_slice: Dict[str, Tuple[int, int]] = {}            # ResBlock name -> (first column, columns) of the emb projections
@@ -291,26 +267,28 @@ class UNetTrunk:
         for key, t in t32.items():
             if any(key.startswith(n + ".") for n in self.st) or ".emb_layers." in key:
                 continue
-            if t.dim() == 4:
-                self.w[key] = ops.pack_conv_weight(t).to(self.device)          # [Cout, Kpad], Cin padded to a multiple of 4
-                if key.endswith(".conv.weight"):                               # Upsample: the four parity-folded 2x2 operands
-                    self.w[key + ".folded"] = ops.upconv2x_weight(t).to(self.device)
-            else:
-                self.w[key] = t.contiguous().to(self.device)
+            self._put(key, t)
+            if key.endswith(".conv.weight"):                                   # Upsample: the four parity-folded 2x2 operands
+                self.w[key + ".folded"] = ops.upconv2x_weight(t).to(self.device)
         # every ResBlock's emb_layers.1 as one [sum of Cout, 4 * model_channels] Linear
-        self.w["emb_layers.weight"] = torch.cat(emb_w).contiguous().to(self.device)
-        self.w["emb_layers.bias"] = torch.cat(emb_b).contiguous().to(self.device)
-        self.w["freqs"] = ops.timestep_freqs(mc).to(self.device)
+        self._put("emb_layers.weight", torch.cat(emb_w))
+        self._put("emb_layers.bias", torch.cat(emb_b))
+        self._put("freqs", ops.timestep_freqs(mc))
         self.torch_glue = _torch_glue()
         return t32
 
-    # ---- building blocks ------------------------------------------------------------------------------------------
-    def _conv(self, name: str, x: torch.Tensor, k: int, stride: int = 1, addend: Optional[torch.Tensor] = None,
-              x2: Optional[torch.Tensor] = None) -> torch.Tensor:
-        w = self.w[f"{name}.weight"]
-        return ops.conv2d_nhwc(x, w, k, k, w.shape[0], stride=stride, shift=self.w[f"{name}.bias"], addend=addend, x2=x2,
-                               precision=self.precision)
+    def _check_common(self, B, H, W, timesteps, context) -> None:
+        """The checks of timesteps [B], context [B,M,context_dim] and the widest activation of a BxHxW latent; no launch."""
+        if not torch.is_tensor(timesteps) or timesteps.dim() != 1 or timesteps.shape[0] != B:
+            raise RuntimeError(f"timesteps must be a tensor [{B}]")
+        cd = int(self.cfg["context_dim"])
+        if context is not None and (not is_f32_cuda(context, 3) or context.shape[0] != B or context.shape[2] != cd):
+            raise RuntimeError(f"context must be a CUDA float32 tensor [{B},M,{cd}]")
+        widest = 2 * max(int(m) for m in self.cfg["channel_mult"][:1]) * self.model_channels
+        check_activation_bytes(B * H * W * widest * 4,
+                               "an activation would pass 2 GiB (32-bit byte offsets in the convolution): slice the batch")
 
+    # ---- building blocks ------------------------------------------------------------------------------------------
     def _norm(self, name: str, x: torch.Tensor, x1: Optional[torch.Tensor] = None, e: Optional[torch.Tensor] = None,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """GroupNorm(32, eps 1e-5) + SiLU (`normalization` = GroupNorm32(32, channels), util.py; nn.SiLU)."""
@@ -393,15 +371,7 @@ class UNetModel(UNetTrunk):
         """Every check that needs no launch; -> (per-transformer reference K/V, control as NHWC views or None)."""
         if H % self.divisor or W % self.divisor:
             raise ValueError(f"the latent's H and W must be multiples of {self.divisor}, got {H}x{W} (the reference fails in th.cat)")
-        if not torch.is_tensor(timesteps) or timesteps.dim() != 1 or timesteps.shape[0] != B:
-            raise RuntimeError(f"timesteps must be a tensor [{B}]")
-        cd = int(self.cfg["context_dim"])
-        if context is not None and (not torch.is_tensor(context) or not context.is_cuda or context.dtype != torch.float32
-                                    or context.dim() != 3 or context.shape[0] != B or context.shape[2] != cd):
-            raise RuntimeError(f"context must be a CUDA float32 tensor [{B},M,{cd}]")
-        widest = 2 * max(int(m) for m in self.cfg["channel_mult"][:1]) * self.model_channels
-        if B * H * W * widest * 4 >= (1 << 31):
-            raise RuntimeError("an activation would pass 2 GiB (32-bit byte offsets in the convolution): slice the batch")
+        self._check_common(B, H, W, timesteps, context)
         ref_by_st = route_reference_kv(reference_kv, self.n_transformers)
         if reference_kv:
             # the shapes each transformer will see, checked here so that a bad entry raises before any launch
@@ -425,7 +395,7 @@ class UNetModel(UNetTrunk):
                 want.append((B, ch, H // ds, W // ds))
             want.append(want[-1])
             for i, (t, s) in enumerate(zip(ctl, want)):
-                if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != s:
+                if not is_f32_cuda(t, 4) or tuple(t.shape) != s:
                     raise ValueError(f"control[{i}] must be a CUDA float32 tensor {s}")
             ctl = [t.permute(0, 2, 3, 1) for t in ctl]
         return ref_by_st, ctl
@@ -439,20 +409,16 @@ class UNetModel(UNetTrunk):
         (the caller's duty; they meet zero weights, but a NaN there would spread), and is read in place: no allocation and no copy
         here, which is how `sampler.GuidedDDIMSampler.decode` keeps one input buffer for a whole loop.  x is not written to."""
         cin = self.in_pad if padded else self.in_channels
-        if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[3] != cin:
+        if not is_f32_cuda(x, 4) or x.shape[3] != cin:
             raise RuntimeError(f"x must be a CUDA float32 tensor with {cin} channels")
         if padded and not x.is_contiguous():
             raise RuntimeError("padded=True takes a contiguous [B,H,W,in_pad] tensor")
         B, H, W, _ = x.shape
         ref_by_st, ctl = self._check_inputs(B, H, W, timesteps, context, control, reference_kv)
-        if not padded and self.in_pad != self.in_channels:
-            xp = torch.zeros((B, H, W, self.in_pad), dtype=torch.float32, device=x.device)     # Cin padded to a multiple of 4
-            xp[..., :self.in_channels] = x
-            x = xp
+        h = x if padded else pad_channels4(x, self.in_channels)                       # a padded x was checked contiguous above
         emb_all = self.emb_projections(timesteps)
         kv_hists: List[Tuple[torch.Tensor, torch.Tensor]] = []
         hs = []
-        h = x.contiguous()
         for blk in self.layout["input"]:                                               # :779-782
             h = self._block(blk, h, emb_all, context, ref_by_st, kv_hists)
             hs.append(h)

@@ -19,77 +19,67 @@ The way back is `VaeDecoder`: `decode_first_stage` (ldm/models/diffusion/ddpm.py
 (nearest 2x + 3x3 convolution, model.py:43-58) is one `ofx_upconv2x` launch that never forms the upsampled map and contracts 4 taps
 per output instead of 9 (OFX_VAE_NO_UPCONV=1 in the environment, read once per process: `ofx_upsample2x_nearest_f32` +
 `ofx_conv2d` instead), and `ofx_decode_to_u8` makes the bytes.  Pinned the same way (tests/golden/make_golden_vae_decoder.py).
+
+Checkpoint loading, weight packing and the convolution call are `modelbase`'s, shared with the other SD-stage models.  Both classes
+check in the order the others do: configuration, then checkpoint, then device.  A checkpoint with a missing key or a wrong shape is
+a KeyError / ValueError on a machine without a device too (it used to be the RuntimeError about the device there); the decoder's
+4-row padding of `conv_out` and its folded upsample operands are this module's own.
 """
 from __future__ import annotations
 
-import functools
-import math
-import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import ops
+from .modelbase import DeviceModel, env_flag, is_f32_cuda, load_tensors, pad_channels4, random_tensors, wb
 
 SCALE_FACTOR = 0.18215
 SD_V1_CONFIG = dict(ch=128, ch_mult=(1, 2, 4, 4), num_res_blocks=2, in_channels=3, z_channels=4, double_z=True, embed_dim=4)
+
+
+def _resblock_wb(out, name, ci, co):
+    """The tensors of a ResnetBlock (model.py:97-127), for the encoder's and the decoder's lists alike."""
+    wb(out, f"{name}.norm1", ci)
+    wb(out, f"{name}.conv1", co, ci, 3, 3)
+    wb(out, f"{name}.norm2", co)
+    wb(out, f"{name}.conv2", co, co, 3, 3)
+    if ci != co:
+        wb(out, f"{name}.nin_shortcut", co, ci, 1, 1)
+
+
+def _attn_wb(out, name, c):
+    wb(out, f"{name}.norm", c)
+    for nm in ("q", "k", "v", "proj_out"):
+        wb(out, f"{name}.{nm}", c, c, 1, 1)
 
 
 def encoder_tensors(cfg: dict = SD_V1_CONFIG) -> List[Tuple[str, Tuple[int, ...]]]:
     """(key, shape) of every tensor of `encoder.*` + `quant_conv.*` for a ddconfig, in module order."""
     ch, mult, nres = cfg["ch"], tuple(cfg["ch_mult"]), cfg["num_res_blocks"]
     out: List[Tuple[str, Tuple[int, ...]]] = []
-
-    def conv(name, co, ci, k):
-        out.append((f"{name}.weight", (co, ci, k, k)))
-        out.append((f"{name}.bias", (co,)))
-
-    def norm(name, c):
-        out.append((f"{name}.weight", (c,)))
-        out.append((f"{name}.bias", (c,)))
-
-    def resblock(name, ci, co):
-        norm(f"{name}.norm1", ci)
-        conv(f"{name}.conv1", co, ci, 3)
-        norm(f"{name}.norm2", co)
-        conv(f"{name}.conv2", co, co, 3)
-        if ci != co:
-            conv(f"{name}.nin_shortcut", co, ci, 1)
-
-    conv("encoder.conv_in", ch, cfg["in_channels"], 3)
+    wb(out, "encoder.conv_in", ch, cfg["in_channels"], 3, 3)
     block_in = ch
     for lvl, m in enumerate(mult):
         block_out = ch * m
         for j in range(nres):
-            resblock(f"encoder.down.{lvl}.block.{j}", block_in, block_out)
+            _resblock_wb(out, f"encoder.down.{lvl}.block.{j}", block_in, block_out)
             block_in = block_out
         if lvl != len(mult) - 1:
-            conv(f"encoder.down.{lvl}.downsample.conv", block_in, block_in, 3)
-    resblock("encoder.mid.block_1", block_in, block_in)
-    norm("encoder.mid.attn_1.norm", block_in)
-    for nm in ("q", "k", "v", "proj_out"):
-        conv(f"encoder.mid.attn_1.{nm}", block_in, block_in, 1)
-    resblock("encoder.mid.block_2", block_in, block_in)
-    norm("encoder.norm_out", block_in)
+            wb(out, f"encoder.down.{lvl}.downsample.conv", block_in, block_in, 3, 3)
+    _resblock_wb(out, "encoder.mid.block_1", block_in, block_in)
+    _attn_wb(out, "encoder.mid.attn_1", block_in)
+    _resblock_wb(out, "encoder.mid.block_2", block_in, block_in)
+    wb(out, "encoder.norm_out", block_in)
     zc = cfg["z_channels"] * (2 if cfg["double_z"] else 1)
-    conv("encoder.conv_out", zc, block_in, 3)
-    conv("quant_conv", 2 * cfg["embed_dim"], zc, 1)
+    wb(out, "encoder.conv_out", zc, block_in, 3, 3)
+    wb(out, "quant_conv", 2 * cfg["embed_dim"], zc, 1, 1)
     return out
 
 
 def random_vae_state_dict(seed: int = 0, cfg: dict = SD_V1_CONFIG) -> Dict[str, torch.Tensor]:
     """Seeded stand-in for the absent checkpoint: fan-in-scaled normal convolution weights, norm scales around 1."""
-    g = torch.Generator().manual_seed(int(seed) + 7919)
-    sd = {}
-    for key, shape in encoder_tensors(cfg):
-        if len(shape) == 4:
-            fan_in = shape[1] * shape[2] * shape[3]
-            sd[key] = torch.randn(shape, generator=g) * (1.0 / math.sqrt(fan_in))
-        elif ".norm" in key and key.endswith(".weight"):
-            sd[key] = 1.0 + 0.1 * torch.randn(shape, generator=g)
-        else:
-            sd[key] = 0.05 * torch.randn(shape, generator=g)
-    return sd
+    return random_tensors(encoder_tensors(cfg), int(seed) + 7919)
 
 
 def decoder_tensors(cfg: dict = SD_V1_CONFIG) -> List[Tuple[str, Tuple[int, ...]]]:
@@ -97,30 +87,11 @@ def decoder_tensors(cfg: dict = SD_V1_CONFIG) -> List[Tuple[str, Tuple[int, ...]
     levels are built from the coarsest down, `up` is indexed from the finest up)."""
     ch, mult, nres = cfg["ch"], tuple(cfg["ch_mult"]), cfg["num_res_blocks"]
     out: List[Tuple[str, Tuple[int, ...]]] = []
-
-    def conv(name, co, ci, k):
-        out.append((f"{name}.weight", (co, ci, k, k)))
-        out.append((f"{name}.bias", (co,)))
-
-    def norm(name, c):
-        out.append((f"{name}.weight", (c,)))
-        out.append((f"{name}.bias", (c,)))
-
-    def resblock(name, ci, co):
-        norm(f"{name}.norm1", ci)
-        conv(f"{name}.conv1", co, ci, 3)
-        norm(f"{name}.norm2", co)
-        conv(f"{name}.conv2", co, co, 3)
-        if ci != co:
-            conv(f"{name}.nin_shortcut", co, ci, 1)
-
     block_in = ch * mult[-1]
-    conv("decoder.conv_in", block_in, cfg["z_channels"], 3)
-    resblock("decoder.mid.block_1", block_in, block_in)
-    norm("decoder.mid.attn_1.norm", block_in)
-    for nm in ("q", "k", "v", "proj_out"):
-        conv(f"decoder.mid.attn_1.{nm}", block_in, block_in, 1)
-    resblock("decoder.mid.block_2", block_in, block_in)
+    wb(out, "decoder.conv_in", block_in, cfg["z_channels"], 3, 3)
+    _resblock_wb(out, "decoder.mid.block_1", block_in, block_in)
+    _attn_wb(out, "decoder.mid.attn_1", block_in)
+    _resblock_wb(out, "decoder.mid.block_2", block_in, block_in)
     io = {}
     for lvl in reversed(range(len(mult))):
         io[lvl] = (block_in, ch * mult[lvl])
@@ -128,73 +99,41 @@ def decoder_tensors(cfg: dict = SD_V1_CONFIG) -> List[Tuple[str, Tuple[int, ...]
     for lvl in range(len(mult)):
         ci, co = io[lvl]
         for j in range(nres + 1):
-            resblock(f"decoder.up.{lvl}.block.{j}", ci if j == 0 else co, co)
+            _resblock_wb(out, f"decoder.up.{lvl}.block.{j}", ci if j == 0 else co, co)
         if lvl != 0:
-            conv(f"decoder.up.{lvl}.upsample.conv", co, co, 3)
-    norm("decoder.norm_out", block_in)
-    conv("decoder.conv_out", cfg.get("out_ch", 3), block_in, 3)
-    conv("post_quant_conv", cfg["z_channels"], cfg["embed_dim"], 1)
+            wb(out, f"decoder.up.{lvl}.upsample.conv", co, co, 3, 3)
+    wb(out, "decoder.norm_out", block_in)
+    wb(out, "decoder.conv_out", cfg.get("out_ch", 3), block_in, 3, 3)
+    wb(out, "post_quant_conv", cfg["z_channels"], cfg["embed_dim"], 1, 1)
     return out
-
-
-def _random_tensors(tensors, g: torch.Generator) -> Dict[str, torch.Tensor]:
-    sd = {}
-    for key, shape in tensors:
-        if len(shape) == 4:
-            fan_in = shape[1] * shape[2] * shape[3]
-            sd[key] = torch.randn(shape, generator=g) * (1.0 / math.sqrt(fan_in))
-        elif ".norm" in key and key.endswith(".weight"):
-            sd[key] = 1.0 + 0.1 * torch.randn(shape, generator=g)
-        else:
-            sd[key] = 0.05 * torch.randn(shape, generator=g)
-    return sd
 
 
 def random_vae_decoder_state_dict(seed: int = 0, cfg: dict = SD_V1_CONFIG) -> Dict[str, torch.Tensor]:
     """Seeded stand-in for the decoder half of the absent checkpoint, drawn from a generator of its own (the encoder's tensors of
     `random_vae_state_dict` do not depend on it)."""
-    return _random_tensors(decoder_tensors(cfg), torch.Generator().manual_seed(int(seed) + 104729))
+    return random_tensors(decoder_tensors(cfg), int(seed) + 104729)
 
 
-@functools.lru_cache(maxsize=None)
 def _no_upconv() -> bool:
     """OFX_VAE_NO_UPCONV=1 (diagnostic, read once per process): the decoder's Upsample layers run unfused."""
-    return os.environ.get("OFX_VAE_NO_UPCONV", "") not in ("", "0")
+    return env_flag("OFX_VAE_NO_UPCONV")
 
 
-class _VaeBlocks:
-    """What `Encoder` and `Decoder` share (model.py): weights on the device in the kernels' layouts, and the convolution, GroupNorm,
-    ResnetBlock and AttnBlock calls."""
+class _VaeBlocks(DeviceModel):
+    """What `Encoder` and `Decoder` share (model.py): weights on the device in the kernels' layouts (`modelbase.DeviceModel`), and
+    the GroupNorm, ResnetBlock and AttnBlock calls."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], tensors, device, cfg: dict, scale_factor: float):
-        if not torch.cuda.is_available():
-            raise RuntimeError(f"{type(self).__name__} needs a HIP device (no CPU fallback)")
-        self.cfg, self.device, self.scale_factor = dict(cfg), torch.device(device), float(scale_factor)
-        sd = {}
-        for k, v in state_dict.items():
-            k = k[len("first_stage_model."):] if k.startswith("first_stage_model.") else k
-            sd[k] = v
-        self.w: Dict[str, torch.Tensor] = {}
-        for key, shape in tensors:
-            if key not in sd:
-                raise KeyError(f"VAE checkpoint lacks {key}")
-            t = sd[key].detach().to(torch.float32)
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError(f"{key}: shape {tuple(t.shape)} != {shape}")
-            self._load(key, t)
-
-    def _load(self, key: str, t: torch.Tensor) -> None:
-        if t.dim() == 4:
-            self.w[key] = ops.pack_conv_weight(t).to(self.device)           # [Cout, Kpad], Cin padded to a multiple of 4
-        else:
-            self.w[key] = t.contiguous().to(self.device)
+        self.cfg, self.scale_factor = dict(cfg), float(scale_factor)
+        self.precision = "fp32"                                    # the arithmetic of every `_conv`
+        strip = len("first_stage_model.")                          # the prefix of full SD checkpoints, where a key has it
+        sd = {k[strip:] if k.startswith("first_stage_model.") else k: v for k, v in state_dict.items()}
+        t32 = load_tensors(sd, tensors, "", "VAE")                 # the checkpoint is checked before the device is asked for
+        self._use_device(device)
+        for key, t in t32.items():
+            self._put(key, t)
 
     # ---- building blocks (model.py line numbers) -----------------------------------------------------------
-    def _conv(self, name: str, x: torch.Tensor, k: int, stride: int = 1, addend: Optional[torch.Tensor] = None,
-              pad=None, out_hw=None) -> torch.Tensor:
-        w = self.w[f"{name}.weight"]
-        return ops.conv2d_nhwc(x, w, k, k, w.shape[0], stride=stride, shift=self.w[f"{name}.bias"], addend=addend, pad=pad, out_hw=out_hw)
-
     def _norm(self, name: str, x: torch.Tensor, silu: bool) -> torch.Tensor:
         return ops.groupnorm(x, self.w[f"{name}.weight"], self.w[f"{name}.bias"], 32, 1e-6, silu)
 
@@ -242,8 +181,7 @@ class VaeEncoder(_VaeBlocks):
         mb = self.max_batch(H, W)
         if B > mb:
             return torch.cat([self.encode_moments(image[b0:b0 + mb]) for b0 in range(0, B, mb)])
-        x = torch.zeros((B, H, W, 4), dtype=torch.float32, device=image.device)        # NHWC, channel 3 = 0 (Cin padded to 4)
-        x[..., :3] = image.permute(0, 2, 3, 1)
+        x = pad_channels4(image.permute(0, 2, 3, 1), self.cfg["in_channels"])          # NHWC, channel 3 = 0 (Cin padded to 4)
         h = self._conv("encoder.conv_in", x, 3)
         for lvl in range(len(self.cfg["ch_mult"])):
             for j in range(self.cfg["num_res_blocks"]):
@@ -282,13 +220,13 @@ class VaeDecoder(_VaeBlocks):
         # Upsample layers that run fused (level -> bool); OFX_VAE_NO_UPCONV=1 turns every one to the unfused pair
         self.fused_upsample = {lvl: not _no_upconv() for lvl in range(1, len(self.cfg["ch_mult"]))}
 
-    def _load(self, key: str, t: torch.Tensor) -> None:
+    def _put(self, key: str, t: torch.Tensor) -> None:
         if key == "decoder.conv_out.weight" and t.shape[0] % 4:
             # rows of 4 floats for the RGB map (the byte exit reads 16-byte pixels): output channels padded with zero weights
             t = torch.cat([t, t.new_zeros((4 - t.shape[0] % 4,) + tuple(t.shape[1:]))])
         elif key == "decoder.conv_out.bias" and t.shape[0] % 4:
             t = torch.cat([t, t.new_zeros((4 - t.shape[0] % 4,))])
-        super()._load(key, t)
+        super()._put(key, t)
         if key.endswith(".upsample.conv.weight"):
             self.w[key + ".folded"] = ops.upconv2x_weight(t).to(self.device)   # [4 parities, Cout, 4 taps, Cin]
 
@@ -327,7 +265,7 @@ class VaeDecoder(_VaeBlocks):
         return self._conv("decoder.conv_out", self._norm("decoder.norm_out", h, True), 3)
 
     def _check(self, z: torch.Tensor) -> None:
-        if not torch.is_tensor(z) or not z.is_cuda or z.dtype != torch.float32 or z.dim() != 4 or z.shape[1] != self.cfg["z_channels"]:
+        if not is_f32_cuda(z, 4) or z.shape[1] != self.cfg["z_channels"]:
             raise RuntimeError(f"z must be a CUDA float32 tensor [B,{self.cfg['z_channels']},h,w]")
         if self.cfg["embed_dim"] % 4 or self.cfg["z_channels"] % 4:
             raise RuntimeError("embed_dim and z_channels must be multiples of 4")
