@@ -376,63 +376,94 @@ int build_gru(ofx_raft* r, const std::map<std::string, HostTensor>& sd, const st
     return 0;
 }
 
+constexpr size_t SK_BYTES = 65536 + (size_t)1024 * 4 * 64 * 64 * sizeof(float);   // counters + 1024 tiles x 4 splits (conv.hip)
+
+// Where a convolution's epilogue leaves instance-norm partial sums (conv.hip); part == nullptr: it produces none
+struct StatsOut {
+    float* part = nullptr;
+    size_t cap = 0;
+};
+
+// One convolution of the engine, operand by operand.  A call site names the operands it uses (designated initialisers, in this order)
+// and nothing else; like ConvExtra (ofx_internal.h), nothing reaches the launch except through these fields.
+struct ConvArgs {
+    const float* in0 = nullptr; int ld0 = 0, c0 = 0;   // the K segments: in0 [.., c0] | in1 [.., c1]
+    const float* in1 = nullptr; int ld1 = 0, c1 = 0;
+    float* out = nullptr; int ldo = 0;
+    int B = 0, Hin = 0, Win = 0, stride = 1;
+    int act = OFX_ACT_NONE, epi = OFX_EPI_PLAIN;
+    const float* res = nullptr; int ldres = 0;
+    const float *nmean = nullptr, *nrstd = nullptr;
+    const float* addend = nullptr; int ldadd = 0;
+    float *aux_z = nullptr, *aux_rh = nullptr, *aux_h = nullptr; int ldh = 0;
+    float *aux_coords = nullptr, *aux_flow4 = nullptr;
+    int row_off = 0, rows = 0;                          // a slice of the weight's rows (rows == 0: all of them)
+    StatsOut stats;
+    hipEvent_t stop_event = nullptr;                    // rides on the kernel's dispatch packet (Streams::arm_*)
+};
+
+// What that one launch did with the two optional requests
+struct ConvDone {
+    int stats_rows = 0;        // rows per image in stats.part, 0 = not produced
+    bool stop_taken = false;   // the kernel carries stop_event (false: take the plain edge)
+};
+
+// What is per stream and per forward, and nothing per call
 struct Launcher {
     hipStream_t s;
-    int st = 0;
-    const float* addend = nullptr;   // consumed (and cleared) by the next conv() call
-    int ldadd = 0;
-    int precision = OFX_PREC_FP32;   // sticky: OFX_PREC_BF16X3 when the forward was asked for the split-bf16 mode
-    void* sk_ws = nullptr;           // split-K scratch of the stream this launcher feeds (null: never split)
-    size_t sk_bytes = 0;
-    float* stats_part = nullptr;     // consumed by the next conv(): instance-norm partial sums out of its epilogue (conv.hip)
-    size_t stats_floats = 0;
-    int stats_rows = 0;              // set by that conv(): rows per image in stats_part, 0 = not produced
-    hipEvent_t stop_event = nullptr; // consumed by the next conv(): rides on its kernel's dispatch packet (Streams::arm_*)
-    bool stop_taken = false;         // set by that conv(): the kernel carries the event (false: take the plain edge)
+    int st = 0;              // sticky: the first error; every later call is skipped
+    int precision;           // OFX_PREC_BF16X3 / _BF16X6 when the forward was asked for a split-bf16 mode
+    void* sk_ws;             // split-K scratch of the stream this launcher feeds (null: never split)
+    size_t sk_bytes;
+    explicit Launcher(hipStream_t s, int precision = OFX_PREC_FP32, void* sk_ws = nullptr)
+        : s(s), precision(precision), sk_ws(sk_ws), sk_bytes(sk_ws ? SK_BYTES : 0) {}
     // generic conv launch; all pointer plumbing in one place
-    void conv(const ConvW& c, const float* in0, int ld0, int c0, const float* in1, int ld1, int c1, float* out, int ldo,
-              int B, int Hin, int Win, int stride, int act, int epi = OFX_EPI_PLAIN, const float* res = nullptr,
-              int ldres = 0, const float* nmean = nullptr, const float* nrstd = nullptr, float* aux_z = nullptr,
-              float* aux_rh = nullptr, float* aux_h = nullptr, int ldh = 0, float* aux_coords = nullptr,
-              float* aux_flow4 = nullptr, int row_off = 0, int rows = 0) {
-        stop_taken = false;
-        if (st) return;
+    ConvDone conv(const ConvW& c, const ConvArgs& a) {
+        ConvDone done;
+        if (st) return done;
         ofx_conv_desc d{};
-        d.in0 = in0; d.ld0 = ld0; d.c0 = c0;
-        d.in1 = in1; d.ld1 = ld1; d.c1 = c1;
-        const int cout = rows ? rows : c.cout;
+        d.in0 = a.in0; d.ld0 = a.ld0; d.c0 = a.c0;
+        d.in1 = a.in1; d.ld1 = a.ld1; d.c1 = a.c1;
+        const int cout = a.rows ? a.rows : c.cout;
+        const bool whole = a.row_off == 0 && a.rows == 0;
         const bool wsplit = precision == OFX_PREC_BF16X3 && c.wsplit != nullptr;
         // (the three-piece format addresses its lo groups from the end of the whole matrix: row slices keep the on-the-fly split)
-        const bool wsplit3 = precision == OFX_PREC_BF16X6 && c.wsplit3 != nullptr && row_off == 0 && rows == 0;
-        d.w = wsplit3 ? c.wsplit3 : (wsplit ? c.wsplit : c.w) + (long)row_off * c.kpad;
-        d.scale = c.scale ? c.scale + row_off : nullptr;
-        d.shift = c.shift ? c.shift + row_off : nullptr;
-        d.out = out; d.ldo = ldo;
-        d.res = res; d.ldres = ldres;
-        d.nmean = nmean; d.nrstd = nrstd;
-        d.addend = addend; d.ldadd = ldadd;
-        addend = nullptr; ldadd = 0;
-        d.aux_z = aux_z; d.aux_rh = aux_rh; d.aux_h = aux_h; d.ldh = ldh;
-        d.aux_coords = aux_coords; d.aux_flow4 = aux_flow4;
-        d.B = B; d.Hin = Hin; d.Win = Win;
+        const bool wsplit3 = precision == OFX_PREC_BF16X6 && c.wsplit3 != nullptr && whole;
+        d.w = wsplit3 ? c.wsplit3 : (wsplit ? c.wsplit : c.w) + (long)a.row_off * c.kpad;
+        d.scale = c.scale ? c.scale + a.row_off : nullptr;
+        d.shift = c.shift ? c.shift + a.row_off : nullptr;
+        d.out = a.out; d.ldo = a.ldo;
+        d.res = a.res; d.ldres = a.ldres;
+        d.nmean = a.nmean; d.nrstd = a.nrstd;
+        d.addend = a.addend; d.ldadd = a.ldadd;
+        d.aux_z = a.aux_z; d.aux_rh = a.aux_rh; d.aux_h = a.aux_h; d.ldh = a.ldh;
+        d.aux_coords = a.aux_coords; d.aux_flow4 = a.aux_flow4;
+        d.B = a.B; d.Hin = a.Hin; d.Win = a.Win;
         const int padH = c.kh / 2, padW = c.kw / 2;
-        d.Hout = (Hin + 2 * padH - c.kh) / stride + 1;
-        d.Wout = (Win + 2 * padW - c.kw) / stride + 1;
-        d.Cout = cout; d.KH = c.kh; d.KW = c.kw; d.stride = stride; d.padH = padH; d.padW = padW;
-        d.act = act; d.epi = epi;
+        d.Hout = (a.Hin + 2 * padH - c.kh) / a.stride + 1;
+        d.Wout = (a.Win + 2 * padW - c.kw) / a.stride + 1;
+        d.Cout = cout; d.KH = c.kh; d.KW = c.kw; d.stride = a.stride; d.padH = padH; d.padW = padW;
+        d.act = a.act; d.epi = a.epi;
         d.precision = wsplit3 ? OFX_PREC_BF16X6_W : wsplit ? OFX_PREC_BF16X3_W : precision;
         d.splitk_ws = sk_ws; d.splitk_ws_bytes = sk_bytes;
-        d.wino_w = row_off == 0 && rows == 0 ? c.wino : nullptr;
-        d.wino4_w = row_off == 0 && rows == 0 ? c.wino4 : nullptr;
-        if (c0 + c1 != c.cin_pad) { st = OFX_EKEY; return; }
+        d.wino_w = whole ? c.wino : nullptr;
+        d.wino4_w = whole ? c.wino4 : nullptr;
+        if (a.c0 + a.c1 != c.cin_pad) { st = OFX_EKEY; return done; }
         ofx_prof_set_tag(c.name.c_str());
         ConvExtra x;
-        x.stats_part = stats_part; x.stats_cap = stats_floats; x.stats_rows = stats_part ? &stats_rows : nullptr;
-        x.stop_event = stop_event; x.stop_taken = &stop_taken;
-        stats_rows = 0;
+        x.stats_part = a.stats.part; x.stats_cap = a.stats.cap; x.stats_rows = a.stats.part ? &done.stats_rows : nullptr;
+        x.stop_event = a.stop_event; x.stop_taken = &done.stop_taken;
         st = ofx_conv2d_ex(&d, &x, s);
-        stats_part = nullptr; stop_event = nullptr;
         ofx_prof_set_tag(nullptr);
+        return done;
+    }
+    // net = tanh(cnet[:, :tanh_rows]), inp = relu(cnet[:, tanh_rows:]) (raft.py:111-114): the context encoder's last convolution as
+    // two row slices of one weight, the relu rows landing relu_off floats into the output row.  `a`: the operands both slices share
+    void conv_tanh_relu(const ConvW& c, ConvArgs a, int tanh_rows, int relu_off) {
+        a.act = OFX_ACT_TANH; a.rows = tanh_rows;
+        conv(c, a);
+        a.out += relu_off; a.act = OFX_ACT_RELU; a.row_off = tanh_rows; a.rows = c.cout - tanh_rows;
+        conv(c, a);
     }
 };
 
@@ -464,11 +495,8 @@ struct Streams {
     int join_armed(int i) const { OFX_HIP_CHECK(hipStreamWaitEvent(main, r->ev_join[i], 0)); return 0; }
 };
 
-constexpr size_t SK_BYTES = 65536 + (size_t)1024 * 4 * 64 * 64 * sizeof(float);   // counters + 1024 tiles x 4 splits (conv.hip)
-
 struct EncBufs {
     void* sk = nullptr;      // split-K scratch of the stream this encoder chain runs on
-    size_t sk_bytes = 0;
     float *x0, *X, *Y, *R1, *R2, *R3;
     float* stats;     // 6 x [chunk][128] floats (mean/rstd for up to 3 norms)
     float* scratch;   // inorm partial sums
@@ -484,10 +512,8 @@ static int run_encoder(ofx_raft* r, const std::string& enc, bool bn, const uint8
                        int precision = OFX_PREC_FP32, bool separate_stats = false, const uint8_t* extra = nullptr) {
     // `extra`: one more image appended to the chunk (the shared key frame riding with the frames: see raft_forward_impl)
     // `out`: [n*h*w][out_ld]; fnet writes 256 channels; cnet writes tanh(0:128) | relu(128:256)
-    Launcher L{s};
-    L.precision = precision;
-    L.sk_ws = eb.sk; L.sk_bytes = eb.sk_bytes;
-    const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8;
+    Launcher L(s, precision, eb.sk);
+    const int H2 = H / 2, W2 = W / 2;
     const int SC = (ENC_CHUNK + 1) * 128;   // floats per stats vector slot
     float* m1 = eb.stats + 0 * SC; float* s1 = eb.stats + 1 * SC;
     float* m2 = eb.stats + 2 * SC; float* s2 = eb.stats + 3 * SC;
@@ -500,23 +526,20 @@ static int run_encoder(ofx_raft* r, const std::string& enc, bool bn, const uint8
         if (st) return st;
         ++n;
     }
-    // statistics of the tensor the conv() just before has written: from its epilogue's partial sums when it produced them.
+    // statistics of the tensor x a convolution has just written: from its epilogue's partial sums when it produced them (`rows`: that
+    // conv()'s stats_rows), with a pass of their own over x otherwise.
     // `norm`: the layer's name -- for "cnetb" (BatchNorm on per-image statistics) its gamma / beta are folded into (mean, rstd)
-    auto stats = [&](const float* x, long HW, int ch, float* mean, float* rstd, const std::string& norm) {
+    auto stats = [&](int rows, const float* x, long HW, int ch, float* mean, float* rstd, const std::string& norm) {
         if (L.st) return;
         const float *gamma = nullptr, *beta = nullptr;
         auto af = r->affine.find(enc + "." + norm);
         if (af != r->affine.end()) { gamma = af->second.first; beta = af->second.second; }
-        if (L.stats_rows > 0) L.st = ofx_inorm_finalize_part(eb.spart, mean, rstd, n, L.stats_rows, HW, ch, 1e-5f, s, gamma, beta);
+        if (rows > 0) L.st = ofx_inorm_finalize_part(eb.spart, mean, rstd, n, rows, HW, ch, 1e-5f, s, gamma, beta);
         else L.st = ofx_inorm_stats_affine(x, ch, mean, rstd, eb.scratch, n, HW, ch, 1e-5f, gamma, beta, s);
-        L.stats_rows = 0;
     };
     static const bool no_epi_stats = getenv("OFX_NO_EPI_STATS") != nullptr;     // diagnostic: always the separate statistics pass
-    auto want_stats = [&]() {
-        if (no_epi_stats || separate_stats) return;
-        L.stats_part = eb.spart;
-        L.stats_floats = eb.spart_floats;
-    };
+    // the `.stats` of a convolution whose output is normalised next
+    const StatsOut epi_stats = no_epi_stats || separate_stats ? StatsOut{} : StatsOut{eb.spart, eb.spart_floats};
     float* X = eb.X;
     float* Y = eb.Y;
     // instance norm: the stem's normalised output is never materialised.  Its raw output stays in X with its statistics in (m3, s3)
@@ -525,12 +548,12 @@ static int run_encoder(ofx_raft* r, const std::string& enc, bool bn, const uint8
     // read + write pass less per encoder.
     bool stem_raw = false;
     if (!bn) {
-        want_stats();
-        L.conv(C("conv1"), eb.x0, 4, 4, nullptr, 0, 0, X, 64, n, H, W, 2, OFX_ACT_NONE);
-        stats(X, (long)H2 * W2, 64, m3, s3, "norm1");
+        const int rows = L.conv(C("conv1"), {.in0 = eb.x0, .ld0 = 4, .c0 = 4, .out = X, .ldo = 64, .B = n, .Hin = H, .Win = W, .stride = 2,
+                                             .stats = epi_stats}).stats_rows;
+        stats(rows, X, (long)H2 * W2, 64, m3, s3, "norm1");
         stem_raw = true;
     } else {
-        L.conv(C("conv1"), eb.x0, 4, 4, nullptr, 0, 0, X, 64, n, H, W, 2, OFX_ACT_RELU);
+        L.conv(C("conv1"), {.in0 = eb.x0, .ld0 = 4, .c0 = 4, .out = X, .ldo = 64, .B = n, .Hin = H, .Win = W, .stride = 2, .act = OFX_ACT_RELU});
     }
     int hin = H2, win = W2, cin = 64;
     const int dims[3] = {64, 96, 128};
@@ -541,19 +564,18 @@ static int run_encoder(ofx_raft* r, const std::string& enc, bool bn, const uint8
             const int ho = hin / stride, wo = win / stride;
             const std::string p = "layer" + std::to_string(li) + "." + std::to_string(bi);
             if (!bn) {
-                want_stats();
-                L.conv(C(p + ".conv1"), X, cin, cin, nullptr, 0, 0, eb.R1, dim, n, hin, win, stride, OFX_ACT_NONE, OFX_EPI_PLAIN, nullptr, 0,
-                       stem_raw ? m3 : nullptr, stem_raw ? s3 : nullptr);
-                stats(eb.R1, (long)ho * wo, dim, m1, s1, p + ".norm1");
+                int rows = L.conv(C(p + ".conv1"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = eb.R1, .ldo = dim, .B = n, .Hin = hin, .Win = win,
+                                                    .stride = stride, .nmean = stem_raw ? m3 : nullptr, .nrstd = stem_raw ? s3 : nullptr,
+                                                    .stats = epi_stats}).stats_rows;
+                stats(rows, eb.R1, (long)ho * wo, dim, m1, s1, p + ".norm1");
                 // norm1 + ReLU fused into conv2's operand load
-                want_stats();
-                L.conv(C(p + ".conv2"), eb.R1, dim, dim, nullptr, 0, 0, eb.R2, dim, n, ho, wo, 1, OFX_ACT_NONE,
-                       OFX_EPI_PLAIN, nullptr, 0, m1, s1);
-                stats(eb.R2, (long)ho * wo, dim, m2, s2, p + ".norm2");
+                rows = L.conv(C(p + ".conv2"), {.in0 = eb.R1, .ld0 = dim, .c0 = dim, .out = eb.R2, .ldo = dim, .B = n, .Hin = ho, .Win = wo,
+                                                .nmean = m1, .nrstd = s1, .stats = epi_stats}).stats_rows;
+                stats(rows, eb.R2, (long)ho * wo, dim, m2, s2, p + ".norm2");
                 if (stride == 2) {
-                    want_stats();
-                    L.conv(C(p + ".down"), X, cin, cin, nullptr, 0, 0, eb.R3, dim, n, hin, win, 2, OFX_ACT_NONE);
-                    stats(eb.R3, (long)ho * wo, dim, m3, s3, p + ".norm3");
+                    rows = L.conv(C(p + ".down"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = eb.R3, .ldo = dim, .B = n, .Hin = hin, .Win = win,
+                                                   .stride = 2, .stats = epi_stats}).stats_rows;
+                    stats(rows, eb.R3, (long)ho * wo, dim, m3, s3, p + ".norm3");
                     if (!L.st) L.st = ofx_inorm_apply(eb.R2, m2, s2, eb.R3, m3, s3, Y, n, (long)ho * wo, dim, 1, s);
                 } else {
                     if (!L.st)
@@ -562,29 +584,23 @@ static int run_encoder(ofx_raft* r, const std::string& enc, bool bn, const uint8
                 }
                 stem_raw = false;
             } else {
-                L.conv(C(p + ".conv1"), X, cin, cin, nullptr, 0, 0, eb.R1, dim, n, hin, win, stride, OFX_ACT_RELU);
+                L.conv(C(p + ".conv1"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = eb.R1, .ldo = dim, .B = n, .Hin = hin, .Win = win,
+                                         .stride = stride, .act = OFX_ACT_RELU});
                 const float* res = X;
                 if (stride == 2) {
-                    L.conv(C(p + ".down"), X, cin, cin, nullptr, 0, 0, eb.R3, dim, n, hin, win, 2, OFX_ACT_NONE);
+                    L.conv(C(p + ".down"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = eb.R3, .ldo = dim, .B = n, .Hin = hin, .Win = win, .stride = 2});
                     res = eb.R3;
                 }
-                L.conv(C(p + ".conv2"), eb.R1, dim, dim, nullptr, 0, 0, Y, dim, n, ho, wo, 1, OFX_ACT_RELU, OFX_EPI_PLAIN,
-                       res, dim);
+                L.conv(C(p + ".conv2"), {.in0 = eb.R1, .ld0 = dim, .c0 = dim, .out = Y, .ldo = dim, .B = n, .Hin = ho, .Win = wo,
+                                         .act = OFX_ACT_RELU, .res = res, .ldres = dim});
             }
             std::swap(X, Y);
             hin = ho; win = wo; cin = dim;
         }
     }
-    (void)H4; (void)W4; (void)H8; (void)W8;
-    if (!split_tanh_relu) {
-        L.conv(C("conv2"), X, 128, 128, nullptr, 0, 0, out, out_ld, n, hin, win, 1, OFX_ACT_NONE);
-    } else {
-        // net = tanh(cnet[:, :128]), inp = relu(cnet[:, 128:256])  (raft.py:111-114)
-        L.conv(C("conv2"), X, 128, 128, nullptr, 0, 0, out, out_ld, n, hin, win, 1, OFX_ACT_TANH, OFX_EPI_PLAIN, nullptr, 0,
-               nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, HD);
-        L.conv(C("conv2"), X, 128, 128, nullptr, 0, 0, out + relu_off, out_ld, n, hin, win, 1, OFX_ACT_RELU, OFX_EPI_PLAIN, nullptr,
-               0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, HD, CD);
-    }
+    const ConvArgs last{.in0 = X, .ld0 = 128, .c0 = 128, .out = out, .ldo = out_ld, .B = n, .Hin = hin, .Win = win};
+    if (!split_tanh_relu) L.conv(C("conv2"), last);
+    else L.conv_tanh_relu(C("conv2"), last, HD, relu_off);
     return L.st;
 }
 
@@ -620,7 +636,6 @@ static RaftWs carve(void* base, size_t cap, int B, int H, int W, int flags, int 
         }
         EncBufs& eb = w.eb[e];
         eb.sk = w.sk[e];
-        eb.sk_bytes = w.sk[e] ? SK_BYTES : 0;
         eb.x0 = c.take((size_t)nch * H * W * 4);
         eb.X = c.take((size_t)nch * half);
         eb.Y = c.take((size_t)nch * half);
@@ -712,35 +727,29 @@ static int run_recurrence(ofx_raft* r, const RaftWs& ws, int B, int h, int w, in
               : ofx_init_state(ws.coords1, ws.frows, ws.hx, HX_LD, FLOW_OFF, B, h, w, s);
     if (st) return st;
     {   // loop-invariant GRU terms: conv(W[:, inp], inp) + bias for z|r and q of both passes
-        Launcher G{s};
-        G.precision = precision;
-        G.sk_ws = ws.sk[0]; G.sk_bytes = ws.sk[0] ? SK_BYTES : 0;
+        Launcher G(s, precision, ws.sk[0]);
         const char* names[4] = {"gru.zr1.inp", "gru.q1.inp", "gru.zr2.inp", "gru.q2.inp"};
         const int offs[4] = {0, 2 * HD, 3 * HD, 5 * HD};
         for (int i = 0; i < 4; ++i)
-            G.conv(r->convs[names[i]], ws.hx + INP_OFF, HX_LD, CD, nullptr, 0, 0, ws.gadd + offs[i], GADD_LD, B, h, w, 1,
-                   OFX_ACT_NONE);
+            G.conv(r->convs[names[i]], {.in0 = ws.hx + INP_OFF, .ld0 = HX_LD, .c0 = CD, .out = ws.gadd + offs[i], .ldo = GADD_LD, .B = B, .Hin = h, .Win = w});
         if (G.st) return G.st;
     }
 
     if (alt) OFX_HIP_CHECK(hipMemsetAsync(ws.corr, 0, (size_t)B * N * CORR_LD * sizeof(float), s));   // (the pad columns: the volume-free kernel writes 324 of 336)
-    Launcher L{s};
-    L.precision = precision;
-    L.sk_ws = ws.sk[0]; L.sk_bytes = ws.sk[0] ? SK_BYTES : 0;
+    Launcher L(s, precision, ws.sk[0]);
     const Streams S{r, s, overlap};
-    Launcher LF{S.get(0)};   // flow branch of the motion encoder: independent of the correlation branch
-    LF.precision = precision;
-    LF.sk_ws = overlap ? ws.sk[1] : ws.sk[0]; LF.sk_bytes = LF.sk_ws ? SK_BYTES : 0;   // its own scratch when it runs concurrently
+    // flow branch of the motion encoder: independent of the correlation branch, with its own scratch when it runs concurrently
+    Launcher LF(S.get(0), precision, overlap ? ws.sk[1] : ws.sk[0]);
     auto C = [&](const char* k) -> const ConvW& { return r->convs[k]; };
     const float* pyr_c[LEVELS] = {ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3]};
     bool fork_on_kernel = false;   // the previous iteration's flow head carries ev_fork
     for (int it = 0; it < iters && !L.st; ++it) {
         // flow features (update.py:93-94) on the side stream, from the flow the previous iteration left
         if ((L.st = fork_on_kernel ? S.fork_armed(0) : S.fork(0))) break;
-        LF.conv(C("convf1"), ws.frows, FROW, FROW, nullptr, 0, 0, ws.f1, 128, B, h, w, 1, OFX_ACT_RELU);   // 7x1 over the flow rows
-        LF.stop_event = S.arm_join(0);
-        LF.conv(C("convf2"), ws.f1, 128, 128, nullptr, 0, 0, ws.corflo + 192, 256, B, h, w, 1, OFX_ACT_RELU);
-        const bool join_on_kernel = LF.stop_taken;
+        LF.conv(C("convf1"), {.in0 = ws.frows, .ld0 = FROW, .c0 = FROW, .out = ws.f1, .ldo = 128, .B = B, .Hin = h, .Win = w,
+                              .act = OFX_ACT_RELU});   // 7x1 over the flow rows
+        const bool join_on_kernel = LF.conv(C("convf2"), {.in0 = ws.f1, .ld0 = 128, .c0 = 128, .out = ws.corflo + 192, .ldo = 256, .B = B,
+                                                          .Hin = h, .Win = w, .act = OFX_ACT_RELU, .stop_event = S.arm_join(0)}).stop_taken;
         if ((L.st = LF.st)) break;
         // correlation features at the current estimate
         if (!alt) {
@@ -749,24 +758,23 @@ static int run_recurrence(ofx_raft* r, const RaftWs& ws, int B, int h, int w, in
             L.st = alt_lookup(ws.fmap1, ws.f2l, aix, ws.coords1, ws.corr, CORR_LD, B, h, w, FD, RADIUS, s);
         }
         // motion encoder (update.py:88-97)
-        L.conv(C("convc1"), ws.corr, CORR_LD, CORR_LD, nullptr, 0, 0, ws.c1, 256, B, h, w, 1, OFX_ACT_RELU);
-        L.conv(C("convc2"), ws.c1, 256, 256, nullptr, 0, 0, ws.corflo, 256, B, h, w, 1, OFX_ACT_RELU);
+        L.conv(C("convc1"), {.in0 = ws.corr, .ld0 = CORR_LD, .c0 = CORR_LD, .out = ws.c1, .ldo = 256, .B = B, .Hin = h, .Win = w, .act = OFX_ACT_RELU});
+        L.conv(C("convc2"), {.in0 = ws.c1, .ld0 = 256, .c0 = 256, .out = ws.corflo, .ldo = 256, .B = B, .Hin = h, .Win = w, .act = OFX_ACT_RELU});
         if (!L.st) L.st = join_on_kernel ? S.join_armed(0) : S.join(0);
-        L.conv(C("conv"), ws.corflo, 256, 256, nullptr, 0, 0, ws.hx + MOT_OFF, HX_LD, B, h, w, 1, OFX_ACT_RELU);
+        L.conv(C("conv"), {.in0 = ws.corflo, .ld0 = 256, .c0 = 256, .out = ws.hx + MOT_OFF, .ldo = HX_LD, .B = B, .Hin = h, .Win = w,
+                           .act = OFX_ACT_RELU});
         // SepConvGRU (update.py:44-60): horizontal then vertical pass
         for (int pass = 1; pass <= 2; ++pass) {
             const char* zr = pass == 1 ? "gru.zr1" : "gru.zr2";
             const char* q = pass == 1 ? "gru.q1" : "gru.q2";
             const float* g = ws.gadd + (pass - 1) * (3 * HD);
-            L.addend = g; L.ldadd = GADD_LD;
-            L.conv(C(zr), ws.hx, HX_LD, 2 * HD, nullptr, 0, 0, nullptr, 0, B, h, w, 1, OFX_ACT_NONE, OFX_EPI_GRU_ZR, nullptr, 0,
-                   nullptr, nullptr, ws.z, ws.rh, ws.hx, HX_LD);
-            L.addend = g + 2 * HD; L.ldadd = GADD_LD;
-            L.conv(C(q), ws.rh, HD, HD, ws.hx + MOT_OFF, HX_LD, 128, nullptr, 0, B, h, w, 1, OFX_ACT_NONE, OFX_EPI_GRU_Q,
-                   nullptr, 0, nullptr, nullptr, ws.z, nullptr, ws.hx, HX_LD);
+            L.conv(C(zr), {.in0 = ws.hx, .ld0 = HX_LD, .c0 = 2 * HD, .B = B, .Hin = h, .Win = w, .epi = OFX_EPI_GRU_ZR, .addend = g,
+                           .ldadd = GADD_LD, .aux_z = ws.z, .aux_rh = ws.rh, .aux_h = ws.hx, .ldh = HX_LD});
+            L.conv(C(q), {.in0 = ws.rh, .ld0 = HD, .c0 = HD, .in1 = ws.hx + MOT_OFF, .ld1 = HX_LD, .c1 = 128, .B = B, .Hin = h, .Win = w,
+                          .epi = OFX_EPI_GRU_Q, .addend = g + 2 * HD, .ldadd = GADD_LD, .aux_z = ws.z, .aux_h = ws.hx, .ldh = HX_LD});
         }
         // flow head (update.py:6-14) + coords1 += delta (raft.py:131) in the epilogue
-        L.conv(C("fh1"), ws.hx, HX_LD, HD, nullptr, 0, 0, ws.c1, 256, B, h, w, 1, OFX_ACT_RELU);
+        L.conv(C("fh1"), {.in0 = ws.hx, .ld0 = HX_LD, .c0 = HD, .out = ws.c1, .ldo = 256, .B = B, .Hin = h, .Win = w, .act = OFX_ACT_RELU});
         if (!L.st) {   // 256 -> 2 channels: dedicated reduction kernel instead of a 1/16-utilised GEMM tile
             const ConvW& f2 = C("fh2");
             const hipEvent_t fork_ev = it + 1 < iters ? S.arm_fork() : nullptr;
@@ -776,8 +784,8 @@ static int run_recurrence(ofx_raft* r, const RaftWs& ws, int B, int h, int w, in
         }
     }
     // mask head (update.py:122-125,135) on the final hidden state, then convex upsample
-    L.conv(C("mask0"), ws.hx, HX_LD, HD, nullptr, 0, 0, ws.c1, 256, B, h, w, 1, OFX_ACT_RELU);
-    L.conv(C("mask2"), ws.c1, 256, 256, nullptr, 0, 0, ws.mask, 576, B, h, w, 1, OFX_ACT_NONE);
+    L.conv(C("mask0"), {.in0 = ws.hx, .ld0 = HX_LD, .c0 = HD, .out = ws.c1, .ldo = 256, .B = B, .Hin = h, .Win = w, .act = OFX_ACT_RELU});
+    L.conv(C("mask2"), {.in0 = ws.c1, .ld0 = 256, .c0 = 256, .out = ws.mask, .ldo = 576, .B = B, .Hin = h, .Win = w});
     if (L.st) return L.st;
     // convex upsample -- with the backward warp of the AI key frame in the same pass when the caller asked for it: the flow is in
     // registers right there, flow_up is then written only if wanted
@@ -796,6 +804,32 @@ static int run_recurrence(ofx_raft* r, const RaftWs& ws, int B, int h, int w, in
     }
 
     return 0;
+}
+
+// The all-pairs volume as a batched 1x1 convolution (conv.hip's generic GEMM), for both networks: level 0 (and level 1 out of the
+// accumulators where the shape allows: level 0 is then never read back) of nz pairs.  f1: rows [N][D] at a_zs floats per pair; f2b:
+// image 2's rows in the blocked order of the volume's columns [Nb][D] at w_zs per pair -- a zero stride broadcasts a shared feature
+// map across the batch.  *fused tells the pooling launch whether level 1 is already there.
+// One pair at a time (the indexed-pairs calls) passes nz = 1 and that pair's own pointers: conv.hip reads nz as `nz > 1 ? nz : 1` and
+// drops the three batch strides of a single z, and the pool's stride is only ever multiplied by z = 0 -- the launch is the one a
+// descriptor without any of them gives.
+static int volume_gemm(const float* f1, long a_zs, const float* f2b, long w_zs, float* l0, float* l1, int nz, int h, int w, int D,
+                       int precision, bool* fused, hipStream_t s) {
+    const long N = (long)h * w, Nb = ofx_corr_slice_floats_l(h, w), slice1 = ofx_corr_slice_floats_l(h >> 1, w >> 1);
+    ofx_conv_desc d{};
+    d.in0 = f1; d.ld0 = D; d.c0 = D;
+    d.w = f2b;
+    d.out = l0; d.ldo = (int)Nb;
+    d.nz = nz; d.a_zs = a_zs; d.w_zs = w_zs; d.o_zs = N * Nb;
+    d.B = 1; d.Hin = h; d.Win = w; d.Hout = h; d.Wout = w; d.Cout = (int)Nb;
+    d.KH = 1; d.KW = 1; d.stride = 1;
+    d.act = OFX_ACT_NONE; d.epi = OFX_EPI_PLAIN;
+    d.precision = precision;
+    *fused = ofx_corr_volpool_ok(h, w) && Nb % 128 == 0 && N * slice1 * 4 < (1L << 31) - 64;   // (every arithmetic since round 4)
+    ConvExtra x;
+    x.alpha = 1.0f / std::sqrt((float)D);
+    if (*fused) x.pool = {l1, N * slice1, (w + 7) >> 3, ((w >> 1) + 7) >> 3, (int)slice1};
+    return ofx_conv2d_ex(&d, &x, s);
 }
 
 // The volume GEMM on the A-stationary kernel (corr_split.hip).  OFX_RAFT_VOL_BF16X3 / _BF16X6 ask for its split-bf16 forms alone (every
@@ -1051,23 +1085,8 @@ static int raft_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* 
         const long Nb = ofx_corr_slice_floats_l(h, w);
         st = ofx_corr_block_rows(ws.fmap2, ws.fmap2b, (int)n2, h, w, FD, s);
         if (st) return st;
-        ofx_conv_desc d{};
-        d.in0 = ws.fmap1; d.ld0 = FD; d.c0 = FD;
-        d.w = ws.fmap2b;
-        d.out = ws.pyr[0]; d.ldo = (int)Nb;
-        d.nz = B; d.a_zs = sh1 ? 0 : N * FD; d.w_zs = sh2 ? 0 : Nb * FD; d.o_zs = N * Nb;
-        d.B = 1; d.Hin = h; d.Win = w; d.Hout = h; d.Wout = w; d.Cout = (int)Nb;
-        d.KH = 1; d.KW = 1; d.stride = 1;
-        d.act = OFX_ACT_NONE; d.epi = OFX_EPI_PLAIN;
-        d.precision = prec;
-        // zero batch strides broadcast a shared key-frame feature map across the batch.  Level 1 of the pyramid comes out
-        // of the GEMM's accumulators when it can (whole-block level 1): level 0 is then never read back
-        const long slice1 = ofx_corr_slice_floats_l(h >> 1, w >> 1);
-        const bool fused = ofx_corr_volpool_ok(h, w) && Nb % 128 == 0 && N * slice1 * 4 < (1L << 31) - 64;   // (every arithmetic since round 4)
-        ConvExtra x;
-        x.alpha = 1.0f / std::sqrt((float)FD);
-        if (fused) x.pool = {ws.pyr[1], N * slice1, (w + 7) >> 3, ((w >> 1) + 7) >> 3, (int)slice1};
-        st = ofx_conv2d_ex(&d, &x, s);
+        bool fused = false;
+        st = volume_gemm(ws.fmap1, sh1 ? 0 : N * FD, ws.fmap2b, sh2 ? 0 : Nb * FD, ws.pyr[0], ws.pyr[1], B, h, w, FD, prec, &fused, s);
         if (!st) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused);
         if (st) return st;
     } else {
@@ -1188,7 +1207,7 @@ int ofx_raft_forward_pairs_warp(ofx_raft* r, const uint8_t* images, int n_images
     }
     const long Nb = ofx_corr_slice_floats_l(h, w);
     const long slice1p = ofx_corr_slice_floats_l(h >> 1, w >> 1);
-    const bool fused_pairs = ofx_corr_volpool_ok(h, w) && Nb % 128 == 0 && N * slice1p * 4 < (1L << 31) - 64;
+    bool fused_pairs = false;
     const int vplanes = alt ? 0 : volume_planes(flags, h, w, 2L * n_images, ws, (long)B * N, B);
     if (vplanes) {
         // split-bf16 volume: every image split once per role (rows scaled in pixel order / columns in quad order), ONE launch over the
@@ -1203,20 +1222,9 @@ int ofx_raft_forward_pairs_warp(ofx_raft* r, const uint8_t* images, int n_images
         st = ofx_corr_block_rows(ws.fmap1, ws.fmap2b, n_images, h, w, FD, s);   // every image can be an image2: blocked copy of all
     }
     if (st) return st;
-    for (int b = 0; b < B && !st && !vplanes && !alt; ++b) {   // one N x Nb correlation GEMM per pair, straight from the shared feature maps
-        ofx_conv_desc d{};
-        d.in0 = ws.fmap1 + (long)idx1[b] * N * FD; d.ld0 = FD; d.c0 = FD;
-        d.w = ws.fmap2b + (long)idx2[b] * Nb * FD;
-        d.out = ws.pyr[0] + (long)b * N * Nb; d.ldo = (int)Nb;
-        d.B = 1; d.Hin = h; d.Win = w; d.Hout = h; d.Wout = w; d.Cout = (int)Nb;
-        d.KH = 1; d.KW = 1; d.stride = 1;
-        d.act = OFX_ACT_NONE; d.epi = OFX_EPI_PLAIN;
-        d.precision = prec;
-        ConvExtra x;
-        x.alpha = 1.0f / std::sqrt((float)FD);
-        if (fused_pairs) x.pool = {ws.pyr[1] + (long)b * N * slice1p, 0, (w + 7) >> 3, ((w >> 1) + 7) >> 3, (int)slice1p};
-        st = ofx_conv2d_ex(&d, &x, s);
-    }
+    for (int b = 0; b < B && !st && !vplanes && !alt; ++b)   // one N x Nb correlation GEMM per pair, straight from the shared feature maps
+        st = volume_gemm(ws.fmap1 + (long)idx1[b] * N * FD, 0, ws.fmap2b + (long)idx2[b] * Nb * FD, 0, ws.pyr[0] + (long)b * N * Nb,
+                         ws.pyr[1] + (long)b * N * slice1p, 1, h, w, FD, prec, &fused_pairs, s);
     if (!st && !alt) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused_pairs || vplanes);
     if (st) return st;
     if (warped) {   // the zero-bordered RGBX copy the warp samples
@@ -1332,7 +1340,7 @@ SmallWs small_carve(void* base, size_t cap, int B, int H, int W, int flags, int 
 // tanh_rows > 0 (cnet): out rows [0, tanh_rows) = tanh, the rest = relu (raft.py:111-114)
 int small_encoder(ofx_raft* r, const char* enc, bool instance, const uint8_t* imgs, int n, int H, int W, int bgr, const SmallWs& ws, float* out,
                   int out_ld, int tanh_rows, hipStream_t s) {
-    Launcher L{s};
+    Launcher L(s);
     auto C = [&](const std::string& k) -> const ConvW& { return r->convs[std::string(enc) + "." + k]; };
     const int SC = ws.nch * 128;
     float* mean[4] = {ws.stats, ws.stats + 2 * SC, ws.stats + 4 * SC, ws.stats + 6 * SC};
@@ -1349,11 +1357,11 @@ int small_encoder(ofx_raft* r, const char* enc, bool instance, const uint8_t* im
     float* Y = ws.Y;
     int hin = H / 2, win = W / 2, cin = 32;
     if (instance) {
-        L.conv(C("conv1"), ws.x0, 4, 4, nullptr, 0, 0, ws.T3, 32, n, H, W, 2, OFX_ACT_NONE);
+        L.conv(C("conv1"), {.in0 = ws.x0, .ld0 = 4, .c0 = 4, .out = ws.T3, .ldo = 32, .B = n, .Hin = H, .Win = W, .stride = 2});
         stats(ws.T3, (long)hin * win, 32, 0);
         norm_relu(ws.T3, (long)hin * win, 32, 0, X);
     } else {
-        L.conv(C("conv1"), ws.x0, 4, 4, nullptr, 0, 0, X, 32, n, H, W, 2, OFX_ACT_RELU);
+        L.conv(C("conv1"), {.in0 = ws.x0, .ld0 = 4, .c0 = 4, .out = X, .ldo = 32, .B = n, .Hin = H, .Win = W, .stride = 2, .act = OFX_ACT_RELU});
     }
     const int dims[3] = {32, 64, 96};
     for (int li = 1; li <= 3; ++li) {
@@ -1364,67 +1372,42 @@ int small_encoder(ofx_raft* r, const char* enc, bool instance, const uint8_t* im
             const long HWo = (long)ho * wo;
             const std::string p = "layer" + std::to_string(li) + "." + std::to_string(bi);
             if (instance) {
-                L.conv(C(p + ".conv1"), X, cin, cin, nullptr, 0, 0, ws.T1, mid, n, hin, win, 1, OFX_ACT_NONE);
+                L.conv(C(p + ".conv1"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = ws.T1, .ldo = mid, .B = n, .Hin = hin, .Win = win});
                 stats(ws.T1, (long)hin * win, mid, 0);
                 norm_relu(ws.T1, (long)hin * win, mid, 0, ws.N1);
-                L.conv(C(p + ".conv2"), ws.N1, mid, mid, nullptr, 0, 0, ws.T2, mid, n, hin, win, stride, OFX_ACT_NONE);
+                L.conv(C(p + ".conv2"), {.in0 = ws.N1, .ld0 = mid, .c0 = mid, .out = ws.T2, .ldo = mid, .B = n, .Hin = hin, .Win = win, .stride = stride});
                 stats(ws.T2, HWo, mid, 1);
                 norm_relu(ws.T2, HWo, mid, 1, ws.N2);
-                L.conv(C(p + ".conv3"), ws.N2, mid, mid, nullptr, 0, 0, ws.T3, dim, n, ho, wo, 1, OFX_ACT_NONE);
+                L.conv(C(p + ".conv3"), {.in0 = ws.N2, .ld0 = mid, .c0 = mid, .out = ws.T3, .ldo = dim, .B = n, .Hin = ho, .Win = wo});
                 stats(ws.T3, HWo, dim, 2);
                 if (stride == 2) {   // relu(norm4(down(x)) + relu(norm3(conv3)))
-                    L.conv(C(p + ".down"), X, cin, cin, nullptr, 0, 0, ws.Dn, dim, n, hin, win, 2, OFX_ACT_NONE);
+                    L.conv(C(p + ".down"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = ws.Dn, .ldo = dim, .B = n, .Hin = hin, .Win = win, .stride = 2});
                     stats(ws.Dn, HWo, dim, 3);
                     if (!L.st) L.st = ofx_inorm_apply(ws.T3, mean[2], rstd[2], ws.Dn, mean[3], rstd[3], Y, n, HWo, dim, 1, s);
                 } else {             // relu(x + relu(norm3(conv3)))
                     if (!L.st) L.st = ofx_inorm_apply(ws.T3, mean[2], rstd[2], X, nullptr, nullptr, Y, n, HWo, dim, 1, s);
                 }
             } else {
-                L.conv(C(p + ".conv1"), X, cin, cin, nullptr, 0, 0, ws.T1, mid, n, hin, win, 1, OFX_ACT_RELU);
-                L.conv(C(p + ".conv2"), ws.T1, mid, mid, nullptr, 0, 0, ws.T2, mid, n, hin, win, stride, OFX_ACT_RELU);
+                L.conv(C(p + ".conv1"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = ws.T1, .ldo = mid, .B = n, .Hin = hin, .Win = win, .act = OFX_ACT_RELU});
+                L.conv(C(p + ".conv2"), {.in0 = ws.T1, .ld0 = mid, .c0 = mid, .out = ws.T2, .ldo = mid, .B = n, .Hin = hin, .Win = win, .stride = stride,
+                                         .act = OFX_ACT_RELU});
                 const float* res = X;
                 if (stride == 2) {
-                    L.conv(C(p + ".down"), X, cin, cin, nullptr, 0, 0, ws.Dn, dim, n, hin, win, 2, OFX_ACT_NONE);
+                    L.conv(C(p + ".down"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = ws.Dn, .ldo = dim, .B = n, .Hin = hin, .Win = win, .stride = 2});
                     res = ws.Dn;
                 }
                 // relu(x' + relu(conv3)): the residual merge of EPI_PLAIN
-                L.conv(C(p + ".conv3"), ws.T2, mid, mid, nullptr, 0, 0, Y, dim, n, ho, wo, 1, OFX_ACT_RELU, OFX_EPI_PLAIN, res, dim);
+                L.conv(C(p + ".conv3"), {.in0 = ws.T2, .ld0 = mid, .c0 = mid, .out = Y, .ldo = dim, .B = n, .Hin = ho, .Win = wo, .act = OFX_ACT_RELU,
+                                         .res = res, .ldres = dim});
             }
             std::swap(X, Y);
             hin = ho; win = wo; cin = dim;
         }
     }
-    const ConvW& c2 = C("conv2");
-    if (tanh_rows <= 0) {
-        L.conv(c2, X, 96, 96, nullptr, 0, 0, out, out_ld, n, hin, win, 1, OFX_ACT_NONE);
-    } else {
-        L.conv(c2, X, 96, 96, nullptr, 0, 0, out, out_ld, n, hin, win, 1, OFX_ACT_TANH, OFX_EPI_PLAIN, nullptr, 0, nullptr, nullptr, nullptr,
-               nullptr, nullptr, 0, nullptr, nullptr, 0, tanh_rows);
-        L.conv(c2, X, 96, 96, nullptr, 0, 0, out + tanh_rows, out_ld, n, hin, win, 1, OFX_ACT_RELU, OFX_EPI_PLAIN, nullptr, 0, nullptr, nullptr,
-               nullptr, nullptr, nullptr, 0, nullptr, nullptr, tanh_rows, c2.cout - tanh_rows);
-    }
+    const ConvArgs last{.in0 = X, .ld0 = 96, .c0 = 96, .out = out, .ldo = out_ld, .B = n, .Hin = hin, .Win = win};
+    if (tanh_rows <= 0) L.conv(C("conv2"), last);
+    else L.conv_tanh_relu(C("conv2"), last, tanh_rows, tanh_rows);
     return L.st;
-}
-
-// level 0 (and level 1 from the accumulators where the shape allows) of the volume of nz pairs: f1 rows [N][128] at a_zs floats per
-// pair, f2 in blocked row order [Nb][128] at w_zs per pair (zero strides broadcast a shared feature map); *fused tells the pooling
-// launch whether level 1 is already there
-int small_volume(const float* f1, long a_zs, const float* f2b, long w_zs, float* l0, float* l1, int nz, int h, int w, bool* fused,
-                 hipStream_t s) {
-    const long N = (long)h * w, Nb = ofx_corr_slice_floats_l(h, w), slice1 = ofx_corr_slice_floats_l(h >> 1, w >> 1);
-    ofx_conv_desc d{};
-    d.in0 = f1; d.ld0 = S_FD; d.c0 = S_FD;
-    d.w = f2b;
-    d.out = l0; d.ldo = (int)Nb;
-    d.nz = nz; d.a_zs = a_zs; d.w_zs = w_zs; d.o_zs = N * Nb;
-    d.B = 1; d.Hin = h; d.Win = w; d.Hout = h; d.Wout = w; d.Cout = (int)Nb;
-    d.KH = 1; d.KW = 1; d.stride = 1;
-    d.act = OFX_ACT_NONE; d.epi = OFX_EPI_PLAIN;
-    *fused = ofx_corr_volpool_ok(h, w) && Nb % 128 == 0 && N * slice1 * 4 < (1L << 31) - 64;
-    ConvExtra x;
-    x.alpha = 1.0f / std::sqrt((float)S_FD);
-    if (*fused) x.pool = {l1, N * slice1, (w + 7) >> 3, ((w >> 1) + 7) >> 3, (int)slice1};
-    return ofx_conv2d_ex(&d, &x, s);
 }
 
 // state init, `iters` refinement iterations of SmallUpdateBlock, upflow8 (with the warp of one shared frame for the first n_warp pairs)
@@ -1436,7 +1419,7 @@ int small_recurrence(ofx_raft* r, const SmallWs& ws, int B, int h, int w, int it
                   : ofx_init_state(ws.coords1, ws.flow4, ws.hx, S_HX_LD, S_FLOW_OFF, B, h, w, s);
     if (st) return st;
     OFX_HIP_CHECK(hipMemsetAsync(ws.corr, 0, (size_t)M * S_CORR_LD * sizeof(float), s));   // the 28 pad columns of every row
-    Launcher L{s};
+    Launcher L(s);
     auto C = [&](const char* k) -> const ConvW& { return r->convs[k]; };
     const float* pyr_c[LEVELS] = {ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3]};
     for (int it = 0; it < iters && !L.st; ++it) {
@@ -1446,20 +1429,22 @@ int small_recurrence(ofx_raft* r, const SmallWs& ws, int B, int h, int w, int it
             L.st = alt_lookup(ws.fmap1, ws.f2l, aix, ws.coords1, ws.corr, S_CORR_LD, B, h, w, S_FD, S_RADIUS, s);
         }
         // SmallMotionEncoder (update.py:70-77): cor_flo = [relu(convc1(corr)) (96) | relu(convf2(relu(convf1(flow)))) (32)]
-        L.conv(C("convc1"), ws.corr, S_CORR_LD, S_CORR_LD, nullptr, 0, 0, ws.corflo, 128, B, h, w, 1, OFX_ACT_RELU);
-        L.conv(C("convf1"), ws.flow4, 4, 4, nullptr, 0, 0, ws.f1, 64, B, h, w, 1, OFX_ACT_RELU);
-        L.conv(C("convf2"), ws.f1, 64, 64, nullptr, 0, 0, ws.corflo + 96, 128, B, h, w, 1, OFX_ACT_RELU);
-        L.conv(C("conv"), ws.corflo, 128, 128, nullptr, 0, 0, ws.hx + S_MOT_OFF, S_HX_LD, B, h, w, 1, OFX_ACT_RELU);
+        L.conv(C("convc1"), {.in0 = ws.corr, .ld0 = S_CORR_LD, .c0 = S_CORR_LD, .out = ws.corflo, .ldo = 128, .B = B, .Hin = h, .Win = w,
+                             .act = OFX_ACT_RELU});
+        L.conv(C("convf1"), {.in0 = ws.flow4, .ld0 = 4, .c0 = 4, .out = ws.f1, .ldo = 64, .B = B, .Hin = h, .Win = w, .act = OFX_ACT_RELU});
+        L.conv(C("convf2"), {.in0 = ws.f1, .ld0 = 64, .c0 = 64, .out = ws.corflo + 96, .ldo = 128, .B = B, .Hin = h, .Win = w, .act = OFX_ACT_RELU});
+        L.conv(C("conv"), {.in0 = ws.corflo, .ld0 = 128, .c0 = 128, .out = ws.hx + S_MOT_OFF, .ldo = S_HX_LD, .B = B, .Hin = h, .Win = w,
+                           .act = OFX_ACT_RELU});
         // ConvGRU (update.py:16-31): z | r in one convolution over cat([h, x]), q over cat([r*h, x]), h updated in place
-        L.conv(C("gru.zr"), ws.hx, S_HX_LD, S_HX_LD, nullptr, 0, 0, nullptr, 0, B, h, w, 1, OFX_ACT_NONE, OFX_EPI_GRU_ZR, nullptr, 0, nullptr,
-               nullptr, ws.z, ws.rh, ws.hx, S_HX_LD);
-        L.conv(C("gru.q"), ws.rh, S_HD, S_HD, ws.hx + S_INP_OFF, S_HX_LD, S_X_CH, nullptr, 0, B, h, w, 1, OFX_ACT_NONE, OFX_EPI_GRU_Q, nullptr,
-               0, nullptr, nullptr, ws.z, nullptr, ws.hx, S_HX_LD);
+        L.conv(C("gru.zr"), {.in0 = ws.hx, .ld0 = S_HX_LD, .c0 = S_HX_LD, .B = B, .Hin = h, .Win = w, .epi = OFX_EPI_GRU_ZR, .aux_z = ws.z,
+                             .aux_rh = ws.rh, .aux_h = ws.hx, .ldh = S_HX_LD});
+        L.conv(C("gru.q"), {.in0 = ws.rh, .ld0 = S_HD, .c0 = S_HD, .in1 = ws.hx + S_INP_OFF, .ld1 = S_HX_LD, .c1 = S_X_CH, .B = B, .Hin = h,
+                            .Win = w, .epi = OFX_EPI_GRU_Q, .aux_z = ws.z, .aux_h = ws.hx, .ldh = S_HX_LD});
         // FlowHead(96, 128) (update.py:6-14); coords1 += delta in the second convolution's epilogue (one rounding: delta, then the add),
         // which also leaves the new flow in hx's flow slot and in convf1's operand
-        L.conv(C("fh1"), ws.hx, S_HX_LD, S_HD, nullptr, 0, 0, ws.fh, 128, B, h, w, 1, OFX_ACT_RELU);
-        L.conv(C("fh2"), ws.fh, 128, 128, nullptr, 0, 0, nullptr, 0, B, h, w, 1, OFX_ACT_NONE, OFX_EPI_FLOW, nullptr, 0, nullptr, nullptr,
-               nullptr, nullptr, ws.hx + S_FLOW_OFF, S_HX_LD, ws.coords1, ws.flow4);
+        L.conv(C("fh1"), {.in0 = ws.hx, .ld0 = S_HX_LD, .c0 = S_HD, .out = ws.fh, .ldo = 128, .B = B, .Hin = h, .Win = w, .act = OFX_ACT_RELU});
+        L.conv(C("fh2"), {.in0 = ws.fh, .ld0 = 128, .c0 = 128, .B = B, .Hin = h, .Win = w, .epi = OFX_EPI_FLOW, .aux_h = ws.hx + S_FLOW_OFF,
+                          .ldh = S_HX_LD, .aux_coords = ws.coords1, .aux_flow4 = ws.flow4});
     }
     if (L.st) return L.st;
     // upflow8 of the last iteration only (raft.py:134-135; test_mode returns the last prediction)
@@ -1600,7 +1585,7 @@ static int small_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t*
         bool fused = false;
         const long Nb = ofx_corr_slice_floats_l(h, w);
         st = ofx_corr_block_rows(ws.fmap2, ws.fmap2b, n2, h, w, S_FD, s);
-        if (!st) st = small_volume(ws.fmap1, sh1 ? 0 : N * S_FD, ws.fmap2b, sh2 ? 0 : Nb * S_FD, ws.pyr[0], ws.pyr[1], B, h, w, &fused, s);
+        if (!st) st = volume_gemm(ws.fmap1, sh1 ? 0 : N * S_FD, ws.fmap2b, sh2 ? 0 : Nb * S_FD, ws.pyr[0], ws.pyr[1], B, h, w, S_FD, OFX_PREC_FP32, &fused, s);
         if (!st) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused);
     } else {
         for (int l = 1; l < LEVELS && !st; ++l) st = ofx_avgpool2_nhwc(ws.f2l[l - 1], ws.f2l[l], n2, h >> (l - 1), w >> (l - 1), S_FD, s);
@@ -1660,8 +1645,8 @@ static int small_forward_pairs_impl(ofx_raft* r, const uint8_t* images, int n_im
     if (!st && !alt) st = ofx_corr_block_rows(ws.fmap1, ws.fmap2b, n_images, h, w, S_FD, s);   // every image can be an image2
     bool fused = false;
     for (int b = 0; b < B && !st && !alt; ++b)   // one correlation GEMM per pair, straight from the shared feature maps
-        st = small_volume(ws.fmap1 + (long)idx1[b] * N * S_FD, 0, ws.fmap2b + (long)idx2[b] * Nb * S_FD, 0, ws.pyr[0] + (long)b * N * Nb,
-                          ws.pyr[1] + (long)b * N * slice1, 1, h, w, &fused, s);
+        st = volume_gemm(ws.fmap1 + (long)idx1[b] * N * S_FD, 0, ws.fmap2b + (long)idx2[b] * Nb * S_FD, 0, ws.pyr[0] + (long)b * N * Nb,
+                         ws.pyr[1] + (long)b * N * slice1, 1, h, w, S_FD, OFX_PREC_FP32, &fused, s);
     if (!st && !alt) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused);
     if (!st && warped) st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
     if (!st) st = small_recurrence(r, ws, B, h, w, iters, alt, aix, flow_up, flow_low, flags & OFX_RAFT_FLOW_INIT, warped, warp_sign, n_warp, s);
