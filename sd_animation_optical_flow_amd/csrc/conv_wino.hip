@@ -100,6 +100,7 @@ struct WinoK {
     int tpr, tpi, mtiles;    // patches (8x16; F(4x4, 3x3): 16x32) per image row / per image, patches in all
     int bytes0, bytes1, bytesu;
     float alpha;
+    int vec4;                // F(4x4, 3x3): out, scale, shift and res are 16-byte aligned, ldo and ldres multiples of 4 floats
 };
 
 // Output block nb of image pb's patch at (y0, x0)
@@ -697,7 +698,7 @@ constexpr int kSmem44 = (kStage44 > kXF4 ? kStage44 : kXF4) * 4;   // bytes: 122
 // NORM: behind the staged slabs, per four channels [mean x 4 | rstd x 4]; most input channels that fit (a multiple of 16)
 constexpr int kNorm44 = kSmem44 / 4 - kStage44;             // 3504 floats
 constexpr int kNorm44MaxCin = kNorm44 / 2 / kWBK * kWBK;    // 1744
-constexpr int kSX4 = 2 * 24 * 32 * 2;                       // STATS: [32-channel half][half-wave][channel][sum, sum of squares]
+constexpr int kSX4 = 2 * 48 * 32 * 2;                       // STATS: [32-channel half][wave, lane / 8][channel][sum, sum of squares]
 static_assert(kNorm44 >= 0 && kSX4 <= kXF4, "the fused options live in the plain kernel's LDS");
 
 __global__ __launch_bounds__(768, 1) void wino44_conv_kernel(const WinoK p) {
@@ -827,6 +828,9 @@ int wino_args(const WinoAlg& a, const ofx_conv_desc* d, float alpha, float* stat
     k.mtiles = (int)mtiles;
     k.bytes0 = (int)ext0; k.bytes1 = (int)ext1; k.bytesu = (int)extu;
     k.alpha = alpha;
+    // whole channel quads of the 3x3 epilogue may move as 16 bytes (decided here, once per launch; else 4 bytes at a time)
+    k.vec4 = ofx_aligned16(d->out) && d->ldo % 4 == 0 && ofx_aligned16(d->scale) && ofx_aligned16(d->shift) &&
+             (!d->res || (ofx_aligned16(d->res) && d->ldres % 4 == 0));
     *out = k;
     return 0;
 }

@@ -212,106 +212,177 @@
         }
     }
 
-    // ---- output transform and plain epilogue.  A^T (4x6) along the column in registers, the six rows meet in LDS, half of the
+    // ---- output transform and epilogue.  A^T (4x6) along the column in registers, the six rows meet in LDS, half of the
     // patch's tiles (two tile rows) at a time: X[wave][b][tile][channel].  Element e of the C layout: tile (e & 3) + 8 (e >> 2) +
     // 4 (lane >> 5), output channel lane & 31 of the wave's 32.
+    //
+    // The row side: a lane takes four adjacent output channels of one pixel, rows ap and ap + 2 of its tile -- five ds_read_b128
+    // (point rows ap .. ap + 4) and two 16-byte stores; eight lanes cover a pixel's 32 channels, one 128-byte line.  A wave's unit
+    // is (channel half ont, row pair ap, tiles tl = {t, t + 4} of one tile row, columns b = 0 .. 3): 32 units per half of the
+    // patch, unit wave + 12 k in pass k, so that ont = wave & 1 and ap = (wave >> 1) & 1 hold for all of a wave's units and are
+    // scalar: one transform per wave behind a scalar branch, scale / shift read once.  Lane = (channel quad lane & 7, b & 1 at bit
+    // 3, tl & 4 at bit 4, b >> 1 at bit 5): with X as the accumulator side writes it (conflict-free: 32 consecutive floats per
+    // half-wave), a 16-lane group of the ds_read_b128 takes the low half of one row and the high half of the row 16 on (640
+    // floats: the same banks), and the high and low halves of the two rows four on (160 floats: 32 banks on) -- 16 different bank
+    // quads (tools/lds_bank_model.py --wino44-exchange).
+    // Addresses: a scalar 64-bit base per pass (image, patch, tile row and column, channel block) and one 32-bit byte offset per
+    // lane that never changes, (16 (tl & 4) / 4 + b) pixels and the channel quad: at most 32 ldo floats.  A quad is stored as
+    // 16 bytes where the host found the destination (and scale, shift, res) aligned for it (p.vec4) and the quad whole; a quad
+    // that straddles Cout, and every quad of an unaligned destination, goes channel by channel and writes nothing from Cout on.
+    // Every output is computed by the operations, in the order, of the one-channel-per-lane form this replaces: the same bits.
     const float act_lo = p.act == OFX_ACT_RELU ? 0.0f : -3.402823466e38f;   // OFX_ACT_NONE: a NaN sum becomes -FLT_MAX (see conv.hip)
     float* const X = smem44;
-    const int tid2 = tid;
-    const int lane2 = tid2 & 63, on = tid2 & 31, grp = tid2 >> 5;
-    // STATS: a half-wave's units alternate between the two 32-channel halves, one accumulator pair per half
-    float st_s[2] = {0.0f, 0.0f}, st_q[2] = {0.0f, 0.0f};
+    const int ont = wave & 1, ap = (wave >> 1) & 1;
+    const int cq = lane & 7, ob = ((lane >> 3) & 1) + 2 * (lane >> 5), t2 = (lane >> 4) & 1;
+    const int oc0 = pt.nb * 64 + ont * 32 + 4 * cq;
+    const int nv = p.Cout - oc0;            // how many of the quad's channels exist (<= 0: none)
+    const bool quad = p.vec4 && nv >= 4;
+    float sc[4], sh[4];                     // under the column side below
+    if (quad) {
+        const float4 s4 = p.scale ? *reinterpret_cast<const float4*>(p.scale + oc0) : make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+        const float4 h4 = p.shift ? *reinterpret_cast<const float4*>(p.shift + oc0) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        sc[0] = s4.x, sc[1] = s4.y, sc[2] = s4.z, sc[3] = s4.w;
+        sh[0] = h4.x, sh[1] = h4.y, sh[2] = h4.z, sh[3] = h4.w;
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            sc[c] = p.scale && c < nv ? p.scale[oc0 + c] : 1.0f;
+            sh[c] = p.shift && c < nv ? p.shift[oc0 + c] : 0.0f;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) sc[c] *= p.alpha;
+    const int xlane = (ob * 16 + t2 * 4) * kLDX4 + 4 * cq;
+    const unsigned olane = (unsigned)((16 * t2 + ob) * p.ldo + ont * 32 + 4 * cq) * 4u;   // bytes
+    char* const out0 = reinterpret_cast<char*>(p.out + (((long)pt.pb * p.H + pt.y0) * p.W + pt.x0) * p.ldo + pt.nb * 64);
+    const long orow_b = (long)p.W * p.ldo * 4;   // a pixel row of the destination, bytes
+    unsigned rlane = 0;
+    const char* res0 = nullptr;
+    long rrow_b = 0;
+    if constexpr (RES) {
+        rlane = (unsigned)((16 * t2 + ob) * p.ldres + ont * 32 + 4 * cq) * 4u;
+        res0 = reinterpret_cast<const char*>(p.res + (((long)pt.pb * p.H + pt.y0) * p.W + pt.x0) * p.ldres + pt.nb * 64);
+        rrow_b = (long)p.W * p.ldres * 4;
+    }
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    struct Ap0 { enum { v = 0 }; };
+    struct Ap1 { enum { v = 1 }; };
+    // STATS: the lane's four channels, every value it stores, in the order of its units
+    float st_s[4] = {0.0f, 0.0f, 0.0f, 0.0f}, st_q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         __syncthreads();   // half 0: every wave's last operand reads are done; half 1: the first half has been read
 #pragma unroll
         for (int eh = 0; eh < 8; ++eh) {
             const int e = 8 * half + eh;
-            const int tl = (e & 3) + 8 * ((e >> 2) & 1) + 4 * (lane2 >> 5);
+            const int tl = (e & 3) + 8 * ((e >> 2) & 1) + 4 * (lane >> 5);
             const float m0 = acc[0][0][e], m1 = acc[1][0][e], m2 = acc[2][0][e], m3 = acc[3][0][e], m4 = acc[4][0][e], m5 = acc[5][0][e];
             const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-            float* const x = X + (wave * 4 * 16 + tl) * kLDX4 + (lane2 & 31);
+            float* const x = X + (wave * 4 * 16 + tl) * kLDX4 + (lane & 31);
             x[0 * 16 * kLDX4] = m0 + s12 + s34;
             x[1 * 16 * kLDX4] = d12 + 2.0f * d34;
             x[2 * 16 * kLDX4] = s12 + 4.0f * s34;
             x[3 * 16 * kLDX4] = d12 + 8.0f * d34 + m5;
         }
         __syncthreads();
-        // unit = (32-channel half, tile, output row pair {0, 2} or {1, 3}): 64 units over the 24 half-waves
-        for (int un = grp; un < 64; un += 24) {
-            const int ap = (un >> 1) & 1, rest = un >> 2;
-            const int tl = (rest & 7) * 2 + (un & 1), ont = rest >> 3;
-            const int oc = pt.nb * 64 + ont * 32 + on;
-            if (oc >= p.Cout) continue;
-            const float sc = (p.scale ? p.scale[oc] : 1.0f) * p.alpha;
-            const float sh = p.shift ? p.shift[oc] : 0.0f;
-            const int oy = pt.y0 + 4 * (2 * half + (tl >> 3)) + ap, ox = pt.x0 + 4 * (tl & 7);
-            float us = 0.0f, uq = 0.0f;   // STATS: this unit's eight values
-            float rv[4][2];               // RES: the unit's eight residual values, in flight under the exchange reads
-            if constexpr (RES) {
+        // pass k: unit wave + 12 k = (ont, ap, ts = wave / 4 + 3 k: tile column ts & 3 (and + 4), tile row ts >> 2 of the half);
+        // waves 8 .. 11 have two.  One copy of the pass per row pair: AP is a constant in it.
+        auto row_side = [&](auto apc) __attribute__((always_inline)) {
+            constexpr int AP = decltype(apc)::v;
+#pragma clang loop unroll(disable)
+            for (int ts = wave >> 2; ts < 8; ts += 3) {
+                const int orow = 4 * (2 * half + (ts >> 2)) + AP, ocol = 4 * (ts & 3);   // the unit's first pixel in the patch
+                char* const oa = out0 + orow * orow_b + (long)(ocol * p.ldo) * 4;
+                char* const ob2 = oa + 2 * orow_b;
+                float ra[4] = {0.0f, 0.0f, 0.0f, 0.0f}, rb[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // RES: in flight under the exchange reads
+                if constexpr (RES) {
+                    const char* const qa = res0 + orow * rrow_b + (long)(ocol * p.ldres) * 4;
+                    const char* const qb = qa + 2 * rrow_b;
+                    if (quad) {
+                        const float4 a4 = *reinterpret_cast<const float4*>(qa + rlane), b4 = *reinterpret_cast<const float4*>(qb + rlane);
+                        ra[0] = a4.x, ra[1] = a4.y, ra[2] = a4.z, ra[3] = a4.w;
+                        rb[0] = b4.x, rb[1] = b4.y, rb[2] = b4.z, rb[3] = b4.w;
+                    } else {
 #pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const long pix = ((long)pt.pb * p.H + oy) * p.W + ox + b;
-                    rv[b][0] = p.res[pix * p.ldres + oc];
-                    rv[b][1] = p.res[(pix + 2L * p.W) * p.ldres + oc];
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                float x[5];   // rows ap .. ap + 4 of the point grid
-#pragma unroll
-                for (int k = 0; k < 5; ++k) x[k] = X[((((ap + k) * 2 + ont) * 4 + b) * 16 + tl) * kLDX4 + on];
-                float ya, yb;   // output rows ap and ap + 2
-                if (ap == 0) {
-                    ya = x[0] + (x[1] + x[2]) + (x[3] + x[4]);
-                    yb = (x[1] + x[2]) + 4.0f * (x[3] + x[4]);
-                } else {
-                    ya = (x[0] - x[1]) + 2.0f * (x[2] - x[3]);
-                    yb = (x[0] - x[1]) + 8.0f * (x[2] - x[3]) + x[4];
-                }
-                const long pix = ((long)pt.pb * p.H + oy) * p.W + ox + b;
-                if constexpr (!RES && !STATS) {
-                    p.out[pix * p.ldo + oc] = fmaxf(ya * sc + sh, act_lo);
-                    p.out[(pix + 2L * p.W) * p.ldo + oc] = fmaxf(yb * sc + sh, act_lo);
-                } else {
-                    float va = fmaxf(ya * sc + sh, act_lo), vb = fmaxf(yb * sc + sh, act_lo);
-                    if constexpr (RES) {
-                        va = fmaxf(va + rv[b][0], 0.0f);
-                        vb = fmaxf(vb + rv[b][1], 0.0f);
-                    }
-                    p.out[pix * p.ldo + oc] = va;
-                    p.out[(pix + 2L * p.W) * p.ldo + oc] = vb;
-                    if constexpr (STATS) {
-                        us += va;
-                        uq = fmaf(va, va, uq);
-                        us += vb;
-                        uq = fmaf(vb, vb, uq);
+                        for (int c = 0; c < 4; ++c)
+                            if (c < nv) {
+                                ra[c] = reinterpret_cast<const float*>(qa + rlane)[c];
+                                rb[c] = reinterpret_cast<const float*>(qb + rlane)[c];
+                            }
                     }
                 }
+                // rows AP .. AP + 4 of the point grid, the quad's channels as two pairs (packed fp32: the same roundings)
+                v2f x[2][5];
+                const float* const xu = X + ((AP * 2 + ont) * 4 * 16 + (ts & 3) + 8 * (ts >> 2)) * kLDX4 + xlane;
+#pragma unroll
+                for (int r = 0; r < 5; ++r) {
+                    const float4 t = *reinterpret_cast<const float4*>(xu + r * (2 * 4 * 16 * kLDX4));
+                    x[0][r] = v2f{t.x, t.y};
+                    x[1][r] = v2f{t.z, t.w};
+                }
+                float va[4], vb[4];   // output rows AP and AP + 2
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const v2f(&xp)[5] = x[h];
+                    v2f ya, yb;
+                    if constexpr (AP == 0) {
+                        ya = xp[0] + (xp[1] + xp[2]) + (xp[3] + xp[4]);
+                        yb = (xp[1] + xp[2]) + 4.0f * (xp[3] + xp[4]);
+                    } else {
+                        ya = (xp[0] - xp[1]) + 2.0f * (xp[2] - xp[3]);
+                        yb = (xp[0] - xp[1]) + 8.0f * (xp[2] - xp[3]) + xp[4];
+                    }
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const int c = 2 * h + e;
+                        va[c] = fmaxf(__builtin_fmaf(ya[e], sc[c], sh[c]), act_lo);
+                        vb[c] = fmaxf(__builtin_fmaf(yb[e], sc[c], sh[c]), act_lo);
+                        if constexpr (RES) {
+                            va[c] = fmaxf(va[c] + ra[c], 0.0f);
+                            vb[c] = fmaxf(vb[c] + rb[c], 0.0f);
+                        }
+                        if constexpr (STATS) {
+                            st_s[c] += va[c];
+                            st_q[c] = fmaf(va[c], va[c], st_q[c]);
+                            st_s[c] += vb[c];
+                            st_q[c] = fmaf(vb[c], vb[c], st_q[c]);
+                        }
+                    }
+                }
+                if (quad) {
+                    *reinterpret_cast<float4*>(oa + olane) = make_float4(va[0], va[1], va[2], va[3]);
+                    *reinterpret_cast<float4*>(ob2 + olane) = make_float4(vb[0], vb[1], vb[2], vb[3]);
+                } else if (nv > 0) {   // (nested, not a run of ifs: forward branches only)
+                    float* const pa = reinterpret_cast<float*>(oa + olane);
+                    float* const pb = reinterpret_cast<float*>(ob2 + olane);
+                    pa[0] = va[0], pb[0] = vb[0];
+                    if (nv > 1) {
+                        pa[1] = va[1], pb[1] = vb[1];
+                        if (nv > 2) {
+                            pa[2] = va[2], pb[2] = vb[2];
+                            if (nv > 3) pa[3] = va[3], pb[3] = vb[3];
+                        }
+                    }
+                }
             }
-            if constexpr (STATS) {   // (selects, not an indexed array: the pairs stay in registers)
-                st_s[0] += ont ? 0.0f : us;
-                st_q[0] += ont ? 0.0f : uq;
-                st_s[1] += ont ? us : 0.0f;
-                st_q[1] += ont ? uq : 0.0f;
-            }
-        }
+        };
+        if (ap == 0) row_side(Ap0{});
+        else row_side(Ap1{});
     }
-    if constexpr (STATS) {   // the 24 half-waves' partials of each channel meet in LDS and are added in index order
+    if constexpr (STATS) {   // a channel's 48 partials (six waves, eight lanes each) meet in LDS and are added in index order
         __syncthreads();     // the last exchange has been read
         float* const Sx = smem44;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            Sx[((h * 24 + grp) * 32 + on) * 2 + 0] = st_s[h];
-            Sx[((h * 24 + grp) * 32 + on) * 2 + 1] = st_q[h];
-        }
+        float* const sx = Sx + (((ont * 48 + (wave >> 1) * 8 + (lane >> 3)) * 32) + 4 * cq) * 2;
+        *reinterpret_cast<float4*>(sx) = make_float4(st_s[0], st_q[0], st_s[1], st_q[1]);
+        *reinterpret_cast<float4*>(sx + 4) = make_float4(st_s[2], st_q[2], st_s[3], st_q[3]);
         __syncthreads();
+        const int grp = tid >> 5, on = tid & 31;
         const int oc = pt.nb * 64 + grp * 32 + on;
         if (tid < 64 && oc < p.Cout) {
             float s = 0.0f, q = 0.0f;
-            for (int g = 0; g < 24; ++g) {
-                s += Sx[((grp * 24 + g) * 32 + on) * 2 + 0];
-                q += Sx[((grp * 24 + g) * 32 + on) * 2 + 1];
+            for (int g = 0; g < 48; ++g) {
+                s += Sx[((grp * 48 + g) * 32 + on) * 2 + 0];
+                q += Sx[((grp * 48 + g) * 32 + on) * 2 + 1];
             }
             const long row = (long)pt.pb * p.tpi + (pt.y0 >> 4) * p.tpr + (pt.x0 >> 5);
             p.stats[(row * p.Cout + oc) * 2 + 0] = s;
