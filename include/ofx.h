@@ -148,6 +148,24 @@ int ofx_sd_handoff(const uint8_t* image_bgr, const uint8_t* reference_bgr, const
                    const uint8_t* mask_latent, float* image, float* cond_image, float* cond_mask, float* latmask,
                    float* cond_mask_latent, int B, int H, int W, int h, int w, void* stream);
 
+/* ---------------------------------------------------------------- fill_mask_input (img2img_inpaint without a reference) */
+/* PIL.ImageFilter.GaussianBlur(radius) on an interleaved 8-bit 4-channel image [B,H,W,4] ('RGBa' / 'RGBA': BoxBlur.c blurs the
+ * four channels alike), bit-exact: the arithmetic of ofx_gaussian_blur_u8 per channel, but every row is prefix-summed in LDS, so
+ * the cost does not depend on the radius.  in / out / scratch 4-byte aligned; scratch: B*H*W*4 bytes, distinct from in / out;
+ * in == out is allowed; radius 0 is a copy.  max(H, W) <= 6144 (24 bytes of LDS per pixel of a row), B <= 65535 and
+ * radius <= 65536: OFX_EINVAL beyond, before any launch. */
+int ofx_gaussian_blur_rgba_u8(const uint8_t* in, uint8_t* out, uint8_t* scratch, int B, int H, int W, float radius,
+                              void* stream);
+/* fill_mask_input (guided_ldm_inpainting.py:161-176), bit-exact to Pillow: image_bgr u8[B,H,W,3] (the channel order does not
+ * matter), mask u8[B,H,W] = the already blurred 'L' mask (255 = repaint) -> out_bgr u8[B,H,W,3], the frame with the masked
+ * region filled from its surroundings: paste through 255 - mask onto an empty premultiplied canvas, then for (radius, repeats)
+ * in (256,1) (64,1) (16,2) (4,4) (2,2) (0,1): GaussianBlur(radius), 'RGBa' -> 'RGBA', `repeats` alpha_composites onto the
+ * accumulator; convert('RGB').  Where mask is 0 out is image exactly.  scratch: ofx_fill_mask_input_scratch_bytes(B, H, W)
+ * bytes, 16-byte aligned, distinct from the three images.  The limits of ofx_gaussian_blur_rgba_u8 apply. */
+size_t ofx_fill_mask_input_scratch_bytes(int B, int H, int W);
+int ofx_fill_mask_input(const uint8_t* image_bgr, const uint8_t* mask, uint8_t* out_bgr, void* scratch, int B, int H, int W,
+                        void* stream);
+
 /* GroupNorm(groups, C, eps, affine) of an NHWC fp32 tensor [B,HW,C] (ldm/modules/diffusionmodules/model.py:40-41,
  * `Normalize` = 32 groups, eps 1e-6), optionally followed by x * sigmoid(x) (`nonlinearity`, :35-37): the pair in front
  * of every convolution of the VAE encoder.  gamma / beta: [C] or NULL.  Statistics in f64.  out may alias x.

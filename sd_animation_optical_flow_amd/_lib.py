@@ -96,6 +96,9 @@ SIGNATURES = {
     "ofx_gaussian_blur_u8": (_i, [_p, _p, _p, _i, _i, _i, _f, _p]),
     "ofx_resize_bicubic_u8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "ofx_sd_handoff": (_i, [_p] * 9 + [_i] * 5 + [_p]),
+    "ofx_gaussian_blur_rgba_u8": (_i, [_p, _p, _p, _i, _i, _i, _f, _p]),
+    "ofx_fill_mask_input_scratch_bytes": (_z, [_i, _i, _i]),
+    "ofx_fill_mask_input": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "ofx_detect_edges_scratch_bytes": (_z, [_i, _i, _i]),
     "ofx_detect_edges": (_i, [_p, _p, _p, _z, _i, _i, _i, _i, _p]),
     "ofx_canny_u8_scratch_bytes": (_z, [_i, _i, _i]),

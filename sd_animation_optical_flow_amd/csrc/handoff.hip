@@ -15,13 +15,11 @@
 
 #include <cmath>
 
-namespace {
-
 // ------------------------------------------------------------------------------------------
 // Pillow GaussianBlur on an 8-bit single-channel image
 // ------------------------------------------------------------------------------------------
 // BoxBlur.c:_gaussian_blur_radius (all locals are C floats there)
-float gaussian_box_radius(float radius, int passes) {
+float ofx_gaussian_box_radius(float radius, int passes) {
     float sigma2, L, l, a;
     sigma2 = radius * radius / passes;
     L = (float)std::sqrt(12.0 * sigma2 + 1.0);
@@ -30,6 +28,15 @@ float gaussian_box_radius(float radius, int passes) {
     a /= 6 * (sigma2 - (l + 1) * (l + 1));
     return l + a;
 }
+
+void ofx_gaussian_box_weights(float radius, int passes, int* r, unsigned* ww, unsigned* fw) {
+    const float fr = ofx_gaussian_box_radius(radius, passes);
+    *r = (int)fr;
+    *ww = (unsigned)((float)(1u << 24) / (fr * 2 + 1));               // ImagingHorizontalBoxBlur
+    *fw = ((1u << 24) - (unsigned)(*r * 2 + 1) * *ww) / 2;
+}
+
+namespace {
 
 // one workgroup per image row: the row lives in LDS, `passes` extended-box passes ping-pong between two copies
 // (ImagingLineBoxBlur8: replicated edges, out = (acc*ww + (left+right)*fw + 2^23) >> 24 in uint32)
@@ -53,23 +60,6 @@ __global__ __launch_bounds__(256) void box_blur_rows_kernel(const uint8_t* __res
         uint8_t* t = a; a = b; b = t;
     }
     for (int x = threadIdx.x; x < W; x += 256) out[base + x] = a[x];
-}
-
-// out[b][x][y] = in[b][y][x]
-__global__ __launch_bounds__(256) void transpose_u8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int H, int W) {
-    __shared__ uint8_t tile[32][33];
-    const long b = blockIdx.z;
-    const int x0 = blockIdx.x * 32, y0 = blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-    for (int j = ty; j < 32; j += 8) {
-        const int y = y0 + j, x = x0 + tx;
-        if (y < H && x < W) tile[j][tx] = in[(b * H + y) * (long)W + x];
-    }
-    __syncthreads();
-    for (int j = ty; j < 32; j += 8) {
-        const int x = x0 + j, y = y0 + tx;
-        if (y < H && x < W) out[(b * W + x) * (long)H + y] = tile[tx][j];
-    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -138,11 +128,6 @@ __global__ __launch_bounds__(256) void resample_cols_kernel(const uint8_t* __res
 // ------------------------------------------------------------------------------------------
 // composite + normalisation + conditioning tensors
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned div255(unsigned a) {   // Paste.c DIV255
-    const unsigned tmp = a + 128u;
-    return ((tmp >> 8) + tmp) >> 8;
-}
-
 __global__ __launch_bounds__(256) void handoff_pixels_kernel(const uint8_t* __restrict__ image_bgr, const uint8_t* __restrict__ ref_bgr,
                                                              const uint8_t* __restrict__ mask, float* __restrict__ image,
                                                              float* __restrict__ cond_image, float* __restrict__ cond_mask, long HW,
@@ -156,7 +141,7 @@ __global__ __launch_bounds__(256) void handoff_pixels_kernel(const uint8_t* __re
 #pragma unroll
         for (int c = 0; c < 3; ++c) {                        // output channel c = R,G,B <- input channel 2-c of BGR
             const unsigned a = image_bgr[i * 3 + (2 - c)], r = ref_bgr[i * 3 + (2 - c)];
-            const unsigned v = div255(a * (255u - m) + r * m);
+            const unsigned v = ofx_div255(a * (255u - m) + r * m);
             const float f = (float)v / 127.5f - 1.0f;
             image[(b * 3 + c) * HW + p] = f;
             cond_image[(b * 3 + c) * HW + p] = f * keep;
@@ -199,15 +184,14 @@ int ofx_gaussian_blur_u8(const uint8_t* in, uint8_t* out, uint8_t* scratch, int 
     OFX_REQUIRE(scratch && scratch != in && scratch != out, OFX_EINVAL);
     OFX_REQUIRE(2L * std::max(H, W) <= 60 * 1024, OFX_EINVAL);                       // a row (and a column) fits LDS twice
     const int passes = 3;
-    const float fr = gaussian_box_radius(radius, passes);
-    const int r = (int)fr;
-    const unsigned ww = (unsigned)((float)(1u << 24) / (fr * 2 + 1));               // ImagingHorizontalBoxBlur
-    const unsigned fw = ((1u << 24) - (unsigned)(r * 2 + 1) * ww) / 2;
+    int r;
+    unsigned ww, fw;
+    ofx_gaussian_box_weights(radius, passes, &r, &ww, &fw);
     OfxProfScope prof("gaussian_blur_u8", s);
     hipLaunchKernelGGL(box_blur_rows_kernel, dim3((unsigned)((long)B * H)), dim3(256), (size_t)2 * W, s, in, out, W, r, ww, fw, passes);
-    hipLaunchKernelGGL(transpose_u8_kernel, dim3(ofx_cdiv(W, 32), ofx_cdiv(H, 32), B), dim3(256), 0, s, out, scratch, H, W);
+    hipLaunchKernelGGL(ofx_transpose_tile_kernel<uint8_t>, dim3(ofx_cdiv(W, 32), ofx_cdiv(H, 32), B), dim3(256), 0, s, out, scratch, H, W);
     hipLaunchKernelGGL(box_blur_rows_kernel, dim3((unsigned)((long)B * W)), dim3(256), (size_t)2 * H, s, scratch, scratch, H, r, ww, fw, passes);
-    hipLaunchKernelGGL(transpose_u8_kernel, dim3(ofx_cdiv(H, 32), ofx_cdiv(W, 32), B), dim3(256), 0, s, scratch, out, W, H);
+    hipLaunchKernelGGL(ofx_transpose_tile_kernel<uint8_t>, dim3(ofx_cdiv(H, 32), ofx_cdiv(W, 32), B), dim3(256), 0, s, scratch, out, W, H);
     return ofx_launch_status();
 }
 

@@ -112,6 +112,12 @@ int ofx_attention_flash_bnhd_launch(const float* q, int ldq, const float* k, int
                                     long bias_bstride, float* out, int ldo, int B, int H, int Nq, int Nk, int D, float scale, int precision,
                                     hipStream_t s);
 
+// handoff.hip (compiled without FMA contraction): BoxBlur.c:_gaussian_blur_radius, the fractional box radius whose `passes`-fold
+// application approximates GaussianBlur(radius), and ImagingHorizontalBoxBlur's weights from it: the integer radius r, the
+// 2^24-scaled weight ww of a full tap and fw of the two fractional far taps.  Shared with fill.hip's 4-channel blur
+float ofx_gaussian_box_radius(float radius, int passes);
+void ofx_gaussian_box_weights(float radius, int passes, int* r, unsigned* ww, unsigned* fw);
+
 // corr.hip / net_misc.hip: internal launchers used by the RAFT engine
 int ofx_local_corr_launch(const float* f1, const float* f2, const float* coords, float* out, long sb, long sn,
                           long sc, long sp, int B, int H1, int W1, int H2, int W2, int C, int N, int r, float scale,
@@ -184,6 +190,31 @@ __device__ __forceinline__ float ofx_tanh(float x) {
     return (t - 1.0f) * __builtin_amdgcn_rcpf(t + 1.0f);
 }
 #endif
+
+// Pillow's DIV255 (Paste.c): a / 255 rounded, exact for a <= 255 * 255
+__device__ __forceinline__ unsigned ofx_div255(unsigned a) {
+    const unsigned tmp = a + 128u;
+    return ((tmp >> 8) + tmp) >> 8;
+}
+
+// out[b][x][y] = in[b][y][x] for pixels of type T, a 32 x 32 tile per workgroup of 256 threads; grid (cdiv(W,32), cdiv(H,32), B):
+// the step between the horizontal and the vertical passes of the Pillow blurs (handoff.hip: 1-byte pixels, fill.hip: 4-byte)
+template <typename T>
+__global__ __launch_bounds__(256) void ofx_transpose_tile_kernel(const T* __restrict__ in, T* __restrict__ out, int H, int W) {
+    __shared__ T tile[32][33];
+    const long b = blockIdx.z;
+    const int x0 = blockIdx.x * 32, y0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
+    for (int j = ty; j < 32; j += 8) {
+        const int y = y0 + j, x = x0 + tx;
+        if (y < H && x < W) tile[j][tx] = in[(b * H + y) * (long)W + x];
+    }
+    __syncthreads();
+    for (int j = ty; j < 32; j += 8) {
+        const int x = x0 + j, y = y0 + tx;
+        if (y < H && x < W) out[(b * W + x) * (long)H + y] = tile[tx][j];
+    }
+}
 
 // Keys cubic weights, A = -0.75 (same polynomial form as OpenCV's interpolateCubic)
 __device__ __forceinline__ void ofx_cubic_coeffs(float t, float w[4]) {

@@ -16,6 +16,7 @@ Same names, argument meaning and mutation behaviour as the reference functions t
     expand_mask(mask, ori_image)                     ofgen_keyframe_inpaint.py:968-973
     PDCNetAux                                        ofgen_keyframe_inpaint.py:549-653  (+ .npy pair cache)
     compose_warp_and_mask                            ofgen_keyframe_inpaint.py:995-1027 (greedy multi-reference)
+    strip_inputs_self_attn / strip_inputs_both       ofgen_keyframe_inpaint.py:823-831, 929-937 (device tensors)
 
 numpy in / numpy out like the reference; every computation is a HIP kernel call (ops.py).  The
 `*_device` variants keep tensors in HBM for callers that chain steps.
@@ -243,6 +244,46 @@ def compose_warp_and_mask(flow_mat: np.ndarray, ai_frames: Sequence[np.ndarray],
         mask2 = ops.expand_mask(mask2.contiguous(), _dev(original_frame, dev)[None], 20, 7)
     np.copyto(flow_mat, fm.cpu().numpy())
     return ret[0].cpu().numpy(), mask2[0].cpu().numpy(), order
+
+
+# --------------------------------------------------------------------------------------------------
+# the wide images of the `self_attn` and `both` modes: the frame to repaint and its reference frames side by side
+# --------------------------------------------------------------------------------------------------
+def _strip(first: torch.Tensor, ai_frames: Sequence, device) -> torch.Tensor:
+    """[h,w,...] tensors side by side along the width: `first`, then every AI frame."""
+    parts = [first] + [_dev(f, device) for f in ai_frames]
+    if any(p.dtype != torch.uint8 or tuple(p.shape) != tuple(first.shape) for p in parts):
+        raise RuntimeError("the frames of a strip must be uint8 and of one shape")
+    return torch.cat(parts, dim=1)
+
+
+def strip_inputs_self_attn(raw_frame, ai_frames: Sequence, device="cuda") -> Tuple[torch.Tensor, torch.Tensor]:
+    """generate_ai_frame_with_ref_self_attn's inputs (ofgen_keyframe_inpaint.py:823-831): raw_frame and the reference frames'
+    AI frames, BGR uint8 [h,w,3] -> (all_frames uint8 [h, w*(n+1), 3], mask uint8 [h, w*(n+1)]) on the device; the mask is 255
+    over the first frame and 0 over the references.  What `sampler.img2img_inpaint(all_frames, None, mask, fill_masked=True)`
+    takes; the answer is the first w columns of its result (:858)."""
+    first = _dev(raw_frame, device)
+    all_frames = _strip(first, ai_frames, device)
+    h, w = first.shape[:2]
+    mask = torch.zeros((h, all_frames.shape[1]), dtype=torch.uint8, device=all_frames.device)
+    mask[:, :w] = 255
+    return all_frames, mask
+
+
+def strip_inputs_both(ret_frame, original_frame, mask2, ai_frames: Sequence, device="cuda"):
+    """generate_ai_frame_with_ref_both's inputs (ofgen_keyframe_inpaint.py:929-937): the warped frame `ret_frame`, the raw frame
+    `original_frame` (BGR uint8 [h,w,3]), `mask2` uint8 [h,w] (255 = repaint; `compose_warp_and_mask` returns both) and the
+    reference frames' AI frames -> (to_inpaint_frames, to_inpaint_ref_frames uint8 [h, w*(n+1), 3], to_inpaint_mask uint8
+    [h, w*(n+1)]) on the device: the warped / raw frame in front of the AI frames, mask2 over the first frame and 0 elsewhere."""
+    ret = _dev(ret_frame, device)
+    frames = _strip(ret, ai_frames, device)
+    ref_frames = _strip(_dev(original_frame, device), ai_frames, device)
+    m2 = _dev(mask2, device)
+    if m2.dtype != torch.uint8 or tuple(m2.shape) != tuple(ret.shape[:2]) or tuple(ref_frames.shape) != tuple(frames.shape):
+        raise RuntimeError("strip_inputs_both: mask2 must be uint8 [h,w] and original_frame of ret_frame's shape")
+    mask = torch.zeros(tuple(frames.shape[:2]), dtype=torch.uint8, device=frames.device)
+    mask[:, :ret.shape[1]] = m2
+    return frames, ref_frames, mask
 
 
 # --------------------------------------------------------------------------------------------------

@@ -707,6 +707,35 @@ def sd_handoff(image_bgr: torch.Tensor, reference_bgr: torch.Tensor, image_mask:
     return image, cond_image, cond_mask, latmask, cml
 
 
+def gaussian_blur_rgba_u8(img: torch.Tensor, radius: float) -> torch.Tensor:
+    """uint8 [B,H,W,4] -> PIL.ImageFilter.GaussianBlur(radius) of every 4-channel image, the channels alike (what Pillow does to
+    'RGBa' / 'RGBA'); the cost does not depend on the radius.  See ofx_gaussian_blur_rgba_u8 in include/ofx.h for the limits."""
+    m = _chk(img, "img", torch.uint8)
+    if m.dim() != 4 or m.shape[3] != 4:
+        raise RuntimeError("gaussian_blur_rgba_u8: img must be [B,H,W,4]")
+    B, H, W, _ = m.shape
+    out = torch.empty_like(m)
+    scratch = torch.empty_like(m)
+    check(_lib.lib().ofx_gaussian_blur_rgba_u8(_ptr(m), _ptr(out), _ptr(scratch), B, H, W, float(radius), _stream()),
+          "ofx_gaussian_blur_rgba_u8")
+    return out
+
+
+def fill_mask_input(image_bgr: torch.Tensor, image_mask: torch.Tensor) -> torch.Tensor:
+    """See ofx_fill_mask_input in include/ofx.h: image_bgr uint8 [B,H,W,3], image_mask uint8 [B,H,W] (the blurred mask, 255 =
+    repaint) -> the filled frame uint8 [B,H,W,3]."""
+    a = _chk(image_bgr, "image_bgr", torch.uint8)
+    m = _chk(image_mask, "image_mask", torch.uint8)
+    if a.dim() != 4 or a.shape[3] != 3 or tuple(m.shape) != tuple(a.shape[:3]):
+        raise RuntimeError("fill_mask_input: shapes must be image_bgr [B,H,W,3], image_mask [B,H,W]")
+    B, H, W, _ = a.shape
+    L = _lib.lib()
+    out = torch.empty_like(a)
+    scratch = torch.empty((L.ofx_fill_mask_input_scratch_bytes(B, H, W),), dtype=torch.uint8, device=a.device)
+    check(L.ofx_fill_mask_input(_ptr(a), _ptr(m), _ptr(out), _ptr(scratch), B, H, W, _stream()), "ofx_fill_mask_input")
+    return out
+
+
 def groupnorm(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], groups: int = 32, eps: float = 1e-6,
               silu: bool = False, out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
     """GroupNorm(groups, C, eps, affine) of an NHWC tensor [B,H,W,C] (+ x * sigmoid(x) when silu): `Normalize` /

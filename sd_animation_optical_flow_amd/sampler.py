@@ -340,8 +340,8 @@ def img2img_inpaint(unet, vae_encoder, vae_decoder, image_bgr, reference_bgr, ma
                     unconditional_context: Optional[torch.Tensor], *, denoising_strength: float = 0.05, ddim_steps: int = 50,
                     mask_blur: float = 16, unconditional_guidance_scale: float = 7.0, guidance_schedule_func: Callable = lambda p: 0.1,
                     noise: Optional[Dict[str, torch.Tensor]] = None, generator: Optional[torch.Generator] = None, control=None,
-                    reference_kv=(), sampler: Optional[GuidedDDIMSampler] = None):
-    """`GuidedLDM.img2img_inpaint` with a reference frame (guided_ldm_inpainting.py:262-345), eta = 0: image_bgr / reference_bgr
+                    reference_kv=(), sampler: Optional[GuidedDDIMSampler] = None, fill_masked: bool = False):
+    """`GuidedLDM.img2img_inpaint` (guided_ldm_inpainting.py:262-345), eta = 0.  With a reference frame: image_bgr / reference_bgr
     uint8 [H,W,3] (cv2 channel order) and mask uint8 [H,W] (255 = repaint) as `handoff.prepare_inpaint_inputs` takes them, context /
     unconditional_context [1,M,context_dim] device tensors (`text_encoder.ClipTextEncoder.conditioning` makes both from a prompt pair) ->
         (x_samples clipped to [-1,1] f32 [1,3,H,W],  image f32 [1,3,H,W],  init_latent_decoded clipped)
@@ -351,22 +351,33 @@ def img2img_inpaint(unet, vae_encoder, vae_decoder, image_bgr, reference_bgr, ma
     noise: explicit tensors under the keys "init" and "cond" (the two encoder samples, [B,4,h,w]), "x1" (stochastic_encode's,
     [B,4,h,w]) and "step" (`decode`'s step_noise, [t_enc,B,4,h,w]); a key left out is drawn from `generator` on the device, in that
     order (init, cond, x1, step), each with one torch.randn.
-    reference_bgr None is the PIL-blur `fill_mask_input` path: NotImplementedError.  t_enc == 0 (the default strength 0.05 needs at
-    least 20 steps) is a ValueError: the reference would run zero steps and index an empty range.  Both raise before any launch.
+    reference_bgr None with fill_masked=True is the path without a reference (`reference_img is None`, :295-296, :310-312; what the
+    `self_attn` and `both` modes of generate_ai_frame_with_ref run on a strip of frames): `image` is `handoff.fill_mask_input` of
+    the frame, init_latent = (1 - nmask) * init_latent + nmask * noise["fill"] ([B,4,h,w], drawn between "init" and "cond":
+    init, fill, cond, x1, step), denoising_strength becomes 1 (t_enc = int(0.999 * ddim_steps)) and the final blend uses that
+    noised init_latent.  reference_bgr None without fill_masked is a NotImplementedError, fill_masked with a reference or
+    noise["fill"] without fill_masked a ValueError.  t_enc == 0 (the default strength 0.05 needs at least 20 steps) is a
+    ValueError: the reference would run zero steps and index an empty range.  All raise before any launch.
     `sampler`: a GuidedDDIMSampler over `unet` to reuse (its `last_kv_hists` is then the caller's to read)."""
-    if reference_bgr is None:
-        raise NotImplementedError("reference_bgr=None is the reference's fill_mask_input path (PIL blurs on the host): not built")
+    if reference_bgr is None and not fill_masked:
+        raise NotImplementedError("reference_bgr=None is the reference's fill_mask_input path: ask for it with fill_masked=True")
+    if fill_masked and reference_bgr is not None:
+        raise ValueError("fill_masked=True is the path without a reference frame: reference_bgr must be None")
+    if fill_masked:
+        denoising_strength = 1                                                          # (:312)
     t_enc = int(min(denoising_strength, 0.999) * ddim_steps)
     if t_enc <= 0:
         raise ValueError(f"denoising_strength={denoising_strength} at {ddim_steps} steps gives t_enc = 0: no step to run")
     noise = dict(noise or {})
-    unknown = set(noise) - {"init", "cond", "x1", "step"}
+    unknown = set(noise) - {"init", "fill", "cond", "x1", "step"}
     if unknown:
         raise ValueError(f"noise has unknown keys {sorted(unknown)}")
+    if "fill" in noise and not fill_masked:
+        raise ValueError("noise['fill'] without fill_masked")
     smp = sampler if sampler is not None else GuidedDDIMSampler(unet)
     smp.make_schedule(ddim_steps, 0.0)
     dev = unet.device
-    inp = prepare_inpaint_inputs(image_bgr, reference_bgr, mask, mask_blur=mask_blur, device=dev)
+    inp = prepare_inpaint_inputs(image_bgr, reference_bgr, mask, mask_blur=mask_blur, device=dev, fill_masked=fill_masked)
     image, latmask = inp["image"], inp["latmask"]
     B, _, h, w = latmask.shape
 
@@ -375,9 +386,13 @@ def img2img_inpaint(unet, vae_encoder, vae_decoder, image_bgr, reference_bgr, ma
             return _latent(noise[key], f"noise[{key!r}]", shape) if len(shape) == 4 else noise[key]
         return torch.randn(shape, generator=generator, device=dev, dtype=torch.float32)
 
-    n_init, n_cond = draw("init", (B, 4, h, w)), draw("cond", (B, 4, h, w))
+    n_init = draw("init", (B, 4, h, w))
+    n_fill = draw("fill", (B, 4, h, w)) if fill_masked else None
+    n_cond = draw("cond", (B, 4, h, w))
     n_x1, n_step = draw("x1", (B, 4, h, w)), draw("step", (t_enc, B, 4, h, w))
     init_latent = vae_encoder.get_first_stage_encoding(image, n_init)
+    if fill_masked:
+        init_latent = final_blend(init_latent, n_fill, latmask)                         # (:311)
     cond_latent = vae_encoder.get_first_stage_encoding(inp["conditioning_image"], n_cond)
     c_concat = torch.cat([inp["conditioning_mask_latent"], cond_latent], dim=1)
     x1 = smp.stochastic_encode(init_latent, t_enc, n_x1)
