@@ -495,6 +495,266 @@ struct Streams {
     int join_armed(int i) const { OFX_HIP_CHECK(hipStreamWaitEvent(main, r->ev_join[i], 0)); return 0; }
 };
 
+// --------------------------------------------------------------------------------------------
+// What the four forwards (plain and indexed pairs, of either network) share around their encoders and recurrences: the parsed call,
+// the correlation section of the workspace, the pair map, the correlation stage, the output tail and the buffer registration.  Every
+// piece is parametrised by data (D, counts, pointers, a flag mask), never by which network calls it.
+
+// One call: the arguments as a C entry point received them, then what parse_call derives from them
+struct Call {
+    const uint8_t* image1 = nullptr;   // u8 [n1][H][W][3]; the indexed-pairs call: all n_images frames
+    const uint8_t* image2 = nullptr;   // u8 [n2][H][W][3]; the indexed-pairs call: unused
+    int n_images = 0;                  // the indexed-pairs call: pair b = frames (idx1[b], idx2[b])
+    const int *idx1 = nullptr, *idx2 = nullptr;
+    int B = 0, H = 0, W = 0, iters = 0, flags = 0;
+    float *flow_up = nullptr, *flow_low = nullptr;
+    // the first n_warp pairs are warped (all B of a plain call; the indexed-pairs call of the forward-backward confidence, whose reverse
+    // flows need no warp, fewer), the rest take the plain upsample
+    const uint8_t* warp_frame = nullptr;
+    float warp_sign = 1.0f;
+    int n_warp = 0;
+    uint8_t* warped = nullptr;
+    void* workspace = nullptr;
+    size_t workspace_bytes = 0;
+    hipStream_t s = nullptr;
+
+    int h = 0, w = 0;      // the 1/8 grid
+    long N = 0, M = 0;     // its pixels: of one pair, of all B
+    int n1 = 0, n2 = 0;    // images on either side: B, 1 when shared, all n_images of the indexed-pairs call
+    int bgr = 0, prec = OFX_PREC_FP32;
+    bool sh1 = false, sh2 = false, alt = false, warm = false, serial = false, sepst = false;
+    // Context-encoder BatchNorm.  Default: the running statistics, folded into the convolutions (a model in .eval(), as PDCNet's
+    // own code and canonical RAFT inference run it).  OFX_RAFT_BN_BATCH: the statistics of the image itself -- what
+    // `RAFT_2` computes AS WRITTEN: the reference never calls .eval() (ofgen_keyframe_inpaint.py:47-60), so its
+    // BatchNorm2d layers (RAFT/core/raft.py:55, extractor.py:118-192) normalise with the statistics of the call's batch,
+    // and every call is one image.  Each image of a batch is normalised by itself here (= B reference calls).
+    bool bnb = false;
+};
+
+// Every argument check of the four forwards, then the derived half of *c.  pairs: the indexed-pairs call; unsupported: the flags the
+// network does not take.  Of several violations OFX_EINVAL is reported before OFX_EALIGN (and the workspace's OFX_ENOMEM, known
+// only after the network's carve, last).
+int parse_call(Call* call, bool pairs, int unsupported) {
+    Call& c = *call;
+    OFX_REQUIRE(c.image1 && c.workspace && (pairs ? c.idx1 && c.idx2 && c.flow_up : c.image2 && (c.flow_up || c.warped)), OFX_EINVAL);
+    OFX_REQUIRE(!(c.flags & OFX_RAFT_FLOW_INIT) || c.flow_low, OFX_EINVAL);   // flow_low carries the initial flow in
+    if (c.warped || c.warp_frame || c.n_warp) {
+        OFX_REQUIRE(c.warp_frame && c.warped && c.n_warp > 0 && c.n_warp <= c.B && (c.warp_sign == 1.0f || c.warp_sign == -1.0f), OFX_EINVAL);
+        OFX_REQUIRE(ofx_upsample_warp_ok(c.n_warp, c.H, c.W) && (((uintptr_t)c.warped) & 3u) == 0, OFX_EINVAL);
+    }
+    OFX_REQUIRE((!pairs || c.n_images > 0) && c.B > 0 && c.H >= 64 && c.W >= 64 && (c.H % 8) == 0 && (c.W % 8) == 0 && c.iters >= 1, OFX_EINVAL);
+    OFX_REQUIRE(!(c.flags & (unsupported | (pairs ? OFX_RAFT_SHARED_IMG1 | OFX_RAFT_SHARED_IMG2 : 0))), OFX_EINVAL);
+    for (int b = 0; pairs && b < c.B; ++b)
+        OFX_REQUIRE(c.idx1[b] >= 0 && c.idx1[b] < c.n_images && c.idx2[b] >= 0 && c.idx2[b] < c.n_images, OFX_EINVAL);
+    if (c.flags & OFX_RAFT_FLOW_INIT) OFX_REQUIRE((((uintptr_t)c.flow_low) & 7u) == 0, OFX_EALIGN);
+    OFX_REQUIRE((((uintptr_t)c.workspace) & 255u) == 0, OFX_EALIGN);
+    c.h = c.H / 8;
+    c.w = c.W / 8;
+    c.N = (long)c.h * c.w;
+    c.M = (long)c.B * c.N;
+    c.bgr = (c.flags & OFX_RAFT_BGR) ? 1 : 0;
+    c.prec = (c.flags & OFX_RAFT_BF16X6) ? OFX_PREC_BF16X6 : (c.flags & OFX_RAFT_BF16X3) ? OFX_PREC_BF16X3 : OFX_PREC_FP32;
+    c.sh1 = c.flags & OFX_RAFT_SHARED_IMG1;
+    c.sh2 = c.flags & OFX_RAFT_SHARED_IMG2;
+    c.alt = c.flags & OFX_RAFT_ALT_CORR;
+    c.warm = c.flags & OFX_RAFT_FLOW_INIT;
+    c.serial = c.flags & OFX_RAFT_SERIAL;
+    c.sepst = c.flags & OFX_RAFT_SEPARATE_STATS;
+    c.bnb = c.flags & OFX_RAFT_BN_BATCH;
+    c.n1 = pairs ? c.n_images : c.sh1 ? 1 : c.B;
+    c.n2 = pairs ? c.n_images : c.sh2 ? 1 : c.B;
+    return 0;
+}
+
+// The correlation section of a workspace: what the correlation stage and the lookups of either network read and write
+struct CorrWs {
+    float *fmap1, *fmap2, *f2l[LEVELS];
+    float* fmap2b;    // image-2 feature maps with rows in the blocked order of the volume's columns (corr.hip)
+    float* pyr[LEVELS];
+    int* idx_dev;     // image indices per pair for the device (image1's, then image2's; zeros for a shared frame), see make_pair_map
+    void* warp_pad;   // zero-bordered RGBX copy of the frame the tail warps (ofx_raft_forward_warp)
+};
+
+// n1 / n2 feature maps of D channels (n_images > 0, the indexed-pairs layout: n1 = n_images maps serve both sides, n2 = 0), the pooled
+// levels of image 2 (alt, the volume-free mode) or its blocked copy and the pyramid of B pairs, then idx_slots ints for the pair map
+void carve_corr(CorrWs* w, Carver& c, int D, int B, int H, int W, long n1, long n2, int n_images, bool alt, int idx_slots) {
+    const int h = H / 8, wd = W / 8;
+    const long N = (long)h * wd;
+    const long M = (long)B * N;
+    w->fmap1 = c.take((size_t)n1 * N * D);
+    w->fmap2 = n2 ? c.take((size_t)n2 * N * D) : w->fmap1;   // directly behind fmap1: fold_key lets the shared key frame's map land there
+    if (alt) {
+        // volume-free mode: the pooled levels of fmap2, once per unique image, and no pyramid at all
+        w->f2l[0] = w->fmap2;
+        for (int l = 1; l < LEVELS; ++l) w->f2l[l] = c.take((size_t)(n_images > 0 ? n_images : n2) * (h >> l) * (wd >> l) * D);
+    } else {
+        w->fmap2b = c.take((size_t)(n_images > 0 ? n_images : n2) * ofx_corr_slice_floats_l(h, wd) * D);
+        for (int l = 0; l < LEVELS; ++l) w->pyr[l] = c.take((size_t)M * ofx_corr_slice_floats_l(h >> l, wd >> l));
+    }
+    w->idx_dev = idx_slots ? (int*)c.take((size_t)idx_slots) : nullptr;
+    w->warp_pad = c.take(ofx_warp_pad_bytes(H, W) / sizeof(float) + 4);
+}
+
+// Which image of fmap1 / fmap2 each pair reads: device arrays for the tiled lookup and the split-plane volume (null = pair b reads image
+// b), and the same on the host (arrays of the indexed-pairs call, or the shared flags) for the per-pixel kernel and the per-pair GEMMs
+struct PairMap {
+    const int *d1 = nullptr, *d2 = nullptr, *h1 = nullptr, *h2 = nullptr;
+    bool sh1 = false, sh2 = false;
+    // from one pair's image to the next, given the size of one: nothing where the pairs share the image or find it by index
+    long step1(long per_image) const { return sh1 || h1 ? 0 : per_image; }
+    long step2(long per_image) const { return sh2 || h2 ? 0 : per_image; }
+};
+
+// dev1 / dev2: the device reads that side's indices -- the lists of the indexed-pairs call, copied into idx_dev; zeros for a shared
+// frame (the image index of every pair)
+int make_pair_map(PairMap* pm, const Call& c, int* idx_dev, bool dev1, bool dev2) {
+    pm->h1 = c.idx1; pm->h2 = c.idx2;
+    pm->sh1 = c.sh1; pm->sh2 = c.sh2;
+    if (c.idx1) {
+        if (dev1) OFX_HIP_CHECK(hipMemcpyAsync(idx_dev, c.idx1, sizeof(int) * c.B, hipMemcpyHostToDevice, c.s));
+        if (dev2) OFX_HIP_CHECK(hipMemcpyAsync(idx_dev + c.B, c.idx2, sizeof(int) * c.B, hipMemcpyHostToDevice, c.s));
+        pm->d1 = dev1 ? idx_dev : nullptr; pm->d2 = dev2 ? idx_dev + c.B : nullptr;
+    } else if ((dev1 && c.sh1) || (dev2 && c.sh2)) {
+        OFX_HIP_CHECK(hipMemsetAsync(idx_dev, 0, sizeof(int) * c.B, c.s));
+        pm->d1 = dev1 && c.sh1 ? idx_dev : nullptr; pm->d2 = dev2 && c.sh2 ? idx_dev : nullptr;
+    }
+    return 0;
+}
+
+// OFX_LOCAL_CORR_NO_TILED=1: every volume-free lookup of the engine on the per-pixel kernel of ofx_local_corr_fwd (diagnostic)
+static bool local_corr_tiled() {
+    static const bool off = [] { const char* e = getenv("OFX_LOCAL_CORR_NO_TILED"); return e && *e && *e != '0'; }();
+    return !off;
+}
+
+// correlation features of all LEVELS levels at coords, without a volume, into the lookup rows (ld floats per pixel)
+static int alt_lookup(const float* fmap1, float* const* f2l, const PairMap& ix, const float* coords, float* corr, int ld, int B, int h, int w,
+                      int D, int radius, hipStream_t s) {
+    const float scale = 1.0f / std::sqrt((float)D);
+    if (local_corr_tiled()) return ofx_local_corr_tiled_launch(fmap1, f2l, ix.d1, ix.d2, coords, corr, ld, B, h, w, D, radius, LEVELS, scale, s);
+    const long N = (long)h * w;
+    const int rd2 = (2 * radius + 1) * (2 * radius + 1);
+    const bool indexed = ix.h1 || ix.h2 || ix.sh1 || ix.sh2;
+    for (int l = 0; l < LEVELS; ++l) {
+        const long n2 = (long)(h >> l) * (w >> l) * D;
+        for (int b = 0; b < (indexed ? B : 1); ++b) {   // the per-pixel kernel pairs image b with image b: one launch per indexed pair
+            const long i1 = ix.h1 ? ix.h1[b] : ix.sh1 ? 0 : b, i2 = ix.h2 ? ix.h2[b] : ix.sh2 ? 0 : b;
+            const int st = ofx_local_corr_launch(fmap1 + i1 * N * D, f2l[l] + i2 * n2, coords + (long)b * N * 2, corr + (long)b * N * ld + (long)l * rd2,
+                                                 N * ld, 0, 1, ld, indexed ? 1 : B, h, w, h >> l, w >> l, D, 1, radius, scale, 1.0f / (float)(1 << l), s);
+            if (st) return st;
+        }
+    }
+    return 0;
+}
+
+// The all-pairs volume as a batched 1x1 convolution (conv.hip's generic GEMM), for both networks: level 0 (and level 1 out of the
+// accumulators where the shape allows: level 0 is then never read back) of nz pairs.  f1: rows [N][D] at a_zs floats per pair; f2b:
+// image 2's rows in the blocked order of the volume's columns [Nb][D] at w_zs per pair -- a zero stride broadcasts a shared feature
+// map across the batch.  *fused tells the pooling launch whether level 1 is already there.
+// One pair at a time (the indexed-pairs calls) passes nz = 1 and that pair's own pointers: conv.hip reads nz as `nz > 1 ? nz : 1` and
+// drops the three batch strides of a single z, and the pool's stride is only ever multiplied by z = 0 -- the launch is the one a
+// descriptor without any of them gives.
+static int volume_gemm(const float* f1, long a_zs, const float* f2b, long w_zs, float* l0, float* l1, int nz, int h, int w, int D,
+                       int precision, bool* fused, hipStream_t s) {
+    const long N = (long)h * w, Nb = ofx_corr_slice_floats_l(h, w), slice1 = ofx_corr_slice_floats_l(h >> 1, w >> 1);
+    ofx_conv_desc d{};
+    d.in0 = f1; d.ld0 = D; d.c0 = D;
+    d.w = f2b;
+    d.out = l0; d.ldo = (int)Nb;
+    d.nz = nz; d.a_zs = a_zs; d.w_zs = w_zs; d.o_zs = N * Nb;
+    d.B = 1; d.Hin = h; d.Win = w; d.Hout = h; d.Wout = w; d.Cout = (int)Nb;
+    d.KH = 1; d.KW = 1; d.stride = 1;
+    d.act = OFX_ACT_NONE; d.epi = OFX_EPI_PLAIN;
+    d.precision = precision;
+    *fused = ofx_corr_volpool_ok(h, w) && Nb % 128 == 0 && N * slice1 * 4 < (1L << 31) - 64;   // (every arithmetic since round 4)
+    ConvExtra x;
+    x.alpha = 1.0f / std::sqrt((float)D);
+    if (*fused) x.pool = {l1, N * slice1, (w + 7) >> 3, ((w >> 1) + 7) >> 3, (int)slice1};
+    return ofx_conv2d_ex(&d, &x, s);
+}
+
+// The correlation stage: what the lookups of the recurrence read, from the feature maps of D channels.  Three forms --
+//   c.alt        volume-free: the pooled levels of every image-2 map, and no volume
+//   planes > 0   the volume on the A-stationary kernel (corr_split.hip): every image split into `planes` bf16 planes (1: exact fp32)
+//                once per role -- rows scaled in pixel order, columns in quad order -- in plane_scratch, then ONE launch over all pairs
+//   planes == 0  the volume on conv.hip's generic GEMM: the blocked copy of every image-2 map, one batched launch -- or, where the pairs
+//                find their images by index, one N x Nb GEMM per pair straight from the shared feature maps
+// and, for both volume forms, the pooling launch of the remaining pyramid levels.  The caller decides `planes`.
+int correlate(const Call& c, const CorrWs& ws, const PairMap& pm, int D, int prec, int planes, void* plane_scratch) {
+    const int B = c.B, h = c.h, w = c.w;
+    const long N = c.N;
+    hipStream_t s = c.s;
+    int st = 0;
+    if (c.alt) {
+        for (int l = 1; l < LEVELS && !st; ++l) st = ofx_avgpool2_nhwc(ws.f2l[l - 1], ws.f2l[l], c.n2, h >> (l - 1), w >> (l - 1), D, s);
+        return st;
+    }
+    bool fused = false;
+    if (planes) {
+        char* pl = (char*)plane_scratch;
+        const long ib = (long)ofx_corr_planes_bytes(h, w, planes);
+        st = ofx_corr_split_planes(ws.fmap1, pl, c.n1, h, w, planes, 0, 1.0f / std::sqrt((float)D), s);
+        if (!st) st = ofx_corr_split_planes(ws.fmap2, pl + ib * c.n1, c.n2, h, w, planes, 1, 1.0f, s);
+        if (!st)
+            st = ofx_corr_vol_split_launch(pl, pl + ib * c.n1, pm.d1, pm.d2, pm.step1(ib), pm.step2(ib), ws.pyr[0], ws.pyr[1], B, h, w, planes, s);
+        fused = true;
+    } else {
+        // the volume's columns in blocked order: permute the rows of the B operand once (6.3 MB per image)
+        const long Nb = ofx_corr_slice_floats_l(h, w), slice1 = ofx_corr_slice_floats_l(h >> 1, w >> 1);
+        st = ofx_corr_block_rows(ws.fmap2, ws.fmap2b, c.n2, h, w, D, s);
+        if (!st && !pm.h1)
+            st = volume_gemm(ws.fmap1, pm.step1(N * D), ws.fmap2b, pm.step2(Nb * D), ws.pyr[0], ws.pyr[1], B, h, w, D, prec, &fused, s);
+        for (int b = 0; b < B && !st && pm.h1; ++b)
+            st = volume_gemm(ws.fmap1 + (long)pm.h1[b] * N * D, 0, ws.fmap2b + (long)pm.h2[b] * Nb * D, 0, ws.pyr[0] + (long)b * N * Nb,
+                             ws.pyr[1] + (long)b * N * slice1, 1, h, w, D, prec, &fused, s);
+    }
+    if (!st) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused);
+    return st;
+}
+
+// The tail of a forward: the final coords1 upsampled to flow_up -- the convex upsample with the mask head's weights, upflow8
+// (utils/utils.py:80-82) with a null mask, as RAFT.forward does when up_mask is None -- with the backward warp of c.warp_frame in the same
+// pass for the first c.n_warp pairs (the flow is in registers right there; flow_up is then written only if wanted), and flow_low
+int finish_flow(const Call& c, const float* coords1, const float* mask, const void* warp_pad) {
+    const int B = c.B, h = c.h, w = c.w, nw = c.n_warp;
+    const long N = c.N;
+    int st = 0;
+    if (nw > 0)
+        st = mask ? ofx_upsample_warp_launch(coords1, mask, c.flow_up, warp_pad, c.warped, nw, h, w, c.warp_sign, c.s)
+                  : ofx_upflow8_warp_launch(coords1, c.flow_up, warp_pad, c.warped, nw, h, w, c.warp_sign, c.s);
+    if (!st && nw < B) {
+        if (!c.flow_up) return OFX_EINVAL;
+        st = mask ? ofx_upsample_flow(coords1 + (long)nw * N * 2, mask + (long)nw * N * 576, c.flow_up + (long)nw * N * 128, B - nw, h, w, c.s)
+                  : ofx_upflow8(coords1 + (long)nw * N * 2, c.flow_up + (long)nw * N * 128, B - nw, h, w, c.s);
+    }
+    if (st) return st;
+    if (c.flow_low) return ofx_coords_to_flow(coords1, c.flow_low, B, h, w, c.s);
+    return 0;
+}
+
+// The intermediates of a plain forward, by name (ofx_raft_buffer): feature maps of D channels, the recurrence's rows at their widths, the
+// pyramid levels in their blocked layout (ofx.h) unless the call was volume-free; mask only where the network has a mask head
+void register_buffers(ofx_raft* r, const Call& c, const CorrWs& ws, int D, float* hx, int hx_ld, float* coords1, float* corr, int corr_ld,
+                      float* mask) {
+    r->bufs.clear();
+    auto reg = [&](const char* k, float* p, size_t nf) { r->bufs[k] = std::make_pair((void*)p, nf); };
+    reg("fmap1", ws.fmap1, (size_t)c.n1 * c.N * D);
+    reg("fmap2", ws.fmap2, (size_t)c.n2 * c.N * D);
+    reg("hx", hx, (size_t)c.M * hx_ld);
+    reg("coords1", coords1, (size_t)c.M * 2);
+    reg("corr", corr, (size_t)c.M * corr_ld);
+    if (mask) reg("mask", mask, (size_t)c.M * 576);
+    if (!c.alt)
+        for (int l = 0; l < LEVELS; ++l) {
+            char nm[8];
+            snprintf(nm, sizeof nm, "pyr%d", l);
+            reg(nm, ws.pyr[l], (size_t)c.M * ofx_corr_slice_floats_l(c.h >> l, c.w >> l));
+        }
+}
+
+// --------------------------------------------------------------------------------------------
+// The basic network (raft-things.pth)
+
 struct EncBufs {
     void* sk = nullptr;      // split-K scratch of the stream this encoder chain runs on
     float *x0, *X, *Y, *R1, *R2, *R3;
@@ -510,7 +770,7 @@ struct EncBufs {
 static int run_encoder(ofx_raft* r, const std::string& enc, bool bn, const uint8_t* imgs, int n, int H, int W,
                        int bgr, const EncBufs& eb, float* out, int out_ld, bool split_tanh_relu, int relu_off, hipStream_t s,
                        int precision = OFX_PREC_FP32, bool separate_stats = false, const uint8_t* extra = nullptr) {
-    // `extra`: one more image appended to the chunk (the shared key frame riding with the frames: see raft_forward_impl)
+    // `extra`: one more image appended to the chunk (the shared key frame riding with the frames: see basic_forward)
     // `out`: [n*h*w][out_ld]; fnet writes 256 channels; cnet writes tanh(0:128) | relu(128:256)
     Launcher L(s, precision, eb.sk);
     const int H2 = H / 2, W2 = W / 2;
@@ -605,16 +865,11 @@ static int run_encoder(ofx_raft* r, const std::string& enc, bool bn, const uint8
 }
 
 // workspace layout shared by the size query and the forward
-struct RaftWs {
+struct RaftWs : CorrWs {
     EncBufs eb[3];    // [1], [2] only exist (else alias [0]) when the encoders may run concurrently
     void* sk[3];      // split-K scratch per stream (small batches only; null otherwise)
-    float *fmap1, *fmap2, *f2l[LEVELS];
-    float* fmap2b;    // image-2 feature maps with rows in the blocked order of the volume's columns (corr.hip)
     float* ctx;       // indexed-pairs mode: per-image context features [n][N][256] (tanh | relu halves)
-    int* idx_dev;     // indexed-pairs mode: image1 index per pair
-    float* pyr[LEVELS];
     float *hx, *gadd, *coords1, *frows, *corr, *c1, *corflo, *f1, *z, *rh, *mask;
-    void* warp_pad;   // zero-bordered RGBX copy of the frame the tail warps (ofx_raft_forward_warp)
     size_t bytes;
 };
 
@@ -653,19 +908,11 @@ static RaftWs carve(void* base, size_t cap, int B, int H, int W, int flags, int 
         n1 = n_images;
         n2 = 0;
         w.ctx = c.take((size_t)n_images * N * (HD + CD));
-        w.idx_dev = (int*)c.take((size_t)2 * B);   // image1 indices, then image2 indices
     }
-    w.fmap1 = c.take((size_t)n1 * N * FD);
-    w.fmap2 = n2 ? c.take((size_t)n2 * N * FD) : w.fmap1;
-    if (flags & OFX_RAFT_ALT_CORR) {
-        // volume-free mode: the pooled levels of fmap2, once per unique image, and no pyramid at all
-        w.f2l[0] = w.fmap2;
-        for (int l = 1; l < LEVELS; ++l) w.f2l[l] = c.take((size_t)(n_images > 0 ? n_images : n2) * (h >> l) * (wd >> l) * FD);
-        if (n_images == 0) w.idx_dev = (int*)c.take((size_t)B);   // all zeros: the image index of every pair of a shared key frame
-    } else {
-        w.fmap2b = c.take((size_t)(n_images > 0 ? n_images : n2) * ofx_corr_slice_floats_l(h, wd) * FD);
-        for (int l = 0; l < LEVELS; ++l) w.pyr[l] = c.take((size_t)M * ofx_corr_slice_floats_l(h >> l, wd >> l));
-    }
+    // index slots: the indexed-pairs call's image1 indices (ofx_ctx_gather reads them in either mode), then its image2 indices; the
+    // volume-free plain call's zeros for a shared frame
+    const bool alt = flags & OFX_RAFT_ALT_CORR;
+    carve_corr(&w, c, FD, B, H, W, n1, n2, n_images, alt, n_images > 0 ? 2 * B : alt ? B : 0);
     w.hx = c.take((size_t)M * HX_LD);
     w.gadd = c.take((size_t)M * GADD_LD);
     w.coords1 = c.take((size_t)M * 2);
@@ -677,51 +924,19 @@ static RaftWs carve(void* base, size_t cap, int B, int H, int W, int flags, int 
     w.z = c.take((size_t)M * HD);
     w.rh = c.take((size_t)M * HD);
     w.mask = c.take((size_t)M * 576);
-    w.warp_pad = c.take(ofx_warp_pad_bytes(H, W) / sizeof(float) + 4);
     w.bytes = c.off;
     return w;
 }
 
-// Which image of fmap1 / fmap2 each pair of a volume-free lookup reads: device arrays for the tiled kernel (null = pair b reads image
-// b), and the same on the host (arrays of the indexed-pairs call, or the shared flags) for the per-pixel kernel
-struct AltIdx {
-    const int *d1 = nullptr, *d2 = nullptr, *h1 = nullptr, *h2 = nullptr;
-    bool sh1 = false, sh2 = false;
-};
-
-// OFX_LOCAL_CORR_NO_TILED=1: every volume-free lookup of the engine on the per-pixel kernel of ofx_local_corr_fwd (diagnostic)
-static bool local_corr_tiled() {
-    static const bool off = [] { const char* e = getenv("OFX_LOCAL_CORR_NO_TILED"); return e && *e && *e != '0'; }();
-    return !off;
-}
-
-// correlation features of all LEVELS levels at coords, without a volume, into the lookup rows (ld floats per pixel)
-static int alt_lookup(const float* fmap1, float* const* f2l, const AltIdx& ix, const float* coords, float* corr, int ld, int B, int h, int w,
-                      int D, int radius, hipStream_t s) {
-    const float scale = 1.0f / std::sqrt((float)D);
-    if (local_corr_tiled()) return ofx_local_corr_tiled_launch(fmap1, f2l, ix.d1, ix.d2, coords, corr, ld, B, h, w, D, radius, LEVELS, scale, s);
-    const long N = (long)h * w;
-    const int rd2 = (2 * radius + 1) * (2 * radius + 1);
-    const bool indexed = ix.h1 || ix.h2 || ix.sh1 || ix.sh2;
-    for (int l = 0; l < LEVELS; ++l) {
-        const long n2 = (long)(h >> l) * (w >> l) * D;
-        for (int b = 0; b < (indexed ? B : 1); ++b) {   // the per-pixel kernel pairs image b with image b: one launch per indexed pair
-            const long i1 = ix.h1 ? ix.h1[b] : ix.sh1 ? 0 : b, i2 = ix.h2 ? ix.h2[b] : ix.sh2 ? 0 : b;
-            const int st = ofx_local_corr_launch(fmap1 + i1 * N * D, f2l[l] + i2 * n2, coords + (long)b * N * 2, corr + (long)b * N * ld + (long)l * rd2,
-                                                 N * ld, 0, 1, ld, indexed ? 1 : B, h, w, h >> l, w >> l, D, 1, radius, scale, 1.0f / (float)(1 << l), s);
-            if (st) return st;
-        }
-    }
-    return 0;
-}
-
 // everything after the feature / context encoders and the correlation volume: state init, the loop-invariant
-// GRU terms, `iters` refinement iterations, mask head, convex upsample
-// warm: flow_low holds the initial flow (OFX_RAFT_FLOW_INIT); it is read here and overwritten with the final flow at the end
-static int run_recurrence(ofx_raft* r, const RaftWs& ws, int B, int h, int w, int iters, bool alt, const AltIdx& aix,
-                          float* flow_up, float* flow_low, hipStream_t s, int precision, bool overlap, bool warm,
-                          uint8_t* warped = nullptr, float warp_sign = 1.0f, int n_warp = -1) {
-    const long N = (long)h * w;
+// GRU terms, `iters` refinement iterations, mask head (the convex upsample is finish_flow's)
+// c.warm: flow_low holds the initial flow (OFX_RAFT_FLOW_INIT); it is read here and overwritten with the final flow by finish_flow
+static int run_recurrence(ofx_raft* r, const RaftWs& ws, const Call& c, const PairMap& aix, bool overlap) {
+    const int B = c.B, h = c.h, w = c.w, iters = c.iters, precision = c.prec;
+    const bool alt = c.alt, warm = c.warm;
+    float* flow_low = c.flow_low;
+    hipStream_t s = c.s;
+    const long N = c.N;
     int st = 0;
     st = warm ? ofx_init_state_warm(ws.coords1, ws.frows, ws.hx, HX_LD, FLOW_OFF, false, flow_low, B, h, w, s)
               : ofx_init_state(ws.coords1, ws.frows, ws.hx, HX_LD, FLOW_OFF, B, h, w, s);
@@ -783,83 +998,470 @@ static int run_recurrence(ofx_raft* r, const RaftWs& ws, int B, int h, int w, in
             fork_on_kernel = fork_ev && !L.st;   // the flow head has one launch: it took the event unless the call failed
         }
     }
-    // mask head (update.py:122-125,135) on the final hidden state, then convex upsample
+    // mask head (update.py:122-125,135) on the final hidden state
     L.conv(C("mask0"), {.in0 = ws.hx, .ld0 = HX_LD, .c0 = HD, .out = ws.c1, .ldo = 256, .B = B, .Hin = h, .Win = w, .act = OFX_ACT_RELU});
     L.conv(C("mask2"), {.in0 = ws.c1, .ld0 = 256, .c0 = 256, .out = ws.mask, .ldo = 576, .B = B, .Hin = h, .Win = w});
-    if (L.st) return L.st;
-    // convex upsample -- with the backward warp of the AI key frame in the same pass when the caller asked for it: the flow is in
-    // registers right there, flow_up is then written only if wanted
-    // (n_warp: only the first n_warp pairs are warped -- the indexed-pairs call of the forward-backward confidence, whose reverse
-    // flows need no warp; the rest take the plain upsample)
-    const int nw = warped ? (n_warp < 0 ? B : std::min(n_warp, B)) : 0;
-    if (nw > 0) st = ofx_upsample_warp_launch(ws.coords1, ws.mask, flow_up, ws.warp_pad, warped, nw, h, w, warp_sign, s);
-    if (!st && nw < B) {
-        if (!flow_up) return OFX_EINVAL;
-        st = ofx_upsample_flow(ws.coords1 + (long)nw * N * 2, ws.mask + (long)nw * N * 576, flow_up + (long)nw * N * 128, B - nw, h, w, s);
-    }
-    if (st) return st;
-    if (flow_low) {
-        st = ofx_coords_to_flow(ws.coords1, flow_low, B, h, w, s);
-        if (st) return st;
-    }
-
-    return 0;
-}
-
-// The all-pairs volume as a batched 1x1 convolution (conv.hip's generic GEMM), for both networks: level 0 (and level 1 out of the
-// accumulators where the shape allows: level 0 is then never read back) of nz pairs.  f1: rows [N][D] at a_zs floats per pair; f2b:
-// image 2's rows in the blocked order of the volume's columns [Nb][D] at w_zs per pair -- a zero stride broadcasts a shared feature
-// map across the batch.  *fused tells the pooling launch whether level 1 is already there.
-// One pair at a time (the indexed-pairs calls) passes nz = 1 and that pair's own pointers: conv.hip reads nz as `nz > 1 ? nz : 1` and
-// drops the three batch strides of a single z, and the pool's stride is only ever multiplied by z = 0 -- the launch is the one a
-// descriptor without any of them gives.
-static int volume_gemm(const float* f1, long a_zs, const float* f2b, long w_zs, float* l0, float* l1, int nz, int h, int w, int D,
-                       int precision, bool* fused, hipStream_t s) {
-    const long N = (long)h * w, Nb = ofx_corr_slice_floats_l(h, w), slice1 = ofx_corr_slice_floats_l(h >> 1, w >> 1);
-    ofx_conv_desc d{};
-    d.in0 = f1; d.ld0 = D; d.c0 = D;
-    d.w = f2b;
-    d.out = l0; d.ldo = (int)Nb;
-    d.nz = nz; d.a_zs = a_zs; d.w_zs = w_zs; d.o_zs = N * Nb;
-    d.B = 1; d.Hin = h; d.Win = w; d.Hout = h; d.Wout = w; d.Cout = (int)Nb;
-    d.KH = 1; d.KW = 1; d.stride = 1;
-    d.act = OFX_ACT_NONE; d.epi = OFX_EPI_PLAIN;
-    d.precision = precision;
-    *fused = ofx_corr_volpool_ok(h, w) && Nb % 128 == 0 && N * slice1 * 4 < (1L << 31) - 64;   // (every arithmetic since round 4)
-    ConvExtra x;
-    x.alpha = 1.0f / std::sqrt((float)D);
-    if (*fused) x.pool = {l1, N * slice1, (w + 7) >> 3, ((w >> 1) + 7) >> 3, (int)slice1};
-    return ofx_conv2d_ex(&d, &x, s);
+    return L.st;
 }
 
 // The volume GEMM on the A-stationary kernel (corr_split.hip).  OFX_RAFT_VOL_BF16X3 / _BF16X6 ask for its split-bf16 forms alone (every
 // convolution stays fp32), the all-layer split modes take them along.  Its operands in fragment order live in the recurrence's scratch
 // (corr ... mask: dead until the first iteration).  0 = the generic batched GEMM of conv.hip (shapes the kernel does not take).
-static int volume_planes(int flags, int h, int w, long n_planes_images, const RaftWs& ws, long M, int nz) {
+static int volume_planes(const Call& c, const RaftWs& ws) {
+    if (c.alt) return 0;
+    const int flags = c.flags, h = c.h, w = c.w;
     // 1: the exact-fp32 form of the same A-stationary kernel (round 6: bit-identical to the generic batched GEMM it replaces, whole-line
     // stores, no operand re-fetch) -- the default wherever the shape allows; OFX_VOL_GENERIC=1 keeps the generic GEMM (diagnostic)
     const int planes = (flags & (OFX_RAFT_VOL_BF16X6 | OFX_RAFT_BF16X6)) ? 3 : (flags & (OFX_RAFT_VOL_BF16X3 | OFX_RAFT_BF16X3)) ? 2 : 1;
     static const bool generic = getenv("OFX_VOL_GENERIC") != nullptr;
-    if ((planes == 1 && generic) || !ofx_corr_volsplit_ok(h, w, FD) || !ofx_corr_volsplit_pays(nz, h, w, planes) || getenv("OFX_NO_VOLSPLIT")) return 0;
-    const size_t room = (size_t)((const char*)(ws.mask + M * 576) - (const char*)ws.corr);
-    return (size_t)n_planes_images * ofx_corr_planes_bytes(h, w, planes) <= room ? planes : 0;
+    if ((planes == 1 && generic) || !ofx_corr_volsplit_ok(h, w, FD) || !ofx_corr_volsplit_pays(c.B, h, w, planes) || getenv("OFX_NO_VOLSPLIT")) return 0;
+    const size_t room = (size_t)((const char*)(ws.mask + c.M * 576) - (const char*)ws.corr);
+    return (size_t)((long)c.n1 + c.n2) * ofx_corr_planes_bytes(h, w, planes) <= room ? planes : 0;
 }
 
-static int raft_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* image2, int B, int H, int W, int iters, int flags,
-                             float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign, uint8_t* warped, void* workspace,
-                             size_t workspace_bytes, void* stream);
+// the workspace of a parsed call, its split-K arrival counters at zero (the kernels leave them at zero)
+static int open_workspace(RaftWs* ws, const Call& c) {
+    *ws = carve(c.workspace, c.workspace_bytes, c.B, c.H, c.W, c.flags, c.n_images);
+    OFX_REQUIRE(ws->bytes <= c.workspace_bytes, OFX_ENOMEM);
+    for (int e = 0; e < 3; ++e)
+        if (ws->sk[e]) OFX_HIP_CHECK(hipMemsetAsync(ws->sk[e], 0, 65536, c.s));
+    return 0;
+}
 
-// the small network (raft.py:29-33, :48-51): its own builder, workspace and schedule, further down
-static int small_detect(const std::map<std::string, HostTensor>& sd);
-static int small_build(ofx_raft* r, const std::map<std::string, HostTensor>& sd);
-static size_t small_workspace_bytes(int B, int H, int W, int n_images);
-static size_t small_workspace_bytes_mode(int B, int H, int W, int flags, int n_images);
-static int small_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* image2, int B, int H, int W, int iters, int flags,
-                              float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign, uint8_t* warped, void* workspace,
-                              size_t workspace_bytes, void* stream);
-static int small_forward_pairs_impl(ofx_raft* r, const uint8_t* images, int n_images, const int* idx1, const int* idx2, int B, int H, int W,
-                                    int iters, int flags, float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign,
-                                    int n_warp, uint8_t* warped, void* workspace, size_t workspace_bytes, void* stream);
+static int basic_forward(ofx_raft* r, const Call& c) {
+    RaftWs ws;
+    int st = open_workspace(&ws, c);
+    if (st) return st;
+    const uint8_t *image1 = c.image1, *image2 = c.image2;
+    const int B = c.B, H = c.H, W = c.W, n1 = c.n1, n2 = c.n2, bgr = c.bgr, prec = c.prec;
+    const long N = c.N, M = c.M;
+    const bool sh1 = c.sh1, sh2 = c.sh2, bnb = c.bnb, sepst = c.sepst;
+    hipStream_t s = c.s;
+    const long img_bytes = (long)H * W * 3;
+    const char* cnet = bnb ? "cnetb" : "cnet";
+
+    // ---- encoders (instance norm => per-image statistics, so chunking is exact).  Three independent chains:
+    // fnet(image1) on the caller's stream, fnet(image2) and cnet(image1) on the side streams when the batch is
+    // too small to fill the machine by itself.
+    const bool overlap = overlap_pays(M) && !c.serial;
+    const Streams S{r, s, overlap};
+    const int ech = enc_chunk(H, W);
+    if ((st = S.fork(0))) return st;
+    if ((st = S.fork(1))) return st;
+    // A shared key frame encoded by itself is a single-image launch sequence on a 256-CU part (1.3 ms where 1/64 of the frames' pass is
+    // 0.3): large batches append it to the last chunk of the frames instead -- instance norm is per image, so the result is the same
+    // network; its feature map lands right behind the frames' (fmap2 follows fmap1 in the workspace).
+    const long half_bytes = (long)(H / 2) * (W / 2) * 64 * 4;
+    const bool fold_key = sh2 && !sh1 && !overlap_pays(M) && ws.fmap2 == ws.fmap1 + (long)n1 * N * FD &&   // (by batch size, not by schedule: OFX_RAFT_SERIAL must not change the arithmetic)
+                          (long)(std::min(ech, (n1 - 1) % ech + 1) + 1) * half_bytes < (1L << 31) - 4096;
+    for (int i0 = 0; i0 < n1 && !st; i0 += ech) {
+        const int n = std::min(ech, n1 - i0);
+        const bool last = i0 + n == n1;
+        st = run_encoder(r, "fnet", false, image1 + i0 * img_bytes, n, H, W, bgr, ws.eb[0], ws.fmap1 + (long)i0 * N * FD, FD,
+                         false, 0, s, prec, sepst, (fold_key && last) ? image2 : nullptr);
+    }
+    for (int i0 = 0; i0 < n2 && !st && !fold_key; i0 += ech) {
+        const int n = std::min(ech, n2 - i0);
+        st = run_encoder(r, "fnet", false, image2 + i0 * img_bytes, n, H, W, bgr, ws.eb[1], ws.fmap2 + (long)i0 * N * FD, FD,
+                         false, 0, S.get(0), prec, sepst);
+    }
+    // context encoder on image1 -> hx[:, 0:128] = tanh (net), hx[:, 256:384] = relu (inp)
+    if (sh1) {
+        if (!st) st = run_encoder(r, cnet, !bnb, image1, 1, H, W, bgr, ws.eb[2], ws.hx, HX_LD, true, INP_OFF, S.get(1), prec, sepst);
+        for (int k = 1; k < B && !st; ++k)   // one shared image1: replicate its context rows
+            OFX_HIP_CHECK(hipMemcpyAsync(ws.hx + (long)k * N * HX_LD, ws.hx, (size_t)N * HX_LD * sizeof(float),
+                                         hipMemcpyDeviceToDevice, S.get(1)));
+    } else {
+        for (int i0 = 0; i0 < B && !st; i0 += ech) {
+            const int n = std::min(ech, B - i0);
+            st = run_encoder(r, cnet, !bnb, image1 + i0 * img_bytes, n, H, W, bgr, ws.eb[2], ws.hx + (long)i0 * N * HX_LD,
+                             HX_LD, true, INP_OFF, S.get(1), prec, sepst);
+        }
+    }
+    if (!st) st = S.join(0);
+    if (!st) st = S.join(1);
+    if (st) return st;
+
+    // ---- correlation; the split planes live in the recurrence's scratch (volume_planes)
+    PairMap pm;
+    if ((st = make_pair_map(&pm, c, ws.idx_dev, c.alt, c.alt))) return st;
+    st = correlate(c, ws, pm, FD, prec, volume_planes(c, ws), ws.corr);
+    if (!st && c.warped) st = ofx_warp_pad_launch(c.warp_frame, ws.warp_pad, H, W, s);   // the zero-bordered RGBX copy the warp samples (1.6 MB at 512x768: stays in L2)
+    if (!st) st = run_recurrence(r, ws, c, pm, overlap);
+    if (!st) st = finish_flow(c, ws.coords1, ws.mask, ws.warp_pad);
+    if (st) return st;
+    register_buffers(r, c, ws, FD, ws.hx, HX_LD, ws.coords1, ws.corr, CORR_LD, ws.mask);   // corr rows of 336: 324 features + 12 zeros
+    return 0;
+}
+
+static int basic_forward_pairs(ofx_raft* r, const Call& c) {
+    RaftWs ws;
+    int st = open_workspace(&ws, c);
+    if (st) return st;
+    const uint8_t* images = c.image1;
+    const int n_images = c.n_images, B = c.B, H = c.H, W = c.W, bgr = c.bgr, prec = c.prec;
+    const long N = c.N;
+    const bool bnb = c.bnb, sepst = c.sepst;
+    hipStream_t s = c.s;
+    const long img_bytes = (long)H * W * 3;
+    const char* cnet = bnb ? "cnetb" : "cnet";
+    // every image is encoded ONCE (feature + context), however many pairs it takes part in: a 15-frame
+    // KeyframeConv window has 210 ordered pairs but only 15 images (ofgen_keyframe_inpaint.py:627-668)
+    const bool overlap = overlap_pays(c.M) && !c.serial;
+    const Streams S{r, s, overlap};
+    if ((st = S.fork(1))) return st;
+    for (int i0 = 0; i0 < n_images && !st; i0 += enc_chunk(H, W)) {
+        const int n = std::min(enc_chunk(H, W), n_images - i0);
+        st = run_encoder(r, "fnet", false, images + i0 * img_bytes, n, H, W, bgr, ws.eb[0], ws.fmap1 + (long)i0 * N * FD, FD,
+                         false, 0, s, prec, sepst);
+        if (!st)
+            st = run_encoder(r, cnet, !bnb, images + i0 * img_bytes, n, H, W, bgr, ws.eb[2], ws.ctx + (long)i0 * N * (HD + CD),
+                             HD + CD, true, HD, S.get(1), prec, sepst);
+    }
+    if (!st) st = S.join(1);
+    if (st) return st;
+    // the pair list on the device: image1's for the context rows, image2's too where the lookup or the split-plane volume reads it
+    const int vplanes = volume_planes(c, ws);
+    PairMap pm;
+    if ((st = make_pair_map(&pm, c, ws.idx_dev, true, c.alt || vplanes))) return st;
+    st = ofx_ctx_gather(ws.ctx, pm.d1, ws.hx, HX_LD, INP_OFF, HD, B, N, s);
+    if (!st) st = correlate(c, ws, pm, FD, prec, vplanes, ws.corr);
+    if (!st && c.warped) st = ofx_warp_pad_launch(c.warp_frame, ws.warp_pad, H, W, s);   // the zero-bordered RGBX copy the warp samples
+    if (!st) st = run_recurrence(r, ws, c, pm, overlap);
+    if (!st) st = finish_flow(c, ws.coords1, ws.mask, ws.warp_pad);
+    if (st) return st;
+    r->bufs.clear();   // the indexed-pairs call registers nothing
+    return 0;
+}
+
+// ============================================================================================
+// The small network (raft-small.pth; RAFT/core/raft.py:29-33, :48-51): SmallEncoder feature / context networks
+// (extractor.py:195-267, bottleneck blocks :60-116), radius-3 lookup, SmallUpdateBlock (update.py:62-77, :99-112: a 3x3 ConvGRU,
+// no mask head) and upflow8 (utils/utils.py:80-82) in place of the convex upsample.  Everything runs on the general kernels the
+// basic network's schedule also uses (ofx_conv2d, ofx_inorm_*, the blocked volume + pool, ofx_corr_lookup's generic kernel,
+// ofx_local_corr) plus ofx_upflow8 / its warp form; every launch stays on the caller's stream (no side streams, no stop events).
+//
+//   encoders   preprocess -> 7x7/s2 conv (3 -> 32) -> 3 stages x 2 bottleneck blocks (32, 64, 96) -> 1x1 conv
+//              fnet: InstanceNorm2d without affine -- statistics pass + normalise/ReLU pass after each raw convolution;
+//              cnet: no norm at all -- ReLU and the residual add live in the convolution epilogues
+//   volume     D = 128 (scaled by 1 / sqrt(128)); the same batched GEMM + pooling kernels as the basic network
+//   iteration  lookup (4 x 49) -> convc1 -> convf1 -> convf2 -> conv -> zr -> q -> flow head (EPI_FLOW: coords1 += delta)
+//   tail       upflow8 (optionally with the warp of one shared frame) of the last iteration only
+namespace {
+
+constexpr int S_HD = 96, S_CD = 64, S_FD = 128, S_RADIUS = 3;
+constexpr int S_CORR_CH = LEVELS * (2 * S_RADIUS + 1) * (2 * S_RADIUS + 1);   // 196
+// convc1's operand row: 196 correlation features + 28 zeros (Kpad of a 1x1 conv over 196 channels is 224 anyway).  The generic
+// lookup writes only the features: the zeros are set once per forward (a NaN left in them times a zero weight would be NaN).
+constexpr int S_CORR_LD = 224;
+// hx row = [h(96) | inp(64) | motion(80) flow(2) | 14 zeros] = 256: the ConvGRU's cat([h, x]) (update.py:20-21) with
+// x = cat([inp, motion features]) (update.py:109); the zeros make x a whole number of 32-channel K chunks for the q convolution's
+// second segment (cat([r*h, x]), update.py:26).  The zeros are set once per forward.
+constexpr int S_HX_LD = 256, S_INP_OFF = S_HD, S_MOT_OFF = S_HD + S_CD, S_FLOW_OFF = S_MOT_OFF + 80;
+constexpr int S_X_CH = S_HX_LD - S_HD;   // 160
+
+struct SmallWs : CorrWs {
+    float *x0, *X, *Y, *T1, *T2, *T3, *Dn, *N1, *N2;   // encoder activations of one chunk
+    float* stats;      // 8 x [chunk][128]: mean / rstd of up to four norms
+    float* scratch;    // f64 partial sums of ofx_inorm_stats
+    float* ctx;
+    float *hx, *coords1, *flow4, *corr, *corflo, *f1, *z, *rh, *fh;
+    int nch;
+    size_t bytes;
+};
+
+SmallWs small_carve(void* base, size_t cap, int B, int H, int W, int flags, int n_images) {
+    SmallWs w{};
+    Carver c(base, cap);
+    const int h = H / 8, wd = W / 8;
+    const long N = (long)h * wd, M = (long)B * N;
+    const int most = n_images > 0 ? n_images : std::max(B, 1);
+    w.nch = std::min(enc_chunk(H, W), most);
+    const size_t act = (size_t)w.nch * (H / 2) * (W / 2) * 32;   // the widest activation: 32 channels at half resolution
+    w.x0 = c.take((size_t)w.nch * H * W * 4);
+    float** bufs[8] = {&w.X, &w.Y, &w.T1, &w.T2, &w.T3, &w.Dn, &w.N1, &w.N2};
+    for (float** b : bufs) *b = c.take(act);
+    w.stats = c.take((size_t)8 * w.nch * 128);
+    w.scratch = c.take((size_t)std::max(w.nch * 64, std::min(w.nch, 7) * 256) * 128 * 2 * 2);   // doubles (ofx.h: ofx_inorm_stats)
+    long n1 = (flags & OFX_RAFT_SHARED_IMG1) ? 1 : B, n2 = (flags & OFX_RAFT_SHARED_IMG2) ? 1 : B;
+    if (n_images > 0) {
+        n1 = n_images;
+        n2 = 0;
+        w.ctx = c.take((size_t)n_images * N * S_HX_LD);
+    }
+    // index slots, volume-free mode only: image indices per pair (image1's, then image2's) for the tiled lookup
+    const bool alt = flags & OFX_RAFT_ALT_CORR;
+    carve_corr(&w, c, S_FD, B, H, W, n1, n2, n_images, alt, alt ? 2 * B : 0);
+    w.hx = c.take((size_t)M * S_HX_LD);
+    w.coords1 = c.take((size_t)M * 2);
+    w.flow4 = c.take((size_t)M * FROW);   // [M][4] flow operand of convf1 (EPI_FLOW); 16 floats a pixel: ofx_init_state zeroes that many
+    w.corr = c.take((size_t)M * S_CORR_LD);
+    w.corflo = c.take((size_t)M * 128);
+    w.f1 = c.take((size_t)M * 64);
+    w.z = c.take((size_t)M * S_HD);
+    w.rh = c.take((size_t)M * S_HD);
+    w.fh = c.take((size_t)M * 128);
+    w.bytes = c.off;
+    return w;
+}
+
+// one SmallEncoder over n images (u8 [n][H][W][3]); out [n*h*w][out_ld].  instance: fnet ('instance', no affine), else cnet ('none');
+// tanh_rows > 0 (cnet): out rows [0, tanh_rows) = tanh, the rest = relu (raft.py:111-114)
+int small_encoder(ofx_raft* r, const char* enc, bool instance, const uint8_t* imgs, int n, int H, int W, int bgr, const SmallWs& ws, float* out,
+                  int out_ld, int tanh_rows, hipStream_t s) {
+    Launcher L(s);
+    auto C = [&](const std::string& k) -> const ConvW& { return r->convs[std::string(enc) + "." + k]; };
+    const int SC = ws.nch * 128;
+    float* mean[4] = {ws.stats, ws.stats + 2 * SC, ws.stats + 4 * SC, ws.stats + 6 * SC};
+    float* rstd[4] = {ws.stats + SC, ws.stats + 3 * SC, ws.stats + 5 * SC, ws.stats + 7 * SC};
+    auto stats = [&](const float* x, long HW, int ch, int k) {
+        if (!L.st) L.st = ofx_inorm_stats(x, ch, mean[k], rstd[k], ws.scratch, n, HW, ch, 1e-5f, s);
+    };
+    auto norm_relu = [&](const float* x, long HW, int ch, int k, float* o) {   // o = relu(inorm(x))
+        if (!L.st) L.st = ofx_inorm_apply(x, mean[k], rstd[k], nullptr, nullptr, nullptr, o, n, HW, ch, 1, s);
+    };
+    int st = ofx_preprocess_u8(imgs, ws.x0, (long)n * H * W, bgr, s);
+    if (st) return st;
+    float* X = ws.X;
+    float* Y = ws.Y;
+    int hin = H / 2, win = W / 2, cin = 32;
+    if (instance) {
+        L.conv(C("conv1"), {.in0 = ws.x0, .ld0 = 4, .c0 = 4, .out = ws.T3, .ldo = 32, .B = n, .Hin = H, .Win = W, .stride = 2});
+        stats(ws.T3, (long)hin * win, 32, 0);
+        norm_relu(ws.T3, (long)hin * win, 32, 0, X);
+    } else {
+        L.conv(C("conv1"), {.in0 = ws.x0, .ld0 = 4, .c0 = 4, .out = X, .ldo = 32, .B = n, .Hin = H, .Win = W, .stride = 2, .act = OFX_ACT_RELU});
+    }
+    const int dims[3] = {32, 64, 96};
+    for (int li = 1; li <= 3; ++li) {
+        const int dim = dims[li - 1], mid = dim / 4;
+        for (int bi = 0; bi < 2; ++bi) {
+            const int stride = (li > 1 && bi == 0) ? 2 : 1;
+            const int ho = (hin - 1) / stride + 1, wo = (win - 1) / stride + 1;   // 3x3 pad 1 and 1x1 pad 0: the same output size
+            const long HWo = (long)ho * wo;
+            const std::string p = "layer" + std::to_string(li) + "." + std::to_string(bi);
+            if (instance) {
+                L.conv(C(p + ".conv1"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = ws.T1, .ldo = mid, .B = n, .Hin = hin, .Win = win});
+                stats(ws.T1, (long)hin * win, mid, 0);
+                norm_relu(ws.T1, (long)hin * win, mid, 0, ws.N1);
+                L.conv(C(p + ".conv2"), {.in0 = ws.N1, .ld0 = mid, .c0 = mid, .out = ws.T2, .ldo = mid, .B = n, .Hin = hin, .Win = win, .stride = stride});
+                stats(ws.T2, HWo, mid, 1);
+                norm_relu(ws.T2, HWo, mid, 1, ws.N2);
+                L.conv(C(p + ".conv3"), {.in0 = ws.N2, .ld0 = mid, .c0 = mid, .out = ws.T3, .ldo = dim, .B = n, .Hin = ho, .Win = wo});
+                stats(ws.T3, HWo, dim, 2);
+                if (stride == 2) {   // relu(norm4(down(x)) + relu(norm3(conv3)))
+                    L.conv(C(p + ".down"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = ws.Dn, .ldo = dim, .B = n, .Hin = hin, .Win = win, .stride = 2});
+                    stats(ws.Dn, HWo, dim, 3);
+                    if (!L.st) L.st = ofx_inorm_apply(ws.T3, mean[2], rstd[2], ws.Dn, mean[3], rstd[3], Y, n, HWo, dim, 1, s);
+                } else {             // relu(x + relu(norm3(conv3)))
+                    if (!L.st) L.st = ofx_inorm_apply(ws.T3, mean[2], rstd[2], X, nullptr, nullptr, Y, n, HWo, dim, 1, s);
+                }
+            } else {
+                L.conv(C(p + ".conv1"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = ws.T1, .ldo = mid, .B = n, .Hin = hin, .Win = win, .act = OFX_ACT_RELU});
+                L.conv(C(p + ".conv2"), {.in0 = ws.T1, .ld0 = mid, .c0 = mid, .out = ws.T2, .ldo = mid, .B = n, .Hin = hin, .Win = win, .stride = stride,
+                                         .act = OFX_ACT_RELU});
+                const float* res = X;
+                if (stride == 2) {
+                    L.conv(C(p + ".down"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = ws.Dn, .ldo = dim, .B = n, .Hin = hin, .Win = win, .stride = 2});
+                    res = ws.Dn;
+                }
+                // relu(x' + relu(conv3)): the residual merge of EPI_PLAIN
+                L.conv(C(p + ".conv3"), {.in0 = ws.T2, .ld0 = mid, .c0 = mid, .out = Y, .ldo = dim, .B = n, .Hin = ho, .Win = wo, .act = OFX_ACT_RELU,
+                                         .res = res, .ldres = dim});
+            }
+            std::swap(X, Y);
+            hin = ho; win = wo; cin = dim;
+        }
+    }
+    const ConvArgs last{.in0 = X, .ld0 = 96, .c0 = 96, .out = out, .ldo = out_ld, .B = n, .Hin = hin, .Win = win};
+    if (tanh_rows <= 0) L.conv(C("conv2"), last);
+    else L.conv_tanh_relu(C("conv2"), last, tanh_rows, tanh_rows);
+    return L.st;
+}
+
+// state init, `iters` refinement iterations of SmallUpdateBlock (upflow8 of the last iteration only -- raft.py:134-135; test_mode returns
+// the last prediction -- is finish_flow's)
+// (c.warm: flow_low holds the initial flow, OFX_RAFT_FLOW_INIT)
+int small_recurrence(ofx_raft* r, const SmallWs& ws, const Call& c, const PairMap& aix) {
+    const int B = c.B, h = c.h, w = c.w, iters = c.iters;
+    const bool alt = c.alt;
+    hipStream_t s = c.s;
+    const long M = c.M;
+    int st = c.warm ? ofx_init_state_warm(ws.coords1, ws.flow4, ws.hx, S_HX_LD, S_FLOW_OFF, true, c.flow_low, B, h, w, s)
+                  : ofx_init_state(ws.coords1, ws.flow4, ws.hx, S_HX_LD, S_FLOW_OFF, B, h, w, s);
+    if (st) return st;
+    OFX_HIP_CHECK(hipMemsetAsync(ws.corr, 0, (size_t)M * S_CORR_LD * sizeof(float), s));   // the 28 pad columns of every row
+    Launcher L(s);
+    auto C = [&](const char* k) -> const ConvW& { return r->convs[k]; };
+    const float* pyr_c[LEVELS] = {ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3]};
+    for (int it = 0; it < iters && !L.st; ++it) {
+        if (!alt) {
+            L.st = ofx_corr_lookup(pyr_c, ws.coords1, ws.corr, S_CORR_LD, B, h, w, LEVELS, S_RADIUS, s);
+        } else {
+            L.st = alt_lookup(ws.fmap1, ws.f2l, aix, ws.coords1, ws.corr, S_CORR_LD, B, h, w, S_FD, S_RADIUS, s);
+        }
+        // SmallMotionEncoder (update.py:70-77): cor_flo = [relu(convc1(corr)) (96) | relu(convf2(relu(convf1(flow)))) (32)]
+        L.conv(C("convc1"), {.in0 = ws.corr, .ld0 = S_CORR_LD, .c0 = S_CORR_LD, .out = ws.corflo, .ldo = 128, .B = B, .Hin = h, .Win = w,
+                             .act = OFX_ACT_RELU});
+        L.conv(C("convf1"), {.in0 = ws.flow4, .ld0 = 4, .c0 = 4, .out = ws.f1, .ldo = 64, .B = B, .Hin = h, .Win = w, .act = OFX_ACT_RELU});
+        L.conv(C("convf2"), {.in0 = ws.f1, .ld0 = 64, .c0 = 64, .out = ws.corflo + 96, .ldo = 128, .B = B, .Hin = h, .Win = w, .act = OFX_ACT_RELU});
+        L.conv(C("conv"), {.in0 = ws.corflo, .ld0 = 128, .c0 = 128, .out = ws.hx + S_MOT_OFF, .ldo = S_HX_LD, .B = B, .Hin = h, .Win = w,
+                           .act = OFX_ACT_RELU});
+        // ConvGRU (update.py:16-31): z | r in one convolution over cat([h, x]), q over cat([r*h, x]), h updated in place
+        L.conv(C("gru.zr"), {.in0 = ws.hx, .ld0 = S_HX_LD, .c0 = S_HX_LD, .B = B, .Hin = h, .Win = w, .epi = OFX_EPI_GRU_ZR, .aux_z = ws.z,
+                             .aux_rh = ws.rh, .aux_h = ws.hx, .ldh = S_HX_LD});
+        L.conv(C("gru.q"), {.in0 = ws.rh, .ld0 = S_HD, .c0 = S_HD, .in1 = ws.hx + S_INP_OFF, .ld1 = S_HX_LD, .c1 = S_X_CH, .B = B, .Hin = h,
+                            .Win = w, .epi = OFX_EPI_GRU_Q, .aux_z = ws.z, .aux_h = ws.hx, .ldh = S_HX_LD});
+        // FlowHead(96, 128) (update.py:6-14); coords1 += delta in the second convolution's epilogue (one rounding: delta, then the add),
+        // which also leaves the new flow in hx's flow slot and in convf1's operand
+        L.conv(C("fh1"), {.in0 = ws.hx, .ld0 = S_HX_LD, .c0 = S_HD, .out = ws.fh, .ldo = 128, .B = B, .Hin = h, .Win = w, .act = OFX_ACT_RELU});
+        L.conv(C("fh2"), {.in0 = ws.fh, .ld0 = 128, .c0 = 128, .B = B, .Hin = h, .Win = w, .epi = OFX_EPI_FLOW, .aux_h = ws.hx + S_FLOW_OFF,
+                          .ldh = S_HX_LD, .aux_coords = ws.coords1, .aux_flow4 = ws.flow4});
+    }
+    return L.st;
+}
+
+// the split-bf16 modes have no small-network form: its convolutions and its D = 128 volume run in exact fp32 only
+constexpr int S_UNSUPPORTED = OFX_RAFT_BF16X3 | OFX_RAFT_BF16X6 | OFX_RAFT_VOL_BF16X3 | OFX_RAFT_VOL_BF16X6;
+
+}  // namespace
+
+// 0 = basic, 1 = small, OFX_EKEY = neither, or keys of both
+static int small_detect(const std::map<std::string, HostTensor>& sd) {
+    auto has = [&](const char* k) { return sd.count(k) > 0; };
+    const bool small = has("update_block.gru.convz.weight") && has("fnet.layer1.0.conv3.weight");
+    const bool basic_marks = has("update_block.gru.convz1.weight") || has("update_block.mask.0.weight") ||
+                             has("update_block.encoder.convc2.weight") || has("cnet.norm1.weight");
+    const bool small_marks = has("update_block.gru.convz.weight") || has("fnet.layer1.0.conv3.weight") || has("cnet.layer1.0.conv3.weight");
+    if (small && !basic_marks) return 1;
+    if (small_marks) return OFX_EKEY;
+    return 0;
+}
+
+static int small_build(ofx_raft* r, const std::map<std::string, HostTensor>& sd) {
+    for (const char* enc : {"fnet", "cnet"}) {
+        const std::string e = enc;
+        int st = add_conv(r, sd, e + ".conv1", e + ".conv1", 4, "", 1.f);
+        if (st) return st;
+        for (int li = 1; li <= 3; ++li)
+            for (int bi = 0; bi < 2; ++bi) {
+                const std::string p = e + ".layer" + std::to_string(li) + "." + std::to_string(bi);
+                for (const char* cv : {".conv1", ".conv2", ".conv3"}) {
+                    st = add_conv(r, sd, p + cv, p + cv, 0, "", 1.f);
+                    if (st) return st;
+                }
+                if (li > 1 && bi == 0) {
+                    st = add_conv(r, sd, p + ".downsample.0", p + ".down", 0, "", 1.f);
+                    if (st) return st;
+                }
+            }
+        st = add_conv(r, sd, e + ".conv2", e + ".conv2", 0, "", 1.f);
+        if (st) return st;
+    }
+    const ConvW& fo = r->convs["fnet.conv2"];
+    const ConvW& co = r->convs["cnet.conv2"];
+    if (fo.cout != S_FD || fo.cin != 96 || co.cout != S_HD + S_CD || co.cin != 96) return OFX_EKEY;
+    const std::string ub = "update_block.";
+    int st = add_conv(r, sd, ub + "encoder.convc1", "convc1", S_CORR_LD, "", 1.f);
+    if (!st && (r->convs["convc1"].cin != S_CORR_CH || r->convs["convc1"].cout != 96)) st = OFX_EKEY;
+    if (!st) st = add_conv(r, sd, ub + "encoder.convf1", "convf1", 4, "", 1.f);   // 7x7 over the [M][4] flow operand (channels 2, 3 zero)
+    if (!st) st = add_conv(r, sd, ub + "encoder.convf2", "convf2", 0, "", 1.f);
+    if (!st) st = add_conv(r, sd, ub + "encoder.conv", "conv", 0, "", 1.f);
+    if (!st && (r->convs["conv"].cout != 80 || r->convs["convf2"].cout != 32)) st = OFX_EKEY;
+    if (!st) {   // z and r share their input: one convolution with Cout = 192 ([convz ; convr] rows), input rows padded 242 -> 256
+        std::vector<float> wzr, shzr;
+        st = add_conv(r, sd, ub + "gru.convz", "gru.z", S_HX_LD, "", 1.f, &wzr, &shzr);
+        if (!st) st = add_conv(r, sd, ub + "gru.convr", "gru.r", S_HX_LD, "", 1.f, &wzr, &shzr);
+        if (!st) {
+            ConvW c = r->convs["gru.z"];
+            if (c.cout != S_HD || c.cin != S_HX_LD - 14 || c.kh != 3 || c.kw != 3) return OFX_EKEY;
+            c.cout *= 2;
+            st = upload_weight(r, wzr, &c);
+            if (!st) st = upload(r, shzr, &c.shift);
+            c.name = "gru.zr";
+            r->convs["gru.zr"] = c;
+        }
+    }
+    if (!st) st = add_conv(r, sd, ub + "gru.convq", "gru.q", S_HX_LD, "", 1.f);
+    if (!st) st = add_conv(r, sd, ub + "flow_head.conv1", "fh1", 0, "", 1.f);
+    if (!st) st = add_conv(r, sd, ub + "flow_head.conv2", "fh2", 0, "", 1.f);
+    if (!st && (r->convs["fh1"].cin != S_HD || r->convs["fh2"].cout != 2)) st = OFX_EKEY;
+    return st;
+}
+
+static size_t small_workspace_bytes(int B, int H, int W, int n_images) {
+    if (n_images > 0) return small_carve(nullptr, 0, B, H, W, 0, n_images).bytes;
+    const size_t a = small_carve(nullptr, 0, B, H, W, 0, 0).bytes, b = small_carve(nullptr, 0, B, H, W, OFX_RAFT_ALT_CORR, 0).bytes;
+    return a > b ? a : b;
+}
+
+static size_t small_workspace_bytes_mode(int B, int H, int W, int flags, int n_images) { return small_carve(nullptr, 0, B, H, W, flags, n_images).bytes; }
+
+static int small_forward(ofx_raft* r, const Call& c) {
+    const SmallWs ws = small_carve(c.workspace, c.workspace_bytes, c.B, c.H, c.W, c.flags, 0);
+    OFX_REQUIRE(ws.bytes <= c.workspace_bytes, OFX_ENOMEM);
+    const uint8_t *image1 = c.image1, *image2 = c.image2;
+    const int B = c.B, H = c.H, W = c.W, n1 = c.n1, n2 = c.n2, bgr = c.bgr;
+    const long N = c.N, M = c.M, img_bytes = (long)H * W * 3;
+    hipStream_t s = c.s;
+    int st = 0;
+    OFX_HIP_CHECK(hipMemsetAsync(ws.hx, 0, (size_t)M * S_HX_LD * sizeof(float), s));   // the 14 pad columns of every row
+    for (int i0 = 0; i0 < n1 && !st; i0 += ws.nch)
+        st = small_encoder(r, "fnet", true, image1 + i0 * img_bytes, std::min(ws.nch, n1 - i0), H, W, bgr, ws, ws.fmap1 + (long)i0 * N * S_FD, S_FD,
+                           0, s);
+    for (int i0 = 0; i0 < n2 && !st; i0 += ws.nch)
+        st = small_encoder(r, "fnet", true, image2 + i0 * img_bytes, std::min(ws.nch, n2 - i0), H, W, bgr, ws, ws.fmap2 + (long)i0 * N * S_FD, S_FD,
+                           0, s);
+    // context network on image1 -> hx[:, 0:96] = tanh (net), hx[:, 96:160] = relu (inp)
+    for (int i0 = 0; i0 < n1 && !st; i0 += ws.nch)
+        st = small_encoder(r, "cnet", false, image1 + i0 * img_bytes, std::min(ws.nch, n1 - i0), H, W, bgr, ws, ws.hx + (long)i0 * N * S_HX_LD,
+                           S_HX_LD, S_HD, s);
+    for (int k = 1; k < B && !st && c.sh1; ++k)   // one shared image1: replicate its context rows
+        OFX_HIP_CHECK(hipMemcpyAsync(ws.hx + (long)k * N * S_HX_LD, ws.hx, (size_t)N * S_HX_LD * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (st) return st;
+    PairMap pm;
+    if ((st = make_pair_map(&pm, c, ws.idx_dev, c.alt, c.alt))) return st;
+    st = correlate(c, ws, pm, S_FD, OFX_PREC_FP32, 0, nullptr);
+    if (!st && c.warped) st = ofx_warp_pad_launch(c.warp_frame, ws.warp_pad, H, W, s);
+    if (!st) st = small_recurrence(r, ws, c, pm);
+    if (!st) st = finish_flow(c, ws.coords1, nullptr, ws.warp_pad);   // no mask head: upflow8
+    if (st) return st;
+    // hx rows of 256: h (96) | inp (64) | motion (80) | flow (2) | zeros; corr rows of 224: 196 features + 28 zeros
+    register_buffers(r, c, ws, S_FD, ws.hx, S_HX_LD, ws.coords1, ws.corr, S_CORR_LD, nullptr);
+    return 0;
+}
+
+static int small_forward_pairs(ofx_raft* r, const Call& c) {
+    const SmallWs ws = small_carve(c.workspace, c.workspace_bytes, c.B, c.H, c.W, c.flags, c.n_images);
+    OFX_REQUIRE(ws.bytes <= c.workspace_bytes, OFX_ENOMEM);
+    const uint8_t* images = c.image1;
+    const int* idx1 = c.idx1;
+    const int n_images = c.n_images, B = c.B, H = c.H, W = c.W, bgr = c.bgr;
+    const long N = c.N, img_bytes = (long)H * W * 3;
+    hipStream_t s = c.s;
+    int st = 0;
+    // every image is encoded once (feature + context network), however many pairs it takes part in; its context rows are laid out as
+    // the hx rows they are copied into (pad columns zero)
+    OFX_HIP_CHECK(hipMemsetAsync(ws.ctx, 0, (size_t)n_images * N * S_HX_LD * sizeof(float), s));
+    for (int i0 = 0; i0 < n_images && !st; i0 += ws.nch) {
+        const int n = std::min(ws.nch, n_images - i0);
+        st = small_encoder(r, "fnet", true, images + i0 * img_bytes, n, H, W, bgr, ws, ws.fmap1 + (long)i0 * N * S_FD, S_FD, 0, s);
+        if (!st) st = small_encoder(r, "cnet", false, images + i0 * img_bytes, n, H, W, bgr, ws, ws.ctx + (long)i0 * N * S_HX_LD, S_HX_LD, S_HD, s);
+    }
+    for (int b = 0; b < B && !st; ++b)
+        OFX_HIP_CHECK(hipMemcpyAsync(ws.hx + (long)b * N * S_HX_LD, ws.ctx + (long)idx1[b] * N * S_HX_LD, (size_t)N * S_HX_LD * sizeof(float),
+                                     hipMemcpyDeviceToDevice, s));
+    if (st) return st;
+    PairMap pm;   // volume-free: the pair list on the device for the lookup
+    if ((st = make_pair_map(&pm, c, ws.idx_dev, c.alt, c.alt))) return st;
+    st = correlate(c, ws, pm, S_FD, OFX_PREC_FP32, 0, nullptr);
+    if (!st && c.warped) st = ofx_warp_pad_launch(c.warp_frame, ws.warp_pad, H, W, s);
+    if (!st) st = small_recurrence(r, ws, c, pm);
+    if (!st) st = finish_flow(c, ws.coords1, nullptr, ws.warp_pad);
+    if (st) return st;
+    r->bufs.clear();   // the indexed-pairs call registers nothing
+    return 0;
+}
 
 extern "C" {
 
@@ -975,163 +1577,35 @@ size_t ofx_raft_workspace_bytes_mode(const ofx_raft* r, int n_images, int B, int
     return carve(nullptr, 0, B, H, W, layout, n_images).bytes;
 }
 
+size_t ofx_raft_workspace_bytes_pairs(const ofx_raft* r, int n_images, int B, int H, int W) {
+    if (n_images <= 0 || B <= 0 || H <= 0 || W <= 0 || (H % 8) || (W % 8)) return 0;
+    if (r && r->variant == 1) return small_workspace_bytes(B, H, W, n_images);
+    return carve(nullptr, 0, B, H, W, 0, n_images).bytes;
+}
+
+// the one way into the four forwards: the argument checks, then the network's plain or indexed-pairs body
+static int forward_call(ofx_raft* r, Call c, bool pairs) {
+    OFX_REQUIRE(r, OFX_EINVAL);
+    const bool small = r->variant == 1;
+    const int st = parse_call(&c, pairs, small ? S_UNSUPPORTED : 0);
+    if (st) return st;
+    if (pairs) return small ? small_forward_pairs(r, c) : basic_forward_pairs(r, c);
+    return small ? small_forward(r, c) : basic_forward(r, c);
+}
+
 int ofx_raft_forward(ofx_raft* r, const uint8_t* image1, const uint8_t* image2, int B, int H, int W, int iters,
                      int flags, float* flow_up, float* flow_low, void* workspace, size_t workspace_bytes, void* stream) {
-    OFX_REQUIRE(flow_up, OFX_EINVAL);
-    return raft_forward_impl(r, image1, image2, B, H, W, iters, flags, flow_up, flow_low, nullptr, 1.0f, nullptr, workspace, workspace_bytes, stream);
+    return forward_call(r, {.image1 = image1, .image2 = image2, .B = B, .H = H, .W = W, .iters = iters, .flags = flags, .flow_up = flow_up,
+                            .flow_low = flow_low, .workspace = workspace, .workspace_bytes = workspace_bytes, .s = (hipStream_t)stream}, false);
 }
 
 int ofx_raft_forward_warp(ofx_raft* r, const uint8_t* image1, const uint8_t* image2, int B, int H, int W, int iters, int flags,
                           float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign, uint8_t* warped, void* workspace,
                           size_t workspace_bytes, void* stream) {
-    OFX_REQUIRE(warp_frame && warped && (warp_sign == 1.0f || warp_sign == -1.0f), OFX_EINVAL);
-    OFX_REQUIRE(ofx_upsample_warp_ok(B, H, W) && (((uintptr_t)warped) & 3u) == 0, OFX_EINVAL);
-    return raft_forward_impl(r, image1, image2, B, H, W, iters, flags, flow_up, flow_low, warp_frame, warp_sign, warped, workspace, workspace_bytes,
-                             stream);
-}
-
-}  // extern "C"
-
-static int raft_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* image2, int B, int H, int W, int iters, int flags,
-                             float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign, uint8_t* warped, void* workspace,
-                             size_t workspace_bytes, void* stream) {
-    OFX_REQUIRE(!(flags & OFX_RAFT_FLOW_INIT) || flow_low, OFX_EINVAL);   // flow_low carries the initial flow in
-    if (flags & OFX_RAFT_FLOW_INIT) OFX_REQUIRE((((uintptr_t)flow_low) & 7u) == 0, OFX_EALIGN);
-    if (r && r->variant == 1)
-        return small_forward_impl(r, image1, image2, B, H, W, iters, flags, flow_up, flow_low, warp_frame, warp_sign, warped, workspace,
-                                  workspace_bytes, stream);
-    OFX_REQUIRE(r && image1 && image2 && (flow_up || warped) && workspace, OFX_EINVAL);
-    OFX_REQUIRE(B > 0 && H >= 64 && W >= 64 && (H % 8) == 0 && (W % 8) == 0 && iters >= 1, OFX_EINVAL);
-    OFX_REQUIRE((((uintptr_t)workspace) & 255u) == 0, OFX_EALIGN);
-    RaftWs ws = carve(workspace, workspace_bytes, B, H, W, flags);
-    OFX_REQUIRE(ws.bytes <= workspace_bytes, OFX_ENOMEM);
-    hipStream_t s = (hipStream_t)stream;
-    for (int e = 0; e < 3; ++e)   // split-K arrival counters start at zero (the kernels leave them at zero)
-        if (ws.sk[e]) OFX_HIP_CHECK(hipMemsetAsync(ws.sk[e], 0, 65536, s));
-    const int h = H / 8, w = W / 8;
-    const long N = (long)h * w;
-    const long M = (long)B * N;
-    const int bgr = (flags & OFX_RAFT_BGR) ? 1 : 0;
-    const int prec = (flags & OFX_RAFT_BF16X6) ? OFX_PREC_BF16X6 : (flags & OFX_RAFT_BF16X3) ? OFX_PREC_BF16X3 : OFX_PREC_FP32;
-    const bool sh1 = flags & OFX_RAFT_SHARED_IMG1, sh2 = flags & OFX_RAFT_SHARED_IMG2;
-    const bool alt = flags & OFX_RAFT_ALT_CORR;
-    const long img_bytes = (long)H * W * 3;
-    // Context-encoder BatchNorm.  Default: the running statistics, folded into the convolutions (a model in .eval(), as PDCNet's
-    // own code and canonical RAFT inference run it).  OFX_RAFT_BN_BATCH: the statistics of the image itself -- what
-    // `RAFT_2` computes AS WRITTEN: the reference never calls .eval() (ofgen_keyframe_inpaint.py:47-60), so its
-    // BatchNorm2d layers (RAFT/core/raft.py:55, extractor.py:118-192) normalise with the statistics of the call's batch,
-    // and every call is one image.  Each image of a batch is normalised by itself here (= B reference calls).
-    const bool bnb = flags & OFX_RAFT_BN_BATCH;
-    const bool sepst = flags & OFX_RAFT_SEPARATE_STATS;
-    const char* cnet = bnb ? "cnetb" : "cnet";
-
-    // ---- encoders (instance norm => per-image statistics, so chunking is exact).  Three independent chains:
-    // fnet(image1) on the caller's stream, fnet(image2) and cnet(image1) on the side streams when the batch is
-    // too small to fill the machine by itself.
-    int st = 0;
-    const int n1 = sh1 ? 1 : B, n2 = sh2 ? 1 : B;
-    const bool overlap = overlap_pays(M) && !(flags & OFX_RAFT_SERIAL);
-    const Streams S{r, s, overlap};
-    const int ech = enc_chunk(H, W);
-    if ((st = S.fork(0))) return st;
-    if ((st = S.fork(1))) return st;
-    // A shared key frame encoded by itself is a single-image launch sequence on a 256-CU part (1.3 ms where 1/64 of the frames' pass is
-    // 0.3): large batches append it to the last chunk of the frames instead -- instance norm is per image, so the result is the same
-    // network; its feature map lands right behind the frames' (fmap2 follows fmap1 in the workspace).
-    const long half_bytes = (long)(H / 2) * (W / 2) * 64 * 4;
-    const bool fold_key = sh2 && !sh1 && !overlap_pays(M) && ws.fmap2 == ws.fmap1 + (long)n1 * N * FD &&   // (by batch size, not by schedule: OFX_RAFT_SERIAL must not change the arithmetic)
-                          (long)(std::min(ech, (n1 - 1) % ech + 1) + 1) * half_bytes < (1L << 31) - 4096;
-    for (int i0 = 0; i0 < n1 && !st; i0 += ech) {
-        const int n = std::min(ech, n1 - i0);
-        const bool last = i0 + n == n1;
-        st = run_encoder(r, "fnet", false, image1 + i0 * img_bytes, n, H, W, bgr, ws.eb[0], ws.fmap1 + (long)i0 * N * FD, FD,
-                         false, 0, s, prec, sepst, (fold_key && last) ? image2 : nullptr);
-    }
-    for (int i0 = 0; i0 < n2 && !st && !fold_key; i0 += ech) {
-        const int n = std::min(ech, n2 - i0);
-        st = run_encoder(r, "fnet", false, image2 + i0 * img_bytes, n, H, W, bgr, ws.eb[1], ws.fmap2 + (long)i0 * N * FD, FD,
-                         false, 0, S.get(0), prec, sepst);
-    }
-    // context encoder on image1 -> hx[:, 0:128] = tanh (net), hx[:, 256:384] = relu (inp)
-    if (sh1) {
-        if (!st) st = run_encoder(r, cnet, !bnb, image1, 1, H, W, bgr, ws.eb[2], ws.hx, HX_LD, true, INP_OFF, S.get(1), prec, sepst);
-        for (int k = 1; k < B && !st; ++k)   // one shared image1: replicate its context rows
-            OFX_HIP_CHECK(hipMemcpyAsync(ws.hx + (long)k * N * HX_LD, ws.hx, (size_t)N * HX_LD * sizeof(float),
-                                         hipMemcpyDeviceToDevice, S.get(1)));
-    } else {
-        for (int i0 = 0; i0 < B && !st; i0 += ech) {
-            const int n = std::min(ech, B - i0);
-            st = run_encoder(r, cnet, !bnb, image1 + i0 * img_bytes, n, H, W, bgr, ws.eb[2], ws.hx + (long)i0 * N * HX_LD,
-                             HX_LD, true, INP_OFF, S.get(1), prec, sepst);
-        }
-    }
-    if (!st) st = S.join(0);
-    if (!st) st = S.join(1);
-    if (st) return st;
-
-    // ---- correlation
-    const int vplanes = alt ? 0 : volume_planes(flags, h, w, (long)n1 + n2, ws, M, B);
-    if (vplanes) {
-        char* pl = (char*)ws.corr;
-        const long ib = (long)ofx_corr_planes_bytes(h, w, vplanes);
-        st = ofx_corr_split_planes(ws.fmap1, pl, n1, h, w, vplanes, 0, 1.0f / std::sqrt((float)FD), s);
-        if (!st) st = ofx_corr_split_planes(ws.fmap2, pl + ib * n1, n2, h, w, vplanes, 1, 1.0f, s);
-        if (!st)
-            st = ofx_corr_vol_split_launch(pl, pl + ib * n1, nullptr, nullptr, sh1 ? 0 : ib, sh2 ? 0 : ib, ws.pyr[0], ws.pyr[1], B, h, w, vplanes, s);
-        if (!st) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, true);
-        if (st) return st;
-    } else if (!alt) {
-        // the volume's columns in blocked order: permute the rows of the B operand once (6.3 MB per image)
-        const long Nb = ofx_corr_slice_floats_l(h, w);
-        st = ofx_corr_block_rows(ws.fmap2, ws.fmap2b, (int)n2, h, w, FD, s);
-        if (st) return st;
-        bool fused = false;
-        st = volume_gemm(ws.fmap1, sh1 ? 0 : N * FD, ws.fmap2b, sh2 ? 0 : Nb * FD, ws.pyr[0], ws.pyr[1], B, h, w, FD, prec, &fused, s);
-        if (!st) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused);
-        if (st) return st;
-    } else {
-        for (int l = 1; l < LEVELS && !st; ++l)
-            st = ofx_avgpool2_nhwc(ws.f2l[l - 1], ws.f2l[l], n2, h >> (l - 1), w >> (l - 1), FD, s);
-        if (st) return st;
-    }
-
-    if (warped) {   // the zero-bordered RGBX copy the warp samples (1.6 MB at 512x768: stays in L2)
-        st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
-        if (st) return st;
-    }
-    AltIdx aix;
-    if (alt && (sh1 || sh2)) {
-        OFX_HIP_CHECK(hipMemsetAsync(ws.idx_dev, 0, sizeof(int) * B, s));
-        aix.d1 = sh1 ? ws.idx_dev : nullptr; aix.d2 = sh2 ? ws.idx_dev : nullptr;
-        aix.sh1 = sh1; aix.sh2 = sh2;
-    }
-    st = run_recurrence(r, ws, B, h, w, iters, alt, aix, flow_up, flow_low, s, prec, overlap, flags & OFX_RAFT_FLOW_INIT,
-                        warped, warp_sign);
-    if (st) return st;
-
-    r->bufs.clear();
-    auto reg = [&](const char* k, float* p, size_t nf) { r->bufs[k] = std::make_pair((void*)p, nf); };
-    reg("fmap1", ws.fmap1, (size_t)n1 * N * FD);
-    reg("fmap2", ws.fmap2, (size_t)n2 * N * FD);
-    reg("hx", ws.hx, (size_t)M * HX_LD);
-    reg("coords1", ws.coords1, (size_t)M * 2);
-    reg("corr", ws.corr, (size_t)M * CORR_LD);   // rows of 336: 324 features + 12 zeros
-    reg("mask", ws.mask, (size_t)M * 576);
-    if (!alt)
-        for (int l = 0; l < LEVELS; ++l) {
-            char nm[8];
-            snprintf(nm, sizeof nm, "pyr%d", l);
-            reg(nm, ws.pyr[l], (size_t)M * ofx_corr_slice_floats_l(h >> l, w >> l));   // blocked layout (ofx.h)
-        }
-    return 0;
-}
-
-extern "C" {
-
-size_t ofx_raft_workspace_bytes_pairs(const ofx_raft* r, int n_images, int B, int H, int W) {
-    if (n_images <= 0 || B <= 0 || H <= 0 || W <= 0 || (H % 8) || (W % 8)) return 0;
-    if (r && r->variant == 1) return small_workspace_bytes(B, H, W, n_images);
-    return carve(nullptr, 0, B, H, W, 0, n_images).bytes;
+    // every pair is warped: n_warp = B
+    return forward_call(r, {.image1 = image1, .image2 = image2, .B = B, .H = H, .W = W, .iters = iters, .flags = flags, .flow_up = flow_up,
+                            .flow_low = flow_low, .warp_frame = warp_frame, .warp_sign = warp_sign, .n_warp = B, .warped = warped,
+                            .workspace = workspace, .workspace_bytes = workspace_bytes, .s = (hipStream_t)stream}, false);
 }
 
 int ofx_raft_forward_pairs(ofx_raft* r, const uint8_t* images, int n_images, const int* idx1, const int* idx2, int B, int H,
@@ -1144,98 +1618,10 @@ int ofx_raft_forward_pairs(ofx_raft* r, const uint8_t* images, int n_images, con
 int ofx_raft_forward_pairs_warp(ofx_raft* r, const uint8_t* images, int n_images, const int* idx1, const int* idx2, int B, int H,
                                 int W, int iters, int flags, float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign,
                                 int n_warp, uint8_t* warped, void* workspace, size_t workspace_bytes, void* stream) {
-    OFX_REQUIRE(r && images && idx1 && idx2 && flow_up && workspace, OFX_EINVAL);
-    OFX_REQUIRE(!(flags & OFX_RAFT_FLOW_INIT) || flow_low, OFX_EINVAL);
-    if (flags & OFX_RAFT_FLOW_INIT) OFX_REQUIRE((((uintptr_t)flow_low) & 7u) == 0, OFX_EALIGN);
-    if (r->variant == 1)
-        return small_forward_pairs_impl(r, images, n_images, idx1, idx2, B, H, W, iters, flags, flow_up, flow_low, warp_frame, warp_sign, n_warp,
-                                        warped, workspace, workspace_bytes, stream);
-    if (warped || warp_frame || n_warp) {
-        OFX_REQUIRE(warp_frame && warped && n_warp > 0 && n_warp <= B && (warp_sign == 1.0f || warp_sign == -1.0f), OFX_EINVAL);
-        OFX_REQUIRE(ofx_upsample_warp_ok(n_warp, H, W) && (((uintptr_t)warped) & 3u) == 0, OFX_EINVAL);
-    }
-    OFX_REQUIRE(n_images > 0 && B > 0 && H >= 64 && W >= 64 && (H % 8) == 0 && (W % 8) == 0 && iters >= 1, OFX_EINVAL);
-    OFX_REQUIRE(!(flags & (OFX_RAFT_SHARED_IMG1 | OFX_RAFT_SHARED_IMG2)), OFX_EINVAL);
-    OFX_REQUIRE((((uintptr_t)workspace) & 255u) == 0, OFX_EALIGN);
-    for (int b = 0; b < B; ++b)
-        OFX_REQUIRE(idx1[b] >= 0 && idx1[b] < n_images && idx2[b] >= 0 && idx2[b] < n_images, OFX_EINVAL);
-    const bool alt = flags & OFX_RAFT_ALT_CORR;
-    RaftWs ws = carve(workspace, workspace_bytes, B, H, W, flags & OFX_RAFT_ALT_CORR, n_images);
-    OFX_REQUIRE(ws.bytes <= workspace_bytes, OFX_ENOMEM);
-    hipStream_t s = (hipStream_t)stream;
-    for (int e = 0; e < 3; ++e)
-        if (ws.sk[e]) OFX_HIP_CHECK(hipMemsetAsync(ws.sk[e], 0, 65536, s));
-    const int h = H / 8, w = W / 8;
-    const long N = (long)h * w;
-    const int bgr = (flags & OFX_RAFT_BGR) ? 1 : 0;
-    const int prec = (flags & OFX_RAFT_BF16X6) ? OFX_PREC_BF16X6 : (flags & OFX_RAFT_BF16X3) ? OFX_PREC_BF16X3 : OFX_PREC_FP32;
-    const long img_bytes = (long)H * W * 3;
-    // Context-encoder BatchNorm.  Default: the running statistics, folded into the convolutions (a model in .eval(), as PDCNet's
-    // own code and canonical RAFT inference run it).  OFX_RAFT_BN_BATCH: the statistics of the image itself -- what
-    // `RAFT_2` computes AS WRITTEN: the reference never calls .eval() (ofgen_keyframe_inpaint.py:47-60), so its
-    // BatchNorm2d layers (RAFT/core/raft.py:55, extractor.py:118-192) normalise with the statistics of the call's batch,
-    // and every call is one image.  Each image of a batch is normalised by itself here (= B reference calls).
-    const bool bnb = flags & OFX_RAFT_BN_BATCH;
-    const bool sepst = flags & OFX_RAFT_SEPARATE_STATS;
-    const char* cnet = bnb ? "cnetb" : "cnet";
-    int st = 0;
-    // every image is encoded ONCE (feature + context), however many pairs it takes part in: a 15-frame
-    // KeyframeConv window has 210 ordered pairs but only 15 images (ofgen_keyframe_inpaint.py:627-668)
-    const bool overlap = overlap_pays((long)B * N) && !(flags & OFX_RAFT_SERIAL);
-    const Streams S{r, s, overlap};
-    if ((st = S.fork(1))) return st;
-    for (int i0 = 0; i0 < n_images && !st; i0 += enc_chunk(H, W)) {
-        const int n = std::min(enc_chunk(H, W), n_images - i0);
-        st = run_encoder(r, "fnet", false, images + i0 * img_bytes, n, H, W, bgr, ws.eb[0], ws.fmap1 + (long)i0 * N * FD, FD,
-                         false, 0, s, prec, sepst);
-        if (!st)
-            st = run_encoder(r, cnet, !bnb, images + i0 * img_bytes, n, H, W, bgr, ws.eb[2], ws.ctx + (long)i0 * N * (HD + CD),
-                             HD + CD, true, HD, S.get(1), prec, sepst);
-    }
-    if (!st) st = S.join(1);
-    if (st) return st;
-    OFX_HIP_CHECK(hipMemcpyAsync(ws.idx_dev, idx1, sizeof(int) * B, hipMemcpyHostToDevice, s));
-    st = ofx_ctx_gather(ws.ctx, ws.idx_dev, ws.hx, HX_LD, INP_OFF, HD, B, N, s);
-    if (st) return st;
-    AltIdx aix;
-    if (alt) {   // volume-free: the pooled levels of every image once, the pair list on the device for the lookup
-        OFX_HIP_CHECK(hipMemcpyAsync(ws.idx_dev + B, idx2, sizeof(int) * B, hipMemcpyHostToDevice, s));
-        for (int l = 1; l < LEVELS && !st; ++l) st = ofx_avgpool2_nhwc(ws.f2l[l - 1], ws.f2l[l], n_images, h >> (l - 1), w >> (l - 1), FD, s);
-        if (st) return st;
-        aix.d1 = ws.idx_dev; aix.d2 = ws.idx_dev + B;
-        aix.h1 = idx1; aix.h2 = idx2;
-    }
-    const long Nb = ofx_corr_slice_floats_l(h, w);
-    const long slice1p = ofx_corr_slice_floats_l(h >> 1, w >> 1);
-    bool fused_pairs = false;
-    const int vplanes = alt ? 0 : volume_planes(flags, h, w, 2L * n_images, ws, (long)B * N, B);
-    if (vplanes) {
-        // split-bf16 volume: every image split once per role (rows scaled in pixel order / columns in quad order), ONE launch over the
-        // pair list through the device-side index arrays
-        char* pl = (char*)ws.corr;
-        const long ib = (long)ofx_corr_planes_bytes(h, w, vplanes);
-        OFX_HIP_CHECK(hipMemcpyAsync(ws.idx_dev + B, idx2, sizeof(int) * B, hipMemcpyHostToDevice, s));
-        st = ofx_corr_split_planes(ws.fmap1, pl, n_images, h, w, vplanes, 0, 1.0f / std::sqrt((float)FD), s);
-        if (!st) st = ofx_corr_split_planes(ws.fmap1, pl + ib * n_images, n_images, h, w, vplanes, 1, 1.0f, s);
-        if (!st) st = ofx_corr_vol_split_launch(pl, pl + ib * n_images, ws.idx_dev, ws.idx_dev + B, 0, 0, ws.pyr[0], ws.pyr[1], B, h, w, vplanes, s);
-    } else if (!alt) {
-        st = ofx_corr_block_rows(ws.fmap1, ws.fmap2b, n_images, h, w, FD, s);   // every image can be an image2: blocked copy of all
-    }
-    if (st) return st;
-    for (int b = 0; b < B && !st && !vplanes && !alt; ++b)   // one N x Nb correlation GEMM per pair, straight from the shared feature maps
-        st = volume_gemm(ws.fmap1 + (long)idx1[b] * N * FD, 0, ws.fmap2b + (long)idx2[b] * Nb * FD, 0, ws.pyr[0] + (long)b * N * Nb,
-                         ws.pyr[1] + (long)b * N * slice1p, 1, h, w, FD, prec, &fused_pairs, s);
-    if (!st && !alt) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused_pairs || vplanes);
-    if (st) return st;
-    if (warped) {   // the zero-bordered RGBX copy the warp samples
-        st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
-        if (st) return st;
-    }
-    st = run_recurrence(r, ws, B, h, w, iters, alt, aix, flow_up, flow_low, s, prec, overlap, flags & OFX_RAFT_FLOW_INIT, warped, warp_sign,
-                        n_warp);
-    if (st) return st;
-    r->bufs.clear();
-    return 0;
+    return forward_call(r, {.image1 = images, .n_images = n_images, .idx1 = idx1, .idx2 = idx2, .B = B, .H = H, .W = W, .iters = iters,
+                            .flags = flags, .flow_up = flow_up, .flow_low = flow_low, .warp_frame = warp_frame, .warp_sign = warp_sign,
+                            .n_warp = n_warp, .warped = warped, .workspace = workspace, .workspace_bytes = workspace_bytes,
+                            .s = (hipStream_t)stream}, true);
 }
 
 int ofx_raft_variant(const ofx_raft* r) {
@@ -1253,404 +1639,3 @@ int ofx_raft_buffer(const ofx_raft* r, const char* name, void** ptr, size_t* nfl
 }
 
 }  // extern "C"
-
-// ============================================================================================
-// The small network (raft-small.pth; RAFT/core/raft.py:29-33, :48-51): SmallEncoder feature / context networks
-// (extractor.py:195-267, bottleneck blocks :60-116), radius-3 lookup, SmallUpdateBlock (update.py:62-77, :99-112: a 3x3 ConvGRU,
-// no mask head) and upflow8 (utils/utils.py:80-82) in place of the convex upsample.  Everything runs on the general kernels the
-// basic network's schedule also uses (ofx_conv2d, ofx_inorm_*, the blocked volume + pool, ofx_corr_lookup's generic kernel,
-// ofx_local_corr) plus ofx_upflow8 / its warp form; every launch stays on the caller's stream (no side streams, no stop events).
-//
-//   encoders   preprocess -> 7x7/s2 conv (3 -> 32) -> 3 stages x 2 bottleneck blocks (32, 64, 96) -> 1x1 conv
-//              fnet: InstanceNorm2d without affine -- statistics pass + normalise/ReLU pass after each raw convolution;
-//              cnet: no norm at all -- ReLU and the residual add live in the convolution epilogues
-//   volume     D = 128 (scaled by 1 / sqrt(128)); the same batched GEMM + pooling kernels as the basic network
-//   iteration  lookup (4 x 49) -> convc1 -> convf1 -> convf2 -> conv -> zr -> q -> flow head (EPI_FLOW: coords1 += delta)
-//   tail       upflow8 (optionally with the warp of one shared frame) of the last iteration only
-namespace {
-
-constexpr int S_HD = 96, S_CD = 64, S_FD = 128, S_RADIUS = 3;
-constexpr int S_CORR_CH = LEVELS * (2 * S_RADIUS + 1) * (2 * S_RADIUS + 1);   // 196
-// convc1's operand row: 196 correlation features + 28 zeros (Kpad of a 1x1 conv over 196 channels is 224 anyway).  The generic
-// lookup writes only the features: the zeros are set once per forward (a NaN left in them times a zero weight would be NaN).
-constexpr int S_CORR_LD = 224;
-// hx row = [h(96) | inp(64) | motion(80) flow(2) | 14 zeros] = 256: the ConvGRU's cat([h, x]) (update.py:20-21) with
-// x = cat([inp, motion features]) (update.py:109); the zeros make x a whole number of 32-channel K chunks for the q convolution's
-// second segment (cat([r*h, x]), update.py:26).  The zeros are set once per forward.
-constexpr int S_HX_LD = 256, S_INP_OFF = S_HD, S_MOT_OFF = S_HD + S_CD, S_FLOW_OFF = S_MOT_OFF + 80;
-constexpr int S_X_CH = S_HX_LD - S_HD;   // 160
-
-struct SmallWs {
-    float *x0, *X, *Y, *T1, *T2, *T3, *Dn, *N1, *N2;   // encoder activations of one chunk
-    float* stats;      // 8 x [chunk][128]: mean / rstd of up to four norms
-    float* scratch;    // f64 partial sums of ofx_inorm_stats
-    float *fmap1, *fmap2, *f2l[LEVELS], *fmap2b, *ctx;
-    int* idx_dev;      // volume-free mode: image indices per pair (image1's, then image2's) for the tiled lookup
-    float* pyr[LEVELS];
-    float *hx, *coords1, *flow4, *corr, *corflo, *f1, *z, *rh, *fh;
-    void* warp_pad;
-    int nch;
-    size_t bytes;
-};
-
-SmallWs small_carve(void* base, size_t cap, int B, int H, int W, int flags, int n_images) {
-    SmallWs w{};
-    Carver c(base, cap);
-    const int h = H / 8, wd = W / 8;
-    const long N = (long)h * wd, M = (long)B * N;
-    const int most = n_images > 0 ? n_images : std::max(B, 1);
-    w.nch = std::min(enc_chunk(H, W), most);
-    const size_t act = (size_t)w.nch * (H / 2) * (W / 2) * 32;   // the widest activation: 32 channels at half resolution
-    w.x0 = c.take((size_t)w.nch * H * W * 4);
-    float** bufs[8] = {&w.X, &w.Y, &w.T1, &w.T2, &w.T3, &w.Dn, &w.N1, &w.N2};
-    for (float** b : bufs) *b = c.take(act);
-    w.stats = c.take((size_t)8 * w.nch * 128);
-    w.scratch = c.take((size_t)std::max(w.nch * 64, std::min(w.nch, 7) * 256) * 128 * 2 * 2);   // doubles (ofx.h: ofx_inorm_stats)
-    long n1 = (flags & OFX_RAFT_SHARED_IMG1) ? 1 : B, n2 = (flags & OFX_RAFT_SHARED_IMG2) ? 1 : B;
-    if (n_images > 0) {
-        n1 = n_images;
-        n2 = 0;
-        w.ctx = c.take((size_t)n_images * N * S_HX_LD);
-    }
-    w.fmap1 = c.take((size_t)n1 * N * S_FD);
-    w.fmap2 = n2 ? c.take((size_t)n2 * N * S_FD) : w.fmap1;
-    if (flags & OFX_RAFT_ALT_CORR) {
-        w.f2l[0] = w.fmap2;
-        for (int l = 1; l < LEVELS; ++l) w.f2l[l] = c.take((size_t)(n_images > 0 ? n_images : n2) * (h >> l) * (wd >> l) * S_FD);
-        w.idx_dev = (int*)c.take((size_t)2 * B);
-    } else {
-        w.fmap2b = c.take((size_t)(n_images > 0 ? n_images : n2) * ofx_corr_slice_floats_l(h, wd) * S_FD);
-        for (int l = 0; l < LEVELS; ++l) w.pyr[l] = c.take((size_t)M * ofx_corr_slice_floats_l(h >> l, wd >> l));
-    }
-    w.hx = c.take((size_t)M * S_HX_LD);
-    w.coords1 = c.take((size_t)M * 2);
-    w.flow4 = c.take((size_t)M * FROW);   // [M][4] flow operand of convf1 (EPI_FLOW); 16 floats a pixel: ofx_init_state zeroes that many
-    w.corr = c.take((size_t)M * S_CORR_LD);
-    w.corflo = c.take((size_t)M * 128);
-    w.f1 = c.take((size_t)M * 64);
-    w.z = c.take((size_t)M * S_HD);
-    w.rh = c.take((size_t)M * S_HD);
-    w.fh = c.take((size_t)M * 128);
-    w.warp_pad = c.take(ofx_warp_pad_bytes(H, W) / sizeof(float) + 4);
-    w.bytes = c.off;
-    return w;
-}
-
-// one SmallEncoder over n images (u8 [n][H][W][3]); out [n*h*w][out_ld].  instance: fnet ('instance', no affine), else cnet ('none');
-// tanh_rows > 0 (cnet): out rows [0, tanh_rows) = tanh, the rest = relu (raft.py:111-114)
-int small_encoder(ofx_raft* r, const char* enc, bool instance, const uint8_t* imgs, int n, int H, int W, int bgr, const SmallWs& ws, float* out,
-                  int out_ld, int tanh_rows, hipStream_t s) {
-    Launcher L(s);
-    auto C = [&](const std::string& k) -> const ConvW& { return r->convs[std::string(enc) + "." + k]; };
-    const int SC = ws.nch * 128;
-    float* mean[4] = {ws.stats, ws.stats + 2 * SC, ws.stats + 4 * SC, ws.stats + 6 * SC};
-    float* rstd[4] = {ws.stats + SC, ws.stats + 3 * SC, ws.stats + 5 * SC, ws.stats + 7 * SC};
-    auto stats = [&](const float* x, long HW, int ch, int k) {
-        if (!L.st) L.st = ofx_inorm_stats(x, ch, mean[k], rstd[k], ws.scratch, n, HW, ch, 1e-5f, s);
-    };
-    auto norm_relu = [&](const float* x, long HW, int ch, int k, float* o) {   // o = relu(inorm(x))
-        if (!L.st) L.st = ofx_inorm_apply(x, mean[k], rstd[k], nullptr, nullptr, nullptr, o, n, HW, ch, 1, s);
-    };
-    int st = ofx_preprocess_u8(imgs, ws.x0, (long)n * H * W, bgr, s);
-    if (st) return st;
-    float* X = ws.X;
-    float* Y = ws.Y;
-    int hin = H / 2, win = W / 2, cin = 32;
-    if (instance) {
-        L.conv(C("conv1"), {.in0 = ws.x0, .ld0 = 4, .c0 = 4, .out = ws.T3, .ldo = 32, .B = n, .Hin = H, .Win = W, .stride = 2});
-        stats(ws.T3, (long)hin * win, 32, 0);
-        norm_relu(ws.T3, (long)hin * win, 32, 0, X);
-    } else {
-        L.conv(C("conv1"), {.in0 = ws.x0, .ld0 = 4, .c0 = 4, .out = X, .ldo = 32, .B = n, .Hin = H, .Win = W, .stride = 2, .act = OFX_ACT_RELU});
-    }
-    const int dims[3] = {32, 64, 96};
-    for (int li = 1; li <= 3; ++li) {
-        const int dim = dims[li - 1], mid = dim / 4;
-        for (int bi = 0; bi < 2; ++bi) {
-            const int stride = (li > 1 && bi == 0) ? 2 : 1;
-            const int ho = (hin - 1) / stride + 1, wo = (win - 1) / stride + 1;   // 3x3 pad 1 and 1x1 pad 0: the same output size
-            const long HWo = (long)ho * wo;
-            const std::string p = "layer" + std::to_string(li) + "." + std::to_string(bi);
-            if (instance) {
-                L.conv(C(p + ".conv1"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = ws.T1, .ldo = mid, .B = n, .Hin = hin, .Win = win});
-                stats(ws.T1, (long)hin * win, mid, 0);
-                norm_relu(ws.T1, (long)hin * win, mid, 0, ws.N1);
-                L.conv(C(p + ".conv2"), {.in0 = ws.N1, .ld0 = mid, .c0 = mid, .out = ws.T2, .ldo = mid, .B = n, .Hin = hin, .Win = win, .stride = stride});
-                stats(ws.T2, HWo, mid, 1);
-                norm_relu(ws.T2, HWo, mid, 1, ws.N2);
-                L.conv(C(p + ".conv3"), {.in0 = ws.N2, .ld0 = mid, .c0 = mid, .out = ws.T3, .ldo = dim, .B = n, .Hin = ho, .Win = wo});
-                stats(ws.T3, HWo, dim, 2);
-                if (stride == 2) {   // relu(norm4(down(x)) + relu(norm3(conv3)))
-                    L.conv(C(p + ".down"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = ws.Dn, .ldo = dim, .B = n, .Hin = hin, .Win = win, .stride = 2});
-                    stats(ws.Dn, HWo, dim, 3);
-                    if (!L.st) L.st = ofx_inorm_apply(ws.T3, mean[2], rstd[2], ws.Dn, mean[3], rstd[3], Y, n, HWo, dim, 1, s);
-                } else {             // relu(x + relu(norm3(conv3)))
-                    if (!L.st) L.st = ofx_inorm_apply(ws.T3, mean[2], rstd[2], X, nullptr, nullptr, Y, n, HWo, dim, 1, s);
-                }
-            } else {
-                L.conv(C(p + ".conv1"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = ws.T1, .ldo = mid, .B = n, .Hin = hin, .Win = win, .act = OFX_ACT_RELU});
-                L.conv(C(p + ".conv2"), {.in0 = ws.T1, .ld0 = mid, .c0 = mid, .out = ws.T2, .ldo = mid, .B = n, .Hin = hin, .Win = win, .stride = stride,
-                                         .act = OFX_ACT_RELU});
-                const float* res = X;
-                if (stride == 2) {
-                    L.conv(C(p + ".down"), {.in0 = X, .ld0 = cin, .c0 = cin, .out = ws.Dn, .ldo = dim, .B = n, .Hin = hin, .Win = win, .stride = 2});
-                    res = ws.Dn;
-                }
-                // relu(x' + relu(conv3)): the residual merge of EPI_PLAIN
-                L.conv(C(p + ".conv3"), {.in0 = ws.T2, .ld0 = mid, .c0 = mid, .out = Y, .ldo = dim, .B = n, .Hin = ho, .Win = wo, .act = OFX_ACT_RELU,
-                                         .res = res, .ldres = dim});
-            }
-            std::swap(X, Y);
-            hin = ho; win = wo; cin = dim;
-        }
-    }
-    const ConvArgs last{.in0 = X, .ld0 = 96, .c0 = 96, .out = out, .ldo = out_ld, .B = n, .Hin = hin, .Win = win};
-    if (tanh_rows <= 0) L.conv(C("conv2"), last);
-    else L.conv_tanh_relu(C("conv2"), last, tanh_rows, tanh_rows);
-    return L.st;
-}
-
-// state init, `iters` refinement iterations of SmallUpdateBlock, upflow8 (with the warp of one shared frame for the first n_warp pairs)
-// (warm: flow_low holds the initial flow, OFX_RAFT_FLOW_INIT)
-int small_recurrence(ofx_raft* r, const SmallWs& ws, int B, int h, int w, int iters, bool alt, const AltIdx& aix, float* flow_up, float* flow_low, bool warm,
-                     uint8_t* warped, float warp_sign, int n_warp, hipStream_t s) {
-    const long N = (long)h * w, M = (long)B * N;
-    int st = warm ? ofx_init_state_warm(ws.coords1, ws.flow4, ws.hx, S_HX_LD, S_FLOW_OFF, true, flow_low, B, h, w, s)
-                  : ofx_init_state(ws.coords1, ws.flow4, ws.hx, S_HX_LD, S_FLOW_OFF, B, h, w, s);
-    if (st) return st;
-    OFX_HIP_CHECK(hipMemsetAsync(ws.corr, 0, (size_t)M * S_CORR_LD * sizeof(float), s));   // the 28 pad columns of every row
-    Launcher L(s);
-    auto C = [&](const char* k) -> const ConvW& { return r->convs[k]; };
-    const float* pyr_c[LEVELS] = {ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3]};
-    for (int it = 0; it < iters && !L.st; ++it) {
-        if (!alt) {
-            L.st = ofx_corr_lookup(pyr_c, ws.coords1, ws.corr, S_CORR_LD, B, h, w, LEVELS, S_RADIUS, s);
-        } else {
-            L.st = alt_lookup(ws.fmap1, ws.f2l, aix, ws.coords1, ws.corr, S_CORR_LD, B, h, w, S_FD, S_RADIUS, s);
-        }
-        // SmallMotionEncoder (update.py:70-77): cor_flo = [relu(convc1(corr)) (96) | relu(convf2(relu(convf1(flow)))) (32)]
-        L.conv(C("convc1"), {.in0 = ws.corr, .ld0 = S_CORR_LD, .c0 = S_CORR_LD, .out = ws.corflo, .ldo = 128, .B = B, .Hin = h, .Win = w,
-                             .act = OFX_ACT_RELU});
-        L.conv(C("convf1"), {.in0 = ws.flow4, .ld0 = 4, .c0 = 4, .out = ws.f1, .ldo = 64, .B = B, .Hin = h, .Win = w, .act = OFX_ACT_RELU});
-        L.conv(C("convf2"), {.in0 = ws.f1, .ld0 = 64, .c0 = 64, .out = ws.corflo + 96, .ldo = 128, .B = B, .Hin = h, .Win = w, .act = OFX_ACT_RELU});
-        L.conv(C("conv"), {.in0 = ws.corflo, .ld0 = 128, .c0 = 128, .out = ws.hx + S_MOT_OFF, .ldo = S_HX_LD, .B = B, .Hin = h, .Win = w,
-                           .act = OFX_ACT_RELU});
-        // ConvGRU (update.py:16-31): z | r in one convolution over cat([h, x]), q over cat([r*h, x]), h updated in place
-        L.conv(C("gru.zr"), {.in0 = ws.hx, .ld0 = S_HX_LD, .c0 = S_HX_LD, .B = B, .Hin = h, .Win = w, .epi = OFX_EPI_GRU_ZR, .aux_z = ws.z,
-                             .aux_rh = ws.rh, .aux_h = ws.hx, .ldh = S_HX_LD});
-        L.conv(C("gru.q"), {.in0 = ws.rh, .ld0 = S_HD, .c0 = S_HD, .in1 = ws.hx + S_INP_OFF, .ld1 = S_HX_LD, .c1 = S_X_CH, .B = B, .Hin = h,
-                            .Win = w, .epi = OFX_EPI_GRU_Q, .aux_z = ws.z, .aux_h = ws.hx, .ldh = S_HX_LD});
-        // FlowHead(96, 128) (update.py:6-14); coords1 += delta in the second convolution's epilogue (one rounding: delta, then the add),
-        // which also leaves the new flow in hx's flow slot and in convf1's operand
-        L.conv(C("fh1"), {.in0 = ws.hx, .ld0 = S_HX_LD, .c0 = S_HD, .out = ws.fh, .ldo = 128, .B = B, .Hin = h, .Win = w, .act = OFX_ACT_RELU});
-        L.conv(C("fh2"), {.in0 = ws.fh, .ld0 = 128, .c0 = 128, .B = B, .Hin = h, .Win = w, .epi = OFX_EPI_FLOW, .aux_h = ws.hx + S_FLOW_OFF,
-                          .ldh = S_HX_LD, .aux_coords = ws.coords1, .aux_flow4 = ws.flow4});
-    }
-    if (L.st) return L.st;
-    // upflow8 of the last iteration only (raft.py:134-135; test_mode returns the last prediction)
-    const int nw = warped ? (n_warp < 0 ? B : std::min(n_warp, B)) : 0;
-    if (nw > 0) st = ofx_upflow8_warp_launch(ws.coords1, flow_up, ws.warp_pad, warped, nw, h, w, warp_sign, s);
-    if (!st && nw < B) {
-        if (!flow_up) return OFX_EINVAL;
-        st = ofx_upflow8(ws.coords1 + (long)nw * N * 2, flow_up + (long)nw * N * 128, B - nw, h, w, s);
-    }
-    if (st) return st;
-    if (flow_low) return ofx_coords_to_flow(ws.coords1, flow_low, B, h, w, s);
-    return 0;
-}
-
-// the split-bf16 modes have no small-network form: its convolutions and its D = 128 volume run in exact fp32 only
-constexpr int S_UNSUPPORTED = OFX_RAFT_BF16X3 | OFX_RAFT_BF16X6 | OFX_RAFT_VOL_BF16X3 | OFX_RAFT_VOL_BF16X6;
-
-void small_register(ofx_raft* r, const SmallWs& ws, long n1, long n2, long M, int h, int w, bool alt) {
-    r->bufs.clear();
-    const long N = (long)h * w;
-    auto reg = [&](const char* k, float* p, size_t nf) { r->bufs[k] = std::make_pair((void*)p, nf); };
-    reg("fmap1", ws.fmap1, (size_t)n1 * N * S_FD);
-    reg("fmap2", ws.fmap2, (size_t)n2 * N * S_FD);
-    reg("hx", ws.hx, (size_t)M * S_HX_LD);            // rows of 256: h (96) | inp (64) | motion (80) | flow (2) | zeros
-    reg("coords1", ws.coords1, (size_t)M * 2);
-    reg("corr", ws.corr, (size_t)M * S_CORR_LD);      // rows of 224: 196 features + 28 zeros
-    if (!alt)
-        for (int l = 0; l < LEVELS; ++l) {
-            char nm[8];
-            snprintf(nm, sizeof nm, "pyr%d", l);
-            reg(nm, ws.pyr[l], (size_t)M * ofx_corr_slice_floats_l(h >> l, w >> l));
-        }
-}
-
-}  // namespace
-
-// 0 = basic, 1 = small, OFX_EKEY = neither, or keys of both
-static int small_detect(const std::map<std::string, HostTensor>& sd) {
-    auto has = [&](const char* k) { return sd.count(k) > 0; };
-    const bool small = has("update_block.gru.convz.weight") && has("fnet.layer1.0.conv3.weight");
-    const bool basic_marks = has("update_block.gru.convz1.weight") || has("update_block.mask.0.weight") ||
-                             has("update_block.encoder.convc2.weight") || has("cnet.norm1.weight");
-    const bool small_marks = has("update_block.gru.convz.weight") || has("fnet.layer1.0.conv3.weight") || has("cnet.layer1.0.conv3.weight");
-    if (small && !basic_marks) return 1;
-    if (small_marks) return OFX_EKEY;
-    return 0;
-}
-
-static int small_build(ofx_raft* r, const std::map<std::string, HostTensor>& sd) {
-    for (const char* enc : {"fnet", "cnet"}) {
-        const std::string e = enc;
-        int st = add_conv(r, sd, e + ".conv1", e + ".conv1", 4, "", 1.f);
-        if (st) return st;
-        for (int li = 1; li <= 3; ++li)
-            for (int bi = 0; bi < 2; ++bi) {
-                const std::string p = e + ".layer" + std::to_string(li) + "." + std::to_string(bi);
-                for (const char* cv : {".conv1", ".conv2", ".conv3"}) {
-                    st = add_conv(r, sd, p + cv, p + cv, 0, "", 1.f);
-                    if (st) return st;
-                }
-                if (li > 1 && bi == 0) {
-                    st = add_conv(r, sd, p + ".downsample.0", p + ".down", 0, "", 1.f);
-                    if (st) return st;
-                }
-            }
-        st = add_conv(r, sd, e + ".conv2", e + ".conv2", 0, "", 1.f);
-        if (st) return st;
-    }
-    const ConvW& fo = r->convs["fnet.conv2"];
-    const ConvW& co = r->convs["cnet.conv2"];
-    if (fo.cout != S_FD || fo.cin != 96 || co.cout != S_HD + S_CD || co.cin != 96) return OFX_EKEY;
-    const std::string ub = "update_block.";
-    int st = add_conv(r, sd, ub + "encoder.convc1", "convc1", S_CORR_LD, "", 1.f);
-    if (!st && (r->convs["convc1"].cin != S_CORR_CH || r->convs["convc1"].cout != 96)) st = OFX_EKEY;
-    if (!st) st = add_conv(r, sd, ub + "encoder.convf1", "convf1", 4, "", 1.f);   // 7x7 over the [M][4] flow operand (channels 2, 3 zero)
-    if (!st) st = add_conv(r, sd, ub + "encoder.convf2", "convf2", 0, "", 1.f);
-    if (!st) st = add_conv(r, sd, ub + "encoder.conv", "conv", 0, "", 1.f);
-    if (!st && (r->convs["conv"].cout != 80 || r->convs["convf2"].cout != 32)) st = OFX_EKEY;
-    if (!st) {   // z and r share their input: one convolution with Cout = 192 ([convz ; convr] rows), input rows padded 242 -> 256
-        std::vector<float> wzr, shzr;
-        st = add_conv(r, sd, ub + "gru.convz", "gru.z", S_HX_LD, "", 1.f, &wzr, &shzr);
-        if (!st) st = add_conv(r, sd, ub + "gru.convr", "gru.r", S_HX_LD, "", 1.f, &wzr, &shzr);
-        if (!st) {
-            ConvW c = r->convs["gru.z"];
-            if (c.cout != S_HD || c.cin != S_HX_LD - 14 || c.kh != 3 || c.kw != 3) return OFX_EKEY;
-            c.cout *= 2;
-            st = upload_weight(r, wzr, &c);
-            if (!st) st = upload(r, shzr, &c.shift);
-            c.name = "gru.zr";
-            r->convs["gru.zr"] = c;
-        }
-    }
-    if (!st) st = add_conv(r, sd, ub + "gru.convq", "gru.q", S_HX_LD, "", 1.f);
-    if (!st) st = add_conv(r, sd, ub + "flow_head.conv1", "fh1", 0, "", 1.f);
-    if (!st) st = add_conv(r, sd, ub + "flow_head.conv2", "fh2", 0, "", 1.f);
-    if (!st && (r->convs["fh1"].cin != S_HD || r->convs["fh2"].cout != 2)) st = OFX_EKEY;
-    return st;
-}
-
-static size_t small_workspace_bytes(int B, int H, int W, int n_images) {
-    if (n_images > 0) return small_carve(nullptr, 0, B, H, W, 0, n_images).bytes;
-    const size_t a = small_carve(nullptr, 0, B, H, W, 0, 0).bytes, b = small_carve(nullptr, 0, B, H, W, OFX_RAFT_ALT_CORR, 0).bytes;
-    return a > b ? a : b;
-}
-
-static size_t small_workspace_bytes_mode(int B, int H, int W, int flags, int n_images) { return small_carve(nullptr, 0, B, H, W, flags, n_images).bytes; }
-
-static int small_forward_impl(ofx_raft* r, const uint8_t* image1, const uint8_t* image2, int B, int H, int W, int iters, int flags,
-                              float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign, uint8_t* warped, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-    OFX_REQUIRE(r && image1 && image2 && (flow_up || warped) && workspace, OFX_EINVAL);
-    OFX_REQUIRE(B > 0 && H >= 64 && W >= 64 && (H % 8) == 0 && (W % 8) == 0 && iters >= 1, OFX_EINVAL);
-    OFX_REQUIRE(!(flags & S_UNSUPPORTED), OFX_EINVAL);
-    OFX_REQUIRE((((uintptr_t)workspace) & 255u) == 0, OFX_EALIGN);
-    const bool sh1 = flags & OFX_RAFT_SHARED_IMG1, sh2 = flags & OFX_RAFT_SHARED_IMG2, alt = flags & OFX_RAFT_ALT_CORR;
-    SmallWs ws = small_carve(workspace, workspace_bytes, B, H, W, flags, 0);
-    OFX_REQUIRE(ws.bytes <= workspace_bytes, OFX_ENOMEM);
-    hipStream_t s = (hipStream_t)stream;
-    const int h = H / 8, w = W / 8, bgr = (flags & OFX_RAFT_BGR) ? 1 : 0;
-    const long N = (long)h * w, M = (long)B * N, img_bytes = (long)H * W * 3;
-    const int n1 = sh1 ? 1 : B, n2 = sh2 ? 1 : B;
-    int st = 0;
-    OFX_HIP_CHECK(hipMemsetAsync(ws.hx, 0, (size_t)M * S_HX_LD * sizeof(float), s));   // the 14 pad columns of every row
-    for (int i0 = 0; i0 < n1 && !st; i0 += ws.nch)
-        st = small_encoder(r, "fnet", true, image1 + i0 * img_bytes, std::min(ws.nch, n1 - i0), H, W, bgr, ws, ws.fmap1 + (long)i0 * N * S_FD, S_FD,
-                           0, s);
-    for (int i0 = 0; i0 < n2 && !st; i0 += ws.nch)
-        st = small_encoder(r, "fnet", true, image2 + i0 * img_bytes, std::min(ws.nch, n2 - i0), H, W, bgr, ws, ws.fmap2 + (long)i0 * N * S_FD, S_FD,
-                           0, s);
-    // context network on image1 -> hx[:, 0:96] = tanh (net), hx[:, 96:160] = relu (inp)
-    for (int i0 = 0; i0 < n1 && !st; i0 += ws.nch)
-        st = small_encoder(r, "cnet", false, image1 + i0 * img_bytes, std::min(ws.nch, n1 - i0), H, W, bgr, ws, ws.hx + (long)i0 * N * S_HX_LD,
-                           S_HX_LD, S_HD, s);
-    for (int k = 1; k < B && !st && sh1; ++k)   // one shared image1: replicate its context rows
-        OFX_HIP_CHECK(hipMemcpyAsync(ws.hx + (long)k * N * S_HX_LD, ws.hx, (size_t)N * S_HX_LD * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (st) return st;
-    if (!alt) {
-        bool fused = false;
-        const long Nb = ofx_corr_slice_floats_l(h, w);
-        st = ofx_corr_block_rows(ws.fmap2, ws.fmap2b, n2, h, w, S_FD, s);
-        if (!st) st = volume_gemm(ws.fmap1, sh1 ? 0 : N * S_FD, ws.fmap2b, sh2 ? 0 : Nb * S_FD, ws.pyr[0], ws.pyr[1], B, h, w, S_FD, OFX_PREC_FP32, &fused, s);
-        if (!st) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused);
-    } else {
-        for (int l = 1; l < LEVELS && !st; ++l) st = ofx_avgpool2_nhwc(ws.f2l[l - 1], ws.f2l[l], n2, h >> (l - 1), w >> (l - 1), S_FD, s);
-    }
-    if (!st && warped) st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
-    AltIdx aix;
-    if (!st && alt && (sh1 || sh2)) {
-        OFX_HIP_CHECK(hipMemsetAsync(ws.idx_dev, 0, sizeof(int) * B, s));
-        aix.d1 = sh1 ? ws.idx_dev : nullptr; aix.d2 = sh2 ? ws.idx_dev : nullptr;
-        aix.sh1 = sh1; aix.sh2 = sh2;
-    }
-    if (!st) st = small_recurrence(r, ws, B, h, w, iters, alt, aix, flow_up, flow_low, flags & OFX_RAFT_FLOW_INIT, warped, warp_sign, -1, s);
-    if (st) return st;
-    small_register(r, ws, n1, n2, M, h, w, alt);
-    return 0;
-}
-
-static int small_forward_pairs_impl(ofx_raft* r, const uint8_t* images, int n_images, const int* idx1, const int* idx2, int B, int H, int W,
-                                    int iters, int flags, float* flow_up, float* flow_low, const uint8_t* warp_frame, float warp_sign,
-                                    int n_warp, uint8_t* warped, void* workspace, size_t workspace_bytes, void* stream) {
-    if (warped || warp_frame || n_warp) {
-        OFX_REQUIRE(warp_frame && warped && n_warp > 0 && n_warp <= B && (warp_sign == 1.0f || warp_sign == -1.0f), OFX_EINVAL);
-        OFX_REQUIRE(ofx_upsample_warp_ok(n_warp, H, W) && (((uintptr_t)warped) & 3u) == 0, OFX_EINVAL);
-    }
-    OFX_REQUIRE(n_images > 0 && B > 0 && H >= 64 && W >= 64 && (H % 8) == 0 && (W % 8) == 0 && iters >= 1, OFX_EINVAL);
-    OFX_REQUIRE(!(flags & (OFX_RAFT_SHARED_IMG1 | OFX_RAFT_SHARED_IMG2 | S_UNSUPPORTED)), OFX_EINVAL);
-    const bool alt = flags & OFX_RAFT_ALT_CORR;
-    OFX_REQUIRE((((uintptr_t)workspace) & 255u) == 0, OFX_EALIGN);
-    for (int b = 0; b < B; ++b)
-        OFX_REQUIRE(idx1[b] >= 0 && idx1[b] < n_images && idx2[b] >= 0 && idx2[b] < n_images, OFX_EINVAL);
-    SmallWs ws = small_carve(workspace, workspace_bytes, B, H, W, flags & OFX_RAFT_ALT_CORR, n_images);
-    OFX_REQUIRE(ws.bytes <= workspace_bytes, OFX_ENOMEM);
-    hipStream_t s = (hipStream_t)stream;
-    const int h = H / 8, w = W / 8, bgr = (flags & OFX_RAFT_BGR) ? 1 : 0;
-    const long N = (long)h * w, img_bytes = (long)H * W * 3;
-    int st = 0;
-    // every image is encoded once (feature + context network), however many pairs it takes part in; its context rows are laid out as
-    // the hx rows they are copied into (pad columns zero)
-    OFX_HIP_CHECK(hipMemsetAsync(ws.ctx, 0, (size_t)n_images * N * S_HX_LD * sizeof(float), s));
-    for (int i0 = 0; i0 < n_images && !st; i0 += ws.nch) {
-        const int n = std::min(ws.nch, n_images - i0);
-        st = small_encoder(r, "fnet", true, images + i0 * img_bytes, n, H, W, bgr, ws, ws.fmap1 + (long)i0 * N * S_FD, S_FD, 0, s);
-        if (!st) st = small_encoder(r, "cnet", false, images + i0 * img_bytes, n, H, W, bgr, ws, ws.ctx + (long)i0 * N * S_HX_LD, S_HX_LD, S_HD, s);
-    }
-    for (int b = 0; b < B && !st; ++b)
-        OFX_HIP_CHECK(hipMemcpyAsync(ws.hx + (long)b * N * S_HX_LD, ws.ctx + (long)idx1[b] * N * S_HX_LD, (size_t)N * S_HX_LD * sizeof(float),
-                                     hipMemcpyDeviceToDevice, s));
-    const long Nb = ofx_corr_slice_floats_l(h, w), slice1 = ofx_corr_slice_floats_l(h >> 1, w >> 1);
-    AltIdx aix;
-    if (!st && alt) {   // volume-free: the pooled levels of every image once, the pair list on the device for the lookup
-        OFX_HIP_CHECK(hipMemcpyAsync(ws.idx_dev, idx1, sizeof(int) * B, hipMemcpyHostToDevice, s));
-        OFX_HIP_CHECK(hipMemcpyAsync(ws.idx_dev + B, idx2, sizeof(int) * B, hipMemcpyHostToDevice, s));
-        for (int l = 1; l < LEVELS && !st; ++l) st = ofx_avgpool2_nhwc(ws.f2l[l - 1], ws.f2l[l], n_images, h >> (l - 1), w >> (l - 1), S_FD, s);
-        aix.d1 = ws.idx_dev; aix.d2 = ws.idx_dev + B;
-        aix.h1 = idx1; aix.h2 = idx2;
-    }
-    if (!st && !alt) st = ofx_corr_block_rows(ws.fmap1, ws.fmap2b, n_images, h, w, S_FD, s);   // every image can be an image2
-    bool fused = false;
-    for (int b = 0; b < B && !st && !alt; ++b)   // one correlation GEMM per pair, straight from the shared feature maps
-        st = volume_gemm(ws.fmap1 + (long)idx1[b] * N * S_FD, 0, ws.fmap2b + (long)idx2[b] * Nb * S_FD, 0, ws.pyr[0] + (long)b * N * Nb,
-                         ws.pyr[1] + (long)b * N * slice1, 1, h, w, S_FD, OFX_PREC_FP32, &fused, s);
-    if (!st && !alt) st = ofx_corr_pool_launch(ws.pyr[0], ws.pyr[1], ws.pyr[2], ws.pyr[3], B, h, w, LEVELS, s, fused);
-    if (!st && warped) st = ofx_warp_pad_launch(warp_frame, ws.warp_pad, H, W, s);
-    if (!st) st = small_recurrence(r, ws, B, h, w, iters, alt, aix, flow_up, flow_low, flags & OFX_RAFT_FLOW_INIT, warped, warp_sign, n_warp, s);
-    if (st) return st;
-    r->bufs.clear();
-    return 0;
-}

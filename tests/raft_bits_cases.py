@@ -8,8 +8,11 @@ A digest covers flow_up, flow_low and the warped frames where the run returns th
 the forward registers (none for the indexed-pairs call).  Every hashed tensor must be finite: a run asserts that, so a digest never
 records NaNs.
 
-OFX_OVERLAP_MAX_M and OFX_NO_EPI_STATS are read once per process: the runs of CHILD_GROUPS go through `child_digests`, one child
-process per group.  Plain data and input construction: importing this module needs no GPU."""
+The split-volume runs (SPLIT_SIZE: the smallest grid the A-stationary volume kernel takes, at batch sizes that just pass its fill
+thresholds) digest their flows and pyramid levels only, and assert once, outside the digest, that the split kernel ran.
+
+OFX_OVERLAP_MAX_M, OFX_NO_EPI_STATS, OFX_LOCAL_CORR_NO_TILED and OFX_VOL_GENERIC are read once per process: the runs of CHILD_GROUPS
+go through `child_digests`, one child process per group.  Plain data and input construction: importing this module needs no GPU."""
 import functools
 import hashlib
 import json
@@ -26,9 +29,17 @@ GOLDEN = os.path.join(HERE, "golden", "raft_bits", "sha256.json")
 ITERS = 3                            # the kernel-carried fork event needs a second iteration
 SIZES = {"": (128, 160), "-72x88": (72, 88)}   # the goldens' size (1/8 grid 16x20); a 9x11 grid with odd tails
 PAIRS = ([0, 1, 0, 2], [1, 0, 2, 1])
+# The split-plane volume (corr_split.hip) needs w/8 % 16 == 0 and h/8 % 8 == 0: a 16x32 grid, N = 512 in two 256-row groups.  It is
+# taken from a fill of 2 * pairs / 256 workgroups per CU of 0.84 (exact fp32 planes) / 0.52 (bf16x6) on: B = 108, B = 68, 96 pairs
+SPLIT_SIZE = (128, 256)
+SPLIT_PAIRS = ([0, 1, 2, 3, 0, 2] * 16, [1, 0, 3, 1, 3, 0] * 16)
 # switch -> value of the child process; the runs of each group are the names under "<switch>=<value>/"
 CHILD_GROUPS = {"OFX_OVERLAP_MAX_M=0": ("basic/forward-B2", "basic/shared-image2-B3", "basic/pairs-volume"),
-                "OFX_NO_EPI_STATS=1": ("basic/forward-B2",)}
+                "OFX_NO_EPI_STATS=1": ("basic/forward-B2",),
+                # the per-pixel lookup: it reads the pair map's host arrays and shared flags
+                "OFX_LOCAL_CORR_NO_TILED=1": ("basic/alternate_corr-shared-image2-B3", "basic/pairs-local", "small/pairs-local"),
+                # the generic GEMM at a shape where the split kernel would otherwise be taken
+                "OFX_VOL_GENERIC=1": ("basic/split-volume-fp32-shared-image2-B108",)}
 
 
 def sha256(tensors):
@@ -63,11 +74,23 @@ def _buffers(eng, alt):
     return [eng.buffer(n) for n in names]
 
 
-def _forward(small=False, size="", B=2, shared=None, engine=(), warp=False, want_flow=True, warm=False, **kw):
+def _split_ran(launch):
+    """One launch under the per-family profile: the split-plane kernel ran -- or, in OFX_VOL_GENERIC's child, did not."""
+    from sd_animation_optical_flow_amd import ops
+    ops.prof_enable(1)
+    try:
+        launch()
+        families = ops.prof_collect()
+    finally:
+        ops.prof_enable(0)
+    assert ("corr_split_planes" in families) == ("OFX_VOL_GENERIC" not in os.environ), sorted(families)
+
+
+def _forward(small=False, size="", B=2, shared=None, engine=(), warp=False, want_flow=True, warm=False, split=False, **kw):
     """engine: the RaftEngine's own keywords as (name, value) pairs; kw: `forward`'s.  shared: 'image1' / 'image2' = one frame for
-    the whole batch on that side."""
+    the whole batch on that side.  split: a split-volume run (see the module's text)."""
     def make():
-        H, W = SIZES[size]
+        H, W = SPLIT_SIZE if split else SIZES[size]
         eng = _engine(small, **dict(engine))
         x = frames(11, 2 * B + 1, H, W).cuda()
         i1 = x[0] if shared == "image1" else x[:B].contiguous()
@@ -81,23 +104,30 @@ def _forward(small=False, size="", B=2, shared=None, engine=(), warp=False, want
 
         def launch():
             out = eng.forward(i1, i2, **args)
+            if split:
+                return list(out) + [eng.buffer(f"pyr{l}") for l in range(4)]
             return [t for t in out if t is not None] + _buffers(eng, bool(kw.get("alternate_corr")))
+        if split:
+            _split_ran(launch)
         return launch
     return make
 
 
-def _pairs(small=False, alt=False, warp=False):
+def _pairs(small=False, alt=False, warp=False, engine=(), split=False):
+    """split: the split-volume run over all four frames and SPLIT_PAIRS."""
     def make():
-        H, W = SIZES[""]
-        eng = _engine(small)
+        H, W = SPLIT_SIZE if split else SIZES[""]
+        eng = _engine(small, **dict(engine))
         x = frames(12, 4, H, W).cuda()
         args = dict(iters=ITERS, alternate_corr=alt)
         if warp:
             args.update(warp_frame=x[3], n_warp=2)
 
         def launch():
-            out = eng.forward_pairs(x[:3].contiguous(), *PAIRS, **args)
+            out = eng.forward_pairs(x, *SPLIT_PAIRS, **args) if split else eng.forward_pairs(x[:3].contiguous(), *PAIRS, **args)
             return list(out) if isinstance(out, tuple) else [out]
+        if split:
+            _split_ran(launch)
         return launch
     return make
 
@@ -115,17 +145,25 @@ def _local_runs():
             ("basic/volume_precision-bf16x6", _forward(engine=(("volume_precision", "bf16x6"),))),
             ("basic/alternate_corr", _forward(alternate_corr=True)),
             ("basic/alternate_corr-shared-image2-B3", _forward(B=3, shared="image2", alternate_corr=True)),
+            ("basic/alternate_corr-shared-image1-B2", _forward(shared="image1", alternate_corr=True)),
+            ("basic/split-volume-fp32-shared-image2-B108", _forward(B=108, shared="image2", split=True)),
+            ("basic/split-volume-bf16x6-B68", _forward(B=68, engine=(("volume_precision", "bf16x6"),), split=True)),
+            ("basic/pairs-split-volume-bf16x6", _pairs(engine=(("volume_precision", "bf16x6"),), split=True)),
             ("basic/warp_frame-no-flow", _forward(warp=True, want_flow=False)),
             ("basic/flow_init", _forward(warm=True))]
     out += [(f"basic/pairs-{'local' if alt else 'volume'}{'-warp' if warp else ''}", _pairs(alt=alt, warp=warp))
             for alt in (False, True) for warp in (False, True)]
     out += [(f"small/forward-B2{sz}", _forward(small=True, size=sz)) for sz in SIZES]
     out += [("small/shared-image2-B3", _forward(small=True, B=3, shared="image2")),
+            ("small/shared-image1-B2", _forward(small=True, shared="image1")),
             ("small/alternate_corr", _forward(small=True, alternate_corr=True)),
+            ("small/alternate_corr-shared-image2-B3", _forward(small=True, B=3, shared="image2", alternate_corr=True)),
             ("small/warp_frame", _forward(small=True, warp=True)),
             ("small/flow_init", _forward(small=True, warm=True)),
             ("small/pairs-volume", _pairs(small=True)),
-            ("small/pairs-local", _pairs(small=True, alt=True))]
+            ("small/pairs-local", _pairs(small=True, alt=True)),
+            ("small/pairs-volume-warp", _pairs(small=True, warp=True)),
+            ("small/pairs-local-warp", _pairs(small=True, alt=True, warp=True))]
     return out
 
 

@@ -1,7 +1,9 @@
 """The RAFT engine held to recorded output bits.
 
 The digests in tests/golden/raft_bits/sha256.json were written by tools/raft_bits.py on the MI355X from the library as it stood when
-the executor's convolution launcher still took 27 positional arguments and carried one-shot members; the runs (raft_bits_cases.py)
+the executor's convolution launcher still took 27 positional arguments and carried one-shot members -- and, for the 12 runs added
+with it (shared-frame index set-up, the small network's warped pairs, the per-pixel lookup, the split-plane volume), from the
+library before the four forwards shared their argument check, correlation stage and tail; the runs (raft_bits_cases.py)
 cover both networks and every schedule the executor takes, flows and registered intermediates alike.  A change of how the executor
 describes or orders its launches keeps these bits; a change of a kernel's arithmetic, a tile choice or a route records new ones.  A
 second launch must give the bits of the first.  GPU tests are marked -m gpu.
