@@ -387,8 +387,11 @@ int ofx_abs_diff_sum_u8(const uint8_t* a, long a_bstride, const uint8_t* b, long
 #define OFX_ACT_TANH    3
 
 #define OFX_EPI_PLAIN   0   /* y = act(acc*scale + shift); if res: y = relu(y + res)            */
-#define OFX_EPI_GRU_ZR  1   /* Cout=2*hd: n<hd -> z=sigmoid -> aux_z ; n>=hd -> r -> aux_rh=r*h   */
-#define OFX_EPI_GRU_Q   2   /* q=tanh; h = (1-z)*h + z*q written in place to aux_h               */
+#define OFX_EPI_GRU_ZR  1   /* Cout=2*hd: n<hd -> z=sigmoid -> aux_z ; n>=hd -> r -> aux_rh=r*h.  hd % 32 == 0 (else OFX_EINVAL: the
+                               kernels take z or r per 32-column sub-tile).  aux_z and aux_rh are dense [M][hd] rows of hd floats:
+                               aux_z[m*hd + n], aux_rh[m*hd + n - hd] = r * aux_h[m*ldh + n - hd]; aux_h is only read, ldh >= hd */
+#define OFX_EPI_GRU_Q   2   /* q=tanh; h = (1-z)*h + z*q written in place to aux_h[m*ldh + n], n < Cout = hd, ldh >= Cout; z is
+                               read from aux_z[m*Cout + n]: dense rows of Cout floats, the array GRU_ZR wrote */
 #define OFX_EPI_FLOW    3   /* Cout=2: coords1 += delta; flow=coords1-grid -> aux_h slot + flow4.  The generic form of the flow
                                head's second convolution; the RAFT executor itself runs flow_head.hip, which leaves convf1's
                                operand as 16-float flow rows instead of this [M][4] array */

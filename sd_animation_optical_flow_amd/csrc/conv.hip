@@ -1672,7 +1672,9 @@ int conv_validate(const ofx_conv_desc* d, const ConvExtra& x, long* split_rows) 
     if (x.pool.out) OFX_REQUIRE(M * (long)x.pool.slice1 * 4 < lim, OFX_EINVAL);
     switch (d->epi) {
         case OFX_EPI_PLAIN: OFX_REQUIRE(d->out != nullptr && d->ldo >= d->Cout && (!d->res || d->ldres >= d->Cout), OFX_EINVAL); break;
-        case OFX_EPI_GRU_ZR: OFX_REQUIRE(d->aux_z && d->aux_rh && d->aux_h && d->Cout % 2 == 0 && d->ldh >= d->Cout / 2, OFX_EINVAL); break;
+        // (hd % 32: the epilogue decides z half or r half once per 32-column sub-tile -- a split inside one would store r columns as z,
+        // into the next row of aux_z; the Winograd route has the analogous `(Cout / 2) % cblk == 0` in its shape test)
+        case OFX_EPI_GRU_ZR: OFX_REQUIRE(d->aux_z && d->aux_rh && d->aux_h && d->Cout % 2 == 0 && (d->Cout / 2) % 32 == 0 && d->ldh >= d->Cout / 2, OFX_EINVAL); break;
         case OFX_EPI_GRU_Q: OFX_REQUIRE(d->aux_z && d->aux_h && d->ldh >= d->Cout, OFX_EINVAL); break;
         case OFX_EPI_FLOW: OFX_REQUIRE(d->aux_coords && d->aux_h && d->aux_flow4 && d->Cout == 2, OFX_EINVAL); break;
         default: return OFX_EINVAL;

@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 import wino_check as wc
+from gru_check import GUARD, _at, _conv_rows, _guarded, _rows_of
 
 ALGS = {"3x3": (3, 3), "1x5": (1, 5), "5x1": (5, 1)}
 CBLK = {"3x3": 64, "1x5": 128, "5x1": 128}       # output channels per workgroup
@@ -350,7 +351,6 @@ def test_engine_3x3_layer_descriptors_against_float64(cuda, layer):
 # the GRU gate epilogues in the engine's layout, with guard rows around every destination
 
 GRU_MAPS = [(1, 8, 16), (1, 8, 128), (1, 64, 16), (3, 24, 48), (1, 136, 240), (2, 136, 240)]
-GUARD = 16                                       # rows before and after every [M][ld] buffer
 
 
 def _check_rows(B, H, W):
@@ -361,27 +361,6 @@ def _check_rows(B, H, W):
     return sorted({0, 1, 2, 6, 7, 8, 9, 14, 15, 16, 17, H - 9, H - 8, H - 3, H - 2, H - 1})
 
 
-def _conv_rows(x, w, kh, kw, rows):
-    """x NCHW -> the 'same' correlation at output rows `rows` only, float64, [B, Cout, len(rows), W]."""
-    ph, pw = kh // 2, kw // 2
-    xp = F.pad(x.double(), (0, 0, ph, ph))
-    sl = torch.stack([xp[:, :, y:y + kh] for y in rows], 1)             # [B, R, C, kh, W]
-    B, R = sl.shape[:2]
-    out = F.conv2d(sl.reshape(B * R, *sl.shape[2:]), w.double(), padding=(0, pw))   # [B R, Cout, 1, W]
-    return out.reshape(B, R, -1, x.shape[3]).permute(0, 2, 1, 3)
-
-
-def _guarded(rows, ld, g, fill=None):
-    """[GUARD + rows + GUARD, ld] with NaN guard rows; the body is `fill` or uniform noise."""
-    buf = torch.full((rows + 2 * GUARD, ld), float("nan"))
-    buf[GUARD:GUARD + rows] = torch.rand((rows, ld), generator=g) if fill is None else fill
-    return buf
-
-
-def _at(buf, ld):   # device pointer of row 0 of a guarded buffer
-    return buf.data_ptr() + 4 * GUARD * ld
-
-
 def _gru_state(B, H, W, seed):
     M = B * H * W
     g = torch.Generator().manual_seed(seed)
@@ -389,10 +368,6 @@ def _gru_state(B, H, W, seed):
                     torch.randn((M, HD), generator=g)], 1)
     gadd = torch.randn((M, GADD_LD), generator=g) * 0.3
     return g, _guarded(M, HX_LD, g, hx), _guarded(M, GADD_LD, g, gadd)
-
-
-def _rows_of(t, B, H, W, rows):   # [M][C] -> [B, C, len(rows), W]
-    return t.view(B, H, W, -1)[:, rows].permute(0, 3, 1, 2)
 
 
 def run_gru_case(epi, alg, B, H, W, seed, cout=None, goff=None):

@@ -16,7 +16,15 @@ TINY = 1e-30
 #   F(2x2,3x3)                                3.17
 #   F(4,5) plain                              21.5
 #   F(4,5) GRU_ZR / GRU_Q (pre-activation)    15.7 / 16.1
+# The direct kernels' GRU gate epilogues over the cases of tests/gru_check.py (test_gpu_conv_gru_direct.py), measured on MI355X:
+#   fp32, every tile / schedule / split-K      2.85  (inside the 5.83 above: K_DIRECT as it stands)
+#   bf16x3 / bf16x3_w                          1.94  against the float64 sum of the three products of the CPU-split operands
+#   bf16x6 / bf16x6_w                          2.31  against the float64 convolution of the exact operands
+# What the split-bf16 constants cover is the fp32 accumulation on the bf16 matrix cores (and, bf16x6, the three dropped products
+# below 2^-23); the operand arithmetic is in the reference.  K_DIRECT_BF16X6 <= 3 K_DIRECT whatever is measured (fp32-accurate).
 K_DIRECT = 11.0
+K_DIRECT_BF16X3 = 3.8
+K_DIRECT_BF16X6 = 4.6
 K_F23 = 6.0
 K_F45 = 42.0
 K_F45_GRU = 32.0
