@@ -125,6 +125,20 @@ int ofx_fb_confidence(const float* flow_fw, const float* flow_bw, float* conf, f
 int ofx_warp_and_mask(const uint8_t* frame, long frame_bstride, const float* flow, const float* conf,
                       uint8_t* warped, uint8_t* mask, int B, int H, int W, int C, int warp_mode,
                       float sign, float thres, int ksize, int cmp_gt, void* stream);
+/* Greedy multi-reference composition (ofgen_keyframe_inpaint.py:995-1024, the loop shared by the four modes of
+ * generate_ai_frame_with_ref) in two launches and without a host read-back.  flow f32[N,H,W,2], conf f32[N,H,W] (raw, not
+ * binarised), frames u8[N,H,W,3]; 1 <= N <= 8 and H*W < 2^31 (OFX_EINVAL otherwise).  Pixel p has the pattern
+ * b_p = sum_s (conf_s(p) > thres) << s (fp32 compare, NaN = 0).  Round r draws order[r]: the lowest s with the largest number
+ * counts[r] of pixels whose bit s is set and none of whose already-drawn bits is set (a drawn reference counts 0; when nothing is
+ * left index 0 is drawn again).  select[p] = the first reference in order whose bit is set in b_p, order[0] where b_p == 0 and
+ * everywhere with first_only (generate_ai_frame_with_ref_both, :900-908); ret[p] = warp of frames[select[p]] by
+ * flow[select[p]] at p, sign +1, the bytes ofx_warp_u8's generic kernel writes; mask[p] = 255 where b_p != 0.
+ * ret u8[H,W,3], mask / select u8[H,W], order / counts i32[N].  scratch: ofx_compose_scratch_bytes(N,H,W) bytes, 16-byte
+ * aligned (OFX_ENOMEM if smaller; 0 bytes = bad shape). */
+size_t ofx_compose_scratch_bytes(int N, int H, int W);
+int ofx_compose_refs(const float* flow, const float* conf, const uint8_t* frames, uint8_t* ret, uint8_t* mask,
+                     uint8_t* select, int* order, int* counts, void* scratch, size_t scratch_bytes, int N, int H, int W,
+                     float thres, int warp_mode, int first_only, void* stream);
 
 /* ---------------------------------------------------------------- SD-inpaint hand-off */
 /* What img2img_inpaint derives from (frame, reference, mask) before its first VAE call

@@ -85,6 +85,8 @@ SIGNATURES = {
     "ofx_conf_sum": (_i, [_p, _p, _i, _l, _i, _i, _p]),
     "ofx_fb_confidence": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p]),
     "ofx_warp_and_mask": (_i, [_p, _l, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _i, _p]),
+    "ofx_compose_scratch_bytes": (_z, [_i, _i, _i]),
+    "ofx_compose_refs": (_i, [_p] * 9 + [_z, _i, _i, _i, _f, _i, _i, _p]),
     "ofx_conv2d": (_i, [C.POINTER(ConvDesc), _p]),
     "ofx_conv2d_plan": (_i, [C.POINTER(ConvDesc), _z, _i, C.POINTER(ConvPlan)]),
     "ofx_pack_conv_weight": (_l, [_p, _i, _i, _i, _i, _i, _p]),

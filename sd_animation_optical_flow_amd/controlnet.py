@@ -254,6 +254,31 @@ def control_weight(c: SingleControlNet, denoise_percentage: float) -> float:
     return 0.0 if denoise_percentage < c.guidance_start or denoise_percentage > c.guidance_end else float(c.weight)
 
 
+def check_control_nets(control_nets: Sequence[SingleControlNet], B: int, C: int, H: int, W: int, timesteps: torch.Tensor, context_dim: int) -> None:
+    """What the first `apply_multi_controlnet` of a frame would reject, checked without a launch: every net is set and takes a
+    [B,C,H,W] latent with a [B,M,context_dim] context, and every condition is a uint8 image 8x the latent that `make_hint` knows
+    how to turn into a hint.  For callers (`GuidedDDIMSampler.decode`) that promise their checks before any GPU work."""
+    for c in control_nets:
+        what = f"SingleControlNet(model={c.model!r})"
+        if c.net is None:
+            raise ValueError(f"{what}.net is None: build a ControlNet and set it (checkpoints are not loaded by model name)")
+        if c.model not in ("canny", "hed", "inpaint"):
+            raise NotImplementedError(f"{what}: make_hint builds 'canny', 'hed' and 'inpaint'")
+        shape, dtype = tuple(getattr(c.condition, "shape", ())), str(getattr(c.condition, "dtype", ""))
+        want = (HINT_SCALE * H, HINT_SCALE * W) + ((3,) if c.model == "inpaint" else ())
+        if shape != want or not dtype.endswith("uint8"):
+            raise ValueError(f"{what}: the condition must be uint8 {want} for a {H}x{W} latent, got {dtype or type(c.condition).__name__} {shape}")
+        if c.model == "inpaint" and (not c.args or "mask" not in c.args):
+            raise KeyError(f"{what} needs args['mask']")
+        net = c.net
+        if net.in_channels != C or int(net.cfg["context_dim"]) != int(context_dim):
+            raise ValueError(f"{what}: the net takes {net.in_channels} latent channels and a context of width {net.cfg['context_dim']}; "
+                             f"the sampler has {C} and {context_dim}")
+        if H % net.divisor or W % net.divisor:
+            raise ValueError(f"{what}: the latent's H and W must be multiples of {net.divisor}, got {H}x{W}")
+        net._check_common(B, H, W, timesteps, None)
+
+
 @torch.no_grad()
 def apply_multi_controlnet(x_noisy: torch.Tensor, t: torch.Tensor, cond_txt: Optional[torch.Tensor], denoise_percentage: float,
                            control_nets: Sequence[SingleControlNet]) -> List[torch.Tensor]:

@@ -852,6 +852,142 @@ __global__ __launch_bounds__(256) void fb_conf_kernel(const float* __restrict__ 
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// greedy multi-reference composition (ofgen_keyframe_inpaint.py:995-1024) without the round loop.
+// After the threshold every confidence is 0 or 1, so the reference's subtract-and-clip is bit logic: pixel p
+// carries the pattern b_p = sum_s (conf_s(p) > thres) << s, round r draws the reference with the most pixels
+// whose bit is set and none of whose already-drawn bits is set, and p is painted by the first drawn reference
+// whose bit it holds.  The draw order is a function of the 256-bin histogram of b_p alone:
+//   pass 1  pattern plane (one byte per pixel) + histogram, integer atomics only (order-independent result)
+//   pass 2  every workgroup derives order and the pattern -> reference table from the histogram, then one
+//           warp sample per pixel.
+// ------------------------------------------------------------------------------------------
+constexpr int kComposeMaxRefs = 8;
+constexpr size_t kComposeHistBytes = 256 * sizeof(int);
+
+struct RunCounter {           // a lane's (pattern, count) pair: one LDS atomic per change of pattern
+    int pat = -1, cnt = 0;
+    __device__ __forceinline__ void add(int p, int* hist) {
+        if (p != pat) {
+            if (cnt) atomicAdd(&hist[pat], cnt);
+            pat = p;
+            cnt = 0;
+        }
+        ++cnt;
+    }
+    __device__ __forceinline__ void flush(int* hist) {
+        if (cnt) atomicAdd(&hist[pat], cnt);
+    }
+};
+
+// VEC: HW % 4 == 0 and conf 16-byte aligned, so each plane is read with 16-byte loads and four patterns are
+// one 4-byte store; otherwise one pixel per iteration.
+template <bool VEC>
+__global__ __launch_bounds__(256) void compose_pattern_kernel(const float* __restrict__ conf, uint8_t* __restrict__ pat,
+                                                              int* __restrict__ ghist, int N, int HW, float thres) {
+    __shared__ int hist[256];
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    RunCounter rc;
+    const int stride = gridDim.x * 256;
+    if (VEC) {
+        const int groups = HW >> 2;
+        for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < groups; g += stride) {
+            int b[4] = {0, 0, 0, 0};
+            for (int s = 0; s < N; ++s) {
+                const float4 c = reinterpret_cast<const float4*>(conf + (size_t)s * HW)[g];
+                b[0] |= (c.x > thres ? 1 : 0) << s;          // fp32 compare: NaN is not confident
+                b[1] |= (c.y > thres ? 1 : 0) << s;
+                b[2] |= (c.z > thres ? 1 : 0) << s;
+                b[3] |= (c.w > thres ? 1 : 0) << s;
+            }
+            reinterpret_cast<uint32_t*>(pat)[g] = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) rc.add(b[j], hist);
+        }
+    } else {
+        for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < HW; p += stride) {
+            int b = 0;
+            for (int s = 0; s < N; ++s) b |= (conf[(size_t)s * HW + p] > thres ? 1 : 0) << s;
+            pat[p] = (uint8_t)b;
+            rc.add(b, hist);
+        }
+    }
+    rc.flush(hist);
+    __syncthreads();
+    const int v = hist[threadIdx.x];
+    if (v) atomicAdd(&ghist[threadIdx.x], v);                // one global atomic per non-empty bin
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void compose_sample_kernel(const float* __restrict__ flow, const uint8_t* __restrict__ frames,
+                                                             const uint8_t* __restrict__ pat, const int* __restrict__ ghist,
+                                                             uint8_t* __restrict__ ret, uint8_t* __restrict__ mask,
+                                                             uint8_t* __restrict__ select, int* __restrict__ order_out,
+                                                             int* __restrict__ counts_out, int N, int H, int W, int first_only,
+                                                             const short* __restrict__ tabi, const float* __restrict__ tabf) {
+    __shared__ int hist[256];
+    __shared__ int order[kComposeMaxRefs];
+    __shared__ int counts[kComposeMaxRefs];
+    __shared__ uint8_t table[256];
+    const int tid = threadIdx.x;
+    hist[tid] = ghist[tid];
+    __syncthreads();
+    if (tid < 64) {
+        // the first wavefront replays the greedy rounds on the histogram; lane l owns patterns l, l+64, l+128, l+192
+        int hv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) hv[k] = hist[tid + 64 * k];
+        int drawn = 0;
+        for (int r = 0; r < N; ++r) {
+            int best = 0, best_cnt = -1;
+            for (int s = 0; s < N; ++s) {
+                int c = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int p = tid + 64 * k;
+                    if (((p >> s) & 1) && !(p & drawn)) c += hv[k];
+                }
+                for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+                if (c > best_cnt) { best_cnt = c; best = s; }      // strict: the lowest index wins a tie
+            }
+            drawn |= 1 << best;
+            if (tid == 0) { order[r] = best; counts[r] = best_cnt; }
+        }
+    }
+    __syncthreads();
+    {
+        int sel = order[0];                                         // b_p == 0: the first warp is copied whole (:1010-1011)
+        if (!first_only)
+            for (int r = N - 1; r >= 0; --r)
+                if ((tid >> order[r]) & 1) sel = order[r];
+        table[tid] = (uint8_t)sel;
+    }
+    if (blockIdx.x == 0 && tid < N) {
+        order_out[tid] = order[tid];
+        counts_out[tid] = counts[tid];
+    }
+    __syncthreads();
+    const int HW = H * W;
+    for (long p = (long)blockIdx.x * 256 + tid; p < HW; p += (long)gridDim.x * 256) {
+        const int b = pat[p];
+        const int s = table[b];
+        const int y = (int)(p / W), x = (int)(p - (long)y * W);
+        const float2 f = reinterpret_cast<const float2*>(flow)[(size_t)s * HW + p];
+        uint8_t px[3];
+        warp_pixel<uint8_t, 3, MODE>(frames + (size_t)s * HW * 3, H, W, map_coord(x, f.x, 1.f), map_coord(y, f.y, 1.f), tabi, tabf, px);
+        ret[(size_t)p * 3 + 0] = px[0];
+        ret[(size_t)p * 3 + 1] = px[1];
+        ret[(size_t)p * 3 + 2] = px[2];
+        mask[p] = b ? 255 : 0;
+        select[p] = (uint8_t)s;
+    }
+}
+
+bool compose_shape_ok(int N, int H, int W) {
+    return N >= 1 && N <= kComposeMaxRefs && H > 0 && W > 0 && (long)H * W < (1L << 31);
+}
+
 int grid_for(long total) { return (int)std::min<long>((total + 255) / 256, 256L * 32); }
 
 }  // namespace
@@ -1003,6 +1139,57 @@ int ofx_warp_and_mask(const uint8_t* frame, long fbs, const float* flow, const f
     int st = ofx_warp_u8(frame, fbs, flow, warped, B, H, W, C, warp_mode, sign, stream);
     if (st) return st;
     return ofx_generate_mask(conf, nullptr, mask, B, H, W, thres, ksize, cmp_gt, stream);
+}
+
+size_t ofx_compose_scratch_bytes(int N, int H, int W) {
+    if (!compose_shape_ok(N, H, W)) return 0;
+    return kComposeHistBytes + (((size_t)H * W + 15) & ~(size_t)15);
+}
+
+int ofx_compose_refs(const float* flow, const float* conf, const uint8_t* frames, uint8_t* ret, uint8_t* mask, uint8_t* select,
+                     int* order, int* counts, void* scratch, size_t scratch_bytes, int N, int H, int W, float thres,
+                     int warp_mode, int first_only, void* stream) {
+    OFX_REQUIRE(compose_shape_ok(N, H, W), OFX_EINVAL);
+    OFX_REQUIRE(flow && conf && frames && ret && mask && select && order && counts && scratch, OFX_EINVAL);
+    OFX_REQUIRE(warp_mode >= 0 && warp_mode <= 2, OFX_EINVAL);
+    OFX_REQUIRE(scratch_bytes >= ofx_compose_scratch_bytes(N, H, W), OFX_ENOMEM);
+    OFX_REQUIRE((((uintptr_t)flow) & 7u) == 0 && (((uintptr_t)scratch) & 15u) == 0 && (((uintptr_t)conf) & 3u) == 0, OFX_EALIGN);
+    const short* tabs_i = nullptr;
+    const float* tabs_f = nullptr;
+    if (warp_mode == OFX_WARP_CV2_CUBIC) {
+        const Cv2Tables* t = nullptr;
+        int st = ensure_tables(&t);
+        if (st) return st;
+        tabs_i = t->i;
+        tabs_f = t->f;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int* hist = (int*)scratch;
+    uint8_t* pat = (uint8_t*)scratch + kComposeHistBytes;
+    const int HW = H * W;
+    OFX_HIP_CHECK(hipMemsetAsync(hist, 0, kComposeHistBytes, s));
+    {
+        const bool vec = (HW & 3) == 0 && (((uintptr_t)conf) & 15u) == 0;
+        const long items = vec ? HW >> 2 : HW;
+        const int grid = (int)std::min<long>((items + 255) / 256, 1024);
+        OfxProfScope prof("compose_pattern", s);
+        if (vec)
+            hipLaunchKernelGGL((compose_pattern_kernel<true>), dim3(grid), dim3(256), 0, s, conf, pat, hist, N, HW, thres);
+        else
+            hipLaunchKernelGGL((compose_pattern_kernel<false>), dim3(grid), dim3(256), 0, s, conf, pat, hist, N, HW, thres);
+        const int st = ofx_launch_status();
+        if (st) return st;
+    }
+    const int grid = grid_for(HW);
+    const int fo = first_only ? 1 : 0;
+    OfxProfScope prof("compose_sample", s);
+    if (warp_mode == OFX_WARP_BILINEAR)
+        hipLaunchKernelGGL((compose_sample_kernel<OFX_WARP_BILINEAR>), dim3(grid), dim3(256), 0, s, flow, frames, pat, hist, ret, mask, select, order, counts, N, H, W, fo, tabs_i, tabs_f);
+    else if (warp_mode == OFX_WARP_BICUBIC)
+        hipLaunchKernelGGL((compose_sample_kernel<OFX_WARP_BICUBIC>), dim3(grid), dim3(256), 0, s, flow, frames, pat, hist, ret, mask, select, order, counts, N, H, W, fo, tabs_i, tabs_f);
+    else
+        hipLaunchKernelGGL((compose_sample_kernel<OFX_WARP_CV2_CUBIC>), dim3(grid), dim3(256), 0, s, flow, frames, pat, hist, ret, mask, select, order, counts, N, H, W, fo, tabs_i, tabs_f);
+    return ofx_launch_status();
 }
 
 }  // extern "C"

@@ -246,6 +246,30 @@ def compose_warp_and_mask(flow_mat: np.ndarray, ai_frames: Sequence[np.ndarray],
     return ret[0].cpu().numpy(), mask2[0].cpu().numpy(), order
 
 
+@torch.no_grad()
+def compose_warp_and_mask_device(flow, conf, ai_frames, original_frame, thres: float = 0.5, warp_mode: Optional[str] = None,
+                                 expand: bool = True, first_only: bool = False, device="cuda"):
+    """`compose_warp_and_mask` for callers that stay in HBM: flow f32 [N,H,W,2], conf f32 [N,H,W] (the raw confidence; nothing is
+    written to), ai_frames u8 [N,H,W,3] or a sequence of N [H,W,3] frames, original_frame u8 [H,W,3]; device tensors or arrays
+    -> (ret_frame u8 [H,W,3], mask2 u8 [H,W], order i32 [N]), all device tensors.  One `ops.compose_refs` (two launches, one
+    warp sample per pixel) instead of N rounds of sum / read-back / full-frame warp / merge; mask2 = 255 - mask, through
+    `ops.expand_mask(., 20, 7)` when `expand`.  first_only: the `both` mode's composition (only order[0] is sampled, the mask
+    still covers every reference).  The host is never synchronised.  N outside 1..8 is a ValueError before any transfer."""
+    mode = warp_mode or _pd.DEFAULT_WARP_MODE
+    n = len(flow)
+    if not 1 <= n <= ops.COMPOSE_MAX_REFS:
+        raise ValueError(f"compose_warp_and_mask_device: 1 to {ops.COMPOSE_MAX_REFS} references, got {n}")
+    if not torch.is_tensor(ai_frames) and not isinstance(ai_frames, np.ndarray):
+        frames = torch.stack([_dev(f, device) for f in ai_frames])
+    else:
+        frames = _dev(ai_frames, device)
+    ret, mask, _, order, _ = ops.compose_refs(_dev(flow, device), _dev(conf, device), frames, thres, mode, first_only)
+    mask2 = 255 - mask
+    if expand:
+        mask2 = ops.expand_mask(mask2[None], _dev(original_frame, device)[None], 20, 7)[0]
+    return ret, mask2, order
+
+
 # --------------------------------------------------------------------------------------------------
 # the wide images of the `self_attn` and `both` modes: the frame to repaint and its reference frames side by side
 # --------------------------------------------------------------------------------------------------
@@ -453,6 +477,39 @@ class PDCNetAux:
     def calculate_multiple_to_one(self, video, source_indices, target_index: int) -> np.ndarray:
         """-> f32[N, 1, H, W, 3] (:602-625)."""
         return self._matrix(video, list(source_indices.indices), [target_index])
+
+    @torch.no_grad()
+    def multiple_to_one_device(self, video, source_indices, target_index: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`calculate_multiple_to_one` for callers that stay in HBM: (flow f32 [N,H,W,2], conf f32 [N,H,W]) on the device, the
+        values of its f32[N,1,H,W,3] matrix.  Identity pairs are zero flow with confidence 1; pairs in the `.npy` cache are
+        uploaded from it; the others come from `pair_fields` and are written to the cache as `calculate_given_pairs` does, which
+        copies them to the host once (a synchronisation; the returned tensors are the device originals, not the round trip)."""
+        sources = [int(s) for s in (source_indices.indices if hasattr(source_indices, "indices") else source_indices)]
+        t = int(target_index)
+        h, w = video.size_hw
+        flow = torch.zeros((len(sources), h, w, 2), dtype=torch.float32, device=self.device)
+        conf = torch.zeros((len(sources), h, w), dtype=torch.float32, device=self.device)
+        todo = []
+        for s in sources:                                     # a source listed twice is computed once
+            if s != t and (s, t) not in self.cached_pair and (s, t) not in todo:
+                todo.append((s, t))
+        fresh = {}
+        if todo:
+            fl, cf = self.pair_fields(video, todo)
+            packed = torch.cat([fl, cf[..., None]], dim=-1).cpu().numpy()
+            for k, pair in enumerate(todo):
+                fresh[pair] = k
+                self._save(pair[0], t, packed[k])
+        for i, s in enumerate(sources):
+            if s == t:
+                conf[i] = 1
+            elif (s, t) in fresh:
+                flow[i], conf[i] = fl[fresh[(s, t)]], cf[fresh[(s, t)]]
+            else:
+                cached = torch.from_numpy(self.load_cached(s, t)).to(self.device)
+                flow[i], conf[i] = cached[..., 0:2], cached[..., 2]
+        self.cached_pair.update(todo)
+        return flow, conf
 
     def calculate_pairwise(self, video, indices) -> np.ndarray:
         """-> f32[N, N, H, W, 3] (:627-653).  Compatibility view (1.06 GB for a 15-frame window at 512x768):

@@ -195,6 +195,47 @@ def conf_sum(x: torch.Tensor, chan: int) -> torch.Tensor:
     return out
 
 
+COMPOSE_MAX_REFS = 8
+
+
+def compose_refs(flow: torch.Tensor, conf: torch.Tensor, frames: torch.Tensor, thres: float, mode: str = "cv2_cubic",
+                 first_only: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The greedy multi-reference composition of generate_ai_frame_with_ref (ofgen_keyframe_inpaint.py:995-1024) in two launches
+    (`ofx_compose_refs`): flow f32 [N,H,W,2], conf f32 [N,H,W] (raw confidence), frames u8 [N,H,W,3] ->
+        (ret u8 [H,W,3], mask u8 [H,W], select u8 [H,W], order i32 [N], counts i32 [N]), all on the device.
+    mask is 255 where some reference is confident (the caller forms 255 - mask); select names the reference each pixel was sampled
+    from; order / counts are the draws of the reference's rounds and their winning pixel counts.  first_only: sample order[0]
+    everywhere (the `both` mode).  1 <= N <= 8 and H*W < 2^31, a ValueError before anything else is looked at.  No host
+    synchronisation."""
+    shp = tuple(getattr(flow, "shape", ()))
+    if len(shp) != 4 or shp[3] != 2:
+        raise ValueError(f"compose_refs: flow must be [N,H,W,2], got {shp}")
+    N, H, W, _ = shp
+    if not 1 <= N <= COMPOSE_MAX_REFS:
+        raise ValueError(f"compose_refs: 1 to {COMPOSE_MAX_REFS} references, got {N}")
+    if H <= 0 or W <= 0 or H * W >= 2 ** 31:
+        raise ValueError(f"compose_refs: H*W must be in 1..2^31-1, got {H}x{W}")
+    if tuple(getattr(conf, "shape", ())) != (N, H, W) or tuple(getattr(frames, "shape", ())) != (N, H, W, 3):
+        raise ValueError(f"compose_refs: conf must be [{N},{H},{W}] and frames [{N},{H},{W},3]")
+    if mode not in WARP_MODES:
+        raise ValueError(f"compose_refs: mode must be one of {sorted(WARP_MODES)}, got {mode!r}")
+    fl = _chk(flow, "flow", torch.float32)
+    cf = _chk(conf, "conf", torch.float32)
+    fr = _chk(frames, "frames", torch.uint8)
+    dev = fl.device
+    L = _lib.lib()
+    nbytes = int(L.ofx_compose_scratch_bytes(N, H, W))
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    ret = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    select = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    oc = torch.empty((2, N), dtype=torch.int32, device=dev)
+    check(L.ofx_compose_refs(_ptr(fl), _ptr(cf), _ptr(fr), _ptr(ret), _ptr(mask), _ptr(select), _ptr(oc[0]), _ptr(oc[1]),
+                             _ptr(scratch), nbytes, N, H, W, float(thres), WARP_MODES[mode], 1 if first_only else 0, _stream()),
+          "ofx_compose_refs")
+    return ret, mask, select, oc[0], oc[1]
+
+
 def fb_confidence(flow_fw: torch.Tensor, flow_bw: torch.Tensor, sigma: float = 3.0) -> Tuple[torch.Tensor, torch.Tensor]:
     """Extension: forward-backward consistency (confidence, log_confidence), each f32 [B,H,W]."""
     a = _chk(flow_fw, "flow_fw", torch.float32)

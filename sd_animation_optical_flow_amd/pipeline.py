@@ -10,8 +10,11 @@ For a clip stored as a `workspace.VideoData`:
                             when a VAE is given, the first-stage latent (`vae.VaeEncoder`)
 
 Everything between reading a PNG and handing tensors to the diffusion model stays in HBM.  What the diffusion model does
-with them (UNet, sampler, ControlNet) is out of scope: `render` is the caller's hook for it -- by
-default the "rendered" frame is the warped AI key frame with the raw frame pasted where the mask says repaint.
+with them is `render`'s: `render.SdRenderer` is the built consumer -- `ClipPipeline(algo, render=renderer,
+render_key=renderer.render_key)` repaints every packet with `run_inpainting` (UNet, guided DDIM sampler, ControlNets; the raw frame
+as reference) and renders key frames as seed frames.  Without a renderer the default hook is a stand-in that runs no model: the
+warped AI key frame with the raw frame pasted where the mask says repaint.  The reference's own hierarchical loop (key frames of key
+frames, multi-reference composition, K/V histories) is `render.run_exp`.
 """
 from __future__ import annotations
 

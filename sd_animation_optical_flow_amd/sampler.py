@@ -24,12 +24,13 @@ Needs no device to import; `ddim_schedule` is pure host code.
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import ops
+from .controlnet import ControlSchedule, SingleControlNet, apply_multi_controlnet, check_control_nets
 from .handoff import prepare_inpaint_inputs
 from .modelbase import is_f32_cuda
 
@@ -165,7 +166,8 @@ class GuidedDDIMSampler:
                unconditional_guidance_scale: float = 1.0, c_concat: Optional[torch.Tensor] = None, init_latent: Optional[torch.Tensor] = None,
                nmask: Optional[torch.Tensor] = None, guidance=None, guidance_schedule_func: Callable = lambda p: 0.1, step_noise=None,
                generator: Optional[torch.Generator] = None, control=None, reference_kv=(), callback: Optional[Callable] = None,
-               guidance_space: str = "latent", temperature: float = 1.0, **not_built) -> Tuple[torch.Tensor, object]:
+               guidance_space: str = "latent", temperature: float = 1.0, control_nets: Optional[Sequence[SingleControlNet]] = None,
+               **not_built) -> Tuple[torch.Tensor, object]:
         """`GuidedDDIMSample.decode`: x_latent f32 [B,4,h,w] on the device (what `stochastic_encode` returned), context [B,M,context_dim]
         -> (x_dec [B,4,h,w], last_gs).  The bookkeeping is `decode_plan`'s; every check runs before the first launch.
 
@@ -189,6 +191,14 @@ class GuidedDDIMSampler:
         control may also be a callable control(i, p), called right before the UNet call of iteration i with `decode_plan`'s p: it
         returns what control= takes, a list at the UNet's batch or None, and each distinct object it returns is validated
         (`unet._check_inputs`) before it is used.  `controlnet.ControlSchedule` is one: the nets' guidance windows.
+        control_nets: what the reference's driver passes (ofgen_keyframe_inpaint.py:798, :1115), a sequence of
+        `controlnet.SingleControlNet`; mutually exclusive with control= (ValueError before any launch), and the nets, their conditions
+        (uint8, 8x the latent) and their sizes are checked before any launch too (`controlnet.check_control_nets`).  Every net's `result` is set
+        to None, and right before the first UNet call `apply_multi_controlnet(x, t, ctx, p, nets)` runs once on exactly that call's
+        inputs -- the latent channels of the loop's buffer as NCHW at the UNet's batch, after the opening blend; the first step's
+        timesteps; the doubled context -- which computes and caches the nets' residuals; the loop then reads them through
+        `ControlSchedule(nets)`.  The reference tree holds no code that says which step's x_noisy the cached residuals come from:
+        the first call of a function that caches on first use is the first step, and that is what this does.
         `self.last_kv_hists` is the K/V history of the LAST UNet call -- the final step (index 0), the least noisy latent, at the
         UNet's batch (unconditional rows first).  The reference's driver stores one history per frame and its tree has no code that
         defines which step's; the last call is what a loop that keeps overwriting one variable leaves behind.
@@ -202,6 +212,12 @@ class GuidedDDIMSampler:
         if guidance_space != "latent":
             raise NotImplementedError(f"guidance_space={guidance_space!r} is not built: the reference's pixel branch reads an undefined name "
                                       "(guided_ldm.py:112)")
+        if control_nets is not None:
+            if control is not None:
+                raise ValueError("control= and control_nets= are mutually exclusive")
+            control_nets = list(control_nets)
+            if not control_nets or any(c.net is None for c in control_nets):
+                raise ValueError("control_nets must be a non-empty sequence of SingleControlNet whose .net is set (None: no ControlNets)")
         sched = self._sched()
         plan = decode_plan(sched, t_start, guidance_schedule_func)
         cfg_on = unconditional_context is not None and unconditional_guidance_scale != 1.0
@@ -272,6 +288,8 @@ class GuidedDDIMSampler:
         ts_all = torch.tensor([[float(step)] * UB for _, _, step, _ in plan], dtype=torch.float32)
         control_fn = control if callable(control) else None                           # control(i, p): validated as it is returned
         unet._check_inputs(UB, h, w, ts_all[0], None, None if control_fn else control, reference_kv)   # raises on a bad control / reference_kv / size
+        if control_nets is not None:
+            check_control_nets(control_nets, UB, Cz, h, w, ts_all[0], cd)             # nets, conditions and sizes: before the opening blend
         # ---- setup: the only allocations and layout changes of the loop
         if step_noise is None and n_noise:
             drawn = torch.randn((n_noise, t_start, B, Cz, h, w), generator=generator, device=dev, dtype=torch.float32)
@@ -304,6 +322,11 @@ class GuidedDDIMSampler:
         if gate[0]:
             k, kw = blend_args(0)
             ops.ddim_step(x0v, k, out0=x0v, out1=x1v, blend_only=True, **kw)
+        if control_nets is not None:
+            for c in control_nets:
+                c.result = None
+            apply_multi_controlnet(buf[..., :Cz].permute(0, 3, 1, 2).contiguous(), ts_all[0], ctx_in, plan[0][0], control_nets)
+            control_fn = ControlSchedule(control_nets)
         kv: List[Tuple[torch.Tensor, torch.Tensor]] = []
         checked: list = []                                                            # the distinct objects control(i, p) has returned
         for i, (p, index, step, gs) in enumerate(plan):
@@ -340,7 +363,8 @@ def img2img_inpaint(unet, vae_encoder, vae_decoder, image_bgr, reference_bgr, ma
                     unconditional_context: Optional[torch.Tensor], *, denoising_strength: float = 0.05, ddim_steps: int = 50,
                     mask_blur: float = 16, unconditional_guidance_scale: float = 7.0, guidance_schedule_func: Callable = lambda p: 0.1,
                     noise: Optional[Dict[str, torch.Tensor]] = None, generator: Optional[torch.Generator] = None, control=None,
-                    reference_kv=(), sampler: Optional[GuidedDDIMSampler] = None, fill_masked: bool = False):
+                    reference_kv=(), sampler: Optional[GuidedDDIMSampler] = None, fill_masked: bool = False,
+                    control_nets: Optional[Sequence[SingleControlNet]] = None, want_init_decoded: bool = True):
     """`GuidedLDM.img2img_inpaint` (guided_ldm_inpainting.py:262-345), eta = 0.  With a reference frame: image_bgr / reference_bgr
     uint8 [H,W,3] (cv2 channel order) and mask uint8 [H,W] (255 = repaint) as `handoff.prepare_inpaint_inputs` takes them, context /
     unconditional_context [1,M,context_dim] device tensors (`text_encoder.ClipTextEncoder.conditioning` makes both from a prompt pair) ->
@@ -358,7 +382,11 @@ def img2img_inpaint(unet, vae_encoder, vae_decoder, image_bgr, reference_bgr, ma
     noised init_latent.  reference_bgr None without fill_masked is a NotImplementedError, fill_masked with a reference or
     noise["fill"] without fill_masked a ValueError.  t_enc == 0 (the default strength 0.05 needs at least 20 steps) is a
     ValueError: the reference would run zero steps and index an empty range.  All raise before any launch.
-    `sampler`: a GuidedDDIMSampler over `unet` to reuse (its `last_kv_hists` is then the caller's to read)."""
+    `sampler`: a GuidedDDIMSampler over `unet` to reuse (its `last_kv_hists` is then the caller's to read).
+    control_nets: `decode`'s (exclusive with control=: a ValueError here too, before any launch).  want_init_decoded=False skips
+    the second VAE decode, which the reference's driver only writes to its visualisation; the third result is then None."""
+    if control is not None and control_nets is not None:
+        raise ValueError("control= and control_nets= are mutually exclusive")
     if reference_bgr is None and not fill_masked:
         raise NotImplementedError("reference_bgr=None is the reference's fill_mask_input path: ask for it with fill_masked=True")
     if fill_masked and reference_bgr is not None:
@@ -399,11 +427,11 @@ def img2img_inpaint(unet, vae_encoder, vae_decoder, image_bgr, reference_bgr, ma
     decoded, last_gs = smp.decode(x1, context, t_enc, unconditional_context=unconditional_context,
                                   unconditional_guidance_scale=unconditional_guidance_scale, c_concat=c_concat, init_latent=init_latent,
                                   nmask=latmask, guidance_schedule_func=guidance_schedule_func, step_noise=n_step, control=control,
-                                  reference_kv=reference_kv)
+                                  reference_kv=reference_kv, control_nets=control_nets)
     if last_gs > 0:
         decoded = final_blend(init_latent, decoded, latmask)
     x_samples = vae_decoder.decode_first_stage(decoded)
-    init_latent_decoded = vae_decoder.decode_first_stage(init_latent).clip(-1, 1)
+    init_latent_decoded = vae_decoder.decode_first_stage(init_latent).clip(-1, 1) if want_init_decoded else None
     return torch.clip(x_samples, -1, 1), image, init_latent_decoded
 
 
@@ -424,7 +452,7 @@ def img2img(unet, vae_encoder, vae_decoder, image_bgr, context: torch.Tensor, un
             denoising_strength: float, ddim_steps: int = 50, target_bgr=None, guidance_schedule_func: Callable = lambda p: 0.1,
             unconditional_guidance_scale: float = 7.0, noise: Optional[Dict[str, torch.Tensor]] = None,
             generator: Optional[torch.Generator] = None, control=None, reference_kv=(),
-            sampler: Optional[GuidedDDIMSampler] = None) -> torch.Tensor:
+            sampler: Optional[GuidedDDIMSampler] = None, control_nets: Optional[Sequence[SingleControlNet]] = None) -> torch.Tensor:
     """`GuidedLDM.img2img`, eta = 0: the seed key frames of the live driver and the guided frames of `ofgen.py`.  image_bgr /
     target_bgr uint8 [H,W,3] or [B,H,W,3] (cv2 channel order; several frames side by side in one wide image are one image), context
     / unconditional_context [B,M,context_dim] device tensors -> x_samples f32 [B,3,H,W] clipped to [-1,1].
@@ -437,7 +465,10 @@ def img2img(unet, vae_encoder, vae_decoder, image_bgr, context: torch.Tensor, un
     drawn only when a target is given.  control (a list or a callable, as `decode` takes) and reference_kv go to `decode`.
     `sampler`: a GuidedDDIMSampler over `unet` to reuse; its `last_kv_hists` is what the driver stores per key frame.
     t_enc == 0 and a UNet whose in_channels is not 4 (there is no c_concat on this path) are ValueErrors before any launch.  No
-    launch of its own: the loop is `decode`, around it two (or three) VAE passes."""
+    launch of its own: the loop is `decode`, around it two (or three) VAE passes.  control_nets is `decode`'s (exclusive with
+    control=: a ValueError here too, before any launch)."""
+    if control is not None and control_nets is not None:
+        raise ValueError("control= and control_nets= are mutually exclusive")
     t_enc = int(min(denoising_strength, 0.999) * ddim_steps)
     if t_enc <= 0:
         raise ValueError(f"denoising_strength={denoising_strength} at {ddim_steps} steps gives t_enc = 0: no step to run")
@@ -473,5 +504,6 @@ def img2img(unet, vae_encoder, vae_decoder, image_bgr, context: torch.Tensor, un
     x1 = smp.stochastic_encode(init_latent, t_enc, n_x1)
     decoded, _ = smp.decode(x1, context, t_enc, unconditional_context=unconditional_context,
                             unconditional_guidance_scale=unconditional_guidance_scale, guidance=target_latent,
-                            guidance_schedule_func=guidance_schedule_func, control=control, reference_kv=reference_kv)
+                            guidance_schedule_func=guidance_schedule_func, control=control, reference_kv=reference_kv,
+                            control_nets=control_nets)
     return torch.clip(vae_decoder.decode_first_stage(decoded), -1, 1)
