@@ -94,6 +94,25 @@ int ofx_dilate_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, int ksiz
 /* out = mask | dilate(255*(gray(|laplacian(image)| mod 256) > edge_thres), ellipse ksize) */
 int ofx_expand_mask(const uint8_t* mask, const uint8_t* image_bgr, uint8_t* out, uint8_t* scratch,
                     int B, int H, int W, int edge_thres, int ksize, void* stream);
+/* The kernel and launch shape ofx_generate_mask / ofx_warp_and_mask (src 0: conf < thres, 1: !(conf > thres)) or ofx_expand_mask
+ * (src 3: Laplacian edges) take for B images of H x W and an odd ksize <= 31, without launching: the launcher calls this and
+ * launches what it says.  aligned16: whether every pointer of the call (confidence, output and, when given, the mask ORed in) is
+ * 16-byte aligned.  Only numbers are looked at: no device is needed.  Succeeds for every shape the entry points accept with
+ * B <= 65535 (the tile kernels put the image index on the grid's z axis); OFX_EINVAL otherwise. */
+#define OFX_MASK_KERNEL_ROWS   0   /* full-width bands of one image: confidence sources, W % 4 == 0, W <= 4096, aligned16 */
+#define OFX_MASK_KERNEL_NARROW 1   /* 56 x 32 ballot tiles: ksize <= 9 */
+#define OFX_MASK_KERNEL_WIDE   2   /* 64 x 32 ballot tiles */
+typedef struct ofx_mask_route {
+    int kernel;              /* OFX_MASK_KERNEL_* */
+    int band_rows;           /* output rows per workgroup: 64, 32 or 16 (rows kernel), 32 (tile kernels) */
+    int threads;             /* per workgroup */
+    int nplanes;             /* rows kernel: distinct half-widths > 0 of the element kept as spread planes in LDS (0..8), or -1:
+                                direct evaluation (more than 8 of them, or the planes would need more than 48 KiB); tiles: 0 */
+    int xcd_map;             /* rows kernel: 1 = workgroup ids laid out so that the bands of an image share an XCD */
+    int lds_bytes;           /* dynamic LDS per workgroup (rows kernel; the tile kernels' LDS is static: 0) */
+    int workgroups;          /* in the grid, the idle ones of a ragged last XCD group included */
+} ofx_mask_route;
+int ofx_mask_plan(int src, int B, int H, int W, int ksize, int aligned16, ofx_mask_route* out);
 /* v = |flow| with v[conf < conf_floor] = 0 (of_calc, ofgen_keyframe_inpaint.py:118-126) */
 int ofx_travel_distance(const float* flow, const float* conf, float* out, int B, int H, int W,
                         float conf_floor, void* stream);
@@ -109,7 +128,8 @@ int ofx_travel_mask(const float* conf, const float* flow, const float* dist, con
 /* merge_images 'naive' (:676-681): out = base*(1-m) + second*m with m = (mask==255) */
 int ofx_merge_images(const uint8_t* base, const uint8_t* second, const uint8_t* mask, uint8_t* out,
                      int B, int H, int W, int C, void* stream);
-/* mix_propagated_ai_frame (:306-315) */
+/* mix_propagated_ai_frame (:306-315): out = raw * (1 - w) + warped * w, w = ppw where mask <= 127, 1 - ppw above; ppw < 0.001:
+ * out = raw (:307-308) */
 int ofx_mix_frames(const uint8_t* raw, const uint8_t* warped, const uint8_t* mask, uint8_t* out,
                    int B, int H, int W, int C, float ppw, void* stream);
 /* sums[n] = sum over HW of conf_like[n, :, :, chan] for a f32[N,H,W,nchan] tensor (f64 accumulate);

@@ -53,6 +53,11 @@ class ConvPlan(C.Structure):
                                        "group_m", "stats_rows")]
 
 
+class MaskRoute(C.Structure):
+    """Mirror of `ofx_mask_route` (include/ofx.h)."""
+    _fields_ = [(n, C.c_int) for n in ("kernel", "band_rows", "threads", "nplanes", "xcd_map", "lds_bytes", "workgroups")]
+
+
 class DdimCoef(C.Structure):
     """Mirror of `ofx_ddim_coef` (include/ofx.h)."""
     _fields_ = [(n, C.c_float) for n in ("cfg", "sqrt_at", "sqrt_1m_at", "sqrt_aprev", "dir_coef", "sigma_t", "g", "sa", "s1")]
@@ -77,6 +82,7 @@ SIGNATURES = {
     "ofx_generate_mask": (_i, [_p, _p, _p, _i, _i, _i, _f, _i, _i, _p]),
     "ofx_dilate_u8": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "ofx_expand_mask": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "ofx_mask_plan": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(MaskRoute)]),
     "ofx_travel_distance": (_i, [_p, _p, _p, _i, _i, _i, _f, _p]),
     "ofx_flow_magnitude": (_i, [_p, _p, _l, _p]),
     "ofx_travel_mask": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p]),

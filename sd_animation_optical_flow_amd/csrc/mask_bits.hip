@@ -64,6 +64,13 @@ __device__ __forceinline__ bool src_bit(const BitArgs& a, long b, int y, int x) 
     return ((g[0] * 9798 + g[1] * 19235 + g[2] * 3735 + (1 << 14)) >> 15) > a.edge_thres;
 }
 
+// the tile kernels' 8-byte store (and or_mask load) at element `base`: the ADDRESSES decide, a caller's mask may start anywhere
+__device__ __forceinline__ bool aligned8(const BitArgs& a, long base) {
+    const uintptr_t o = reinterpret_cast<uintptr_t>(a.out + base);
+    const uintptr_t m = a.or_mask ? reinterpret_cast<uintptr_t>(a.or_mask + base) : (uintptr_t)0;
+    return ((o | m) & 7u) == 0;
+}
+
 struct U128 {
     unsigned long long lo, hi;
 };
@@ -150,7 +157,7 @@ __global__ __launch_bounds__(256) void mask_bits_kernel(const BitArgs a) {
     if (xs >= a.W) return;
     const unsigned bits = (unsigned)((outbits[row] >> (seg * 8)) & 0xFFu);
     const long base = (b * a.H + y) * (long)a.W + xs;
-    if (xs + 8 <= a.W && ((base & 7) == 0)) {
+    if (xs + 8 <= a.W && aligned8(a, base)) {
         unsigned long long v = 0;
 #pragma unroll
         for (int i = 0; i < 8; ++i)
@@ -220,7 +227,7 @@ __global__ __launch_bounds__(256) void mask_bits_narrow_kernel(const BitArgs a) 
     if (xs >= a.W) return;
     const unsigned bits = (unsigned)((outbits[row] >> (seg * 8)) & 0xFFu);
     const long base = (b * a.H + y) * (long)a.W + xs;
-    if (xs + 8 <= a.W && ((base & 7) == 0)) {
+    if (xs + 8 <= a.W && aligned8(a, base)) {
         unsigned long long v = 0;
 #pragma unroll
         for (int i = 0; i < 8; ++i)
@@ -450,71 +457,123 @@ __global__ __launch_bounds__(NT) void mask_rows_kernel(const BitArgs a, const in
 
 }  // namespace
 
+
+namespace {
+
+// mask_rows_kernel's static LDS (hw_s, plane_s, plane_hw_s: 72 bytes, rounded up to the dynamic array's alignment)
+constexpr size_t kRowsStaticLds = 80;
+constexpr size_t kLdsPerWorkgroup = 64 * 1024;
+constexpr size_t kPlanesLdsCap = 48 * 1024;
+
+// the distinct half widths > 0 of the element, ascending -> plane_hw; returns how many, -1 when more than 8
+int element_planes(int r, const signed char* hw, signed char* plane_hw) {
+    int np = 0;
+    for (int hwv = 1; hwv <= kMaxR; ++hwv) {
+        bool used = false;
+        for (int i = 0; i < 2 * r + 1; ++i) used |= hw[i] == hwv;
+        if (!used) continue;
+        if (np == 8) return -1;
+        plane_hw[np++] = (signed char)hwv;
+    }
+    return np;
+}
+
+size_t rows_lds_bytes(int bh, int r, int W, int np) {
+    const size_t nwords = (size_t)((W + 31) >> 5);
+    return sizeof(unsigned) * ((size_t)(bh + 2 * r) * (nwords + 2) + (size_t)bh * nwords + (size_t)np * (bh + 2 * r) * nwords);
+}
+
+}  // namespace
+
 // hw[]: ellipse half width per row dy = -r..r (-1 = empty row); see make_ellipse in warp_mask.hip
+int ofx_mask_bits_plan(int src, int B, int H, int W, int r, const signed char* hw, int aligned16, ofx_mask_route* out) {
+    OFX_REQUIRE(out && hw && B > 0 && H > 0 && W > 0 && r >= 0 && r <= kMaxR, OFX_EINVAL);
+    OFX_REQUIRE(src == OFX_MSRC_CONF_LT || src == OFX_MSRC_CONF_NGT || src == OFX_MSRC_EDGES, OFX_EINVAL);
+    ofx_mask_route p{};
+    if (src != OFX_MSRC_EDGES && (W & 3) == 0 && W <= 4096 && aligned16) {
+        // band height / workgroup shape, measured at B = 64, 512x768, 7x7 (tools/mask_bench.py): 64 rows x 512 threads
+        // 26.7-27.5 us, 32 x 256: 28.1-29.4, 96 x 512: 28.4, 16 x 256: 29.9, 64 x 1024: 32.4 (the vertical halo is 2r
+        // rows per band, so taller bands re-read less); small batches take shorter bands to keep every CU busy
+        int bh = 64;
+        if ((long)B * ofx_cdiv(H, 64) < 512) bh = 32;
+        if ((long)B * ofx_cdiv(H, 32) < 512) bh = 16;
+        signed char plane_hw[8];
+        const int distinct = element_planes(r, hw, plane_hw);
+        // a band that does not fit a workgroup's LDS (wide frames in a large batch) takes the next smaller height
+        for (; bh >= 16; bh >>= 1) {
+            int np = distinct;
+            if (np > 0 && rows_lds_bytes(bh, r, W, np) > kPlanesLdsCap) np = -1;   // wide frames x many widths: direct
+            const size_t lds = rows_lds_bytes(bh, r, W, np > 0 ? np : 0);
+            if (lds + kRowsStaticLds > kLdsPerWorkgroup) continue;
+            const int nbands = ofx_cdiv(H, bh);
+            p.xcd_map = B >= 16 ? 1 : 0;
+            const long nwg = p.xcd_map ? (long)ofx_cdiv(B, 8) * 8 * nbands : (long)B * nbands;
+            OFX_REQUIRE(nwg < (1L << 31), OFX_EINVAL);
+            p.kernel = OFX_MASK_KERNEL_ROWS;
+            p.band_rows = bh;
+            p.threads = bh == 64 ? 512 : 256;
+            p.nplanes = np;
+            p.lds_bytes = (int)lds;
+            p.workgroups = (int)nwg;
+            *out = p;
+            return 0;
+        }
+        // no band height fits: the ballot tiles below have no such limit
+    }
+    OFX_REQUIRE(B <= 65535, OFX_EINVAL);   // the image index is the grid's z
+    p.kernel = r <= kNH ? OFX_MASK_KERNEL_NARROW : OFX_MASK_KERNEL_WIDE;
+    p.band_rows = kTH;
+    p.threads = 256;
+    p.workgroups = (int)((long)ofx_cdiv(W, r <= kNH ? kNW : kTW) * ofx_cdiv(H, kTH) * B);
+    *out = p;
+    return 0;
+}
+
 int ofx_mask_bits_launch(int src, const float* conf, float* log_conf, const uint8_t* image, const uint8_t* or_mask,
                          uint8_t* out, int B, int H, int W, float thres, int edge_thres, int r, const signed char* hw,
                          const char* name, hipStream_t s) {
-    OFX_REQUIRE(r >= 0 && r <= kMaxR, OFX_EINVAL);
+    ofx_mask_route p;
+    const int aligned16 = ofx_aligned16(conf) && ofx_aligned16(out) && (or_mask == nullptr || ofx_aligned16(or_mask));
+    const int st = ofx_mask_bits_plan(src, B, H, W, r, hw, aligned16, &p);
+    if (st != 0) return st;
     BitArgs a{};
     a.conf = conf; a.log_conf = log_conf; a.image = image; a.or_mask = or_mask; a.out = out;
     a.H = H; a.W = W; a.thres = thres; a.edge_thres = edge_thres; a.r = r;
     for (int i = 0; i < 2 * kMaxR + 1; ++i) a.hw[i] = i < 2 * r + 1 ? hw[i] : (signed char)-1;
     OfxProfScope prof(name, s);
-    if (src != OFX_MSRC_EDGES && (W & 3) == 0 && W <= 4096 && ofx_aligned16(conf) && ofx_aligned16(out) &&
-        (or_mask == nullptr || ofx_aligned16(or_mask))) {
-        // band height / workgroup shape, measured at B = 64, 512x768, 7x7 (tools/mask_bench.py): 64 rows x 512 threads
-        // 26.7-27.5 us, 32 x 256: 28.1-29.4, 96 x 512: 28.4, 16 x 256: 29.9, 64 x 1024: 32.4 (the vertical halo is 2r
-        // rows per band, so taller bands re-read less); small batches take shorter bands to keep every CU busy
-        const int nwords = (W + 31) >> 5;
-        int bh = 64;
-        if ((long)B * ofx_cdiv(H, 64) < 512) bh = 32;
-        if ((long)B * ofx_cdiv(H, 32) < 512) bh = 16;
-        const int nbands = ofx_cdiv(H, bh);
-        const int xcd_map = B >= 16 ? 1 : 0;
-        const long nwg = xcd_map ? (long)ofx_cdiv(B, 8) * 8 * nbands : (long)B * nbands;
-        OFX_REQUIRE(nwg < (1L << 31), OFX_EINVAL);
-        // distinct half widths of the element -> planes
-        a.nplanes = 0;
-        for (int hwv = 1; hwv <= kMaxR && a.nplanes >= 0; ++hwv) {
-            bool used = false;
-            for (int i = 0; i < 2 * r + 1; ++i) used |= a.hw[i] == hwv;
-            if (!used) continue;
-            if (a.nplanes == 8) { a.nplanes = -1; break; }
-            a.plane_hw[a.nplanes++] = (signed char)hwv;
-        }
+    if (p.kernel == OFX_MASK_KERNEL_ROWS) {
+        // element rows -> planes (-1: empty row, -2: half width 0, the raw bitmap)
+        a.nplanes = p.nplanes;
+        if (p.nplanes > 0) element_planes(r, a.hw, a.plane_hw);
         for (int i = 0; i < 2 * kMaxR + 1; ++i) {
             a.plane_of[i] = -1;
             if (i < 2 * r + 1 && a.hw[i] == 0) a.plane_of[i] = -2;
-            for (int k = 0; k < a.nplanes; ++k)
+            for (int k = 0; k < p.nplanes; ++k)
                 if (i < 2 * r + 1 && a.hw[i] == a.plane_hw[k]) a.plane_of[i] = (signed char)k;
         }
-        auto lds_words = [&](int np) { return (size_t)(bh + 2 * r) * (nwords + 2) + (size_t)bh * nwords + (size_t)np * (bh + 2 * r) * nwords; };
-        if (a.nplanes > 0 && lds_words(a.nplanes) * sizeof(unsigned) > 48 * 1024) a.nplanes = -1;   // wide frames x many widths: direct
-        const size_t lds = lds_words(a.nplanes > 0 ? a.nplanes : 0) * sizeof(unsigned);
-        OFX_REQUIRE(lds <= 64 * 1024, OFX_EINVAL);
-#define OFX_MASK_ROWS(NT, BATCH)                                                                                             \
-    do {                                                                                                                     \
-        if (src == OFX_MSRC_CONF_LT)                                                                                         \
-            hipLaunchKernelGGL((mask_rows_kernel<OFX_MSRC_CONF_LT, NT, BATCH>), dim3((unsigned)nwg), dim3(NT), lds, s, a, nbands, B, \
-                               xcd_map, bh);                                                                                 \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((mask_rows_kernel<OFX_MSRC_CONF_NGT, NT, BATCH>), dim3((unsigned)nwg), dim3(NT), lds, s, a, nbands, B, \
-                               xcd_map, bh);                                                                                 \
+        const int bh = p.band_rows, nbands = ofx_cdiv(H, bh), xcd_map = p.xcd_map;
+        const dim3 grid((unsigned)p.workgroups);
+        const size_t lds = (size_t)p.lds_bytes;
+#define OFX_MASK_ROWS(NT, BATCH)                                                                                              \
+    do {                                                                                                                      \
+        if (src == OFX_MSRC_CONF_LT)                                                                                          \
+            hipLaunchKernelGGL((mask_rows_kernel<OFX_MSRC_CONF_LT, NT, BATCH>), grid, dim3(NT), lds, s, a, nbands, B, xcd_map, bh);  \
+        else                                                                                                                  \
+            hipLaunchKernelGGL((mask_rows_kernel<OFX_MSRC_CONF_NGT, NT, BATCH>), grid, dim3(NT), lds, s, a, nbands, B, xcd_map, bh); \
     } while (0)
-        if (bh == 64)
+        if (p.threads == 512)
             OFX_MASK_ROWS(512, 9);
         else
             OFX_MASK_ROWS(256, 8);
 #undef OFX_MASK_ROWS
         return ofx_launch_status();
     }
-    if (r <= kNH) {
+    if (p.kernel == OFX_MASK_KERNEL_NARROW) {
         dim3 gridn(ofx_cdiv(W, kNW), ofx_cdiv(H, kTH), B);
         switch (src) {
             case OFX_MSRC_CONF_LT: hipLaunchKernelGGL((mask_bits_narrow_kernel<OFX_MSRC_CONF_LT>), gridn, dim3(256), 0, s, a); break;
             case OFX_MSRC_CONF_NGT: hipLaunchKernelGGL((mask_bits_narrow_kernel<OFX_MSRC_CONF_NGT>), gridn, dim3(256), 0, s, a); break;
-            case OFX_MSRC_EDGES: hipLaunchKernelGGL((mask_bits_narrow_kernel<OFX_MSRC_EDGES>), gridn, dim3(256), 0, s, a); break;
-            default: return OFX_EINVAL;
+            default: hipLaunchKernelGGL((mask_bits_narrow_kernel<OFX_MSRC_EDGES>), gridn, dim3(256), 0, s, a); break;
         }
         return ofx_launch_status();
     }
@@ -522,8 +581,7 @@ int ofx_mask_bits_launch(int src, const float* conf, float* log_conf, const uint
     switch (src) {
         case OFX_MSRC_CONF_LT: hipLaunchKernelGGL((mask_bits_kernel<OFX_MSRC_CONF_LT>), grid, dim3(256), 0, s, a); break;
         case OFX_MSRC_CONF_NGT: hipLaunchKernelGGL((mask_bits_kernel<OFX_MSRC_CONF_NGT>), grid, dim3(256), 0, s, a); break;
-        case OFX_MSRC_EDGES: hipLaunchKernelGGL((mask_bits_kernel<OFX_MSRC_EDGES>), grid, dim3(256), 0, s, a); break;
-        default: return OFX_EINVAL;
+        default: hipLaunchKernelGGL((mask_bits_kernel<OFX_MSRC_EDGES>), grid, dim3(256), 0, s, a); break;
     }
     return ofx_launch_status();
 }

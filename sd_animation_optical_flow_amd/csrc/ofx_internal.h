@@ -150,6 +150,8 @@ enum { OFX_MSRC_CONF_LT = 0, OFX_MSRC_CONF_NGT = 1, OFX_MSRC_EDGES = 3 };   // c
 int ofx_mask_bits_launch(int src, const float* conf, float* log_conf, const uint8_t* image, const uint8_t* or_mask,
                          uint8_t* out, int B, int H, int W, float thres, int edge_thres, int r, const signed char* hw,
                          const char* name, hipStream_t s);
+// the route of that launch (host only; ofx_mask_plan of include/ofx.h with the element already made)
+int ofx_mask_bits_plan(int src, int B, int H, int W, int r, const signed char* hw, int aligned16, ofx_mask_route* out);
 // warp_fast.hip: bilinear warp of one shared uint8 RGB key frame (0 = launched, OFX_EINVAL = shape not taken)
 int ofx_warp_bilinear_shared_launch(const uint8_t* frame, const float* flow, uint8_t* out, int B, int H, int W, float sign,
                                     hipStream_t s);

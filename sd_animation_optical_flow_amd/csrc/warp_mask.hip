@@ -1024,6 +1024,13 @@ int ofx_generate_mask(const float* conf, float* log_conf, uint8_t* mask, int B, 
                                 el.r, el.hw, "generate_mask", (hipStream_t)stream);
 }
 
+int ofx_mask_plan(int src, int B, int H, int W, int ksize, int aligned16, ofx_mask_route* out) {
+    OFX_REQUIRE(out && B > 0 && H > 0 && W > 0, OFX_EINVAL);
+    OFX_REQUIRE(ksize >= 1 && ksize <= kMaxK && (ksize & 1), OFX_EINVAL);
+    const Ellipse el = make_ellipse(ksize);
+    return ofx_mask_bits_plan(src, B, H, W, el.r, el.hw, aligned16, out);
+}
+
 int ofx_dilate_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, int ksize, void* stream) {
     OFX_REQUIRE(in && out && in != out && B > 0 && H > 0 && W > 0, OFX_EINVAL);
     OFX_REQUIRE(ksize >= 1 && ksize <= kMaxK && (ksize & 1), OFX_EINVAL);
@@ -1105,8 +1112,10 @@ int ofx_mix_frames(const uint8_t* raw, const uint8_t* warped, const uint8_t* mas
     OFX_REQUIRE(raw && warped && mask && out && B > 0 && H > 0 && W > 0 && C > 0, OFX_EINVAL);
     const long npix = (long)B * H * W;
     hipStream_t s = (hipStream_t)stream;
-    const float w_lo = ppw;
-    const float w_hi = (float)(1.0 - (double)ppw);
+    // :307-308: a weight below 0.001 returns the raw frame (both weights 0: raw * 1 + warped * 0, exact for bytes)
+    const bool keep_raw = (double)ppw < 0.001;
+    const float w_lo = keep_raw ? 0.f : ppw;
+    const float w_hi = keep_raw ? 0.f : (float)(1.0 - (double)ppw);
     OfxProfScope prof("mix_frames", s);
     hipLaunchKernelGGL(mix_kernel, dim3(grid_for(npix)), dim3(256), 0, s, raw, warped, mask, out, C, npix, w_lo, w_hi);
     return ofx_launch_status();
