@@ -457,6 +457,14 @@ int ofx_abs_diff_sum_u8(const uint8_t* a, long a_bstride, const uint8_t* b, long
                                  the GRU / flow epilogues, nmean / nrstd, ofx_conv2d_stats, nz > 1, the pooled correlation
                                  volume, a split-K workspace (splitk_ws != NULL) and the paired-pipeline tile marker.  wino_w /
                                  wino4_w are ignored, as under the split-bf16 modes */
+#define OFX_PREC_F16_EPI (OFX_PREC_F16 | 256)   /* 261: the arithmetic, tiles and kernels of OFX_PREC_F16 (ofx_conv_plan.prec reads
+                                 OFX_PREC_F16) with three more things served, the descriptors of the flow network under
+                                 OFX_RAFT_F16: the GRU gate epilogues OFX_EPI_GRU_ZR / _Q (the gate algebra is fp32 on the
+                                 accumulators); nmean / nrstd (the normalised, ReLU'd fp32 value is what is rounded to half);
+                                 ofx_conv2d_stats (the statistics come from the fp32 accumulators, as in fp32).  A value of its own so
+                                 that what OFX_PREC_F16 documents as rejected stays rejected for callers written against it.  Still
+                                 OFX_EINVAL before any launch: the flow epilogue, nz > 1, the pooled volume, a split-K workspace
+                                 and the paired-pipeline tile marker */
 
 typedef struct ofx_conv_desc {
     /* input: NHWC fp32, up to two channel segments (torch.cat along C without materialising) */
@@ -742,6 +750,16 @@ size_t ofx_raft_workspace_bytes_mode(const ofx_raft* r, int n_images, int B, int
                                      final low-resolution flow.  coords1 = coords0 + init (one fp32 rounding); the first iteration sees
                                      the flow (coords0 + init) - coords0.  Every entry point and both networks; without the flag nothing
                                      changes.  ofx_forward_interpolate makes the init of the next pair of a video from this one's. */
+#define OFX_RAFT_F16 4096         /* opt-in, the basic network only: every convolution of the encoders and the update block in
+                                     the fp16 arithmetic (descriptors with OFX_PREC_F16_EPI; the reference's args.mixed_precision, RAFT/core/raft.py:99,110,127).  Rounded to
+                                     half: the two operands of each convolution as they are staged, nothing else.  Not rounded: the
+                                     activations in memory, the feature maps, the correlation volume (exact fp32 as in the reference,
+                                     which casts the maps back with .float(); OFX_RAFT_VOL_BF16X3 / _BF16X6 stay independent and may
+                                     be combined), the lookup, the flow head, coords1 + delta and the convex upsample -- a subset of
+                                     autocast's roundings.  With OFX_RAFT_BF16X3 or _BF16X6: OFX_EINVAL.  The convolutions get no
+                                     split-K workspace in this mode (that arithmetic has no split-K kernels), so small grids run
+                                     unsplit: a single pair may be slower than in fp32.  Flow EPE vs float64 ~1e-2 px after 20
+                                     iterations (fp32: ~5e-6): the 1e-3 px bar of the default path does not apply */
 
 /* RAFT.forward(test_mode=True): image1/image2 u8 [B,H,W,3] on device -> flow_up f32[B,H,W,2]
  * (flow on image1's grid pointing into image2) and, if non-NULL, flow_low f32[B,H/8,W/8,2].
@@ -777,8 +795,8 @@ int ofx_raft_forward_pairs_warp(ofx_raft* r, const uint8_t* images, int n_images
 /* Which network the checkpoint given to ofx_raft_create holds: 0 = basic (raft-things.pth: BasicEncoder, SepConvGRU, convex
  * upsample), 1 = small (raft-small.pth: SmallEncoder, radius-3 lookup, ConvGRU, upflow8; RAFT/core/raft.py:29-33, :48-51).
  * ofx_raft_create picks it from the key set (update_block.gru.convz + fnet.layer1.0.conv3 = small); a dict with keys of both or a
- * partial one is OFX_EKEY.  The small network takes every entry point and flag above except the split-bf16 modes (OFX_RAFT_BF16X3,
- * _BF16X6, _VOL_BF16X3, _VOL_BF16X6: OFX_EINVAL) -- it runs in exact fp32 only; OFX_RAFT_BN_BATCH has no meaning for it (no
+ * partial one is OFX_EKEY.  The small network takes every entry point and flag above except the split-bf16 modes and fp16
+ * (OFX_RAFT_BF16X3, _BF16X6, _VOL_BF16X3, _VOL_BF16X6, _F16: OFX_EINVAL) -- it runs in exact fp32 only; OFX_RAFT_BN_BATCH has no meaning for it (no
  * BatchNorm) and is ignored; its launches always stay on the caller's stream (OFX_RAFT_SERIAL implied).  Its widest convolution
  * operand is the 256-float GRU row, so one call takes up to (2^31 - 4096) / ((H/8)*(W/8)*1024) pairs. */
 int ofx_raft_variant(const ofx_raft* r);

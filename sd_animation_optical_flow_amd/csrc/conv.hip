@@ -25,8 +25,12 @@
 //   PREC = 5  opt-in "fp16" (OFX_PREC_F16; `UNetModel(precision="fp16")`): both operands rounded fp32 -> fp16 (round-to-nearest-even,
 //             v_cvt_pk_f16_f32) at LDS-commit time, ONE v_mfma_f32_32x32x16_f16 per (i, j) and 16 k, fp32 accumulate: the pattern of
 //             PREC = 1 with one piece instead of two -- the same ROWB rows, row permutation and b128 fragment reads -- at half the
-//             LDS bytes and a third of the MFMAs.  Plain epilogue only; tiles 128x128, 128x64 and 64x64, all three with the halo
-//             patch (16-channel slabs) and the scalar-coordinate schedule; BK 16 or 32 off the patch.  Range and subnormals: ofx.h.
+//             LDS bytes and a third of the MFMAs.  Tiles 128x128, 128x64 and 64x64, all three with the halo patch (16-channel
+//             slabs) and the scalar-coordinate schedule; BK 16 or 32 off the patch.  Epilogues: plain (with the transcendental
+//             activations, the fused instance norm on load -- the normalised, ReLU'd fp32 value is what is rounded to half -- and
+//             the epilogue statistics, taken from the fp32 accumulators) and the two GRU gate epilogues (`RaftEngine(precision="fp16")`;
+//             a descriptor asks for these three with OFX_PREC_F16_EPI, OFX_PREC_F16 itself keeps rejecting them as documented);
+//             no flow epilogue, pooled volume, batched GEMM, split-K or paired pipelines.  Range and subnormals: ofx.h.
 //
 // Tiling (64-wide wavefronts): 256 threads = 4 waves per workgroup, a BMxBN output tile, BK = 16 or
 // 32.  Both operands are staged k-contiguous in LDS with a row stride of BK+4 floats (20 / 36), which
@@ -122,20 +126,25 @@ constexpr int kKAlign = 32;   // packed weights are zero-padded along K to this 
 // (profiles/r23_unet_f16_rate.txt, section 3): 128x128 needs 118-128 VGPRs at BK 16 and 142-150 at BK 32 -- asked for more than
 // three it spills (152-340 bytes of scratch per lane at five); 128x64 and 64x64 fit five to eight waves per SIMD on their own.
 // -DOFX_F16_OCC=n builds another arm for every tile (tools/build_variant.sh); that file says which arms were timed.
-constexpr int f16_occupancy(int BM, int BN) {
+// The GRU gate epilogues fit these budgets as they are (113-120 VGPRs on the 128x128 tile at BK 16, 143-154 at BK 32).  The fused norm
+// on load off the halo patch at BK 32 does not: it holds a (mean, rstd) quad pair per staged row, four rows per thread on the 128-row
+// tiles -- 88-156 bytes of scratch per lane at the budgets above -- so those two arms (`norm32`) run one workgroup per CU lower and
+// carry none (profiles/r36_raft_f16_rate.txt, section 1: the table of every arm).
+constexpr int f16_occupancy(int BM, int BN, bool norm32 = false) {
 #ifdef OFX_F16_OCC
     return OFX_F16_OCC;
 #else
-    return (BM == 128 && BN == 128) ? 3 : 4;
+    return ((BM == 128 && BN == 128) ? 3 : 4) - (norm32 && BM == 128 ? 1 : 0);
 #endif
 }
 
 template <int BM, int BN, int WM, int WN, int EPI, bool NORM, int BK, int PREC, int KS = 1, bool SK = false, int MODE = 0>
-__global__ __launch_bounds__(256 * KS, PREC == OFX_PREC_F16 ? f16_occupancy(BM, BN) : (BK == 16 && KS == 1) ? ((PREC == 3 || PREC == 4) ? 2 : (PREC == 0 && BM <= 128 && BN <= 128 && !NORM && EPI != OFX_EPI_FLOW) ? 4 : 3) : 1) void igemm_kernel(const ConvK p) {
+__global__ __launch_bounds__(256 * KS, PREC == OFX_PREC_F16 ? f16_occupancy(BM, BN, NORM && BK == 32) : (BK == 16 && KS == 1) ? ((PREC == 3 || PREC == 4) ? 2 : (PREC == 0 && BM <= 128 && BN <= 128 && !NORM && EPI != OFX_EPI_FLOW) ? 4 : 3) : 1) void igemm_kernel(const ConvK p) {
     constexpr bool UK = MODE == 1, PATCH = MODE == 2;
     constexpr bool X6 = PREC == 3 || PREC == 4;           // three bf16 pieces per operand, six products
     constexpr bool F16 = PREC == OFX_PREC_F16;            // one fp16 piece per operand, one product
-    static_assert(!F16 || (!NORM && KS == 1 && !SK && (EPI == OFX_EPI_PLAIN || EPI == kEpiPlainT)), "fp16: the plain epilogue only, one pipeline, no split-K");
+    static_assert(!F16 || (KS == 1 && !SK && (EPI == OFX_EPI_PLAIN || EPI == kEpiPlainT || EPI == OFX_EPI_GRU_ZR || EPI == OFX_EPI_GRU_Q)),
+                  "fp16: the plain and the GRU gate epilogues, one pipeline, no split-K");
     // halo patch rows staged per channel slab, rounded up to whole groups of 16: 8x16 patches 12 x 16 / 10 x 18 / 8 x 20 -> 192,
     // 8x8 patches (the 64-row tile) 12 x 8 / 10 x 10 / 8 x 12 -> 112
     // (the 256-row tile: 16x16 patches, 20 x 16 / 18 x 18 / 16 x 20 -> 336)
@@ -1275,9 +1284,12 @@ template <int BM, int BN, int WM, int WN, int BK, int PREC, int KS, bool SK, int
 int launch_tile_uk(const ConvK& k, int epi, bool norm, int nz, hipStream_t s, hipEvent_t ev) {
     dim3 grid((unsigned)(k.mtiles * k.ntiles * (k.ksplit > 1 ? k.ksplit : 1)), (unsigned)nz, 1);
     dim3 block(256 * KS, 1, 1);
-    if constexpr (PREC == OFX_PREC_F16) {   // the plain epilogue only (conv_validate has rejected the rest): nothing else is instantiated
-        if (epi != OFX_EPI_PLAIN || norm) return OFX_EINVAL;
-        if (k.act >= OFX_ACT_SIGMOID) OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, kEpiPlainT, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
+    if constexpr (PREC == OFX_PREC_F16) {   // the plain and the GRU gate epilogues (conv_validate has rejected the rest): nothing else is instantiated
+        if (epi == OFX_EPI_GRU_ZR && !norm) OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_GRU_ZR, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
+        else if (epi == OFX_EPI_GRU_Q && !norm) OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_GRU_Q, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
+        else if (epi != OFX_EPI_PLAIN || (norm && k.act >= OFX_ACT_SIGMOID)) return OFX_EINVAL;
+        else if (k.act >= OFX_ACT_SIGMOID) OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, kEpiPlainT, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
+        else if (norm) OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_PLAIN, true, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
         else OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_PLAIN, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
         return ofx_launch_status();
     } else
@@ -1338,7 +1350,7 @@ const TileInst kTiles[] = {
     OFX_TILE(128, 64, 64, 32, 16, 3, 1, false),  OFX_TILE(64, 64, 32, 32, 16, 3, 1, false),   OFX_TILE(128, 128, 64, 64, 32, 1, 1, false),
     OFX_TILE(128, 64, 64, 32, 16, 2, 1, false),  OFX_TILE(128, 64, 64, 32, 16, 1, 1, false),  OFX_TILE(64, 64, 32, 32, 16, 2, 1, false),
     OFX_TILE(64, 64, 32, 32, 16, 1, 1, false),
-    // fp16 (opt-in, the UNet's precision="fp16"): the same three tiles.  The halo patch walks 16-channel slabs (BK = 16); off it
+    // fp16 (opt-in, the UNet's and the RAFT engine's precision="fp16"): the same three tiles.  The halo patch walks 16-channel slabs (BK = 16); off it
     // (general / scalar-coordinate schedules) the plan takes BK = 32, and BK = 16 is the other arm of that choice, reached by a
     // forced tile (tile = 16e6 + ...) or OFX_CONV_F16_BK=16
     OFX_TILE(128, 128, 64, 64, 16, 5, 1, false), OFX_TILE(128, 64, 64, 32, 16, 5, 1, false),  OFX_TILE(64, 64, 32, 32, 16, 5, 1, false),
@@ -1414,7 +1426,7 @@ int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, C
     const int nz = d->nz > 1 ? d->nz : 1, cin = d->c0 + d->c1;
     const int K = d->KH * d->KW * cin, Kpad = ((K + kKAlign - 1) / kKAlign) * kKAlign;
     const long M = (long)d->B * d->Hout * d->Wout;
-    const bool want_stats = x.stats_rows != nullptr, pool = x.pool.out != nullptr, fp32 = d->precision == OFX_PREC_FP32, f16 = d->precision == OFX_PREC_F16;
+    const bool want_stats = x.stats_rows != nullptr, pool = x.pool.out != nullptr, fp32 = d->precision == OFX_PREC_FP32, f16 = d->precision == OFX_PREC_F16 || d->precision == OFX_PREC_F16_EPI;
     p->name = nz > 1 ? "igemm_corr_volume"
               : d->epi == OFX_EPI_GRU_ZR ? "igemm_conv_gru_zr"
               : d->epi == OFX_EPI_GRU_Q  ? "igemm_conv_gru_q"
@@ -1538,7 +1550,7 @@ int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, C
     } else if (patch && !whole) {
         mtiles = d->B * ((d->Hin + ph - 1) / ph) * ((d->Win + 15) / 16);
     }
-    int prec = d->precision;
+    int prec = f16 ? OFX_PREC_F16 : d->precision;   // (OFX_PREC_F16_EPI is the same arithmetic and the same kernels: it only widens what conv_validate lets through)
     if (!fp32) {
 #ifdef OFX_CONV_LEAN
         return OFX_EINVAL;
@@ -1628,11 +1640,14 @@ int conv_validate(const ofx_conv_desc* d, const ConvExtra& x, long* split_rows) 
     }
     if (d->addend) OFX_REQUIRE(d->ldadd >= d->Cout, OFX_EINVAL);
     const int nz = d->nz > 1 ? d->nz : 1;
-    OFX_REQUIRE(d->precision >= OFX_PREC_FP32 && d->precision <= OFX_PREC_F16, OFX_EINVAL);
-    // OFX_PREC_F16 serves the plain epilogue of one convolution: no gate / flow epilogue, fused norm, epilogue statistics, pooled
-    // volume, batched GEMM, split-K workspace or paired pipelines (none of those kernels is instantiated in this arithmetic)
-    if (d->precision == OFX_PREC_F16)
-        OFX_REQUIRE(d->epi == OFX_EPI_PLAIN && !d->nmean && !x.stats_rows && !x.pool.out && nz == 1 && !d->splitk_ws && d->tile < 2000000000, OFX_EINVAL);
+    OFX_REQUIRE((d->precision >= OFX_PREC_FP32 && d->precision <= OFX_PREC_F16) || d->precision == OFX_PREC_F16_EPI, OFX_EINVAL);
+    // The fp16 arithmetic serves one convolution: no flow epilogue, pooled volume, batched GEMM, split-K workspace or paired
+    // pipelines (none of those kernels is instantiated in it).  Under OFX_PREC_F16 itself the gate epilogues, the fused norm on load
+    // and the epilogue statistics stay rejected as well, as that value has always documented (callers written against it keep what
+    // they were promised); OFX_PREC_F16_EPI is the same arithmetic with those three let through (the flow network's descriptors)
+    if (d->precision == OFX_PREC_F16 || d->precision == OFX_PREC_F16_EPI)
+        OFX_REQUIRE(d->epi != OFX_EPI_FLOW && !x.pool.out && nz == 1 && !d->splitk_ws && d->tile < 2000000000, OFX_EINVAL);
+    if (d->precision == OFX_PREC_F16) OFX_REQUIRE(d->epi == OFX_EPI_PLAIN && !d->nmean && !x.stats_rows, OFX_EINVAL);
     // OFX_PREC_BF16X6_W: the kernel finds the lo pieces of the pre-split matrix at w + Cout * Kpad * 4 -- true only for the WHOLE matrix
     // `ofx_split_conv_weight3` converted (Cout = its row count) of ONE problem; a batched GEMM advances w per problem
     if (d->precision == OFX_PREC_BF16X6_W) OFX_REQUIRE(nz == 1, OFX_EINVAL);

@@ -412,11 +412,12 @@ struct ConvDone {
 struct Launcher {
     hipStream_t s;
     int st = 0;              // sticky: the first error; every later call is skipped
-    int precision;           // OFX_PREC_BF16X3 / _BF16X6 when the forward was asked for a split-bf16 mode
+    int precision;           // OFX_PREC_BF16X3 / _BF16X6 / _F16 when the forward was asked for a split-bf16 mode / for fp16
     void* sk_ws;             // split-K scratch of the stream this launcher feeds (null: never split)
     size_t sk_bytes;
-    explicit Launcher(hipStream_t s, int precision = OFX_PREC_FP32, void* sk_ws = nullptr)
-        : s(s), precision(precision), sk_ws(sk_ws), sk_bytes(sk_ws ? SK_BYTES : 0) {}
+    // (fp16 has no split-K kernels and rejects a workspace: its launchers get none, and small grids run unsplit)
+    explicit Launcher(hipStream_t s, int precision = OFX_PREC_FP32, void* sk_ws_ = nullptr)
+        : s(s), precision(precision), sk_ws(precision == OFX_PREC_F16 ? nullptr : sk_ws_), sk_bytes(sk_ws ? SK_BYTES : 0) {}
     // generic conv launch; all pointer plumbing in one place
     ConvDone conv(const ConvW& c, const ConvArgs& a) {
         ConvDone done;
@@ -444,7 +445,8 @@ struct Launcher {
         d.Wout = (a.Win + 2 * padW - c.kw) / a.stride + 1;
         d.Cout = cout; d.KH = c.kh; d.KW = c.kw; d.stride = a.stride; d.padH = padH; d.padW = padW;
         d.act = a.act; d.epi = a.epi;
-        d.precision = wsplit3 ? OFX_PREC_BF16X6_W : wsplit ? OFX_PREC_BF16X3_W : precision;
+        // (fp16: the value that lets the gate epilogues, the norm on load and the epilogue statistics through)
+        d.precision = wsplit3 ? OFX_PREC_BF16X6_W : wsplit ? OFX_PREC_BF16X3_W : precision == OFX_PREC_F16 ? OFX_PREC_F16_EPI : precision;
         d.splitk_ws = sk_ws; d.splitk_ws_bytes = sk_bytes;
         d.wino_w = whole ? c.wino : nullptr;
         d.wino4_w = whole ? c.wino4 : nullptr;
@@ -553,7 +555,8 @@ int parse_call(Call* call, bool pairs, int unsupported) {
     c.N = (long)c.h * c.w;
     c.M = (long)c.B * c.N;
     c.bgr = (c.flags & OFX_RAFT_BGR) ? 1 : 0;
-    c.prec = (c.flags & OFX_RAFT_BF16X6) ? OFX_PREC_BF16X6 : (c.flags & OFX_RAFT_BF16X3) ? OFX_PREC_BF16X3 : OFX_PREC_FP32;
+    OFX_REQUIRE(!(c.flags & OFX_RAFT_F16) || !(c.flags & (OFX_RAFT_BF16X3 | OFX_RAFT_BF16X6)), OFX_EINVAL);   // one arithmetic for the convolutions
+    c.prec = (c.flags & OFX_RAFT_F16) ? OFX_PREC_F16 : (c.flags & OFX_RAFT_BF16X6) ? OFX_PREC_BF16X6 : (c.flags & OFX_RAFT_BF16X3) ? OFX_PREC_BF16X3 : OFX_PREC_FP32;
     c.sh1 = c.flags & OFX_RAFT_SHARED_IMG1;
     c.sh2 = c.flags & OFX_RAFT_SHARED_IMG2;
     c.alt = c.flags & OFX_RAFT_ALT_CORR;
@@ -690,6 +693,7 @@ int correlate(const Call& c, const CorrWs& ws, const PairMap& pm, int D, int pre
         return st;
     }
     bool fused = false;
+    if (prec == OFX_PREC_F16) prec = OFX_PREC_FP32;   // fp16 rounds the convolutions' operands only: the volume stays exact fp32 (raft.py:102-103, .float())
     if (planes) {
         char* pl = (char*)plane_scratch;
         const long ib = (long)ofx_corr_planes_bytes(h, w, planes);
@@ -1322,7 +1326,7 @@ int small_recurrence(ofx_raft* r, const SmallWs& ws, const Call& c, const PairMa
 }
 
 // the split-bf16 modes have no small-network form: its convolutions and its D = 128 volume run in exact fp32 only
-constexpr int S_UNSUPPORTED = OFX_RAFT_BF16X3 | OFX_RAFT_BF16X6 | OFX_RAFT_VOL_BF16X3 | OFX_RAFT_VOL_BF16X6;
+constexpr int S_UNSUPPORTED = OFX_RAFT_BF16X3 | OFX_RAFT_BF16X6 | OFX_RAFT_VOL_BF16X3 | OFX_RAFT_VOL_BF16X6 | OFX_RAFT_F16;
 
 }  // namespace
 
@@ -1570,7 +1574,7 @@ size_t ofx_raft_workspace_bytes(const ofx_raft* r, int B, int H, int W) {
 }
 
 size_t ofx_raft_workspace_bytes_mode(const ofx_raft* r, int n_images, int B, int H, int W, int flags) {
-    if (n_images < 0 || B <= 0 || H <= 0 || W <= 0 || (H % 8) || (W % 8) || flags < 0 || flags >= 2 * OFX_RAFT_FLOW_INIT) return 0;
+    if (n_images < 0 || B <= 0 || H <= 0 || W <= 0 || (H % 8) || (W % 8) || flags < 0 || flags >= 2 * OFX_RAFT_F16) return 0;
     if (n_images > 0 && (flags & (OFX_RAFT_SHARED_IMG1 | OFX_RAFT_SHARED_IMG2))) return 0;
     const int layout = flags & (OFX_RAFT_ALT_CORR | OFX_RAFT_SHARED_IMG1 | OFX_RAFT_SHARED_IMG2);
     if (r && r->variant == 1) return small_workspace_bytes_mode(B, H, W, layout, n_images);

@@ -59,8 +59,12 @@ class RAFT_2:
     tests/golden/raft_ref_trainbn_128x160.npz (the reference module left in train mode) -- DESIGN.md section 2."""
 
     def __init__(self, model="../RAFT/models/raft-things.pth", device="cuda", iters: int = 20, alternate_corr: bool = False,
-                 cnet_norm: str = "batch", warm_start: bool = False):
-        """warm_start=True (extension: RAFT's warm start for video, RAFT.forward(flow_init=...) with utils.forward_interpolate): every
+                 cnet_norm: str = "batch", warm_start: bool = False, mixed_precision: bool = False):
+        """mixed_precision=True (the reference's own `args.mixed_precision`, RAFT/core/raft.py:99,110,127; `RAFT_2` hard-codes False,
+        ofgen_keyframe_inpaint.py:57): the engine's precision="fp16" -- the convolutions' operands rounded to half, everything else
+        fp32 (`RaftEngine`).  The basic network only: with a small-network checkpoint it is a ValueError.
+
+        warm_start=True (extension: RAFT's warm start for video, RAFT.forward(flow_init=...) with utils.forward_interpolate): every
         `calc` after the first starts its refinement from `forward_interpolate` of the previous call's 1/8-resolution flow -- what
         makes the reference's consecutive-frame chain `of_calc(last_frame, frame)` warm.  A call starts cold when the padded frame
         size changed or the carried field is not finite; `reset()` drops the state.  Default: every call cold, as the reference."""
@@ -68,7 +72,8 @@ class RAFT_2:
         self.iters = iters
         self.alternate_corr = alternate_corr
         self.warm_start = warm_start
-        self.model = RaftEngine(load_checkpoint(model), self.device, cnet_norm=cnet_norm)
+        self.mixed_precision = bool(mixed_precision)
+        self.model = RaftEngine(load_checkpoint(model), self.device, cnet_norm=cnet_norm, precision="fp16" if self.mixed_precision else "fp32")
         self._low: Optional[torch.Tensor] = None      # the previous call's flow_low [1,h,w,2] (warm_start)
 
     def reset(self) -> None:
@@ -104,9 +109,10 @@ def forward_interpolate(flow) -> torch.Tensor:
     return out.permute(2, 0, 1).contiguous().cpu()
 
 
-def create_of_algo(ckpt="../DenseMatching/pre_trained_models/PDCNet_plus_m.pth.tar", corr: str = "volume"):
-    """ofgen_keyframe_inpaint.py:73-77.  corr (extension): 'local' / 'auto' = volume-free correlation (`RaftEngine`'s `corr`)."""
-    return _pd.create_of_algo(ckpt, corr=corr)
+def create_of_algo(ckpt="../DenseMatching/pre_trained_models/PDCNet_plus_m.pth.tar", corr: str = "volume", precision: str = "fp32"):
+    """ofgen_keyframe_inpaint.py:73-77.  corr (extension): 'local' / 'auto' = volume-free correlation (`RaftEngine`'s `corr`).
+    precision (extension): one of `raft.PRECISIONS`, passed through; 'fp32' (default) is the reference's arithmetic."""
+    return _pd.create_of_algo(ckpt, precision=precision, corr=corr)
 
 
 def warp_frame(frame, flow, mode: Optional[str] = None, device="cuda") -> np.ndarray:

@@ -343,8 +343,9 @@ def split_conv_weight3(w_packed: torch.Tensor) -> torch.Tensor:
 
 # conv2d_nhwc(precision=) -> OFX_PREC_*.  *_w: the weight comes from split_conv_weight / split_conv_weight3.  "fp16": both operands
 # rounded to half as they are staged, fp32 accumulate (OFX_PREC_F16; plain fp32 [Cout, Kpad] weights, fp32 activations and epilogue;
-# no nmean / stats_part / splitk_ws)
-CONV_PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16x3_w": 2, "bf16x6": 3, "bf16x6_w": 4, "fp16": 5}
+# no nmean / stats_part / splitk_ws).  "fp16_epi": the same arithmetic with nmean and stats_part served (OFX_PREC_F16_EPI, the flow
+# network's encoder layers under `RaftEngine(precision="fp16")`)
+CONV_PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16x3_w": 2, "bf16x6": 3, "bf16x6_w": 4, "fp16": 5, "fp16_epi": 5 | 256}
 
 
 def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout: int, *, stride: int = 1,

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .raft import RaftEngine
+from .raft import PRECISIONS, RaftEngine
 from .weights import load_checkpoint
 
 DEFAULT_WARP_MODE = "cv2_cubic"      # the reference warps with cv2.remap(INTER_CUBIC), pdcnet_of.py:41
@@ -39,6 +39,8 @@ class PDCNetPlus:
 
     def __init__(self, ckpt_path="pre_trained_models/PDCNet_plus_m.pth.tar", device=None, iters: int = 20,
                  confidence_sigma: float = 3.0, precision: str = "fp32", volume_precision: Optional[str] = None, corr: str = "volume"):
+        if precision not in PRECISIONS:                # before the checkpoint is read: 'fp32', 'bf16x3', 'bf16x6' or 'fp16' (`RaftEngine`)
+            raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
         self.state_dict = load_checkpoint(ckpt_path)
         self.corr = corr                               # extension: 'local' / 'auto' = volume-free correlation (RaftEngine's `corr`)
         self.precision = precision
@@ -183,7 +185,9 @@ def _unpad(t: torch.Tensor, H: int, W: int) -> torch.Tensor:
 
 def create_of_algo(ckpt, precision: str = "fp32", volume_precision: Optional[str] = None, corr: str = "volume") -> PDCNetPlus:
     """pdcnet_of.py:77-79.  `precision` / `volume_precision` / `corr` are extensions (default: the reference's fp32 arithmetic everywhere,
-    on the all-pairs volume; corr='local' / 'auto': the volume-free correlation, see `RaftEngine`)."""
+    on the all-pairs volume; corr='local' / 'auto': the volume-free correlation, see `RaftEngine`).  precision: one of
+    `raft.PRECISIONS` -- 'fp32', 'bf16x3', 'bf16x6' or 'fp16' (RAFT's mixed precision: the convolutions' operands rounded to half,
+    flow EPE ~1e-2 px instead of ~5e-6; see `RaftEngine`); anything else is a ValueError before the checkpoint is read."""
     return PDCNetPlus(ckpt, precision=precision, volume_precision=volume_precision, corr=corr)
 
 

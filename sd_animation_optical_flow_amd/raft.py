@@ -20,9 +20,10 @@ from .weights import raft_variant
 
 FLAG_BGR, FLAG_SHARED_IMG2, FLAG_SHARED_IMG1, FLAG_ALT_CORR, FLAG_BF16X3, FLAG_SERIAL, FLAG_BF16X6, FLAG_BN_BATCH, FLAG_SEPARATE_STATS = 1, 2, 4, 8, 16, 32, 64, 128, 256
 CNET_NORMS = {"eval": 0, "batch": FLAG_BN_BATCH}
-PRECISIONS = {"fp32": 0, "bf16x3": FLAG_BF16X3, "bf16x6": FLAG_BF16X6}
 FLAG_VOL_BF16X3, FLAG_VOL_BF16X6 = 512, 1024
 FLAG_FLOW_INIT = 2048
+FLAG_F16 = 4096
+PRECISIONS = {"fp32": 0, "bf16x3": FLAG_BF16X3, "bf16x6": FLAG_BF16X6, "fp16": FLAG_F16}
 VOLUME_PRECISIONS = {None: 0, "fp32": 0, "bf16x3": FLAG_VOL_BF16X3, "bf16x6": FLAG_VOL_BF16X6}
 # floats of the widest row a convolution of one executor call addresses, per network (see pairs_per_call)
 ROW_FLOATS = {"basic": 768, "small": 256}
@@ -45,6 +46,16 @@ class RaftEngine:
         mode: operands split into two bf16 values, three bf16 MFMAs per product, fp32 accumulate; flow EPE
         ~1e-4 px against the fp32 path) or 'bf16x6' (opt-in: three bf16 pieces = the fp32 value exactly, six
         products, fp32 accumulate: fp32-level accuracy on the bf16 matrix cores).
+        'fp16' (opt-in; the reference's `args.mixed_precision`, RAFT/core/raft.py:99,110,127): every convolution of the two encoders
+        and the update block on the fp16 matrix cores, one product per operand pair, fp32 accumulate.  What is rounded to half: the
+        two OPERANDS of the convolutions only (activations and weights, as they are staged; after a fused instance norm, the
+        normalised value).  What is not: the activations in memory (every stored tensor, the hidden state and the GRU gate algebra
+        included, stays fp32), the correlation volume and its lookup (exact fp32, as in the reference, which casts the feature maps
+        back with .float(); `volume_precision` stays independent), the flow head's last layer, coords1 + delta and the convex
+        upsample.  That is a SUBSET of autocast's roundings (autocast also stores every convolution's output, the norms and the gate
+        products in half).  Flow EPE against float64 ~1e-2 px after 20 iterations, at the level of the reference under autocast: the
+        1e-3 px bar of the default path does not apply to this mode.  Its convolutions get no split-K workspace, so grids that do not
+        fill the chip run unsplit: a single pair may be slower than in fp32.
         volume_precision: None / 'fp32' (default), 'bf16x3' or 'bf16x6' -- the arithmetic of the all-pairs correlation volume ALONE
         (RAFT/core/corr.py:52-60), every convolution stays exact fp32: the GEMM runs on the bf16 matrix cores from operands pre-split
         into bf16 planes (csrc/corr_split.hip; needs H % 64 == 0 and W % 128 == 0, other shapes silently take the fp32 GEMM).
