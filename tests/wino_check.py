@@ -20,11 +20,52 @@ TINY = 1e-30
 #   fp32, every tile / schedule / split-K      2.85  (inside the 5.83 above: K_DIRECT as it stands)
 #   bf16x3 / bf16x3_w                          1.94  against the float64 sum of the three products of the CPU-split operands
 #   bf16x6 / bf16x6_w                          2.31  against the float64 convolution of the exact operands
-# What the split-bf16 constants cover is the fp32 accumulation on the bf16 matrix cores (and, bf16x6, the three dropped products
-# below 2^-23); the operand arithmetic is in the reference.  K_DIRECT_BF16X6 <= 3 K_DIRECT whatever is measured (fp32-accurate).
+# The split-bf16 kernels' plain epilogue over the cases of tests/bf16_check.py (test_gpu_conv_bf16.py), measured on MI355X; the
+# pre-split weight formats gave the ratios of the on-the-fly split at every case (bit-identical wherever the two reach one plan):
+#   case                        plan (bf16x3)                         bf16x3 / _w    bf16x6 / _w
+#   patch-3x3-128x64            128x64 BK 16 patch                    2.02           3.05
+#   patch-1x5-128x128-x2        128x128 BK 16 patch                   2.46           4.85
+#   patch-5x1-128x128-x2        128x128 BK 16 patch                   2.52           3.33
+#   patch-1x5-seam-128x128-x2   128x128 BK 16 patch                   2.28           3.06
+#   patch-over-128x64           128x64 BK 16 patch                    1.87           2.26
+#   patch-over-128x128          128x128 BK 16 patch                   2.07           2.80
+#   gather-64x64                64x64 BK 16 gather                    1.88           2.60
+#   gather-128x64               128x64 BK 16 gather                   1.75           2.46
+#   gather-128x128              128x128 BK 16 gather                  1.86           2.41
+#   gather-auto                 128x128 BK 16 gather                  2.04           2.80
+#   gather-auto-ws              128x128 BK 16 gather                  2.09           3.03
+#   small-grid-auto-ws          64x64 BK 16 gather                    2.02           2.08
+#   bk32-k324                   128x128 BK 32 gather (others BK 16)   3.24           2.96
+#   bk32-3x3-c48                128x128 BK 32 gather (others BK 16)   2.29           2.70
+#   stride2-3x3-96              128x128 BK 16 gather                  1.82           2.53
+#   stride2-1x1                 64x64 BK 16 gather                    1.54           1.93
+#   stem-7x7-s2                 64x64 BK 16 gather                    2.26           2.66
+#   convf1-7x7                  64x64 BK 16 gather                    2.67           3.06
+#   cout2                       128x128 BK 16 patch                   1.21           1.66
+#   out-slice-126               64x64 BK 16 gather                    2.69           3.69
+#   out-slice-126-patch         128x128 BK 16 patch                   2.07           3.67
+#   epi-scale-shift-res-relu    128x64 BK 16 patch                    1.92           2.36
+#   epi-addend-shift            64x64 BK 16 gather                    1.87           2.36
+#   epi-tanh-patch              128x128 BK 16 patch                   0.72           1.27
+#   epi-sigmoid-gather          64x64 BK 16 gather                    0.24           0.79
+#   epi-tanh-gather-128x64      128x64 BK 16 gather                   0.25           0.77
+#   norm-gather-relu            64x64 BK 16 gather                    1.50           2.21
+#   norm-patch                  128x64 BK 16 patch                    1.83           2.99
+#   exact-patch                 128x64 BK 16 patch                    1.13           3.59
+#   exact-gather                64x64 BK 16 gather                    1.12           1.77
+#   spread-patch                128x128 BK 16 patch                   0.11           0.00
+#   spread-gather               128x64 BK 16 gather                   0.22           0.00
+#   maximum                                                           3.24           4.85   (4.85: one element of 65536; every other case <= 3.69)
+# bf16x3: 3.24 is inside K_DIRECT_BF16X3 = 3.8, which stays as it stands (and keeps the 2x rule: 3.8 <= 2 x 3.24).  bf16x6: 4.85 is above
+# the 4.6 the gate cases gave, so the constant moves, to 1.5 x 4.85 and not to the full 2 x: a bf16x6 launch that loses one of its
+# 2^-16 / 2^-18 products everywhere stands at 9.9 ... 13 at K = 576 ... 864 (bf16_check.py, mm_dropped / lh_dropped), and a constant
+# of 9.7 would leave that no margin.
+# What the split-bf16 constants cover is the fp32 accumulation on the bf16 matrix cores; the operand arithmetic is in the reference
+# (bf16x6, gate cases: with the three dropped products below 2^-23; bf16_check.py carries them as a derived term of its own).
+# K_DIRECT_BF16X6 <= 3 K_DIRECT whatever is measured (fp32-accurate).
 K_DIRECT = 11.0
 K_DIRECT_BF16X3 = 3.8
-K_DIRECT_BF16X6 = 4.6
+K_DIRECT_BF16X6 = 7.3    # measured maximum 4.85
 K_F23 = 6.0
 K_F45 = 42.0
 K_F45_GRU = 32.0
