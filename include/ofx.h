@@ -485,7 +485,9 @@ typedef struct ofx_conv_desc {
     int act, epi;
     int tile;                                    /* 0 = auto; else [2000000000 +] BK*1000000 + BM*1000 + BN, e.g. 16128128;
                                                     tiles 128x{32,64,128,192}, 64x64; BK 16 or 32; the 2e9 marker selects the
-                                                    paired-pipeline variant of the 64x64 / BK 32 tile (small grids) */
+                                                    paired-pipeline variant of the 64x64 / BK 32 tile (small grids).  fp32: a BK
+                                                    or a marker the BM x BN tile does not exist with is OFX_EINVAL (BK may be
+                                                    left out: BM*1000 + BN takes the tile's own) */
     int precision;                               /* OFX_PREC_FP32 (default, exact fp32 MFMA) or one of the opt-in OFX_PREC_* above */
     void* splitk_ws;                             /* optional device scratch (256-byte aligned) for split-K on small grids: */
     size_t splitk_ws_bytes;                      /* partial tiles + per-tile arrival counters.  The first 64 KiB hold the

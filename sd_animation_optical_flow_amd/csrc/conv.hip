@@ -1603,6 +1603,9 @@ int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, C
             if (d->tile >= 2000000000 || (d->tile < 1000000 && blocks <= kn.pair_max && Kpad >= 8 * 32)) ks = 2;
         }
     }
+    // fp32: a forced tile names a row of kTiles.  A chunk length its BM x BN does not exist with (128x96 at BK 32, 128x32 at BK 16)
+    // or the paired-pipeline marker on anything but the 64x64 / BK 32 tile is an error, not a quiet launch of another row
+    if (fp32 && d->tile && ((tile_bk && tile_bk != lbk) || (d->tile >= 2000000000 && ks != 2))) return OFX_EINVAL;
     // fp16 takes the scalar-coordinate schedule by the chunk length of ITS tile (the 1x1 GEMMs of the transformers, the strided layers)
     const bool uk16 = f16 && !kn.no_uk && cin % lbk == 0 && (d->c1 == 0 || d->c0 % lbk == 0);
     const bool sk = p->ksplit > 1;
