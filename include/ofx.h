@@ -19,7 +19,7 @@
  *   ofx_generate_mask, ofx_dilate_u8, ofx_expand_mask, ofx_travel_distance, ofx_flow_magnitude, ofx_merge_images,
  *   ofx_mix_frames, ofx_conf_sum
  *   ofx_groupnorm, ofx_softmax_rows, ofx_attention_f32, ofx_attention_prec
- *   ofx_upconv2x, ofx_upsample2x_nearest_f32, ofx_decode_to_u8
+ *   ofx_upconv2x, ofx_upconv2x_prec, ofx_upsample2x_nearest_f32, ofx_decode_to_u8
  *                               ldm/modules/diffusionmodules/model.py:35-41,152-203 ; ldm/modules/attention.py:314,426
  *   ofx_layernorm, ofx_geglu, ofx_attention_bnhd_f32, ofx_attention_bnhd_prec
  *                               ldm/modules/attention.py:54-56,326-436,456-469,515-537 (SpatialTransformer)
@@ -282,6 +282,21 @@ int ofx_attention_bnhd_prec(const float* q, int ldq, const float* k, int ldk, co
 long ofx_upconv2x_weight(const float* w_oihw, int Cout, int Cin, float* out);
 int ofx_upconv2x(const float* x, const float* w, const float* bias, float* out, int ldo, int B, int H, int W, int Cin, int Cout,
                  void* stream);
+/* ofx_upconv2x with the arithmetic of the contraction chosen by `precision` (an OFX_PREC_* value, defined below with the convolutions'
+ * modes: 0 and 5 here).  The argument checks of ofx_upconv2x apply unchanged.
+ *   OFX_PREC_FP32 (0)  ofx_upconv2x itself, bit for bit (called through).
+ *   OFX_PREC_F16 (5)   opt-in (`VaeDecoder(precision="fp16")`): the arithmetic of OFX_PREC_F16 in ofx_conv2d on the same four parity
+ *       GEMMs and the same 128 x BN tiles.  x and the folded w stay fp32 in memory; each element is rounded to fp16 once, to nearest
+ *       even (v_cvt_pk_f16_f32), as it is staged, 32 channels of a tap per chunk; one v_mfma_f32_32x32x16_f16 per 16 k with fp32
+ *       accumulation; the bias add and the stored result are fp32.  It is the FOLDED weight that is rounded (w1 + w2 summed in
+ *       float64, rounded to fp32 by ofx_upconv2x_weight, then to fp16 here), so the result differs from the unfused fp16 pair by
+ *       those roundings.  Magnitudes beyond 65504 become infinities, as under torch.autocast; subnormals are not flushed.
+ *   any other value    OFX_EINVAL before any launch.
+ * ofx_upconv2x_bn (host, no device): the column-tile width BN in {64, 128} of the 128 x BN tile both entry points launch for this
+ * Cout and precision (OFX_EINVAL for Cout <= 0 or another precision). */
+int ofx_upconv2x_prec(const float* x, const float* w, const float* bias, float* out, int ldo, int B, int H, int W, int Cin, int Cout,
+                      int precision, void* stream);
+int ofx_upconv2x_bn(int Cout, int precision);
 /* F.interpolate(x, scale_factor=2.0, mode="nearest") of an NHWC fp32 tensor: [B,H,W,C] -> [B,2H,2W,C] (the materialising half of the
  * unfused pair; the VAE decoder takes it with OFX_VAE_NO_UPCONV=1).  C % 4 == 0, 16-byte aligned; B*2H*2W < 2^31. */
 int ofx_upsample2x_nearest_f32(const float* in, float* out, int B, int H, int W, int C, void* stream);

@@ -129,6 +129,8 @@ SIGNATURES = {
     "ofx_attention_bnhd_prec": (_i, [_p, _i, _p, _i, _p, _i, _p, _l, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
     "ofx_upconv2x_weight": (_l, [_p, _i, _i, _p]),
     "ofx_upconv2x": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "ofx_upconv2x_prec": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "ofx_upconv2x_bn": (_i, [_i, _i]),
     "ofx_upsample2x_nearest_f32": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "ofx_decode_to_u8": (_i, [_p, _i, _p, _i, _i, _i, _p]),
     "ofx_groupnorm_cat_scratch_bytes": (_z, [_i, _i]),

@@ -7,6 +7,8 @@
 //                             (ofx_upconv2x_weight).  Four implicit GEMMs (one per parity, blockIdx.y) of M = B*H*W low-resolution
 //                             pixels, N = Cout, K = 4 * Cin on v_mfma_f32_32x32x2_f32; each scatters its rows to its parity of the
 //                             [B,2H,2W] map.  4 taps per output instead of 9, and the 4x larger map is written once, never read.
+//   ofx_upconv2x_prec         the same with the arithmetic chosen: OFX_PREC_FP32 calls through; OFX_PREC_F16 rounds both operands to
+//                             fp16 as they are staged and contracts them on v_mfma_f32_32x32x16_f16 (fp32 accumulate, bias and store)
 //   ofx_upsample2x_nearest_f32  the materialising upsample (the unfused pair's first half)
 //   ofx_decode_to_u8          f32 RGB in [-1,1] -> u8 BGR, the bits of the reference's numpy expression
 //
@@ -24,6 +26,8 @@ namespace {
 
 constexpr int kBK = 16;            // K chunk
 constexpr int kLDK = kBK + 4;      // LDS row stride in floats
+constexpr int kBKh = 32;           // K chunk of the fp16 form (the convolution family's rule off the halo patch)
+constexpr int kRowBh = kBKh * 2 + 16;   // its LDS row in bytes: 32 halves + 16 bytes of padding (conv.hip, ROWB)
 
 struct UpK {
     const float* x;
@@ -33,14 +37,24 @@ struct UpK {
     int B, H, W, Cin, Cout, ldo;
     int M;                         // B * H * W
     int ntiles;
-    int cchunks;                   // ceil(Cin / 16)
+    int cchunks;                   // ceil(Cin / 16); fp16: ceil(Cin / 32)
 };
 
-template <int BN>
+// PREC = OFX_PREC_F16: the arithmetic of conv.hip's fp16 kernels on the same problem.  Both operands stay fp32 in memory and are
+// rounded fp32 -> fp16 (nearest even, v_cvt_pk_f16_f32) as they are committed to LDS; 32 channels of a tap per chunk, rows of 80
+// bytes written 8 bytes per float4 slot; a fragment is one ds_read_b128 (lane l: row l & 31, the eight consecutive k of group
+// l >> 5 -- the same on both operands), ONE v_mfma_f32_32x32x16_f16 per (i, j) and 16 k, fp32 accumulate.  Loads, guards, pipeline
+// and epilogue are the fp32 form's.
+template <int BN, int PREC = OFX_PREC_FP32>
 __global__ __launch_bounds__(256) void upconv2x_kernel(const UpK p) {
+    constexpr bool F16 = PREC == OFX_PREC_F16;
+    static_assert(F16 || PREC == OFX_PREC_FP32, "fp32 or fp16");
     constexpr int BM = 128, WM = 64, WN = BN / 2, TM = WM / 32, TN = WN / 32;
-    constexpr int B_PER = BN / 64;                    // 64 rows of 4 float4 slots per pass of the 256 threads
-    constexpr int STAGE = (BM + BN) * kLDK;
+    constexpr int BK = F16 ? kBKh : kBK;
+    constexpr int QPR = BK / 4;                       // float4 slots per staged row
+    constexpr int RPG = 256 / QPR;                    // rows per pass of the 256 threads: 64, fp16 32
+    constexpr int A_PER = BM / RPG, B_PER = BN / RPG;
+    constexpr int STAGE = F16 ? (BM + BN) * (kRowBh / 4) : (BM + BN) * kLDK;   // floats
     __shared__ __attribute__((aligned(16))) float smem[2 * STAGE];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -49,16 +63,17 @@ __global__ __launch_bounds__(256) void upconv2x_kernel(const UpK p) {
     const int par = blockIdx.y, py = par >> 1, px = par & 1;
     const int m0 = mt * BM, n0 = nt * BN;
 
-    // staging role: float4 slot kq of rows r0 and r0 + 64; rows permuted inside groups of 16 so that one ds_write_b128 pass
-    // (16 lanes) covers 16 distinct 16-byte bank groups (conv.hip, r0)
-    const int kq = tid & 3, j0 = tid >> 2;
-    const int r0 = (j0 & 3) * 4 + ((j0 >> 2) & 3) + (j0 >> 4) * 16;
+    // staging role: float4 slot kq of rows r0 + RPG i; rows permuted inside groups of 16 so that one ds_write_b128 pass
+    // (16 lanes) covers 16 distinct 16-byte bank groups (conv.hip, r0).  fp16: 8-byte writes, 32 lanes per pass, the rows of one
+    // pass every 4th row (80-byte rows then start 32 bytes apart modulo 256)
+    const int kq = tid % QPR, j0 = tid / QPR;
+    const int r0 = F16 ? 16 * (j0 >> 4) + 4 * (j0 & 3) + ((j0 >> 2) & 3) : (j0 & 3) * 4 + ((j0 >> 2) & 3) + (j0 >> 4) * 16;
     const int HW = p.H * p.W;
-    int a_b[2], a_y[2], a_x[2];
-    bool a_ok[2];
+    int a_b[A_PER], a_y[A_PER], a_x[A_PER];
+    bool a_ok[A_PER];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int m = m0 + r0 + 64 * i;
+    for (int i = 0; i < A_PER; ++i) {
+        const int m = m0 + r0 + RPG * i;
         a_ok[i] = m < p.M;
         const int mm = a_ok[i] ? m : 0;
         a_b[i] = mm / HW;
@@ -69,15 +84,15 @@ __global__ __launch_bounds__(256) void upconv2x_kernel(const UpK p) {
     const size_t wrow = (size_t)4 * p.Cin;            // floats per output channel of one parity
     const float* wpar = p.w + (size_t)par * p.Cout * wrow;
 
-    f32x4 ra[2], rb[B_PER];        // native vectors: a select between two of them stays in registers
+    f32x4 ra[A_PER], rb[B_PER];    // native vectors: a select between two of them stays in registers
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     // branch-free: a lane whose float4 does not exist reads the first 16 bytes of the operand instead and keeps zeros
     auto load = [&](int t, int cb) __attribute__((always_inline)) {
         const int ty = t >> 1, tx = t & 1;
-        const int c = cb * kBK + kq * 4;
+        const int c = cb * BK + kq * 4;
         const bool cok = c < p.Cin;                   // Cin % 4 == 0: a float4 is inside or outside as a whole
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < A_PER; ++i) {
             const int iy = a_y[i] - 1 + py + ty, ix = a_x[i] - 1 + px + tx;
             const bool ok = cok && a_ok[i] && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
             const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? p.x + (((size_t)a_b[i] * p.H + iy) * p.W + ix) * p.Cin + c : p.x);
@@ -85,17 +100,28 @@ __global__ __launch_bounds__(256) void upconv2x_kernel(const UpK p) {
         }
 #pragma unroll
         for (int i = 0; i < B_PER; ++i) {
-            const int n = n0 + r0 + 64 * i;
+            const int n = n0 + r0 + RPG * i;
             const bool ok = cok && n < p.Cout;
             const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? wpar + (size_t)n * wrow + (size_t)t * p.Cin + c : p.w);
             rb[i] = ok ? v : zero4;
         }
     };
     auto commit = [&](float* st) __attribute__((always_inline)) {
+        if constexpr (F16) {
+            // fp32 -> fp16, round-to-nearest-even; beyond +-65504 the result is an infinity (conv.hip, cvt_store)
+            typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+            char* a0 = reinterpret_cast<char*>(st);
+            char* b0 = a0 + BM * kRowBh;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) *reinterpret_cast<f32x4*>(st + (r0 + 64 * i) * kLDK + kq * 4) = ra[i];
+            for (int i = 0; i < A_PER; ++i) *reinterpret_cast<f16x4*>(a0 + (r0 + RPG * i) * kRowBh + kq * 8) = __builtin_convertvector(ra[i], f16x4);
 #pragma unroll
-        for (int i = 0; i < B_PER; ++i) *reinterpret_cast<f32x4*>(st + (BM + r0 + 64 * i) * kLDK + kq * 4) = rb[i];
+            for (int i = 0; i < B_PER; ++i) *reinterpret_cast<f16x4*>(b0 + (r0 + RPG * i) * kRowBh + kq * 8) = __builtin_convertvector(rb[i], f16x4);
+        } else {
+#pragma unroll
+            for (int i = 0; i < A_PER; ++i) *reinterpret_cast<f32x4*>(st + (r0 + RPG * i) * kLDK + kq * 4) = ra[i];
+#pragma unroll
+            for (int i = 0; i < B_PER; ++i) *reinterpret_cast<f32x4*>(st + (BM + r0 + RPG * i) * kLDK + kq * 4) = rb[i];
+        }
     };
 
     f32x16 acc[TM][TN];
@@ -122,24 +148,43 @@ __global__ __launch_bounds__(256) void upconv2x_kernel(const UpK p) {
             load(t_next, cb_next);
             advance();
         }
-        const float* As = smem + (kt & 1) * STAGE;
-        const float* Bs = As + BM * kLDK;
+        if constexpr (F16) {
+            typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+            const char* a0 = reinterpret_cast<const char*>(smem + (kt & 1) * STAGE);
+            const char* b0 = a0 + BM * kRowBh;
 #pragma unroll
-        for (int ks = 0; ks < kBK / 8; ++ks) {
-            f32x4 a[TM], b[TN];
+            for (int ks = 0; ks < BK / 16; ++ks) {
+                f16x8 a[TM], b[TN];
+                const int ko = ks * 32 + (lane >> 5) * 16;                    // bytes: halves 16 ks + 8 (lane >> 5) .. + 7
 #pragma unroll
-            for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const f32x4*>(As + (wm * WM + i * 32 + frow) * kLDK + ks * 8 + fk);
+                for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const f16x8*>(a0 + (wm * WM + i * 32 + frow) * kRowBh + ko);
 #pragma unroll
-            for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const f32x4*>(Bs + (wn * WN + j * 32 + frow) * kLDK + ks * 8 + fk);
+                for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const f16x8*>(b0 + (wn * WN + j * 32 + frow) * kRowBh + ko);
 #pragma unroll
-            for (int i = 0; i < TM; ++i)
+                for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].x, b[j].x, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, b[j].y, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].z, b[j].z, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, b[j].w, acc[i][j], 0, 0, 0);
-                }
+                    for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i][j], 0, 0, 0);
+            }
+        } else {
+            const float* As = smem + (kt & 1) * STAGE;
+            const float* Bs = As + BM * kLDK;
+#pragma unroll
+            for (int ks = 0; ks < kBK / 8; ++ks) {
+                f32x4 a[TM], b[TN];
+#pragma unroll
+                for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const f32x4*>(As + (wm * WM + i * 32 + frow) * kLDK + ks * 8 + fk);
+#pragma unroll
+                for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const f32x4*>(Bs + (wn * WN + j * 32 + frow) * kLDK + ks * 8 + fk);
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].x, b[j].x, acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, b[j].y, acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].z, b[j].z, acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, b[j].w, acc[i][j], 0, 0, 0);
+                    }
+            }
         }
         if (more) commit(smem + ((kt + 1) & 1) * STAGE);
         __syncthreads();
@@ -250,8 +295,14 @@ extern "C" long ofx_upconv2x_weight(const float* w, int Cout, int Cin, float* ou
     return n;
 }
 
-extern "C" int ofx_upconv2x(const float* x, const float* w, const float* bias, float* out, int ldo, int B, int H, int W, int Cin,
-                            int Cout, void* stream) {
+extern "C" int ofx_upconv2x_bn(int Cout, int precision) {
+    if (Cout <= 0 || (precision != OFX_PREC_FP32 && precision != OFX_PREC_F16)) return OFX_EINVAL;
+    return Cout <= 64 ? 64 : 128;
+}
+
+// the checks and the launch of both entry points; precision is OFX_PREC_FP32 or OFX_PREC_F16 here
+static int upconv2x_checked(const float* x, const float* w, const float* bias, float* out, int ldo, int B, int H, int W, int Cin,
+                            int Cout, int precision, void* stream) {
     OFX_REQUIRE(x && w && out, OFX_EINVAL);
     OFX_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && ldo >= Cout, OFX_EINVAL);
     OFX_REQUIRE(Cin % 4 == 0 && ofx_aligned16(x) && ofx_aligned16(w), OFX_EALIGN);
@@ -263,18 +314,37 @@ extern "C" int ofx_upconv2x(const float* x, const float* w, const float* bias, f
     k.x = x; k.w = w; k.bias = bias; k.out = out;
     k.B = B; k.H = H; k.W = W; k.Cin = Cin; k.Cout = Cout; k.ldo = ldo;
     k.M = (int)M;
-    k.cchunks = (Cin + kBK - 1) / kBK;
-    const int bn = Cout <= 64 ? 64 : 128;
+    const bool f16 = precision == OFX_PREC_F16;
+    const int bk = f16 ? kBKh : kBK;
+    k.cchunks = (Cin + bk - 1) / bk;
+    const int bn = ofx_upconv2x_bn(Cout, precision);
     k.ntiles = (Cout + bn - 1) / bn;
     const long mtiles = (M + 127) / 128;
     OFX_REQUIRE(mtiles * k.ntiles < (1L << 31), OFX_EINVAL);
     hipStream_t s = (hipStream_t)stream;
-    OfxProfScope prof("upconv2x", s);
+    OfxProfScope prof(f16 ? "upconv2x_f16" : "upconv2x", s);
     prof.flops(2.0 * 4.0 * (double)M * Cout * 4.0 * Cin);
     dim3 grid((unsigned)(mtiles * k.ntiles), 4, 1), block(256, 1, 1);
-    if (bn == 64) hipLaunchKernelGGL(upconv2x_kernel<64>, grid, block, 0, s, k);
-    else hipLaunchKernelGGL(upconv2x_kernel<128>, grid, block, 0, s, k);
+    if (f16) {
+        if (bn == 64) hipLaunchKernelGGL((upconv2x_kernel<64, OFX_PREC_F16>), grid, block, 0, s, k);
+        else hipLaunchKernelGGL((upconv2x_kernel<128, OFX_PREC_F16>), grid, block, 0, s, k);
+    } else {
+        if (bn == 64) hipLaunchKernelGGL(upconv2x_kernel<64>, grid, block, 0, s, k);
+        else hipLaunchKernelGGL(upconv2x_kernel<128>, grid, block, 0, s, k);
+    }
     return ofx_launch_status();
+}
+
+extern "C" int ofx_upconv2x(const float* x, const float* w, const float* bias, float* out, int ldo, int B, int H, int W, int Cin,
+                            int Cout, void* stream) {
+    return upconv2x_checked(x, w, bias, out, ldo, B, H, W, Cin, Cout, OFX_PREC_FP32, stream);
+}
+
+extern "C" int ofx_upconv2x_prec(const float* x, const float* w, const float* bias, float* out, int ldo, int B, int H, int W, int Cin,
+                                 int Cout, int precision, void* stream) {
+    OFX_REQUIRE(precision == OFX_PREC_FP32 || precision == OFX_PREC_F16, OFX_EINVAL);
+    if (precision == OFX_PREC_FP32) return ofx_upconv2x(x, w, bias, out, ldo, B, H, W, Cin, Cout, stream);
+    return upconv2x_checked(x, w, bias, out, ldo, B, H, W, Cin, Cout, precision, stream);
 }
 
 extern "C" int ofx_upsample2x_nearest_f32(const float* in, float* out, int B, int H, int W, int C, void* stream) {

@@ -829,11 +829,33 @@ def upconv2x_weight(w_oihw: torch.Tensor) -> torch.Tensor:
     return _wino_weight("ofx_upconv2x_weight", w, co, ci).reshape(4, co, 4, ci)
 
 
+# upconv2x(precision=) -> OFX_PREC_* of ofx_upconv2x_prec.  "fp16": x and the folded weights rounded to half (nearest even) as the
+# kernel stages them, the contraction on the fp16 matrix cores with fp32 accumulation, bias and result fp32 (include/ofx.h).
+UPCONV_PRECISIONS = {"fp32": 0, "fp16": 5}
+
+
+def check_upconv_precision(precision, name: str = "precision") -> str:
+    if not isinstance(precision, str) or precision not in UPCONV_PRECISIONS:
+        raise ValueError(f"{name} must be one of {tuple(UPCONV_PRECISIONS)}, got {precision!r}")
+    return precision
+
+
+def upconv2x_bn(cout: int, precision: str = "fp32") -> int:
+    """The column-tile width (64 or 128) of the 128 x BN tile `upconv2x` launches for `cout` output channels (ofx_upconv2x_bn; no
+    device needed)."""
+    bn = _lib.lib().ofx_upconv2x_bn(int(cout), UPCONV_PRECISIONS[check_upconv_precision(precision)])
+    if bn < 0:
+        raise _lib.OfxError(bn, "ofx_upconv2x_bn")
+    return bn
+
+
 def upconv2x(x: torch.Tensor, w_folded: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-             out_off: int = 0) -> torch.Tensor:
+             out_off: int = 0, precision: str = "fp32") -> torch.Tensor:
     """conv3x3(pad 1)(nearest 2x upsample of x) + bias in one kernel that never forms the upsampled map: x [B,H,W,Cin],
     w_folded [4,Cout,4,Cin] from `upconv2x_weight` (on the device) -> [B,2H,2W,Cout].  `out` [B,2H,2W,C >= out_off + Cout]: write
-    channels [out_off, out_off + Cout) of it (a strided row)."""
+    channels [out_off, out_off + Cout) of it (a strided row).  precision: "fp32" (default, `ofx_upconv2x`) or "fp16"
+    (`ofx_upconv2x_prec`: both operands rounded to half as they are staged, fp32 accumulation); anything else is a ValueError."""
+    check_upconv_precision(precision)                              # before a device is touched
     x = _chk(x, "x", torch.float32)
     w = _chk(w_folded, "w_folded", torch.float32)
     if x.dim() != 4 or w.dim() != 4 or w.shape[0] != 4 or w.shape[2] != 4 or w.shape[3] != x.shape[3]:
@@ -848,8 +870,12 @@ def upconv2x(x: torch.Tensor, w_folded: torch.Tensor, bias: Optional[torch.Tenso
     out = _chk(out, "out", torch.float32)
     if tuple(out.shape[:3]) != (B, 2 * H, 2 * W) or out_off < 0 or out.shape[3] < out_off + co:
         raise RuntimeError(f"out must be [{B},{2 * H},{2 * W},>= {out_off + co}], got {tuple(out.shape)}")
-    check(_lib.lib().ofx_upconv2x(_ptr(x), _ptr(w), _ptr(b), C.c_void_p(out.data_ptr() + 4 * out_off), out.shape[3], B, H, W, ci, co,
-                                  _stream()), "ofx_upconv2x")
+    po = C.c_void_p(out.data_ptr() + 4 * out_off)
+    if precision == "fp32":
+        check(_lib.lib().ofx_upconv2x(_ptr(x), _ptr(w), _ptr(b), po, out.shape[3], B, H, W, ci, co, _stream()), "ofx_upconv2x")
+    else:
+        check(_lib.lib().ofx_upconv2x_prec(_ptr(x), _ptr(w), _ptr(b), po, out.shape[3], B, H, W, ci, co, UPCONV_PRECISIONS[precision],
+                                           _stream()), "ofx_upconv2x_prec")
     return out
 
 

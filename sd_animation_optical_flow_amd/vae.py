@@ -20,6 +20,17 @@ The way back is `VaeDecoder`: `decode_first_stage` (ldm/models/diffusion/ddpm.py
 per output instead of 9 (OFX_VAE_NO_UPCONV=1 in the environment, read once per process: `ofx_upsample2x_nearest_f32` +
 `ofx_conv2d` instead), and `ofx_decode_to_u8` makes the bytes.  Pinned the same way (tests/golden/make_golden_vae_decoder.py).
 
+`precision=` ("fp32", the default and bit for bit what the classes did without the argument, or "fp16") on both classes is the
+arithmetic of every contraction but the attention's: the reference runs its whole diffusion stage, first stage included, under
+`torch.autocast` (ofgen_keyframe_inpaint.py:212,273, ofgen.py:104).  "fp16" gives every `_conv` the fp16 matrix-core arithmetic of
+`ops.conv2d_nhwc(precision="fp16")` and the decoder's `Upsample` that of `ops.upconv2x(precision="fp16")` (the unfused pair:
+`upsample2x_nearest` + the same `_conv`): both operands rounded fp32 -> fp16, to nearest even, as the kernel stages them, fp32
+accumulation, fp32 bias, addend and result.  GroupNorm, SiLU, the mid-block attention (one head of d = 512, not a fused head size)
+and its softmax, the weights and every activation in memory, `sample` and `decode_to_u8` stay fp32 in both modes.  Range: the layers
+that read the un-normalised residual stream (`nin_shortcut`, `Upsample`, `Downsample`) round it to half like every other operand, so
+a value beyond +-65504 there becomes an infinity, as in the reference's autocast run.  Anything else is a ValueError, raised before
+the checkpoint is looked at or a device asked for.
+
 Checkpoint loading, weight packing and the convolution call are `modelbase`'s, shared with the other SD-stage models.  Both classes
 check in the order the others do: configuration, then checkpoint, then device.  A checkpoint with a missing key or a wrong shape is
 a KeyError / ValueError on a machine without a device too (it used to be the RuntimeError about the device there); the decoder's
@@ -114,6 +125,15 @@ def random_vae_decoder_state_dict(seed: int = 0, cfg: dict = SD_V1_CONFIG) -> Di
     return random_tensors(decoder_tensors(cfg), int(seed) + 104729)
 
 
+VAE_PRECISIONS = ("fp32", "fp16")      # `precision=` of VaeEncoder / VaeDecoder
+
+
+def check_precision(precision) -> str:
+    if not isinstance(precision, str) or precision not in VAE_PRECISIONS:
+        raise ValueError(f"precision must be one of {VAE_PRECISIONS}, got {precision!r}")
+    return precision
+
+
 def _no_upconv() -> bool:
     """OFX_VAE_NO_UPCONV=1 (diagnostic, read once per process): the decoder's Upsample layers run unfused."""
     return env_flag("OFX_VAE_NO_UPCONV")
@@ -123,9 +143,9 @@ class _VaeBlocks(DeviceModel):
     """What `Encoder` and `Decoder` share (model.py): weights on the device in the kernels' layouts (`modelbase.DeviceModel`), and
     the GroupNorm, ResnetBlock and AttnBlock calls."""
 
-    def __init__(self, state_dict: Dict[str, torch.Tensor], tensors, device, cfg: dict, scale_factor: float):
+    def __init__(self, state_dict: Dict[str, torch.Tensor], tensors, device, cfg: dict, scale_factor: float, precision: str):
         self.cfg, self.scale_factor = dict(cfg), float(scale_factor)
-        self.precision = "fp32"                                    # the arithmetic of every `_conv`
+        self.precision = check_precision(precision)                # the arithmetic of every `_conv`; before the checkpoint or a device
         strip = len("first_stage_model.")                          # the prefix of full SD checkpoints, where a key has it
         sd = {k[strip:] if k.startswith("first_stage_model.") else k: v for k, v in state_dict.items()}
         t32 = load_tensors(sd, tensors, "", "VAE")                 # the checkpoint is checked before the device is asked for
@@ -158,8 +178,9 @@ class _VaeBlocks(DeviceModel):
 class VaeEncoder(_VaeBlocks):
     """`AutoencoderKL.encode` + `get_first_stage_encoding` on a HIP device."""
 
-    def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", cfg: dict = SD_V1_CONFIG, scale_factor: float = SCALE_FACTOR):
-        super().__init__(state_dict, encoder_tensors(cfg), device, cfg, scale_factor)
+    def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", cfg: dict = SD_V1_CONFIG, scale_factor: float = SCALE_FACTOR,
+                 precision: str = "fp32"):
+        super().__init__(state_dict, encoder_tensors(cfg), device, cfg, scale_factor, precision)
 
     def max_batch(self, H: int, W: int) -> int:
         """Images one pass of the encoder can take at this size: the convolution kernel addresses its operands with 32-bit byte
@@ -215,8 +236,9 @@ class VaeEncoder(_VaeBlocks):
 class VaeDecoder(_VaeBlocks):
     """`AutoencoderKL.decode` / `decode_first_stage` / `decode_latent` on a HIP device."""
 
-    def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", cfg: dict = SD_V1_CONFIG, scale_factor: float = SCALE_FACTOR):
-        super().__init__(state_dict, decoder_tensors(cfg), device, cfg, scale_factor)
+    def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", cfg: dict = SD_V1_CONFIG, scale_factor: float = SCALE_FACTOR,
+                 precision: str = "fp32"):
+        super().__init__(state_dict, decoder_tensors(cfg), device, cfg, scale_factor, precision)
         # Upsample layers that run fused (level -> bool); OFX_VAE_NO_UPCONV=1 turns every one to the unfused pair
         self.fused_upsample = {lvl: not _no_upconv() for lvl in range(1, len(self.cfg["ch_mult"]))}
 
@@ -234,8 +256,8 @@ class VaeDecoder(_VaeBlocks):
         """Upsample.forward (:52-58): interpolate(scale_factor=2.0, mode="nearest") + 3x3 convolution."""
         name = f"decoder.up.{lvl}.upsample.conv"
         if self.fused_upsample[lvl]:
-            return ops.upconv2x(x, self.w[f"{name}.weight.folded"], self.w[f"{name}.bias"])
-        return self._conv(name, ops.upsample2x_nearest(x), 3)
+            return ops.upconv2x(x, self.w[f"{name}.weight.folded"], self.w[f"{name}.bias"], precision=self.precision)
+        return self._conv(name, ops.upsample2x_nearest(x), 3)                  # the unfused pair, the convolution in `self.precision`
 
     def max_batch(self, H: int, W: int) -> int:
         """Frames of HxW pixels one pass of the decoder can take: the convolution kernel addresses its operands with 32-bit byte

@@ -12,7 +12,12 @@ each line gives the mean over rounds with the fastest and slowest round behind i
   decoder   milliseconds per frame of `VaeDecoder.decode`, every Upsample fused against every Upsample unfused (what
             OFX_VAE_NO_UPCONV=1 selects), and of `decode_latent` (the byte exit included).
 
-    python tools/vae_decode_rate.py [--out profiles/r16_vae_decode_rate.txt] [--only layers|decoder]
+  --precision fp32,fp16   the precision arms instead: per Upsample layer `ops.upconv2x(precision=)` and the unfused pair in every arm,
+            then `VaeDecoder.decode` (fused and unfused), `decode_latent` and `VaeEncoder.encode_moments` on the same frame with one
+            object per arm.  Every arm of a section alternates inside every round; the first arm is the yardstick (the fp32 path
+            of the same build in the same session).
+
+    python tools/vae_decode_rate.py [--out profiles/r16_vae_decode_rate.txt] [--only layers|decoder] [--precision fp32,fp16]
 """
 import argparse
 import json
@@ -114,25 +119,99 @@ def decoder_case(reps, rounds, lines):
     lines.append(f"    unfused / fused = {r['unfused'][0] / r['fused'][0]:.3f}     max |fused - unfused| over the image = {diff:.2e}")
 
 
+def precision_layer_case(lvl, c, H, W, precs, reps, rounds, lines):
+    """One Upsample layer in every precision of `precs`, fused and unfused, all arms alternating inside every round."""
+    g = torch.Generator(device="cuda").manual_seed(lvl)
+    x = torch.randn((1, H, W, c), generator=g, device="cuda")
+    w = torch.randn((c, c, 3, 3), generator=torch.Generator().manual_seed(lvl)) / (9 * c) ** 0.5
+    b = torch.randn((c,), generator=g, device="cuda") * 0.1
+    wf, wp = ops.upconv2x_weight(w).cuda(), ops.pack_conv_weight(w).cuda()
+    fns = {}
+    for p in precs:
+        fns[f"fused {p}"] = lambda p=p: ops.upconv2x(x, wf, b, precision=p)
+        fns[f"unfused {p}"] = lambda p=p: ops.conv2d_nhwc(ops.upsample2x_nearest(x), wp, 3, 3, c, shift=b, precision=p)
+    r = alternate(fns, reps, rounds)
+    nominal = 2.0 * 4 * H * W * c * 9 * c
+    lines.append(f"up.{lvl}.upsample  {c} -> {c}, {H}x{W} -> {2 * H}x{2 * W}   (nominal {nominal / 1e9:.1f} GFLOP, fused executes 4/9; "
+                 f"BN {ops.upconv2x_bn(c)})")
+    for p in precs:
+        lines.append(f"    ofx_upconv2x {p:4s}                        {fmt(r[f'fused {p}'])}   {nominal * 4 / 9 / r[f'fused {p}'][0] / 1e9:7.1f} executed TFLOP/s")
+        lines.append(f"    ofx_upsample2x_nearest + ofx_conv2d {p:4s} {fmt(r[f'unfused {p}'])}")
+    base = precs[0]
+    for p in precs[1:]:
+        lines.append(f"    fused {base} / fused {p} = {r[f'fused {base}'][0] / r[f'fused {p}'][0]:.3f}     unfused {p} / fused {p} = "
+                     f"{r[f'unfused {p}'][0] / r[f'fused {p}'][0]:.3f}     max |fused {p} - fused {base}| = "
+                     f"{float((fns[f'fused {p}']() - fns[f'fused {base}']()).abs().max()):.2e}")
+
+
+def precision_model_case(precs, reps, rounds, lines):
+    """`VaeDecoder.decode` / `decode_latent` and `VaeEncoder.encode_moments` on one 512x768 frame, one object per precision."""
+    from sd_animation_optical_flow_amd.vae import VaeEncoder, random_vae_state_dict
+    dsd, esd = random_vae_decoder_state_dict(0), random_vae_state_dict(0)
+    z = torch.randn((1, 4, 96, 64), generator=torch.Generator().manual_seed(1)).cuda()
+    image = (torch.rand((1, 3, 768, 512), generator=torch.Generator().manual_seed(2)) * 2 - 1).cuda()
+    decs = {p: VaeDecoder(dsd, precision=p) for p in precs}
+    encs = {p: VaeEncoder(esd, precision=p) for p in precs}
+
+    def unfused(dec):
+        def f():
+            keep = dec.fused_upsample
+            dec.fused_upsample = {k: False for k in keep}
+            try:
+                return dec.decode(z)
+            finally:
+                dec.fused_upsample = keep
+        return f
+    fns = {}
+    for p in precs:
+        fns[f"decode {p}"] = lambda p=p: decs[p].decode(z)
+        fns[f"decode unfused {p}"] = unfused(decs[p])
+        fns[f"decode_latent {p}"] = lambda p=p: decs[p].decode_latent(z)
+        fns[f"encode_moments {p}"] = lambda p=p: encs[p].encode_moments(image)
+    r = alternate(fns, reps, rounds)
+    lines.append("VaeDecoder / VaeEncoder, one 512x768 frame (latent 96x64), ms per frame")
+    for what in ("decode", "decode unfused", "decode_latent", "encode_moments"):
+        for p in precs:
+            lines.append(f"    {what + ' ' + p:28s} {fmt(r[f'{what} {p}'])}")
+        base = precs[0]
+        for p in precs[1:]:
+            lines.append(f"      {base} / {p} = {r[f'{what} {base}'][0] / r[f'{what} {p}'][0]:.3f}")
+    for p in precs[1:]:
+        lines.append(f"    max |decode {p} - decode {precs[0]}| = {float((decs[p].decode(z) - decs[precs[0]].decode(z)).abs().max()):.2e}     "
+                     f"max |encode_moments {p} - {precs[0]}| = {float((encs[p].encode_moments(image) - encs[precs[0]].encode_moments(image)).abs().max()):.2e}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "r16_vae_decode_rate.txt"))
     ap.add_argument("--only", choices=["layers", "decoder"])
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--precision", help='comma-separated arms, e.g. "fp32,fp16": the first is the yardstick; the Upsample layers, '
+                    "VaeDecoder.decode / decode_latent and VaeEncoder.encode_moments in every arm instead of the fused / unfused report")
     a = ap.parse_args()
+    precs = [ops.check_upconv_precision(p) for p in a.precision.split(",")] if a.precision else None
+    if precs and a.rounds < 3:
+        sys.exit("--precision: at least 3 rounds")
     if not torch.cuda.is_available():
         sys.exit("vae_decode_rate.py needs a GPU: nothing is measured without one")
-    lines = [f"tools/vae_decode_rate.py --reps {a.reps} --rounds {a.rounds}   ({torch.cuda.get_device_name(0)})",
+    lines = [f"tools/vae_decode_rate.py --reps {a.reps} --rounds {a.rounds}{' --precision ' + a.precision if a.precision else ''}   "
+             f"({torch.cuda.get_device_name(0)})",
              "device-event time per call, mean over rounds (fastest .. slowest round); the variants alternate inside every round", ""]
     if a.only in (None, "layers"):
         for (lvl, c, H, W) in LAYERS:
             with Watchdog(120, f"layer up.{lvl}"):
-                layer_case(lvl, c, H, W, a.reps, a.rounds, lines)
+                if precs:
+                    precision_layer_case(lvl, c, H, W, precs, a.reps, a.rounds, lines)
+                else:
+                    layer_case(lvl, c, H, W, a.reps, a.rounds, lines)
             lines.append("")
     if a.only in (None, "decoder"):
         with Watchdog(300, "decoder"):
-            decoder_case(max(2, a.reps // 2), a.rounds, lines)
+            if precs:
+                precision_model_case(precs, max(2, a.reps // 2), a.rounds, lines)
+            else:
+                decoder_case(max(2, a.reps // 2), a.rounds, lines)
     text = "\n".join(lines) + "\n"
     print(text)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
