@@ -497,6 +497,17 @@ typedef struct ofx_conv_desc {
     float* aux_coords; float* aux_flow4;         /* EPI_FLOW only: coords1 [M][2], flow4 [M][4] = (fx, fy, 0, 0) per pixel */
     long a_zs, w_zs, o_zs; int nz;               /* batched-GEMM mode (nz>1): per-z strides in elements */
     int B, Hin, Win, Hout, Wout, Cout, KH, KW, stride, padH, padW;
+                                                 /* Geometry: out[b, oy, ox, n] sums x[b, oy*stride - padH + ky, ox*stride - padW + kx, c]
+                                                    * w[n][(ky*KW + kx)*(c0+c1) + c] over ky < KH, kx < KW, c; a tap outside
+                                                    [0, Hin) x [0, Win) contributes zero (never the next row or image), also under
+                                                    nmean / nrstd.  padH, padW >= 0 (negative: OFX_EINVAL) are the rows above and the
+                                                    columns left of the image; Hout and Wout are the caller's: any positive size, smaller
+                                                    or larger than (Hin + 2 padH - KH) / stride + 1 (outputs beyond it read zeros below
+                                                    and to the right; padH = padW = 0, stride 2, Hout = Hin / 2 is the VAE's Downsample).
+                                                    The direct kernels' general and scalar-coordinate schedules serve every such
+                                                    descriptor; the halo-patch schedule and the Winograd routes take only 'same' stride-1
+                                                    ones (padH = KH / 2, padW = KW / 2, Hout = Hin, Wout = Win): any other is planned
+                                                    on the former, and a tile that forces a Winograd route for it is OFX_EINVAL */
     int act, epi;
     int tile;                                    /* 0 = auto; else [2000000000 +] BK*1000000 + BM*1000 + BN, e.g. 16128128;
                                                     tiles 128x{32,64,128,192}, 64x64; BK 16 or 32; the 2e9 marker selects the

@@ -1637,6 +1637,7 @@ int conv_validate(const ofx_conv_desc* d, const ConvExtra& x, long* split_rows) 
     }
     OFX_REQUIRE(d->B > 0 && d->Hin > 0 && d->Win > 0 && d->Hout > 0 && d->Wout > 0 && d->Cout > 0, OFX_EINVAL);
     OFX_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0, OFX_EINVAL);
+    OFX_REQUIRE(d->padH >= 0 && d->padW >= 0, OFX_EINVAL);       // (ofx.h: padding is rows / columns of zeros, never a crop)
     if (d->nmean) {
         OFX_REQUIRE(d->nrstd && ofx_aligned16(d->nmean) && ofx_aligned16(d->nrstd), OFX_EALIGN);
         OFX_REQUIRE(d->in1 == nullptr && d->epi == OFX_EPI_PLAIN, OFX_EINVAL);   // fused norm: single segment, plain epilogue

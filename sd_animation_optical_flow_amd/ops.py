@@ -367,6 +367,9 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
     (sum, sum of squares) partials of the outputs there when the launch can produce them ([B][rows][cout][2]; see inorm_finalize).
     `precision`: a key of CONV_PRECISIONS (default exact fp32).
     Returns [B,Hout,Wout,cout], or `out`; with `stats_part`, (that, rows per image), rows = 0 when none were produced."""
+    ph, pw = (kh // 2, kw // 2) if pad is None else pad
+    if ph < 0 or pw < 0:            # (ofx_conv2d: OFX_EINVAL) padding is rows / columns of zeros above and left of the image, never a crop
+        raise RuntimeError(f"pad must be >= 0, got {(ph, pw)}")
     x = _chk(x, "x", torch.float32)
     B, H, W, c0 = x.shape
     d = ConvDesc()
@@ -378,7 +381,6 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
     d.w = wp.data_ptr()
     d.scale = 0 if scale is None else _chk(scale, "scale", torch.float32).data_ptr()
     d.shift = 0 if shift is None else _chk(shift, "shift", torch.float32).data_ptr()
-    ph, pw = (kh // 2, kw // 2) if pad is None else pad
     Ho, Wo = ((H + 2 * ph - kh) // stride + 1, (W + 2 * pw - kw) // stride + 1) if out_hw is None else out_hw
     if out is None:
         out = torch.empty((B, Ho, Wo, cout), dtype=torch.float32, device=x.device)

@@ -43,6 +43,9 @@ around 1.  `exact`: operands that are already bf16 values (x3) / have at most 16
 meet the float64 convolution of those operands within the accumulation bound alone.  `spread`: channel pairs scaled by 2^-12 ... 2^12
 (the weight by the inverse), the second channel of a pair nearly equal with the opposite weight: M >> |ref|.
 
+Geometry.  A case may carry `pad` = (padH, padW) and `out_hw` = (Hout, Wout) (wino_check.geometry_of: default 'same' padding and the
+size that follows, which every case of this table has); geom_check.py holds the cases off 'same' padding and registers them here.
+
 Simulated bugs (`simulated_bugs`), each applied on the CPU to the pieces or the products, with the cases it concerns in `bugs_for`.
 `lower` pieces: lo (x3), mid and lo (x6).
     lower_a_dropped_in_the_last_chunk          the products of A's lower pieces missing over the last BK-wide chunk of K
@@ -139,13 +142,28 @@ CASES = [
 IDS = [c["name"] for c in CASES]
 
 
+OTHER = {}                          # cases of another table that uses this module's inputs, oracle and launch (geom_check.py), by name
+
+
+def register(c):
+    """Make a case of another table known to `case` (hence to inputs / reference / buffers).  Its name must be new."""
+    assert c["name"] not in IDS and c["name"] not in OTHER, c["name"]
+    OTHER[c["name"]] = c
+    return c
+
+
 def case(name):
-    return CASES[IDS.index(name)]
+    return OTHER[name] if name in OTHER else CASES[IDS.index(name)]
+
+
+def pad_of(c):
+    """(padH, padW): the case's optional `pad`, default 'same' (k // 2)."""
+    return wc.geometry_of(c)[0]
 
 
 def out_hw(c):
-    ph, pw = c["kh"] // 2, c["kw"] // 2
-    return (c["H"] + 2 * ph - c["kh"]) // c["stride"] + 1, (c["W"] + 2 * pw - c["kw"]) // c["stride"] + 1
+    """(Hout, Wout): the case's optional `out_hw`, default the size that follows from the padding."""
+    return wc.geometry_of(c)[1]
 
 
 def k_of(c):
@@ -215,7 +233,10 @@ def pieces(t, fam):
 
 
 def conv(c, x, w):
-    """x NHWC, w OIHW (any float dtype) -> the case's convolution in float64, NHWC."""
+    """x NHWC, w OIHW (any float dtype) -> the case's convolution in float64, NHWC.  A case with a geometry of its own (`pad` /
+    `out_hw`) goes through wino_check.conv64_geometry."""
+    if "pad" in c or "out_hw" in c:
+        return wc.conv64_geometry(x, w, c["stride"], pad_of(c), out_hw(c))
     out = F.conv2d(x.double().permute(0, 3, 1, 2), w.double(), stride=c["stride"], padding=(c["kh"] // 2, c["kw"] // 2))
     return out.permute(0, 2, 3, 1)
 
@@ -354,7 +375,7 @@ def descriptor(c, prec, ptr):
     if e.get("norm"):
         d.nmean, d.nrstd = ptr("nmean"), ptr("nrstd")
     d.B, d.Hin, d.Win, d.Hout, d.Wout, d.Cout = c["B"], c["H"], c["W"], Ho, Wo, c["cout"]
-    d.KH, d.KW, d.stride, d.padH, d.padW = c["kh"], c["kw"], c["stride"], c["kh"] // 2, c["kw"] // 2
+    d.KH, d.KW, d.stride, (d.padH, d.padW) = c["kh"], c["kw"], c["stride"], pad_of(c)
     d.act, d.epi, d.tile, d.precision = ACTS[e.get("act")], 0, c["tile"], prec
     if e.get("ws"):
         d.splitk_ws, d.splitk_ws_bytes = ptr("ws"), WS_BYTES

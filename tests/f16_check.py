@@ -26,6 +26,11 @@ K * 2^-14 * max |other operand|.
 Range.  65504 is the largest fp16 value: the "max" case holds +-65504 exactly in a few positions of x and w and stays finite.
 Beyond it an operand becomes an infinity (as under torch.autocast); no case goes there.
 
+Geometry.  A case may carry `kh` / `kw` in place of the square `k`, and `pad` = (padH, padW) and `out_hw` = (Hout, Wout)
+(wino_check.geometry_of: default 'same' padding and the size that follows, which every case of this table has); geom_check.py holds
+the cases off 'same' padding.  Its `ring` cases (`exact_zero`, `shift_amp`) have outputs with no tap inside the image: there the
+accumulator is an exact 0, the shift alone is stored, and the assertion on |shift| applies where there is a tap.
+
 Inputs.  Seeded N(0, 1.5^2) activations and fan-in-scaled N(0, 1/K) weights; shift / addend / res N(0, 0.5^2), scale around 1.
 """
 import math
@@ -34,6 +39,7 @@ import torch
 import torch.nn.functional as F
 
 import sd_ops_check as SC
+import wino_check as wc
 
 U, FLOOR = SC.U, SC.FLOOR
 PREC_F16 = 5                               # include/ofx.h
@@ -75,9 +81,19 @@ for _bm, _bn in ((128, 128), (128, 64), (64, 64)):
 IDS = [c["name"] for c in CASES]
 
 
+def filter_of(c):
+    """(KH, KW): the square `k`, or the optional `kh` / `kw`."""
+    return c.get("kh", c.get("k")), c.get("kw", c.get("k"))
+
+
+def pad_of(c):
+    """(padH, padW): the case's optional `pad`, default 'same' (k // 2)."""
+    return wc.geometry_of(c)[0]
+
+
 def out_hw(c):
-    k, s = c["k"], c["stride"]
-    return (c["H"] + 2 * (k // 2) - k) // s + 1, (c["W"] + 2 * (k // 2) - k) // s + 1
+    """(Hout, Wout): the case's optional `out_hw`, default the size that follows from the padding."""
+    return wc.geometry_of(c)[1]
 
 
 def inputs(c):
@@ -85,20 +101,20 @@ def inputs(c):
     shift [cout], addend / res [B,Ho,Wo,cout] the case has (else None)."""
     g = SC._gen("f16-" + c["name"])
     e = c["extra"]
-    B, H, W, c0, c1, co, k = c["B"], c["H"], c["W"], c["c0"], c["c1"], c["cout"], c["k"]
+    B, H, W, c0, c1, co, (kh, kw) = c["B"], c["H"], c["W"], c["c0"], c["c1"], c["cout"], filter_of(c)
     cin = c0 + c1
     mag = e.get("mag", 1.0)
     x = torch.randn((B, H, W, cin), generator=g) * 1.5 * mag
-    w = torch.randn((co, cin, k, k), generator=g) * (mag / math.sqrt(cin * k * k))
+    w = torch.randn((co, cin, kh, kw), generator=g) * (mag / math.sqrt(cin * kh * kw))
     if e.get("extreme"):
         x[0, 0, 0, 0], x[0, 4, 5, 7], x[0, H - 1, W - 1, cin - 1] = 65504.0, -65504.0, 65504.0
-        w[0, 0, 0, 0], w[co - 1, cin - 1, k - 1, k - 1] = 65504.0, -65504.0
+        w[0, 0, 0, 0], w[co - 1, cin - 1, kh - 1, kw - 1] = 65504.0, -65504.0
     Ho, Wo = out_hw(c)
     r = dict(x=x[..., :c0].contiguous(), x2=x[..., c0:].contiguous() if c1 else None, w=w, scale=None, shift=None, addend=None, res=None)
     if e.get("scale"):
         r["scale"] = 1.0 + 0.25 * torch.randn((co,), generator=g)
     if e.get("shift"):
-        r["shift"] = 0.5 * torch.randn((co,), generator=g)
+        r["shift"] = e.get("shift_amp", 0.5) * torch.randn((co,), generator=g)
     if e.get("addend"):
         r["addend"] = 0.5 * torch.randn((B, Ho, Wo, co), generator=g)
     if e.get("res"):
@@ -107,16 +123,20 @@ def inputs(c):
 
 
 def reference(c, t):
-    """-> (ref, bound) float64 [B,Ho,Wo,cout] for the tensors `t` of `inputs(c)` (header)."""
-    k, s = c["k"], c["stride"]
+    """-> (ref, bound) float64 [B,Ho,Wo,cout] for the tensors `t` of `inputs(c)` (header).  A case with a geometry of its own
+    (`pad` / `out_hw`, with `H` and `W`) goes through wino_check.conv64_geometry: taps outside the image are zero."""
+    s = c["stride"]
     x = t["x"] if t["x2"] is None else torch.cat([t["x"], t["x2"]], dim=3)
     xh = x.half().double().permute(0, 3, 1, 2)
     wh = t["w"].half().double()
     assert bool(torch.isfinite(xh).all()) and bool(torch.isfinite(wh).all())
     K = wh[0].numel()
     nhwc = lambda a: a.permute(0, 2, 3, 1)
-    acc = nhwc(F.conv2d(xh, wh, stride=s, padding=k // 2))
-    mag = nhwc(F.conv2d(xh.abs(), wh.abs(), stride=s, padding=k // 2))
+    if "pad" in c or "out_hw" in c:
+        conv = lambda a, b: wc.conv64_geometry(nhwc(a), b, s, pad_of(c), out_hw(c))
+    else:
+        conv = lambda a, b: nhwc(F.conv2d(a, b, stride=s, padding=(wh.shape[2] // 2, wh.shape[3] // 2)))
+    acc, mag = conv(xh, wh), conv(xh.abs(), wh.abs())
     sc = torch.ones(()) .double() if t["scale"] is None else t["scale"].double()
     v = acc * sc
     side = torch.zeros_like(v)
@@ -129,7 +149,13 @@ def reference(c, t):
     if t["res"] is not None:
         v = (v + t["res"].double()).clamp_min(0.0)
         side = side + t["res"].double().abs()
-    assert bool((side <= mag * sc.abs()).all()), f"{c['name']}: outside the range in which the bound covers the epilogue's roundings"
+    covered = side <= mag * sc.abs()
+    if c["extra"].get("exact_zero"):
+        # outputs with no tap inside the image (a geometry's ring, geom_check.py): the accumulator is an exact 0 and 0 + shift rounds
+        # nowhere, so there is no rounding to cover as long as a shift is all there is (the caller holds them to relu(shift) bit for bit)
+        assert bool((mag == 0).any()) and t["scale"] is None and t["addend"] is None and t["res"] is None
+        covered = covered | (mag == 0)
+    assert bool(covered.all()), f"{c['name']}: outside the range in which the bound covers the epilogue's roundings"
     bound = (K + 2) * U * mag * sc.abs() + 2 * U * v.abs() + FLOOR
     return v, bound
 

@@ -25,6 +25,13 @@ Inputs follow f16_check / bf16_check: seeded N(0, 1.5^2) activations, fan-in-sca
 N(0, 0.5^2), scale around 1.  `spread`: channel pairs scaled by 2^-12 ... 2^12 (the weight by the inverse), the second channel of a
 pair nearly equal with the opposite weight: M >> |ref|, so a term lost under cancellation shows.
 
+Geometry.  A case may carry `pad` = (padH, padW) and `out_hw` = (Hout, Wout) (wino_check.geometry_of); the default, which every
+case of this table has, is 'same' padding k // 2 and the output size that follows.  With either key the reference is
+wino_check.conv64_geometry -- zero-pad (after the norm on load: padding stays 0), F.conv2d with no padding, crop -- and `descriptor`
+passes the four integers on.  geom_check.py holds the cases off 'same' padding and registers them here (`register`), so that inputs,
+oracle, guarded buffers and descriptor are this module's; its `ring` cases (`exact_zero`, `shift_amp`) have outputs with no tap inside
+the image, where the accumulator is an exact 0, the shift alone is stored, and the assertion below applies where there is a tap.
+
 Case table.  Every case names the row of kTiles it runs (ROWS) and carries the plan it must reach, (bm, bn, bk, ks, ksplit, mode);
 test_fp32_check_host.py holds every case to it through ofx_conv2d_plan and the table to kTiles / tile_has_patch / tile_has_scalar
 as conv.hip has them.  Maps: gru_check.MAPS (W 1x8x16 whole patches, R 1x9x17 overhanging / ragged, D 2x16x16), G 1x10x14 (with
@@ -220,13 +227,33 @@ IDS = [c["name"] for c in CASES]
 assert len(set(IDS)) == len(IDS)
 
 
+OTHER = {}                          # cases of another table that uses this module's inputs, oracle and launch (geom_check.py), by name
+
+
+def register(c):
+    """Make a case of another table known to `case` (hence to inputs / reference / buffers).  Its name must be new."""
+    assert c["name"] not in IDS and c["name"] not in OTHER, c["name"]
+    OTHER[c["name"]] = c
+    return c
+
+
 def case(name):
-    return CASES[IDS.index(name)]
+    return OTHER[name] if name in OTHER else CASES[IDS.index(name)]
+
+
+def pad_of(c):
+    """(padH, padW): the case's optional `pad`, default 'same' (k // 2)."""
+    return wc.geometry_of(c)[0]
 
 
 def out_hw(c):
-    ph, pw = c["kh"] // 2, c["kw"] // 2
-    return (c["H"] + 2 * ph - c["kh"]) // c["stride"] + 1, (c["W"] + 2 * pw - c["kw"]) // c["stride"] + 1
+    """(Hout, Wout): the case's optional `out_hw`, default the size that follows from the padding."""
+    return wc.geometry_of(c)[1]
+
+
+def pad_amounts(c):
+    """(top, bottom, left, right) zeros around the case's image (wino_check.pad_amounts)."""
+    return wc.pad_amounts(c["H"], c["W"], c["kh"], c["kw"], c["stride"], pad_of(c), out_hw(c))
 
 
 def rows_of(c):
@@ -271,7 +298,7 @@ def inputs(name):
     if e.get("scale"):
         t["scale"] = 1.0 + 0.25 * torch.randn((co,), generator=g)
     if e.get("shift"):
-        t["shift"] = 0.5 * torch.randn((co,), generator=g)
+        t["shift"] = e.get("shift_amp", 0.5) * torch.randn((co,), generator=g)
     if e.get("addend"):
         t["addend"] = 0.5 * torch.randn((B, Ho, Wo, co), generator=g)
     if e.get("res"):
@@ -291,7 +318,10 @@ def norm_on_load(x, mean, rstd, relu=True):
 
 
 def conv(c, x, w, padded=False):
-    """x NHWC, w OIHW (any float dtype) -> the case's convolution in float64, NHWC.  padded: x already carries its padding."""
+    """x NHWC, w OIHW (any float dtype) -> the case's convolution in float64, NHWC.  padded: x already carries its padding
+    (pad_amounts).  A case with a geometry of its own (`pad` / `out_hw`) goes through wino_check.conv64_geometry."""
+    if "pad" in c or "out_hw" in c:
+        return wc.conv64_geometry(x, w, c["stride"], pad_of(c), out_hw(c), padded)
     pad = (0, 0) if padded else (c["kh"] // 2, c["kw"] // 2)
     return F.conv2d(x.double().permute(0, 3, 1, 2), w.double(), stride=c["stride"], padding=pad).permute(0, 2, 3, 1)
 
@@ -333,7 +363,14 @@ def reference(name):
     mag = conv_abs * sc
     derived = NORM_ULP * conv_abs * sc if e.get("norm") else torch.zeros_like(conv_abs)
     side = sum((t[n].double().abs() for n in ("shift", "addend", "res") if t[n] is not None), torch.zeros_like(mag))
-    assert bool((side <= mag).all()), f"{name}: |shift| + |addend| + |res| above the convolution's magnitude"
+    r.no_tap = conv_abs == 0                                             # outputs with no tap inside the image (a geometry's ring)
+    if e.get("exact_zero"):
+        # there the accumulator is an exact 0 and 0 * scale + shift rounds nowhere: the epilogue's roundings need no cover, as long
+        # as nothing else is added (the caller holds such outputs to relu(shift) bit for bit)
+        assert bool(r.no_tap.any()) and t["addend"] is None and t["res"] is None and t["scale"] is None and not e.get("norm"), name
+        assert bool(((side <= mag) | r.no_tap).all()), f"{name}: |shift| above the convolution's magnitude where it has one"
+    else:
+        assert bool((side <= mag).all()), f"{name}: |shift| + |addend| + |res| above the convolution's magnitude"
     r.mag = mag + side
     r.v, r.out = r.epilogue(r.acc)
     act = e.get("act")
@@ -384,11 +421,12 @@ def _guarded(body, ld=None):
     return buf
 
 
-def buffers(c):
+def buffers(c, t=None):
     """{name: CPU float32 [GUARD + rows + GUARD, ld]} of everything the descriptor points at but the workspace: NaN guard rows
-    around every one, NaN in the addend's columns past Cout, `out` all NaN over its full ldo."""
+    around every one, NaN in the addend's columns past Cout, `out` all NaN over its full ldo.  t: the tensors, default the case's
+    `inputs` (a table with inputs of its own passes them in this module's layout)."""
     from sd_animation_optical_flow_amd import ops
-    t = inputs(c["name"])
+    t = inputs(c["name"]) if t is None else t
     b = dict(in0=_guarded(t["x"][..., :c["c0"]]), w=_guarded(ops.pack_conv_weight(t["w"])),
              out=torch.full((rows_of(c) + 2 * GUARD, ldo_of(c)), NAN))
     if c["c1"]:
@@ -429,8 +467,8 @@ def descriptor(c, ptr, ws=0):
     if e.get("norm"):
         d.nmean, d.nrstd = ptr("nmean"), ptr("nrstd")
     d.B, d.Hin, d.Win, d.Hout, d.Wout, d.Cout = c["B"], c["H"], c["W"], Ho, Wo, c["cout"]
-    d.KH, d.KW, d.stride, d.padH, d.padW = c["kh"], c["kw"], c["stride"], c["kh"] // 2, c["kw"] // 2
-    d.act, d.epi, d.tile, d.precision = ACTS[e.get("act")], 0, c["tile"], 0
+    d.KH, d.KW, d.stride, (d.padH, d.padW) = c["kh"], c["kw"], c["stride"], pad_of(c)
+    d.act, d.epi, d.tile, d.precision = ACTS[e.get("act")], 0, c["tile"], c.get("precision", 0)
     if e.get("ws"):
         d.splitk_ws, d.splitk_ws_bytes = ws, WS_BYTES
     return d
@@ -538,8 +576,7 @@ def simulated_bugs(c):
     if "norm_relu_missing" in names:
         accs["norm_relu_missing"] = conv(c, norm_on_load(t["x"], t["nmean"], t["nrstd"], relu=False), w)
     if "padding_normalised" in names:
-        ph, pw = c["kh"] // 2, c["kw"] // 2
-        xpad = F.pad(t["x"], (0, 0, pw, pw, ph, ph))
+        xpad = wc.pad_nhwc(t["x"], pad_amounts(c))                       # ('same': k // 2 all round, but for a stride's unused last row)
         accs["padding_normalised"] = conv(c, norm_on_load(xpad, t["nmean"], t["nrstd"]), w, padded=True)
     out = {k: r.epilogue(v)[1] for k, v in accs.items()}
     if "scale_after_shift" in names:

@@ -117,6 +117,81 @@ TINY = 1e-30
 # maximum 4.51 (p-256x64-patch-over: 3x3 on overhanging 16x16 patches), inside the sweep's 5.83 and K_DIRECT = 11.0, which stays
 # as it stands: no constant of its own for this table, the 7x7 stem (196 taps) included at 2.63.  The transcendental cases are
 # small because ACT_ULP is taken off first; the spread cases because M >> |ref| by construction.
+# The direct kernels off 'same' padding over the cases of tests/geom_check.py (test_gpu_conv_geometry.py: pads, output sizes and strides
+# that padH = KH // 2 never reaches, the VAE encoder's Downsample on every fp32 row of kTiles and every fp16 instantiation), measured on
+# MI355X with the constants above and below as they stand -- a geometry changes which terms enter a sum, not the arithmetic.  fp32,
+# |err| / (slope 2^-24 M) against the float64 convolution of the exact operands (x2: paired pipelines, split n: split-K):
+#   case                       plan                        ratio  | case                       plan                        ratio
+#   g-valid-gather             128x128 BK 16 gather        4.26   | g-down-256x64-gather       256x64 BK 16 gather         3.32
+#   g-valid-scalar             64x64 BK 32 scalar          5.14   | g-down-256x64-scalar       256x64 BK 16 scalar         3.55
+#   g-valid-s2-gather          256x64 BK 16 gather         2.68   | g-down-128x192-gather      128x192 BK 16 gather        2.93
+#   g-valid-s2-scalar          128x128 BK 16 scalar        3.29   | g-down-128x96-gather       128x96 BK 16 gather         3.85
+#   g-valid-s2-R-gather        64x64 BK 32 gather          2.85   | g-down-128x96-scalar       128x96 BK 16 scalar         3.44
+#   g-valid-s2-R-scalar        128x64 BK 16 scalar         2.97   | g-down-128x64-gather       128x64 BK 16 gather         3.26
+#   g-wide-gather              128x192 BK 16 gather        4.55   | g-down-128x64-scalar       128x64 BK 16 scalar         2.55
+#   g-wide-scalar              256x64 BK 16 scalar         5.34   | g-down-128x128k32-gather   128x128 BK 32 gather        3.67
+#   g-ring-gather              128x96 BK 16 gather         3.46   | g-down-128x128k32-scalar   128x128 BK 32 scalar        4.01
+#   g-ring-scalar              128x64 BK 32 scalar         3.70   | g-down-128x64k32-gather    128x64 BK 32 gather         2.32
+#   g-ring-1x1-gather          64x64 BK 16 gather          2.58   | g-down-128x64k32-scalar    128x64 BK 32 scalar         2.97
+#   g-ring-1x1-scalar          128x32 BK 32 scalar         3.77   | g-down-128x32-gather       128x32 BK 32 gather         2.58
+#   g-asym-h-gather            128x64 BK 16 gather         3.75   | g-down-128x32-scalar       128x32 BK 32 scalar         3.43
+#   g-asym-h-scalar            128x96 BK 16 scalar         4.51   | g-down-64x64k16-gather     64x64 BK 16 gather          3.40
+#   g-asym-w-gather            128x128 BK 32 gather        3.94   | g-down-64x64k16-scalar     64x64 BK 16 scalar          3.78
+#   g-asym-w-scalar            64x64 BK 16 scalar          4.07   | g-down-64x64x2-gather      64x64 BK 32 x2 gather       2.79
+#   g-valid-1x5-gather         128x64 BK 32 gather         3.32   | g-down-64x64x2-scalar      64x64 BK 32 x2 scalar       2.24
+#   g-valid-1x5-scalar         128x128 BK 32 scalar        3.57   | g-down-64x64-gather        64x64 BK 32 gather          3.14
+#   g-valid-5x1-gather         128x32 BK 32 gather         3.16   | g-down-64x64-scalar        64x64 BK 32 scalar          4.93
+#   g-valid-5x1-scalar         64x64 BK 32 x2 scalar       2.05   | g-down-64x64sk-gather      64x64 BK 32 split 2 gather  4.19
+#   g-crop-gather              64x64 BK 32 x2 gather       2.50   | g-down-64x64sk-scalar      64x64 BK 32 split 3 scalar  1.81
+#   g-crop-scalar              128x64 BK 16 scalar         3.22   | g-down-norm-gather         128x64 BK 16 gather         2.92
+#   g-over-gather              64x64 BK 16 gather          4.04   | g-down-norm-scalar         64x64 BK 32 scalar          1.54
+#   g-over-scalar              128x128 BK 16 scalar        3.70   | g-down-slice               128x128 BK 16 scalar        3.77
+#   g-down-x2                  128x128 BK 32 scalar        3.41   | g-down-tanh                64x64 BK 16 gather          1.11
+#   g-valid-x2                 128x64 BK 16 scalar         3.24   | g-down-ssrr                128x64 BK 32 scalar         2.42
+#   g-wide-x2                  64x64 BK 32 scalar          4.05   | g-valid-addend-shift       128x96 BK 16 scalar         3.92
+#   g-down-128x128-gather      128x128 BK 16 gather        3.01   | g-model-fp32               64x64 BK 32 x2 scalar       2.03
+#   g-down-128x128-scalar      128x128 BK 16 scalar        4.49   |
+# maximum 5.34 (g-wide-scalar: 3x3, pad (2, 2), out (H + 2, W + 2) on two 256-row tiles), inside the sweep's 5.83 and K_DIRECT = 11.0.
+# fp16 (OFX_PREC_F16; the norm cases OFX_PREC_F16_EPI), |err| / f16_check's derived bound, which is 1 at the bound:
+#   case                               plan                  ratio  | case                               plan                  ratio
+#   g-f16-valid-gather                 64x64 BK 32 gather    0.032  | g-f16-crop-scalar                  64x64 BK 32 scalar    0.002
+#   g-f16-valid-scalar                 64x64 BK 32 scalar    0.003  | g-f16-over-gather                  64x64 BK 32 gather    0.036
+#   g-f16-valid-s2-gather              64x64 BK 32 gather    0.030  | g-f16-over-scalar                  64x64 BK 32 scalar    0.002
+#   g-f16-valid-s2-scalar              64x64 BK 32 scalar    0.002  | g-f16-down-128x128-bk16-gather     128x128 BK 16 gather  0.031
+#   g-f16-wide-gather                  64x64 BK 32 gather    0.038  | g-f16-down-128x128-bk16-scalar     128x128 BK 16 scalar  0.002
+#   g-f16-wide-scalar                  64x64 BK 32 scalar    0.002  | g-f16-down-128x128-bk32-gather     128x128 BK 32 gather  0.027
+#   g-f16-ring-gather                  64x64 BK 32 gather    0.046  | g-f16-down-128x128-bk32-scalar     128x128 BK 32 scalar  0.002
+#   g-f16-ring-scalar                  64x64 BK 32 scalar    0.002  | g-f16-down-128x64-bk16-gather      128x64 BK 16 gather   0.032
+#   g-f16-ring-1x1-gather              64x64 BK 32 gather    0.261  | g-f16-down-128x64-bk16-scalar      128x64 BK 16 scalar   0.003
+#   g-f16-ring-1x1-scalar              64x64 BK 32 scalar    0.020  | g-f16-down-128x64-bk32-gather      128x64 BK 32 gather   0.028
+#   g-f16-asym-h-gather                64x64 BK 32 gather    0.035  | g-f16-down-128x64-bk32-scalar      128x64 BK 32 scalar   0.004
+#   g-f16-asym-h-scalar                64x64 BK 32 scalar    0.002  | g-f16-down-64x64-bk16-gather       64x64 BK 16 gather    0.039
+#   g-f16-asym-w-gather                64x64 BK 32 gather    0.043  | g-f16-down-64x64-bk16-scalar       64x64 BK 16 scalar    0.004
+#   g-f16-asym-w-scalar                64x64 BK 32 scalar    0.002  | g-f16-down-64x64-bk32-gather       64x64 BK 32 gather    0.041
+#   g-f16-valid-1x5-gather             64x64 BK 32 gather    0.059  | g-f16-down-64x64-bk32-scalar       64x64 BK 32 scalar    0.004
+#   g-f16-valid-1x5-scalar             64x64 BK 32 scalar    0.006  | g-f16-down-norm-gather             128x64 BK 32 gather   0.014
+#   g-f16-valid-5x1-gather             64x64 BK 32 gather    0.065  | g-f16-down-norm-scalar             64x64 BK 16 scalar    0.006
+#   g-f16-valid-5x1-scalar             64x64 BK 32 scalar    0.005  | g-f16-down-small                   64x64 BK 32 scalar    0.004
+#   g-f16-crop-gather                  64x64 BK 32 gather    0.033  | g-f16-model-fp16                   64x64 BK 32 scalar    0.002
+# maximum 0.261 (g-f16-ring-1x1-gather: K = 4, where the bound is smallest).  Split bf16, |err| / (2^-24 M); the pre-split weight formats gave the
+# ratios of the on-the-fly split at every case (bit-identical wherever the two reach one plan):
+#   case                    plan (bf16x3)                         bf16x3 / _w    bf16x6 / _w
+#   g-bf16-down-64x64       64x64 BK 16 gather                    1.86           2.01
+#   g-bf16-down-128x64      128x64 BK 16 gather                   1.61           2.62
+#   g-bf16-down-128x128     128x128 BK 16 gather                  1.86           2.23
+#   g-bf16-down-bk32        128x128 BK 32 gather (others BK 16)   2.72           3.04
+#   g-bf16-valid-64x64      64x64 BK 16 gather                    2.59           2.52
+#   g-bf16-valid-128x64     128x64 BK 16 gather                   2.07           2.37
+#   g-bf16-valid-128x128    128x128 BK 16 gather                  1.74           2.56
+#   g-bf16-valid-bk32       128x128 BK 32 gather (others BK 16)   2.46           2.73
+#   g-bf16-wide-64x64       64x64 BK 16 gather                    3.00           2.84
+#   g-bf16-wide-128x64      128x64 BK 16 gather                   1.92           2.66
+#   g-bf16-wide-128x128     128x128 BK 16 gather                  2.22           2.67
+#   g-bf16-wide-bk32        128x128 BK 32 gather (others BK 16)   2.17           2.50
+#   g-bf16-down-norm        64x64 BK 16 gather                    1.05           2.92
+#   maximum                                                       3.00           3.04   (inside K_DIRECT_BF16X3 = 3.8 and K_DIRECT_BF16X6 = 7.3)
+# Every output with no tap inside the image (the frame of `ring` / `ring-1x1`, the rows and columns of `over` beyond the natural
+# output) came out as the epilogue of an exact zero, bit for bit, in all three arithmetics.  No kernel defect found.
 K_DIRECT = 11.0
 K_DIRECT_BF16X3 = 3.8
 K_DIRECT_BF16X6 = 7.3    # measured maximum 4.85
@@ -135,6 +210,39 @@ def pad_of(kh, kw):
 def conv64(x, w, kh, kw):
     """x NCHW, w OIHW (any float dtype) -> the 'same' correlation in float64."""
     return F.conv2d(x.double(), w.double().view(w.shape[0], -1, kh, kw), padding=pad_of(kh, kw))
+
+
+def geometry_of(c):
+    """A case's (padH, padW), (Hout, Wout) (ofx_conv_desc, include/ofx.h).  The optional keys `pad` and `out_hw` give them; the default
+    is 'same' padding k // 2 and the output size that follows.  Filters: `kh` / `kw`, or a square `k`."""
+    kh, kw = c.get("kh", c.get("k")), c.get("kw", c.get("k"))
+    ph, pw = c.get("pad") or (kh // 2, kw // 2)
+    natural = ((c["H"] + 2 * ph - kh) // c["stride"] + 1, (c["W"] + 2 * pw - kw) // c["stride"] + 1)
+    return (ph, pw), tuple(c.get("out_hw") or natural)
+
+
+def pad_amounts(hin, win, kh, kw, stride, pad, out_hw):
+    """(top, bottom, left, right) rows / columns of zeros around an image: `pad` above and left, below and right as many as the last
+    output needs, (Hout - 1) stride + KH - padH - Hin clamped at 0."""
+    (ph, pw), (ho, wo) = pad, out_hw
+    return ph, max((ho - 1) * stride + kh - ph - hin, 0), pw, max((wo - 1) * stride + kw - pw - win, 0)
+
+
+def pad_nhwc(x, amounts):
+    top, bottom, left, right = amounts
+    return F.pad(x, (0, 0, left, right, top, bottom))
+
+
+def conv64_geometry(x, w, stride, pad, out_hw, padded=False):
+    """x NHWC, w OIHW (any float dtype) -> the float64 convolution of a descriptor's geometry, NHWC: out[b, oy, ox, n] sums
+    x[b, oy stride - padH + ky, ox stride - padW + kx, c] w[n, c, ky, kx], taps outside the image zero.  Zero-pad, F.conv2d with no
+    padding, crop to [:Hout, :Wout].  padded: x already carries pad_amounts' zeros (or whatever a simulated bug put there)."""
+    kh, kw = w.shape[2:]
+    if not padded:
+        x = pad_nhwc(x, pad_amounts(x.shape[1], x.shape[2], kh, kw, stride, pad, out_hw))
+    out = F.conv2d(x.double().permute(0, 3, 1, 2), w.double(), stride=stride)
+    assert out.shape[2] >= out_hw[0] and out.shape[3] >= out_hw[1]
+    return out[:, :, :out_hw[0], :out_hw[1]].permute(0, 2, 3, 1)
 
 
 def _chan(v):
