@@ -266,6 +266,34 @@ int ofx_attention_bnhd_f32(const float* q, int ldq, const float* k, int ldk, con
 int ofx_attention_bnhd_prec(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* bias,
                             long bias_bstride, float* out, int ldo, int B, int H, int Nq, int Nk, int D, float scale, int precision,
                             void* stream);
+/* ofx_attention_bnhd_prec with K and V read through a segment table, in place: K / V of image b are the logical concatenation of
+ * seg_counts[b] segments -- what torch.cat along the tokens would build -- and image b owns the next seg_counts[b] entries of
+ * `segs` (a HOST array of sum(seg_counts) entries, copied into the kernel arguments: no device allocation, nothing to keep alive
+ * after the call returns but the tensors themselves).  A segment is n tokens; token t of it has head h at k[t * ldk + h * D],
+ * v[t * ldv + h * D] (strides in elements).  kv_type is the element type of EVERY segment of the launch: OFX_KV_F32, or OFX_KV_F16
+ * (IEEE half) -- half elements feed the OFX_PREC_F16 kernel as they are (no second rounding) and are converted exactly in the
+ * OFX_PREC_FP32 kernel.  q, bias and out are float32 as in ofx_attention_bnhd_f32; Nk is the per-image total.  The tile walk, the
+ * bias column, the ragged-tail mask and the online softmax use the logical key index, so the result is bit for bit that of
+ * ofx_attention_bnhd_prec on the concatenated float32 tensors (for OFX_KV_F16: on the halves widened to float32, and with
+ * OFX_PREC_F16 also on any float32 values that round to those halves).
+ * OFX_EINVAL before any launch: D outside {40, 64, 80, 128, 160}; seg_counts[b] outside 1 .. OFX_KV_MAX_SEGMENTS; more than
+ * OFX_KV_MAX_ENTRIES entries in all; n <= 0; per-image totals that differ; a segment with a null or misaligned pointer (16 bytes
+ * for float32 rows, 8 for half rows), a stride < H * D or not a multiple of 4 elements; an unknown kv_type or precision.  q, bias
+ * and out are checked as ofx_attention_bnhd_f32 checks them (OFX_EALIGN for their alignment). */
+#define OFX_KV_F32 0
+#define OFX_KV_F16 1
+#define OFX_KV_MAX_SEGMENTS 8
+#define OFX_KV_MAX_ENTRIES 64
+typedef struct ofx_kv_segment {
+    const void* k;   /* n rows of keys,   ldk elements apart */
+    const void* v;   /* n rows of values, ldv elements apart */
+    int n;
+    int ldk;
+    int ldv;
+} ofx_kv_segment;
+int ofx_attention_bnhd_segs(const float* q, int ldq, const ofx_kv_segment* segs, const int* seg_counts, int kv_type, const float* bias,
+                            long bias_bstride, float* out, int ldo, int B, int H, int Nq, int D, float scale, int precision,
+                            void* stream);
 
 /* ---------------------------------------------------------------- first-stage decoder (decode_first_stage / decode_latent) */
 /* `Upsample` of the VAE decoder (ldm/modules/diffusionmodules/model.py:43-58): out = conv3x3(pad 1)(interpolate(x, 2x, nearest)) + bias

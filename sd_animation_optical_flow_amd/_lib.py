@@ -63,6 +63,15 @@ class DdimCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("cfg", "sqrt_at", "sqrt_1m_at", "sqrt_aprev", "dir_coef", "sigma_t", "g", "sa", "s1")]
 
 
+class KvSegment(C.Structure):
+    """Mirror of `ofx_kv_segment` (include/ofx.h)."""
+    _fields_ = [("k", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int), ("ldk", C.c_int), ("ldv", C.c_int)]
+
+
+KV_TYPES = {"fp32": 0, "fp16": 1}                  # OFX_KV_F32 / OFX_KV_F16
+KV_MAX_SEGMENTS, KV_MAX_ENTRIES = 8, 64            # OFX_KV_MAX_SEGMENTS / OFX_KV_MAX_ENTRIES
+
+
 class Tensor(C.Structure):
     """Mirror of `ofx_tensor`."""
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("ndim", C.c_int), ("shape", C.c_long * 4)]
@@ -127,6 +136,7 @@ SIGNATURES = {
     "ofx_geglu": (_i, [_p, _i, _p, _i, _i, _i, _p]),
     "ofx_attention_bnhd_f32": (_i, [_p, _i, _p, _i, _p, _i, _p, _l, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
     "ofx_attention_bnhd_prec": (_i, [_p, _i, _p, _i, _p, _i, _p, _l, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
+    "ofx_attention_bnhd_segs": (_i, [_p, _i, C.POINTER(KvSegment), C.POINTER(_i), _i, _p, _l, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
     "ofx_upconv2x_weight": (_l, [_p, _i, _i, _p]),
     "ofx_upconv2x": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "ofx_upconv2x_prec": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),

@@ -111,6 +111,11 @@ int ofx_attention_flash_launch(const float* q, const float* k, const float* v, c
 int ofx_attention_flash_bnhd_launch(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* bias,
                                     long bias_bstride, float* out, int ldo, int B, int H, int Nq, int Nk, int D, float scale, int precision,
                                     hipStream_t s);
+// the strided kernels with K / V read through a segment table (ofx_attention_bnhd_segs, transformer.hip validates the arguments):
+// image b owns the next counts[b] entries of `segs`, Nk is every image's total
+int ofx_attention_flash_segs_launch(const float* q, int ldq, const ofx_kv_segment* segs, const int* counts, int kv_type, const float* bias,
+                                    long bias_bstride, float* out, int ldo, int B, int H, int Nq, int Nk, int D, float scale, int precision,
+                                    hipStream_t s);
 
 // handoff.hip (compiled without FMA contraction): BoxBlur.c:_gaussian_blur_radius, the fractional box radius whose `passes`-fold
 // application approximates GaussianBlur(radius), and ImagingHorizontalBoxBlur's weights from it: the integer radius r, the

@@ -136,4 +136,34 @@ int ofx_attention_bnhd_prec(const float* q, int ldq, const float* k, int ldk, co
     return attention_bnhd_checked(q, ldq, k, ldk, v, ldv, bias, bias_bstride, out, ldo, B, H, Nq, Nk, D, scale, precision, stream);
 }
 
+int ofx_attention_bnhd_segs(const float* q, int ldq, const ofx_kv_segment* segs, const int* seg_counts, int kv_type, const float* bias,
+                            long bias_bstride, float* out, int ldo, int B, int H, int Nq, int D, float scale, int precision, void* stream) {
+    OFX_REQUIRE(precision == OFX_PREC_FP32 || precision == OFX_PREC_F16, OFX_EINVAL);
+    OFX_REQUIRE(kv_type == OFX_KV_F32 || kv_type == OFX_KV_F16, OFX_EINVAL);
+    OFX_REQUIRE(q && segs && seg_counts && out && B > 0 && H > 0 && Nq > 0 && ofx_attention_flash_ok(D), OFX_EINVAL);
+    OFX_REQUIRE((long)B * H <= 0x7fffffffL && B <= OFX_KV_MAX_ENTRIES, OFX_EINVAL);
+    const long hd = (long)H * D;
+    OFX_REQUIRE(ldq >= hd && ldo >= hd, OFX_EINVAL);
+    OFX_REQUIRE(ldq % 4 == 0 && ldo % 4 == 0 && ofx_aligned16(q) && ofx_aligned16(out) && (uintptr_t)bias % 4 == 0, OFX_EALIGN);
+    // float32 rows are staged with 16-byte loads, half rows with 8-byte loads: 4 elements either way
+    const uintptr_t amask = kv_type == OFX_KV_F32 ? 15u : 7u;
+    long Nk = -1;
+    int at = 0;
+    for (int b = 0; b < B; ++b) {
+        const int cnt = seg_counts[b];
+        OFX_REQUIRE(cnt >= 1 && cnt <= OFX_KV_MAX_SEGMENTS && at + cnt <= OFX_KV_MAX_ENTRIES, OFX_EINVAL);
+        long total = 0;
+        for (int i = 0; i < cnt; ++i, ++at) {
+            const ofx_kv_segment& g = segs[at];
+            OFX_REQUIRE(g.k && g.v && g.n > 0 && g.ldk >= hd && g.ldv >= hd, OFX_EINVAL);
+            OFX_REQUIRE(g.ldk % 4 == 0 && g.ldv % 4 == 0 && ((uintptr_t)g.k & amask) == 0 && ((uintptr_t)g.v & amask) == 0, OFX_EINVAL);
+            total += g.n;
+        }
+        OFX_REQUIRE(total <= 0x7fffffffL && (Nk < 0 || total == Nk), OFX_EINVAL);
+        Nk = total;
+    }
+    return ofx_attention_flash_segs_launch(q, ldq, segs, seg_counts, kv_type, bias, bias_bstride, out, ldo, B, H, Nq, (int)Nk, D, scale,
+                                           precision, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -1096,6 +1096,116 @@ def attention_bnhd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
     return out
 
 
+KV_DTYPES = {"fp32": torch.float32, "fp16": torch.float16}       # `kv_dtype=` of the models: the dtype of a recorded K/V history
+
+
+def check_kv_dtype(kv_dtype, name: str = "kv_dtype") -> str:
+    if not isinstance(kv_dtype, str) or kv_dtype not in KV_DTYPES:
+        raise ValueError(f"{name} must be one of {tuple(KV_DTYPES)}, got {kv_dtype!r}")
+    return kv_dtype
+
+
+def _kv_segment_lists(segments, B: int) -> list:
+    """`segments` of `attention_bnhd_segments` -> B lists of (k, v), checked as far as metadata goes (no device): the list
+    structure, one dtype throughout, the table limits.  ValueError otherwise."""
+    if not isinstance(segments, (list, tuple)) or len(segments) == 0:
+        raise ValueError("segments must be a non-empty list of (k, v) pairs, or one such list per image")
+    is_pair = lambda e: isinstance(e, (list, tuple)) and len(e) == 2 and all(isinstance(t, torch.Tensor) for t in e)
+    if all(is_pair(e) for e in segments):
+        per_image = [list(segments)] * B                          # one list shared by all images
+    else:
+        if len(segments) != B:
+            raise ValueError(f"segments holds {len(segments)} per-image lists, q has {B} images")
+        per_image = [list(s) if isinstance(s, (list, tuple)) else [s] for s in segments]
+        for b, segs in enumerate(per_image):
+            if not segs or not all(is_pair(e) for e in segs):
+                raise ValueError(f"segments[{b}] must be a non-empty list of (k, v) tensor pairs")
+    dtypes = {t.dtype for segs in per_image for e in segs for t in e}
+    if len(dtypes) != 1 or next(iter(dtypes)) not in (torch.float32, torch.float16):
+        raise ValueError(f"segments must be all float32 or all float16 (one element type per launch), got {sorted(str(d) for d in dtypes)}")
+    if max(len(s) for s in per_image) > _lib.KV_MAX_SEGMENTS or sum(len(s) for s in per_image) > _lib.KV_MAX_ENTRIES:
+        raise ValueError(f"at most {_lib.KV_MAX_SEGMENTS} segments per image and {_lib.KV_MAX_ENTRIES} in all, got "
+                         f"{[len(s) for s in per_image]}")
+    return per_image
+
+
+def attention_bnhd_segments(q: torch.Tensor, segments, heads: int, bias: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                            out: Optional[torch.Tensor] = None, precision: str = "fp32") -> torch.Tensor:
+    """`attention_bnhd` with K and V read in place through a segment table (`ofx_attention_bnhd_segs`): image b attends to the
+    logical concatenation of its segments, nothing is copied, widened or concatenated.  segments: one list of (k, v) per image, or
+    one list shared by all images; each k / v is [n_i, H*D], contiguous or a last-axis slice of a wider tensor (a third of a q|k|v
+    buffer), all float32 or all float16; every image's n_i sum to the same Nk.  At most 8 segments per image, 64 in all.  q, bias
+    ([Nq,Nk] or [B*H,Nq,Nk]) and out are float32 as in `attention_bnhd`.  Bit for bit `attention_bnhd` on the concatenated float32
+    tensors; float16 segments feed the "fp16" kernel without a second rounding and are widened exactly in the "fp32" kernel.
+    Every check runs before a device is touched; a bad structure, mixed dtypes or a table beyond the limits is a ValueError."""
+    check_attention_precision(precision)
+    if not isinstance(q, torch.Tensor) or q.dim() != 3:
+        raise RuntimeError("q must be a CUDA float32 tensor [B,Nq,H*D]")
+    B, Nq, W = (int(s) for s in q.shape)
+    H = int(heads)
+    if H <= 0 or W % H:
+        raise RuntimeError("attention_bnhd_segments: q [B,Nq,H*D] expected")
+    D = W // H
+    per_image = _kv_segment_lists(segments, B)
+    half = per_image[0][0][0].dtype == torch.float16
+    table = (_lib.KvSegment * sum(len(s) for s in per_image))()
+    counts = (C.c_int * B)(*[len(s) for s in per_image])
+    for b, segs in enumerate(per_image):                          # shapes and totals first: metadata, as the checks above
+        for i, (k, v) in enumerate(segs):
+            for t in (k, v):
+                if t.dim() != 2 or t.shape[1] != W or t.shape[0] != k.shape[0] or t.shape[0] == 0:
+                    raise ValueError(f"segments[{b}][{i}]: k and v must be [n, {W}] with one n > 0, got {tuple(k.shape)} and {tuple(v.shape)}")
+    totals = [sum(int(k.shape[0]) for k, _ in segs) for segs in per_image]
+    if len(set(totals)) != 1:
+        raise ValueError(f"every image's segments must sum to one token count, got {totals}")
+    at = 0
+    for b, segs in enumerate(per_image):
+        for i, (k, v) in enumerate(segs):
+            lds = []
+            for nm, t in (("k", k), ("v", v)):
+                ld = int(t.stride(0)) if t.shape[0] > 1 else W
+                if (W > 1 and t.stride(1) != 1) or ld < W or ld % 4 or not t.is_cuda or t.device != q.device:
+                    raise RuntimeError(f"segments[{b}][{i}].{nm} must be on q's device, dense along the last axis, rows a multiple of 4 "
+                                       f"elements apart")
+                lds.append(ld)
+            table[at].k, table[at].v, table[at].n, table[at].ldk, table[at].ldv = k.data_ptr(), v.data_ptr(), int(k.shape[0]), lds[0], lds[1]
+            at += 1
+    return _attention_bnhd_segment_table(q, table, counts, half, totals[0], H, bias, scale, out, precision)
+
+
+def _kv_segment_table(rows):
+    """(kptr, vptr, n, ldk, ldv) rows -> the `ofx_kv_segment` array `ofx_attention_bnhd_segs` takes."""
+    return (_lib.KvSegment * len(rows))(*rows)
+
+
+def _attention_bnhd_segment_table(q: torch.Tensor, table, counts, half: bool, Nk: int, heads: int, bias: Optional[torch.Tensor] = None,
+                                 scale: Optional[float] = None, out: Optional[torch.Tensor] = None, precision: str = "fp32") -> torch.Tensor:
+    """Internal.  The launch of `attention_bnhd_segments` for a caller that holds the table already (`_kv_segment_table`; image b owns the next
+    counts[b] entries, a ctypes int array) and keeps the segments' tensors alive: `SpatialTransformer` builds one table per forward
+    from entries it has planned, without a tensor view per image and entry.  q, bias and out are checked here; the table is
+    checked by the C entry, before any launch."""
+    check_attention_precision(precision)
+    B, Nq, W = (int(s) for s in q.shape)
+    H = int(heads)
+    D = W // H
+    ldq = _bnhd(q, "q")
+    per_bh = bias is not None and bias.dim() == 3
+    if bias is not None:
+        bias = _chk(bias, "bias", torch.float32)
+        if tuple(bias.shape) not in ((Nq, Nk), (B * H, Nq, Nk)):
+            raise RuntimeError("attention_bnhd_segments: bias must be [Nq,Nk] or [B*H,Nq,Nk]")
+    if out is None:
+        out = torch.empty((B, Nq, W), dtype=torch.float32, device=q.device)
+    ldo = _bnhd(out, "out")
+    if tuple(out.shape) != (B, Nq, W):
+        raise RuntimeError(f"out must be {(B, Nq, W)}, got {tuple(out.shape)}")
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    check(_lib.lib().ofx_attention_bnhd_segs(_ptr(q), ldq, table, counts, _lib.KV_TYPES["fp16" if half else "fp32"], _ptr(bias),
+                                             Nq * Nk if per_bh else 0, _ptr(out), ldo, B, H, Nq, D, scale, ATTENTION_PRECISIONS[precision],
+                                             _stream()), "ofx_attention_bnhd_segs")
+    return out
+
+
 # --------------------------------------------------------------------------------------
 # CLIP text encoder pieces (hack.py:32-70): the token + position embedding and quick_gelu
 # --------------------------------------------------------------------------------------

@@ -19,6 +19,8 @@ A K/V history (`kv_hist`, `GuidedDDIMSampler.last_kv_hists`) holds the self-atte
 the UNet's last call.  At SD v1.5 and 512x768 that is 139 MB per batch row (16 attention layers: 5 at 6144 tokens x 320 channels,
 5 at 1536 x 640, 5 at 384 x 1280, 1 at 96 x 1280, keys and values, fp32), so 277 MB per frame at UNet batch 2 -- derived from
 the layer table; `tools/render_rate.py` reports the same figure from the tensors.  `run_exp` keeps them on the device in a dict and drops them as the reference does.
+`kv_dtype="fp16"` (`UNetModel`, `SdRenderer`, `run_exp`) keeps them in half, as the reference's autocast does: 139 MB per frame in
+memory and in `video.put_kv`'s pickle; the fused attention reads them in place in either dtype (`transformer` module docstring).
 
 Needs no device to import; `generation_plan` is pure Python.
 """
@@ -76,6 +78,15 @@ def _frame(a, device) -> torch.Tensor:
     return t.to(device).contiguous()
 
 
+def as_kv_dtype(kv, kv_dtype: str):
+    """A K/V history (a list of (k, v) pairs) with every tensor in `kv_dtype` ("fp32" / "fp16"): the list itself where every tensor
+    already is (no copy), a converted copy otherwise -- to half with round to nearest even and infinities beyond +-65504."""
+    dt = ops.KV_DTYPES[ops.check_kv_dtype(kv_dtype)]
+    if all((not torch.is_tensor(t)) or t.dtype == dt for e in kv for t in e):
+        return kv
+    return [tuple(t.to(dt) if torch.is_tensor(t) else t for t in e) for e in kv]
+
+
 def generation_plan(history: Sequence, num_ref: int) -> List[Tuple[int, int, List[int], List[int], Optional[int]]]:
     """The bookkeeping of run_exp's generation loop (:1173-1240), pure Python.  history: the index sets the analysis left, from
     all frames (level 0) to the seed frames (frame 0 already added); each a `VideoFrameIndices` or any iterable of ints, none is
@@ -115,11 +126,15 @@ class SdRenderer:
     or that pair.  controls: `ControlSpec`s (`driver_controls`); their guidance windows are the specs'.  seed: every
     `run_inpainting` / `generate_seed_frames` call draws its noise from a device generator seeded with it, as the reference
     calls torch.manual_seed(1234) per call (:274-275).  An instance is also `ClipPipeline`'s pair of hooks: `render=renderer`,
-    `render_key=renderer.render_key`."""
+    `render_key=renderer.render_key`.  kv_dtype: "fp32" (default) or "fp16", the dtype of every K/V history the methods hand back
+    (anything else is a ValueError).  UNets built with the same `kv_dtype=` record it directly; a history of the other dtype is
+    converted once as it is handed back (`as_kv_dtype`)."""
 
     def __init__(self, unet_inpaint, vae_encoder, vae_decoder, conditioning, controls: Sequence[ControlSpec] = (), *, unet_seed=None,
                  ddim_steps: int = 50, ds: float = 0.6, mask_blur: float = 4, unconditional_guidance_scale: float = 7.0,
-                 guidance_schedule_func: Callable = lambda p: 0.1, seed: int = 1234, warp_mode: Optional[str] = None):
+                 guidance_schedule_func: Callable = lambda p: 0.1, seed: int = 1234, warp_mode: Optional[str] = None,
+                 kv_dtype: str = "fp32"):
+        self.kv_dtype = ops.check_kv_dtype(kv_dtype)               # before anything else is looked at
         self.unet_inpaint, self.unet_seed = unet_inpaint, unet_seed
         self.vae_encoder, self.vae_decoder = vae_encoder, vae_decoder
         self.conditioning = conditioning
@@ -134,6 +149,9 @@ class SdRenderer:
     @property
     def device(self):
         return self.unet_inpaint.device
+
+    def _kv(self, kv):
+        return as_kv_dtype(kv, self.kv_dtype)
 
     def _generator(self) -> torch.Generator:
         return torch.Generator(device=self.device).manual_seed(self.seed)
@@ -174,7 +192,7 @@ class SdRenderer:
                                   unconditional_guidance_scale=self.unconditional_guidance_scale,
                                   guidance_schedule_func=self.guidance_schedule_func, generator=self._generator(), control_nets=nets,
                                   reference_kv=reference_kv, sampler=smp, fill_masked=reference is None, want_init_decoded=False)
-        return ops.decode_to_u8(x.permute(0, 2, 3, 1).contiguous())[0], smp.last_kv_hists
+        return ops.decode_to_u8(x.permute(0, 2, 3, 1).contiguous())[0], self._kv(smp.last_kv_hists)
 
     # ---- generate_seed_frames (:1088-1117) -------------------------------------------------------------------------------
     @torch.no_grad()
@@ -195,7 +213,7 @@ class SdRenderer:
                     unconditional_guidance_scale=self.unconditional_guidance_scale, generator=self._generator(),
                     control_nets=self.control_nets(large), sampler=smp)
         wide = ops.decode_to_u8(x.permute(0, 2, 3, 1).contiguous())[0]
-        return [p.contiguous() for p in torch.chunk(wide, len(frames), dim=1)], smp.last_kv_hists
+        return [p.contiguous() for p in torch.chunk(wide, len(frames), dim=1)], self._kv(smp.last_kv_hists)
 
     # ---- generate_ai_frame_with_ref (:722-1086) --------------------------------------------------------------------------
     @torch.no_grad()
@@ -251,19 +269,21 @@ class SdRenderer:
 @torch.no_grad()
 def run_exp(video, pdcnet, renderer: SdRenderer, num_ref_for_generation: int = 1, ds: float = 0.6,
             mode: str = "warp_and_inpaint_crossattn", kernel_size: int = 30, stride: int = 15, dilation: int = 2,
-            persist_kv: bool = False) -> Dict[int, list]:
+            persist_kv: bool = False, kv_dtype: Optional[str] = None) -> Dict[int, list]:
     """The reference's `run_exp` from the analysis on (:1153-1241) over a `workspace.VideoData` and an `ofgen.PDCNetAux`:
     `KeyframeConv` level by level (`d{level:02d}/` under the workspace) down to one seed frame, frame 0 added, the seed frames
     (`generate_seed_frames`, ds 0.8), then `generation_plan`: per frame `multiple_to_one_device`, `generate_ai_frame_with_ref`,
     `put_ai_frame`.  K/V histories stay on the device in a dict keyed by frame index, which is returned; the previous frame's is
     dropped at level 0 as the reference does.  persist_kv also pickles them through `video.put_kv` / `remove_kv` (277 MB per
-    frame at v1.5 and 512x768, module docstring).  An unknown mode or a renderer without `unet_seed` is a ValueError before
-    anything runs."""
+    frame at v1.5 and 512x768, module docstring; half of that with kv_dtype "fp16").  kv_dtype: "fp32" or "fp16", the dtype of the
+    histories in the returned dict and in `video.put_kv`; None (default) is the renderer's own `kv_dtype`, "fp32" unless it was
+    built otherwise.  An unknown mode or kv_dtype, or a renderer without `unet_seed`, is a ValueError before anything runs."""
     import os
 
     from .workspace import VideoFrameIndices
     if mode not in MODES:
         raise ValueError(f"unknown mode {mode!r}: one of {MODES}")
+    kv_dtype = ops.check_kv_dtype(getattr(renderer, "kv_dtype", "fp32") if kv_dtype is None else kv_dtype)
     if renderer.unet_seed is None:
         raise ValueError("run_exp needs a renderer with unet_seed (the seed frames)")
     n_seed_frames = 1
@@ -282,6 +302,7 @@ def run_exp(video, pdcnet, renderer: SdRenderer, num_ref_for_generation: int = 1
     ai: Dict[int, torch.Tensor] = {}
 
     def put(idx, frame, kv):
+        kv = as_kv_dtype(kv, kv_dtype)
         ai[idx] = frame
         video.put_ai_frame(idx, frame.cpu().numpy())
         kv_map[idx] = kv

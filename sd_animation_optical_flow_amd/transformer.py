@@ -25,6 +25,22 @@ on the fp16 matrix cores with fp32 accumulation; the softmax, the scale and the 
 before the attention -- are exactly what they are without it.  It exists on the fused route only: with OFX_ST_TORCH_GLUE=1, or a head
 size outside `FUSED_HEAD_SIZES`, "fp16" is a ValueError at construction (no silent fallback).
 
+Reference K/V are read in place: on the fused route the entries of `reference_kv` reach the kernel as a per-image segment table
+(`ops.attention_bnhd_segments`, `ofx_attention_bnhd_segs`), float32 or float16 as they are stored, bit for bit what attending to
+their float32 concatenation gives; nothing is widened or joined with torch.cat, and the "positive" mode is one launch (image 0's
+segment is its own k / v thirds of the qkv buffer) unless the history is float16, where it stays two (one element type per launch).
+`plan_kv_route` decides from shapes and dtypes alone; entries in the reference's [(b h), n, d] layout, mixed dtypes, tables beyond
+8 segments per image / 64 per launch and the unfused routes keep the concatenation path, which widens float16 entries.
+`kv_dtype=` ("fp32" default, "fp16") is the dtype of the returned `kv_hists`: "fp16" rounds the block's own K/V to half (nearest
+even, beyond +-65504 to infinity, as under torch.autocast, whose `kv_hist` is half too) -- half the memory and half the pickle.  The
+block's own attention still reads the float32 K/V.  Histories of either dtype are accepted as `reference_kv`.  A float16 history
+pairs with `attention_precision="fp16"`, where a launch on half entries is about 14 % faster than the concatenation path; with
+fp32 attention it trades time for memory: the fp32 kernel widens half rows as it stages them and a launch is about 15 % slower
+than widening and concatenating first (2.60 against 2.26 ms at 6144 queries x 12288 keys, profiles/r38_kv_history_rate.txt).
+
+OFX_ST_KV_CONCAT=1 in the environment (read once per process; the A/B baseline and a diagnostic): reference K/V always take the
+concatenation path.
+
 OFX_ST_TORCH_GLUE=1 in the environment (read once per process; the A/B baseline and a diagnostic): LayerNorm and GEGLU through
 torch.nn.functional, attention through permute + `ops.attention`, i.e. the glue this module replaces.  Head sizes the fused kernel
 does not take (`FUSED_HEAD_SIZES`) go the permute + `ops.attention` way on their own.
@@ -37,6 +53,8 @@ reference tree: parity is pinned with seeded weights loaded into the reference's
 """
 from __future__ import annotations
 
+import ctypes
+import weakref
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -150,13 +168,57 @@ def plan_reference_kv(shapes: Sequence[Tuple[Tuple[int, ...], Tuple[int, ...]]],
                      f"count), or batch {B - 1} with exactly {N} tokens")
 
 
+def _kv_concat() -> bool:
+    """OFX_ST_KV_CONCAT=1 (A/B baseline and diagnostic, read once per process): reference K/V always go the concatenation way --
+    every entry widened to float32, several joined with torch.cat -- and never through the segment table."""
+    return env_flag("OFX_ST_KV_CONCAT")
+
+
+_kv_concat.cache_clear = env_flag.cache_clear                      # clearable like _torch_glue, where a test changes the environment
+
+
+KV_MAX_SEGMENTS, KV_MAX_ENTRIES = 8, 64        # OFX_KV_MAX_SEGMENTS / OFX_KV_MAX_ENTRIES (include/ofx.h)
+
+
+def plan_kv_route(mode: str, dtypes: Sequence, ref_layout: Sequence[bool], B: int, d_head: int, *, torch_glue: bool = False,
+                  force_concat: bool = False) -> str:
+    """How the self-attention reads reference K/V entries of these dtypes (torch dtypes or their names) for a batch of B images,
+    decided from metadata alone (no device): "segments" -- the fused kernel reads every entry in place through a segment table
+    (`ops.attention_bnhd_segments`), nothing is widened or concatenated; "segments+own" -- `mode` "positive" with a float16 history:
+    image 0 on its own float32 K/V in one launch, images 1.. on the segments in a second (one element type per launch); "concat"
+    -- today's path, entries widened to float32 and joined with torch.cat.  "concat" is what remains for entries in the reference's
+    [(b h), n, d] layout, head sizes outside FUSED_HEAD_SIZES, OFX_ST_TORCH_GLUE=1 (`torch_glue`), OFX_ST_KV_CONCAT=1
+    (`force_concat`), entries of mixed or other dtypes, and tables beyond 8 segments per image or 64 entries per launch.
+    The arithmetic of the attention is not asked: a float16 history under fp32 attention stays on the segment route, which keeps
+    its memory saving (nothing is widened in memory) at the cost of a slower launch -- the trade stated in the module docstring."""
+    if mode not in ("all", "positive"):
+        raise ValueError(f"mode must be 'all' or 'positive', got {mode!r}")
+    names = {str(d).replace("torch.", "") for d in dtypes}
+    if force_concat or torch_glue or int(d_head) not in FUSED_HEAD_SIZES or any(ref_layout) or len(names) != 1:
+        return "concat"
+    dt = next(iter(names))
+    if dt not in ("float32", "float16"):
+        return "concat"
+    E = len(ref_layout)                                            # entries; `dtypes` may name every k and v tensor, or one per entry
+    if E < 1 or E > KV_MAX_SEGMENTS:
+        return "concat"
+    if mode == "all":
+        return "segments" if B * E <= KV_MAX_ENTRIES else "concat"
+    if dt == "float32":                                            # image 0's own k / v is one more segment of the same launch
+        return "segments" if 1 + (B - 1) * E <= KV_MAX_ENTRIES else "concat"
+    return "segments+own" if (B - 1) * E <= KV_MAX_ENTRIES else "concat"
+
+
 class SpatialTransformer(DeviceModel):
     """`ldm.modules.attention.SpatialTransformer` (use_linear=False, inference) on a HIP device."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], n_heads: int, d_head: int, device="cuda", prefix: str = "",
-                 use_linear: bool = False, precision: str = "fp32", attention_precision: str = "fp32"):
+                 use_linear: bool = False, precision: str = "fp32", attention_precision: str = "fp32", kv_dtype: str = "fp32"):
         self.precision = check_precision(precision)                # before the checkpoint is looked at or a device asked for
         self.attention_precision = ops.check_attention_precision(attention_precision, "attention_precision")
+        self.kv_dtype = ops.check_kv_dtype(kv_dtype)
+        self.kv_concat = _kv_concat()
+        self._kv_memo = None                                       # `_reference_kv`: the plan of the previous call's reference tensors
         if self.attention_precision != "fp32":                     # the fused kernel only: no unfused fp16 path, no silent fallback
             if _torch_glue():
                 raise ValueError(f"attention_precision={attention_precision!r} does not combine with OFX_ST_TORCH_GLUE=1")
@@ -221,14 +283,51 @@ class SpatialTransformer(DeviceModel):
         out.copy_(o)
         return out
 
+    def _attention_segments(self, q: torch.Tensor, table, nk: int, half: bool, out: Optional[torch.Tensor] = None, ctab=None) -> torch.Tensor:
+        """`ops.attention_bnhd_segments` on table rows per image (`_reference_kv`): one launch, K / V read where they lie.  ctab: the
+        (`ofx_kv_segment` array, counts) of exactly these rows, where `_reference_kv` has built them already."""
+        if ctab is None:
+            ctab = (ops._kv_segment_table([r for t in table for r in t]), (ctypes.c_int * len(table))(*[len(t) for t in table]))
+        return ops._attention_bnhd_segment_table(q, ctab[0], ctab[1], half, nk, self.heads, out=out, precision=self.attention_precision)
+
     def _reference_kv(self, reference_kv, B: int, N: int):
-        """-> None, or (mode, k, v) on the device in our layout, entries concatenated along tokens (attention.py:361-362)."""
+        """-> None, or (mode, route, payload) with `route` of `plan_kv_route`.  "concat": payload = (k, v) on the device in our
+        layout, float32, entries concatenated along tokens (attention.py:361-362).  "segments" / "segments+own": payload = (table, tokens, half,
+        tensors, ctab): table[b] holds the `ofx_kv_segment` rows of every entry for reference image b, in the entries' own dtype and
+        memory (`tensors` keeps them alive) -- nothing widened, nothing concatenated."""
         if not reference_kv:
             return None
         entries = [tuple(e) for e in reference_kv]
         if any(len(e) not in (2, 3) for e in entries):
             raise ValueError("reference_kv entries are (k, v) or (k, v, layer) tuples")
+        # A sampler hands every UNet call of a frame the SAME tensors: the plan and the table of the previous call are kept (by weak
+        # reference: no history is kept alive here) and reused while every entry is that very tensor at that very address
+        ts = [t for e in entries for t in e[:2]]
+        m = self._kv_memo
+        if m is not None and m[0] == (B, N, len(ts)) and all(r() is t and p == t.data_ptr() and sh == t.shape
+                                                             for (r, p, sh), t in zip(m[1], ts)):
+            return m[2]
+        self._kv_memo = None
         mode, _, ref_layout = plan_reference_kv([(e[0].shape, e[1].shape) for e in entries], B, N, self.heads, self.d_head)
+        route = plan_kv_route(mode, [t.dtype for e in entries for t in e[:2]], ref_layout, B, self.d_head, torch_glue=self.torch_glue,
+                              force_concat=self.kv_concat)
+        if route != "concat":
+            # rows the kernel can load 4 elements at a time where they are; anything else (never a recorded history) is copied once
+            rows = lambda t: t if (t.stride(2) == 1 and t.stride(1) >= t.shape[2] and t.stride(1) % 4 == 0 and t.stride(0) % 4 == 0
+                                   and t.data_ptr() % (4 * t.element_size()) == 0) else t.contiguous()
+            dev = [(rows(e[0].to(self.device)), rows(e[1].to(self.device))) for e in entries]
+            # the table rows (k pointer, v pointer, tokens, row strides) of every reference image, by pointer arithmetic: this
+            # forward is host-enqueue bound, and a tensor view per image and entry costs more than the launch it feeds
+            es = dev[0][0].element_size()
+            table = [[(k.data_ptr() + b * k.stride(0) * es, v.data_ptr() + b * v.stride(0) * es, int(k.shape[1]), int(k.stride(1)),
+                       int(v.stride(1))) for k, v in dev] for b in range(dev[0][0].shape[0])]
+            # "all": the table is the launch's own, built once; "positive" prepends image 0's k / v of each call
+            ctab = (ops._kv_segment_table([r for t in table for r in t]), (ctypes.c_int * len(table))(*[len(t) for t in table])) \
+                if mode == "all" else None
+            ref = (mode, route, (table, sum(int(k.shape[1]) for k, _ in dev), dev[0][0].dtype == torch.float16, dev, ctab))
+            if all(d is t for d, t in zip((d for pair in dev for d in pair), ts)):      # read where the caller's tensors lie: no copy of ours
+                self._kv_memo = ((B, N, len(ts)), [(weakref.ref(t), t.data_ptr(), t.shape) for t in ts], ref[:2] + (ref[2][:3] + (None, ctab),))
+            return ref
         ks, vs = [], []
         for e, rl in zip(entries, ref_layout):
             for t, dst in ((e[0], ks), (e[1], vs)):
@@ -236,7 +335,7 @@ class SpatialTransformer(DeviceModel):
                 dst.append(from_reference_layout(t, self.heads) if rl else t.contiguous())
         k = ks[0] if len(ks) == 1 else torch.cat(ks, dim=1)
         v = vs[0] if len(vs) == 1 else torch.cat(vs, dim=1)
-        return mode, k, v
+        return mode, "concat", (k, v)
 
     def _block(self, i: int, x: torch.Tensor, context: Optional[torch.Tensor], ref) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
         """BasicTransformerBlock._forward (:464-469) on tokens x [B, N, inner]."""
@@ -246,16 +345,31 @@ class SpatialTransformer(DeviceModel):
         # self-attention: one GEMM for q | k | v, the attention reads its thirds in place
         qkv = self._gemm(f"{b}.attn1.to_qkv", self._layernorm(f"{b}.norm1", x), False)
         q, k, v = qkv[..., :inner], qkv[..., inner:2 * inner], qkv[..., 2 * inner:]
-        kv_hist = (k.contiguous(), v.contiguous())                 # the block's own K/V, recorded before any replacement (:353)
+        # the block's own K/V, recorded before any replacement (:353); kv_dtype="fp16": one rounding copy (nearest even, beyond
+        # +-65504 to infinity, as under autocast) in place of the plain one
+        kv_hist = (k.contiguous(), v.contiguous()) if self.kv_dtype == "fp32" else tuple(
+            torch.empty((B, N, inner), dtype=torch.float16, device=x.device).copy_(t) for t in (k, v))
         if ref is None:
             a = self._attention(q, k, v)
+        elif ref[1] == "segments":
+            # the fused kernel reads every entry where it lies; "positive" (:365-366): image 0's segment is its own k / v thirds
+            table, nk, half, _, ctab = ref[2]
+            if ref[0] != "all":
+                table = [[(k.data_ptr(), v.data_ptr(), N, int(k.stride(1)), int(v.stride(1)))]] + table
+            a = self._attention_segments(q, table, nk, half, ctab=ctab)
+        elif ref[1] == "segments+own":
+            # "positive" with a float16 history: one element type per launch, so image 0 on its own float32 K/V stays a launch
+            a = torch.empty((B, N, inner), dtype=torch.float32, device=x.device)
+            self._attention(q[:1], k[:1], v[:1], out=a[:1])
+            table, nk, half, _, _ = ref[2]
+            self._attention_segments(q[1:], table, nk, half, out=a[1:])
         elif ref[0] == "all":
-            a = self._attention(q, ref[1], ref[2])                 # k = k2, v = v2 (:368-369)
+            a = self._attention(q, *ref[2])                        # k = k2, v = v2 (:368-369)
         else:
             # k[nhead:] = k2 (:365-366): image 0 on its own K/V, images 1.. on the references'; two launches into one buffer
             a = torch.empty((B, N, inner), dtype=torch.float32, device=x.device)
             self._attention(q[:1], k[:1], v[:1], out=a[:1])
-            self._attention(q[1:], ref[1], ref[2], out=a[1:])
+            self._attention(q[1:], *ref[2], out=a[1:])
         x = self._gemm(f"{b}.attn1.to_out.0", a, True, addend=x)
         # cross-attention (a second self-attention without context, :467)
         hn = self._layernorm(f"{b}.norm2", x)

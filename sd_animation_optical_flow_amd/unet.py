@@ -221,10 +221,11 @@ class UNetTrunk(DeviceModel):
         return _layers(self.layout)
 
     def _setup(self, state_dict: Dict[str, torch.Tensor], cfg: dict, device, prefix: str, precision: str,
-               attention_precision: str) -> Dict[str, torch.Tensor]:
+               attention_precision: str, kv_dtype: str = "fp32") -> Dict[str, torch.Tensor]:
         """Everything `__init__` does; -> the checked fp32 CPU tensors by key (for what a subclass loads beyond `self.w`)."""
         self.precision = check_precision(precision)                # before the checkpoint is looked at or a device asked for
         self.attention_precision = ops.check_attention_precision(attention_precision, "attention_precision")
+        self.kv_dtype = ops.check_kv_dtype(kv_dtype)               # the dtype of the returned kv_hists (`SpatialTransformer(kv_dtype=)`)
         self.layout = self._layout(cfg)
         self.cfg = self.layout["cfg"]
         c = self.cfg
@@ -251,7 +252,8 @@ class UNetTrunk(DeviceModel):
                 # the fp16 attention kernel exists for the fused head sizes only (all 16 transformers of SD v1.5: 40 / 80 / 160).  A
                 # transformer with another head size keeps fp32 attention, and says so: a warning below, `attention_precision_of`
                 ap = self.attention_precision if int(l[4]) in FUSED_HEAD_SIZES else "fp32"
-                self.st[name] = SpatialTransformer(sub, l[3], l[4], device=self.device, precision=self.precision, attention_precision=ap)
+                self.st[name] = SpatialTransformer(sub, l[3], l[4], device=self.device, precision=self.precision, attention_precision=ap,
+                                                   kv_dtype=self.kv_dtype)
             elif kind == "res":
                 emb_w.append(t32[f"{name}.emb_layers.1.weight"])
                 emb_b.append(t32[f"{name}.emb_layers.1.bias"])
@@ -361,11 +363,13 @@ class UNetModel(UNetTrunk):
     (`SpatialTransformer(attention_precision=)`; the K/V a transformer records is unchanged by it).  That kernel exists for the head
     sizes 40 / 64 / 80 / 128 / 160 -- all 16 transformers of SD v1.5.  In a configuration with another head size (the test
     configuration u0 has a 192-wide middle head) that transformer keeps fp32 attention: a UserWarning names it at construction and
-    `attention_precision_of` maps every transformer to the mode it runs.  A SpatialTransformer built directly raises instead."""
+    `attention_precision_of` maps every transformer to the mode it runs.  A SpatialTransformer built directly raises instead.
+    `kv_dtype`: "fp32" (default) or "fp16", the dtype of the returned `kv_hists` (`SpatialTransformer(kv_dtype=)`); histories of
+    either dtype are accepted as `reference_kv`, and on the fused route they are attended to in place, unwidened."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: dict = SD_V15_UNET, device="cuda", prefix: str = "model.diffusion_model.",
-                 precision: str = "fp32", attention_precision: str = "fp32"):
-        self._setup(state_dict, cfg, device, prefix, precision, attention_precision)
+                 precision: str = "fp32", attention_precision: str = "fp32", kv_dtype: str = "fp32"):
+        self._setup(state_dict, cfg, device, prefix, precision, attention_precision, kv_dtype)
 
     def _check_inputs(self, B, H, W, timesteps, context, control, reference_kv):
         """Every check that needs no launch; -> (per-transformer reference K/V, control as NHWC views or None)."""
