@@ -311,7 +311,7 @@ long ofx_upconv2x_weight(const float* w_oihw, int Cout, int Cin, float* out);
 int ofx_upconv2x(const float* x, const float* w, const float* bias, float* out, int ldo, int B, int H, int W, int Cin, int Cout,
                  void* stream);
 /* ofx_upconv2x with the arithmetic of the contraction chosen by `precision` (an OFX_PREC_* value, defined below with the convolutions'
- * modes: 0 and 5 here).  The argument checks of ofx_upconv2x apply unchanged.
+ * modes: 0, 5 and 7 here).  The argument checks of ofx_upconv2x apply unchanged.
  *   OFX_PREC_FP32 (0)  ofx_upconv2x itself, bit for bit (called through).
  *   OFX_PREC_F16 (5)   opt-in (`VaeDecoder(precision="fp16")`): the arithmetic of OFX_PREC_F16 in ofx_conv2d on the same four parity
  *       GEMMs and the same 128 x BN tiles.  x and the folded w stay fp32 in memory; each element is rounded to fp16 once, to nearest
@@ -319,7 +319,10 @@ int ofx_upconv2x(const float* x, const float* w, const float* bias, float* out, 
  *       accumulation; the bias add and the stored result are fp32.  It is the FOLDED weight that is rounded (w1 + w2 summed in
  *       float64, rounded to fp32 by ofx_upconv2x_weight, then to fp16 here), so the result differs from the unfused fp16 pair by
  *       those roundings.  Magnitudes beyond 65504 become infinities, as under torch.autocast; subnormals are not flushed.
- *   any other value    OFX_EINVAL before any launch.
+ *   OFX_PREC_F16_W (7) the kernel of OFX_PREC_F16 with `w` read as IEEE halves [4][Cout][4][Cin] (ofx_half_conv_weight of the folded
+ *       fp32 operand; 16-byte aligned): staged as they are, bit-identical to 5 on fp32 weights that round to them.  ofx_upconv2x_bn
+ *       answers as for 5.
+ *   any other value   OFX_EINVAL before any launch.
  * ofx_upconv2x_bn (host, no device): the column-tile width BN in {64, 128} of the 128 x BN tile both entry points launch for this
  * Cout and precision (OFX_EINVAL for Cout <= 0 or another precision). */
 int ofx_upconv2x_prec(const float* x, const float* w, const float* bias, float* out, int ldo, int B, int H, int W, int Cin, int Cout,
@@ -508,12 +511,20 @@ int ofx_abs_diff_sum_u8(const uint8_t* a, long a_bstride, const uint8_t* b, long
                                  that what OFX_PREC_F16 documents as rejected stays rejected for callers written against it.  Still
                                  OFX_EINVAL before any launch: the flow epilogue, nz > 1, the pooled volume, a split-K workspace
                                  and the paired-pipeline tile marker */
+#define OFX_PREC_F16_W 7      /* OFX_PREC_F16 with `w` already in the kernel's format: IEEE halves [Cout][Kpad] (same packing, k order
+                                 and Kpad; rows are multiples of 64 bytes, `w` 16-byte aligned), as ofx_half_conv_weight makes them from
+                                 the packed fp32 matrix.  The halves are staged as they are -- no convert, no second rounding -- so the
+                                 output is bit-identical to OFX_PREC_F16 on any fp32 weights that round to them, at half the weight
+                                 bytes held and streamed.  The arithmetic, tiles, schedules, plain epilogue, plan (every field but
+                                 `prec`, which reads OFX_PREC_F16_W) and rejections of OFX_PREC_F16; the extensions of
+                                 OFX_PREC_F16_EPI do not exist in this format (7 | 256 is OFX_EINVAL) */
 
 typedef struct ofx_conv_desc {
     /* input: NHWC fp32, up to two channel segments (torch.cat along C without materialising) */
     const float* in0; int ld0; int c0;
     const float* in1; int ld1; int c1;          /* in1 may be NULL (c1 = 0); with in1, c0 and c1 multiples of 32 (else OFX_EALIGN) */
-    /* weights packed [Cout][Kpad], k = (ky*KW + kx)*(c0+c1) + c, Kpad = K rounded up to 32 */
+    /* weights packed [Cout][Kpad], k = (ky*KW + kx)*(c0+c1) + c, Kpad = K rounded up to 32.  fp32, except under the `_W` precisions,
+       which read the field in their own format: OFX_PREC_F16_W reads it as IEEE halves [Cout][Kpad] (2 bytes per element) */
     const float* w;
     const float* scale;                          /* [Cout] or NULL (=1) */
     const float* shift;                          /* [Cout] or NULL (=0) */
@@ -638,6 +649,11 @@ long ofx_wino44_conv_weight(const float* w_oihw, int Cout, int Cin, float* out);
  * passes d->Cout = that row count and d->nz <= 1 (a row slice or a batched GEMM would read the lo groups from the wrong place;
  * ofx_conv2d returns OFX_EINVAL for nz > 1, and for a precision outside OFX_PREC_FP32 .. OFX_PREC_F16). */
 int ofx_split_conv_weight3(const float* packed, long n_floats, float* out);
+/* Host-side: packed fp32 weights [n_floats] -> IEEE halves [n_floats] (2 * n_floats bytes in `out_halves`), the operand of
+ * OFX_PREC_F16_W and, for the folded weights of ofx_upconv2x_weight, of ofx_upconv2x_prec with that precision.  Round-to-nearest-even,
+ * bit-identical to the kernels' convert: fp16 subnormals are produced (not flushed), a magnitude that rounds beyond 65504 becomes an
+ * infinity, NaN stays NaN.  Returns 0, or OFX_EINVAL for a NULL pointer or n_floats <= 0. */
+int ofx_half_conv_weight(const float* packed, long n_floats, void* out_halves);
 
 /* instance norm statistics over HW per (b,c): mean and 1/sqrt(var+eps) (biased var), NHWC input with rows of ld >= C floats
  * (ld > C: the statistics of a channel slice).  C % 4 == 0, C <= 256, ld % 4 == 0 and x 16-byte aligned: OFX_EALIGN otherwise.

@@ -108,8 +108,11 @@ def _torch_glue() -> bool:
 class ControlNet(UNetTrunk):
     """`controlnet.ControlNet` (inference) on a HIP device.  `precision` / `attention_precision` are the trunk's, as in `UNetModel`;
     the hint stem is exact fp32 in every mode.  `kv_dtype` is the trunk's too: checked and handed to the transformers, whose K/V a
-    ControlNet records and drops (it takes no reference K/V and returns none)."""
+    ControlNet records and drops (it takes no reference K/V and returns none).  `weight_dtype` ("fp32" default, "fp16" with
+    precision="fp16" only) stores the trunk's and the zero convolutions' operands in half, as in `UNetModel`; the hint stem's
+    weights stay fp32."""
     _what = "ControlNet"
+    _fp32_weight_prefixes = ("input_hint_block.",)               # `ops.conv3x3_silu`, exact fp32 in every mode
 
     @staticmethod
     def _layout(cfg):
@@ -123,8 +126,8 @@ class ControlNet(UNetTrunk):
         return [l for blk in self.layout["input"] for l in blk] + list(self.layout["middle"])
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: dict = SD_V15_CONTROLNET, device="cuda", prefix: str = "control_model.",
-                 precision: str = "fp32", attention_precision: str = "fp32", kv_dtype: str = "fp32"):
-        t32 = self._setup(state_dict, cfg, device, prefix, precision, attention_precision, kv_dtype)
+                 precision: str = "fp32", attention_precision: str = "fp32", kv_dtype: str = "fp32", weight_dtype: str = "fp32"):
+        t32 = self._setup(state_dict, cfg, device, prefix, precision, attention_precision, kv_dtype, weight_dtype)
         self.hint_channels = int(self.cfg["hint_channels"])
         self.hint_pad = (self.hint_channels + 3) // 4 * 4
         self.stem_glue = _torch_glue()

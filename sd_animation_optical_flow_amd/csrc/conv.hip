@@ -31,6 +31,10 @@
 //             the epilogue statistics, taken from the fp32 accumulators) and the two GRU gate epilogues (`RaftEngine(precision="fp16")`;
 //             a descriptor asks for these three with OFX_PREC_F16_EPI, OFX_PREC_F16 itself keeps rejecting them as documented);
 //             no flow epilogue, pooled volume, batched GEMM, split-K or paired pipelines.  Range and subnormals: ofx.h.
+//   PREC = 7  PREC = 5 with the WEIGHTS arriving as halves (OFX_PREC_F16_W, ofx_half_conv_weight; `weight_dtype="fp16"` of the SD
+//             models): one 8-byte load per thread and row where PREC = 5 has a 16-byte one, committed to LDS as loaded -- the B-side
+//             converts leave the kernel and the weight stream halves.  Same LDS layout, MFMA loop and A side: the same bits out.
+//             Plain epilogue only.
 //
 // Tiling (64-wide wavefronts): 256 threads = 4 waves per workgroup, a BMxBN output tile, BK = 16 or
 // 32.  Both operands are staged k-contiguous in LDS with a row stride of BK+4 floats (20 / 36), which
@@ -139,12 +143,14 @@ constexpr int f16_occupancy(int BM, int BN, bool norm32 = false) {
 }
 
 template <int BM, int BN, int WM, int WN, int EPI, bool NORM, int BK, int PREC, int KS = 1, bool SK = false, int MODE = 0>
-__global__ __launch_bounds__(256 * KS, PREC == OFX_PREC_F16 ? f16_occupancy(BM, BN, NORM && BK == 32) : (BK == 16 && KS == 1) ? ((PREC == 3 || PREC == 4) ? 2 : (PREC == 0 && BM <= 128 && BN <= 128 && !NORM && EPI != OFX_EPI_FLOW) ? 4 : 3) : 1) void igemm_kernel(const ConvK p) {
+__global__ __launch_bounds__(256 * KS, (PREC == OFX_PREC_F16 || PREC == OFX_PREC_F16_W) ? f16_occupancy(BM, BN, NORM && BK == 32) : (BK == 16 && KS == 1) ? ((PREC == 3 || PREC == 4) ? 2 : (PREC == 0 && BM <= 128 && BN <= 128 && !NORM && EPI != OFX_EPI_FLOW) ? 4 : 3) : 1) void igemm_kernel(const ConvK p) {
     constexpr bool UK = MODE == 1, PATCH = MODE == 2;
     constexpr bool X6 = PREC == 3 || PREC == 4;           // three bf16 pieces per operand, six products
-    constexpr bool F16 = PREC == OFX_PREC_F16;            // one fp16 piece per operand, one product
+    constexpr bool F16W = PREC == OFX_PREC_F16_W;         // fp16 with the weights already halves in memory: 8-byte loads, committed as they are
+    constexpr bool F16 = PREC == OFX_PREC_F16 || F16W;    // one fp16 piece per operand, one product
     static_assert(!F16 || (KS == 1 && !SK && (EPI == OFX_EPI_PLAIN || EPI == kEpiPlainT || EPI == OFX_EPI_GRU_ZR || EPI == OFX_EPI_GRU_Q)),
                   "fp16: the plain and the GRU gate epilogues, one pipeline, no split-K");
+    static_assert(!F16W || (!NORM && (EPI == OFX_EPI_PLAIN || EPI == kEpiPlainT)), "fp16 on half weights: the plain epilogue only");
     // halo patch rows staged per channel slab, rounded up to whole groups of 16: 8x16 patches 12 x 16 / 10 x 18 / 8 x 20 -> 192,
     // 8x8 patches (the 64-row tile) 12 x 8 / 10 x 10 / 8 x 12 -> 112
     // (the 256-row tile: 16x16 patches, 20 x 16 / 18 x 18 / 16 x 20 -> 336)
@@ -233,6 +239,7 @@ __global__ __launch_bounds__(256 * KS, PREC == OFX_PREC_F16 ? f16_occupancy(BM, 
     const int bytes1s = in1 ? p.bytes1 : p.bytes0;
     const __amdgpu_buffer_rsrc_t rsrcw = __builtin_amdgcn_make_buffer_rsrc((void*)wgt, (short)0, p.bytesw, 0x00020000);
     // PREC = 4: the lo x4 groups of the pre-split weights sit behind the [hi x4 | mid x4] groups, 8 bytes per four k (half the offsets)
+    // PREC = 7: the whole matrix is halves -- the same rows at half the byte offsets, half the extent
     const __amdgpu_buffer_rsrc_t rsrcw2 = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)wgt + (PREC == 4 ? p.bytesw : 0)), (short)0, p.bytesw >> 1, 0x00020000);
     constexpr int kOOB = 0x7FFFFFF0;
 
@@ -300,7 +307,7 @@ __global__ __launch_bounds__(256 * KS, PREC == OFX_PREC_F16 ? f16_occupancy(BM, 
     }
 
     if constexpr (PATCH) {
-        static_assert(!PATCH || (PREC <= 5 && KS == 1 && ((BM == 128 && (WM == 64 || WM == 32) && BK == 16 && !SK) || (PREC == 0 && BM == 64 && WM == 32 && BK == 32) ||
+        static_assert(!PATCH || ((PREC <= 5 || F16W) && KS == 1 && ((BM == 128 && (WM == 64 || WM == 32) && BK == 16 && !SK) || (PREC == 0 && BM == 64 && WM == 32 && BK == 32) ||
                                                          (F16 && BM == 64 && WM == 32 && BK == 16) ||
                                                          (PREC == 0 && BM == 256 && WM == 64 && BK == 16 && !SK))),
                       "patch mode: 128-row tiles with 16-channel slabs (fp32, split bf16 or fp16), the fp32 64x64 small-grid tile with 32-channel slabs (split-K allowed), or the fp16 64x64 tile with 16-channel slabs");
@@ -455,7 +462,8 @@ __global__ __launch_bounds__(256 * KS, PREC == OFX_PREC_F16 ? f16_occupancy(BM, 
         auto b_issue = [&]() __attribute__((always_inline)) {
             const int so = (itap * p.cin + icb * BK) * 4;
 #define OFX_B_ISSUE(i) \
-    if constexpr (B_PER > i) { v4i t = __builtin_amdgcn_raw_buffer_load_b128(rsrcw, browb[i], so, 0); rb##i = *reinterpret_cast<float4*>(&t); \
+    if constexpr (B_PER > i && F16W) { typedef int v2i_ __attribute__((ext_vector_type(2))); v2i_ u = __builtin_amdgcn_raw_buffer_load_b64(rsrcw2, browb[i] >> 1, so >> 1, 0); rl##i = *reinterpret_cast<float2*>(&u); } \
+    else if constexpr (B_PER > i) { v4i t = __builtin_amdgcn_raw_buffer_load_b128(rsrcw, browb[i], so, 0); rb##i = *reinterpret_cast<float4*>(&t); \
         if constexpr (PREC == 4) { typedef int v2i_ __attribute__((ext_vector_type(2))); v2i_ u = __builtin_amdgcn_raw_buffer_load_b64(rsrcw2, browb[i] >> 1, so >> 1, 0); rl##i = *reinterpret_cast<float2*>(&u); } }
             OFX_B_ISSUE(0) OFX_B_ISSUE(1) OFX_B_ISSUE(2) OFX_B_ISSUE(3)
 #undef OFX_B_ISSUE
@@ -479,7 +487,9 @@ __global__ __launch_bounds__(256 * KS, PREC == OFX_PREC_F16 ? f16_occupancy(BM, 
 #define OFX_B_COMMIT(i) \
     if constexpr (B_PER > i) { \
         const int o = (r0 + RPG * i) * ROWB + kq * 8; \
-        if constexpr (F16) { \
+        if constexpr (F16W) { \
+            *reinterpret_cast<float2*>(b_hi + o) = rl##i; \
+        } else if constexpr (F16) { \
             cvt_store(b_hi + o, rb##i); \
         } else if constexpr (PREC == 2) { \
             *reinterpret_cast<float2*>(b_hi + o) = make_float2(rb##i.x, rb##i.y); \
@@ -727,7 +737,8 @@ __global__ __launch_bounds__(256 * KS, PREC == OFX_PREC_F16 ? f16_occupancy(BM, 
             okbits >>= 16;   // the chunk just issued becomes the one the next commit sees
         }
 #define OFX_B_ISSUE(i) \
-    if constexpr (B_PER > i) { v4i t = __builtin_amdgcn_raw_buffer_load_b128(rsrcw, voffb[i], 0, 0); rb##i = *reinterpret_cast<float4*>(&t); \
+    if constexpr (B_PER > i && F16W) { typedef int v2i_ __attribute__((ext_vector_type(2))); v2i_ u = __builtin_amdgcn_raw_buffer_load_b64(rsrcw2, voffb[i] >> 1, 0, 0); rl##i = *reinterpret_cast<float2*>(&u); } \
+    else if constexpr (B_PER > i) { v4i t = __builtin_amdgcn_raw_buffer_load_b128(rsrcw, voffb[i], 0, 0); rb##i = *reinterpret_cast<float4*>(&t); \
         if constexpr (PREC == 4) { typedef int v2i_ __attribute__((ext_vector_type(2))); v2i_ u = __builtin_amdgcn_raw_buffer_load_b64(rsrcw2, voffb[i] >> 1, 0, 0); rl##i = *reinterpret_cast<float2*>(&u); } }
         OFX_B_ISSUE(0) OFX_B_ISSUE(1) OFX_B_ISSUE(2) OFX_B_ISSUE(3)
 #undef OFX_B_ISSUE
@@ -786,7 +797,8 @@ __global__ __launch_bounds__(256 * KS, PREC == OFX_PREC_F16 ? f16_occupancy(BM, 
 #pragma unroll
             for (int i = 0; i < A_PER; ++i) cvt_store(a0 + (r0 + RPG * i) * ROWB + kq * 8, norm_a(i));
 #define OFX_B_COMMIT(i) \
-    if constexpr (B_PER > i) cvt_store(b0 + (r0 + RPG * i) * ROWB + kq * 8, rb##i);
+    if constexpr (B_PER > i && F16W) *reinterpret_cast<float2*>(b0 + (r0 + RPG * i) * ROWB + kq * 8) = rl##i; \
+    else if constexpr (B_PER > i) cvt_store(b0 + (r0 + RPG * i) * ROWB + kq * 8, rb##i);
             OFX_B_COMMIT(0) OFX_B_COMMIT(1) OFX_B_COMMIT(2) OFX_B_COMMIT(3)
 #undef OFX_B_COMMIT
         } else if constexpr (X6) {
@@ -1275,16 +1287,21 @@ __global__ __launch_bounds__(256 * KS, PREC == OFX_PREC_F16 ? f16_occupancy(BM, 
 constexpr bool tile_has_patch(int BM, int BN, int BK, int PREC, int KS, bool SK) {
     return KS == 1 && ((PREC == 0 && BM == 128 && BK == 16 && !SK && (BN == 64 || BN == 96 || BN == 128 || BN == 192)) || (PREC == 0 && BM == 64 && BN == 64 && BK == 32) ||
                        (PREC == 0 && BM == 256 && BN == 64 && BK == 16 && !SK) ||
-                       ((PREC == 1 || PREC == 2 || PREC == 3 || PREC == 4 || PREC == OFX_PREC_F16) && BM == 128 && BK == 16 && !SK && (BN == 64 || BN == 128)) ||
-                       (PREC == OFX_PREC_F16 && BM == 64 && BN == 64 && BK == 16 && !SK));   // fp16: also the 64x64 tile, on 8x8 patches
+                       ((PREC == 1 || PREC == 2 || PREC == 3 || PREC == 4 || PREC == OFX_PREC_F16 || PREC == OFX_PREC_F16_W) && BM == 128 && BK == 16 && !SK && (BN == 64 || BN == 128)) ||
+                       ((PREC == OFX_PREC_F16 || PREC == OFX_PREC_F16_W) && BM == 64 && BN == 64 && BK == 16 && !SK));   // fp16: also the 64x64 tile, on 8x8 patches
 }
-constexpr bool tile_has_scalar(int BN, int PREC) { return (PREC == 0 && BN != 192) || PREC == OFX_PREC_F16; }   // the 128x192 tile measured 0.8 % slower with scalar chunk coordinates
+constexpr bool tile_has_scalar(int BN, int PREC) { return (PREC == 0 && BN != 192) || PREC == OFX_PREC_F16 || PREC == OFX_PREC_F16_W; }   // the 128x192 tile measured 0.8 % slower with scalar chunk coordinates
 
 template <int BM, int BN, int WM, int WN, int BK, int PREC, int KS, bool SK, int UK>
 int launch_tile_uk(const ConvK& k, int epi, bool norm, int nz, hipStream_t s, hipEvent_t ev) {
     dim3 grid((unsigned)(k.mtiles * k.ntiles * (k.ksplit > 1 ? k.ksplit : 1)), (unsigned)nz, 1);
     dim3 block(256 * KS, 1, 1);
-    if constexpr (PREC == OFX_PREC_F16) {   // the plain and the GRU gate epilogues (conv_validate has rejected the rest): nothing else is instantiated
+    if constexpr (PREC == OFX_PREC_F16_W) {   // half weights: the plain epilogue alone (conv_validate has rejected the rest)
+        if (epi != OFX_EPI_PLAIN || norm) return OFX_EINVAL;
+        if (k.act >= OFX_ACT_SIGMOID) OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, kEpiPlainT, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
+        else OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_PLAIN, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
+        return ofx_launch_status();
+    } else if constexpr (PREC == OFX_PREC_F16) {   // the plain and the GRU gate epilogues (conv_validate has rejected the rest): nothing else is instantiated
         if (epi == OFX_EPI_GRU_ZR && !norm) OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_GRU_ZR, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
         else if (epi == OFX_EPI_GRU_Q && !norm) OFX_LAUNCH((igemm_kernel<BM, BN, WM, WN, OFX_EPI_GRU_Q, false, BK, PREC, KS, SK, UK>), grid, block, s, ev, k);
         else if (epi != OFX_EPI_PLAIN || (norm && k.act >= OFX_ACT_SIGMOID)) return OFX_EINVAL;
@@ -1355,6 +1372,9 @@ const TileInst kTiles[] = {
     // forced tile (tile = 16e6 + ...) or OFX_CONV_F16_BK=16
     OFX_TILE(128, 128, 64, 64, 16, 5, 1, false), OFX_TILE(128, 64, 64, 32, 16, 5, 1, false),  OFX_TILE(64, 64, 32, 32, 16, 5, 1, false),
     OFX_TILE(128, 128, 64, 64, 32, 5, 1, false), OFX_TILE(128, 64, 64, 32, 32, 5, 1, false),  OFX_TILE(64, 64, 32, 32, 32, 5, 1, false),
+    // fp16 on weights stored in half (OFX_PREC_F16_W; `weight_dtype="fp16"` of the SD models): the same six tiles, plain epilogue only
+    OFX_TILE(128, 128, 64, 64, 16, 7, 1, false), OFX_TILE(128, 64, 64, 32, 16, 7, 1, false),  OFX_TILE(64, 64, 32, 32, 16, 7, 1, false),
+    OFX_TILE(128, 128, 64, 64, 32, 7, 1, false), OFX_TILE(128, 64, 64, 32, 32, 7, 1, false),  OFX_TILE(64, 64, 32, 32, 32, 7, 1, false),
 #endif
     // BK = 16 keeps LDS at 40 KB and registers under 128 for the 128x128 tile -> 4 workgroups per CU (3 for 128x192); the
     // extra resident wave per SIMD hides the commit/barrier/issue phases better than a longer chunk does
@@ -1426,7 +1446,7 @@ int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, C
     const int nz = d->nz > 1 ? d->nz : 1, cin = d->c0 + d->c1;
     const int K = d->KH * d->KW * cin, Kpad = ((K + kKAlign - 1) / kKAlign) * kKAlign;
     const long M = (long)d->B * d->Hout * d->Wout;
-    const bool want_stats = x.stats_rows != nullptr, pool = x.pool.out != nullptr, fp32 = d->precision == OFX_PREC_FP32, f16 = d->precision == OFX_PREC_F16 || d->precision == OFX_PREC_F16_EPI;
+    const bool want_stats = x.stats_rows != nullptr, pool = x.pool.out != nullptr, fp32 = d->precision == OFX_PREC_FP32, f16 = d->precision == OFX_PREC_F16 || d->precision == OFX_PREC_F16_EPI || d->precision == OFX_PREC_F16_W;
     p->name = nz > 1 ? "igemm_corr_volume"
               : d->epi == OFX_EPI_GRU_ZR ? "igemm_conv_gru_zr"
               : d->epi == OFX_EPI_GRU_Q  ? "igemm_conv_gru_q"
@@ -1550,7 +1570,8 @@ int conv_plan(const ofx_conv_desc* d, const ConvExtra& x, const ConvKnobs& kn, C
     } else if (patch && !whole) {
         mtiles = d->B * ((d->Hin + ph - 1) / ph) * ((d->Win + 15) / 16);
     }
-    int prec = f16 ? OFX_PREC_F16 : d->precision;   // (OFX_PREC_F16_EPI is the same arithmetic and the same kernels: it only widens what conv_validate lets through)
+    // (OFX_PREC_F16_W: the same plan in every other field -- `f16` above covers it -- on the kernels that read half weights)
+    int prec = d->precision == OFX_PREC_F16_W ? OFX_PREC_F16_W : f16 ? OFX_PREC_F16 : d->precision;   // (OFX_PREC_F16_EPI is the same arithmetic and the same kernels: it only widens what conv_validate lets through)
     if (!fp32) {
 #ifdef OFX_CONV_LEAN
         return OFX_EINVAL;
@@ -1644,14 +1665,15 @@ int conv_validate(const ofx_conv_desc* d, const ConvExtra& x, long* split_rows) 
     }
     if (d->addend) OFX_REQUIRE(d->ldadd >= d->Cout, OFX_EINVAL);
     const int nz = d->nz > 1 ? d->nz : 1;
-    OFX_REQUIRE((d->precision >= OFX_PREC_FP32 && d->precision <= OFX_PREC_F16) || d->precision == OFX_PREC_F16_EPI, OFX_EINVAL);
+    OFX_REQUIRE((d->precision >= OFX_PREC_FP32 && d->precision <= OFX_PREC_F16) || d->precision == OFX_PREC_F16_EPI || d->precision == OFX_PREC_F16_W, OFX_EINVAL);
     // The fp16 arithmetic serves one convolution: no flow epilogue, pooled volume, batched GEMM, split-K workspace or paired
     // pipelines (none of those kernels is instantiated in it).  Under OFX_PREC_F16 itself the gate epilogues, the fused norm on load
     // and the epilogue statistics stay rejected as well, as that value has always documented (callers written against it keep what
     // they were promised); OFX_PREC_F16_EPI is the same arithmetic with those three let through (the flow network's descriptors)
-    if (d->precision == OFX_PREC_F16 || d->precision == OFX_PREC_F16_EPI)
+    // OFX_PREC_F16_W (the same kernels on weights stored in half) rejects exactly what OFX_PREC_F16 does
+    if (d->precision == OFX_PREC_F16 || d->precision == OFX_PREC_F16_EPI || d->precision == OFX_PREC_F16_W)
         OFX_REQUIRE(d->epi != OFX_EPI_FLOW && !x.pool.out && nz == 1 && !d->splitk_ws && d->tile < 2000000000, OFX_EINVAL);
-    if (d->precision == OFX_PREC_F16) OFX_REQUIRE(d->epi == OFX_EPI_PLAIN && !d->nmean && !x.stats_rows, OFX_EINVAL);
+    if (d->precision == OFX_PREC_F16 || d->precision == OFX_PREC_F16_W) OFX_REQUIRE(d->epi == OFX_EPI_PLAIN && !d->nmean && !x.stats_rows, OFX_EINVAL);
     // OFX_PREC_BF16X6_W: the kernel finds the lo pieces of the pre-split matrix at w + Cout * Kpad * 4 -- true only for the WHOLE matrix
     // `ofx_split_conv_weight3` converted (Cout = its row count) of ONE problem; a batched GEMM advances w per problem
     if (d->precision == OFX_PREC_BF16X6_W) OFX_REQUIRE(nz == 1, OFX_EINVAL);
@@ -1855,6 +1877,42 @@ extern "C" int ofx_split_conv_weight3(const float* packed, long n, float* out) {
             o[2 * g + 4 + i] = mid;
             o2[g + i] = bf16_rne(r2);
         }
+    return 0;
+}
+
+// packed fp32 weights [n] -> IEEE halves [n], round-to-nearest-even as v_cvt_pk_f16_f32 rounds them (subnormals kept, overflow to
+// infinity, NaN stays NaN): the operand of OFX_PREC_F16_W.  Integer arithmetic on the bit patterns, so that no host compiler flag or
+// rounding mode can make it differ from the device's convert.
+extern "C" int ofx_half_conv_weight(const float* packed, long n, void* out_halves) {
+    if (!packed || !out_halves || n <= 0) return OFX_EINVAL;
+    uint16_t* o = reinterpret_cast<uint16_t*>(out_halves);
+    for (long i = 0; i < n; ++i) {
+        uint32_t u;
+        memcpy(&u, &packed[i], 4);
+        const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
+        const uint32_t a = u & 0x7FFFFFFFu;
+        uint16_t h;
+        if (a > 0x7F800000u) {
+            h = (uint16_t)(0x7E00u | ((a >> 13) & 0x3FFu));          // NaN: quiet, payload kept
+        } else if (a >= 0x47800000u) {
+            h = 0x7C00u;                                              // 2^16 and beyond (infinity included)
+        } else if (a >= 0x38800000u) {
+            // normal half: rebias the exponent (127 -> 15), drop 13 mantissa bits to nearest even; a carry out of the mantissa
+            // runs into the exponent, 65520 and above reaching the pattern of infinity
+            const uint32_t r = a - 0x38000000u;
+            h = (uint16_t)((r + 0xFFFu + ((r >> 13) & 1u)) >> 13);
+        } else if (a < 0x33000000u) {
+            h = 0;                                                    // below 2^-25: zero (2^-25 itself is a tie, to even = 0, below)
+        } else {
+            // subnormal half: multiples of 2^-24.  The 24-bit significand shifted right by 126 - e (14 .. 25 bits), nearest even
+            const int e = (int)(a >> 23);
+            const uint32_t m = (a & 0x7FFFFFu) | 0x800000u;
+            const int sh = 126 - e;
+            const uint32_t q = m >> sh, rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1);
+            h = (uint16_t)(q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u));
+        }
+        o[i] = (uint16_t)(sign | h);
+    }
     return 0;
 }
 

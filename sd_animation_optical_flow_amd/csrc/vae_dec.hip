@@ -45,9 +45,14 @@ struct UpK {
 // bytes written 8 bytes per float4 slot; a fragment is one ds_read_b128 (lane l: row l & 31, the eight consecutive k of group
 // l >> 5 -- the same on both operands), ONE v_mfma_f32_32x32x16_f16 per (i, j) and 16 k, fp32 accumulate.  Loads, guards, pipeline
 // and epilogue are the fp32 form's.
+// PREC = OFX_PREC_F16_W: the same with the folded weights stored in half (ofx_half_conv_weight): 8-byte loads of four halves,
+// committed as loaded -- the same LDS contents, so the same bits out.
+// (the 128 x 64 tile on half weights asks for the five waves per SIMD its fp32-weight twin reaches on its own: left alone it compiles
+// to 8 registers more and four waves; every other instantiation keeps the default)
 template <int BN, int PREC = OFX_PREC_FP32>
-__global__ __launch_bounds__(256) void upconv2x_kernel(const UpK p) {
-    constexpr bool F16 = PREC == OFX_PREC_F16;
+__global__ __launch_bounds__(256, (PREC == OFX_PREC_F16_W && BN == 64) ? 5 : 1) void upconv2x_kernel(const UpK p) {
+    constexpr bool F16W = PREC == OFX_PREC_F16_W;     // the folded weights are halves in memory: 8-byte loads, committed as they are
+    constexpr bool F16 = PREC == OFX_PREC_F16 || F16W;
     static_assert(F16 || PREC == OFX_PREC_FP32, "fp32 or fp16");
     constexpr int BM = 128, WM = 64, WN = BN / 2, TM = WM / 32, TN = WN / 32;
     constexpr int BK = F16 ? kBKh : kBK;
@@ -83,9 +88,13 @@ __global__ __launch_bounds__(256) void upconv2x_kernel(const UpK p) {
     }
     const size_t wrow = (size_t)4 * p.Cin;            // floats per output channel of one parity
     const float* wpar = p.w + (size_t)par * p.Cout * wrow;
+    const _Float16* wparh = reinterpret_cast<const _Float16*>(p.w) + (size_t)par * p.Cout * wrow;   // F16W: the same element, two bytes each
 
-    f32x4 ra[A_PER], rb[B_PER];    // native vectors: a select between two of them stays in registers
+    typedef float f32x2_ __attribute__((ext_vector_type(2)));
+    f32x4 ra[A_PER], rb[F16W ? 1 : B_PER];    // native vectors: a select between two of them stays in registers
+    f32x2_ rh[F16W ? B_PER : 1];              // half weights: four halves per slot
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    const f32x2_ zero2 = {0.f, 0.f};
     // branch-free: a lane whose float4 does not exist reads the first 16 bytes of the operand instead and keeps zeros
     auto load = [&](int t, int cb) __attribute__((always_inline)) {
         const int ty = t >> 1, tx = t & 1;
@@ -102,8 +111,13 @@ __global__ __launch_bounds__(256) void upconv2x_kernel(const UpK p) {
         for (int i = 0; i < B_PER; ++i) {
             const int n = n0 + r0 + RPG * i;
             const bool ok = cok && n < p.Cout;
-            const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? wpar + (size_t)n * wrow + (size_t)t * p.Cin + c : p.w);
-            rb[i] = ok ? v : zero4;
+            if constexpr (F16W) {   // the same element index, two bytes per element (Cin % 4 == 0: 8-byte aligned)
+                const f32x2_ v = *reinterpret_cast<const f32x2_*>(ok ? wparh + (size_t)n * wrow + (size_t)t * p.Cin + c : reinterpret_cast<const _Float16*>(p.w));
+                rh[i] = ok ? v : zero2;
+            } else {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? wpar + (size_t)n * wrow + (size_t)t * p.Cin + c : p.w);
+                rb[i] = ok ? v : zero4;
+            }
         }
     };
     auto commit = [&](float* st) __attribute__((always_inline)) {
@@ -115,7 +129,10 @@ __global__ __launch_bounds__(256) void upconv2x_kernel(const UpK p) {
 #pragma unroll
             for (int i = 0; i < A_PER; ++i) *reinterpret_cast<f16x4*>(a0 + (r0 + RPG * i) * kRowBh + kq * 8) = __builtin_convertvector(ra[i], f16x4);
 #pragma unroll
-            for (int i = 0; i < B_PER; ++i) *reinterpret_cast<f16x4*>(b0 + (r0 + RPG * i) * kRowBh + kq * 8) = __builtin_convertvector(rb[i], f16x4);
+            for (int i = 0; i < B_PER; ++i) {
+                if constexpr (F16W) *reinterpret_cast<f32x2_*>(b0 + (r0 + RPG * i) * kRowBh + kq * 8) = rh[i];
+                else *reinterpret_cast<f16x4*>(b0 + (r0 + RPG * i) * kRowBh + kq * 8) = __builtin_convertvector(rb[i], f16x4);
+            }
         } else {
 #pragma unroll
             for (int i = 0; i < A_PER; ++i) *reinterpret_cast<f32x4*>(st + (r0 + RPG * i) * kLDK + kq * 4) = ra[i];
@@ -296,11 +313,11 @@ extern "C" long ofx_upconv2x_weight(const float* w, int Cout, int Cin, float* ou
 }
 
 extern "C" int ofx_upconv2x_bn(int Cout, int precision) {
-    if (Cout <= 0 || (precision != OFX_PREC_FP32 && precision != OFX_PREC_F16)) return OFX_EINVAL;
+    if (Cout <= 0 || (precision != OFX_PREC_FP32 && precision != OFX_PREC_F16 && precision != OFX_PREC_F16_W)) return OFX_EINVAL;
     return Cout <= 64 ? 64 : 128;
 }
 
-// the checks and the launch of both entry points; precision is OFX_PREC_FP32 or OFX_PREC_F16 here
+// the checks and the launch of both entry points; precision is OFX_PREC_FP32, OFX_PREC_F16 or OFX_PREC_F16_W (w: halves) here
 static int upconv2x_checked(const float* x, const float* w, const float* bias, float* out, int ldo, int B, int H, int W, int Cin,
                             int Cout, int precision, void* stream) {
     OFX_REQUIRE(x && w && out, OFX_EINVAL);
@@ -314,7 +331,7 @@ static int upconv2x_checked(const float* x, const float* w, const float* bias, f
     k.x = x; k.w = w; k.bias = bias; k.out = out;
     k.B = B; k.H = H; k.W = W; k.Cin = Cin; k.Cout = Cout; k.ldo = ldo;
     k.M = (int)M;
-    const bool f16 = precision == OFX_PREC_F16;
+    const bool f16w = precision == OFX_PREC_F16_W, f16 = precision == OFX_PREC_F16 || f16w;
     const int bk = f16 ? kBKh : kBK;
     k.cchunks = (Cin + bk - 1) / bk;
     const int bn = ofx_upconv2x_bn(Cout, precision);
@@ -325,7 +342,10 @@ static int upconv2x_checked(const float* x, const float* w, const float* bias, f
     OfxProfScope prof(f16 ? "upconv2x_f16" : "upconv2x", s);
     prof.flops(2.0 * 4.0 * (double)M * Cout * 4.0 * Cin);
     dim3 grid((unsigned)(mtiles * k.ntiles), 4, 1), block(256, 1, 1);
-    if (f16) {
+    if (f16w) {
+        if (bn == 64) hipLaunchKernelGGL((upconv2x_kernel<64, OFX_PREC_F16_W>), grid, block, 0, s, k);
+        else hipLaunchKernelGGL((upconv2x_kernel<128, OFX_PREC_F16_W>), grid, block, 0, s, k);
+    } else if (f16) {
         if (bn == 64) hipLaunchKernelGGL((upconv2x_kernel<64, OFX_PREC_F16>), grid, block, 0, s, k);
         else hipLaunchKernelGGL((upconv2x_kernel<128, OFX_PREC_F16>), grid, block, 0, s, k);
     } else {
@@ -342,7 +362,7 @@ extern "C" int ofx_upconv2x(const float* x, const float* w, const float* bias, f
 
 extern "C" int ofx_upconv2x_prec(const float* x, const float* w, const float* bias, float* out, int ldo, int B, int H, int W, int Cin,
                                  int Cout, int precision, void* stream) {
-    OFX_REQUIRE(precision == OFX_PREC_FP32 || precision == OFX_PREC_F16, OFX_EINVAL);
+    OFX_REQUIRE(precision == OFX_PREC_FP32 || precision == OFX_PREC_F16 || precision == OFX_PREC_F16_W, OFX_EINVAL);
     if (precision == OFX_PREC_FP32) return ofx_upconv2x(x, w, bias, out, ldo, B, H, W, Cin, Cout, stream);
     return upconv2x_checked(x, w, bias, out, ldo, B, H, W, Cin, Cout, precision, stream);
 }

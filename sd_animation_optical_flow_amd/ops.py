@@ -341,11 +341,22 @@ def split_conv_weight3(w_packed: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def half_conv_weight(w_packed: torch.Tensor) -> torch.Tensor:
+    """Packed fp32 weights (CPU; `pack_conv_weight`, or the folded operand of `upconv2x_weight`) -> the same shape in float16,
+    rounded to nearest even exactly as the fp16 kernels round a weight when they stage it (ofx_half_conv_weight: subnormals kept,
+    beyond +-65504 an infinity).  Feed it to conv2d_nhwc(..., precision="fp16_w") / upconv2x(..., precision="fp16")."""
+    w = w_packed.detach().to(torch.float32).contiguous().cpu()
+    out = torch.empty(w.shape, dtype=torch.float16)
+    check(_lib.lib().ofx_half_conv_weight(C.c_void_p(w.data_ptr()), w.numel(), C.c_void_p(out.data_ptr())), "ofx_half_conv_weight")
+    return out
+
+
 # conv2d_nhwc(precision=) -> OFX_PREC_*.  *_w: the weight comes from split_conv_weight / split_conv_weight3.  "fp16": both operands
 # rounded to half as they are staged, fp32 accumulate (OFX_PREC_F16; plain fp32 [Cout, Kpad] weights, fp32 activations and epilogue;
 # no nmean / stats_part / splitk_ws).  "fp16_epi": the same arithmetic with nmean and stats_part served (OFX_PREC_F16_EPI, the flow
-# network's encoder layers under `RaftEngine(precision="fp16")`)
-CONV_PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16x3_w": 2, "bf16x6": 3, "bf16x6_w": 4, "fp16": 5, "fp16_epi": 5 | 256}
+# network's encoder layers under `RaftEngine(precision="fp16")`).  "fp16_w": "fp16" on weights already stored in half
+# (OFX_PREC_F16_W; a float16 [Cout, Kpad] from half_conv_weight, staged as it is: bit-identical to "fp16" on the fp32 weights)
+CONV_PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16x3_w": 2, "bf16x6": 3, "bf16x6_w": 4, "fp16": 5, "fp16_epi": 5 | 256, "fp16_w": 7}
 
 
 def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout: int, *, stride: int = 1,
@@ -365,7 +376,8 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
     F(4x4,3x3) kernel where its grid pays (tile = TILE_WINOGRAD4 forces it), `res`, `nmean` / `nrstd` and `stats_part` included.  `out` [B,Hout,Wout,C >= out_off + cout]: write channels
     [out_off, out_off + cout) of it.  `stats_part` (f32 on the device): run ofx_conv2d_stats, which leaves the per-channel
     (sum, sum of squares) partials of the outputs there when the launch can produce them ([B][rows][cout][2]; see inorm_finalize).
-    `precision`: a key of CONV_PRECISIONS (default exact fp32).
+    `precision`: a key of CONV_PRECISIONS (default exact fp32).  "fp16_w" takes a float16 `w_packed` (half_conv_weight) and every
+    other precision a float32 one: a mismatch either way is a RuntimeError before any launch.
     Returns [B,Hout,Wout,cout], or `out`; with `stats_part`, (that, rows per image), rows = 0 when none were produced."""
     ph, pw = (kh // 2, kw // 2) if pad is None else pad
     if ph < 0 or pw < 0:            # (ofx_conv2d: OFX_EINVAL) padding is rows / columns of zeros above and left of the image, never a crop
@@ -377,7 +389,7 @@ def conv2d_nhwc(x: torch.Tensor, w_packed: torch.Tensor, kh: int, kw: int, cout:
     if x2 is not None:
         x2 = _chk(x2, "x2", torch.float32)
         d.in1, d.ld1, d.c1 = x2.data_ptr(), x2.shape[-1], x2.shape[-1]
-    wp = _chk(w_packed, "w_packed", torch.float32)
+    wp = _chk(w_packed, "w_packed", torch.float16 if precision == "fp16_w" else torch.float32)
     d.w = wp.data_ptr()
     d.scale = 0 if scale is None else _chk(scale, "scale", torch.float32).data_ptr()
     d.shift = 0 if shift is None else _chk(shift, "shift", torch.float32).data_ptr()
@@ -856,10 +868,13 @@ def upconv2x(x: torch.Tensor, w_folded: torch.Tensor, bias: Optional[torch.Tenso
     """conv3x3(pad 1)(nearest 2x upsample of x) + bias in one kernel that never forms the upsampled map: x [B,H,W,Cin],
     w_folded [4,Cout,4,Cin] from `upconv2x_weight` (on the device) -> [B,2H,2W,Cout].  `out` [B,2H,2W,C >= out_off + Cout]: write
     channels [out_off, out_off + Cout) of it (a strided row).  precision: "fp32" (default, `ofx_upconv2x`) or "fp16"
-    (`ofx_upconv2x_prec`: both operands rounded to half as they are staged, fp32 accumulation); anything else is a ValueError."""
+    (`ofx_upconv2x_prec`: both operands rounded to half as they are staged, fp32 accumulation); anything else is a ValueError.
+    Under "fp16" a float16 `w_folded` (`half_conv_weight` of the folded operand) is read as it is (OFX_PREC_F16_W), bit-identical
+    to the float32 operand it was rounded from; a float16 `w_folded` under "fp32" is a RuntimeError before any launch."""
     check_upconv_precision(precision)                              # before a device is touched
     x = _chk(x, "x", torch.float32)
-    w = _chk(w_folded, "w_folded", torch.float32)
+    half_w = precision == "fp16" and isinstance(w_folded, torch.Tensor) and w_folded.dtype == torch.float16
+    w = _chk(w_folded, "w_folded", torch.float16 if half_w else torch.float32)
     if x.dim() != 4 or w.dim() != 4 or w.shape[0] != 4 or w.shape[2] != 4 or w.shape[3] != x.shape[3]:
         raise RuntimeError(f"upconv2x: x [B,H,W,Cin] and w_folded [4,Cout,4,Cin] expected, got {tuple(x.shape)} and {tuple(w.shape)}")
     B, H, W, ci = x.shape
@@ -876,8 +891,8 @@ def upconv2x(x: torch.Tensor, w_folded: torch.Tensor, bias: Optional[torch.Tenso
     if precision == "fp32":
         check(_lib.lib().ofx_upconv2x(_ptr(x), _ptr(w), _ptr(b), po, out.shape[3], B, H, W, ci, co, _stream()), "ofx_upconv2x")
     else:
-        check(_lib.lib().ofx_upconv2x_prec(_ptr(x), _ptr(w), _ptr(b), po, out.shape[3], B, H, W, ci, co, UPCONV_PRECISIONS[precision],
-                                           _stream()), "ofx_upconv2x_prec")
+        check(_lib.lib().ofx_upconv2x_prec(_ptr(x), _ptr(w), _ptr(b), po, out.shape[3], B, H, W, ci, co,
+                                           CONV_PRECISIONS["fp16_w"] if half_w else UPCONV_PRECISIONS[precision], _stream()), "ofx_upconv2x_prec")
     return out
 
 

@@ -61,7 +61,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .modelbase import DeviceModel, check_activation_bytes, env_flag, is_f32_cuda, load_tensors, random_tensors, wb
+from .modelbase import DeviceModel, check_activation_bytes, check_weight_dtype, env_flag, is_f32_cuda, load_tensors, random_tensors, wb
 
 FUSED_HEAD_SIZES = (40, 64, 80, 128, 160)      # ofx_attention_flash_ok (csrc/attn_flash.hip)
 # `precision=` of SpatialTransformer / UNetModel: the arithmetic of every `ops.conv2d_nhwc` contraction (weights stay plain fp32)
@@ -210,11 +210,15 @@ def plan_kv_route(mode: str, dtypes: Sequence, ref_layout: Sequence[bool], B: in
 
 
 class SpatialTransformer(DeviceModel):
-    """`ldm.modules.attention.SpatialTransformer` (use_linear=False, inference) on a HIP device."""
+    """`ldm.modules.attention.SpatialTransformer` (use_linear=False, inference) on a HIP device.  `weight_dtype`: "fp32" (default)
+    or "fp16" (with precision="fp16" only): `proj_in` / `proj_out` and every Linear are stored in half and read by the same fp16
+    kernels, bit-identical results; norm scales and biases stay fp32 (`modelbase.DeviceModel`)."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], n_heads: int, d_head: int, device="cuda", prefix: str = "",
-                 use_linear: bool = False, precision: str = "fp32", attention_precision: str = "fp32", kv_dtype: str = "fp32"):
+                 use_linear: bool = False, precision: str = "fp32", attention_precision: str = "fp32", kv_dtype: str = "fp32",
+                 weight_dtype: str = "fp32"):
         self.precision = check_precision(precision)                # before the checkpoint is looked at or a device asked for
+        self.weight_dtype = check_weight_dtype(weight_dtype, self.precision)   # storage of the GEMM operands (`DeviceModel`)
         self.attention_precision = ops.check_attention_precision(attention_precision, "attention_precision")
         self.kv_dtype = ops.check_kv_dtype(kv_dtype)
         self.kv_concat = _kv_concat()
@@ -415,13 +419,13 @@ class SpatialTransformer(DeviceModel):
         # proj_in / proj_out stay direct calls with constant keys: this forward is host-enqueue bound at the UNet's sizes, and
         # `_conv` would add two name lookups to each (profiles/r30_model_base_rate.txt was measured with these lines)
         t = ops.conv2d_nhwc(t, self.w["proj_in.weight"], 1, 1, self.inner, shift=self.w["proj_in.bias"],
-                            precision=self.precision).view(B, N, self.inner)
+                            precision=self._precision_of(self.w["proj_in.weight"])).view(B, N, self.inner)
         kv_hists = []
         for i in range(self.depth):
             t, kv = self._block(i, t, ctxs[i], ref)
             kv_hists.append(kv)
         out = ops.conv2d_nhwc(t.view(B, h, w, self.inner), self.w["proj_out.weight"], 1, 1, self.in_channels,
-                              shift=self.w["proj_out.bias"], addend=x, precision=self.precision)
+                              shift=self.w["proj_out.bias"], addend=x, precision=self._precision_of(self.w["proj_out.weight"]))
         return out, kv_hists
 
     @torch.no_grad()

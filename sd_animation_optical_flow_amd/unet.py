@@ -58,7 +58,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .modelbase import DeviceModel, check_activation_bytes, env_flag, is_f32_cuda, load_tensors, pad_channels4, random_tensors, wb
+from .modelbase import DeviceModel, check_activation_bytes, check_weight_dtype, env_flag, is_f32_cuda, load_tensors, pad_channels4, random_tensors, wb
 from .transformer import FUSED_HEAD_SIZES, MODEL_PRECISIONS, SpatialTransformer, check_precision, plan_reference_kv, spatial_transformer_tensors
 
 # `unet_config` of guided_ldm_inpaint_v15.yaml (in_channels 9) / guided_ldm_v15.yaml (in_channels 4)
@@ -217,13 +217,16 @@ class UNetTrunk(DeviceModel):
     def _tensors(c):
         return unet_tensors(c)
 
+    _fp32_weight_prefixes: Tuple[str, ...] = ()                   # 4-D weights that no `ofx_conv2d` launch reads, by key prefix
+
     def _trunk_layers(self) -> List[tuple]:
         return _layers(self.layout)
 
     def _setup(self, state_dict: Dict[str, torch.Tensor], cfg: dict, device, prefix: str, precision: str,
-               attention_precision: str, kv_dtype: str = "fp32") -> Dict[str, torch.Tensor]:
+               attention_precision: str, kv_dtype: str = "fp32", weight_dtype: str = "fp32") -> Dict[str, torch.Tensor]:
         """Everything `__init__` does; -> the checked fp32 CPU tensors by key (for what a subclass loads beyond `self.w`)."""
         self.precision = check_precision(precision)                # before the checkpoint is looked at or a device asked for
+        self.weight_dtype = check_weight_dtype(weight_dtype, self.precision)   # storage of the conv / GEMM operands (`DeviceModel`)
         self.attention_precision = ops.check_attention_precision(attention_precision, "attention_precision")
         self.kv_dtype = ops.check_kv_dtype(kv_dtype)               # the dtype of the returned kv_hists (`SpatialTransformer(kv_dtype=)`)
         self.layout = self._layout(cfg)
@@ -253,7 +256,7 @@ class UNetTrunk(DeviceModel):
                 # transformer with another head size keeps fp32 attention, and says so: a warning below, `attention_precision_of`
                 ap = self.attention_precision if int(l[4]) in FUSED_HEAD_SIZES else "fp32"
                 self.st[name] = SpatialTransformer(sub, l[3], l[4], device=self.device, precision=self.precision, attention_precision=ap,
-                                                   kv_dtype=self.kv_dtype)
+                                                   kv_dtype=self.kv_dtype, weight_dtype=self.weight_dtype)
             elif kind == "res":
                 emb_w.append(t32[f"{name}.emb_layers.1.weight"])
                 emb_b.append(t32[f"{name}.emb_layers.1.bias"])
@@ -269,7 +272,9 @@ class UNetTrunk(DeviceModel):
         for key, t in t32.items():
             if any(key.startswith(n + ".") for n in self.st) or ".emb_layers." in key:
                 continue
-            self._put(key, t)
+            # not `ofx_conv2d` operands, fp32 in every `weight_dtype`: Upsample (ofx_upconv2x, fp32 in every precision) and what
+            # a subclass names (ControlNet's hint stem)
+            self._put(key, t, operand=not (key.endswith(".conv.weight") or key.startswith(self._fp32_weight_prefixes)))
             if key.endswith(".conv.weight"):                                   # Upsample: the four parity-folded 2x2 operands
                 self.w[key + ".folded"] = ops.upconv2x_weight(t).to(self.device)
         # every ResBlock's emb_layers.1 as one [sum of Cout, 4 * model_channels] Linear
@@ -365,11 +370,14 @@ class UNetModel(UNetTrunk):
     configuration u0 has a 192-wide middle head) that transformer keeps fp32 attention: a UserWarning names it at construction and
     `attention_precision_of` maps every transformer to the mode it runs.  A SpatialTransformer built directly raises instead.
     `kv_dtype`: "fp32" (default) or "fp16", the dtype of the returned `kv_hists` (`SpatialTransformer(kv_dtype=)`); histories of
-    either dtype are accepted as `reference_kv`, and on the fused route they are attended to in place, unwidened."""
+    either dtype are accepted as `reference_kv`, and on the fused route they are attended to in place, unwidened.
+    `weight_dtype`: "fp32" (default) or "fp16", with precision="fp16" only (ValueError otherwise): every convolution and GEMM
+    operand is stored in half and read as such by the same fp16 kernels -- bit-identical outputs, half the weight bytes
+    (`modelbase.DeviceModel` lists what stays fp32)."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: dict = SD_V15_UNET, device="cuda", prefix: str = "model.diffusion_model.",
-                 precision: str = "fp32", attention_precision: str = "fp32", kv_dtype: str = "fp32"):
-        self._setup(state_dict, cfg, device, prefix, precision, attention_precision, kv_dtype)
+                 precision: str = "fp32", attention_precision: str = "fp32", kv_dtype: str = "fp32", weight_dtype: str = "fp32"):
+        self._setup(state_dict, cfg, device, prefix, precision, attention_precision, kv_dtype, weight_dtype)
 
     def _check_inputs(self, B, H, W, timesteps, context, control, reference_kv):
         """Every check that needs no launch; -> (per-transformer reference K/V, control as NHWC views or None)."""

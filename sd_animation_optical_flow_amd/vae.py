@@ -43,7 +43,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import ops
-from .modelbase import DeviceModel, env_flag, is_f32_cuda, load_tensors, pad_channels4, random_tensors, wb
+from .modelbase import DeviceModel, check_weight_dtype, env_flag, is_f32_cuda, load_tensors, pad_channels4, random_tensors, wb
 
 SCALE_FACTOR = 0.18215
 SD_V1_CONFIG = dict(ch=128, ch_mult=(1, 2, 4, 4), num_res_blocks=2, in_channels=3, z_channels=4, double_z=True, embed_dim=4)
@@ -143,9 +143,11 @@ class _VaeBlocks(DeviceModel):
     """What `Encoder` and `Decoder` share (model.py): weights on the device in the kernels' layouts (`modelbase.DeviceModel`), and
     the GroupNorm, ResnetBlock and AttnBlock calls."""
 
-    def __init__(self, state_dict: Dict[str, torch.Tensor], tensors, device, cfg: dict, scale_factor: float, precision: str):
+    def __init__(self, state_dict: Dict[str, torch.Tensor], tensors, device, cfg: dict, scale_factor: float, precision: str,
+                 weight_dtype: str = "fp32"):
         self.cfg, self.scale_factor = dict(cfg), float(scale_factor)
         self.precision = check_precision(precision)                # the arithmetic of every `_conv`; before the checkpoint or a device
+        self.weight_dtype = check_weight_dtype(weight_dtype, self.precision)   # storage of the convolution operands (`DeviceModel`)
         strip = len("first_stage_model.")                          # the prefix of full SD checkpoints, where a key has it
         sd = {k[strip:] if k.startswith("first_stage_model.") else k: v for k, v in state_dict.items()}
         t32 = load_tensors(sd, tensors, "", "VAE")                 # the checkpoint is checked before the device is asked for
@@ -176,11 +178,12 @@ class _VaeBlocks(DeviceModel):
 
 
 class VaeEncoder(_VaeBlocks):
-    """`AutoencoderKL.encode` + `get_first_stage_encoding` on a HIP device."""
+    """`AutoencoderKL.encode` + `get_first_stage_encoding` on a HIP device.  `weight_dtype`: "fp32" (default) or "fp16" (with
+    precision="fp16" only): the convolution operands stored in half, bit-identical results (`modelbase.DeviceModel`)."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", cfg: dict = SD_V1_CONFIG, scale_factor: float = SCALE_FACTOR,
-                 precision: str = "fp32"):
-        super().__init__(state_dict, encoder_tensors(cfg), device, cfg, scale_factor, precision)
+                 precision: str = "fp32", weight_dtype: str = "fp32"):
+        super().__init__(state_dict, encoder_tensors(cfg), device, cfg, scale_factor, precision, weight_dtype)
 
     def max_batch(self, H: int, W: int) -> int:
         """Images one pass of the encoder can take at this size: the convolution kernel addresses its operands with 32-bit byte
@@ -234,11 +237,13 @@ class VaeEncoder(_VaeBlocks):
 
 
 class VaeDecoder(_VaeBlocks):
-    """`AutoencoderKL.decode` / `decode_first_stage` / `decode_latent` on a HIP device."""
+    """`AutoencoderKL.decode` / `decode_first_stage` / `decode_latent` on a HIP device.  `weight_dtype`: "fp32" (default) or "fp16"
+    (with precision="fp16" only): the convolution operands and the folded `Upsample` operands stored in half, bit-identical
+    results (`modelbase.DeviceModel`)."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", cfg: dict = SD_V1_CONFIG, scale_factor: float = SCALE_FACTOR,
-                 precision: str = "fp32"):
-        super().__init__(state_dict, decoder_tensors(cfg), device, cfg, scale_factor, precision)
+                 precision: str = "fp32", weight_dtype: str = "fp32"):
+        super().__init__(state_dict, decoder_tensors(cfg), device, cfg, scale_factor, precision, weight_dtype)
         # Upsample layers that run fused (level -> bool); OFX_VAE_NO_UPCONV=1 turns every one to the unfused pair
         self.fused_upsample = {lvl: not _no_upconv() for lvl in range(1, len(self.cfg["ch_mult"]))}
 
@@ -250,7 +255,11 @@ class VaeDecoder(_VaeBlocks):
             t = torch.cat([t, t.new_zeros((4 - t.shape[0] % 4,))])
         super()._put(key, t)
         if key.endswith(".upsample.conv.weight"):
-            self.w[key + ".folded"] = ops.upconv2x_weight(t).to(self.device)   # [4 parities, Cout, 4 taps, Cin]
+            folded = ops.upconv2x_weight(t)                                    # [4 parities, Cout, 4 taps, Cin]
+            if self.weight_dtype == "fp16":                                    # `ops.upconv2x(precision="fp16")` reads halves as they are
+                folded = ops.half_conv_weight(folded)
+                self.half_keys.add(key + ".folded")
+            self.w[key + ".folded"] = folded.to(self.device)
 
     def _upsample(self, lvl: int, x: torch.Tensor) -> torch.Tensor:
         """Upsample.forward (:52-58): interpolate(scale_factor=2.0, mode="nearest") + 3x3 convolution."""
